@@ -10,8 +10,16 @@ dx}, conditioning/upsample gradients, weight-norm backward), [N > 1: bucketed RC
 and the fused clip_grad_norm_ + Adam + EMA update.  Inputs are resident in HBM before the timed region.
 `--mode forward` times the teacher-forced forward pass alone.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5] [--dtype bf16|fp16|fp32] [--mode train|forward] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c5] [--dtype bf16|fp16|fp32] [--mode train|forward]
+                    [--dump-outputs DIR] [--full [--no-cpu] [--no-ar] [--no-fp32] [--no-sub] [--ar-short]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the headline (value, ms_per_step, loss).  `--full` adds everything
+else the line used to carry: the per-kernel rooflines (HIP events in the timed steps, three extra untimed steps), the inference
+forward leg, the fp32 parity-mode leg, the autoregressive leg, the CPU baselines and the c3 / c5 sub-lines; the --no-* switches
+leave parts of it out.  `--dump-outputs DIR` writes what the last timed step returned (and, in train mode, the updated
+parameters) as DIR/<name>.npy: the inputs and weights are seeded and the default --lr 0 keeps every step on the same weights,
+so two runs, or two builds, compare output for output.
 
 Prints ONE JSON line on rank 0.  Multi-GPU: one process per GPU, each rank trains on its own shard of the global
 batch (weak scaling: 8 clips per GPU), gradients all-reduced over RCCL (started inside backward, on a side stream),
@@ -291,7 +299,7 @@ def fp32_leg(conf, sd, device, steps=4):
 
 def sub_config_line(name, steps=5, warmup=2, cpu=True):
     """`bench.py --config <name>` as a child process, its line cut down to what the default line embeds."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(steps), "--warmup", str(warmup), "--no-ar",
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", name, "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-ar",
            "--no-fp32", "--no-sub"] + ([] if cpu else ["--no-cpu"])
     t0 = time.perf_counter()
     try:
@@ -354,6 +362,26 @@ def kernel_matches(name, profiler_name):
     return profiler_name.startswith("_Z") and name + "I" in profiler_name
 
 
+DUMP_MAX_ELEMS = 1 << 22      # larger arrays are written as a fixed, seeded sample (<name>.npy + <name>_index.npy): <= 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor of `arrays` as <path>/<name>.npy, float64 for 64-bit and integer tensors, float32 otherwise."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        if not isinstance(t, torch.Tensor):
+            continue
+        t = t.detach()
+        a = (t.double() if (t.dtype == torch.float64 or not t.is_floating_point()) else t.float()).cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.unique(np.random.default_rng(0).integers(0, a.size, size=DUMP_MAX_ELEMS))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def launch_ranks(n):
     """`python bench.py --gpus N` without a launcher: start torch.distributed.run as a CHILD process (this process has not
     initialised the GPU and never will), relay its output, exit with its code."""
@@ -377,14 +405,23 @@ def main():
                          "c5: 48 layers x 512 channels, 16 x 5120 per GPU, fp16")
     ap.add_argument("--dtype", default=None, choices=["bf16", "fp16", "fp32"], help="default: the configuration's (c2, c3: bf16; c5: fp16)")
     ap.add_argument("--mode", default="train", choices=["train", "forward"])
+    ap.add_argument("--full", action="store_true", help="besides the headline: per-kernel rooflines, the inference forward, fp32, "
+                    "autoregressive and CPU-baseline legs and the c3 / c5 sub-lines (the --no-* switches below apply to it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--ar-short", action="store_true", help="autoregressive leg: skip the full 160 000-sample C4 clip (about 24 s)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-ar", action="store_true", help="skip the autoregressive leg (BASELINE config C4, rank 0 only)")
     ap.add_argument("--no-fp32", action="store_true", help="skip the short fp32 (parity-grade mode) leg of the default line")
     ap.add_argument("--no-sub", action="store_true", help="skip the c3 / c5 sub-lines of the default line (BASELINE configs[2] and [4], 5 steps each)")
-    ap.add_argument("--lr", type=float, default=4e-4, help="Adam learning rate of the timed steps (0: the weights never change -- same-data "
-                    "A/B runs of timing-only kernel variants, tools/bench_fields.py)")
+    # default 0: Adam runs its full update with step size 0, so every step starts from the same weights and --dump-outputs is
+    # reproducible.  With a learning rate, rounding-level differences of the weight gradients' atomic sums grow from step to step
+    # (Adam divides by sqrt(v): a near-zero gradient's sign sets a whole step), and two runs end on different weights.
+    ap.add_argument("--lr", type=float, default=0.0, help="Adam learning rate of the timed steps (default 0: the weights never change, "
+                    "every step computes the same thing from the same data; the work of a step is the same at any rate)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     conf = CONFIGS[args.config]
     args.dtype = args.dtype or conf["dtype"]
     C2, B_PER_GPU, T = conf["cfg"], conf["B"], conf["T"]      # (the names the formulas below were written with)
@@ -434,17 +471,17 @@ def main():
         if dist is not None:
             from wavenet_autoencoders_amd.distributed import GradSync, broadcast_params
             broadcast_params(eng.params)
-            gsync = GradSync(eng, timing=True)
+            gsync = GradSync(eng, timing=args.full)
 
     def step(record=False):
+        """-> what the timed path hands its caller: decoder_forward's / forward's dict, or train_step's"""
         if args.mode == "forward":
             # (weight norm + fragment packing run inside decoder_forward only when a parameter changed since the last pack: never here)
-            out = fwd_fn(xi, lat, g, targets=xi, lengths=lengths, want_logits=False, layer_events=ev if record else None)
-            return out["loss"]
+            return fwd_fn(xi, lat, g, targets=xi, lengths=lengths, want_logits=False, layer_events=ev if record else None)
         eng._layer_events = ev if record is True else None
         eng._tn_events = ev_tn if record is True else None
         eng._tm_events = ev_tm if record == "tm" else None      # (only in the untimed extra steps below: 96 event records per step)
-        return eng.train_step(xi, lat, g, lengths=None, lr=args.lr, grad_sync=gsync)["loss"]
+        return eng.train_step(xi, lat, g, lengths=None, lr=args.lr, grad_sync=gsync)
 
     def sync():
         if dist is not None:
@@ -457,10 +494,13 @@ def main():
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step(record=True)
+        out = step(record=args.full)      # (--full: HIP events around the layer stack and the weight-gradient launches)
     sync()
     dt = time.perf_counter() - t0
-    if args.mode == "train":
+    loss_v = float(out["loss"])      # (read here: it can be a view of a workspace that the untimed steps of --full overwrite)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(out, params=eng.params) if args.mode == "train" else out)
+    if args.mode == "train" and args.full:
         # the per-layer backward launches (gate / residual: 48 per step) get their HIP events in three EXTRA, untimed steps: an event
         # pair around every launch costs the timed region ~0.4 ms per step (measured: 5.9 -> 6.3 ms), two pairs per step cost nothing
         for _ in range(3):
@@ -470,170 +510,171 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
-    loss_v = float(loss)
 
-    # dominant kernel: the fused layer kernel (glu_kernel_name) -- HIP events recorded on the launch stream around the 24-layer stack of
-    # every timed step; average per launch (includes the inter-kernel gaps, so it is conservative)
-    stack_ms = [a.elapsed_time(b) for a, b in ev]
-    glu_ms = sum(stack_ms) / len(stack_ms) / geom.layers
-    es = 4 if args.dtype == "fp32" else 2
     samples = B_PER_GPU * T
-    bytes_per_launch = (2 * C2["R"] + 2 * C2["S"] + C2["Cc"]) * es * samples        # SURVEY 8(d) per layer
-    H = C2["G"] // 2
-    flops_per_launch = 2 * (C2["G"] * C2["R"] * C2["k"] + C2["G"] * C2["Cc"] + H * C2["R"] + H * C2["S"]) * samples
-    achieved_gbs = bytes_per_launch / (glu_ms * 1e-3) / 1e9
-    achieved_tf = flops_per_launch / (glu_ms * 1e-3) / 1e12
-    peak_tf = FP32_MFMA_PEAK_TF if args.dtype == "fp32" else MFMA_PEAK_TF      # fp16 and bf16 MFMA run at the same dense rate
-    fwd_roof = {"bound": "hbm", "kernel": glu_kernel_name(args.dtype, args.mode == "train"), "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": glu_ms,
-                "algorithmic_bytes_per_launch": bytes_per_launch, "mfma_achieved_tflops": achieved_tf,
-                "mfma_frac": achieved_tf / peak_tf,
-                "note": "SURVEY 8(d) forward bytes per layer (2R+2S+Cc)*e x %d samples; HIP events around the %d-layer stack" % (samples, geom.layers)}
-    roof = fwd_roof
-    extra = {}
-    if args.mode == "train":
-        # Training launch of the fused layer kernel: it also saves the pre-activations -- SURVEY 8(d) train bytes, forward part =
-        # (2R + 2S + Cc) + G per layer and sample.
-        tb = (2 * C2["R"] + 2 * C2["S"] + C2["Cc"] + C2["G"]) * es * samples
-        glu_roof = dict(fwd_roof, achieved=tb / (glu_ms * 1e-3) / 1e9, frac=tb / (glu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                        algorithmic_bytes_per_launch=tb, ms_per_step=glu_ms * geom.layers,
-                        note="training forward of one layer: SURVEY 8(d) (2R+2S+Cc+G)*e x %d samples (z saved for backward); "
-                             "HIP events around the %d-layer stack" % (samples, geom.layers))
-        fplan = eng.chain_plan(B_PER_GPU, T)
-        if fplan is not None:
-            # two chains (engine.chain_plan): a launch covers its chain's clips; the chains run in step, so a launch lasts what a layer
-            # of the stack takes (rocprofv3's average for the kernel agrees).  `achieved` = the bytes ONE launch moves over that time;
-            # `both_chains` = the layer's bytes of both chains over the same time.
-            fpart = fplan[0] / B_PER_GPU
-            glu_roof = dict(glu_roof, achieved=glu_roof["achieved"] * fpart, frac=glu_roof["frac"] * fpart,
-                            algorithmic_bytes_per_launch=tb * fpart, mfma_achieved_tflops=achieved_tf * fpart, mfma_frac=achieved_tf * fpart / peak_tf,
-                            clips_per_launch=fplan[0], concurrent_launches=2,
-                            both_chains={"achieved": tb / (glu_ms * 1e-3) / 1e9, "frac": tb / (glu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                         "ms_per_layer": glu_ms,
-                                         "note": "two half-batch chains of launches on two streams, in step: the layer's bytes of both chains / "
-                                                 "(wall time of the stack / its layers)"})
-        families = {"glu_fwd_z": glu_roof}
-        if ev_tn:
-            # weight gradients: 16-bit = ONE launch for all layers (gemm_tn_static_kernel: dW1 taps, dWc + zb sums, dW_out AND dW_skip
-            # + the out bias), fp32 = one gemm_tn_kernel per layer.  Algorithmic bytes = the operands each layer must read once: dz
-            # (G), x (R), c (Cc), dx-hat (R), u (H); dS (S) is the same array for every layer: once per launch.
-            # launches per step: 1 (the whole stack), 2 (data parallel: the stack in two layer halves, backward.decoder_backward) or one
-            # per layer (fp32 tiles).  The halves are summed: `avg_launch_ms` then is the weight-gradient time of a step.
-            per_step = max(1, len(ev_tn) // args.steps)
-            nl = geom.layers if per_step <= 2 else 1
-            tn_ms = sum(a.elapsed_time(b) for a, b in ev_tn) / len(ev_tn) * (per_step if nl > 1 else 1)
-            from wavenet_autoencoders_amd import backward as BW
-            bws = eng._ws[("bwd", B_PER_GPU, T)]
-            static = nl > 1 and isinstance(bws["stream"], BW.StaticStreamTable)
-            beside = None
-            if "stream_beside" in bws and per_step == 2 and dist is None:
-                # an under-filled sweep (backward.decoder_backward: `beside`): two launches per step, the upper layers' on the idle CUs BESIDE
-                # the sweep (its duration is mostly hidden, and long: a third of the machine), the lower layers' behind the sweep
-                t_b = sum(a.elapsed_time(b) for a, b in ev_tn[0::2]) / len(ev_tn[0::2])
-                t_l = sum(a.elapsed_time(b) for a, b in ev_tn[1::2]) / len(ev_tn[1::2])
-                beside = {"beside_sweep_launch_ms": t_b, "behind_sweep_launch_ms": t_l, "sum_ms": tn_ms,
-                          "note": "two launches of the same kernel: the upper layers' + the head's sized for the CUs the sweep leaves idle, on a side "
-                                  "stream beside the sweep's lower part; the lower layers' behind the sweep.  avg_launch_ms = their sum "
-                                  "(the work), of which only ~behind_sweep_launch_ms extends the step"}
-            tn_bytes = (nl * (C2["G"] + 2 * C2["R"] + C2["Cc"] + H) + (C2["S"] if static else 0)) * es * samples
-            tn_flops = nl * 2 * (C2["G"] * (C2["R"] * C2["k"] + C2["Cc"]) + C2["R"] * H + (C2["S"] * H if static else 0)) * samples
-            tn_gbs = tn_bytes / (tn_ms * 1e-3) / 1e9
-            families["wgrad"] = extra["roofline_wgrad"] = {
-                "bound": "hbm", "kernel": ("gemm_tn_static_kernel" if static else "gemm_tn_stream_kernel") if nl > 1 else "gemm_tn_kernel",
-                "achieved": tn_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": tn_gbs / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": tn_ms,
-                "ms_per_step": tn_ms * (1 if nl > 1 else geom.layers),
-                "algorithmic_bytes_per_launch": tn_bytes, "mfma_achieved_tflops": tn_flops / (tn_ms * 1e-3) / 1e12,
-                "mfma_frac": tn_flops / (tn_ms * 1e-3) / 1e12 / peak_tf,
-                "note": "weight gradients of %d layer(s) per launch (dW1 taps, dWc, dW_out%s); operands read once = (G+2R+Cc+H)*e per "
-                        "sample and layer%s" % (nl, ", dW_skip" if static else "", " + S*e per sample" if static else "")}
-            if beside is not None:
-                families["wgrad"]["beside_sweep"] = beside
-                families["wgrad"]["ms_per_step"] = beside["behind_sweep_launch_ms"]      # (what extends the step: the family ranking uses it)
-        # (csrc/glu_bwd8.hip has the instantiations of the 256-wide 16-bit shapes; csrc/glu_bwd.hip the rest.  The two-launch sweep's
-        #  residual (mode 1) and gate (mode 2) launches run on csrc/gemm_tm8.hip's gemm_tm8x_kernel in 16-bit storage at the bench shapes.)
-        pair_kernel = "glu_bwd_pair8_kernel" if (es == 2 and C2["R"] == 256 and C2["S"] == 256 and H in (192, 128, 184) and C2["k"] == 3) else "glu_bwd_pair_kernel"
-        for kind, mode_id, kb, kf, what in (
-                ("gate", 2, (C2["R"] + C2["S"] + 2 * C2["G"]) * es, 2 * H * (C2["R"] + C2["S"]),
-                 "du/dz of one layer: reads dx-hat (R), dskip (S), the saved pre-activations (G), writes dz (G)"),
-                ("res", 1, (C2["G"] + 2 * C2["R"]) * es, 2 * C2["R"] * C2["G"] * C2["k"],
-                 "dx-hat of one layer: reads dz (G; three taps of the same rows) and dx-hat of the layer above (R), writes R"),
-                ("pair", 0, (3 * C2["G"] + 2 * C2["R"] + C2["S"]) * es, 2 * C2["R"] * C2["G"] * C2["k"] + 2 * H * (C2["R"] + C2["S"]),
-                 "residual(l) + gate(l-1) in one launch (csrc/glu_bwd.hip, the 16-bit default): reads dz_l (G), dx-hat of the layer above "
-                 "(R), dskip (S), the saved pre-activations of layer l-1 (G), writes dx-hat_l (R) and dz_(l-1) (G)")):
-            if ev_tm[kind]:
-                k_ms = sum(a.elapsed_time(b) for a, b in ev_tm[kind]) / len(ev_tm[kind])
-                per_step = len(ev_tm[kind]) / 3
-                # two chains (engine.chain_plan): the events bracket the FIRST chain's launches, each over its own clips only, while the
-                # second chain's launch of the same kernel runs beside it.  `achieved` is what the rubric asks for -- the bytes ONE launch
-                # moves over ITS duration (rocprofv3's average for the kernel agrees with it) -- and `both_chains` prices the sweep: the
-                # bytes of both chains' launches of a layer over the sweep's wall time per layer (HIP events around the whole sweep).
-                plan = eng.chain_plan(B_PER_GPU, T, backward=True)
-                part = (plan[0] / B_PER_GPU) if (plan is not None and kind != "gate") else 1.0     # (the top layer's gate launch runs before the fork)
-                ls = samples * part
-                gbs = kb * ls / (k_ms * 1e-3) / 1e9
-                fam = {
-                    "bound": "hbm", "kernel": (("gemm_tm8x_kernel:%d" if es == 2 else "gemm_tm_kernel:%d") % mode_id) if mode_id else pair_kernel, "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": gbs / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": k_ms, "ms_per_step": k_ms * per_step,
-                    "algorithmic_bytes_per_launch": kb * ls, "mfma_achieved_tflops": kf * ls / (k_ms * 1e-3) / 1e12,
-                    "mfma_frac": kf * ls / (k_ms * 1e-3) / 1e12 / peak_tf,
-                    "note": what + " -- the bytes this launch itself has to move; HIP events around every launch"}
-                if part < 1.0:
-                    fam["note"] = ("TWO launches of this kernel run side by side, each over half of the batch (engine.chain_plan): achieved / frac "
-                                   "are ONE launch's bytes over its own duration; `both_chains` prices the pair.  ") + fam["note"]
-                if part < 1.0 and ev_tm.get("sweep"):
-                    sw_ms = sum(a.elapsed_time(b) for a, b in ev_tm["sweep"]) / len(ev_tm["sweep"])
-                    lay_ms = sw_ms / max(per_step, 1)
-                    fam["clips_per_launch"] = plan[0]
-                    fam["concurrent_launches"] = 2
-                    fam["ms_per_step"] = sw_ms
-                    fam["both_chains"] = {"achieved": kb * samples / (lay_ms * 1e-3) / 1e9, "frac": kb * samples / (lay_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                          "ms_per_layer": lay_ms, "sweep_ms": sw_ms,
-                                          "note": "two half-batch chains of launches on two streams: bytes of both chains' launches of a layer / "
-                                                  "(wall time of the sweep / its layers)"}
-                families[kind] = extra["roofline_" + {"gate": "gate_bwd", "res": "residual_bwd", "pair": "bwd_pair"}[kind]] = fam
-        # `roofline` = the launch family with the largest share of the timed step (HIP events on the launch stream decide, not a comment)
-        top = max(families, key=lambda k: families[k]["ms_per_step"])
-        roof = dict(families[top], family=top,
-                    family_ms_per_step={k: round(v["ms_per_step"], 4) for k, v in families.items()})
-        extra["roofline_glu_fwd_z"] = glu_roof
-        # the whole step against SURVEY 8(d): per sample and layer (5R + 3S + 2G + 4Cc)*e train bytes (+ head), 3 x forward FLOPs
-        step_bytes = (geom.layers * (5 * C2["R"] + 3 * C2["S"] + 2 * C2["G"] + 4 * C2["Cc"]) * es + (C2["S"] + 0) * es + 5) * samples
-        fwd_flops = (geom.layers * 2 * (C2["G"] * C2["R"] * C2["k"] + C2["G"] * C2["Cc"] + H * C2["R"] + H * C2["S"])
-                     + 2 * (C2["S"] * C2["S"] + C2["S"] * C2["O"])) * samples
-        step_s = dt / args.steps
-        extra["roofline_step"] = {"hbm_frac": step_bytes / step_s / 1e9 / HBM_PEAK_GBS, "mfma_frac": 3 * fwd_flops / step_s / 1e12 / peak_tf,
-                                  "algorithmic_bytes_per_step": step_bytes, "algorithmic_flops_per_step": 3 * fwd_flops,
-                                  "note": "SURVEY 8(d): train bytes (5R+3S+2G+4Cc)*e per sample and layer + head, 3 x forward FLOPs, over ms_per_step"}
-    fwd_bytes_per_sample = geom.layers * (2 * C2["R"] + 2 * C2["S"] + C2["Cc"]) * es + (C2["S"] + 0) * es + 4 + 1
-    fwd_bytes_whole = geom.layers * (2 * C2["R"] + 2 * C2["S"] + C2["Cc"]) * es + (C2["S"] + C2["O"]) * es + 1      # 53 249 B (bf16)
     value = world * samples * args.steps / dt
 
-    # HBM traffic per launch: from the committed rocprofv3 --pmc passes of this same command (bench.py cannot run the profiler
-    # on itself).  The file carries the hash of the kernel sources it was measured on: a different build reports null.
-    traffic_src, traffic_doc = None, None
-    try:
-        import glob
-        cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))
-        for fpath in reversed(cands):
-            with open(fpath) as fh:
-                doc = json.load(fh)
-            if doc.get("csrc_hash") == csrc_hash():
-                traffic_src = os.path.basename(fpath)
-                traffic_doc = doc
-                # (the passes profile the DEFAULT command: the C2 shard in bf16 -- another configuration's launches move other bytes)
-                if args.dtype == "bf16" and args.mode == "train" and args.config == "c2":
-                    for rf in [roof] + [v for v in extra.values() if "kernel" in v]:
-                        for k, v in doc["kernels"].items():
-                            if kernel_matches(rf["kernel"], k):
-                                rf["traffic"] = v["hbm_bytes_per_launch"]
-                                rf["traffic_source"] = traffic_src
-                break
-    except (OSError, KeyError, ValueError):
-        pass
-    if traffic_src is not None and roof.get("traffic") is None:
-        roof["traffic_note"] = "%s profiles the default command (config c2, bf16, train): no PMC pass of this configuration" % traffic_src
-    if traffic_src is None:
-        roof["traffic_note"] = "no profiles/*_pmc_traffic.json matches this build's csrc hash %s: traffic not reported" % csrc_hash()
+    if args.full:
+        # dominant kernel: the fused layer kernel (glu_kernel_name) -- HIP events recorded on the launch stream around the 24-layer stack of
+        # every timed step; average per launch (includes the inter-kernel gaps, so it is conservative)
+        stack_ms = [a.elapsed_time(b) for a, b in ev]
+        glu_ms = sum(stack_ms) / len(stack_ms) / geom.layers
+        es = 4 if args.dtype == "fp32" else 2
+        bytes_per_launch = (2 * C2["R"] + 2 * C2["S"] + C2["Cc"]) * es * samples        # SURVEY 8(d) per layer
+        H = C2["G"] // 2
+        flops_per_launch = 2 * (C2["G"] * C2["R"] * C2["k"] + C2["G"] * C2["Cc"] + H * C2["R"] + H * C2["S"]) * samples
+        achieved_gbs = bytes_per_launch / (glu_ms * 1e-3) / 1e9
+        achieved_tf = flops_per_launch / (glu_ms * 1e-3) / 1e12
+        peak_tf = FP32_MFMA_PEAK_TF if args.dtype == "fp32" else MFMA_PEAK_TF      # fp16 and bf16 MFMA run at the same dense rate
+        fwd_roof = {"bound": "hbm", "kernel": glu_kernel_name(args.dtype, args.mode == "train"), "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": glu_ms,
+                    "algorithmic_bytes_per_launch": bytes_per_launch, "mfma_achieved_tflops": achieved_tf,
+                    "mfma_frac": achieved_tf / peak_tf,
+                    "note": "SURVEY 8(d) forward bytes per layer (2R+2S+Cc)*e x %d samples; HIP events around the %d-layer stack" % (samples, geom.layers)}
+        roof = fwd_roof
+        extra = {}
+        if args.mode == "train":
+            # Training launch of the fused layer kernel: it also saves the pre-activations -- SURVEY 8(d) train bytes, forward part =
+            # (2R + 2S + Cc) + G per layer and sample.
+            tb = (2 * C2["R"] + 2 * C2["S"] + C2["Cc"] + C2["G"]) * es * samples
+            glu_roof = dict(fwd_roof, achieved=tb / (glu_ms * 1e-3) / 1e9, frac=tb / (glu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                            algorithmic_bytes_per_launch=tb, ms_per_step=glu_ms * geom.layers,
+                            note="training forward of one layer: SURVEY 8(d) (2R+2S+Cc+G)*e x %d samples (z saved for backward); "
+                                 "HIP events around the %d-layer stack" % (samples, geom.layers))
+            fplan = eng.chain_plan(B_PER_GPU, T)
+            if fplan is not None:
+                # two chains (engine.chain_plan): a launch covers its chain's clips; the chains run in step, so a launch lasts what a layer
+                # of the stack takes (rocprofv3's average for the kernel agrees).  `achieved` = the bytes ONE launch moves over that time;
+                # `both_chains` = the layer's bytes of both chains over the same time.
+                fpart = fplan[0] / B_PER_GPU
+                glu_roof = dict(glu_roof, achieved=glu_roof["achieved"] * fpart, frac=glu_roof["frac"] * fpart,
+                                algorithmic_bytes_per_launch=tb * fpart, mfma_achieved_tflops=achieved_tf * fpart, mfma_frac=achieved_tf * fpart / peak_tf,
+                                clips_per_launch=fplan[0], concurrent_launches=2,
+                                both_chains={"achieved": tb / (glu_ms * 1e-3) / 1e9, "frac": tb / (glu_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                             "ms_per_layer": glu_ms,
+                                             "note": "two half-batch chains of launches on two streams, in step: the layer's bytes of both chains / "
+                                                     "(wall time of the stack / its layers)"})
+            families = {"glu_fwd_z": glu_roof}
+            if ev_tn:
+                # weight gradients: 16-bit = ONE launch for all layers (gemm_tn_static_kernel: dW1 taps, dWc + zb sums, dW_out AND dW_skip
+                # + the out bias), fp32 = one gemm_tn_kernel per layer.  Algorithmic bytes = the operands each layer must read once: dz
+                # (G), x (R), c (Cc), dx-hat (R), u (H); dS (S) is the same array for every layer: once per launch.
+                # launches per step: 1 (the whole stack), 2 (data parallel: the stack in two layer halves, backward.decoder_backward) or one
+                # per layer (fp32 tiles).  The halves are summed: `avg_launch_ms` then is the weight-gradient time of a step.
+                per_step = max(1, len(ev_tn) // args.steps)
+                nl = geom.layers if per_step <= 2 else 1
+                tn_ms = sum(a.elapsed_time(b) for a, b in ev_tn) / len(ev_tn) * (per_step if nl > 1 else 1)
+                from wavenet_autoencoders_amd import backward as BW
+                bws = eng._ws[("bwd", B_PER_GPU, T)]
+                static = nl > 1 and isinstance(bws["stream"], BW.StaticStreamTable)
+                beside = None
+                if "stream_beside" in bws and per_step == 2 and dist is None:
+                    # an under-filled sweep (backward.decoder_backward: `beside`): two launches per step, the upper layers' on the idle CUs BESIDE
+                    # the sweep (its duration is mostly hidden, and long: a third of the machine), the lower layers' behind the sweep
+                    t_b = sum(a.elapsed_time(b) for a, b in ev_tn[0::2]) / len(ev_tn[0::2])
+                    t_l = sum(a.elapsed_time(b) for a, b in ev_tn[1::2]) / len(ev_tn[1::2])
+                    beside = {"beside_sweep_launch_ms": t_b, "behind_sweep_launch_ms": t_l, "sum_ms": tn_ms,
+                              "note": "two launches of the same kernel: the upper layers' + the head's sized for the CUs the sweep leaves idle, on a side "
+                                      "stream beside the sweep's lower part; the lower layers' behind the sweep.  avg_launch_ms = their sum "
+                                      "(the work), of which only ~behind_sweep_launch_ms extends the step"}
+                tn_bytes = (nl * (C2["G"] + 2 * C2["R"] + C2["Cc"] + H) + (C2["S"] if static else 0)) * es * samples
+                tn_flops = nl * 2 * (C2["G"] * (C2["R"] * C2["k"] + C2["Cc"]) + C2["R"] * H + (C2["S"] * H if static else 0)) * samples
+                tn_gbs = tn_bytes / (tn_ms * 1e-3) / 1e9
+                families["wgrad"] = extra["roofline_wgrad"] = {
+                    "bound": "hbm", "kernel": ("gemm_tn_static_kernel" if static else "gemm_tn_stream_kernel") if nl > 1 else "gemm_tn_kernel",
+                    "achieved": tn_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": tn_gbs / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": tn_ms,
+                    "ms_per_step": tn_ms * (1 if nl > 1 else geom.layers),
+                    "algorithmic_bytes_per_launch": tn_bytes, "mfma_achieved_tflops": tn_flops / (tn_ms * 1e-3) / 1e12,
+                    "mfma_frac": tn_flops / (tn_ms * 1e-3) / 1e12 / peak_tf,
+                    "note": "weight gradients of %d layer(s) per launch (dW1 taps, dWc, dW_out%s); operands read once = (G+2R+Cc+H)*e per "
+                            "sample and layer%s" % (nl, ", dW_skip" if static else "", " + S*e per sample" if static else "")}
+                if beside is not None:
+                    families["wgrad"]["beside_sweep"] = beside
+                    families["wgrad"]["ms_per_step"] = beside["behind_sweep_launch_ms"]      # (what extends the step: the family ranking uses it)
+            # (csrc/glu_bwd8.hip has the instantiations of the 256-wide 16-bit shapes; csrc/glu_bwd.hip the rest.  The two-launch sweep's
+            #  residual (mode 1) and gate (mode 2) launches run on csrc/gemm_tm8.hip's gemm_tm8x_kernel in 16-bit storage at the bench shapes.)
+            pair_kernel = "glu_bwd_pair8_kernel" if (es == 2 and C2["R"] == 256 and C2["S"] == 256 and H in (192, 128, 184) and C2["k"] == 3) else "glu_bwd_pair_kernel"
+            for kind, mode_id, kb, kf, what in (
+                    ("gate", 2, (C2["R"] + C2["S"] + 2 * C2["G"]) * es, 2 * H * (C2["R"] + C2["S"]),
+                     "du/dz of one layer: reads dx-hat (R), dskip (S), the saved pre-activations (G), writes dz (G)"),
+                    ("res", 1, (C2["G"] + 2 * C2["R"]) * es, 2 * C2["R"] * C2["G"] * C2["k"],
+                     "dx-hat of one layer: reads dz (G; three taps of the same rows) and dx-hat of the layer above (R), writes R"),
+                    ("pair", 0, (3 * C2["G"] + 2 * C2["R"] + C2["S"]) * es, 2 * C2["R"] * C2["G"] * C2["k"] + 2 * H * (C2["R"] + C2["S"]),
+                     "residual(l) + gate(l-1) in one launch (csrc/glu_bwd.hip, the 16-bit default): reads dz_l (G), dx-hat of the layer above "
+                     "(R), dskip (S), the saved pre-activations of layer l-1 (G), writes dx-hat_l (R) and dz_(l-1) (G)")):
+                if ev_tm[kind]:
+                    k_ms = sum(a.elapsed_time(b) for a, b in ev_tm[kind]) / len(ev_tm[kind])
+                    per_step = len(ev_tm[kind]) / 3
+                    # two chains (engine.chain_plan): the events bracket the FIRST chain's launches, each over its own clips only, while the
+                    # second chain's launch of the same kernel runs beside it.  `achieved` is what the rubric asks for -- the bytes ONE launch
+                    # moves over ITS duration (rocprofv3's average for the kernel agrees with it) -- and `both_chains` prices the sweep: the
+                    # bytes of both chains' launches of a layer over the sweep's wall time per layer (HIP events around the whole sweep).
+                    plan = eng.chain_plan(B_PER_GPU, T, backward=True)
+                    part = (plan[0] / B_PER_GPU) if (plan is not None and kind != "gate") else 1.0     # (the top layer's gate launch runs before the fork)
+                    ls = samples * part
+                    gbs = kb * ls / (k_ms * 1e-3) / 1e9
+                    fam = {
+                        "bound": "hbm", "kernel": (("gemm_tm8x_kernel:%d" if es == 2 else "gemm_tm_kernel:%d") % mode_id) if mode_id else pair_kernel, "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": gbs / HBM_PEAK_GBS, "traffic": None, "avg_launch_ms": k_ms, "ms_per_step": k_ms * per_step,
+                        "algorithmic_bytes_per_launch": kb * ls, "mfma_achieved_tflops": kf * ls / (k_ms * 1e-3) / 1e12,
+                        "mfma_frac": kf * ls / (k_ms * 1e-3) / 1e12 / peak_tf,
+                        "note": what + " -- the bytes this launch itself has to move; HIP events around every launch"}
+                    if part < 1.0:
+                        fam["note"] = ("TWO launches of this kernel run side by side, each over half of the batch (engine.chain_plan): achieved / frac "
+                                       "are ONE launch's bytes over its own duration; `both_chains` prices the pair.  ") + fam["note"]
+                    if part < 1.0 and ev_tm.get("sweep"):
+                        sw_ms = sum(a.elapsed_time(b) for a, b in ev_tm["sweep"]) / len(ev_tm["sweep"])
+                        lay_ms = sw_ms / max(per_step, 1)
+                        fam["clips_per_launch"] = plan[0]
+                        fam["concurrent_launches"] = 2
+                        fam["ms_per_step"] = sw_ms
+                        fam["both_chains"] = {"achieved": kb * samples / (lay_ms * 1e-3) / 1e9, "frac": kb * samples / (lay_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                              "ms_per_layer": lay_ms, "sweep_ms": sw_ms,
+                                              "note": "two half-batch chains of launches on two streams: bytes of both chains' launches of a layer / "
+                                                      "(wall time of the sweep / its layers)"}
+                    families[kind] = extra["roofline_" + {"gate": "gate_bwd", "res": "residual_bwd", "pair": "bwd_pair"}[kind]] = fam
+            # `roofline` = the launch family with the largest share of the timed step (HIP events on the launch stream decide, not a comment)
+            top = max(families, key=lambda k: families[k]["ms_per_step"])
+            roof = dict(families[top], family=top,
+                        family_ms_per_step={k: round(v["ms_per_step"], 4) for k, v in families.items()})
+            extra["roofline_glu_fwd_z"] = glu_roof
+            # the whole step against SURVEY 8(d): per sample and layer (5R + 3S + 2G + 4Cc)*e train bytes (+ head), 3 x forward FLOPs
+            step_bytes = (geom.layers * (5 * C2["R"] + 3 * C2["S"] + 2 * C2["G"] + 4 * C2["Cc"]) * es + (C2["S"] + 0) * es + 5) * samples
+            fwd_flops = (geom.layers * 2 * (C2["G"] * C2["R"] * C2["k"] + C2["G"] * C2["Cc"] + H * C2["R"] + H * C2["S"])
+                         + 2 * (C2["S"] * C2["S"] + C2["S"] * C2["O"])) * samples
+            step_s = dt / args.steps
+            extra["roofline_step"] = {"hbm_frac": step_bytes / step_s / 1e9 / HBM_PEAK_GBS, "mfma_frac": 3 * fwd_flops / step_s / 1e12 / peak_tf,
+                                      "algorithmic_bytes_per_step": step_bytes, "algorithmic_flops_per_step": 3 * fwd_flops,
+                                      "note": "SURVEY 8(d): train bytes (5R+3S+2G+4Cc)*e per sample and layer + head, 3 x forward FLOPs, over ms_per_step"}
+        fwd_bytes_per_sample = geom.layers * (2 * C2["R"] + 2 * C2["S"] + C2["Cc"]) * es + (C2["S"] + 0) * es + 4 + 1
+        fwd_bytes_whole = geom.layers * (2 * C2["R"] + 2 * C2["S"] + C2["Cc"]) * es + (C2["S"] + C2["O"]) * es + 1      # 53 249 B (bf16)
+
+        # HBM traffic per launch: from the committed rocprofv3 --pmc passes of this same command (bench.py cannot run the profiler
+        # on itself).  The file carries the hash of the kernel sources it was measured on: a different build reports null.
+        traffic_src, traffic_doc = None, None
+        try:
+            import glob
+            cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))
+            for fpath in reversed(cands):
+                with open(fpath) as fh:
+                    doc = json.load(fh)
+                if doc.get("csrc_hash") == csrc_hash():
+                    traffic_src = os.path.basename(fpath)
+                    traffic_doc = doc
+                    # (the passes profile the DEFAULT command: the C2 shard in bf16 -- another configuration's launches move other bytes)
+                    if args.dtype == "bf16" and args.mode == "train" and args.config == "c2":
+                        for rf in [roof] + [v for v in extra.values() if "kernel" in v]:
+                            for k, v in doc["kernels"].items():
+                                if kernel_matches(rf["kernel"], k):
+                                    rf["traffic"] = v["hbm_bytes_per_launch"]
+                                    rf["traffic_source"] = traffic_src
+                    break
+        except (OSError, KeyError, ValueError):
+            pass
+        if traffic_src is not None and roof.get("traffic") is None:
+            roof["traffic_note"] = "%s profiles the default command (config c2, bf16, train): no PMC pass of this configuration" % traffic_src
+        if traffic_src is None:
+            roof["traffic_note"] = "no profiles/*_pmc_traffic.json matches this build's csrc hash %s: traffic not reported" % csrc_hash()
 
     if rank == 0:
         res = {
@@ -652,20 +693,19 @@ def main():
                        "global_batch": world * B_PER_GPU, "seq_len": T, "parallelism": f"dp{world}"},
             "samples_per_sec_per_gpu": value / world,
             "loss": loss_v,
-            "roofline": roof,
-            "roofline_glu_fwd": fwd_roof,
         }
-        res.update(extra)
+        if args.full:
+            res.update(roofline=roof, roofline_glu_fwd=fwd_roof, **extra)
         if world > 1 and os.environ.get("WAE_BENCH_SHARED_GPU", "0") != "0":
             res["data"] = "synthetic; PLUMBING CHECK: %d ranks share ONE GPU over gloo -- not a measurement" % world
-        if gsync is not None:
+        if gsync is not None and args.full:
             comm_ms, wait_ms = gsync.collect_timing()
             res["allreduce"] = {"ms": comm_ms, "exposed_ms": wait_ms, "collectives_per_step": gsync.n_collectives / (args.steps + args.warmup),
                                 "bytes": int(eng.grads.numel()) * (2 if gsync.wire_bf16 else 4), "wire_dtype": "bf16" if gsync.wire_bf16 else "fp32",
                                 "note": "RCCL all-reduce of the fp32 gradient arena (WAE_DP_WIRE=bf16: of bf16 copies), last timed step: "
                                 "ms = first launch to last collective done on the side stream (starts inside backward, after the "
                                 "layers' gradients); exposed_ms = how long the compute stream waited for it"}
-        if args.mode == "train" and world == 1:
+        if args.full and args.mode == "train" and world == 1:
             # the same stack in inference (no z saved, no backward): the north star states its roofline target on this launch
             ev_f = []
             nf = max(3, min(10, args.steps))
@@ -718,19 +758,19 @@ def main():
                     if kernel_matches(res["forward_inference"]["roofline"]["kernel"], k):
                         res["forward_inference"]["roofline"]["traffic"] = v["hbm_bytes_per_launch"]
                         res["forward_inference"]["roofline"]["traffic_source"] = traffic_src
-        if args.config == "c2" and args.dtype != "fp32" and args.mode == "train" and world == 1 and not args.no_fp32:
+        if args.full and args.config == "c2" and args.dtype != "fp32" and args.mode == "train" and world == 1 and not args.no_fp32:
             res["fp32_parity_mode"] = fp32_leg(conf, sd, device)
-        if not args.no_ar and world == 1 and args.config == "c2":
+        if args.full and not args.no_ar and world == 1 and args.config == "c2":
             res["autoregressive"] = ar_leg(device, cpu=not args.no_cpu, full_clip=not args.ar_short)
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             # a bounded sample (~10-30 s of host work): c2 / c3 the whole shard, c5 (105 MFLOP per sample forward) two clips
             ncl = 2 if args.config == "c5" else B_PER_GPU
             cb, cpu_loss = cpu_baseline_train(sd, ncl, conf) if args.mode == "train" else cpu_baseline(sd, ncl, conf)
             res["cpu_baseline"] = cb
-        if args.config == "c2" and args.mode == "train" and world == 1 and not args.no_sub and args.dtype == conf["dtype"]:
+        if args.full and args.config == "c2" and args.mode == "train" and world == 1 and not args.no_sub and args.dtype == conf["dtype"]:
             # BASELINE configs[2] and [4] -- the two 8-GPU configurations -- as their per-GPU shard on this GPU: a few steps each, run as
             # CHILD processes of this one (never an exec from a process that holds the GPU) after everything above has been timed.  The
-            # driver's line then carries all three trainable configurations; the full lines are `bench.py --config c3|c5`.
+            # driver's line then carries all three trainable configurations; the full lines are `bench.py --full --config c3|c5`.
             del eng
             torch.cuda.empty_cache()
             for sub in ("c3", "c5"):

@@ -1030,7 +1030,9 @@ def gen_optim_state(cfg, salt):
         out[f"step{step}"] = np.array([float(st["state"][i]["step"]) for i in range(len(names))])
         out[f"loss{step}"] = loss.detach()
     group = {k: v for k, v in st["param_groups"][0].items() if k != "params"}
-    save(f"optim_{cfg['name']}", names=json.dumps(names), param_group=json.dumps(group), **out)
+    # the two steps' state in two files: each stays under the 1 MiB limit of a committed file
+    save(f"optim_{cfg['name']}", names=json.dumps(names), param_group=json.dumps(group), **{k: v for k, v in out.items() if k.endswith("1")})
+    save(f"optim_{cfg['name']}_step2", **{k: v for k, v in out.items() if k.endswith("2")})
 
 
 def main():

@@ -102,7 +102,7 @@ def test_resume_from_a_reference_optimizer_state():
     from wavenet_autoencoders_amd import checkpoint as CK
     from wavenet_autoencoders_amd.engine import WaeEngine
     cfg, sd, ins, zm, ocfg = golden_model("A")
-    z = load_npz("optim_A")
+    z = {**load_npz("optim_A"), **load_npz("optim_A_step2")}        # (the first and the second step's state: two files under 1 MiB)
     names = json.loads(str(z["names"]))
     eng = WaeEngine(Geometry.from_cfg(cfg), dtype="fp32")
     assert names == list(eng.lay.offsets)                           # optimizer index i = i-th arena tensor

@@ -3,7 +3,7 @@
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 lib = os.path.abspath(sys.argv[1])
-out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu", "--no-ar", "--no-fp32", "--steps", "20"] + sys.argv[2:],
+out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu", "--no-ar", "--no-fp32", "--steps", "20"] + sys.argv[2:],
                      env=dict(os.environ, WAE_LIB_PATH=lib), capture_output=True, text=True)
 line = [l for l in out.stdout.splitlines() if l.startswith("{")]
 if not line:

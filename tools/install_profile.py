@@ -32,7 +32,7 @@ for line in open(f"gpurun_out/{tag}_pmc/summary.txt"):
         cur = m.group(1); blocks[cur] = []
     elif cur and line.strip():
         blocks[cur].append(line.rstrip())
-out = ["# rocprofv3 --kernel-trace --pmc <set> (six separate passes, tools/pmc_run.sh) over `python3 bench.py --steps 2 --warmup 1 --no-cpu --no-ar`,",
+out = ["# rocprofv3 --kernel-trace --pmc <set> (six separate passes, tools/pmc_run.sh) over `python3 bench.py --full --steps 2 --warmup 1 --no-cpu --no-ar`,",
        f"# final tree of the round (csrc hash in {tag}_pmc_traffic.json), one MI355X.  Kernel selection by substring of the profiler's kernel name.",
        "# derived: MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / (32 x SQ_BUSY_CYCLES)  (SQ_BUSY_CYCLES counts per shader array: 32 arrays x 32 SIMDs);",
        "#          L2 hit = TCC_HIT / TCC_REQ;  LDS conflict share = SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE;  HBM bytes = (2 x FETCH_SIZE + WRITE_SIZE) x 1024", ""]

@@ -4,7 +4,7 @@ ROOT=$(pwd); cd /tmp && export TMPDIR=/tmp
 for w in 0 1; do
   export WAE_HEAD_WIDE=$w
   rm -rf /tmp/hw$w
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/hw$w -- python3 $ROOT/bench.py --mode forward --steps 10 --warmup 3 --no-cpu --no-ar > /tmp/hw$w.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/hw$w -- python3 $ROOT/bench.py --full --mode forward --steps 10 --warmup 3 --no-cpu --no-ar > /tmp/hw$w.log 2>&1
   echo "== WAE_HEAD_WIDE=$w"
   python3 - /tmp/hw$w <<'PY'
 import csv, glob, sys
