@@ -290,6 +290,18 @@ int wae_dmol_loss_fwd(const float* y_hat, const float* y, float* nll, float* dy_
 int wae_dmol_sample(const float* y, const float* u_mix, const float* u_log, float* out, int32_t B, int32_t M,
                     int32_t Tn, float log_scale_min, int32_t clamp_log_scale, void* stream);
 
+/* ---- mixture of Gaussians, output_distribution "Normal" (mixture.py:161-222; wrapper MixtureGaussianLoss vqwae_train.py:404-422,
+ * shift :766) -- replaces mix_gaussian_loss(y_hat, y, log_scale_min, reduce=False) and its autograd backward.
+ * y_hat (B,C,T) fp32: C == 2 one Gaussian [mu | log s]; otherwise M = C/3 (<= 32) as [logit pi | mu | log s], C == 3 being one
+ * Gaussian whose logit row is ignored (gradient 0).  log s is clamped from below at log_scale_min (zero gradient under the clamp).
+ * nll[b,t] = -log p(y[b,t+shift] | y_hat[b,:,t]) (0 where t+shift >= T); dy_hat (B,C,T) or NULL = d nll[b,t] / d y_hat[b,:,t]. */
+int wae_mog_loss_fwd(const float* y_hat, const float* y, float* nll, float* dy_hat, int32_t B, int32_t C, int32_t T,
+                     float log_scale_min, int32_t shift, void* stream);
+/* ---- sample_from_mix_gaussian (mixture.py:225-270) with caller-supplied draws: Gumbel-max mixture pick on u_mix (B,Tn,M) in
+ * (1e-5, 1-1e-5) when M > 1 (NULL allowed when M == 1), mu + exp(log s) z with z (B,Tn) ~ N(0,1), clamp to [-1,1] -> out (B,Tn).
+ * As in the reference, log s is not clamped here. */
+int wae_mog_sample(const float* y, const float* u_mix, const float* z, float* out, int32_t B, int32_t C, int32_t Tn, void* stream);
+
 /* ---- a15 clip_grad_norm_ + Adam + EMA over the flat arena (vqwae_train.py:776-787, :339-350) ---------------
  * coef = min(1, clip/(||g||+1e-6)) (clip <= 0: off); torch.optim.Adam update with bias correction for the
  * 1-based `step`; shadow -= (1-ema_decay)*(shadow-p) when shadow != NULL.  scratch: one double.
@@ -352,6 +364,16 @@ int wae_ar_generate_scalar(const wae_ar_desc* d, const int32_t* dilations, const
                            const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
                            const float* inputs_f, const float* u_mix, const float* u_log, float log_scale_min,
                            int32_t clamp_log_scale, float* out_samples, float* out_params, void* stream);
+/* The same decoding for output_distribution "Normal" (wavenet.py:329-331: sample_from_mix_gaussian, mixture.py:225-270, in place of
+ * the logistic draw): the persistent kernel of wae_ar_generate_scalar with a Gaussian draw per step on the caller's u_mix (B,T,M)
+ * (NULL allowed when M == 1) and z (B,T) standard normals.  O == 2 ([mu | log s]) or O = 3M; log_scale_min is accepted and unused,
+ * as in the reference's sampler.  out_samples (B,T) and/or out_params (B,O,T); inputs_f teacher-forces as above. */
+int wae_ar_generate_scalar_mog(const wae_ar_desc* d, const int32_t* dilations, const int64_t* ring_off, float* ring,
+                               int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
+                               const float* bias2, const float* zb, const float* first_tab, const float* first_bias,
+                               const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
+                               const float* inputs_f, const float* u_mix, const float* z, float log_scale_min,
+                               float* out_samples, float* out_params, void* stream);
 
 /* The same decoding with ONE utterance spread over C cooperating workgroups / CUs (csrc/ar_coop.hip): every layer is
  * split by gate channels; the members all-reduce their shares of x' once per layer and of the skip vector once per

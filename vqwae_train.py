@@ -66,7 +66,7 @@ def build_geometry(hp) -> Geometry:
                     upsample_scales=list(hp.upsample_params["upsample_scales"]) if hp.upsample_conditional_features else None,
                     cin_pad=hp.cin_pad, scalar_input=is_scalar_input(hp.input_type), use_speaker_embedding=True,
                     c_in=hp.dim_in, encoder_hid=hp.encoder_hid, K=256, conv_in=hp.upsample_net != "UpsampleNetwork",
-                    up_act=up_act, up_act_slope=up_slope)
+                    up_act=up_act, up_act_slope=up_slope, output_distribution=hp.output_distribution)
 
 
 def evaluate(eng, loader, device, hp):
@@ -78,7 +78,7 @@ def evaluate(eng, loader, device, hp):
         ln = None if bool((lengths == T).all()) else lengths
         if eng.g.scalar_input:
             out = eng.forward(x.to(device), c.to(device), g.to(device), want_logits=True, train=False)
-            ce, _ = eng.dmol_loss_and_grad(out["logits"], x.to(device), ln, hp.quantize_channels, hp.log_scale_min)
+            ce, _ = eng.scalar_loss_and_grad(out["logits"], x.to(device), ln, hp.quantize_channels, hp.log_scale_min)
         else:
             out = eng.forward(x.to(device), c.to(device), g.to(device), targets=x.to(device), lengths=ln, want_logits=False, train=False)
             ce = out["loss"]
@@ -100,7 +100,8 @@ def eval_model(eng, x, c, g, lengths, global_step, eval_dir, hp, use_ema, hop):
     (The reference's wave plots are out of scope.)  Returns (predicted, target) float waveforms."""
     import numpy as np
     from scipy.io import wavfile
-    from wavenet_autoencoders_amd.data import inv_mulaw_quantize
+    from wavenet_autoencoders_amd.data import inv_mulaw, inv_mulaw_quantize
+    from wavenet_autoencoders_amd.wavenet_vocoder.util import is_mulaw
     idx = int(np.random.randint(0, x.shape[0]))
     length = int(lengths[idx])
     y_target = x[idx, :length].detach().cpu().numpy()
@@ -122,9 +123,13 @@ def eval_model(eng, x, c, g, lengths, global_step, eval_dir, hp, use_ema, hop):
             Tgen = min(length, (quant.shape[-1] - 2 * hp.cin_pad) * int(np.prod(eng.g.upsample_scales)))
             y_target = y_target[:Tgen]
         if eng.g.scalar_input:
+            # a draw of the model's output distribution per step (logistic or Gaussian mixture, :664-670)
             out = eng.incremental_forward(quant, gi, Tgen, mode="sample", log_scale_min=hp.log_scale_min)
             y_hat = out["x"][0].float().cpu().numpy()
             y_target = y_target.astype(np.float32)
+            if is_mulaw(hp.input_type):                                                            # :677-679
+                y_hat = inv_mulaw(y_hat, hp.quantize_channels)
+                y_target = inv_mulaw(y_target, hp.quantize_channels)
         else:
             out = eng.incremental_forward(quant, gi, Tgen, mode="sample", init_idx=127)
             y_hat = inv_mulaw_quantize(out["idx"][0].cpu().numpy(), hp.quantize_channels - 1)       # :621-623 use 255
@@ -204,18 +209,19 @@ def main(argv=None):
     hop = hp.hop_size
     dev_loader = None
     if args.synthetic or not args.dump_root:
-        loader = SyntheticBatcher(per_rank, hop, hp.max_time_steps, hp.dim_in, hp.n_speakers, steps=args.max_steps or 20, rank=rank)
+        loader = SyntheticBatcher(per_rank, hop, hp.max_time_steps, hp.dim_in, hp.n_speakers, steps=args.max_steps or 20, rank=rank,
+                                  scalar=geom.scalar_input)
     else:
         feat = args.feat + (".norm.npy" if str(args.use_norm).lower() in ("true", "1") else ".npy")
         min_frames = (hp.max_time_steps // hop + 2 * hp.cin_pad) if hp.max_time_steps is not None else 0
         items = read_index(args.dump_root, "train_no_dev", min_frames, hp.n_speakers)
         loader = CropBatcher(items, hp.batch_size, hop, hp.max_time_steps, feat, hp.cin_pad, rank, world, train=True,
-                             n_classes=hp.quantize_channels)
+                             n_classes=hp.quantize_channels, scalar=geom.scalar_input)
         if os.path.exists(os.path.join(args.dump_root, "dev", "train.txt")):
             dev_items = read_index(args.dump_root, "dev", min_frames, hp.n_speakers)
             if dev_items:
                 dev_loader = CropBatcher(dev_items, hp.batch_size, hop, hp.max_time_steps, feat, hp.cin_pad, rank, world,
-                                         train=False, n_classes=hp.quantize_channels)
+                                         train=False, n_classes=hp.quantize_channels, scalar=geom.scalar_input)
     sync = D.GradSync(eng) if world > 1 else None
 
     max_steps = args.max_steps or hp.max_train_steps

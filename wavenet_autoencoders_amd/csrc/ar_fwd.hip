@@ -45,6 +45,9 @@ struct ArArgs {
   float* out_f;           // (B, T) drawn samples, or null
   float log_scale_min;
   int clamp_log_scale;
+  // output_distribution of the scalar draw: 0 mixture of logistics (u_mix, u_log), 1 mixture of Gaussians (u_mix, z)
+  int dist;
+  const float* z;         // (B, T) standard normal draws of the Gaussian (dist 1), or null
   int psum_floats;        // max over the matrix-vector products of slices x padded rows (>= AR_THREADS)
 };
 
@@ -261,7 +264,7 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
       __syncthreads();
     }
     // ---- next input: teacher forcing / greedy / categorical draw (wavenet.py:300-338) -------------------------
-    if (tid == 0 && p.scalar) {
+    if (tid == 0 && p.scalar && p.dist == 0) {
       // sample_from_discretized_mix_logistic (mixture.py:118-156) on caller-supplied uniforms: Gumbel-max mixture pick,
       // logistic draw, clamp to [-1, 1] -- the arithmetic of dmol_sample_kernel (csrc/loss.hip)
       float xs = 0.f;
@@ -279,6 +282,28 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
         if (p.clamp_log_scale) ls = fmaxf(ls, p.log_scale_min);
         const float u = p.u_log[(int64_t)b * p.T + t];
         xs = fminf(fmaxf(mu + expf(ls) * (logf(u) - logf(1.f - u)), -1.f), 1.f);
+        if (p.out_f) p.out_f[(int64_t)b * p.T + t] = xs;
+      }
+      fcur[0] = (p.inputs_f && t + 1 < p.n_forced) ? p.inputs_f[(int64_t)b * p.T + t + 1] : xs;
+    }
+    if (tid == 0 && p.scalar && p.dist == 1) {
+      // sample_from_mix_gaussian (mixture.py:225-270) on caller-supplied draws: Gumbel-max mixture pick when M > 1, mu + exp(log s) z
+      // (log s unclamped, as there), clamp to [-1, 1] -- the arithmetic of mog_sample_kernel (csrc/loss.hip).  O == 2: [mu | log s];
+      // otherwise [logit pi | mu | log s] with M = O / 3 (O == 3: one Gaussian, the logit ignored)
+      float xs = 0.f;
+      if (p.z) {
+        const int M = p.O == 2 ? 1 : p.O / 3;
+        const int mu0 = p.O == 2 ? 0 : M, ls0 = p.O == 2 ? 1 : 2 * M;
+        int arg = 0;
+        if (M > 1) {
+          const float* um = p.u_mix + ((int64_t)b * p.T + t) * M;
+          float best = -INFINITY;
+          for (int i = 0; i < M; ++i) {
+            const float v = lbuf[i] - logf(-logf(um[i]));
+            if (v > best) { best = v; arg = i; }
+          }
+        }
+        xs = fminf(fmaxf(lbuf[mu0 + arg] + expf(lbuf[ls0 + arg]) * p.z[(int64_t)b * p.T + t], -1.f), 1.f);
         if (p.out_f) p.out_f[(int64_t)b * p.T + t] = xs;
       }
       fcur[0] = (p.inputs_f && t + 1 < p.n_forced) ? p.inputs_f[(int64_t)b * p.T + t + 1] : xs;
@@ -319,7 +344,7 @@ static int ar_launch(const wae_ar_desc* d, const int32_t* dilations, const int64
                      const float* first_tab, const float* first_bias, const void* w_head, const float* head_bias, const void* c_up,
                      int32_t c_dtype, const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
                      const float* inputs_f, const float* u_mix, const float* u_log, float* out_f, float log_scale_min,
-                     int clamp_log_scale, void* stream) {
+                     int clamp_log_scale, int dist, const float* z, void* stream) {
   ArArgs a;
   a.dtype = d->dtype; a.B = d->B; a.T = d->T; a.L = d->L; a.R = d->R; a.G = d->G; a.S = d->S; a.O = d->O; a.Cc = d->Cc;
   a.Ccp = d->Ccp; a.Hp = d->Hp; a.ktaps = d->ktaps; a.mode = d->mode; a.Rp = d->Rp; a.scale = d->scale; a.dil = dilations;
@@ -329,7 +354,7 @@ static int ar_launch(const wae_ar_desc* d, const int32_t* dilations, const int64
   a.c_dtype = c_dtype; a.inputs = inputs; a.init_idx = d->init_idx;
   a.n_forced = (inputs || inputs_f) ? (d->n_forced > 0 && d->n_forced < d->T ? d->n_forced : d->T) : 0; a.uniforms = uniforms; a.out_idx = out_idx;
   a.out_logits = out_logits; a.scalar = d->scalar_input ? 1 : 0; a.inputs_f = inputs_f; a.u_mix = u_mix; a.u_log = u_log;
-  a.out_f = out_f; a.log_scale_min = log_scale_min; a.clamp_log_scale = clamp_log_scale;
+  a.out_f = out_f; a.log_scale_min = log_scale_min; a.clamp_log_scale = clamp_log_scale; a.dist = dist; a.z = z;
   const int epl = wae_is16(d->dtype) ? 8 : 4;
   const int H = d->G / 2;
   auto ru = [](int x, int m) { return (x + m - 1) / m * m; };
@@ -374,7 +399,7 @@ extern "C" int wae_ar_generate(const wae_ar_desc* d, const int32_t* dilations, c
   WAE_REQUIRE(inputs || (d->init_idx >= 0 && d->init_idx < d->O), "ar_generate: init_idx %d is not a class (O = %d)", d->init_idx, d->O);
   return ar_launch(d, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
                    first_bias, w_head, head_bias, c_up, c_dtype, inputs, uniforms, out_idx, out_logits, nullptr, nullptr, nullptr,
-                   nullptr, -7.0f, 0, stream);
+                   nullptr, -7.0f, 0, 0, nullptr, stream);
 }
 
 extern "C" int wae_ar_generate_scalar(const wae_ar_desc* d, const int32_t* dilations, const int64_t* ring_off, float* ring,
@@ -396,5 +421,28 @@ extern "C" int wae_ar_generate_scalar(const wae_ar_desc* d, const int32_t* dilat
   WAE_REQUIRE(out_samples || out_params, "ar_generate_scalar: no output requested");
   return ar_launch(d, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
                    first_bias, w_head, head_bias, c_up, c_dtype, nullptr, nullptr, nullptr, out_params, inputs_f, u_mix, u_log,
-                   out_samples, log_scale_min, clamp_log_scale, stream);
+                   out_samples, log_scale_min, clamp_log_scale, 0, nullptr, stream);
+}
+
+extern "C" int wae_ar_generate_scalar_mog(const wae_ar_desc* d, const int32_t* dilations, const int64_t* ring_off, float* ring,
+                                          int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
+                                          const float* bias2, const float* zb, const float* first_tab, const float* first_bias,
+                                          const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
+                                          const float* inputs_f, const float* u_mix, const float* z, float log_scale_min,
+                                          float* out_samples, float* out_params, void* stream) {
+  WAE_REQUIRE(d && dilations && ring_off && ring && w_layers && bias2 && zb && first_tab && first_bias && w_head && head_bias,
+              "ar_generate_scalar_mog: null pointer argument");
+  WAE_REQUIRE(wae_dtype_ok(d->dtype), "ar_generate_scalar_mog: bad dtype");
+  WAE_REQUIRE(d->scalar_input && (d->O == 2 || (d->O > 0 && d->O % 3 == 0)),
+              "ar_generate_scalar_mog: needs a scalar-input decoder with 2 or 3M output channels");
+  WAE_REQUIRE(d->B > 0 && d->T > 0 && d->L > 0 && d->R > 0 && d->G > 0 && d->G % 2 == 0 && d->S > 0, "ar_generate_scalar_mog: bad sizes");
+  WAE_REQUIRE(d->Cc <= 0 || c_up, "ar_generate_scalar_mog: Cc > 0 but c_up is null");
+  WAE_REQUIRE((inputs_f && (d->n_forced <= 0 || d->n_forced >= d->T)) || z,
+              "ar_generate_scalar_mog: needs teacher-forced inputs for every step or the normal draws z");
+  WAE_REQUIRE(!z || d->O <= 3 || u_mix, "ar_generate_scalar_mog: %d mixtures need the uniforms u_mix", d->O / 3);
+  WAE_REQUIRE(!out_samples || z, "ar_generate_scalar_mog: samples need the draws");
+  WAE_REQUIRE(out_samples || out_params, "ar_generate_scalar_mog: no output requested");
+  return ar_launch(d, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
+                   first_bias, w_head, head_bias, c_up, c_dtype, nullptr, nullptr, nullptr, out_params, inputs_f, u_mix, nullptr,
+                   out_samples, log_scale_min, 0, 1, z, stream);
 }

@@ -128,6 +128,128 @@ extern "C" int wae_dmol_sample(const float* y, const float* u_mix, const float* 
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Mixture of Gaussians (output_distribution "Normal"): loss (+ gradient wrt the network output) and sampler.
+// Reference: wavenet_vocoder/mixture.py:161-222 (mix_gaussian_loss), :225-270 (sample_from_mix_gaussian); wrapper
+// vqwae_train.py:404-422, shift :766.  Channels: C == 2 is one Gaussian [mu | log s]; otherwise M = C/3 as
+// [logit pi | mu | log s], and C == 3 is one Gaussian whose logit row is ignored.  Same shape of work as dmol_loss_kernel:
+// one lane per (clip, step), the mixtures a register loop, the (B,C,T) parameters read once, coalesced along T.
+// ---------------------------------------------------------------------------------------------------
+#define MOG_MAX_M 32
+
+__device__ __forceinline__ void mog_layout(int C, int& M, int& mu0, int& ls0) {
+  M = C == 2 ? 1 : C / 3;
+  mu0 = C == 2 ? 0 : M;
+  ls0 = C == 2 ? 1 : 2 * M;
+}
+
+__global__ void __launch_bounds__(256) mog_loss_kernel(const float* __restrict__ y_hat, const float* __restrict__ y,
+                                                       float* __restrict__ nll, float* __restrict__ dy_hat, int C, int T,
+                                                       float log_scale_min, int shift) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const int b = blockIdx.y;
+  if (t >= T) return;
+  int M, mu0, ls0;
+  mog_layout(C, M, mu0, ls0);
+  const bool mix = M > 1;
+  const float* yh = y_hat + (int64_t)b * C * T + t;
+  float* dyh = dy_hat ? dy_hat + (int64_t)b * C * T + t : nullptr;
+  const int ty = t + shift;
+  if (ty >= T) {  // no target for the last `shift` positions
+    nll[(int64_t)b * T + t] = 0.f;
+    if (dyh)
+      for (int i = 0; i < C; ++i) dyh[(int64_t)i * T] = 0.f;
+    return;
+  }
+  const float yy = y[(int64_t)b * T + ty];
+  float lp[MOG_MAX_M], dmu[MOG_MAX_M], dls[MOG_MAX_M];
+  float llse = 0.f;
+  if (mix) {  // log_softmax over the mixture logits (mixture.py:208)
+    float lmax = -INFINITY;
+    for (int i = 0; i < M; ++i) lmax = fmaxf(lmax, yh[(int64_t)i * T]);
+    float lsum = 0.f;
+    for (int i = 0; i < M; ++i) lsum += expf(yh[(int64_t)i * T] - lmax);
+    llse = lmax + logf(lsum);
+  }
+  float m = -INFINITY;
+  for (int i = 0; i < M; ++i) {
+    const float mu = yh[(int64_t)(mu0 + i) * T];
+    const float raw = yh[(int64_t)(ls0 + i) * T];
+    const float ls = fmaxf(raw, log_scale_min);                        // :192 / :197
+    const float pass = raw >= log_scale_min ? 1.f : 0.f;                // clamp gradient
+    // Normal(0, exp(ls)).log_prob(y - mu) as torch.distributions forms it (:201-204)
+    const float s = expf(ls);
+    const float var = s * s;
+    const float cen = yy - mu;
+    const float val = -(cen * cen) / (2.f * var) - logf(s) - 0.91893853320467274178f;   // log sqrt(2 pi)
+    lp[i] = mix ? val + (yh[(int64_t)i * T] - llse) : val;
+    dmu[i] = cen / var;                                                 // d log p / d mu
+    dls[i] = (cen * cen / var - 1.f) * pass;                            // d log p / d log s
+    m = fmaxf(m, lp[i]);
+  }
+  float lse = lp[0];
+  if (mix) {                                                            // log_sum_exp (:17-23)
+    float sum = 0.f;
+    for (int i = 0; i < M; ++i) sum += expf(lp[i] - m);
+    lse = m + logf(sum);
+  }
+  nll[(int64_t)b * T + t] = -lse;
+  if (dyh) {
+    if (C == 3) dyh[0] = 0.f;                                           // the ignored logit row
+    for (int i = 0; i < M; ++i) {
+      const float w = mix ? expf(lp[i] - lse) : 1.f;                    // posterior responsibility
+      if (mix) dyh[(int64_t)i * T] = expf(yh[(int64_t)i * T] - llse) - w;
+      dyh[(int64_t)(mu0 + i) * T] = -w * dmu[i];
+      dyh[(int64_t)(ls0 + i) * T] = -w * dls[i];
+    }
+  }
+}
+
+extern "C" int wae_mog_loss_fwd(const float* y_hat, const float* y, float* nll, float* dy_hat, int32_t B, int32_t C, int32_t T,
+                                float log_scale_min, int32_t shift, void* stream) {
+  WAE_REQUIRE(y_hat && y && nll && B > 0 && T > 0 && shift >= 0, "mog_loss: bad arguments");
+  WAE_REQUIRE(C == 2 || (C > 0 && C % 3 == 0), "mog_loss: channels must be 2 or a multiple of 3 (got %d)", C);
+  WAE_REQUIRE(C == 2 || C / 3 <= MOG_MAX_M, "mog_loss: mixtures must be in 1..%d (got %d)", MOG_MAX_M, C / 3);
+  hipLaunchKernelGGL(mog_loss_kernel, dim3((T + 255) / 256, B), dim3(256), 0, as_stream(stream), y_hat, y, nll, dy_hat, C, T,
+                     log_scale_min, shift);
+  return wae_check_launch("mog_loss_fwd");
+}
+
+// sampler with caller-supplied draws: Gumbel-max mixture pick on u_mix in (1e-5, 1-1e-5) when M > 1 (mixture.py:249-252),
+// mu + exp(log s) z with z ~ N(0,1) (:265-267; log s is NOT clamped, as there), clamp to [-1,1] (:269).
+// y (B,C,Tn), u_mix (B,Tn,M) or NULL when M == 1, z (B,Tn) -> out (B,Tn).
+__global__ void __launch_bounds__(256) mog_sample_kernel(const float* __restrict__ y, const float* __restrict__ u_mix,
+                                                         const float* __restrict__ z, float* __restrict__ out, int C, int Tn) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  const int b = blockIdx.y;
+  if (t >= Tn) return;
+  int M, mu0, ls0;
+  mog_layout(C, M, mu0, ls0);
+  const float* yh = y + (int64_t)b * C * Tn + t;
+  int arg = 0;
+  if (M > 1) {
+    const float* um = u_mix + ((int64_t)b * Tn + t) * M;
+    float best = -INFINITY;
+    for (int i = 0; i < M; ++i) {
+      const float v = yh[(int64_t)i * Tn] - logf(-logf(um[i]));
+      if (v > best) { best = v; arg = i; }
+    }
+  }
+  const float mu = yh[(int64_t)(mu0 + arg) * Tn];
+  const float ls = yh[(int64_t)(ls0 + arg) * Tn];
+  const float x = mu + expf(ls) * z[(int64_t)b * Tn + t];
+  out[(int64_t)b * Tn + t] = fminf(fmaxf(x, -1.f), 1.f);
+}
+
+extern "C" int wae_mog_sample(const float* y, const float* u_mix, const float* z, float* out, int32_t B, int32_t C, int32_t Tn,
+                              void* stream) {
+  WAE_REQUIRE(y && z && out && B > 0 && Tn > 0, "mog_sample: bad arguments");
+  WAE_REQUIRE(C == 2 || (C > 0 && C % 3 == 0), "mog_sample: channels must be 2 or a multiple of 3 (got %d)", C);
+  WAE_REQUIRE(C <= 3 || u_mix, "mog_sample: %d mixtures need the uniforms u_mix", C / 3);
+  hipLaunchKernelGGL(mog_sample_kernel, dim3((Tn + 255) / 256, B), dim3(256), 0, as_stream(stream), y, u_mix, z, out, C, Tn);
+  return wae_check_launch("mog_sample");
+}
+
+// ---------------------------------------------------------------------------------------------------
 // K15: clip_grad_norm_ + Adam + EMA over the flat parameter arena (vqwae_train.py:776-787, :339-350)
 //   pass 1 (grad_sqnorm): partial sums of g^2 per workgroup -> one fp64 atomic per workgroup
 //   pass 2 (clip_adam_ema): coef = min(1, thresh/(norm+1e-6)); Adam(lr, betas, eps, weight_decay), bias-corrected;

@@ -32,6 +32,12 @@ def mulaw_quantize(x, mu=255):
     return ((y + 1) / 2 * mu).astype(np.int64)
 
 
+def inv_mulaw(y, mu=255):
+    """nnmnkwii.preprocessing.inv_mulaw restated: sign(y) ((1+mu)^|y| - 1) / mu."""
+    y = np.asarray(y, dtype=np.float64)
+    return np.sign(y) * (1.0 / mu) * ((1.0 + mu) ** np.abs(y) - 1.0)
+
+
 def inv_mulaw_quantize(y, mu=255):
     y = 2 * np.asarray(y, dtype=np.float64) / mu - 1
     return np.sign(y) * (1.0 / mu) * ((1.0 + mu) ** np.abs(y) - 1.0)
@@ -114,17 +120,20 @@ def global_batches(order, batch_size, world):
 class CropBatcher:
     """One rank's view of a phase: yields (x ids (B,T) int32, c (B, c_in, frames) float32, g (B,) int64, lengths (B,))
     for its slice of every global batch.  train=True: SimilarLengthSampler order; else a plain shuffle (the reference's dev
-    loader, shuffle=True).  Class ids are checked against [0, n_classes) here, on the host (the kernels index tables with them)."""
+    loader, shuffle=True).  Class ids are checked against [0, n_classes) here, on the host (the kernels index tables with them).
+    scalar=True (input_type "raw" / "mulaw", is_scalar_input): wave.npy holds float samples in [-1, 1], read as float32 and not
+    range-checked; x is (B,T) float32 and short clips are padded with 0.0 (vqwae_train.py:508-523).  Crops, order and sharding
+    are the same as for class ids."""
 
     def __init__(self, items, batch_size, hop, max_time_steps, feat="mfcc.norm.npy", cin_pad=0, rank=0, world=1, seed=1234,
-                 train=True, n_classes=256, pad_class=None):
+                 train=True, n_classes=256, pad_class=None, scalar=False):
         if batch_size % world != 0:
             raise ValueError("batch size % num gpu must be 0 (vqwae_train.py:754)")
         self.items = items
         self.bs, self.per, self.rank, self.world = batch_size, batch_size // world, rank, world
         self.hop, self.cin_pad, self.feat = hop, cin_pad, feat
         self.frames = (max_time_steps - max_time_steps % hop) // hop if max_time_steps is not None else None
-        self.train, self.n_classes = train, n_classes
+        self.train, self.n_classes, self.scalar = train, n_classes, bool(scalar)
         self.pad_class = int(mulaw_quantize(0, n_classes - 1)) if pad_class is None else pad_class     # vqwae_train.py:509
         lengths = [n for _, n, _ in items]
         if world > 1 and self.frames is not None and any(n < self.frames for n in lengths):
@@ -161,16 +170,22 @@ class CropBatcher:
             s = int(self.crop_rng.integers(self.cin_pad, len(c) - self.frames - self.cin_pad))
             x = x[s * self.hop:(s + self.frames) * self.hop]
             c = c[s - self.cin_pad:s + self.frames + self.cin_pad]
+        if self.scalar:
+            return x.astype(np.float32), np.ascontiguousarray(c.T, dtype=np.float32), spk
         if x.size and (int(x.min()) < 0 or int(x.max()) >= self.n_classes):
             raise IndexError(f"{d}/wave.npy holds class ids outside [0, {self.n_classes})")
         return x.astype(np.int32), np.ascontiguousarray(c.T, dtype=np.float32), spk
 
     def collate(self, idx):
-        """collate_fn (vqwae_train.py:438-552) on class ids: pad x with the silence class, c with zeros, report the lengths."""
+        """collate_fn (vqwae_train.py:438-552) on class ids: pad x with the silence class (scalar samples: 0.0, :508-523), c with
+        zeros, report the lengths."""
         rows = [self.load(j) for j in idx]
         T = max(len(r[0]) for r in rows)
         F = max(r[1].shape[1] for r in rows)
-        x = np.full((len(rows), T), self.pad_class, dtype=np.int32)
+        if self.scalar:
+            x = np.zeros((len(rows), T), dtype=np.float32)
+        else:
+            x = np.full((len(rows), T), self.pad_class, dtype=np.int32)
         c = np.zeros((len(rows), rows[0][1].shape[0], F), dtype=np.float32)
         for i, (xi, ci, _) in enumerate(rows):
             x[i, :len(xi)] = xi
@@ -185,10 +200,12 @@ class CropBatcher:
 
 
 class SyntheticBatcher:
-    """Dataset-free stand-in with the statistics of SURVEY 8d (ids U{0..255}, MFCC-like N(0,1), speakers U{0..n})."""
+    """Dataset-free stand-in with the statistics of SURVEY 8d (ids U{0..255}, MFCC-like N(0,1), speakers U{0..n}); scalar=True:
+    float32 samples U[-1, 1] instead of ids."""
 
-    def __init__(self, batch_size, hop, max_time_steps, c_in=39, n_speakers=153, steps=100, rank=0, seed=1234):
+    def __init__(self, batch_size, hop, max_time_steps, c_in=39, n_speakers=153, steps=100, rank=0, seed=1234, scalar=False):
         self.bs, self.T, self.F, self.c_in, self.n, self.steps = batch_size, max_time_steps, max_time_steps // hop, c_in, n_speakers, steps
+        self.scalar = bool(scalar)
         self.rng = np.random.default_rng(seed + rank)
 
     def __len__(self):
@@ -196,7 +213,10 @@ class SyntheticBatcher:
 
     def __iter__(self):
         for _ in range(self.steps):
-            x = torch.from_numpy(self.rng.integers(0, 256, size=(self.bs, self.T), dtype=np.int32))
+            if self.scalar:
+                x = torch.from_numpy(self.rng.uniform(-1.0, 1.0, size=(self.bs, self.T)).astype(np.float32))
+            else:
+                x = torch.from_numpy(self.rng.integers(0, 256, size=(self.bs, self.T), dtype=np.int32))
             c = torch.from_numpy(self.rng.standard_normal((self.bs, self.c_in, self.F)).astype(np.float32))
             g = torch.from_numpy(self.rng.integers(0, self.n, size=(self.bs,), dtype=np.int64))
             yield x, c, g, torch.full((self.bs,), self.T)

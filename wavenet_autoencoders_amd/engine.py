@@ -642,7 +642,7 @@ class WaeEngine:
                             init_idx: int = 127, c_is_upsampled: bool = False, want_logits: bool = False,
                             gvec: Optional[torch.Tensor] = None, u_mix: Optional[torch.Tensor] = None,
                             u_log: Optional[torch.Tensor] = None, log_scale_min: float = -7.0, clamp_log_scale: bool = False,
-                            n_forced: Optional[int] = None):
+                            n_forced: Optional[int] = None, z: Optional[torch.Tensor] = None):
         """WaveNet.incremental_forward (wavenet.py:218-346) as one persistent launch.
 
         mode "logits": teacher-forced on test_inputs (B,T) class ids (softmax=False, quantize=False) -> logits (B,O,T);
@@ -655,7 +655,9 @@ class WaeEngine:
         run as a forced first step.  Returns dict(idx (B,T) int32, logits (B,O,T) | None).
         Scalar-input decoders: test_inputs (B,T) fp32 teacher-forces the inputs (mode "logits" -> the mixture parameters
         (B,3M,T) as `logits`); mode "sample" draws every step from the mixture of logistics on the uniforms u_mix (B,T,M),
-        u_log (B,T) (torch.rand in (1e-5, 1-1e-5) if None) -> dict(x (B,T) fp32, logits | None)."""
+        u_log (B,T) (torch.rand in (1e-5, 1-1e-5) if None) -> dict(x (B,T) fp32, logits | None).  With geometry
+        output_distribution "Normal" the draw is sample_from_mix_gaussian's (mixture.py:225-270) on u_mix (B,T,M) (M > 1 only) and
+        standard normals z (B,T) (torch.rand / torch.randn if z is None); log_scale_min is unused there, as in the reference."""
         g, lib = self.g, self.lib
         if not getattr(self, "_ar_packed", False) or self.weights_dirty:
             self.pack_ar_weights()
@@ -717,28 +719,47 @@ class WaeEngine:
         ring = torch.zeros(B * C * self.ar_ring_total, dtype=torch.float32, device=dev)
         if g.scalar_input:
             es = self.ar_w.element_size()
-            M = g.O // 3
+            normal = g.output_distribution == "Normal"
+            M = 1 if (normal and g.O == 2) else g.O // 3
             tf = test_inputs.to(dev, torch.float32).contiguous() if test_inputs is not None else None
-            if m == 2 and u_mix is None:
+            if normal:
+                if u_log is not None:
+                    raise ValueError("output_distribution 'Normal' draws from u_mix and z, not u_log")
+                if m == 2 and z is None:
+                    # mixture.py:249 (the mixture pick, M > 1 only), then Normal(...).sample() (:266)
+                    u_mix = torch.rand(B, T, M, device=dev) * (1 - 2e-5) + 1e-5 if M > 1 else None
+                    z = torch.randn(B, T, device=dev)
+            elif z is not None:
+                raise ValueError("output_distribution 'Logistic' draws from u_mix and u_log, not z")
+            elif m == 2 and u_mix is None:
                 u_mix = torch.rand(B, T, M, device=dev) * (1 - 2e-5) + 1e-5          # mixture.py:138,151
                 u_log = torch.rand(B, T, device=dev) * (1 - 2e-5) + 1e-5
             um = u_mix.to(dev, torch.float32).contiguous() if u_mix is not None else None
+            zn = z.to(dev, torch.float32).contiguous() if z is not None else None
             ul = u_log.to(dev, torch.float32).contiguous() if u_log is not None else None
             if m == 0 and tf is None:
                 raise ValueError("mode 'logits' needs test_inputs")
-            xs = torch.empty(B, T, dtype=torch.float32, device=dev) if um is not None else None
+            xs = torch.empty(B, T, dtype=torch.float32, device=dev) if (zn if normal else um) is not None else None
             params = torch.empty(B, g.O, T, dtype=torch.float32, device=dev) if (want_logits or m == 0) else None
             if m >= 3:
                 raise ValueError("scalar-input decoders feed the drawn sample back: modes 'logits' and 'sample' only")
             d = L.ArDesc(self.dt, B, T, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, 0, 1,
                          math.sqrt(1.0 / g.layers), nf)
-            L.check(lib.wae_ar_generate_scalar(ctypes.byref(d), L.ptr(self.ar_dil), L.ptr(self.ar_ring_off), L.ptr(ring),
-                                               self.ar_ring_total, L.ptr(self.ar_w), self.ar_layer_elems * es, self.ar_w2_off * es,
-                                               L.ptr(self.ar_b2), L.ptr(zb), L.ptr(self.first_tab), L.ptr(self.first_bias),
-                                               L.ptr(self.ar_wh), L.ptr(self.ar_hb), L.ptr(c_up), self.dt,
-                                               L.ptr(tf), L.ptr(um), L.ptr(ul), float(log_scale_min),
-                                               int(bool(clamp_log_scale)), L.ptr(xs), L.ptr(params), st), "ar_generate_scalar")
-            self._ar_keep = (c_up, zb, ring, tf, um, ul, gid32)
+            if normal:
+                L.check(lib.wae_ar_generate_scalar_mog(ctypes.byref(d), L.ptr(self.ar_dil), L.ptr(self.ar_ring_off), L.ptr(ring),
+                                                       self.ar_ring_total, L.ptr(self.ar_w), self.ar_layer_elems * es,
+                                                       self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(zb), L.ptr(self.first_tab),
+                                                       L.ptr(self.first_bias), L.ptr(self.ar_wh), L.ptr(self.ar_hb), L.ptr(c_up), self.dt,
+                                                       L.ptr(tf), L.ptr(um), L.ptr(zn), float(log_scale_min), L.ptr(xs), L.ptr(params),
+                                                       st), "ar_generate_scalar_mog")
+            else:
+                L.check(lib.wae_ar_generate_scalar(ctypes.byref(d), L.ptr(self.ar_dil), L.ptr(self.ar_ring_off), L.ptr(ring),
+                                                   self.ar_ring_total, L.ptr(self.ar_w), self.ar_layer_elems * es, self.ar_w2_off * es,
+                                                   L.ptr(self.ar_b2), L.ptr(zb), L.ptr(self.first_tab), L.ptr(self.first_bias),
+                                                   L.ptr(self.ar_wh), L.ptr(self.ar_hb), L.ptr(c_up), self.dt,
+                                                   L.ptr(tf), L.ptr(um), L.ptr(ul), float(log_scale_min),
+                                                   int(bool(clamp_log_scale)), L.ptr(xs), L.ptr(params), st), "ar_generate_scalar")
+            self._ar_keep = (c_up, zb, ring, tf, um, ul, zn, gid32)
             return dict(x=xs, logits=params)
         inputs = test_inputs.to(torch.int32).contiguous() if test_inputs is not None else None
         if inputs is None and not 0 <= int(init_idx) < g.O:
@@ -830,6 +851,15 @@ class WaeEngine:
         dy = torch.empty_like(y_hat)
         L.check(lib.wae_dmol_loss_fwd(L.ptr(y_hat), L.ptr(yf), L.ptr(nll), L.ptr(dy), B, g.O // 3, T, int(num_classes),
                                       float(log_scale_min), 1, st), "dmol_loss")
+        loss, dyt, ln = self._masked_step_loss(nll, dy, lengths, scale)
+        self._dmol_keep = (yf, nll, dy, ln)
+        return loss, dyt
+
+    def _masked_step_loss(self, nll, dy, lengths, scale):
+        """Per-step losses nll (B,T) and their gradient dy (B,O,T) -> (masked mean over the shifted steps, scale * gradient of
+        that mean as (B,T,Op) in the compute dtype, device lengths): wae_masked_mean, wae_to_btc_masked."""
+        g, lib, st = self.g, self.lib, self.stream()
+        B, T = nll.shape
         if lengths is None:
             count, ln = B * (T - 1), None
         else:
@@ -841,8 +871,28 @@ class WaeEngine:
         L.check(lib.wae_to_btc_masked(L.ptr(dy), L.ptr(dyt), B, g.O, T, g.Op, self.dt, L.ptr(ln),
                                       float(scale) * self.grad_scale / max(count, 1), st),
                 "to_btc dy")
-        self._dmol_keep = (yf, nll, dy, ln)
-        return loss[0], dyt
+        return loss[0], dyt, ln
+
+    def mog_loss_and_grad(self, y_hat: torch.Tensor, y: torch.Tensor, lengths, log_scale_min: float = -7.0, scale: float = 1.0):
+        """MixtureGaussianLoss (vqwae_train.py:404-422 with the shift of :766): y_hat (B,C,T) fp32 (C = 2 or 3M), y (B,T) fp32
+        -> (masked mean loss, scale * d loss / d y_hat as (B,T,Op) in the compute dtype for decoder_backward's ext_dy).
+        Per-step loss and its gradient: wae_mog_loss_fwd; masked mean and transposition as in dmol_loss_and_grad."""
+        lib, st = self.lib, self.stream()
+        B, C, T = y_hat.shape
+        yf = y.contiguous().float()
+        nll = torch.empty(B, T, dtype=torch.float32, device=self.device)
+        dy = torch.empty_like(y_hat)
+        L.check(lib.wae_mog_loss_fwd(L.ptr(y_hat), L.ptr(yf), L.ptr(nll), L.ptr(dy), B, C, T, float(log_scale_min), 1, st), "mog_loss")
+        loss, dyt, ln = self._masked_step_loss(nll, dy, lengths, scale)
+        self._mog_keep = (yf, nll, dy, ln)
+        return loss, dyt
+
+    def scalar_loss_and_grad(self, y_hat, y, lengths, quantize_channels: int = 65536, log_scale_min: float = -7.0,
+                             scale: float = 1.0):
+        """The criterion of a scalar-input decoder after its output_distribution (vqwae_train.py:802-812)."""
+        if self.g.output_distribution == "Normal":
+            return self.mog_loss_and_grad(y_hat, y, lengths, log_scale_min, scale=scale)
+        return self.dmol_loss_and_grad(y_hat, y, lengths, quantize_channels, log_scale_min, scale=scale)
 
     def train_step(self, x, c, gid, lengths=None, lr: float = 4e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                    weight_decay: float = 0.0, clip_thresh: float = 100.0, ema_decay: float = 0.9999, grad_hook=None,
@@ -852,7 +902,8 @@ class WaeEngine:
         clip_grad_norm_ + Adam + EMA.  Returns dict(loss, ce, vq_loss, perp, grad_norm).
         ce_scale: factor on the CE gradient (ragged data-parallel shards: n_local * world / n_global, so that the rank mean is
         the gradient of the global masked mean of vqwae_train.py:374-379); vq_loss keeps weight 1 (rank mean, :759).
-        Class-id input: masked cross-entropy; scalar input (hparams input_type "raw"): discretized mixture of logistics."""
+        Class-id input: masked cross-entropy; scalar input (hparams input_type "raw" / "mulaw"): discretized mixture of logistics,
+        or mixture of Gaussians with geometry output_distribution "Normal"."""
         if not hasattr(self, "exp_avg"):
             self.init_optimizer()
         self.prepare_weights(side=True)
@@ -880,7 +931,7 @@ class WaeEngine:
                 out = fwd(x, c, gid, targets=None, lengths=None, want_logits=True, train=True)
                 if not self.g.has_encoder:
                     self._fe = None
-                loss, dyt = self.dmol_loss_and_grad(out["logits"], x, lengths, quantize_channels, log_scale_min, scale=ce_scale)
+                loss, dyt = self.scalar_loss_and_grad(out["logits"], x, lengths, quantize_channels, log_scale_min, scale=ce_scale)
                 out["loss"] = loss
                 grads = self.backward(x, gid, None, lengths, ext_dy=dyt, vq_scale=1.0, grad_sync=grad_sync)
             elif self.g.has_encoder:

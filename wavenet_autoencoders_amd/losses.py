@@ -5,7 +5,7 @@ import torch
 from torch import nn
 
 from . import _lib as L
-from .wavenet_vocoder.mixture import discretized_mix_logistic_loss
+from .wavenet_vocoder.mixture import discretized_mix_logistic_loss, mix_gaussian_loss
 
 
 def sequence_mask(sequence_length, max_len=None):
@@ -153,6 +153,24 @@ class DiscretizedMixturelogisticLoss(nn.Module):
         mask_ = mask.expand_as(target)
         losses = discretized_mix_logistic_loss(input, target, num_classes=self.num_classes, log_scale_min=self.log_scale_min,
                                                reduce=False)
+        assert losses.size() == target.size()
+        return _MaskedMeanFn.apply(losses, mask_)
+
+
+class MixtureGaussianLoss(nn.Module):
+    """vqwae_train.py:404-422; log_scale_min comes from the constructor instead of the module-global hparams."""
+
+    def __init__(self, log_scale_min=-7.0):
+        super().__init__()
+        self.log_scale_min = log_scale_min
+
+    def forward(self, input, target, lengths=None, mask=None, max_len=None):
+        if lengths is None and mask is None:
+            raise RuntimeError("Should provide either lengths or mask")
+        if mask is None:
+            mask = sequence_mask(lengths, max_len).unsqueeze(-1)
+        mask_ = mask.expand_as(target)
+        losses = mix_gaussian_loss(input, target, log_scale_min=self.log_scale_min, reduce=False)
         assert losses.size() == target.size()
         return _MaskedMeanFn.apply(losses, mask_)
 

@@ -72,6 +72,10 @@ class Geometry:
     # kernel's operand ([c ; g] in c_up, [Wc | Wg] in the packed GEMM-1 stream), forward and backward; the hoisted per-clip projection
     # (gproj) is not used.  Set by the stand-alone layer module when it is handed such a tensor.
     g_local: bool = False
+    # output_distribution (wavenet.py:109, hparams.py): the distribution a scalar-input decoder's outputs parameterise -- "Logistic"
+    # (discretized mixture of logistics) or "Normal" (mixture of Gaussians, mixture.py:161-270).  Ignored for class-id decoders
+    # (mulaw-quantize), as in the reference.
+    output_distribution: str = "Logistic"
 
     def __post_init__(self):
         assert self.layers % self.stacks == 0                       # wavenet.py:117
@@ -96,6 +100,13 @@ class Geometry:
             self.dilations = [int(d) for d in self.dilations_override]
         self.receptive_field = (self.k - 1) * sum(self.dilations) + 1   # wavenet.py:42-60
         self.has_encoder = self.c_in is not None
+        if self.scalar_input:
+            if self.output_distribution not in ("Logistic", "Normal"):
+                # vqwae_train.py:810-812
+                raise RuntimeError(f"Not supported output distribution type: {self.output_distribution}")
+            if self.output_distribution == "Normal" and not (self.O == 2 or self.O % 3 == 0):
+                # mixture.py:178-182: [mean, log_scale] or nr_mix = C / 3
+                raise ValueError(f"output_distribution 'Normal' needs out_channels 2 or a multiple of 3 (got {self.O})")
         if self.up_act == "LeakyReLU" and not self.up_act_slope >= 0.0:
             # wae_act_bwd forms act'(x) from the sign of the stored OUTPUT (csrc/misc.hip: act_bwd_kernel); with a negative slope the
             # output's sign no longer is the input's (torch accepts such slopes): refused, not differentiated wrongly
@@ -108,7 +119,8 @@ class Geometry:
                         upsample_scales=cfg.get("upsample_scales"), cin_pad=cfg.get("cin_pad", 0),
                         scalar_input=bool(cfg.get("scalar_input")), c_in=cfg.get("c_in"),
                         encoder_hid=cfg.get("encoder_hid"), K=cfg.get("K", 256), conv_in=bool(cfg.get("conv_in", True)),
-                        up_act=cfg.get("up_act", "none"), up_act_slope=float(cfg.get("up_act_slope", 0.01)))
+                        up_act=cfg.get("up_act", "none"), up_act_slope=float(cfg.get("up_act_slope", 0.01)),
+                        output_distribution=cfg.get("output_distribution", "Logistic"))
 
 
 ENCODER_BLOCKS = [(3, 1), (3, 1), (5, 2), (5, 2), (3, 1), (3, 1), (1, 1), (1, 1), (1, 1), (1, 1)]  # vqvae_model.py:32-40

@@ -55,7 +55,8 @@ class VQVAE(ArenaModel):
         geom = P.Geometry(layers=wg.layers, stacks=wg.stacks, R=wg.R, G=wg.G, S=wg.S, O=wg.O, Cc=wg.Cc, Cg=wg.Cg, k=wg.k,
                           n_speakers=wg.n_speakers, upsample_scales=wg.upsample_scales, cin_pad=wg.cin_pad,
                           scalar_input=wg.scalar_input, use_speaker_embedding=wg.use_speaker_embedding, c_in=c_in,
-                          encoder_hid=encoder_hid, K=K, conv_in=wg.conv_in, up_act=wg.up_act, up_act_slope=wg.up_act_slope)
+                          encoder_hid=encoder_hid, K=K, conv_in=wg.conv_in, up_act=wg.up_act, up_act_slope=wg.up_act_slope,
+                          output_distribution=wg.output_distribution)
         self.out_channels, self.scalar_input = wavenet.out_channels, wavenet.scalar_input
         self.dropout = float(getattr(wavenet, "dropout", 0.0))          # the decoder layers' dropout (modules.py:127-128)
         self._init_arena(geom, "")
@@ -91,11 +92,8 @@ class VQVAE(ArenaModel):
             init = 127 if self.scalar_input else _start_classes(initial_input, self.out_channels, eng)     # one start class per utterance
             gid = g.reshape(-1) if g is not None else None
             if self.scalar_input:
-                M = self.out_channels // 3
-                dev = c.device
-                out = eng.incremental_forward(quant, gid, int(T), mode="sample", log_scale_min=log_scale_min,
-                                              u_mix=torch.rand(c.shape[0], int(T), M, device=dev) * (1 - 2e-5) + 1e-5,
-                                              u_log=torch.rand(c.shape[0], int(T), device=dev) * (1 - 2e-5) + 1e-5)
+                # the draws of the model's output distribution (wavenet.py:325-333): engine.incremental_forward makes them
+                out = eng.incremental_forward(quant, gid, int(T), mode="sample", log_scale_min=log_scale_min)
                 return out["x"].unsqueeze(1)
             if quantize:
                 if not softmax:

@@ -162,7 +162,7 @@ class WaveNet(ArenaModel):
                           n_speakers=n_speakers if (gin_channels > 0 and use_speaker_embedding) else None,
                           upsample_scales=scales, cin_pad=cin_pad, scalar_input=scalar_input,
                           use_speaker_embedding=bool(use_speaker_embedding), conv_in=upsample_net != "UpsampleNetwork",
-                          up_act=up_act, up_act_slope=up_slope)
+                          up_act=up_act, up_act_slope=up_slope, output_distribution=output_distribution)
         self._init_arena(geom, "wavenet.")
         self.receptive_field = receptive_field_size(layers, stacks, kernel_size)
 
@@ -207,15 +207,11 @@ class WaveNet(ArenaModel):
                     tf = tf.reshape(tf.shape[0], -1)                                     # (B,1,T) or (B,T,1) -> (B,T)
                 T = max(int(T or 0), tf.shape[1])                                        # wavenet.py:259-262
             c_is_up = c is not None and (not self.geom.upsample_scales or c.shape[-1] == int(T))
-            B = c.shape[0] if c is not None else (tf.shape[0] if tf is not None else 1)
-            dev = next(self.parameters()).device
-            M = self.out_channels // 3
             with torch.no_grad():
-                # every step draws from its mixture (wavenet.py:325-333); forced steps consume test_inputs instead of the draw
+                # every step draws from its mixture -- logistic or Gaussian after output_distribution (wavenet.py:325-333; the
+                # engine draws the uniforms / normals); forced steps consume test_inputs instead of the draw
                 out = eng.incremental_forward(c, gid, int(T), mode="sample", test_inputs=tf,
-                                              c_is_upsampled=c_is_up, gvec=gvec, log_scale_min=log_scale_min,
-                                              u_mix=torch.rand(B, int(T), M, device=dev) * (1 - 2e-5) + 1e-5,
-                                              u_log=torch.rand(B, int(T), device=dev) * (1 - 2e-5) + 1e-5)
+                                              c_is_upsampled=c_is_up, gvec=gvec, log_scale_min=log_scale_min)
             return out["x"].unsqueeze(1)
         tf = None
         if test_inputs is not None:
