@@ -338,7 +338,7 @@ typedef struct wae_ar_desc {
   int32_t L, R, Rp, G, Hp, S, O, Cc, Ccp, ktaps;
   int32_t mode;
   int32_t init_idx;
-  int32_t scalar_input; /* 0: wae_ar_generate / wae_ar_generate_coop; 1: wae_ar_generate_scalar */
+  int32_t scalar_input; /* 0: wae_ar_generate / wae_ar_generate_coop; 1: wae_ar_generate_scalar[_mog] / wae_ar_generate_coop_scalar */
   float scale;          /* sqrt(1/L) */
   int32_t n_forced;     /* with inputs: steps t < n_forced consume inputs[t], later steps the fed-back output
                            (test_inputs shorter than T, wavenet.py:300-305); <= 0 or >= T: every step is forced */
@@ -410,6 +410,25 @@ int wae_ar_generate_coop_fused(const wae_ar_desc* d, int32_t C, const int32_t* d
                          const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
                          const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
                          uint64_t* msg, float* acc, int32_t* error, const void* w_fused, void* stream);
+/* Scalar-input decoders on C cooperating workgroups: the network, split and exchanges of wae_ar_generate_coop (its weight, ring, zb,
+ * c_up, msg, acc and error arguments, with the same sizes and the same zeroing by the caller) with the first conv and the draw of
+ * wae_ar_generate_scalar / wae_ar_generate_scalar_mog (wavenet.py:284-285, 325-333): the current input is a float, w * x + b is the
+ * first conv, and after the all-gather of the step's parameters every member runs the same draw on the same bits -- dist 0:
+ * sample_from_discretized_mix_logistic (mixture.py:118-156) on u_mix (B,T,M) and draws = u_log (B,T), O = 3M, log scale clamped to
+ * log_scale_min when clamp_log_scale != 0; dist 1: sample_from_mix_gaussian (mixture.py:225-270) on u_mix (B,T,M) (NULL allowed when
+ * M == 1) and draws = z (B,T), O == 2 or 3M, log scale unclamped (log_scale_min and clamp_log_scale unused).  It is the arithmetic of
+ * wae_dmol_sample / wae_mog_sample on the returned parameters, bit for bit.  mode 0: inputs_f (B,T) teacher-forces every step;
+ * mode 2: the draws are required, inputs_f (optional) forces steps t < desc.n_forced and the start value is inputs_f[0] (0 without
+ * it).  out_samples (B,T) and/or out_params (B,O,T), written by member 0.  Always the any-shape kernel: B <= 8, C in 1..32, R, S and
+ * O <= 256; the split of the sums differs from the one-CU kernel's, so the two agree to rounding, not bitwise; error[0] != 0
+ * afterwards means a wait timed out. */
+int wae_ar_generate_coop_scalar(const wae_ar_desc* d, int32_t C, int32_t dist, const int32_t* dilations, const int64_t* ring_off,
+                                float* ring, int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes,
+                                int64_t w2_off_bytes, const float* bias2, const float* zb, const float* first_tab,
+                                const float* first_bias, const void* w_head, const float* head_bias, const void* c_up,
+                                int32_t c_dtype, const float* inputs_f, const float* u_mix, const float* draws,
+                                float log_scale_min, int32_t clamp_log_scale, float* out_samples, float* out_params,
+                                uint64_t* msg, float* acc, int32_t* error, void* stream);
 
 /* ---- backward data path of the gated stack: C[t][M] = sum_s W_s . X_s[t + shift_s] on time-major operands ----
  * (autograd of modules.py:115-163; see csrc/gemm_tm.hip).  mode 0: out (t, M) = acc.  mode 1 (residual):

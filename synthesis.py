@@ -9,6 +9,8 @@ options:
     --length=<T>             Accepted and, as in the reference (synthesis.py:327-329), overridden by frames * up_factor.
     --initial-value=<n>      Initial mu-law class id (default: mulaw_quantize(0) = 127).
     --dtype=<fp32|bf16>      Compute precision [default: fp32].
+    --coop-scalar            Scalar-input models ("raw" / "mulaw"): decode on the cooperative kernel (up to 32 CUs per utterance)
+                             instead of one CU.  No effect on class-id ("mulaw-quantize") models.
 """
 import argparse
 import json
@@ -81,6 +83,7 @@ def main(argv=None):
     ap.add_argument("--length", type=int)
     ap.add_argument("--initial-value", type=int, default=127)
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
+    ap.add_argument("--coop-scalar", action="store_true")
     args = ap.parse_args(argv)
     if args.preset:
         with open(args.preset) as f:
@@ -91,6 +94,8 @@ def main(argv=None):
     eng = WaeEngine(build_geometry(hparams), dtype=args.dtype)
     ck = torch.load(args.checkpoint, map_location="cpu")
     eng.load_state_dict(ck["state_dict"])
+    if args.coop_scalar:
+        eng.ar_path(scalar_coop=True)
     with open(args.speaker2ind) as f:
         sp2ind = json.load(f)
     os.makedirs(args.dst_dir, exist_ok=True)

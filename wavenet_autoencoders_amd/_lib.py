@@ -147,6 +147,8 @@ SIGNATURES = {
                              + [c_i32] + [c_vp] * 8),
     "wae_ar_generate_coop_fused": (c_i32, [ctypes.POINTER(ArDesc), c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64] + [c_vp] * 7
                                    + [c_i32] + [c_vp] * 9),
+    "wae_ar_generate_coop_scalar": (c_i32, [ctypes.POINTER(ArDesc), c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64]
+                                    + [c_vp] * 7 + [c_i32] + [c_vp] * 3 + [c_f32, c_i32] + [c_vp] * 6),
     "wae_ce_logits_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "wae_ce_logits_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "wae_weighted_mean": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),

@@ -56,6 +56,17 @@ struct ArcArgs {
   int NV;                    // values per member and exchange = max(channels per member, skip rows per member)
   float* acc;                // (B, ARC_ACC_FLOATS(R, S, O)) exchange granules, zeroed
   int* error;
+  // scalar-input decoders (ar_coop_kernel<E, true> only; wavenet.py:284-285,325-333): the fed-back quantity is a float drawn from the
+  // step's mixture parameters, as in csrc/ar_fwd.hip
+  const float* inputs_f;     // (B, T) teacher-forced samples or null; n_forced as for inputs
+  const float* u_mix;        // (B, T, M) uniforms of the mixture pick, or null
+  const float* u_log;        // (B, T) uniforms of the logistic draw (dist 0), or null
+  const float* z;            // (B, T) standard normal draws of the Gaussian (dist 1), or null
+  int dist;                  // 0 mixture of logistics (u_mix, u_log), 1 mixture of Gaussians (u_mix when M > 1, z)
+  float log_scale_min;
+  int clamp_log_scale;
+  float* out_samples;        // (B, T) drawn samples, or null
+  float* out_params;         // (B, O, T) mixture parameters of every step, or null
 };
 
 template <typename E>
@@ -422,9 +433,57 @@ __device__ __forceinline__ void arc_draw(const ArcArgs& p, float* lbuf, float* p
   arc_barrier();
 }
 
+// ---- next input of a scalar-input decoder (wavenet.py:325-333) from the mixture parameters in lbuf: fcur[0] <- the sample fed back,
+//      out_samples[t] <- the sample drawn.  The draw of csrc/ar_fwd.hip, expression for expression (sample_from_discretized_mix_logistic,
+//      mixture.py:118-156; sample_from_mix_gaussian, mixture.py:225-270 -- the arithmetic of dmol_sample_kernel / mog_sample_kernel,
+//      csrc/loss.hip), on every member: identical code on identical data, so every member feeds back the same bits.  The step's draws
+//      were requested at the top of the sample and wait in registers: um = u_mix[b, t, tid] (tid < M), ud = u_log[b, t] / z[b, t] and
+//      forced = inputs_f[b, t + 1] on thread 0.  The Gumbel scores are formed by M threads (each is one value's own expression), the
+//      first-maximum scan and the draw by thread 0, as the serial loop of csrc/ar_fwd.hip.
+__device__ __forceinline__ void arc_draw_scalar(const ArcArgs& p, const float* lbuf, float* psum, float* fcur, int b, int m, int t,
+                                                float um, float ud, float forced) {
+  const int tid = threadIdx.x;
+  const bool sampled = p.dist == 0 ? p.u_mix != nullptr : p.z != nullptr;
+  const int M = p.O == 2 ? 1 : p.O / 3;
+  const bool pick = sampled && (p.dist == 0 || M > 1);      // uniform
+  if (pick) {
+    if (tid < M) psum[tid] = lbuf[tid] - logf(-logf(um));
+    arc_barrier();
+  }
+  if (tid == 0) {
+    float xs = 0.f;
+    if (sampled) {
+      int arg = 0;
+      if (pick) {
+        float best = -INFINITY;
+        for (int i = 0; i < M; ++i) {
+          const float v = psum[i];
+          if (v > best) { best = v; arg = i; }
+        }
+      }
+      if (p.dist == 0) {
+        const float mu = lbuf[M + arg];
+        float ls = lbuf[2 * M + arg];
+        if (p.clamp_log_scale) ls = fmaxf(ls, p.log_scale_min);
+        const float u = ud;
+        xs = fminf(fmaxf(mu + expf(ls) * (logf(u) - logf(1.f - u)), -1.f), 1.f);
+      } else {
+        // O == 2: [mu | log s]; otherwise [logit pi | mu | log s] (O == 3: one Gaussian, the logit ignored); log s unclamped
+        const int mu0 = p.O == 2 ? 0 : M, ls0 = p.O == 2 ? 1 : 2 * M;
+        xs = fminf(fmaxf(lbuf[mu0 + arg] + expf(lbuf[ls0 + arg]) * ud, -1.f), 1.f);
+      }
+      if (m == 0 && p.out_samples) p.out_samples[(int64_t)b * p.T + t] = xs;
+    }
+    fcur[0] = (p.inputs_f && t + 1 < p.n_forced) ? forced : xs;
+  }
+  arc_barrier();
+}
+
 __device__ __forceinline__ int arc_uni(const int* q) { return __builtin_amdgcn_readfirstlane(*q); }
 
-template <typename E>
+// SCALAR: the scalar-input form (wae_ar_generate_coop_scalar).  The network is the same; the current input is a float in LDS, the first
+// conv is w * x + b (wavenet.py:311 on one input channel) and the draw is arc_draw_scalar.  The class-id instantiations are untouched.
+template <typename E, bool SCALAR = false>
 __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int EPL = ET<E>::EPL;
@@ -446,7 +505,8 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
   float* lbuf = hbuf + Sk;                // O logits, then exp(l - max)
   float* psum = lbuf + ((p.O + 3) & ~3);  // ARC_THREADS
   float* myskip = psum + ARC_THREADS;     // this member's gated activations of the layer (hc values; wide members only)
-  int* ibuf = (int*)(myskip + ((max(sc, hc) + 3) & ~3));   // [0] = current input id, [1] = abort flag, [2] = argmax
+  int* ibuf = (int*)(myskip + ((max(sc, hc) + 3) & ~3));   // [0] = current input id, [1] = abort flag, [2] = argmax, [3] = current input value (SCALAR)
+  float* fcur = (float*)(ibuf + 3);
   // the layers' dilations, ring offsets and ring cursors (row of the current sample = t mod ring length, advanced once per sample).
   // As loads from the argument arrays inside the layer loop, dilation and offset were vector loads with a full wait each (the
   // compiler cannot prove them invariant next to the ring stores): two L2 round trips in front of every history request.
@@ -461,7 +521,12 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
 
   for (int i = tid; i < NWV * 2 * EPL + K1p; i += ARC_THREADS) sm[i] = 0.f;
   for (int i = tid; i < Sk; i += ARC_THREADS) { skipb[i] = 0.f; hbuf[i] = 0.f; }
-  if (tid == 0) { ibuf[0] = p.n_forced > 0 ? p.inputs[(int64_t)b * p.T] : p.init_idx; ibuf[1] = 0; }
+  if constexpr (SCALAR) {
+    // wavenet.py:284-285: the start value is zero; a forced first step overrides it (wavenet.py:300-302)
+    if (tid == 0) { ibuf[0] = 0; ibuf[1] = 0; fcur[0] = (p.inputs_f && p.n_forced > 0) ? p.inputs_f[(int64_t)b * p.T] : 0.f; }
+  } else {
+    if (tid == 0) { ibuf[0] = p.n_forced > 0 ? p.inputs[(int64_t)b * p.T] : p.init_idx; ibuf[1] = 0; }
+  }
   for (int i = tid; i < p.L; i += ARC_THREADS) { ldil[i] = p.dil[i]; lroff[i] = (int)p.ring_off[i]; lpos[i] = 0; }
   arc_barrier();
 
@@ -635,6 +700,12 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
   };
   float creg = tid < p.Cc ? c_load(0, tid) : 0.f;
   const float fbias = tid < p.R ? p.first_bias[tid] : 0.f;
+  // SCALAR: the first conv has one input channel -- its weight column stays in a register; the mixtures of the head
+  const float fw = (SCALAR && tid < p.R) ? p.first_tab[tid] : 0.f;
+  const int Mx = p.O == 2 ? 1 : p.O / 3;
+  const bool draw_mix = SCALAR && (p.dist == 0 ? p.u_mix != nullptr : (p.z != nullptr && Mx > 1));
+  const float* const draws = p.dist == 0 ? (p.u_mix ? p.u_log : nullptr) : p.z;
+  float* const outl = SCALAR ? p.out_params : p.out_logits;
 
   // A layer is two workgroup barriers (round 3; five before).  Thread tid keeps x[tid] in a register; behind the all-reduce it writes
   // the next layer's current tap straight into vbuf (and into that layer's ring); the next layer's history taps -- requested right
@@ -644,13 +715,22 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
   float xreg = 0.f;
   for (int t = 0; t < p.T; ++t) {
     const int cur = ibuf[0];
+    // SCALAR: this step's draws and the next forced input, requested here: they travel under the layers and wait in registers
+    float d_um = 0.f, d_ud = 0.f, d_forced = 0.f;
     {
       const int roff0 = arc_uni(lroff), pos0 = arc_uni(lpos);
       if (tid < p.R) {
-        xreg = p.first_tab[(int64_t)cur * p.Rp + tid] + fbias;
+        if constexpr (SCALAR) xreg = fmaf(fw, fcur[0], fbias);
+        else xreg = p.first_tab[(int64_t)cur * p.Rp + tid] + fbias;
         vbuf[(p.ktaps - 1) * p.R + tid] = xreg;
         ring[(unsigned)(roff0 + pos0 * p.R + tid)] = xreg;
       }
+    }
+    if constexpr (SCALAR) {
+      const int64_t bt = (int64_t)b * p.T + t;
+      if (draw_mix && tid < Mx) d_um = p.u_mix[bt * Mx + tid];
+      if (tid == 0 && draws) d_ud = draws[bt];
+      if (tid == 0 && p.inputs_f && t + 1 < p.n_forced) d_forced = p.inputs_f[bt + 1];
     }
     // layer 0's history taps: zeros at t = 0, placed after the last gate of sample t - 1 after
     if (tid < p.Cc) vbuf[p.ktaps * p.R + tid] = creg;
@@ -792,13 +872,14 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
                          [&](float v) {
                            if (tid < p.O) {
                              lbuf[tid] = v;
-                             if (p.out_logits && m == 0) p.out_logits[((int64_t)b * p.O + tid) * p.T + t] = v;
+                             if (outl && m == 0) outl[((int64_t)b * p.O + tid) * p.T + t] = v;
                            }
                          }))
         return;
     }
     ARC_TICK(5);
-    arc_draw(p, lbuf, psum, ibuf, b, m, t);
+    if constexpr (SCALAR) arc_draw_scalar(p, lbuf, psum, fcur, b, m, t, d_um, d_ud, d_forced);
+    else arc_draw(p, lbuf, psum, ibuf, b, m, t);
     ARC_TICK(6);
   }
 #ifdef WAE_ARC_PROFILE
@@ -1599,6 +1680,48 @@ extern "C" int wae_ar_coop_msg_values(const wae_ar_desc* d, int32_t C) {
   return hc > sc ? hc : sc;
 }
 
+// the arguments every cooperative kernel shares (everything else zero / null)
+static ArcArgs arc_common_args(const wae_ar_desc* d, int32_t C, const int32_t* dilations, const int64_t* ring_off, float* ring,
+                               int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
+                               const float* bias2, const float* zb, const float* first_tab, const float* first_bias, const void* w_head,
+                               const float* head_bias, const void* c_up, int32_t c_dtype, uint64_t* msg, float* acc, int32_t* error) {
+  ArcArgs a = {};
+  const int H = d->G / 2;
+  const int hc = (H + C - 1) / C, sc = (d->S + C - 1) / C;
+  a.dtype = d->dtype; a.B = d->B; a.T = d->T; a.L = d->L; a.R = d->R; a.G = d->G; a.S = d->S; a.O = d->O; a.Cc = d->Cc;
+  a.Ccp = d->Ccp; a.Hp = d->Hp; a.ktaps = d->ktaps; a.mode = d->mode; a.Rp = d->Rp; a.C = C; a.scale = d->scale; a.dil = dilations;
+  a.ring_off = ring_off; a.ring = ring; a.ring_total = ring_total; a.w_layers = (const char*)w_layers;
+  a.layer_stride = layer_stride_bytes; a.w2_off = w2_off_bytes; a.bias2 = bias2; a.zb = zb; a.first_tab = first_tab;
+  a.first_bias = first_bias; a.w_head = (const char*)w_head; a.head_bias = head_bias; a.c_up = (const char*)c_up;
+  a.c_dtype = c_dtype;
+  a.msg = (unsigned long long*)msg; a.NV = hc > sc ? hc : sc; a.acc = acc; a.error = error;
+  return a;
+}
+
+// dynamic LDS of the any-shape kernel (ar_coop_kernel's carve, rounded up)
+static size_t arc_generic_lds(const wae_ar_desc* d, int32_t C) {
+  const int epl = wae_is16(d->dtype) ? 8 : 4;
+  const int H = d->G / 2;
+  const int hc = (H + C - 1) / C, sc = (d->S + C - 1) / C;
+  auto ru = [](int x, int mm) { return (x + mm - 1) / mm * mm; };
+  return sizeof(float) * (size_t)(ru(d->ktaps * d->R + (d->Cc > 0 ? d->Cc : 0), epl) + d->R + ru(H, epl) + 2 * ru(d->S, epl) + ru(d->O, 4) +
+                                  ARC_THREADS + ru(hc > sc ? hc : sc, 4) + 8 + 3 * d->L + 64);
+}
+
+template <bool SCALAR>
+static void launch_arc_generic(const ArcArgs& a, int dtype, size_t lds, hipStream_t st) {
+  if (dtype == WAE_BF16) {
+    (void)hipFuncSetAttribute((const void*)ar_coop_kernel<__bf16, SCALAR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((ar_coop_kernel<__bf16, SCALAR>), dim3(8 * a.C), dim3(ARC_THREADS), lds, st, a);
+  } else if (dtype == WAE_F16) {
+    (void)hipFuncSetAttribute((const void*)ar_coop_kernel<f16, SCALAR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((ar_coop_kernel<f16, SCALAR>), dim3(8 * a.C), dim3(ARC_THREADS), lds, st, a);
+  } else {
+    (void)hipFuncSetAttribute((const void*)ar_coop_kernel<float, SCALAR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((ar_coop_kernel<float, SCALAR>), dim3(8 * a.C), dim3(ARC_THREADS), lds, st, a);
+  }
+}
+
 static int ar_generate_coop_impl(const wae_ar_desc* d, int32_t C, const int32_t* dilations, const int64_t* ring_off, float* ring,
                                  int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
                                  const float* bias2, const float* zb, const float* first_tab, const float* first_bias,
@@ -1619,26 +1742,17 @@ static int ar_generate_coop_impl(const wae_ar_desc* d, int32_t C, const int32_t*
   WAE_REQUIRE(d->mode != 0 || (inputs && (d->n_forced <= 0 || d->n_forced >= d->T)), "ar_generate_coop: mode 0 needs inputs for every step");
   WAE_REQUIRE(inputs || (d->init_idx >= 0 && d->init_idx < d->O), "ar_generate_coop: init_idx %d is not a class (O = %d)", d->init_idx,
               d->O);
-  WAE_REQUIRE(!d->scalar_input, "ar_generate_coop: scalar-input (DMoL) decoding is not implemented yet");
+  WAE_REQUIRE(!d->scalar_input, "ar_generate_coop: scalar-input decoders go through wae_ar_generate_coop_scalar");
   const int H = d->G / 2;
   const int hc = (H + C - 1) / C, sc = (d->S + C - 1) / C;
   WAE_REQUIRE(2 * hc <= ARC_THREADS && sc <= ARC_THREADS, "ar_generate_coop: too few workgroups for G=%d, S=%d", d->G, d->S);
-  ArcArgs a;
-  a.dtype = d->dtype; a.B = d->B; a.T = d->T; a.L = d->L; a.R = d->R; a.G = d->G; a.S = d->S; a.O = d->O; a.Cc = d->Cc;
-  a.Ccp = d->Ccp; a.Hp = d->Hp; a.ktaps = d->ktaps; a.mode = d->mode; a.Rp = d->Rp; a.C = C; a.scale = d->scale; a.dil = dilations;
-  a.ring_off = ring_off; a.ring = ring; a.ring_total = ring_total; a.w_layers = (const char*)w_layers;
-  a.layer_stride = layer_stride_bytes; a.w2_off = w2_off_bytes; a.bias2 = bias2; a.zb = zb; a.first_tab = first_tab;
-  a.first_bias = first_bias; a.w_head = (const char*)w_head; a.head_bias = head_bias; a.c_up = (const char*)c_up;
-  a.w_fused = nullptr;
-  a.nlds = 0;
-  a.nbank = 0;
-  a.c_dtype = c_dtype; a.inputs = inputs; a.init_idx = d->init_idx; a.uniforms = uniforms; a.out_idx = out_idx;
+  ArcArgs a = arc_common_args(d, C, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
+                              first_bias, w_head, head_bias, c_up, c_dtype, msg, acc, error);
+  a.inputs = inputs; a.init_idx = d->init_idx; a.uniforms = uniforms; a.out_idx = out_idx;
   a.n_forced = inputs ? (d->n_forced > 0 && d->n_forced < d->T ? d->n_forced : d->T) : 0;
-  a.out_logits = out_logits; a.msg = (unsigned long long*)msg; a.NV = hc > sc ? hc : sc; a.acc = acc; a.error = error;
+  a.out_logits = out_logits;
   const int epl = wae_is16(d->dtype) ? 8 : 4;
-  auto ru = [](int x, int mm) { return (x + mm - 1) / mm * mm; };
-  const size_t lds = sizeof(float) * (size_t)(ru(d->ktaps * d->R + (d->Cc > 0 ? d->Cc : 0), epl) + d->R + ru(H, epl) +
-                                              2 * ru(d->S, epl) + ru(d->O, 4) + ARC_THREADS + ru(hc > sc ? hc : sc, 4) + 8 + 3 * d->L + 64);
+  const size_t lds = arc_generic_lds(d, C);
   WAE_REQUIRE(ring_total < (int64_t)1 << 31, "ar_generate_coop: ring_total %lld does not fit 32-bit offsets", (long long)ring_total);
   hipStream_t st = as_stream(stream);
   // the message banks must start with sequence numbers no exchange will use (0): the caller zeroes msg and error
@@ -1674,16 +1788,7 @@ static int ar_generate_coop_impl(const wae_ar_desc* d, int32_t C, const int32_t*
     else done = false;
     if (done) return wae_check_launch("ar_generate_coop");
   }
-  if (d->dtype == WAE_BF16) {
-    (void)hipFuncSetAttribute((const void*)ar_coop_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ar_coop_kernel<__bf16>, dim3(8 * C), dim3(ARC_THREADS), lds, st, a);
-  } else if (d->dtype == WAE_F16) {
-    (void)hipFuncSetAttribute((const void*)ar_coop_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ar_coop_kernel<f16>, dim3(8 * C), dim3(ARC_THREADS), lds, st, a);
-  } else {
-    (void)hipFuncSetAttribute((const void*)ar_coop_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ar_coop_kernel<float>, dim3(8 * C), dim3(ARC_THREADS), lds, st, a);
-  }
+  launch_arc_generic<false>(a, d->dtype, lds, st);
   return wae_check_launch("ar_generate_coop");
 }
 
@@ -1707,4 +1812,57 @@ extern "C" int wae_ar_generate_coop_fused(const wae_ar_desc* d, int32_t C, const
   return ar_generate_coop_impl(d, C, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
                                first_bias, w_head, head_bias, c_up, c_dtype, inputs, uniforms, out_idx, out_logits, msg, acc, error, w_fused,
                                stream);
+}
+
+// Scalar-input decoders on the any-shape cooperative kernel (ar_coop_kernel<E, true>): the network, the split and the exchanges of
+// wae_ar_generate_coop; the first conv and the draw of wae_ar_generate_scalar (dist 0) / wae_ar_generate_scalar_mog (dist 1).
+extern "C" int wae_ar_generate_coop_scalar(const wae_ar_desc* d, int32_t C, int32_t dist, const int32_t* dilations, const int64_t* ring_off,
+                                           float* ring, int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes,
+                                           int64_t w2_off_bytes, const float* bias2, const float* zb, const float* first_tab,
+                                           const float* first_bias, const void* w_head, const float* head_bias, const void* c_up,
+                                           int32_t c_dtype, const float* inputs_f, const float* u_mix, const float* draws,
+                                           float log_scale_min, int32_t clamp_log_scale, float* out_samples, float* out_params,
+                                           uint64_t* msg, float* acc, int32_t* error, void* stream) {
+  WAE_REQUIRE(d && dilations && ring_off && ring && w_layers && bias2 && zb && first_tab && first_bias && w_head && head_bias && msg &&
+                  acc && error, "ar_generate_coop_scalar: null pointer argument");
+  WAE_REQUIRE(wae_dtype_ok(d->dtype), "ar_generate_coop_scalar: bad dtype");
+  WAE_REQUIRE(d->scalar_input, "ar_generate_coop_scalar: needs a scalar-input decoder (class ids go through wae_ar_generate_coop)");
+  WAE_REQUIRE(dist == 0 || dist == 1, "ar_generate_coop_scalar: dist must be 0 (mixture of logistics) or 1 (mixture of Gaussians)");
+  WAE_REQUIRE(dist != 0 || (d->O > 0 && d->O % 3 == 0), "ar_generate_coop_scalar: the mixture of logistics has 3M output channels (got %d)",
+              d->O);
+  WAE_REQUIRE(dist != 1 || d->O == 2 || (d->O > 0 && d->O % 3 == 0),
+              "ar_generate_coop_scalar: the mixture of Gaussians has 2 or 3M output channels (got %d)", d->O);
+  WAE_REQUIRE(d->B > 0 && d->B <= 8, "ar_generate_coop_scalar: 1..8 utterances per launch (one XCD each); use wae_ar_generate_scalar for more");
+  WAE_REQUIRE(C >= 1 && C <= ARC_CMAX, "ar_generate_coop_scalar: 1..%d cooperating workgroups per utterance", ARC_CMAX);
+  WAE_REQUIRE(d->T > 0 && d->L > 0 && d->R > 0 && d->R <= ARC_THREADS && d->G > 0 && d->G % 2 == 0 && d->S > 0 && d->S <= ARC_THREADS &&
+                  d->O <= ARC_THREADS, "ar_generate_coop_scalar: bad sizes (R, S, O <= %d)", ARC_THREADS);
+  WAE_REQUIRE(d->Cc <= 0 || c_up, "ar_generate_coop_scalar: Cc > 0 but c_up is null");
+  WAE_REQUIRE(d->mode == 0 || d->mode == 2, "ar_generate_coop_scalar: mode must be 0 (teacher-forced parameters) or 2 (sample)");
+  const bool sampled = dist == 0 ? (u_mix && draws) : draws != nullptr;
+  WAE_REQUIRE(dist != 0 || !u_mix == !draws, "ar_generate_coop_scalar: u_mix and u_log come together");
+  WAE_REQUIRE(d->mode != 2 || sampled, "ar_generate_coop_scalar: sample mode needs its draws (%s)", dist == 0 ? "u_mix and u_log" : "z");
+  WAE_REQUIRE(dist != 1 || !sampled || d->O <= 3 || u_mix, "ar_generate_coop_scalar: %d mixtures need the uniforms u_mix", d->O / 3);
+  WAE_REQUIRE(d->mode != 0 || (inputs_f && (d->n_forced <= 0 || d->n_forced >= d->T)),
+              "ar_generate_coop_scalar: mode 0 needs teacher-forced inputs for every step");
+  WAE_REQUIRE(!out_samples || sampled, "ar_generate_coop_scalar: samples need the draws");
+  WAE_REQUIRE(out_samples || out_params, "ar_generate_coop_scalar: no output requested");
+  const int H = d->G / 2;
+  const int hc = (H + C - 1) / C, sc = (d->S + C - 1) / C;
+  WAE_REQUIRE(2 * hc <= ARC_THREADS && sc <= ARC_THREADS, "ar_generate_coop_scalar: too few workgroups for G=%d, S=%d", d->G, d->S);
+  WAE_REQUIRE(ring_total < (int64_t)1 << 31, "ar_generate_coop_scalar: ring_total %lld does not fit 32-bit offsets", (long long)ring_total);
+  ArcArgs a = arc_common_args(d, C, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
+                              first_bias, w_head, head_bias, c_up, c_dtype, msg, acc, error);
+  a.inputs_f = inputs_f;
+  a.n_forced = inputs_f ? (d->n_forced > 0 && d->n_forced < d->T ? d->n_forced : d->T) : 0;
+  a.dist = dist;
+  a.u_mix = sampled ? u_mix : nullptr;
+  a.u_log = dist == 0 && sampled ? draws : nullptr;
+  a.z = dist == 1 ? draws : nullptr;
+  a.log_scale_min = log_scale_min;
+  a.clamp_log_scale = dist == 0 ? clamp_log_scale : 0;
+  a.out_samples = out_samples;
+  a.out_params = out_params;
+  // (the caller zeroes msg, acc and error, as for wae_ar_generate_coop)
+  launch_arc_generic<true>(a, d->dtype, arc_generic_lds(d, C), as_stream(stream));
+  return wae_check_launch("ar_generate_coop_scalar");
 }

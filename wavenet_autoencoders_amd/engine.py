@@ -97,6 +97,7 @@ class WaeEngine:
         self._ws: Dict[tuple, dict] = {}
         # which form of the cooperative decode kernel runs (ar_path(); arguments of the C ABI, not environment variables)
         self.ar_generic, self.ar_one_handover, self.ar_resident = False, False, (0, 0)
+        self.ar_scalar_coop = False
         self._param_gen, self._prep_gen, self._ar_gen = 1, 0, -1
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)      # sticky WAE_ERR_* bits set by the kernels (include/wae.h)
 
@@ -599,16 +600,21 @@ class WaeEngine:
         self._ar_packed = True
 
     def ar_path(self, generic: bool = False, one_handover: bool = False, lds_layers: Optional[int] = None,
-                reg_layers: Optional[int] = None):
+                reg_layers: Optional[int] = None, scalar_coop: bool = False):
         """Selects the form of the cooperative decode kernel (csrc/ar_coop.hip) for this engine's next incremental_forward calls -- the
         A/B and test handles that rounds 4-5 read from the environment inside the library: `generic` = the any-shape kernel on the
         reference's geometry too; `one_handover` = one exchange per layer on host-formed W1_cur . W_out products (measured slower:
         23.9 against 31.4 kHz; wae_ar_generate_coop_fused); lds_layers / reg_layers = how many layers' weight packets stay in LDS / in
-        registers (None: as many as fit, 0: none -- (0, 0) is the streaming form; results are bitwise the same for every split)."""
+        registers (None: as many as fit, 0: none -- (0, 0) is the streaming form; results are bitwise the same for every split).
+        `scalar_coop` = scalar-input decoders ("raw" / "mulaw" inputs) decode on the cooperative any-shape kernel too
+        (wae_ar_generate_coop_scalar) where class-id decoders would (<= 8 utterances; R, S, O <= 256; WAE_AR_COOP on; modes "logits" /
+        "sample"), else on the one-CU kernel as without it.  Opt-in: the split sums round differently from the one-CU kernel's, whose
+        roll-out tests/test_gpu_mog.py pins bit for bit.  No effect on class-id decoders."""
         enc = lambda v: 0 if v is None else (-1 if int(v) == 0 else int(v))  # noqa: E731  (wae_ar_desc: 0 = default, < 0 = none)
         if bool(one_handover) != self.ar_one_handover:
             self._ar_packed = False                    # the products are formed by pack_ar_weights
         self.ar_generic, self.ar_one_handover, self.ar_resident = bool(generic), bool(one_handover), (enc(lds_layers), enc(reg_layers))
+        self.ar_scalar_coop = bool(scalar_coop)
         return self
 
     def _pack_ar_fused(self):
@@ -711,8 +717,9 @@ class WaeEngine:
                 "gproj")
         # one utterance per XCD, its gate rows split over up to 32 CUs (csrc/ar_coop.hip); bigger batches run one
         # utterance per CU (csrc/ar_fwd.hip): better aggregate throughput, 3-4x lower speed per utterance
-        coop = (B <= 8 and g.R <= 256 and g.S <= 256 and g.O <= 256 and not g.scalar_input and m <= 2
-                and self.opt.ar_coop)
+        # scalar-input decoders take that path on request only (ar_path(scalar_coop=True)), in the modes their kernel has
+        coop = (B <= 8 and g.R <= 256 and g.S <= 256 and g.O <= 256 and m <= 2 and self.opt.ar_coop
+                and (not g.scalar_input or (self.ar_scalar_coop and m in (0, 2))))
         C = max(1, min(self.opt.ar_coop_c, 32, g.H, g.S)) if coop else 1
         # zeros: the rows read as history before their first write (t - d, t - 2d of the first samples) are the causal pad; the
         # cooperative kernel zero-fills its ring itself, but only when its members share an XCD (round-5 advisor finding)
@@ -745,7 +752,22 @@ class WaeEngine:
                 raise ValueError("scalar-input decoders feed the drawn sample back: modes 'logits' and 'sample' only")
             d = L.ArDesc(self.dt, B, T, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, 0, 1,
                          math.sqrt(1.0 / g.layers), nf)
-            if normal:
+            if coop:
+                nv = lib.wae_ar_coop_msg_values(ctypes.byref(d), C)
+                msg = torch.zeros(B * 2 * C * nv, dtype=torch.int64, device=dev)
+                acc = torch.zeros(B * lib.wae_ar_coop_acc_floats(ctypes.byref(d)), dtype=torch.float32, device=dev)
+                err = torch.zeros(64, dtype=torch.int32, device=dev)   # [0] = time-out flag, as for class ids
+                L.check(lib.wae_ar_generate_coop_scalar(ctypes.byref(d), C, 1 if normal else 0, L.ptr(self.ar_dil), L.ptr(self.ar_ring_off),
+                                                        L.ptr(ring), self.ar_ring_total, L.ptr(self.ar_w), self.ar_layer_elems * es,
+                                                        self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(zb), L.ptr(self.first_tab),
+                                                        L.ptr(self.first_bias), L.ptr(self.ar_wh), L.ptr(self.ar_hb), L.ptr(c_up), self.dt,
+                                                        L.ptr(tf), L.ptr(um), L.ptr(zn if normal else ul), float(log_scale_min),
+                                                        int(bool(clamp_log_scale)), L.ptr(xs), L.ptr(params), L.ptr(msg), L.ptr(acc),
+                                                        L.ptr(err), st), "ar_generate_coop_scalar")
+                self._ar_profile = err
+                if int(err[0].item()) != 0:  # synchronises, as the class-id path does
+                    raise L.WaeError("ar_generate_coop: an exchange between the cooperating workgroups timed out")
+            elif normal:
                 L.check(lib.wae_ar_generate_scalar_mog(ctypes.byref(d), L.ptr(self.ar_dil), L.ptr(self.ar_ring_off), L.ptr(ring),
                                                        self.ar_ring_total, L.ptr(self.ar_w), self.ar_layer_elems * es,
                                                        self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(zb), L.ptr(self.first_tab),
