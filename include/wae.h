@@ -347,6 +347,20 @@ typedef struct wae_ar_desc {
   int32_t resident_lds;  /* layers whose weight packets the fast kernel keeps in LDS: 0 = as many as fit, n > 0 = n, < 0 = none */
   int32_t resident_regs; /* ... and in registers (accumulation registers, then hand-allocated arch VGPRs): 0 = all that fit, n > 0 = n,
                             < 0 = none.  Where the packets wait is not arithmetic: results are bitwise the same for every split. */
+  /* Streaming (every wae_ar_generate* entry).  The reference keeps each layer's input window between incremental_forward calls
+   * (conv.py:17-62: input_buffer is shifted by one row per call and survives the call) until clear_buffer drops it
+   * (wavenet.py:348-356).  Here that window is the caller's `ring`, and t0 says how much of it is filled:
+   * t0 == 0: a fresh decode, exactly as without the field (the ring counts as empty; the cooperative kernels zero-fill it).
+   * t0 > 0: a continuation.  t0 is the absolute index of this launch's first step; `ring` holds what earlier launches -- same geometry,
+   *   weights, dtype, C, kernel form and residency split -- wrote for steps [0, t0).  The launch does not zero-fill the ring and writes
+   *   only the rows of its own steps; ring rows, ring cursors and every "history before the clip starts" test use t0 + t.  The per-step
+   *   operands (inputs, inputs_f, uniforms, u_mix, u_log / z / draws, c_up, out_idx, out_samples, out_logits, out_params) are indexed
+   *   from this launch's step 0 with row length T, and n_forced counts from this launch's step 0.  The first step of a continuation is
+   *   always forced: the caller puts the previous launch's last output (or the teacher-forced value) in inputs[b][0] / inputs_f[b][0].
+   *   msg, acc and error are zeroed by the caller per launch, as ever: the exchange sequence numbers restart.
+   * Refused before any launch: t0 < 0; t0 + T beyond int32_t; t0 > 0 without inputs / inputs_f; t0 > 0 in modes 3 / 4 (the vector they
+   * feed back lives on chip); t0 > 0 with wae_ar_generate_coop_fused's w_fused (the one-hand-over form has no resume prologue). */
+  int32_t t0;
 } wae_ar_desc;
 int wae_ar_generate(const wae_ar_desc* d, const int32_t* dilations, const int64_t* ring_off, float* ring,
                     int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
@@ -383,7 +397,7 @@ int wae_ar_generate_scalar_mog(const wae_ar_desc* d, const int32_t* dilations, c
  * the launch; error[0] != 0 afterwards means a wait timed out (the output is then invalid).  No atomics: every share is one
  * stored {sequence number, fp32} granule and the members add them in a fixed order -- results are bitwise reproducible.  The
  * reference's geometry (R = G = S = O = 256, 3 taps, Cc <= 256) on C = 32 runs a kernel with those sizes as constants
- * (wae_ar_desc.coop_generic = 1 keeps the any-shape kernel); both zero-fill / overwrite `ring` themselves (the caller should still hand
+ * (wae_ar_desc.coop_generic = 1 keeps the any-shape kernel); both zero-fill / overwrite `ring` themselves when t0 == 0 (the caller should still hand
  * over a zeroed ring: the fast kernel's members zero-fill their shares only when they sit on one XCD).  That kernel's
  * 32 members share ONE history ring per utterance (member 0's region of the (B, C, ring_total) allocation: every member writes every
  * row, the same bits) and, in 16-bit storage, keep every layer's weight packets on chip for the whole clip -- 6 layers in LDS, 11 in

@@ -11,6 +11,9 @@ options:
     --dtype=<fp32|bf16>      Compute precision [default: fp32].
     --coop-scalar            Scalar-input models ("raw" / "mulaw"): decode on the cooperative kernel (up to 32 CUs per utterance)
                              instead of one CU.  No effect on class-id ("mulaw-quantize") models.
+    --stream-chunk=<N>       Decode in resumable launches of N samples (WaeEngine.incremental_stream) and post-process every chunk as
+                             it arrives; prints the wall time to the first chunk of audio.  The wav written is the same file.
+    --seed=<n>               torch.manual_seed(n) before decoding: the same draws, hence the same wav, from run to run.
 """
 import argparse
 import json
@@ -52,8 +55,34 @@ def postprocess_wave(y, postprocess, global_gain_scale):
     return y.astype(np.float32)
 
 
-def wavegen(eng, length, c, g, initial_value=127):
-    """wavegen (synthesis.py:295-396): c (Tc, D) features, g speaker id -> float waveform in [-1, 1]."""
+class ChunkPostprocess:
+    """postprocess_wave a chunk at a time: inv_preemphasis is a one-pole recursive filter, so a chunk continues from the filter state
+    the previous chunk left (scipy.signal.lfilter's zi / zf); the gain is point-wise.  The chunks' outputs, concatenated, are the array
+    postprocess_wave returns for the whole signal, bit for bit (the same float64 recurrence in the same order;
+    tests/test_ar_stream_cpu.py)."""
+
+    def __init__(self, postprocess, global_gain_scale, coef=0.85):
+        if postprocess not in ("", None, "none", "inv_preemphasis"):
+            raise NotImplementedError(f"postprocess={postprocess!r}: audio.py offers inv_preemphasis only")
+        self.filter = postprocess == "inv_preemphasis"
+        self.gain, self.coef = global_gain_scale, coef
+        self.zi = np.zeros(1, dtype=np.float64)
+
+    def __call__(self, y):
+        y = np.asarray(y, dtype=np.float64)
+        if self.filter:
+            from scipy import signal
+            y, self.zi = signal.lfilter([1], [1, -self.coef], y, zi=self.zi)
+        if self.gain > 0:
+            y = y / self.gain
+        return y.astype(np.float32)
+
+
+def wavegen(eng, length, c, g, initial_value=127, chunk=None, on_chunk=None):
+    """wavegen (synthesis.py:295-396): c (Tc, D) features, g speaker id -> float waveform in [-1, 1].
+    chunk: decode in resumable launches of that many samples (WaeEngine.incremental_stream) and post-process each chunk with the
+    filter state carried over; on_chunk(t0, audio) is called with every chunk's float32 audio and its first sample's index as soon as
+    it exists.  The waveform returned is the same array as without `chunk`, given the same random draws."""
     device = eng.device
     ct = torch.from_numpy(np.ascontiguousarray(c.T[None]).astype(np.float32)).to(device)      # (1, D, Tc)  :342
     gid = torch.tensor([g], dtype=torch.int64, device=device) if g is not None else None
@@ -61,6 +90,25 @@ def wavegen(eng, length, c, g, initial_value=127):
         eng.prepare_weights()
     lat = eng.encoder_forward(ct)
     quant, _, _ = eng.vq_forward(lat)
+    if chunk is not None:
+        if eng.g.scalar_input:
+            items = eng.incremental_stream(quant, gid, int(length), int(chunk), mode="sample", log_scale_min=hparams.log_scale_min)
+        else:
+            items = eng.incremental_stream(quant, gid, int(length), int(chunk), mode="sample", init_idx=int(initial_value))
+        post = ChunkPostprocess(hparams.postprocess, hparams.global_gain_scale)
+        parts, t0 = [], 0
+        for item in items:
+            if eng.g.scalar_input:
+                y = item["x"][0].cpu().numpy().astype(np.float64)
+                if is_mulaw(hparams.input_type):
+                    y = inv_mulaw(y, hparams.quantize_channels)
+            else:
+                y = inv_mulaw_quantize(item["idx"][0].cpu().numpy(), hparams.quantize_channels)
+            parts.append(post(y))
+            if on_chunk is not None:
+                on_chunk(t0, parts[-1])
+            t0 += len(parts[-1])
+        return np.concatenate(parts)
     if eng.g.scalar_input:
         # input_type "raw" / "mulaw": one draw of the model's output distribution per sample (logistic or Gaussian mixture,
         # wavenet.py:325-333), then inv_mulaw for "mulaw" (synthesis.py:382-385)
@@ -84,6 +132,8 @@ def main(argv=None):
     ap.add_argument("--initial-value", type=int, default=127)
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--coop-scalar", action="store_true")
+    ap.add_argument("--stream-chunk", type=int)
+    ap.add_argument("--seed", type=int)
     args = ap.parse_args(argv)
     if args.preset:
         with open(args.preset) as f:
@@ -119,7 +169,19 @@ def main(argv=None):
         if tar not in sp2ind:
             raise KeyError(f"cant find sp {tar} in sp2ind {args.speaker2ind}")
         length = c.shape[0] * up                                                              # overrides --length (:327-329)
-        y = wavegen(eng, length, c, sp2ind[tar], args.initial_value)
+        if args.seed is not None:
+            torch.manual_seed(args.seed)
+        if args.stream_chunk:
+            import time
+            t_start, first = time.perf_counter(), []
+
+            def on_chunk(t0, audio):
+                if not first:
+                    first.append(time.perf_counter() - t_start)
+                    print(f"first audio: {len(audio)} samples after {first[0] * 1e3:.1f} ms ({src} -> {tar})", flush=True)
+            y = wavegen(eng, length, c, sp2ind[tar], args.initial_value, chunk=args.stream_chunk, on_chunk=on_chunk)
+        else:
+            y = wavegen(eng, length, c, sp2ind[tar], args.initial_value)
         out = f"{out_dir}{tar}_{fid}.wav"
         wavfile.write(out, hparams.sample_rate, y)
         print("Finished! Check out {} for generated audio samples.".format(out), flush=True)

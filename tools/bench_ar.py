@@ -1,11 +1,15 @@
 #!/usr/bin/env python
 """AR synthesis speed (BASELINE config C4): hps/vqwae.json decoder, B utterances, T samples.
 
-usage: bench_ar.py [dtype] [B] [T] [--generic] [--scalar]
+usage: bench_ar.py [dtype] [B] [T] [--generic] [--scalar] [--chunk N[,N...]]
     --generic   the class-id decode on the any-shape cooperative kernel (WaeEngine.ar_path(generic=True))
     --scalar    scalar-input decoders instead: the same decoder with a scalar head (O = 30 mixture of logistics, O = 2 "Normal"), the
                 one-CU path (the default routing) against the cooperative path (ar_path(scalar_coop=True)) on the same draws, the two
-                alternating, best of three decodes each"""
+                alternating, best of three decodes each
+    --chunk N[,N...]  streaming (WaeEngine.incremental_stream): the one-shot decode against the same decode in launches of N steps, for
+                every N listed, in one process -- kHz per utterance (best of three decodes each, after a warm-up) and the wall time from
+                opening the stream to the first chunk's samples on the host.  Without a dtype argument both bf16 and fp32 run; T defaults
+                to 16000 (one second at hps/vqwae.json's rate)."""
 import os
 import sys
 import time
@@ -19,8 +23,14 @@ from wavenet_autoencoders_amd.engine import WaeEngine  # noqa: E402
 
 CFG = dict(layers=20, stacks=2, R=256, G=256, S=256, O=256, Cc=64, Cg=32, k=3, n_speakers=153,
            upsample_scales=[4, 4, 8, 5], cin_pad=0)
-flags = [a for a in sys.argv[1:] if a.startswith("--")]
-pos = [a for a in sys.argv[1:] if not a.startswith("--")]
+argv = sys.argv[1:]
+chunk_sizes = None
+if "--chunk" in argv:
+    i = argv.index("--chunk")
+    chunk_sizes = [int(n) for n in argv[i + 1].split(",")]
+    del argv[i:i + 2]
+flags = [a for a in argv if a.startswith("--")]
+pos = [a for a in argv if not a.startswith("--")]
 dtype = pos[0] if len(pos) > 0 else "bf16"
 B = int(pos[1]) if len(pos) > 1 else 1
 T = int(pos[2]) if len(pos) > 2 else 6400
@@ -61,6 +71,52 @@ def bench_scalar():
               f"(free-running decodes part where a mixture pick ties)")
 
 
+def bench_stream():
+    Ts = int(pos[2]) if len(pos) > 2 else 16000
+    for dt_name in ([pos[0]] if pos else ["bf16", "fp32"]):
+        eng = WaeEngine(Geometry.from_cfg(CFG), dtype=dt_name).ar_path(generic="--generic" in flags)
+        eng.load_state_dict(O.make_state_dict(dict(CFG), salt=7, with_encoder=False))
+        lat = torch.randn(B, 64, Ts // 640, device="cuda")
+        gid = torch.zeros(B, dtype=torch.int64, device="cuda")
+        uni = torch.rand(B, Ts, device="cuda")
+
+        def one_shot():
+            return eng.incremental_forward(lat, gid, Ts, mode="sample", uniforms=uni)["idx"]
+
+        def streamed(n):
+            first, parts = None, []
+            t_open = time.perf_counter()
+            for item in eng.incremental_stream(lat, gid, Ts, n, mode="sample", uniforms=uni):
+                if first is None:
+                    item["idx"].cpu()                       # the first chunk's samples on the host: what a player waits for
+                    first = time.perf_counter() - t_open
+                parts.append(item["idx"])
+            return torch.cat(parts, dim=1), first
+
+        def timed(fn):
+            fn()
+            torch.cuda.synchronize()
+            best, res = None, None
+            for _ in range(3):
+                t0 = time.perf_counter()
+                res = fn()
+                torch.cuda.synchronize()
+                d = time.perf_counter() - t0
+                best = d if best is None else min(best, d)
+            return best, res
+        d1, ref = timed(one_shot)
+        print(f"AR stream {dt_name} B={B} T={Ts} one-shot          : {d1:.3f} s -> {Ts / d1 / 1e3:6.2f} kHz per utterance")
+        for n in chunk_sizes:
+            dn, (idx, first) = timed(lambda: streamed(n))
+            same = bool(torch.equal(idx, ref))
+            print(f"AR stream {dt_name} B={B} T={Ts} chunk {n:6d} ({-(-Ts // n):4d} launches): {dn:.3f} s -> {Ts / dn / 1e3:6.2f} kHz per utterance, "
+                  f"{dn / d1:.3f}x the one-shot time, first chunk after {first * 1e3:.1f} ms, bitwise equal to the one-shot decode: {same}")
+            assert same, f"chunk {n}: the streamed decode differs from the one-shot decode"
+
+
+if chunk_sizes is not None:
+    bench_stream()
+    sys.exit(0)
 if "--scalar" in flags:
     bench_scalar()
     sys.exit(0)

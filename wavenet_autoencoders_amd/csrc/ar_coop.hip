@@ -67,6 +67,7 @@ struct ArcArgs {
   int clamp_log_scale;
   float* out_samples;        // (B, T) drawn samples, or null
   float* out_params;         // (B, O, T) mixture parameters of every step, or null
+  int t0;                    // wae_ar_desc.t0: absolute index of this launch's first step; > 0: the rings hold steps [0, t0)
 };
 
 template <typename E>
@@ -507,7 +508,7 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
   float* myskip = psum + ARC_THREADS;     // this member's gated activations of the layer (hc values; wide members only)
   int* ibuf = (int*)(myskip + ((max(sc, hc) + 3) & ~3));   // [0] = current input id, [1] = abort flag, [2] = argmax, [3] = current input value (SCALAR)
   float* fcur = (float*)(ibuf + 3);
-  // the layers' dilations, ring offsets and ring cursors (row of the current sample = t mod ring length, advanced once per sample).
+  // the layers' dilations, ring offsets and ring cursors (row of the current sample = (t0 + t) mod ring length, advanced once per sample).
   // As loads from the argument arrays inside the layer loop, dilation and offset were vector loads with a full wait each (the
   // compiler cannot prove them invariant next to the ring stores): two L2 round trips in front of every history request.
   int* ldil = ibuf + 8;
@@ -527,7 +528,10 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
   } else {
     if (tid == 0) { ibuf[0] = p.n_forced > 0 ? p.inputs[(int64_t)b * p.T] : p.init_idx; ibuf[1] = 0; }
   }
-  for (int i = tid; i < p.L; i += ARC_THREADS) { ldil[i] = p.dil[i]; lroff[i] = (int)p.ring_off[i]; lpos[i] = 0; }
+  for (int i = tid; i < p.L; i += ARC_THREADS) {
+    const int di = p.dil[i];
+    ldil[i] = di; lroff[i] = (int)p.ring_off[i]; lpos[i] = p.t0 % ((p.ktaps - 1) * di + 1);
+  }
   arc_barrier();
 
   unsigned long long* hbanks = (unsigned long long*)(p.acc + (int64_t)b * ARC_ACC_FLOATS(p.R, p.S, p.O));   // all-gather of h1 (head rows are split over the members)
@@ -610,6 +614,11 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
     if (hist_more)
       for (int i = tid + ARC_HP * ARC_THREADS; i < (p.ktaps - 1) * p.R; i += ARC_THREADS) vbuf[i] = hist_load(l, t, i);
   };
+  if (p.t0 > 0) {
+    // a continuation: layer 0's history taps of the first step are rows an earlier launch wrote (a fresh decode has none: vbuf is zero)
+    request_hist(ldil[0], lroff[0], lpos[0], p.t0);
+    place_hist(0, p.t0);
+  }
   // The weights a member needs for a layer -- ARC_W1P packets of its slice of one gate row, two packets of W_out row tid
   // and of W_skip row tid -- depend on nothing computed: they are requested one layer ahead and wait in registers.
   const int rw = 2 * nch;
@@ -821,7 +830,7 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
       // load latency of the exchange, so the first polling pass usually finds every share; the history rows return in front of the
       // shares (loads return in order) and go into vbuf with the new current tap.
       {
-        const int ln = l + 1 < p.L ? l + 1 : 0, tn = l + 1 < p.L ? t : t + 1;
+        const int ln = l + 1 < p.L ? l + 1 : 0, tn = p.t0 + (l + 1 < p.L ? t : t + 1);      // tn: absolute (ring rows, start of the clip)
         const float bx = b2_x;
         const int dN = arc_uni(ldil + ln), roffN = arc_uni(lroff + ln);
         int posN = arc_uni(lpos + ln);
@@ -902,7 +911,9 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
 //   exchange arc_allsum2; between its stores and its requests: the next layer's weights, scalars and history rows (addresses = a
 //            per-thread offset + a per-layer base; the ring rows of every layer for this sample are tabulated once per sample)
 //   after    residual, the next layer's three taps into vbuf, its current tap into its ring; barrier
-// The rings are zeroed at start (4 MB per member, once per clip), so "before the clip starts" needs no test.
+// The rings are zeroed at start (4 MB per member, once per clip: by the launch with t0 == 0), so "before the clip starts" needs no test,
+// in a continuation (t0 > 0) either: what resumes is the prologue -- the cursors start at t0 mod ring length, nothing is zero-filled and
+// the first step's history taps are loaded; the per-sample loop is the same code.
 template <int I, int N, typename F>
 __device__ __forceinline__ void arc_static_for(F&& f) {
   if constexpr (I < N) {
@@ -1162,8 +1173,11 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
   unsigned long long* msg_b = p.msg + (int64_t)b * 2 * C * p.NV;
   for (int i = tid; i < 32 + K1p + 2 * S; i += ARC_THREADS) sm[i] = 0.f;
   if (tid == 0) { ibuf[0] = p.n_forced > 0 ? p.inputs[(int64_t)b * p.T] : p.init_idx; ibuf[1] = 0; }
-  for (int i = tid; i < L; i += ARC_THREADS) { ldil[i] = p.dil[i]; lroff[i] = (int)p.ring_off[i]; lpos[i] = 0; }
-  {
+  for (int i = tid; i < L; i += ARC_THREADS) {
+    const int di = p.dil[i];
+    ldil[i] = di; lroff[i] = (int)p.ring_off[i]; lpos[i] = p.t0 % (2 * di + 1);
+  }
+  if (p.t0 == 0) {      // a continuation keeps the rows of steps [0, t0) (and the zeros of the rows no step has written yet)
     // (shared ring: member m zeroes its 32nd; the members meet in the XCC-id gather below before anyone reads a row)
     const int64_t n4 = p.ring_total / 4, lo4 = n4 * m / C, hi4 = n4 * (m + 1) / C;
     f32x4* r4 = (f32x4*)ring;
@@ -1179,8 +1193,8 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
     r0 += r0 < 0 ? rlen : 0;
     return int4{ro + r0 * R, ro + r1 * R, ro + pos * R, 0};
   };
-  for (int i = tid; i < L; i += ARC_THREADS) ltab[i] = tab_entry(i, 0);
-  if (tid == 0) ltab[L] = tab_entry(0, 1);
+  for (int i = tid; i < L; i += ARC_THREADS) ltab[i] = tab_entry(i, lpos[i]);
+  if (tid == 0) ltab[L] = tab_entry(0, lpos[0] + 1 == 2 * ldil[0] + 1 ? 0 : lpos[0] + 1);
 
   unsigned long long* hbanks = (unsigned long long*)(p.acc + (int64_t)b * ARC_ACC_FLOATS(R, S, O));
   unsigned long long* ybanks = hbanks + 2 * S;
@@ -1337,6 +1351,10 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
   };
   float hp0, hp1;
   if (tid < Cc) vbuf[3 * R + tid] = creg;         // sample 0: no history (vbuf is zero), its conditioning row
+  if (p.t0 > 0) {                                 // a continuation: the first step's history taps are rows of earlier launches
+    vbuf[tid] = h0;
+    vbuf[R + tid] = h1;
+  }
   arc_barrier();
   hist_part(hp0, hp1);
 
@@ -1695,6 +1713,7 @@ static ArcArgs arc_common_args(const wae_ar_desc* d, int32_t C, const int32_t* d
   a.first_bias = first_bias; a.w_head = (const char*)w_head; a.head_bias = head_bias; a.c_up = (const char*)c_up;
   a.c_dtype = c_dtype;
   a.msg = (unsigned long long*)msg; a.NV = hc > sc ? hc : sc; a.acc = acc; a.error = error;
+  a.t0 = d->t0;
   return a;
 }
 
@@ -1743,6 +1762,8 @@ static int ar_generate_coop_impl(const wae_ar_desc* d, int32_t C, const int32_t*
   WAE_REQUIRE(inputs || (d->init_idx >= 0 && d->init_idx < d->O), "ar_generate_coop: init_idx %d is not a class (O = %d)", d->init_idx,
               d->O);
   WAE_REQUIRE(!d->scalar_input, "ar_generate_coop: scalar-input decoders go through wae_ar_generate_coop_scalar");
+  WAE_AR_REQUIRE_T0("ar_generate_coop", d, inputs);
+  WAE_REQUIRE(d->t0 == 0 || !w_fused, "ar_generate_coop_fused: the one-hand-over form (w_fused) cannot continue a decode (t0 > 0); pass w_fused = NULL");
   const int H = d->G / 2;
   const int hc = (H + C - 1) / C, sc = (d->S + C - 1) / C;
   WAE_REQUIRE(2 * hc <= ARC_THREADS && sc <= ARC_THREADS, "ar_generate_coop: too few workgroups for G=%d, S=%d", d->G, d->S);
@@ -1837,6 +1858,7 @@ extern "C" int wae_ar_generate_coop_scalar(const wae_ar_desc* d, int32_t C, int3
   WAE_REQUIRE(d->T > 0 && d->L > 0 && d->R > 0 && d->R <= ARC_THREADS && d->G > 0 && d->G % 2 == 0 && d->S > 0 && d->S <= ARC_THREADS &&
                   d->O <= ARC_THREADS, "ar_generate_coop_scalar: bad sizes (R, S, O <= %d)", ARC_THREADS);
   WAE_REQUIRE(d->Cc <= 0 || c_up, "ar_generate_coop_scalar: Cc > 0 but c_up is null");
+  WAE_AR_REQUIRE_T0("ar_generate_coop_scalar", d, inputs_f);
   WAE_REQUIRE(d->mode == 0 || d->mode == 2, "ar_generate_coop_scalar: mode must be 0 (teacher-forced parameters) or 2 (sample)");
   const bool sampled = dist == 0 ? (u_mix && draws) : draws != nullptr;
   WAE_REQUIRE(dist != 0 || !u_mix == !draws, "ar_generate_coop_scalar: u_mix and u_log come together");

@@ -49,6 +49,7 @@ struct ArArgs {
   int dist;
   const float* z;         // (B, T) standard normal draws of the Gaussian (dist 1), or null
   int psum_floats;        // max over the matrix-vector products of slices x padded rows (>= AR_THREADS)
+  int t0;                 // absolute index of this launch's first step (wae_ar_desc.t0): the ring holds the rows of steps [0, t0)
 };
 
 template <typename E>
@@ -199,14 +200,15 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
       const int64_t roff = p.ring_off[l];
       const int rlen = (p.ktaps - 1) * d + 1;
       float* rl = ring + roff;
+      const int ta = p.t0 + t;                 // the step's absolute index: ring rows and the start of the clip count from the first launch
       // ---- assemble [x[t-(k-1)d] .. x[t]] and push x[t] into the layer's ring (conv.py:35-44, O(1)) -------
       for (int i = tid; i < p.ktaps * p.R; i += AR_THREADS) {
         const int tap = i / p.R, ch = i - tap * p.R;
-        const int tt = t - (p.ktaps - 1 - tap) * d;
+        const int tt = ta - (p.ktaps - 1 - tap) * d;
         float v;
         if (tap == p.ktaps - 1) {
           v = xbuf[ch];
-          rl[(int64_t)(t % rlen) * p.R + ch] = v;
+          rl[(int64_t)(ta % rlen) * p.R + ch] = v;
         } else {
           v = tt >= 0 ? rl[(int64_t)(tt % rlen) * p.R + ch] : 0.f;   // zero history before the clip starts
         }
@@ -355,6 +357,7 @@ static int ar_launch(const wae_ar_desc* d, const int32_t* dilations, const int64
   a.n_forced = (inputs || inputs_f) ? (d->n_forced > 0 && d->n_forced < d->T ? d->n_forced : d->T) : 0; a.uniforms = uniforms; a.out_idx = out_idx;
   a.out_logits = out_logits; a.scalar = d->scalar_input ? 1 : 0; a.inputs_f = inputs_f; a.u_mix = u_mix; a.u_log = u_log;
   a.out_f = out_f; a.log_scale_min = log_scale_min; a.clamp_log_scale = clamp_log_scale; a.dist = dist; a.z = z;
+  a.t0 = d->t0;
   const int epl = wae_is16(d->dtype) ? 8 : 4;
   const int H = d->G / 2;
   auto ru = [](int x, int m) { return (x + m - 1) / m * m; };
@@ -395,6 +398,8 @@ extern "C" int wae_ar_generate(const wae_ar_desc* d, const int32_t* dilations, c
   WAE_REQUIRE(d->mode != 0 || (inputs && (d->n_forced <= 0 || d->n_forced >= d->T)), "ar_generate: mode 0 needs inputs for every step");
   WAE_REQUIRE(d->mode < 3 || out_logits, "ar_generate: modes 3 / 4 return their vectors through out_logits");
   WAE_REQUIRE(!d->scalar_input, "ar_generate: scalar-input decoders go through wae_ar_generate_scalar");
+  WAE_AR_REQUIRE_T0("ar_generate", d, inputs);
+  WAE_REQUIRE(d->t0 == 0 || d->mode < 3, "ar_generate: a continuation (t0 > 0) cannot resume modes 3 / 4: the vector they feed back stays on chip");
   // the start class indexes the first-conv table: wavenet.py:288 sets class 127, an IndexError there when O <= 127
   WAE_REQUIRE(inputs || (d->init_idx >= 0 && d->init_idx < d->O), "ar_generate: init_idx %d is not a class (O = %d)", d->init_idx, d->O);
   return ar_launch(d, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
@@ -414,6 +419,7 @@ extern "C" int wae_ar_generate_scalar(const wae_ar_desc* d, const int32_t* dilat
   WAE_REQUIRE(d->scalar_input && d->O > 0 && d->O % 3 == 0, "ar_generate_scalar: needs a scalar-input decoder with 3M output channels");
   WAE_REQUIRE(d->B > 0 && d->T > 0 && d->L > 0 && d->R > 0 && d->G > 0 && d->G % 2 == 0 && d->S > 0, "ar_generate_scalar: bad sizes");
   WAE_REQUIRE(d->Cc <= 0 || c_up, "ar_generate_scalar: Cc > 0 but c_up is null");
+  WAE_AR_REQUIRE_T0("ar_generate_scalar", d, inputs_f);
   WAE_REQUIRE((inputs_f && (d->n_forced <= 0 || d->n_forced >= d->T)) || (u_mix && u_log),
               "ar_generate_scalar: needs teacher-forced inputs for every step or the uniforms of the draws");
   WAE_REQUIRE(!u_mix == !u_log, "ar_generate_scalar: u_mix and u_log come together");
@@ -437,6 +443,7 @@ extern "C" int wae_ar_generate_scalar_mog(const wae_ar_desc* d, const int32_t* d
               "ar_generate_scalar_mog: needs a scalar-input decoder with 2 or 3M output channels");
   WAE_REQUIRE(d->B > 0 && d->T > 0 && d->L > 0 && d->R > 0 && d->G > 0 && d->G % 2 == 0 && d->S > 0, "ar_generate_scalar_mog: bad sizes");
   WAE_REQUIRE(d->Cc <= 0 || c_up, "ar_generate_scalar_mog: Cc > 0 but c_up is null");
+  WAE_AR_REQUIRE_T0("ar_generate_scalar_mog", d, inputs_f);
   WAE_REQUIRE((inputs_f && (d->n_forced <= 0 || d->n_forced >= d->T)) || z,
               "ar_generate_scalar_mog: needs teacher-forced inputs for every step or the normal draws z");
   WAE_REQUIRE(!z || d->O <= 3 || u_mix, "ar_generate_scalar_mog: %d mixtures need the uniforms u_mix", d->O / 3);

@@ -819,6 +819,209 @@ class WaeEngine:
         self._ar_keep = (c_up, zb, ring, inputs, uni, gid32)   # keep device buffers alive until the stream has run
         return dict(idx=out_idx, logits=logits)
 
+    def incremental_stream(self, c: Optional[torch.Tensor], gid: Optional[torch.Tensor], T: int, chunk, mode: str = "sample",
+                           test_inputs: Optional[torch.Tensor] = None, uniforms: Optional[torch.Tensor] = None,
+                           init_idx: int = 127, c_is_upsampled: bool = False, want_logits: bool = False,
+                           gvec: Optional[torch.Tensor] = None, u_mix: Optional[torch.Tensor] = None,
+                           u_log: Optional[torch.Tensor] = None, log_scale_min: float = -7.0, clamp_log_scale: bool = False,
+                           n_forced: Optional[int] = None, z: Optional[torch.Tensor] = None):
+        """incremental_forward in resumable launches: a generator over the clip's chunks.
+
+        `chunk`: steps per launch (the last chunk takes what remains), or a sequence of chunk lengths that sums to T.  The other
+        arguments are incremental_forward's.  Every item is the dict incremental_forward returns, restricted to the next chunk's steps:
+        idx (B,n) / x (B,n), logits (B,O,n) when asked for; concatenated along time the items are the one-shot result of the same
+        arguments bit for bit (wae_ar_desc.t0, include/wae.h: a launch with t0 > 0 continues from the history ring the earlier launches
+        left, where the reference keeps each conv's input window between calls, conv.py:17-62).
+        Opening the stream (this call) does what does not depend on the chunk, once: the weight packing, the conditioning upsample of
+        the whole `c` (the encoder side is not causal), the speaker projection, the ring and -- where the caller passed none -- the
+        random draws of all T steps, in incremental_forward's order, so that a seeded stream equals the seeded one-shot call.  The kernel
+        path (cooperative or one CU, C, ar_path() settings) is fixed there too.  Per chunk: the operands' time slices, the forced first
+        input (the previous chunk's last output, or the teacher-forced value), the chunk-relative n_forced, the zeroed exchange buffers
+        and the time-out check (one device read per chunk on the cooperative paths).  Closing the generator early is legal and frees the
+        state; nothing of it outlives the generator.  ValueError before any launch: modes "probs" / "raw" (their fed-back vector stays
+        on chip), ar_path(one_handover=True), a chunk < 1, chunk lengths that do not sum to T."""
+        g, lib = self.g, self.lib
+        if mode in ("probs", "raw"):
+            raise ValueError(f"incremental_stream: mode '{mode}' feeds a vector back that lives on chip; stream 'logits', 'argmax' or 'sample'")
+        if self.ar_one_handover:
+            raise ValueError("incremental_stream: the one-hand-over kernel (ar_path(one_handover=True)) cannot continue a decode")
+        T = int(T)
+        if isinstance(chunk, (int, np.integer)):
+            if int(chunk) < 1:
+                raise ValueError(f"incremental_stream: chunk {int(chunk)} < 1")
+            chunks = [min(int(chunk), T - t) for t in range(0, T, int(chunk))]
+        else:
+            chunks = [int(n) for n in chunk]
+            if not chunks or min(chunks) < 1:
+                raise ValueError("incremental_stream: every chunk has at least one step")
+            if sum(chunks) != T:
+                raise ValueError(f"incremental_stream: the chunk lengths sum to {sum(chunks)}, not to T = {T}")
+        m = {"logits": 0, "argmax": 1, "sample": 2}[mode]
+        if not getattr(self, "_ar_packed", False) or self.weights_dirty:
+            self.pack_ar_weights()
+        st = self.stream()
+        B = c.shape[0] if c is not None else (test_inputs.shape[0] if test_inputs is not None else 1)
+        dev = self.device
+        # ---- incremental_forward's argument handling, unchanged: start classes, the forced prefix, conditioning, speaker rows ----------
+        if not isinstance(init_idx, int) and not g.scalar_input:
+            ii = torch.as_tensor(init_idx).reshape(-1).to("cpu", torch.int64)
+            if ii.numel() == 1:
+                init_idx = int(ii[0])
+            else:
+                if ii.numel() != B:
+                    raise ValueError(f"init_idx: {ii.numel()} start classes for {B} utterances")
+                if int(ii.min()) < 0 or int(ii.max()) >= g.O:
+                    raise IndexError(f"index {int(ii.max() if ii.max() >= g.O else ii.min())} is out of bounds for dimension 2 with size {g.O}")
+                if test_inputs is None:
+                    test_inputs, n_forced = ii.to(dev, torch.int32).reshape(B, 1), 1
+                init_idx = int(ii[0])
+        if test_inputs is not None:
+            nf = int(test_inputs.shape[1]) if n_forced is None else int(n_forced)
+            nf = max(0, min(nf, int(test_inputs.shape[1]), T))
+            if nf == 0:
+                test_inputs = None
+        else:
+            nf = 0
+        if m == 0 and nf < T:
+            raise ValueError("mode 'logits' is teacher-forced: test_inputs must cover all T steps")
+        if g.scalar_input and m == 1:
+            raise ValueError("scalar-input decoders feed the drawn sample back: modes 'logits' and 'sample' only")
+        c_up = None
+        if g.Ccp:
+            c_up = torch.zeros(B, T, g.Ccp, dtype=self.tdtype, device=dev)
+            if c_is_upsampled or not g.upsample_scales:
+                assert c.shape[-1] == T, f"c {tuple(c.shape)} != T {T}"
+                L.check(lib.wae_to_btc(L.ptr(c.contiguous().float()), L.ptr(c_up), B, g.Cc, T, g.Ccp, self.dt, st), "to_btc")
+            else:
+                assert (c.shape[-1] - 2 * g.cin_pad) * int(np.prod(g.upsample_scales)) == T, "c does not upsample to T"
+                self.upsample_forward(c.float(), c_up)
+        zb = torch.empty(B, g.layers, 2 * g.Hp, dtype=torch.float32, device=dev)
+        wg_off = self.lay.off("wavenet.conv_layers.0.conv1x1g.weight_v") if g.Cg > 0 else -1
+        emb_off = self.lay.offsets.get("wavenet.embed_speakers.weight", 0)
+        use_gid = gid is not None and "wavenet.embed_speakers.weight" in self.lay.offsets
+        gid32 = gid.to(torch.int32).contiguous() if gid is not None else None
+        L.check(lib.wae_gproj_fwd(L.ptr(self.eff), wg_off if (gid is not None or gvec is not None) else -1,
+                                  self.lay.off("wavenet.conv_layers.0.conv.bias"), self.lay.layer_stride,
+                                  L.ptr(gid32) if use_gid else None, emb_off, L.ptr(gvec) if gvec is not None else None,
+                                  L.ptr(zb), B, g.layers, g.G, g.Hp, max(g.Cg, 0), int(g.n_speakers or 0), L.ptr(self.err), st),
+                "gproj")
+        coop = (B <= 8 and g.R <= 256 and g.S <= 256 and g.O <= 256 and m <= 2 and self.opt.ar_coop
+                and (not g.scalar_input or (self.ar_scalar_coop and m in (0, 2))))
+        C = max(1, min(self.opt.ar_coop_c, 32, g.H, g.S)) if coop else 1
+        ring = torch.zeros(B * C * self.ar_ring_total, dtype=torch.float32, device=dev)     # the stream's state: every launch continues in it
+        normal = g.scalar_input and g.output_distribution == "Normal"
+        M = (1 if (normal and g.O == 2) else g.O // 3) if g.scalar_input else 0
+        if g.scalar_input:
+            if normal:
+                if u_log is not None:
+                    raise ValueError("output_distribution 'Normal' draws from u_mix and z, not u_log")
+                if m == 2 and z is None:
+                    u_mix = torch.rand(B, T, M, device=dev) * (1 - 2e-5) + 1e-5 if M > 1 else None
+                    z = torch.randn(B, T, device=dev)
+            elif z is not None:
+                raise ValueError("output_distribution 'Logistic' draws from u_mix and u_log, not z")
+            elif m == 2 and u_mix is None:
+                u_mix = torch.rand(B, T, M, device=dev) * (1 - 2e-5) + 1e-5
+                u_log = torch.rand(B, T, device=dev) * (1 - 2e-5) + 1e-5
+            forced = test_inputs.to(dev, torch.float32).contiguous() if test_inputs is not None else None
+            um = u_mix.to(dev, torch.float32).contiguous() if u_mix is not None else None
+            draw = z if normal else u_log
+            draw = draw.to(dev, torch.float32).contiguous() if draw is not None else None
+            uni = None
+            sampled = (draw if normal else um) is not None
+        else:
+            forced = test_inputs.to(dev, torch.int32).contiguous() if test_inputs is not None else None
+            if forced is None and not 0 <= int(init_idx) < g.O:
+                raise IndexError(f"index {int(init_idx)} is out of bounds for dimension 2 with size {g.O}")
+            if m == 2 and uniforms is None:
+                uniforms = torch.rand(B, T, device=dev)
+            uni = uniforms.to(dev).float().contiguous() if uniforms is not None else None
+            um = draw = None
+            sampled = True
+        want = want_logits or m == 0
+        es = self.ar_w.element_size()
+        path = (int(self.ar_generic), self.ar_resident[0], self.ar_resident[1])
+        msg = acc = err = None
+        if coop:
+            d0 = L.ArDesc(self.dt, B, T, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, 0, int(g.scalar_input))
+            nv = lib.wae_ar_coop_msg_values(ctypes.byref(d0), C)
+            msg = torch.empty(B * 2 * C * nv, dtype=torch.int64, device=dev)
+            acc = torch.empty(B * lib.wae_ar_coop_acc_floats(ctypes.byref(d0)), dtype=torch.float32, device=dev)
+            err = torch.empty(64, dtype=torch.int32, device=dev)
+        return self._ar_stream_chunks(chunks, B, T, m, C, coop, normal, sampled, want, nf, forced, init_idx, c_up, zb, ring, uni, um, draw,
+                                      float(log_scale_min), int(bool(clamp_log_scale)), path, msg, acc, err, es, gid32)
+
+    def _ar_stream_chunks(self, chunks, B, T, m, C, coop, normal, sampled, want, nf, forced, init_idx, c_up, zb, ring, uni, um, draw,
+                          log_scale_min, clamp, path, msg, acc, err, es, gid32):
+        """The launches of an open incremental_stream: chunk k runs steps [t0, t0 + n) with wae_ar_desc.t0 = t0."""
+        g, lib, dev = self.g, self.lib, self.device
+        sl = lambda a, t0, n: None if a is None else a[:, t0:t0 + n].contiguous()  # noqa: E731  (B == 1: the slice itself, no copy)
+        last = None                     # (B,) the previous chunk's last output: the forced first input of a chunk past the forced prefix
+        t0, mine = 0, None
+        try:
+            for n in chunks:
+                st = self.stream()
+                k = max(0, min(n, nf - t0))             # steps of this chunk that the caller's inputs force
+                if k > 0 or t0 > 0:
+                    if k == n:
+                        inp = sl(forced, t0, n)
+                    else:
+                        inp = torch.zeros(B, n, dtype=torch.float32 if g.scalar_input else torch.int32, device=dev)
+                        if k > 0:
+                            inp[:, :k] = forced[:, t0:t0 + k]
+                        else:
+                            inp[:, 0] = last
+                    nfc = max(1, k)
+                else:
+                    inp, nfc = None, 0
+                cu = sl(c_up, t0, n)
+                d = L.ArDesc(self.dt, B, n, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m,
+                             0 if g.scalar_input else int(init_idx), int(g.scalar_input), math.sqrt(1.0 / g.layers), nfc,
+                             0 if g.scalar_input else path[0], 0 if g.scalar_input else path[1], 0 if g.scalar_input else path[2], t0)
+                logits = torch.empty(B, g.O, n, dtype=torch.float32, device=dev) if want else None
+                if coop:
+                    msg.zero_()
+                    acc.zero_()
+                    err.zero_()
+                common = (L.ptr(self.ar_dil), L.ptr(self.ar_ring_off), L.ptr(ring), self.ar_ring_total, L.ptr(self.ar_w),
+                          self.ar_layer_elems * es, self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(zb), L.ptr(self.first_tab),
+                          L.ptr(self.first_bias), L.ptr(self.ar_wh), L.ptr(self.ar_hb), L.ptr(cu), self.dt, L.ptr(inp))
+                if g.scalar_input:
+                    umc, dc = sl(um, t0, n), sl(draw, t0, n)
+                    xs = torch.empty(B, n, dtype=torch.float32, device=dev) if sampled else None
+                    if coop:
+                        L.check(lib.wae_ar_generate_coop_scalar(ctypes.byref(d), C, 1 if normal else 0, *common, L.ptr(umc), L.ptr(dc),
+                                                                log_scale_min, clamp, L.ptr(xs), L.ptr(logits), L.ptr(msg), L.ptr(acc),
+                                                                L.ptr(err), st), "ar_generate_coop_scalar")
+                    elif normal:
+                        L.check(lib.wae_ar_generate_scalar_mog(ctypes.byref(d), *common, L.ptr(umc), L.ptr(dc), log_scale_min, L.ptr(xs),
+                                                               L.ptr(logits), st), "ar_generate_scalar_mog")
+                    else:
+                        L.check(lib.wae_ar_generate_scalar(ctypes.byref(d), *common, L.ptr(umc), L.ptr(dc), log_scale_min, clamp,
+                                                           L.ptr(xs), L.ptr(logits), st), "ar_generate_scalar")
+                    item, keep = dict(x=xs, logits=logits), (cu, inp, umc, dc)
+                    last = xs[:, -1] if xs is not None else None
+                else:
+                    uc = sl(uni, t0, n)
+                    out_idx = torch.empty(B, n, dtype=torch.int32, device=dev)
+                    if coop:
+                        L.check(lib.wae_ar_generate_coop_fused(ctypes.byref(d), C, *common, L.ptr(uc), L.ptr(out_idx), L.ptr(logits),
+                                                               L.ptr(msg), L.ptr(acc), L.ptr(err), None, st), "ar_generate_coop")
+                    else:
+                        L.check(lib.wae_ar_generate(ctypes.byref(d), *common, L.ptr(uc), L.ptr(out_idx), L.ptr(logits), st), "ar_generate")
+                    item, keep = dict(idx=out_idx, logits=logits), (cu, inp, uc)
+                    last = out_idx[:, -1]
+                if coop:
+                    self._ar_profile = err
+                    if int(err[0].item()) != 0:      # synchronises once per chunk
+                        raise L.WaeError("ar_generate_coop: an exchange between the cooperating workgroups timed out")
+                mine = self._ar_keep = (c_up, zb, ring, gid32) + keep      # the launch's operands live until the stream has run
+                t0 += n
+                yield item
+        finally:
+            if getattr(self, "_ar_keep", None) is mine:
+                self._ar_keep = None    # closed (early or at the end): the ring and the operands go with the generator
+
     # ------------------------------------------------------------------ full autoencoder
     def forward(self, x: torch.Tensor, c: torch.Tensor, gid: Optional[torch.Tensor], targets=None, lengths=None,
                 want_logits=True, train=False, beta: float = 0.25, dropout_on: bool = True, layer_events: Optional[list] = None):

@@ -104,6 +104,42 @@ class VQVAE(ArenaModel):
             # quantize=False: the probability / logit rows are the outputs and the fed-back inputs (wavenet.py:303-305,335-338)
             return eng.incremental_forward(quant, gid, int(T), mode="probs" if softmax else "raw", init_idx=init)["logits"]
 
+    def incremental_stream(self, initial_input, c, g, T, softmax, quantize, tqdm, log_scale_min, chunk=1600):
+        """incremental_forward in resumable launches: the encoder and the quantiser run once, on the whole `c` (they are not causal),
+        then the decoder yields what incremental_forward returns `chunk` steps at a time (an int, or a sequence of chunk lengths
+        summing to T; engine.incremental_stream) -- the same one-hot (B, C, n) / scalar (B, 1, n) shapes, the same bits given the same
+        draws.  quantize=False feeds a vector back that stays on chip: ValueError."""
+        eng = self.engine()
+        with torch.no_grad():
+            if eng.weights_dirty:
+                eng.prepare_weights()
+            lat = eng.encoder_forward(c.float())
+            quant, idx, stats = eng.vq_forward(lat)
+            from .wavenet_vocoder.wavenet import _start_classes
+            init = 127 if self.scalar_input else _start_classes(initial_input, self.out_channels, eng)
+            gid = g.reshape(-1) if g is not None else None
+            if self.scalar_input:
+                items = eng.incremental_stream(quant, gid, int(T), chunk, mode="sample", log_scale_min=log_scale_min)
+                post = lambda out: out["x"].unsqueeze(1)  # noqa: E731
+            elif quantize:
+                if not softmax:
+                    raise ValueError("quantize=True draws from the softmax probabilities: pass softmax=True")
+                items = eng.incremental_stream(quant, gid, int(T), chunk, mode="sample", init_idx=init)
+                post = lambda out: torch.nn.functional.one_hot(out["idx"].long(), self.out_channels).float().transpose(1, 2).contiguous()  # noqa: E731
+            else:
+                items = eng.incremental_stream(quant, gid, int(T), chunk, mode="probs" if softmax else "raw", init_idx=init)
+                post = lambda out: out["logits"]  # noqa: E731
+
+        def run():
+            try:
+                for item in items:
+                    with torch.no_grad():
+                        out = post(item)
+                    yield out
+            finally:
+                items.close()
+        return run()
+
     def encode(self, x):
         """quantised latents of MFCC features (vqvae_model.py:80-84; inference_2019.py:243-262)."""
         eng = self.engine()

@@ -193,6 +193,35 @@ class WaveNet(ArenaModel):
                             softmax=True, quantize=True, log_scale_min=-50.0):
         """wavenet.py:218-346 as one persistent kernel launch: sampling (quantize=True) -> one-hot (B, C, T); quantize=False ->
         the logits / softmax rows (B, C, T), fed back as the next step's input once test_inputs is used up."""
+        eng, args, kw, post = self._incremental_plan(initial_input, c, g, T, test_inputs, softmax, quantize, log_scale_min)
+        with torch.no_grad():
+            return post(eng.incremental_forward(*args, **kw))
+
+    def incremental_stream(self, initial_input=None, c=None, g=None, T=100, test_inputs=None, tqdm=lambda x: x,
+                           softmax=True, quantize=True, log_scale_min=-50.0, chunk=1600):
+        """incremental_forward in resumable launches (engine.incremental_stream): a generator that yields what incremental_forward
+        returns, `chunk` steps at a time (an int, or a sequence of chunk lengths summing to T) -- one-hot (B, C, n), the samples
+        (B, 1, n) of a scalar-input decoder, or the logits / softmax rows (B, C, n) of a fully teacher-forced quantize=False call.
+        Concatenated along time the items are incremental_forward's result bit for bit, given the same random draws (the stream makes
+        its draws for all T steps when it is opened).  The whole `c` is taken when the stream opens.  quantize=False in free-running
+        mode feeds a vector back that stays on chip: ValueError."""
+        eng, args, kw, post = self._incremental_plan(initial_input, c, g, T, test_inputs, softmax, quantize, log_scale_min)
+        with torch.no_grad():
+            items = eng.incremental_stream(*args, chunk, **kw)
+
+        def run():
+            try:
+                for item in items:
+                    with torch.no_grad():
+                        out = post(item)
+                    yield out
+            finally:
+                items.close()
+        return run()
+
+    def _incremental_plan(self, initial_input, c, g, T, test_inputs, softmax, quantize, log_scale_min):
+        """The engine call behind incremental_forward / incremental_stream: (engine, (c, gid, T), keyword arguments, post) with
+        post: the engine's result dict (of the clip or of a chunk) -> the tensor the reference returns."""
         if self.training:
             raise RuntimeError("incremental_forward only supports eval mode")          # conv.py:19-20
         eng = self.engine()
@@ -207,12 +236,10 @@ class WaveNet(ArenaModel):
                     tf = tf.reshape(tf.shape[0], -1)                                     # (B,1,T) or (B,T,1) -> (B,T)
                 T = max(int(T or 0), tf.shape[1])                                        # wavenet.py:259-262
             c_is_up = c is not None and (not self.geom.upsample_scales or c.shape[-1] == int(T))
-            with torch.no_grad():
-                # every step draws from its mixture -- logistic or Gaussian after output_distribution (wavenet.py:325-333; the
-                # engine draws the uniforms / normals); forced steps consume test_inputs instead of the draw
-                out = eng.incremental_forward(c, gid, int(T), mode="sample", test_inputs=tf,
-                                              c_is_upsampled=c_is_up, gvec=gvec, log_scale_min=log_scale_min)
-            return out["x"].unsqueeze(1)
+            # every step draws from its mixture -- logistic or Gaussian after output_distribution (wavenet.py:325-333; the
+            # engine draws the uniforms / normals); forced steps consume test_inputs instead of the draw
+            return eng, (c, gid, int(T)), dict(mode="sample", test_inputs=tf, c_is_upsampled=c_is_up, gvec=gvec,
+                                               log_scale_min=log_scale_min), lambda out: out["x"].unsqueeze(1)
         tf = None
         if test_inputs is not None:
             tf = _ids_from_input(test_inputs, self.out_channels, False, eng)
@@ -225,22 +252,23 @@ class WaveNet(ArenaModel):
         gvec = None if (g is None or gid is not None) else g.reshape(g.shape[0], -1).float().contiguous()
         c_is_up = c is not None and (not self.geom.upsample_scales or c.shape[-1] == T)
         kw = dict(test_inputs=tf, n_forced=nf, init_idx=init, c_is_upsampled=c_is_up, gvec=gvec)
-        with torch.no_grad():
-            if quantize:
-                if not softmax:
-                    # the reference hands raw logits to OneHotCategorical(probs=...), which rejects negative entries
-                    raise ValueError("quantize=True draws from the softmax probabilities: pass softmax=True")
-                # every step's output is a draw from its distribution (wavenet.py:335-338), forced or not
-                out = eng.incremental_forward(c, gid, T, mode="sample", **kw)
-                return torch.nn.functional.one_hot(out["idx"].long(), self.out_channels).float().transpose(1, 2).contiguous()
-            if nf >= T:                      # fully teacher-forced: logits (or probabilities) of every step
-                y = eng.incremental_forward(c, gid, T, mode="logits", **kw)["logits"]
-                return softmax_bct(y) if softmax else y
-            # quantize=False, free-running: the probability (softmax=True) or logit vector itself is fed back (wavenet.py:303-305)
-            return eng.incremental_forward(c, gid, T, mode="probs" if softmax else "raw", **kw)["logits"]
+        if quantize:
+            if not softmax:
+                # the reference hands raw logits to OneHotCategorical(probs=...), which rejects negative entries
+                raise ValueError("quantize=True draws from the softmax probabilities: pass softmax=True")
+            # every step's output is a draw from its distribution (wavenet.py:335-338), forced or not
+            return eng, (c, gid, T), dict(mode="sample", **kw), lambda out: torch.nn.functional.one_hot(
+                out["idx"].long(), self.out_channels).float().transpose(1, 2).contiguous()
+        if nf >= T:                      # fully teacher-forced: logits (or probabilities) of every step
+            return eng, (c, gid, T), dict(mode="logits", **kw), lambda out: softmax_bct(out["logits"]) if softmax else out["logits"]
+        # quantize=False, free-running: the probability (softmax=True) or logit vector itself is fed back (wavenet.py:303-305)
+        return eng, (c, gid, T), dict(mode="probs" if softmax else "raw", **kw), lambda out: out["logits"]
 
     def clear_buffer(self):
-        """The per-layer history lives inside one kernel launch; nothing persists between calls (wavenet.py:348-356)."""
+        """The per-layer history lives in a ring that one decode owns: inside an open incremental_stream it persists from chunk to
+        chunk (the window Conv1d.incremental_forward keeps between calls, conv.py:17-62) and goes when the stream is exhausted or
+        closed; incremental_forward starts from an empty one every call.  Nothing persists on the module, so there is nothing to clear
+        (wavenet.py:348-356)."""
 
     def make_generation_fast_(self):
         """Weight norm is folded once into the packed weights at synthesis time (wavenet.py:358-364 removes the hooks);
