@@ -78,6 +78,16 @@ class ChunkPostprocess:
         return y.astype(np.float32)
 
 
+def decoded_wave(out):
+    """A decode result of one utterance (WaeEngine.incremental_forward, or a chunk of incremental_stream) -> the float waveform before
+    post-processing (synthesis.py:382-385): class ids through inv_mulaw_quantize; the samples of a scalar-input decoder as they are
+    ("raw") or through inv_mulaw ("mulaw")."""
+    if out.get("idx") is not None:
+        return inv_mulaw_quantize(out["idx"][0].cpu().numpy(), hparams.quantize_channels)
+    y = out["x"][0].cpu().numpy().astype(np.float64)
+    return inv_mulaw(y, hparams.quantize_channels) if is_mulaw(hparams.input_type) else y
+
+
 def wavegen(eng, length, c, g, initial_value=127, chunk=None, on_chunk=None):
     """wavegen (synthesis.py:295-396): c (Tc, D) features, g speaker id -> float waveform in [-1, 1].
     chunk: decode in resumable launches of that many samples (WaeEngine.incremental_stream) and post-process each chunk with the
@@ -90,36 +100,20 @@ def wavegen(eng, length, c, g, initial_value=127, chunk=None, on_chunk=None):
         eng.prepare_weights()
     lat = eng.encoder_forward(ct)
     quant, _, _ = eng.vq_forward(lat)
-    if chunk is not None:
-        if eng.g.scalar_input:
-            items = eng.incremental_stream(quant, gid, int(length), int(chunk), mode="sample", log_scale_min=hparams.log_scale_min)
-        else:
-            items = eng.incremental_stream(quant, gid, int(length), int(chunk), mode="sample", init_idx=int(initial_value))
-        post = ChunkPostprocess(hparams.postprocess, hparams.global_gain_scale)
-        parts, t0 = [], 0
-        for item in items:
-            if eng.g.scalar_input:
-                y = item["x"][0].cpu().numpy().astype(np.float64)
-                if is_mulaw(hparams.input_type):
-                    y = inv_mulaw(y, hparams.quantize_channels)
-            else:
-                y = inv_mulaw_quantize(item["idx"][0].cpu().numpy(), hparams.quantize_channels)
-            parts.append(post(y))
-            if on_chunk is not None:
-                on_chunk(t0, parts[-1])
-            t0 += len(parts[-1])
-        return np.concatenate(parts)
-    if eng.g.scalar_input:
-        # input_type "raw" / "mulaw": one draw of the model's output distribution per sample (logistic or Gaussian mixture,
-        # wavenet.py:325-333), then inv_mulaw for "mulaw" (synthesis.py:382-385)
-        out = eng.incremental_forward(quant, gid, int(length), mode="sample", log_scale_min=hparams.log_scale_min)
-        y = out["x"][0].cpu().numpy().astype(np.float64)
-        if is_mulaw(hparams.input_type):
-            y = inv_mulaw(y, hparams.quantize_channels)
-        return postprocess_wave(y, hparams.postprocess, hparams.global_gain_scale)
-    out = eng.incremental_forward(quant, gid, int(length), mode="sample", init_idx=int(initial_value))
-    idx = out["idx"][0].cpu().numpy()
-    return postprocess_indices(idx, hparams.quantize_channels, hparams.postprocess, hparams.global_gain_scale)
+    # input_type "raw" / "mulaw": one draw of the model's output distribution per sample (logistic or Gaussian mixture,
+    # wavenet.py:325-333); "mulaw-quantize": a categorical draw per sample, from the start class
+    kw = dict(log_scale_min=hparams.log_scale_min) if eng.g.scalar_input else dict(init_idx=int(initial_value))
+    if chunk is None:
+        out = eng.incremental_forward(quant, gid, int(length), mode="sample", **kw)
+        return postprocess_wave(decoded_wave(out), hparams.postprocess, hparams.global_gain_scale)
+    post = ChunkPostprocess(hparams.postprocess, hparams.global_gain_scale)
+    parts, t0 = [], 0
+    for item in eng.incremental_stream(quant, gid, int(length), int(chunk), mode="sample", **kw):
+        parts.append(post(decoded_wave(item)))
+        if on_chunk is not None:
+            on_chunk(t0, parts[-1])
+        t0 += len(parts[-1])
+    return np.concatenate(parts)
 
 
 def main(argv=None):

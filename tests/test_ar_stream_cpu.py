@@ -114,6 +114,37 @@ def test_the_one_handover_form_cannot_be_continued():
     assert b"ar_generate_coop_fused" in err and b"w_fused" in err and b"t0 > 0" in err
 
 
+def test_decode_entries_bind_the_declared_argument_types():
+    """The six wae_ar_generate* signatures, written out parameter by parameter from include/wae.h (not from the prefix _lib.py
+    composes them from): the bound argtypes are these lists, element for element."""
+    from wavenet_autoencoders_amd import _lib
+    D, vp, i32, i64, f32 = ctypes.POINTER(_lib.ArDesc), ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+    expected = {
+        # d, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab, first_bias,
+        # w_head, head_bias, c_up, c_dtype, inputs, uniforms, out_idx, out_logits, stream
+        "wae_ar_generate": [D, vp, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp],
+        # ... c_dtype, inputs_f, u_mix, u_log, log_scale_min, clamp_log_scale, out_samples, out_params, stream
+        "wae_ar_generate_scalar": [D, vp, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, f32, i32, vp, vp, vp],
+        # ... c_dtype, inputs_f, u_mix, z, log_scale_min, out_samples, out_params, stream
+        "wae_ar_generate_scalar_mog": [D, vp, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, f32, vp, vp, vp],
+        # d, C, ... c_dtype, inputs, uniforms, out_idx, out_logits, msg, acc, error, stream
+        "wae_ar_generate_coop": [D, i32, vp, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp],
+        # ... error, w_fused, stream
+        "wae_ar_generate_coop_fused": [D, i32, vp, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp,
+                                       vp, vp],
+        # d, C, dist, ... c_dtype, inputs_f, u_mix, draws, log_scale_min, clamp_log_scale, out_samples, out_params, msg, acc, error, stream
+        "wae_ar_generate_coop_scalar": [D, i32, i32, vp, vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, f32, i32,
+                                        vp, vp, vp, vp, vp, vp],
+    }
+    hdr = open(os.path.join(ROOT, "include", "wae.h")).read()
+    for name, args in expected.items():
+        res, bound = _lib.SIGNATURES[name]
+        assert res is i32 and list(bound) == args, name
+        assert list(getattr(_lib.lib(), name).argtypes) == args, name
+        decl = hdr[hdr.index("int " + name + "("):]
+        assert len(args) == decl[:decl.index(";")].count(",") + 1, name      # one type per declared parameter
+
+
 def test_incremental_stream_is_on_every_layer_of_the_surface():
     from wavenet_autoencoders_amd.engine import WaeEngine
     from wavenet_autoencoders_amd.vqvae_model import VQVAE

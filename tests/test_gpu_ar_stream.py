@@ -236,6 +236,30 @@ def test_seeded_draws_equal_the_seeded_one_shot_call(monkeypatch):
         assert torch.equal(got["x"], one), dist
 
 
+@pytest.mark.parametrize("path", ["class_one_cu", "class_coop", "scalar_logistic", "scalar_normal", "scalar_coop"])
+def test_default_draws_are_made_in_the_same_order(path, monkeypatch):
+    """No draws passed: after the same torch seed the one-shot call and the stream make the same draws, on every decode path"""
+    coop = path in ("class_coop", "scalar_coop")
+    cfg = dict(SMALL)
+    if path.startswith("scalar"):
+        cfg.update(O=6 if path == "scalar_normal" else 30, scalar_input=True,
+                   output_distribution="Normal" if path == "scalar_normal" else "Logistic")
+    eng = _engine(cfg, "fp32", monkeypatch, coop="1" if coop else "0", **(dict(scalar_coop=True) if path == "scalar_coop" else {}))
+    c, gid, uni, forced = _class_inputs(SMALL, 2)
+    kw = dict(mode="sample", c_is_upsampled=True, **({} if cfg.get("scalar_input") else dict(init_idx=31)))
+    key = "x" if cfg.get("scalar_input") else "idx"
+    eng._ar_profile = None
+    torch.manual_seed(23)
+    one = eng.incremental_forward(c, gid, T, **kw)[key].clone()
+    torch.manual_seed(23)
+    got, _ = _cat(eng.incremental_stream(c, gid, T, CHUNKS, **kw))
+    assert torch.equal(got[key], one)
+    assert (eng._ar_profile is not None) == coop                        # the path the case names ran
+    torch.manual_seed(24)
+    other = eng.incremental_forward(c, gid, T, **kw)[key]
+    assert not torch.equal(other, one)                                  # (the draws matter: another seed, another roll-out)
+
+
 def test_early_close_frees_the_stream_and_leaves_the_engine_usable(monkeypatch):
     eng = _engine(REF, "bf16", monkeypatch)
     c, gid, uni, forced = _class_inputs(REF, 1)

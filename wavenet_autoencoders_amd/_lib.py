@@ -81,6 +81,11 @@ class HeadDesc(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in ("dtype", "B", "T", "Ku", "Sp", "Op", "O")] + [("scale", c_f32)]
 
 
+# the 16 arguments every wae_ar_generate* entry starts with: the descriptor, (dilations, ring_off, ring, ring_total, w_layers,
+# layer_stride_bytes, w2_off_bytes), (bias2, zb, first_tab, first_bias, w_head, head_bias, c_up), c_dtype; the cooperative entries
+# put C (and dist) behind the descriptor
+_AR = [ctypes.POINTER(ArDesc), c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64] + [c_vp] * 7 + [c_i32]
+
 # name -> (restype, argtypes); mirrors include/wae.h one to one
 SIGNATURES = {
     "wae_version": (ctypes.c_char_p, []),
@@ -136,20 +141,14 @@ SIGNATURES = {
     "wae_mog_loss_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp]),
     "wae_mog_sample": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "wae_clip_adam_ema": (c_i32, [c_vp] * 5 + [c_i64, c_vp, c_vp, c_i32] + [ctypes.c_double] * 7 + [c_vp]),
-    "wae_ar_generate": (c_i32, [ctypes.POINTER(ArDesc), c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64] + [c_vp] * 7 + [c_i32]
-                        + [c_vp] * 5),
-    "wae_ar_generate_scalar": (c_i32, [ctypes.POINTER(ArDesc), c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64] + [c_vp] * 7 + [c_i32]
-                               + [c_vp] * 3 + [c_f32, c_i32, c_vp, c_vp, c_vp]),
-    "wae_ar_generate_scalar_mog": (c_i32, [ctypes.POINTER(ArDesc), c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64] + [c_vp] * 7 + [c_i32]
-                                   + [c_vp] * 3 + [c_f32, c_vp, c_vp, c_vp]),
+    "wae_ar_generate": (c_i32, _AR + [c_vp] * 5),
+    "wae_ar_generate_scalar": (c_i32, _AR + [c_vp] * 3 + [c_f32, c_i32, c_vp, c_vp, c_vp]),
+    "wae_ar_generate_scalar_mog": (c_i32, _AR + [c_vp] * 3 + [c_f32, c_vp, c_vp, c_vp]),
     "wae_ar_coop_msg_values": (c_i32, [ctypes.POINTER(ArDesc), c_i32]),
     "wae_ar_coop_acc_floats": (c_i64, [ctypes.POINTER(ArDesc)]),
-    "wae_ar_generate_coop": (c_i32, [ctypes.POINTER(ArDesc), c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64] + [c_vp] * 7
-                             + [c_i32] + [c_vp] * 8),
-    "wae_ar_generate_coop_fused": (c_i32, [ctypes.POINTER(ArDesc), c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64] + [c_vp] * 7
-                                   + [c_i32] + [c_vp] * 9),
-    "wae_ar_generate_coop_scalar": (c_i32, [ctypes.POINTER(ArDesc), c_i32, c_i32, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64]
-                                    + [c_vp] * 7 + [c_i32] + [c_vp] * 3 + [c_f32, c_i32] + [c_vp] * 6),
+    "wae_ar_generate_coop": (c_i32, _AR[:1] + [c_i32] + _AR[1:] + [c_vp] * 8),
+    "wae_ar_generate_coop_fused": (c_i32, _AR[:1] + [c_i32] + _AR[1:] + [c_vp] * 9),
+    "wae_ar_generate_coop_scalar": (c_i32, _AR[:1] + [c_i32, c_i32] + _AR[1:] + [c_vp] * 3 + [c_f32, c_i32] + [c_vp] * 6),
     "wae_ce_logits_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "wae_ce_logits_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "wae_weighted_mean": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import dataclasses
 import math
 
 from typing import Dict, Optional
@@ -30,6 +31,35 @@ def _dt(dtype) -> int:
     if dtype in ("fp16", "f16", "half", torch.float16, L.WAE_F16) and not isinstance(dtype, bool):
         return L.WAE_F16
     raise ValueError(f"unsupported compute dtype {dtype!r} (use 'fp32', 'bf16' or 'fp16')")
+
+
+@dataclasses.dataclass
+class _ArDecode:
+    """One autoregressive decode between WaeEngine._ar_open and its launches (_ar_launch): what does not depend on the chunk."""
+    # geometry, mode, start class, ar_path() settings.  ONE descriptor for all launches: _ar_launch overwrites d.T, d.n_forced and d.t0
+    # with the chunk's before every call (the library reads it during the call, never later), so outside a launch those three are stale
+    d: L.ArDesc
+    n_forced: int               # steps of the clip that `forced` covers
+    forced: Optional[torch.Tensor]
+    c_up: Optional[torch.Tensor]
+    zb: torch.Tensor
+    gid32: Optional[torch.Tensor]   # (held only so that wae_gproj_fwd's operand outlives its launch)
+    coop: bool
+    C: int
+    ring: torch.Tensor          # the decode's state: every launch continues in it
+    normal: bool
+    uni: Optional[torch.Tensor]
+    u_mix: Optional[torch.Tensor]
+    draw: Optional[torch.Tensor]    # u_log, or z of a "Normal" decoder
+    sampled: bool
+    want: bool
+    log_scale_min: float
+    clamp: int
+    w_fused: Optional[torch.Tensor]
+    msg: Optional[torch.Tensor]
+    acc: Optional[torch.Tensor]
+    err: Optional[torch.Tensor]
+    last: Optional[torch.Tensor] = None     # (B,) the previous launch's last output
 
 
 class WaeEngine:
@@ -664,13 +694,78 @@ class WaeEngine:
         u_log (B,T) (torch.rand in (1e-5, 1-1e-5) if None) -> dict(x (B,T) fp32, logits | None).  With geometry
         output_distribution "Normal" the draw is sample_from_mix_gaussian's (mixture.py:225-270) on u_mix (B,T,M) (M > 1 only) and
         standard normals z (B,T) (torch.rand / torch.randn if z is None); log_scale_min is unused there, as in the reference."""
-        g, lib = self.g, self.lib
+        s = self._ar_open(c, gid, T, mode=mode, test_inputs=test_inputs, uniforms=uniforms, init_idx=init_idx,
+                          c_is_upsampled=c_is_upsampled, want_logits=want_logits, gvec=gvec, u_mix=u_mix, u_log=u_log,
+                          log_scale_min=log_scale_min, clamp_log_scale=clamp_log_scale, n_forced=n_forced, z=z)
+        return self._ar_launch(s, 0, int(T))      # the one-chunk case of incremental_stream; _ar_keep holds the operands until the next decode
+
+    def incremental_stream(self, c: Optional[torch.Tensor], gid: Optional[torch.Tensor], T: int, chunk, mode: str = "sample",
+                           test_inputs: Optional[torch.Tensor] = None, uniforms: Optional[torch.Tensor] = None,
+                           init_idx: int = 127, c_is_upsampled: bool = False, want_logits: bool = False,
+                           gvec: Optional[torch.Tensor] = None, u_mix: Optional[torch.Tensor] = None,
+                           u_log: Optional[torch.Tensor] = None, log_scale_min: float = -7.0, clamp_log_scale: bool = False,
+                           n_forced: Optional[int] = None, z: Optional[torch.Tensor] = None):
+        """incremental_forward in resumable launches: a generator over the clip's chunks.
+
+        `chunk`: steps per launch (the last chunk takes what remains), or a sequence of chunk lengths that sums to T.  The other
+        arguments are incremental_forward's.  Every item is the dict incremental_forward returns, restricted to the next chunk's steps:
+        idx (B,n) / x (B,n), logits (B,O,n) when asked for; concatenated along time the items are the one-shot result of the same
+        arguments bit for bit (wae_ar_desc.t0, include/wae.h: a launch with t0 > 0 continues from the history ring the earlier launches
+        left, where the reference keeps each conv's input window between calls, conv.py:17-62).
+        Opening the stream (this call) is the step incremental_forward opens with (_ar_open): what does not depend on the chunk, once --
+        the weight packing, the conditioning upsample of the whole `c` (the encoder side is not causal), the speaker projection, the
+        ring and -- where the caller passed none -- the random draws of all T steps, so that a seeded stream equals the seeded one-shot
+        call.  The kernel path (cooperative or one CU, C, ar_path() settings) is fixed there too.  Every chunk is then the launch
+        incremental_forward makes once for the whole clip (_ar_launch): the operands' time slices, the forced first input (the previous
+        chunk's last output, or the teacher-forced value), the chunk-relative n_forced, the zeroed exchange buffers and the time-out
+        check (one device read per chunk on the cooperative paths).  Closing the generator early is legal and frees the
+        state; nothing of it outlives the generator.  ValueError before any launch: modes "probs" / "raw" (their fed-back vector stays
+        on chip), ar_path(one_handover=True), a chunk < 1, chunk lengths that do not sum to T."""
+        if mode in ("probs", "raw"):
+            raise ValueError(f"incremental_stream: mode '{mode}' feeds a vector back that lives on chip; stream 'logits', 'argmax' or 'sample'")
+        if self.ar_one_handover:
+            raise ValueError("incremental_stream: the one-hand-over kernel (ar_path(one_handover=True)) cannot continue a decode")
+        T = int(T)
+        if isinstance(chunk, (int, np.integer)):
+            if int(chunk) < 1:
+                raise ValueError(f"incremental_stream: chunk {int(chunk)} < 1")
+            chunks = [min(int(chunk), T - t) for t in range(0, T, int(chunk))]
+        else:
+            chunks = [int(n) for n in chunk]
+            if not chunks or min(chunks) < 1:
+                raise ValueError("incremental_stream: every chunk has at least one step")
+            if sum(chunks) != T:
+                raise ValueError(f"incremental_stream: the chunk lengths sum to {sum(chunks)}, not to T = {T}")
+        s = self._ar_open(c, gid, T, mode=mode, test_inputs=test_inputs, uniforms=uniforms, init_idx=init_idx,
+                          c_is_upsampled=c_is_upsampled, want_logits=want_logits, gvec=gvec, u_mix=u_mix, u_log=u_log,
+                          log_scale_min=log_scale_min, clamp_log_scale=clamp_log_scale, n_forced=n_forced, z=z)
+        return self._ar_chunks(s, chunks)
+
+    def _ar_chunks(self, s, chunks):
+        """The launches of an open incremental_stream: chunk k runs steps [t0, t0 + n) with wae_ar_desc.t0 = t0."""
+        t0, mine = 0, None
+        try:
+            for n in chunks:
+                item = self._ar_launch(s, t0, n)
+                mine = self._ar_keep
+                t0 += n
+                yield item
+        finally:
+            if getattr(self, "_ar_keep", None) is mine:
+                self._ar_keep = None    # closed (early or at the end): the ring and the operands go with the generator
+
+    def _ar_open(self, c, gid, T, *, mode, test_inputs, uniforms, init_idx, c_is_upsampled, want_logits, gvec, u_mix, u_log,
+                 log_scale_min, clamp_log_scale, n_forced, z):
+        """What a decode of T steps fixes before its first launch, whatever its chunks (incremental_forward's arguments) -> the state
+        _ar_launch runs steps of: the packed weights, the start classes, the forced prefix, the upsampled conditioning, the speaker
+        rows, the kernel path, the zeroed ring, the draws of all T steps and the exchange buffers."""
+        g, lib, dev = self.g, self.lib, self.device
         if not getattr(self, "_ar_packed", False) or self.weights_dirty:
             self.pack_ar_weights()
         st = self.stream()
+        T = int(T)
         B = c.shape[0] if c is not None else (test_inputs.shape[0] if test_inputs is not None else 1)
         m = {"logits": 0, "argmax": 1, "sample": 2, "probs": 3, "raw": 4}[mode]
-        dev = self.device
         if not isinstance(init_idx, int) and not g.scalar_input:
             ii = torch.as_tensor(init_idx).reshape(-1).to("cpu", torch.int64)
             if ii.numel() == 1:
@@ -683,19 +778,16 @@ class WaeEngine:
                 if test_inputs is None:     # (forced steps override the start class anyway: wavenet.py:300-302)
                     test_inputs, n_forced = ii.to(dev, torch.int32).reshape(B, 1), 1
                 init_idx = int(ii[0])
+        nf = 0
         if test_inputs is not None:
             nf = int(test_inputs.shape[1]) if n_forced is None else int(n_forced)
             nf = max(0, min(nf, int(test_inputs.shape[1]), T))
-            if nf < T:                      # the kernels index inputs as (B, T)
-                pad = torch.zeros(test_inputs.shape[0], T, dtype=test_inputs.dtype, device=test_inputs.device)
-                pad[:, :nf] = test_inputs[:, :nf]
-                test_inputs = pad
             if nf == 0:
                 test_inputs = None
-        else:
-            nf = 0
         if m == 0 and nf < T:
             raise ValueError("mode 'logits' is teacher-forced: test_inputs must cover all T steps (use 'raw' to feed logits back)")
+        if g.scalar_input and m not in (0, 2):
+            raise ValueError("scalar-input decoders feed the drawn sample back: modes 'logits' and 'sample' only")
         c_up = None
         if g.Ccp:
             c_up = torch.zeros(B, T, g.Ccp, dtype=self.tdtype, device=dev)
@@ -722,13 +814,13 @@ class WaeEngine:
                 and (not g.scalar_input or (self.ar_scalar_coop and m in (0, 2))))
         C = max(1, min(self.opt.ar_coop_c, 32, g.H, g.S)) if coop else 1
         # zeros: the rows read as history before their first write (t - d, t - 2d of the first samples) are the causal pad; the
-        # cooperative kernel zero-fills its ring itself, but only when its members share an XCD (round-5 advisor finding)
+        # cooperative kernel zero-fills its ring itself, but only when its members share an XCD (round-5 advisor finding).  Every
+        # launch of the decode continues in it.
         ring = torch.zeros(B * C * self.ar_ring_total, dtype=torch.float32, device=dev)
+        normal = g.scalar_input and g.output_distribution == "Normal"
+        uni = um = draw = None
         if g.scalar_input:
-            es = self.ar_w.element_size()
-            normal = g.output_distribution == "Normal"
             M = 1 if (normal and g.O == 2) else g.O // 3
-            tf = test_inputs.to(dev, torch.float32).contiguous() if test_inputs is not None else None
             if normal:
                 if u_log is not None:
                     raise ValueError("output_distribution 'Normal' draws from u_mix and z, not u_log")
@@ -741,286 +833,94 @@ class WaeEngine:
             elif m == 2 and u_mix is None:
                 u_mix = torch.rand(B, T, M, device=dev) * (1 - 2e-5) + 1e-5          # mixture.py:138,151
                 u_log = torch.rand(B, T, device=dev) * (1 - 2e-5) + 1e-5
-            um = u_mix.to(dev, torch.float32).contiguous() if u_mix is not None else None
-            zn = z.to(dev, torch.float32).contiguous() if z is not None else None
-            ul = u_log.to(dev, torch.float32).contiguous() if u_log is not None else None
-            if m == 0 and tf is None:
-                raise ValueError("mode 'logits' needs test_inputs")
-            xs = torch.empty(B, T, dtype=torch.float32, device=dev) if (zn if normal else um) is not None else None
-            params = torch.empty(B, g.O, T, dtype=torch.float32, device=dev) if (want_logits or m == 0) else None
-            if m >= 3:
-                raise ValueError("scalar-input decoders feed the drawn sample back: modes 'logits' and 'sample' only")
-            d = L.ArDesc(self.dt, B, T, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, 0, 1,
-                         math.sqrt(1.0 / g.layers), nf)
-            if coop:
-                nv = lib.wae_ar_coop_msg_values(ctypes.byref(d), C)
-                msg = torch.zeros(B * 2 * C * nv, dtype=torch.int64, device=dev)
-                acc = torch.zeros(B * lib.wae_ar_coop_acc_floats(ctypes.byref(d)), dtype=torch.float32, device=dev)
-                err = torch.zeros(64, dtype=torch.int32, device=dev)   # [0] = time-out flag, as for class ids
-                L.check(lib.wae_ar_generate_coop_scalar(ctypes.byref(d), C, 1 if normal else 0, L.ptr(self.ar_dil), L.ptr(self.ar_ring_off),
-                                                        L.ptr(ring), self.ar_ring_total, L.ptr(self.ar_w), self.ar_layer_elems * es,
-                                                        self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(zb), L.ptr(self.first_tab),
-                                                        L.ptr(self.first_bias), L.ptr(self.ar_wh), L.ptr(self.ar_hb), L.ptr(c_up), self.dt,
-                                                        L.ptr(tf), L.ptr(um), L.ptr(zn if normal else ul), float(log_scale_min),
-                                                        int(bool(clamp_log_scale)), L.ptr(xs), L.ptr(params), L.ptr(msg), L.ptr(acc),
-                                                        L.ptr(err), st), "ar_generate_coop_scalar")
-                self._ar_profile = err
-                if int(err[0].item()) != 0:  # synchronises, as the class-id path does
-                    raise L.WaeError("ar_generate_coop: an exchange between the cooperating workgroups timed out")
-            elif normal:
-                L.check(lib.wae_ar_generate_scalar_mog(ctypes.byref(d), L.ptr(self.ar_dil), L.ptr(self.ar_ring_off), L.ptr(ring),
-                                                       self.ar_ring_total, L.ptr(self.ar_w), self.ar_layer_elems * es,
-                                                       self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(zb), L.ptr(self.first_tab),
-                                                       L.ptr(self.first_bias), L.ptr(self.ar_wh), L.ptr(self.ar_hb), L.ptr(c_up), self.dt,
-                                                       L.ptr(tf), L.ptr(um), L.ptr(zn), float(log_scale_min), L.ptr(xs), L.ptr(params),
-                                                       st), "ar_generate_scalar_mog")
-            else:
-                L.check(lib.wae_ar_generate_scalar(ctypes.byref(d), L.ptr(self.ar_dil), L.ptr(self.ar_ring_off), L.ptr(ring),
-                                                   self.ar_ring_total, L.ptr(self.ar_w), self.ar_layer_elems * es, self.ar_w2_off * es,
-                                                   L.ptr(self.ar_b2), L.ptr(zb), L.ptr(self.first_tab), L.ptr(self.first_bias),
-                                                   L.ptr(self.ar_wh), L.ptr(self.ar_hb), L.ptr(c_up), self.dt,
-                                                   L.ptr(tf), L.ptr(um), L.ptr(ul), float(log_scale_min),
-                                                   int(bool(clamp_log_scale)), L.ptr(xs), L.ptr(params), st), "ar_generate_scalar")
-            self._ar_keep = (c_up, zb, ring, tf, um, ul, zn, gid32)
-            return dict(x=xs, logits=params)
-        inputs = test_inputs.to(torch.int32).contiguous() if test_inputs is not None else None
-        if inputs is None and not 0 <= int(init_idx) < g.O:
-            # wavenet.py:288 writes a one at class 127 of the start vector: the same IndexError when there are fewer classes
-            raise IndexError(f"index {int(init_idx)} is out of bounds for dimension 2 with size {g.O}")
-        if m == 2 and uniforms is None:
-            uniforms = torch.rand(B, T, device=dev)
-        uni = uniforms.float().contiguous() if uniforms is not None else None
-        out_idx = torch.empty(B, T, dtype=torch.int32, device=dev)
-        logits = torch.empty(B, g.O, T, dtype=torch.float32, device=dev) if (want_logits or m == 0 or m >= 3) else None
-        es = self.ar_w.element_size()
-        d = L.ArDesc(self.dt, B, T, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, int(init_idx), 0,
-                     math.sqrt(1.0 / g.layers), nf, int(self.ar_generic), self.ar_resident[0], self.ar_resident[1])
-        if coop:
-            nv = lib.wae_ar_coop_msg_values(ctypes.byref(d), C)
-            msg = torch.zeros(B * 2 * C * nv, dtype=torch.int64, device=dev)
-            acc = torch.zeros(B * lib.wae_ar_coop_acc_floats(ctypes.byref(d)), dtype=torch.float32, device=dev)
-            err = torch.zeros(64, dtype=torch.int32, device=dev)   # [0] = time-out flag; the rest: profile counters of a -DWAE_ARC_PROFILE build
-            L.check(lib.wae_ar_generate_coop_fused(ctypes.byref(d), C, L.ptr(self.ar_dil), L.ptr(self.ar_ring_off), L.ptr(ring),
-                                                   self.ar_ring_total, L.ptr(self.ar_w), self.ar_layer_elems * es, self.ar_w2_off * es,
-                                                   L.ptr(self.ar_b2), L.ptr(zb), L.ptr(self.first_tab), L.ptr(self.first_bias),
-                                                   L.ptr(self.ar_wh), L.ptr(self.ar_hb), L.ptr(c_up), self.dt, L.ptr(inputs),
-                                                   L.ptr(uni), L.ptr(out_idx), L.ptr(logits), L.ptr(msg), L.ptr(acc), L.ptr(err),
-                                                   L.ptr(getattr(self, "ar_wm", None) if self.ar_one_handover else None), st),
-                    "ar_generate_coop")
-            self._ar_profile = err
-            if int(err[0].item()) != 0:  # synchronises: generation is a blocking call for its callers anyway
-                raise L.WaeError("ar_generate_coop: an exchange between the cooperating workgroups timed out")
-        else:
-            L.check(lib.wae_ar_generate(ctypes.byref(d), L.ptr(self.ar_dil), L.ptr(self.ar_ring_off), L.ptr(ring), self.ar_ring_total,
-                                        L.ptr(self.ar_w), self.ar_layer_elems * es, self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(zb),
-                                        L.ptr(self.first_tab), L.ptr(self.first_bias), L.ptr(self.ar_wh), L.ptr(self.ar_hb),
-                                        L.ptr(c_up), self.dt, L.ptr(inputs), L.ptr(uni), L.ptr(out_idx), L.ptr(logits), st),
-                    "ar_generate")
-        self._ar_keep = (c_up, zb, ring, inputs, uni, gid32)   # keep device buffers alive until the stream has run
-        return dict(idx=out_idx, logits=logits)
-
-    def incremental_stream(self, c: Optional[torch.Tensor], gid: Optional[torch.Tensor], T: int, chunk, mode: str = "sample",
-                           test_inputs: Optional[torch.Tensor] = None, uniforms: Optional[torch.Tensor] = None,
-                           init_idx: int = 127, c_is_upsampled: bool = False, want_logits: bool = False,
-                           gvec: Optional[torch.Tensor] = None, u_mix: Optional[torch.Tensor] = None,
-                           u_log: Optional[torch.Tensor] = None, log_scale_min: float = -7.0, clamp_log_scale: bool = False,
-                           n_forced: Optional[int] = None, z: Optional[torch.Tensor] = None):
-        """incremental_forward in resumable launches: a generator over the clip's chunks.
-
-        `chunk`: steps per launch (the last chunk takes what remains), or a sequence of chunk lengths that sums to T.  The other
-        arguments are incremental_forward's.  Every item is the dict incremental_forward returns, restricted to the next chunk's steps:
-        idx (B,n) / x (B,n), logits (B,O,n) when asked for; concatenated along time the items are the one-shot result of the same
-        arguments bit for bit (wae_ar_desc.t0, include/wae.h: a launch with t0 > 0 continues from the history ring the earlier launches
-        left, where the reference keeps each conv's input window between calls, conv.py:17-62).
-        Opening the stream (this call) does what does not depend on the chunk, once: the weight packing, the conditioning upsample of
-        the whole `c` (the encoder side is not causal), the speaker projection, the ring and -- where the caller passed none -- the
-        random draws of all T steps, in incremental_forward's order, so that a seeded stream equals the seeded one-shot call.  The kernel
-        path (cooperative or one CU, C, ar_path() settings) is fixed there too.  Per chunk: the operands' time slices, the forced first
-        input (the previous chunk's last output, or the teacher-forced value), the chunk-relative n_forced, the zeroed exchange buffers
-        and the time-out check (one device read per chunk on the cooperative paths).  Closing the generator early is legal and frees the
-        state; nothing of it outlives the generator.  ValueError before any launch: modes "probs" / "raw" (their fed-back vector stays
-        on chip), ar_path(one_handover=True), a chunk < 1, chunk lengths that do not sum to T."""
-        g, lib = self.g, self.lib
-        if mode in ("probs", "raw"):
-            raise ValueError(f"incremental_stream: mode '{mode}' feeds a vector back that lives on chip; stream 'logits', 'argmax' or 'sample'")
-        if self.ar_one_handover:
-            raise ValueError("incremental_stream: the one-hand-over kernel (ar_path(one_handover=True)) cannot continue a decode")
-        T = int(T)
-        if isinstance(chunk, (int, np.integer)):
-            if int(chunk) < 1:
-                raise ValueError(f"incremental_stream: chunk {int(chunk)} < 1")
-            chunks = [min(int(chunk), T - t) for t in range(0, T, int(chunk))]
-        else:
-            chunks = [int(n) for n in chunk]
-            if not chunks or min(chunks) < 1:
-                raise ValueError("incremental_stream: every chunk has at least one step")
-            if sum(chunks) != T:
-                raise ValueError(f"incremental_stream: the chunk lengths sum to {sum(chunks)}, not to T = {T}")
-        m = {"logits": 0, "argmax": 1, "sample": 2}[mode]
-        if not getattr(self, "_ar_packed", False) or self.weights_dirty:
-            self.pack_ar_weights()
-        st = self.stream()
-        B = c.shape[0] if c is not None else (test_inputs.shape[0] if test_inputs is not None else 1)
-        dev = self.device
-        # ---- incremental_forward's argument handling, unchanged: start classes, the forced prefix, conditioning, speaker rows ----------
-        if not isinstance(init_idx, int) and not g.scalar_input:
-            ii = torch.as_tensor(init_idx).reshape(-1).to("cpu", torch.int64)
-            if ii.numel() == 1:
-                init_idx = int(ii[0])
-            else:
-                if ii.numel() != B:
-                    raise ValueError(f"init_idx: {ii.numel()} start classes for {B} utterances")
-                if int(ii.min()) < 0 or int(ii.max()) >= g.O:
-                    raise IndexError(f"index {int(ii.max() if ii.max() >= g.O else ii.min())} is out of bounds for dimension 2 with size {g.O}")
-                if test_inputs is None:
-                    test_inputs, n_forced = ii.to(dev, torch.int32).reshape(B, 1), 1
-                init_idx = int(ii[0])
-        if test_inputs is not None:
-            nf = int(test_inputs.shape[1]) if n_forced is None else int(n_forced)
-            nf = max(0, min(nf, int(test_inputs.shape[1]), T))
-            if nf == 0:
-                test_inputs = None
-        else:
-            nf = 0
-        if m == 0 and nf < T:
-            raise ValueError("mode 'logits' is teacher-forced: test_inputs must cover all T steps")
-        if g.scalar_input and m == 1:
-            raise ValueError("scalar-input decoders feed the drawn sample back: modes 'logits' and 'sample' only")
-        c_up = None
-        if g.Ccp:
-            c_up = torch.zeros(B, T, g.Ccp, dtype=self.tdtype, device=dev)
-            if c_is_upsampled or not g.upsample_scales:
-                assert c.shape[-1] == T, f"c {tuple(c.shape)} != T {T}"
-                L.check(lib.wae_to_btc(L.ptr(c.contiguous().float()), L.ptr(c_up), B, g.Cc, T, g.Ccp, self.dt, st), "to_btc")
-            else:
-                assert (c.shape[-1] - 2 * g.cin_pad) * int(np.prod(g.upsample_scales)) == T, "c does not upsample to T"
-                self.upsample_forward(c.float(), c_up)
-        zb = torch.empty(B, g.layers, 2 * g.Hp, dtype=torch.float32, device=dev)
-        wg_off = self.lay.off("wavenet.conv_layers.0.conv1x1g.weight_v") if g.Cg > 0 else -1
-        emb_off = self.lay.offsets.get("wavenet.embed_speakers.weight", 0)
-        use_gid = gid is not None and "wavenet.embed_speakers.weight" in self.lay.offsets
-        gid32 = gid.to(torch.int32).contiguous() if gid is not None else None
-        L.check(lib.wae_gproj_fwd(L.ptr(self.eff), wg_off if (gid is not None or gvec is not None) else -1,
-                                  self.lay.off("wavenet.conv_layers.0.conv.bias"), self.lay.layer_stride,
-                                  L.ptr(gid32) if use_gid else None, emb_off, L.ptr(gvec) if gvec is not None else None,
-                                  L.ptr(zb), B, g.layers, g.G, g.Hp, max(g.Cg, 0), int(g.n_speakers or 0), L.ptr(self.err), st),
-                "gproj")
-        coop = (B <= 8 and g.R <= 256 and g.S <= 256 and g.O <= 256 and m <= 2 and self.opt.ar_coop
-                and (not g.scalar_input or (self.ar_scalar_coop and m in (0, 2))))
-        C = max(1, min(self.opt.ar_coop_c, 32, g.H, g.S)) if coop else 1
-        ring = torch.zeros(B * C * self.ar_ring_total, dtype=torch.float32, device=dev)     # the stream's state: every launch continues in it
-        normal = g.scalar_input and g.output_distribution == "Normal"
-        M = (1 if (normal and g.O == 2) else g.O // 3) if g.scalar_input else 0
-        if g.scalar_input:
-            if normal:
-                if u_log is not None:
-                    raise ValueError("output_distribution 'Normal' draws from u_mix and z, not u_log")
-                if m == 2 and z is None:
-                    u_mix = torch.rand(B, T, M, device=dev) * (1 - 2e-5) + 1e-5 if M > 1 else None
-                    z = torch.randn(B, T, device=dev)
-            elif z is not None:
-                raise ValueError("output_distribution 'Logistic' draws from u_mix and u_log, not z")
-            elif m == 2 and u_mix is None:
-                u_mix = torch.rand(B, T, M, device=dev) * (1 - 2e-5) + 1e-5
-                u_log = torch.rand(B, T, device=dev) * (1 - 2e-5) + 1e-5
             forced = test_inputs.to(dev, torch.float32).contiguous() if test_inputs is not None else None
             um = u_mix.to(dev, torch.float32).contiguous() if u_mix is not None else None
             draw = z if normal else u_log
             draw = draw.to(dev, torch.float32).contiguous() if draw is not None else None
-            uni = None
             sampled = (draw if normal else um) is not None
+            init_idx, path = 0, (0, 0, 0)
         else:
             forced = test_inputs.to(dev, torch.int32).contiguous() if test_inputs is not None else None
             if forced is None and not 0 <= int(init_idx) < g.O:
+                # wavenet.py:288 writes a one at class 127 of the start vector: the same IndexError when there are fewer classes
                 raise IndexError(f"index {int(init_idx)} is out of bounds for dimension 2 with size {g.O}")
             if m == 2 and uniforms is None:
                 uniforms = torch.rand(B, T, device=dev)
             uni = uniforms.to(dev).float().contiguous() if uniforms is not None else None
-            um = draw = None
             sampled = True
-        want = want_logits or m == 0
-        es = self.ar_w.element_size()
-        path = (int(self.ar_generic), self.ar_resident[0], self.ar_resident[1])
+            path = (int(self.ar_generic), self.ar_resident[0], self.ar_resident[1])
+        d = L.ArDesc(self.dt, B, T, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, int(init_idx),
+                     int(g.scalar_input), math.sqrt(1.0 / g.layers), nf, *path)
         msg = acc = err = None
         if coop:
-            d0 = L.ArDesc(self.dt, B, T, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, 0, int(g.scalar_input))
-            nv = lib.wae_ar_coop_msg_values(ctypes.byref(d0), C)
+            nv = lib.wae_ar_coop_msg_values(ctypes.byref(d), C)
             msg = torch.empty(B * 2 * C * nv, dtype=torch.int64, device=dev)
-            acc = torch.empty(B * lib.wae_ar_coop_acc_floats(ctypes.byref(d0)), dtype=torch.float32, device=dev)
-            err = torch.empty(64, dtype=torch.int32, device=dev)
-        return self._ar_stream_chunks(chunks, B, T, m, C, coop, normal, sampled, want, nf, forced, init_idx, c_up, zb, ring, uni, um, draw,
-                                      float(log_scale_min), int(bool(clamp_log_scale)), path, msg, acc, err, es, gid32)
+            acc = torch.empty(B * lib.wae_ar_coop_acc_floats(ctypes.byref(d)), dtype=torch.float32, device=dev)
+            err = torch.empty(64, dtype=torch.int32, device=dev)   # [0] = time-out flag; the rest: profile counters of a -DWAE_ARC_PROFILE build
+        return _ArDecode(d=d, n_forced=nf, forced=forced, c_up=c_up, zb=zb, gid32=gid32, coop=coop, C=C, ring=ring, normal=normal,
+                         uni=uni, u_mix=um, draw=draw, sampled=sampled, want=want_logits or m == 0 or m >= 3,
+                         log_scale_min=float(log_scale_min), clamp=int(bool(clamp_log_scale)),
+                         w_fused=self.ar_wm if self.ar_one_handover else None, msg=msg, acc=acc, err=err)
 
-    def _ar_stream_chunks(self, chunks, B, T, m, C, coop, normal, sampled, want, nf, forced, init_idx, c_up, zb, ring, uni, um, draw,
-                          log_scale_min, clamp, path, msg, acc, err, es, gid32):
-        """The launches of an open incremental_stream: chunk k runs steps [t0, t0 + n) with wae_ar_desc.t0 = t0."""
-        g, lib, dev = self.g, self.lib, self.device
-        sl = lambda a, t0, n: None if a is None else a[:, t0:t0 + n].contiguous()  # noqa: E731  (B == 1: the slice itself, no copy)
-        last = None                     # (B,) the previous chunk's last output: the forced first input of a chunk past the forced prefix
-        t0, mine = 0, None
-        try:
-            for n in chunks:
-                st = self.stream()
-                k = max(0, min(n, nf - t0))             # steps of this chunk that the caller's inputs force
-                if k > 0 or t0 > 0:
-                    if k == n:
-                        inp = sl(forced, t0, n)
-                    else:
-                        inp = torch.zeros(B, n, dtype=torch.float32 if g.scalar_input else torch.int32, device=dev)
-                        if k > 0:
-                            inp[:, :k] = forced[:, t0:t0 + k]
-                        else:
-                            inp[:, 0] = last
-                    nfc = max(1, k)
+    def _ar_launch(self, s, t0, n):
+        """Steps [t0, t0 + n) of the decode `s` (_ar_open) as one launch -> the dict incremental_forward returns, for those steps."""
+        g, lib, dev, d, st = self.g, self.lib, self.device, s.d, self.stream()
+        sl = lambda a: None if a is None else a[:, t0:t0 + n].contiguous()  # noqa: E731  (B == 1 or the whole clip: the slice itself, no copy)
+        k = max(0, min(n, s.n_forced - t0))         # steps of this launch that the caller's inputs force
+        if k > 0 or t0 > 0:
+            if k == n:
+                inp = sl(s.forced)
+            else:                                   # the kernels index inputs as (B, n)
+                inp = torch.zeros(d.B, n, dtype=torch.float32 if g.scalar_input else torch.int32, device=dev)
+                if k > 0:
+                    inp[:, :k] = s.forced[:, t0:t0 + k]
                 else:
-                    inp, nfc = None, 0
-                cu = sl(c_up, t0, n)
-                d = L.ArDesc(self.dt, B, n, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m,
-                             0 if g.scalar_input else int(init_idx), int(g.scalar_input), math.sqrt(1.0 / g.layers), nfc,
-                             0 if g.scalar_input else path[0], 0 if g.scalar_input else path[1], 0 if g.scalar_input else path[2], t0)
-                logits = torch.empty(B, g.O, n, dtype=torch.float32, device=dev) if want else None
-                if coop:
-                    msg.zero_()
-                    acc.zero_()
-                    err.zero_()
-                common = (L.ptr(self.ar_dil), L.ptr(self.ar_ring_off), L.ptr(ring), self.ar_ring_total, L.ptr(self.ar_w),
-                          self.ar_layer_elems * es, self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(zb), L.ptr(self.first_tab),
-                          L.ptr(self.first_bias), L.ptr(self.ar_wh), L.ptr(self.ar_hb), L.ptr(cu), self.dt, L.ptr(inp))
-                if g.scalar_input:
-                    umc, dc = sl(um, t0, n), sl(draw, t0, n)
-                    xs = torch.empty(B, n, dtype=torch.float32, device=dev) if sampled else None
-                    if coop:
-                        L.check(lib.wae_ar_generate_coop_scalar(ctypes.byref(d), C, 1 if normal else 0, *common, L.ptr(umc), L.ptr(dc),
-                                                                log_scale_min, clamp, L.ptr(xs), L.ptr(logits), L.ptr(msg), L.ptr(acc),
-                                                                L.ptr(err), st), "ar_generate_coop_scalar")
-                    elif normal:
-                        L.check(lib.wae_ar_generate_scalar_mog(ctypes.byref(d), *common, L.ptr(umc), L.ptr(dc), log_scale_min, L.ptr(xs),
-                                                               L.ptr(logits), st), "ar_generate_scalar_mog")
-                    else:
-                        L.check(lib.wae_ar_generate_scalar(ctypes.byref(d), *common, L.ptr(umc), L.ptr(dc), log_scale_min, clamp,
-                                                           L.ptr(xs), L.ptr(logits), st), "ar_generate_scalar")
-                    item, keep = dict(x=xs, logits=logits), (cu, inp, umc, dc)
-                    last = xs[:, -1] if xs is not None else None
-                else:
-                    uc = sl(uni, t0, n)
-                    out_idx = torch.empty(B, n, dtype=torch.int32, device=dev)
-                    if coop:
-                        L.check(lib.wae_ar_generate_coop_fused(ctypes.byref(d), C, *common, L.ptr(uc), L.ptr(out_idx), L.ptr(logits),
-                                                               L.ptr(msg), L.ptr(acc), L.ptr(err), None, st), "ar_generate_coop")
-                    else:
-                        L.check(lib.wae_ar_generate(ctypes.byref(d), *common, L.ptr(uc), L.ptr(out_idx), L.ptr(logits), st), "ar_generate")
-                    item, keep = dict(idx=out_idx, logits=logits), (cu, inp, uc)
-                    last = out_idx[:, -1]
-                if coop:
-                    self._ar_profile = err
-                    if int(err[0].item()) != 0:      # synchronises once per chunk
-                        raise L.WaeError("ar_generate_coop: an exchange between the cooperating workgroups timed out")
-                mine = self._ar_keep = (c_up, zb, ring, gid32) + keep      # the launch's operands live until the stream has run
-                t0 += n
-                yield item
-        finally:
-            if getattr(self, "_ar_keep", None) is mine:
-                self._ar_keep = None    # closed (early or at the end): the ring and the operands go with the generator
+                    inp[:, 0] = s.last              # past the forced prefix a continuation starts from the previous launch's last output
+            d.n_forced = max(1, k)
+        else:
+            inp, d.n_forced = None, 0
+        d.T, d.t0 = n, t0
+        cu = sl(s.c_up)
+        logits = torch.empty(d.B, g.O, n, dtype=torch.float32, device=dev) if s.want else None
+        if s.coop:
+            s.msg.zero_()
+            s.acc.zero_()
+            s.err.zero_()
+        es = self.ar_w.element_size()
+        common = (L.ptr(self.ar_dil), L.ptr(self.ar_ring_off), L.ptr(s.ring), self.ar_ring_total, L.ptr(self.ar_w),
+                  self.ar_layer_elems * es, self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(s.zb), L.ptr(self.first_tab),
+                  L.ptr(self.first_bias), L.ptr(self.ar_wh), L.ptr(self.ar_hb), L.ptr(cu), self.dt, L.ptr(inp))
+        if g.scalar_input:
+            um, dr = sl(s.u_mix), sl(s.draw)
+            xs = torch.empty(d.B, n, dtype=torch.float32, device=dev) if s.sampled else None
+            if s.coop:
+                L.check(lib.wae_ar_generate_coop_scalar(ctypes.byref(d), s.C, int(s.normal), *common, L.ptr(um), L.ptr(dr),
+                                                        s.log_scale_min, s.clamp, L.ptr(xs), L.ptr(logits), L.ptr(s.msg), L.ptr(s.acc),
+                                                        L.ptr(s.err), st), "ar_generate_coop_scalar")
+            elif s.normal:
+                L.check(lib.wae_ar_generate_scalar_mog(ctypes.byref(d), *common, L.ptr(um), L.ptr(dr), s.log_scale_min, L.ptr(xs),
+                                                       L.ptr(logits), st), "ar_generate_scalar_mog")
+            else:
+                L.check(lib.wae_ar_generate_scalar(ctypes.byref(d), *common, L.ptr(um), L.ptr(dr), s.log_scale_min, s.clamp,
+                                                   L.ptr(xs), L.ptr(logits), st), "ar_generate_scalar")
+            item, keep = dict(x=xs, logits=logits), (um, dr)
+            s.last = xs[:, -1] if xs is not None else None
+        else:
+            uc = sl(s.uni)
+            out_idx = torch.empty(d.B, n, dtype=torch.int32, device=dev)
+            if s.coop:
+                L.check(lib.wae_ar_generate_coop_fused(ctypes.byref(d), s.C, *common, L.ptr(uc), L.ptr(out_idx), L.ptr(logits),
+                                                       L.ptr(s.msg), L.ptr(s.acc), L.ptr(s.err), L.ptr(s.w_fused), st), "ar_generate_coop")
+            else:
+                L.check(lib.wae_ar_generate(ctypes.byref(d), *common, L.ptr(uc), L.ptr(out_idx), L.ptr(logits), st), "ar_generate")
+            item, keep = dict(idx=out_idx, logits=logits), (uc,)
+            s.last = out_idx[:, -1]
+        if s.coop:
+            self._ar_profile = s.err
+            if int(s.err[0].item()) != 0:       # synchronises, once per launch: generation is a blocking call for its callers anyway
+                raise L.WaeError("ar_generate_coop: an exchange between the cooperating workgroups timed out")
+        self._ar_keep = (s, cu, inp) + keep     # the launch's operands (and the decode's: ring, zb, ...) live until the stream has run
+        return item
 
     # ------------------------------------------------------------------ full autoencoder
     def forward(self, x: torch.Tensor, c: torch.Tensor, gid: Optional[torch.Tensor], targets=None, lengths=None,

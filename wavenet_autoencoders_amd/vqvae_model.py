@@ -6,7 +6,7 @@ import torch
 
 from . import packing as P
 from .wavenet_vocoder._base import ArenaModel
-from .wavenet_vocoder.wavenet import WaveNet, _ids_from_input, softmax_bct
+from .wavenet_vocoder.wavenet import WaveNet, _ids_from_input, _start_classes, softmax_bct, stream_post
 
 
 class _VQVAEFn(torch.autograd.Function):
@@ -82,63 +82,40 @@ class VQVAE(ArenaModel):
 
     def incremental_forward(self, initial_input, c, g, T, softmax, quantize, tqdm, log_scale_min):
         """encoder -> VQ -> autoregressive decoder (vqvae_model.py:73-79)."""
-        eng = self.engine()
+        eng, args, kw, post = self._incremental_plan(initial_input, c, g, T, softmax, quantize, log_scale_min)
         with torch.no_grad():
-            if eng.weights_dirty:
-                eng.prepare_weights()
-            lat = eng.encoder_forward(c.float())
-            quant, idx, stats = eng.vq_forward(lat)
-            from .wavenet_vocoder.wavenet import _start_classes
-            init = 127 if self.scalar_input else _start_classes(initial_input, self.out_channels, eng)     # one start class per utterance
-            gid = g.reshape(-1) if g is not None else None
-            if self.scalar_input:
-                # the draws of the model's output distribution (wavenet.py:325-333): engine.incremental_forward makes them
-                out = eng.incremental_forward(quant, gid, int(T), mode="sample", log_scale_min=log_scale_min)
-                return out["x"].unsqueeze(1)
-            if quantize:
-                if not softmax:
-                    raise ValueError("quantize=True draws from the softmax probabilities: pass softmax=True")
-                out = eng.incremental_forward(quant, gid, int(T), mode="sample", init_idx=init)
-                idxs = out["idx"].long()
-                return torch.nn.functional.one_hot(idxs, self.out_channels).float().transpose(1, 2).contiguous()
-            # quantize=False: the probability / logit rows are the outputs and the fed-back inputs (wavenet.py:303-305,335-338)
-            return eng.incremental_forward(quant, gid, int(T), mode="probs" if softmax else "raw", init_idx=init)["logits"]
+            return post(eng.incremental_forward(*args, **kw))
 
     def incremental_stream(self, initial_input, c, g, T, softmax, quantize, tqdm, log_scale_min, chunk=1600):
         """incremental_forward in resumable launches: the encoder and the quantiser run once, on the whole `c` (they are not causal),
         then the decoder yields what incremental_forward returns `chunk` steps at a time (an int, or a sequence of chunk lengths
         summing to T; engine.incremental_stream) -- the same one-hot (B, C, n) / scalar (B, 1, n) shapes, the same bits given the same
         draws.  quantize=False feeds a vector back that stays on chip: ValueError."""
+        eng, args, kw, post = self._incremental_plan(initial_input, c, g, T, softmax, quantize, log_scale_min)
+        with torch.no_grad():
+            return stream_post(eng.incremental_stream(*args, chunk, **kw), post)
+
+    def _incremental_plan(self, initial_input, c, g, T, softmax, quantize, log_scale_min):
+        """Encoder, quantiser and start classes, once; then as WaveNet._incremental_plan: (engine, (quant, gid, T), keyword arguments,
+        post) with post: the engine's result dict (of the clip or of a chunk) -> the tensor the reference returns."""
         eng = self.engine()
         with torch.no_grad():
             if eng.weights_dirty:
                 eng.prepare_weights()
             lat = eng.encoder_forward(c.float())
             quant, idx, stats = eng.vq_forward(lat)
-            from .wavenet_vocoder.wavenet import _start_classes
-            init = 127 if self.scalar_input else _start_classes(initial_input, self.out_channels, eng)
-            gid = g.reshape(-1) if g is not None else None
-            if self.scalar_input:
-                items = eng.incremental_stream(quant, gid, int(T), chunk, mode="sample", log_scale_min=log_scale_min)
-                post = lambda out: out["x"].unsqueeze(1)  # noqa: E731
-            elif quantize:
-                if not softmax:
-                    raise ValueError("quantize=True draws from the softmax probabilities: pass softmax=True")
-                items = eng.incremental_stream(quant, gid, int(T), chunk, mode="sample", init_idx=init)
-                post = lambda out: torch.nn.functional.one_hot(out["idx"].long(), self.out_channels).float().transpose(1, 2).contiguous()  # noqa: E731
-            else:
-                items = eng.incremental_stream(quant, gid, int(T), chunk, mode="probs" if softmax else "raw", init_idx=init)
-                post = lambda out: out["logits"]  # noqa: E731
-
-        def run():
-            try:
-                for item in items:
-                    with torch.no_grad():
-                        out = post(item)
-                    yield out
-            finally:
-                items.close()
-        return run()
+            init = 127 if self.scalar_input else _start_classes(initial_input, self.out_channels, eng)     # one start class per utterance
+        args = (quant, g.reshape(-1) if g is not None else None, int(T))
+        if self.scalar_input:
+            # the draws of the model's output distribution (wavenet.py:325-333): engine.incremental_forward makes them
+            return eng, args, dict(mode="sample", log_scale_min=log_scale_min), lambda out: out["x"].unsqueeze(1)
+        if quantize:
+            if not softmax:
+                raise ValueError("quantize=True draws from the softmax probabilities: pass softmax=True")
+            return eng, args, dict(mode="sample", init_idx=init), lambda out: torch.nn.functional.one_hot(
+                out["idx"].long(), self.out_channels).float().transpose(1, 2).contiguous()
+        # quantize=False: the probability / logit rows are the outputs and the fed-back inputs (wavenet.py:303-305,335-338)
+        return eng, args, dict(mode="probs" if softmax else "raw", init_idx=init), lambda out: out["logits"]
 
     def encode(self, x):
         """quantised latents of MFCC features (vqvae_model.py:80-84; inference_2019.py:243-262)."""

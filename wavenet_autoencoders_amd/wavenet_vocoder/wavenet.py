@@ -52,6 +52,18 @@ def _start_classes(initial_input, out_channels, eng):
     return ids
 
 
+def stream_post(items, post):
+    """What the modules' incremental_stream returns: `post` (_incremental_plan) on every item of the engine's stream `items`; closing
+    it closes the engine's stream."""
+    try:
+        for item in items:
+            with torch.no_grad():
+                out = post(item)
+            yield out
+    finally:
+        items.close()
+
+
 class _DecoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, ids, c, g, c_is_up, train, *params):
@@ -207,17 +219,7 @@ class WaveNet(ArenaModel):
         mode feeds a vector back that stays on chip: ValueError."""
         eng, args, kw, post = self._incremental_plan(initial_input, c, g, T, test_inputs, softmax, quantize, log_scale_min)
         with torch.no_grad():
-            items = eng.incremental_stream(*args, chunk, **kw)
-
-        def run():
-            try:
-                for item in items:
-                    with torch.no_grad():
-                        out = post(item)
-                    yield out
-            finally:
-                items.close()
-        return run()
+            return stream_post(eng.incremental_stream(*args, chunk, **kw), post)
 
     def _incremental_plan(self, initial_input, c, g, T, test_inputs, softmax, quantize, log_scale_min):
         """The engine call behind incremental_forward / incremental_stream: (engine, (c, gid, T), keyword arguments, post) with
