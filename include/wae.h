@@ -389,6 +389,34 @@ int wae_ar_generate_scalar_mog(const wae_ar_desc* d, const int32_t* dilations, c
                                const float* inputs_f, const float* u_mix, const float* z, float log_scale_min,
                                float* out_samples, float* out_params, void* stream);
 
+/* A work list of utterances of unequal lengths in ONE launch (csrc/ar_fwd.hip: ar_list_kernel): n_slots persistent workgroups, each
+ * running the one-CU kernel's per-utterance body (the same device function, so an item's results are wae_ar_generate's for that
+ * utterance alone, bit for bit, whichever slot decodes it and in whatever order).  A workgroup takes the next item index with one
+ * returning atomic add on `next` (one int32_t the caller zeroes before the launch), decodes that item to its end, and leaves when the
+ * index reaches n_items; no workgroup waits for another.  Items are taken in array order: put the longest first to keep the tail of
+ * the launch short.
+ * The per-step operands are packed item after item: c_up (total, Ccp), inputs / uniforms / out_idx (total), out_logits one (O, T)
+ * block per item at float offset off * O, with total = the sum of the items' T; item.off is the item's first step there (with
+ * off = b * T and row = b this is wae_ar_generate's (B, T) layout).  zb holds one (L, 2Hp) row per value of item.row (wae_gproj_fwd).
+ * ring: n_slots x ring_total floats, never zero-filled: a decode reads a history row only behind its own write of that row.
+ * item.n_forced: the first n_forced steps consume inputs[off + t] (clamped to [0, T]; 0, or inputs == NULL: the item starts from
+ * item.init_idx, which is clamped to a class); mode 0 forces every step.  d->B, d->T, d->n_forced and d->init_idx are not read.
+ * Class-id decoders in modes 0 / 1 / 2.  Refused before any launch: d->scalar_input and modes 3 / 4 (WAE_EUNSUPPORTED); t0 != 0,
+ * n_items < 1, n_slots < 1, NULL items or next, mode 0 without inputs, mode 2 without uniforms (WAE_EINVAL). */
+typedef struct wae_ar_item {
+  int64_t off;      /* first step of the item in the packed per-step operands */
+  int32_t T;        /* steps to decode (an item with T <= 0 is skipped) */
+  int32_t n_forced;
+  int32_t init_idx;
+  int32_t row;      /* the item's row of zb */
+} wae_ar_item;
+int wae_ar_generate_list(const wae_ar_desc* d, int32_t n_items, int32_t n_slots, const wae_ar_item* items, int32_t* next,
+                         const int32_t* dilations, const int64_t* ring_off, float* ring, int64_t ring_total,
+                         const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes, const float* bias2,
+                         const float* zb, const float* first_tab, const float* first_bias, const void* w_head,
+                         const float* head_bias, const void* c_up, int32_t c_dtype, const int32_t* inputs,
+                         const float* uniforms, int32_t* out_idx, float* out_logits, void* stream);
+
 /* The same decoding with ONE utterance spread over C cooperating workgroups / CUs (csrc/ar_coop.hip): every layer is
  * split by gate channels; the members all-reduce their shares of x' once per layer and of the skip vector once per
  * sample through `acc` (B x wae_ar_coop_acc_floats(d) floats), `msg` ((B, 2, C, NV) 8-byte granules, NV =

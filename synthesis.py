@@ -14,6 +14,10 @@ options:
     --stream-chunk=<N>       Decode in resumable launches of N samples (WaeEngine.incremental_stream) and post-process every chunk as
                              it arrives; prints the wall time to the first chunk of audio.  The wav written is the same file.
     --seed=<n>               torch.manual_seed(n) before decoding: the same draws, hence the same wav, from run to run.
+    --batch-decode           Read every pair of <syn_list> first and decode them all in one launch (WaeEngine.decode_list: one
+                             utterance per CU, the next one as soon as a CU is free) instead of one after another.  The wavs
+                             written are the same files (with --seed: byte for byte those of the loop on the one-CU kernel,
+                             WAE_AR_COOP=0).  Class-id ("mulaw-quantize") models; not with --stream-chunk.
 """
 import argparse
 import json
@@ -116,6 +120,50 @@ def wavegen(eng, length, c, g, initial_value=127, chunk=None, on_chunk=None):
     return np.concatenate(parts)
 
 
+def read_features(args, src):
+    """A source of <syn_list> -> (its path under the dump, file id, (Tc, D) features zero-padded to whole latent frames)
+    (synthesis.py:475-486)."""
+    if args.lan == "surprise":
+        src = "test/" + src
+    fid = src.split("_")[1]
+    path = f"{args.dump_root}/{src}/mfcc.norm.npy"
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"cant find con file in {path}")
+    c = np.load(path)
+    div = 100 // int(args.frame_rate)
+    if c.shape[0] % div != 0:
+        c = np.pad(c, [[0, div - c.shape[0] % div], [0, 0]], mode="constant", constant_values=0.0)
+    return src, fid, c
+
+
+def batch_decode(eng, args, pairs, sp2ind, out_dir):
+    """--batch-decode: the loop of main() with its decodes gathered into one WaeEngine.decode_list call.  Per pair, in the list's
+    order: the seed (if any), the encoder, the quantizer and the draws of all its samples -- the order in which the loop consumes
+    the generator -- then one launch for all pairs, then the loop's post-processing and file names."""
+    from scipy.io import wavfile
+    device = eng.device
+    if eng.weights_dirty:
+        eng.prepare_weights()
+    items, names = [], []
+    for src, tar in pairs:
+        src, fid, c = read_features(args, src)
+        if tar not in sp2ind:
+            raise KeyError(f"cant find sp {tar} in sp2ind {args.speaker2ind}")
+        length = c.shape[0] * int(args.up_factor)
+        if args.seed is not None:
+            torch.manual_seed(args.seed)
+        ct = torch.from_numpy(np.ascontiguousarray(c.T[None]).astype(np.float32)).to(device)
+        quant, _, _ = eng.vq_forward(eng.encoder_forward(ct))
+        items.append(dict(c=quant[0].clone(), gid=sp2ind[tar], T=length, init_idx=int(args.initial_value),
+                          uniforms=torch.rand(1, length, device=device)))
+        names.append(f"{out_dir}{tar}_{fid}.wav")
+    for out, res in zip(names, eng.decode_list(items, mode="sample")):
+        y = postprocess_indices(res["idx"].cpu().numpy(), hparams.quantize_channels, hparams.postprocess, hparams.global_gain_scale)
+        wavfile.write(out, hparams.sample_rate, y)
+        print("Finished! Check out {} for generated audio samples.".format(out), flush=True)
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     for a in ("dump_root", "checkpoint", "dst_dir", "syn_list", "speaker2ind", "lan", "up_factor", "frame_rate", "start_ind"):
@@ -128,7 +176,10 @@ def main(argv=None):
     ap.add_argument("--coop-scalar", action="store_true")
     ap.add_argument("--stream-chunk", type=int)
     ap.add_argument("--seed", type=int)
+    ap.add_argument("--batch-decode", action="store_true")
     args = ap.parse_args(argv)
+    if args.batch_decode and args.stream_chunk:
+        ap.error("--batch-decode decodes the whole list in one launch: it cannot be combined with --stream-chunk")
     if args.preset:
         with open(args.preset) as f:
             hparams.parse_json(f.read())
@@ -149,17 +200,10 @@ def main(argv=None):
     from scipy.io import wavfile
     out_dir = f"{args.dst_dir}2019/{args.lan}/test/"                                          # synthesis.py:521-522 (string concat)
     os.makedirs(out_dir, exist_ok=True)
+    if args.batch_decode:
+        return batch_decode(eng, args, pairs, sp2ind, out_dir)
     for src, tar in pairs:
-        if args.lan == "surprise":
-            src = "test/" + src                                                               # :475-476
-        fid = src.split("_")[1]                                                               # :478
-        path = f"{args.dump_root}/{src}/mfcc.norm.npy"
-        if not os.path.exists(path):
-            raise FileNotFoundError(f"cant find con file in {path}")
-        c = np.load(path)
-        div = 100 // int(args.frame_rate)                                                     # zero-pad to whole latent frames (:482-486)
-        if c.shape[0] % div != 0:
-            c = np.pad(c, [[0, div - c.shape[0] % div], [0, 0]], mode="constant", constant_values=0.0)
+        src, fid, c = read_features(args, src)
         if tar not in sp2ind:
             raise KeyError(f"cant find sp {tar} in sp2ind {args.speaker2ind}")
         length = c.shape[0] * up                                                              # overrides --length (:327-329)

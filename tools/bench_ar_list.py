@@ -1,0 +1,93 @@
+#!/usr/bin/env python
+"""Throughput of list decoding (WaeEngine.decode_list): hps/vqwae.json's decoder on a work list of unequal lengths.
+
+usage: bench_ar_list.py [--items N] [--dtypes bf16,fp32] [--slots cu[,2cu,N...]] [--loop K] [--min-len 8000] [--max-len 64000]
+    --items N     clips in the list (default 512); lengths are drawn with numpy.random.default_rng(1234), uniform in
+                  [--min-len, --max-len] samples, and rounded to whole latent frames (640 samples: the conditioning is upsampled per clip)
+    --dtypes      storage types to run (default bf16,fp32)
+    --slots       workgroups to launch, one run each: "cu" = the device's CU count (decode_list's default), "2cu" twice that, or a number
+    --loop K      also decode the first K clips one after another with incremental_forward (what synthesis.py does without
+                  --batch-decode, on whatever kernel WAE_AR_COOP selects) and print that aggregate rate; 0 (default) skips it
+Prints, per run, the wall time of the whole decode_list call (packing the operands, upsampling, the launch, synchronised) and the
+aggregate kHz = sum of lengths / time, beside the efficiency the launch plan predicts (packing.ar_list_plan), and one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from oracle import wae_oracle as O  # closed-form weights only  # noqa: E402
+from wavenet_autoencoders_amd import Geometry  # noqa: E402
+from wavenet_autoencoders_amd.engine import WaeEngine  # noqa: E402
+from wavenet_autoencoders_amd.packing import ar_list_plan  # noqa: E402
+
+CFG = dict(layers=20, stacks=2, R=256, G=256, S=256, O=256, Cc=64, Cg=32, k=3, n_speakers=153,
+           upsample_scales=[4, 4, 8, 5], cin_pad=0)
+HOP = 640
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--items", type=int, default=512)
+    ap.add_argument("--dtypes", default="bf16,fp32")
+    ap.add_argument("--slots", default="cu")
+    ap.add_argument("--loop", type=int, default=0)
+    ap.add_argument("--min-len", type=int, default=8000)
+    ap.add_argument("--max-len", type=int, default=64000)
+    args = ap.parse_args()
+    rng = np.random.default_rng(1234)
+    lens = rng.integers(args.min_len, args.max_len + 1, args.items)
+    lens = (np.maximum(1, np.rint(lens / HOP)).astype(np.int64) * HOP).tolist()
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    slot_runs = [cus if s == "cu" else 2 * cus if s == "2cu" else int(s) for s in args.slots.split(",")]
+    gen = torch.Generator(device="cuda").manual_seed(1234)
+    items = [dict(T=T, c=torch.randn(64, T // HOP, device="cuda", generator=gen), gid=i % CFG["n_speakers"],
+                  uniforms=torch.rand(T, device="cuda", generator=gen)) for i, T in enumerate(lens)]
+    total = sum(lens)
+    print(f"list: {len(lens)} clips, {total} samples, lengths {min(lens)} .. {max(lens)} (mean {total / len(lens):.0f}); {cus} CUs")
+    record = dict(items=len(lens), samples=total, cus=cus, runs=[])
+    sd = O.make_state_dict(dict(CFG), salt=7, with_encoder=False)
+    for dtype in args.dtypes.split(","):
+        eng = WaeEngine(Geometry.from_cfg(CFG), dtype=dtype)
+        eng.load_state_dict(sd)
+        # warm-up: the kernels' code objects and the packed weights, on a list short enough not to matter
+        eng.decode_list([dict(it, T=HOP, c=it["c"][:, :1].contiguous(), uniforms=it["uniforms"][:HOP]) for it in items[:cus]])
+        torch.cuda.synchronize()
+        for slots in slot_runs:
+            plan = ar_list_plan(lens, slots)
+            t0 = time.perf_counter()
+            out = eng.decode_list(items, mode="sample", slots=slots)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            classes = int(torch.unique(out[0]["idx"]).numel())
+            print(f"decode_list {dtype} slots={plan.slots}: {dt:.2f} s -> {total / dt / 1e3:.1f} kHz aggregate; plan efficiency "
+                  f"{plan.efficiency:.3f} (busiest slot {plan.makespan} samples -> {plan.makespan / dt / 1e3:.2f} kHz per slot); "
+                  f"{classes} distinct classes in clip 0", flush=True)
+            record["runs"].append(dict(kind="decode_list", dtype=dtype, slots=plan.slots, seconds=dt, khz=total / dt / 1e3,
+                                       plan_efficiency=plan.efficiency, makespan=plan.makespan))
+            del out
+        if args.loop > 0:
+            sub = items[:args.loop]
+            first = sub[0]
+            eng.incremental_forward(first["c"][None, :, :1].contiguous(), torch.tensor([0], device="cuda"), HOP, mode="sample")
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for it in sub:
+                eng.incremental_forward(it["c"][None], torch.tensor([it["gid"]], device="cuda"), it["T"], mode="sample",
+                                        uniforms=it["uniforms"][None])
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            n = sum(it["T"] for it in sub)
+            kern = "one CU per clip" if getattr(eng, "_ar_profile", None) is None else "cooperative, one clip at a time"
+            print(f"incremental_forward loop {dtype} first {len(sub)} clips ({n} samples; {kern}): {dt:.2f} s -> {n / dt / 1e3:.1f} kHz",
+                  flush=True)
+            record["runs"].append(dict(kind="loop", dtype=dtype, clips=len(sub), samples=n, seconds=dt, khz=n / dt / 1e3, kernel=kern))
+    print(json.dumps(record))
+
+
+if __name__ == "__main__":
+    main()

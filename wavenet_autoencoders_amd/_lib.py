@@ -28,6 +28,10 @@ class ArDesc(ctypes.Structure):
                                                                        ("t0", c_i32)]      # t0: trailing, so every positional construction means 0
 
 
+class ArItem(ctypes.Structure):          # include/wae.h: wae_ar_item (device array element of wae_ar_generate_list)
+    _fields_ = [("off", c_i64), ("T", c_i32), ("n_forced", c_i32), ("init_idx", c_i32), ("row", c_i32)]
+
+
 class TmDesc(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in ("dtype", "B", "T", "M", "nsrc", "mode")] + [("alpha", c_f32), ("flags", c_i32)]
 
@@ -83,7 +87,7 @@ class HeadDesc(ctypes.Structure):
 
 # the 16 arguments every wae_ar_generate* entry starts with: the descriptor, (dilations, ring_off, ring, ring_total, w_layers,
 # layer_stride_bytes, w2_off_bytes), (bias2, zb, first_tab, first_bias, w_head, head_bias, c_up), c_dtype; the cooperative entries
-# put C (and dist) behind the descriptor
+# put C (and dist) behind the descriptor, the list entry (n_items, n_slots, items, next)
 _AR = [ctypes.POINTER(ArDesc), c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64] + [c_vp] * 7 + [c_i32]
 
 # name -> (restype, argtypes); mirrors include/wae.h one to one
@@ -144,6 +148,7 @@ SIGNATURES = {
     "wae_ar_generate": (c_i32, _AR + [c_vp] * 5),
     "wae_ar_generate_scalar": (c_i32, _AR + [c_vp] * 3 + [c_f32, c_i32, c_vp, c_vp, c_vp]),
     "wae_ar_generate_scalar_mog": (c_i32, _AR + [c_vp] * 3 + [c_f32, c_vp, c_vp, c_vp]),
+    "wae_ar_generate_list": (c_i32, _AR[:1] + [c_i32, c_i32, c_vp, c_vp] + _AR[1:] + [c_vp] * 5),
     "wae_ar_coop_msg_values": (c_i32, [ctypes.POINTER(ArDesc), c_i32]),
     "wae_ar_coop_acc_floats": (c_i64, [ctypes.POINTER(ArDesc)]),
     "wae_ar_generate_coop": (c_i32, _AR[:1] + [c_i32] + _AR[1:] + [c_vp] * 8),

@@ -133,12 +133,23 @@ __device__ __forceinline__ void load_w<f16>(const char* p, float (&w)[8]) {
   for (int i = 0; i < 8; ++i) w[i] = (float)v[i];
 }
 
+// What one utterance adds to the launch's arguments: its ring slot, its zb row, its first step in the per-step operands (c_up,
+// inputs, uniforms, out_idx, ...; out_logits holds its (O, T) block at base * O) and its own length, forced prefix and start class.
+// ar_kernel decodes utterance blockIdx.x (base = b * T); ar_list_kernel one queue item after another.
+struct ArUtt {
+  float* ring;
+  const float* zb;
+  int64_t base;
+  int T, n_forced, init_idx;
+};
+
+// One utterance from its first step to its last, by the whole workgroup.  Every LDS word the steps read is written here first, and a
+// ring row is read only behind its write in this very decode (the `tt >= 0` test below; a layer's (k-1)d+1 rows cover exactly the
+// steps t-(k-1)d .. t), so a workgroup may run this again and again in the same LDS and the same ring slot.
 template <typename E>
-__global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
+__device__ __forceinline__ void ar_decode(const ArArgs& p, const ArUtt& ut, float* sm) {
   constexpr int EPL = ET<E>::EPL;
   const int tid = threadIdx.x;
-  const int b = blockIdx.x;
   const int H = p.G / 2;
   const int K1 = p.ktaps * p.R + (p.Cc > 0 ? p.Cc : 0);
   const int K1p = (K1 + EPL - 1) / EPL * EPL;
@@ -154,8 +165,8 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
   float* psum = lbuf + ((p.O + 3) & ~3);  // p.psum_floats
   int* ibuf = (int*)(psum + p.psum_floats);     // [0] = current input id
 
-  float* ring = p.ring + (int64_t)b * p.ring_total;
-  const float* zb_b = p.zb + (int64_t)b * p.L * 2 * p.Hp;
+  float* ring = ut.ring;
+  const float* zb_b = ut.zb;
   int gp, gRW, gNS, wp_, wRW, wNS, sp_, sRW, sNS, op_, oRW, oNS;
   layout_rows(p.G, gp, gRW, gNS);
   layout_rows(p.R + p.S, wp_, wRW, wNS);
@@ -167,12 +178,12 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
   for (int i = tid; i < Sk; i += AR_THREADS) { skipb[i] = 0.f; hbuf[i] = 0.f; }
   float* fcur = (float*)(ibuf + 1);   // scalar input: the current input value
   if (tid == 0) {
-    ibuf[0] = (p.inputs && p.n_forced > 0) ? p.inputs[(int64_t)b * p.T] : p.init_idx;
-    fcur[0] = (p.inputs_f && p.n_forced > 0) ? p.inputs_f[(int64_t)b * p.T] : 0.f;     // wavenet.py:284-285: the start value is zero
+    ibuf[0] = (p.inputs && ut.n_forced > 0) ? p.inputs[ut.base] : ut.init_idx;
+    fcur[0] = (p.inputs_f && ut.n_forced > 0) ? p.inputs_f[ut.base] : 0.f;     // wavenet.py:284-285: the start value is zero
   }
   __syncthreads();
 
-  for (int t = 0; t < p.T; ++t) {
+  for (int t = 0; t < ut.T; ++t) {
     // ---- first conv: one-hot input == column gather (wavenet.py:311); scalar input: w * x + b ----------------
     const int cur = ibuf[0];
     if (cur < 0) {
@@ -189,7 +200,7 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
                            : p.first_tab[(int64_t)cur * p.Rp + r] + p.first_bias[r];
     }
     for (int cc = AR_THREADS - 1 - tid; cc < p.Cc; cc += AR_THREADS) {   // local conditioning of this step -> tail of the operand vector
-      const int64_t ci = ((int64_t)b * p.T + t) * p.Ccp + cc;
+      const int64_t ci = (ut.base + t) * p.Ccp + cc;
       vbuf[p.ktaps * p.R + cc] = p.c_dtype == WAE_BF16 ? (float)((const __bf16*)p.c_up)[ci] : (p.c_dtype == WAE_F16 ? (float)((const f16*)p.c_up)[ci] : ((const float*)p.c_up)[ci]);
     }
     for (int i = tid; i < p.S; i += AR_THREADS) skipb[i] = 0.f;
@@ -249,7 +260,7 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
     for (int i = tid; i < p.O; i += AR_THREADS) {
       const float y = psum_total(psum, i, op_, oNS) + p.head_bias[p.S + i];
       lbuf[i] = y;
-      if (p.out_logits && p.mode != 3) p.out_logits[((int64_t)b * p.O + i) * p.T + t] = y;
+      if (p.out_logits && p.mode != 3) p.out_logits[(ut.base * p.O + (int64_t)i * ut.T) + t] = y;
     }
     __syncthreads();
     if (p.mode == 3) {
@@ -261,7 +272,7 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
       for (int i = tid; i < p.O; i += AR_THREADS) {
         const float pr = expf(lbuf[i] - mx) / den;
         lbuf[i] = pr;
-        if (p.out_logits) p.out_logits[((int64_t)b * p.O + i) * p.T + t] = pr;
+        if (p.out_logits) p.out_logits[(ut.base * p.O + (int64_t)i * ut.T) + t] = pr;
       }
       __syncthreads();
     }
@@ -272,7 +283,7 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
       float xs = 0.f;
       if (p.u_mix) {
         const int M = p.O / 3;
-        const float* um = p.u_mix + ((int64_t)b * p.T + t) * M;
+        const float* um = p.u_mix + (ut.base + t) * M;
         float best = -INFINITY;
         int arg = 0;
         for (int i = 0; i < M; ++i) {
@@ -282,11 +293,11 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
         const float mu = lbuf[M + arg];
         float ls = lbuf[2 * M + arg];
         if (p.clamp_log_scale) ls = fmaxf(ls, p.log_scale_min);
-        const float u = p.u_log[(int64_t)b * p.T + t];
+        const float u = p.u_log[ut.base + t];
         xs = fminf(fmaxf(mu + expf(ls) * (logf(u) - logf(1.f - u)), -1.f), 1.f);
-        if (p.out_f) p.out_f[(int64_t)b * p.T + t] = xs;
+        if (p.out_f) p.out_f[ut.base + t] = xs;
       }
-      fcur[0] = (p.inputs_f && t + 1 < p.n_forced) ? p.inputs_f[(int64_t)b * p.T + t + 1] : xs;
+      fcur[0] = (p.inputs_f && t + 1 < ut.n_forced) ? p.inputs_f[ut.base + t + 1] : xs;
     }
     if (tid == 0 && p.scalar && p.dist == 1) {
       // sample_from_mix_gaussian (mixture.py:225-270) on caller-supplied draws: Gumbel-max mixture pick when M > 1, mu + exp(log s) z
@@ -298,17 +309,17 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
         const int mu0 = p.O == 2 ? 0 : M, ls0 = p.O == 2 ? 1 : 2 * M;
         int arg = 0;
         if (M > 1) {
-          const float* um = p.u_mix + ((int64_t)b * p.T + t) * M;
+          const float* um = p.u_mix + (ut.base + t) * M;
           float best = -INFINITY;
           for (int i = 0; i < M; ++i) {
             const float v = lbuf[i] - logf(-logf(um[i]));
             if (v > best) { best = v; arg = i; }
           }
         }
-        xs = fminf(fmaxf(lbuf[mu0 + arg] + expf(lbuf[ls0 + arg]) * p.z[(int64_t)b * p.T + t], -1.f), 1.f);
-        if (p.out_f) p.out_f[(int64_t)b * p.T + t] = xs;
+        xs = fminf(fmaxf(lbuf[mu0 + arg] + expf(lbuf[ls0 + arg]) * p.z[ut.base + t], -1.f), 1.f);
+        if (p.out_f) p.out_f[ut.base + t] = xs;
       }
-      fcur[0] = (p.inputs_f && t + 1 < p.n_forced) ? p.inputs_f[(int64_t)b * p.T + t + 1] : xs;
+      fcur[0] = (p.inputs_f && t + 1 < ut.n_forced) ? p.inputs_f[ut.base + t + 1] : xs;
     }
     if (tid == 0 && !p.scalar) {
       int nxt;
@@ -323,7 +334,7 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
         for (int i = 0; i < p.O; ++i) den += expf(lbuf[i] - mx);
         double tot = 0.0;
         for (int i = 0; i < p.O; ++i) tot += (double)(expf(lbuf[i] - mx) / den);
-        const double thr = (double)p.uniforms[(int64_t)b * p.T + t] * tot;
+        const double thr = (double)p.uniforms[ut.base + t] * tot;
         double c = 0.0;
         int cnt = 0;
         for (int i = 0; i < p.O; ++i) {
@@ -332,8 +343,8 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
         }
         produced = min(cnt, p.O - 1);
       }
-      p.out_idx[(int64_t)b * p.T + t] = produced;
-      if (p.inputs && t + 1 < p.n_forced) nxt = p.inputs[(int64_t)b * p.T + t + 1];
+      p.out_idx[ut.base + t] = produced;
+      if (p.inputs && t + 1 < ut.n_forced) nxt = p.inputs[ut.base + t + 1];
       else nxt = p.mode >= 3 ? -1 : produced;
       ibuf[0] = nxt;
     }
@@ -341,12 +352,59 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
   }
 }
 
+template <typename E>
+__global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int b = blockIdx.x;
+  const ArUtt ut = {p.ring + (int64_t)b * p.ring_total, p.zb + (int64_t)b * p.L * 2 * p.Hp, (int64_t)b * p.T, p.T, p.n_forced, p.init_idx};
+  ar_decode<E>(p, ut, sm);
+}
+
+// wae_ar_generate_list: n_slots persistent workgroups empty a queue of utterances of any lengths.  Thread 0 takes the next item index
+// with one returning atomic add on the caller-zeroed counter and hands it to the workgroup through LDS; the workgroup decodes that
+// item to its end in its own ring slot (blockIdx.x) and comes back for the next.  No workgroup ever waits for another.
+struct ArListArgs {
+  ArArgs a;
+  const wae_ar_item* items;
+  int32_t* next;
+  int n_items;
+  int qword;   // float index of the queue word in dynamic LDS, behind everything ar_decode carves
+};
+
+template <typename E>
+__global__ void __launch_bounds__(AR_THREADS) ar_list_kernel(ArListArgs q) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const ArArgs& p = q.a;
+  int* taken = (int*)sm + q.qword;
+  float* ring = p.ring + (int64_t)blockIdx.x * p.ring_total;
+  for (;;) {
+    if (threadIdx.x == 0) *taken = atomicAdd(q.next, 1);
+    __syncthreads();
+    const int it = *taken;
+    if (it >= q.n_items) return;   // the same word for every thread: the workgroup leaves together
+    const wae_ar_item w = q.items[it];
+    if (w.T > 0) {
+      // mode 0 is teacher-forced throughout; a start class outside the table would read beyond first_tab
+      const int nf = !p.inputs ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
+      const ArUtt ut = {ring, p.zb + (int64_t)w.row * p.L * 2 * p.Hp, w.off, w.T, nf, min(max(w.init_idx, 0), p.O - 1)};
+      ar_decode<E>(p, ut, sm);
+    }
+    __syncthreads();               // every thread has read the word before thread 0 writes the next
+  }
+}
+
+struct ArList {   // wae_ar_generate_list's own arguments
+  const wae_ar_item* items;
+  int32_t* next;
+  int n_items, n_slots;
+};
+
 static int ar_launch(const wae_ar_desc* d, const int32_t* dilations, const int64_t* ring_off, float* ring, int64_t ring_total,
                      const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes, const float* bias2, const float* zb,
                      const float* first_tab, const float* first_bias, const void* w_head, const float* head_bias, const void* c_up,
                      int32_t c_dtype, const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
                      const float* inputs_f, const float* u_mix, const float* u_log, float* out_f, float log_scale_min,
-                     int clamp_log_scale, int dist, const float* z, void* stream) {
+                     int clamp_log_scale, int dist, const float* z, void* stream, const ArList* list = nullptr) {
   ArArgs a;
   a.dtype = d->dtype; a.B = d->B; a.T = d->T; a.L = d->L; a.R = d->R; a.G = d->G; a.S = d->S; a.O = d->O; a.Cc = d->Cc;
   a.Ccp = d->Ccp; a.Hp = d->Hp; a.ktaps = d->ktaps; a.mode = d->mode; a.Rp = d->Rp; a.scale = d->scale; a.dil = dilations;
@@ -367,6 +425,22 @@ static int ar_launch(const wae_ar_desc* d, const int32_t* dilations, const int64
   const size_t lds = sizeof(float) * (size_t)(ru(d->ktaps * d->R + (d->Cc > 0 ? d->Cc : 0), epl) + d->R + ru(H, epl) +
                                               2 * ru(d->S, epl) + ru(d->O, 4) + psz + 4);
   hipStream_t st = as_stream(stream);
+  if (list) {
+    // the queue word sits behind ar_decode's carve; per-utterance B, T, n_forced and init_idx come from the items
+    const ArListArgs q = {a, list->items, list->next, list->n_items, (int)(lds / sizeof(float))};
+    const size_t ldq = lds + 16;
+    if (d->dtype == WAE_BF16) {
+      (void)hipFuncSetAttribute((const void*)ar_list_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldq);
+      hipLaunchKernelGGL(ar_list_kernel<__bf16>, dim3(list->n_slots), dim3(AR_THREADS), ldq, st, q);
+    } else if (d->dtype == WAE_F16) {
+      (void)hipFuncSetAttribute((const void*)ar_list_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldq);
+      hipLaunchKernelGGL(ar_list_kernel<f16>, dim3(list->n_slots), dim3(AR_THREADS), ldq, st, q);
+    } else {
+      (void)hipFuncSetAttribute((const void*)ar_list_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldq);
+      hipLaunchKernelGGL(ar_list_kernel<float>, dim3(list->n_slots), dim3(AR_THREADS), ldq, st, q);
+    }
+    return wae_check_launch("ar_generate_list");
+  }
   if (d->dtype == WAE_BF16) {
     (void)hipFuncSetAttribute((const void*)ar_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(ar_kernel<__bf16>, dim3(d->B), dim3(AR_THREADS), lds, st, a);
@@ -405,6 +479,38 @@ extern "C" int wae_ar_generate(const wae_ar_desc* d, const int32_t* dilations, c
   return ar_launch(d, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
                    first_bias, w_head, head_bias, c_up, c_dtype, inputs, uniforms, out_idx, out_logits, nullptr, nullptr, nullptr,
                    nullptr, -7.0f, 0, 0, nullptr, stream);
+}
+
+extern "C" int wae_ar_generate_list(const wae_ar_desc* d, int32_t n_items, int32_t n_slots, const wae_ar_item* items, int32_t* next,
+                                    const int32_t* dilations, const int64_t* ring_off, float* ring, int64_t ring_total,
+                                    const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes, const float* bias2,
+                                    const float* zb, const float* first_tab, const float* first_bias, const void* w_head,
+                                    const float* head_bias, const void* c_up, int32_t c_dtype, const int32_t* inputs,
+                                    const float* uniforms, int32_t* out_idx, float* out_logits, void* stream) {
+  WAE_REQUIRE(d && dilations && ring_off && ring && w_layers && bias2 && zb && first_tab && first_bias && w_head && head_bias &&
+                  out_idx, "ar_generate_list: null pointer argument");
+  WAE_REQUIRE(items && next, "ar_generate_list: the item array and the queue counter are required");
+  WAE_REQUIRE(n_items >= 1, "ar_generate_list: n_items %d < 1", n_items);
+  WAE_REQUIRE(n_slots >= 1, "ar_generate_list: n_slots %d < 1", n_slots);
+  WAE_REQUIRE(wae_dtype_ok(d->dtype), "ar_generate_list: bad dtype");
+  WAE_REQUIRE(d->L > 0 && d->R > 0 && d->G > 0 && d->G % 2 == 0 && d->S > 0 && d->O > 0, "ar_generate_list: bad sizes");
+  WAE_REQUIRE(d->Cc <= 0 || c_up, "ar_generate_list: Cc > 0 but c_up is null");
+  if (d->scalar_input) {
+    wae_set_error("ar_generate_list: list decoding covers class-id decoders; scalar-input decoders go through wae_ar_generate_scalar");
+    return WAE_EUNSUPPORTED;
+  }
+  if (d->mode == 3 || d->mode == 4) {
+    wae_set_error("ar_generate_list: modes 3 / 4 (dense feedback) are not list-decoded; use wae_ar_generate");
+    return WAE_EUNSUPPORTED;
+  }
+  WAE_REQUIRE(d->mode >= 0 && d->mode <= 2, "ar_generate_list: mode must be 0 (logits), 1 (argmax) or 2 (sample)");
+  WAE_REQUIRE(d->t0 == 0, "ar_generate_list: t0 %d: a list decode cannot be continued", d->t0);
+  WAE_REQUIRE(d->mode != 0 || inputs, "ar_generate_list: mode 0 needs inputs for every step");
+  WAE_REQUIRE(d->mode != 2 || uniforms, "ar_generate_list: sample mode needs uniforms");
+  const ArList list = {items, next, n_items, n_slots};
+  return ar_launch(d, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
+                   first_bias, w_head, head_bias, c_up, c_dtype, inputs, uniforms, out_idx, out_logits, nullptr, nullptr, nullptr,
+                   nullptr, -7.0f, 0, 0, nullptr, stream, &list);
 }
 
 extern "C" int wae_ar_generate_scalar(const wae_ar_desc* d, const int32_t* dilations, const int64_t* ring_off, float* ring,

@@ -922,6 +922,128 @@ class WaeEngine:
         self._ar_keep = (s, cu, inp) + keep     # the launch's operands (and the decode's: ring, zb, ...) live until the stream has run
         return item
 
+    def decode_list(self, items, mode: str = "sample", slots: Optional[int] = None, want_logits: bool = False,
+                    c_is_upsampled: bool = False):
+        """A work list of utterances of unequal lengths in ONE launch (include/wae.h: wae_ar_generate_list): `slots` persistent
+        workgroups, one per CU, each decoding one item after another until the list is empty -- throughput decoding, where
+        incremental_forward takes equal lengths only and a loop over it leaves most of the device idle.
+
+        items: a sequence of mappings with `T` (steps), `c` ((Cc, Tc) conditioning or None: the latent frames, upsampled here as
+        incremental_forward does, or the (Cc, T) per-sample features when c_is_upsampled or the geometry has no upsampling network),
+        `gid` (speaker id or None; all items or none) and optionally `test_inputs` (class ids of the forced prefix, up to T of them),
+        `uniforms` ((T,) draws in [0, 1) of mode "sample") and `init_idx` (the start class where nothing is forced; 127 by default).
+        mode "logits" (teacher-forced on test_inputs of all T steps), "argmax" or "sample", as incremental_forward.  Where an item has
+        no uniforms they are drawn as torch.rand(1, T) on the device, item after item in the caller's order: with the same
+        torch.manual_seed before every item this is what a loop of incremental_forward draws.
+        slots: workgroups (and ring slots of ar_ring_total floats each) to launch, by default min(len(items), CUs of the device); a
+        workgroup's registers fill a CU, so more slots than CUs only queue.  The launch order is longest first (packing.ar_list_plan).
+        Returns, in the caller's order, a list of dict(idx (T,) int32, logits (O, T) fp32 | None); every item is, bit for bit, what
+        incremental_forward returns for that utterance alone on the one-CU kernel (WAE_AR_COOP=0).
+        Always the list kernel: ar_path() and WAE_AR_COOP have no effect here.  Class-id decoders only: a scalar-input geometry
+        raises NotImplementedError, an empty list ValueError, both before any launch."""
+        g = self.g
+        if g.scalar_input:
+            raise NotImplementedError("decode_list: list decoding covers class-id decoders; decode scalar-input models one batch at a "
+                                      "time with incremental_forward")
+        items = list(items)
+        if not items:
+            raise ValueError("decode_list: an empty list")
+        if mode not in ("logits", "argmax", "sample"):
+            raise ValueError(f"decode_list: mode '{mode}' is not list-decoded; use 'logits', 'argmax' or 'sample'")
+        m = {"logits": 0, "argmax": 1, "sample": 2}[mode]
+        lib, dev, n = self.lib, self.device, len(items)
+        Ts = [int(it["T"]) for it in items]
+        if slots is None:
+            slots = torch.cuda.get_device_properties(dev).multi_processor_count
+        plan = P.ar_list_plan(Ts, slots)
+        total, off = plan.total, [int(o) for o in plan.offsets]
+        gids = [it.get("gid") for it in items]
+        if any(x is None for x in gids) and not all(x is None for x in gids):
+            raise ValueError("decode_list: give every item a gid, or none")
+        flat = lambda a, dt: torch.as_tensor(a).reshape(-1).to(dev, dt)  # noqa: E731
+        forced, nfs, inits = [], [], []
+        for i, it in enumerate(items):
+            ti = it.get("test_inputs")
+            ti = flat(ti, torch.int32)[:Ts[i]] if ti is not None else None
+            nfs.append(0 if ti is None else int(ti.numel()))
+            forced.append(ti if nfs[i] else None)
+            if m == 0 and nfs[i] < Ts[i]:
+                raise ValueError(f"decode_list: mode 'logits' is teacher-forced: test_inputs of item {i} must cover all {Ts[i]} steps")
+            init = it.get("init_idx")
+            init = 127 if init is None else int(torch.as_tensor(init).reshape(-1)[0])
+            if nfs[i] == 0 and not 0 <= init < g.O:
+                # wavenet.py:288 writes a one at the start class of the start vector: the same IndexError when there are fewer classes
+                raise IndexError(f"index {init} is out of bounds for dimension 2 with size {g.O}")
+            inits.append(init if nfs[i] == 0 else 0)
+            if g.Ccp and it.get("c") is None:
+                raise ValueError(f"decode_list: item {i} has no conditioning c, the decoder has {g.Cc} conditioning channels")
+        if not getattr(self, "_ar_packed", False) or self.weights_dirty:
+            self.pack_ar_weights()
+        st = self.stream()
+        inputs = None
+        if any(f is not None for f in forced):
+            inputs = torch.zeros(total, dtype=torch.int32, device=dev)
+            for i, f in enumerate(forced):
+                if f is not None:
+                    inputs[off[i]:off[i] + nfs[i]] = f
+            if int(inputs.min()) < 0 or int(inputs.max()) >= g.O:
+                raise IndexError(f"decode_list: test_inputs hold a class id outside [0, {g.O})")
+        c_up = None
+        if g.Ccp:
+            c_up = torch.zeros(total, g.Ccp, dtype=self.tdtype, device=dev)
+            up = int(np.prod(g.upsample_scales)) if g.upsample_scales else 1
+            for i, it in enumerate(items):
+                c = torch.as_tensor(it["c"]).to(dev, torch.float32)
+                c = (c if c.dim() == 3 else c[None]).contiguous()
+                out = c_up[off[i]:off[i] + Ts[i]].view(1, Ts[i], g.Ccp)      # the item's slice: one utterance of batch 1
+                if c_is_upsampled or not g.upsample_scales:
+                    assert c.shape[-1] == Ts[i], f"item {i}: c {tuple(c.shape)} != T {Ts[i]}"       # wavenet.py:278
+                    L.check(lib.wae_to_btc(L.ptr(c), L.ptr(out), 1, g.Cc, Ts[i], g.Ccp, self.dt, st), "to_btc")
+                else:
+                    assert (c.shape[-1] - 2 * g.cin_pad) * up == Ts[i], f"item {i}: c does not upsample to T"
+                    self.upsample_forward(c, out)
+        zb = torch.empty(n, g.layers, 2 * g.Hp, dtype=torch.float32, device=dev)
+        has_gid = gids[0] is not None
+        gid32 = torch.tensor([int(torch.as_tensor(x).reshape(-1)[0]) for x in gids], dtype=torch.int32, device=dev) if has_gid else None
+        wg_off = self.lay.off("wavenet.conv_layers.0.conv1x1g.weight_v") if g.Cg > 0 else -1
+        use_gid = has_gid and "wavenet.embed_speakers.weight" in self.lay.offsets
+        L.check(lib.wae_gproj_fwd(L.ptr(self.eff), wg_off if has_gid else -1, self.lay.off("wavenet.conv_layers.0.conv.bias"),
+                                  self.lay.layer_stride, L.ptr(gid32) if use_gid else None,
+                                  self.lay.offsets.get("wavenet.embed_speakers.weight", 0), None, L.ptr(zb), n, g.layers, g.G, g.Hp,
+                                  max(g.Cg, 0), int(g.n_speakers or 0), L.ptr(self.err), st), "gproj")
+        uni = None
+        if m == 2:
+            uni = torch.empty(total, dtype=torch.float32, device=dev)
+            for i, it in enumerate(items):
+                u = it.get("uniforms")
+                u = torch.rand(1, Ts[i], device=dev) if u is None else flat(u, torch.float32)
+                assert u.numel() == Ts[i], f"item {i}: {u.numel()} uniforms for {Ts[i]} steps"
+                uni[off[i]:off[i] + Ts[i]] = u.reshape(-1)
+        rec = np.zeros(n, dtype=np.dtype([("off", "<i8"), ("T", "<i4"), ("n_forced", "<i4"), ("init_idx", "<i4"), ("row", "<i4")]))
+        assert rec.dtype.itemsize == ctypes.sizeof(L.ArItem)
+        for k, i in enumerate(plan.order):      # launch order: longest first; row = the caller's index
+            rec[k] = (off[i], Ts[i], nfs[i], inits[i], int(i))
+        items_d = torch.from_numpy(rec.view(np.uint8)).to(dev)
+        nxt = torch.zeros(1, dtype=torch.int32, device=dev)
+        # not zeroed: a decode reads a history row only behind its own write of it (csrc/ar_fwd.hip: ar_decode), in the first item of a
+        # slot as in every later one
+        ring = torch.empty(plan.slots * self.ar_ring_total, dtype=torch.float32, device=dev)
+        out_idx = torch.empty(total, dtype=torch.int32, device=dev)
+        want = want_logits or m == 0
+        logits = torch.empty(total * g.O, dtype=torch.float32, device=dev) if want else None
+        d = L.ArDesc(self.dt, n, 0, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, 0, 0,
+                     math.sqrt(1.0 / g.layers), 0)
+        es = self.ar_w.element_size()
+        L.check(lib.wae_ar_generate_list(ctypes.byref(d), n, plan.slots, L.ptr(items_d), L.ptr(nxt), L.ptr(self.ar_dil),
+                                         L.ptr(self.ar_ring_off), L.ptr(ring), self.ar_ring_total, L.ptr(self.ar_w),
+                                         self.ar_layer_elems * es, self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(zb),
+                                         L.ptr(self.first_tab), L.ptr(self.first_bias), L.ptr(self.ar_wh), L.ptr(self.ar_hb),
+                                         L.ptr(c_up), self.dt, L.ptr(inputs), L.ptr(uni), L.ptr(out_idx), L.ptr(logits), st),
+                "ar_generate_list")
+        self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, uni)      # the launch's operands live until the stream has run
+        return [dict(idx=out_idx[off[i]:off[i] + Ts[i]],
+                     logits=logits[off[i] * g.O:(off[i] + Ts[i]) * g.O].view(g.O, Ts[i]) if want else None) for i in range(n)]
+
     # ------------------------------------------------------------------ full autoencoder
     def forward(self, x: torch.Tensor, c: torch.Tensor, gid: Optional[torch.Tensor], targets=None, lengths=None,
                 want_logits=True, train=False, beta: float = 0.25, dropout_on: bool = True, layer_events: Optional[list] = None):

@@ -22,10 +22,11 @@ GEMM 2 stream ``[q2][mt][kb][lane][j]``: M-tile gm = q2*MT2 + mt over [out rows 
 """
 from __future__ import annotations
 
+import heapq
 import math
 from collections import OrderedDict
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -437,6 +438,42 @@ def ar_ring_offsets(g: Geometry) -> np.ndarray:
     for d in g.dilations:
         off.append(off[-1] + ((g.k - 1) * d + 1) * g.R)
     return np.asarray(off, dtype=np.int64)
+
+
+class ArListPlan(NamedTuple):
+    """ar_list_plan's answer.  order: item indices in launch order; offsets[i]: first step of the caller's item i in the packed
+    per-step operands (caller's order, contiguous); total: their sum of lengths; slots: workgroups to launch; makespan: steps of the
+    busiest slot when every free slot takes the next item of `order` (what the kernel's queue does, all steps costing the same)."""
+    order: np.ndarray
+    offsets: np.ndarray
+    total: int
+    slots: int
+    makespan: int
+
+    @property
+    def efficiency(self) -> float:
+        """share of slots x makespan that decodes: sum T_i / (slots x longest slot load)"""
+        return self.total / float(self.slots * self.makespan)
+
+
+def ar_list_plan(lengths, slots: int) -> ArListPlan:
+    """Launch plan of a list decode (include/wae.h: wae_ar_generate_list) for utterances of `lengths` steps on `slots` workgroups.
+    Longest first, so that the tail of the launch -- slots idling while the last items finish -- is short; equal lengths keep the
+    caller's order (a stable sort), so the plan is a function of the lengths alone.  slots is clamped to the item count."""
+    n = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if n.size < 1:
+        raise ValueError("ar_list_plan: an empty list")
+    if int(n.min()) < 1:
+        raise ValueError(f"ar_list_plan: every item has at least one step (got {int(n.min())})")
+    if int(slots) < 1:
+        raise ValueError(f"ar_list_plan: slots {int(slots)} < 1")
+    slots = min(int(slots), int(n.size))
+    order = np.argsort(-n, kind="stable")
+    offsets = np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64)
+    free = [0] * slots                      # a heap of the times at which the slots come back to the queue
+    for i in order:
+        heapq.heappush(free, heapq.heappop(free) + int(n[i]))
+    return ArListPlan(order, offsets, int(n.sum()), slots, max(free))
 
 
 # ---------------------------------------------------------------------------------------------------
