@@ -674,6 +674,57 @@ def test_weight_gradients_beside_an_underfilled_sweep(dtype):
     assert float((got[False][1] - got[True][1]).abs().max()) < 2e-3
 
 
+def test_two_chains_with_weight_gradients_beside_the_sweep():
+    """Two chains of the sweep AND the upper layers' weight gradients beside it (opt.chains "2" on an under-filled sweep of >= 8 layers;
+    `auto` never combines them): the launch that leaves the sweep reads dz / dx-hat / z rows of BOTH chains, so the chains are joined
+    in front of it and forked again behind it (backward._leave_sweep) -- ordered behind the main stream alone it read rows the trailing
+    chain had not written.  The model of test_weight_gradients_beside_an_underfilled_sweep, one step: dz, every dx-hat and dc BITWISE
+    those of one chain with the one launch behind the sweep, every parameter gradient to the tolerance of two orders of the same
+    atomic sums."""
+    from wavenet_autoencoders_amd import Geometry
+    from wavenet_autoencoders_amd import backward as BW
+    from wavenet_autoencoders_amd.engine import WaeEngine
+    cfg = dict(layers=10, stacks=2, R=256, G=256, S=256, O=256, Cc=64, Cg=32, k=3, n_speakers=11, upsample_scales=[4, 4, 8, 5], cin_pad=0)
+    B, T, hop = 3, 1920, 640
+    sd = O.make_state_dict(dict(cfg), salt=9, with_encoder=False)
+    gen = torch.Generator().manual_seed(377)
+    x = torch.randint(0, 256, (B, T), generator=gen).cuda()
+    c = torch.randn(B, 64, T // hop, generator=gen).cuda()
+    g = torch.randint(0, cfg["n_speakers"], (B,), generator=gen).cuda()
+    lengths = torch.tensor([T - 97 * i for i in range(B)])
+    got = {}
+    for chains, side in (("1", False), ("2", True)):
+        eng = WaeEngine(Geometry.from_cfg(cfg), dtype="bf16")
+        eng.opt.chains, eng.opt.side = chains, side
+        eng.load_state_dict(sd, strict=False)
+        eng.decoder_forward(x, c, g, targets=x, lengths=lengths.cuda(), train=True, want_logits=False)
+        dc = BW.decoder_backward(eng, x, x, lengths, g)
+        ws = eng._ws[("bwd", B, T)]
+        assert (eng.chain_plan(B, T, backward=True) is not None) == side and ("stream_beside" in ws) == side
+        torch.cuda.synchronize()
+        got[side] = dict(dz=ws["dz"].clone(), gx=[t_.clone() for t_ in ws["gx"]], dc=dc.clone(), grads=BW.finish_grads(eng).clone())
+        torch.cuda.synchronize()
+        lay = eng.lay
+        del eng
+        torch.cuda.empty_cache()
+    one, two = got[False], got[True]
+    i16 = lambda t_: t_.contiguous().view(torch.int16)  # noqa: E731
+    assert float(one["dz"].float().abs().max()) > 0
+    assert torch.equal(i16(one["dz"]), i16(two["dz"])), "dz"
+    assert torch.equal(i16(one["dc"]), i16(two["dc"])), "dc"
+    assert len(one["gx"]) == cfg["layers"]
+    for i, (a, b_) in enumerate(zip(one["gx"], two["gx"])):
+        assert torch.equal(i16(a), i16(b_)), ("dx-hat", i)
+    bad = {}
+    for k in lay.offsets:
+        a = one["grads"][lay.off(k):lay.off(k) + lay.numel(k)]
+        b_ = two["grads"][lay.off(k):lay.off(k) + lay.numel(k)]
+        err, ref = float((a - b_).abs().max()), float(a.abs().max())
+        if err > 1e-4 * ref + 1e-7:
+            bad[k] = (err, ref)
+    assert not bad, bad
+
+
 def test_weight_gradients_beside_the_sweep_with_the_encoder_in_front():
     """The same on the reference's own preset (hps/vqwae.json in full: encoder, VQ, upsampling network, 20-layer decoder; a short
     batch): there the lower layers' launch also leaves 32 CUs to the front end's backward, which runs on its own side stream from the

@@ -298,3 +298,77 @@ def test_two_chains_rule():
     assert not two_chains("auto", True, 1, 64000, backward=True)                   # one clip cannot be cut
     assert not two_chains("1", True, *c5, backward=True) and two_chains("2", True, 2, 256, backward=False)
     assert not two_chains("2", True, 1, 256, backward=False) and not two_chains("2", False, 2, 256, backward=True)
+
+
+TN_SHARE_CASES = [(ng, B, T, ts, ncu, swap) for ng in (1, 2, 3, 10, 24, 25) for B in (1, 2, 3, 8, 32) for T in (2, 15, 33, 257, 1000, 8000)
+                  for ts in (1, 5, 6) for ncu in (96, 224, 250, 256) for swap in (False, True) if ts >= 2 or not swap]
+
+
+def test_tn_team_shares_invariants():
+    """packing.tn_team_shares: the (group, 32-row slab) list of a weight-gradient team launch cut into one share per team -- what
+    backward.StreamTable / StaticStreamTable.finalize upload."""
+    for ng, B, T, ts, ncu, swap in TN_SHARE_CASES:
+        case = (ng, B, T, ts, ncu, swap)
+        sh = P.tn_team_shares(ng, B, T, ts, ncu, swap)
+        per = B * ((T + 31) // 32)
+        assert sh.nteams == max(1, ncu // ts) and sh.nwg >= sh.nteams * ts, case
+        assert len(sh.team_seg) == sh.nteams + 1 and sh.team_seg[0] == 0 and sh.team_seg[-1] == len(sh.segs), case
+        seen = np.zeros((ng, per), dtype=np.int32)
+        sizes = []
+        for t in range(sh.nteams):
+            mine = sh.segs[sh.team_seg[t]:sh.team_seg[t + 1]]
+            slabs = []                                        # (variant, group, slab) in the team's walking order
+            for job, lo, hi in mine:
+                assert job % ts == 0 and 0 <= lo < hi <= per, (case, t)      # non-empty, inside its group
+                var, grp = divmod(job // ts, ng)
+                assert var in ((0, 1) if swap else (0,)), (case, t)
+                seen[grp, lo:hi] += 1
+                slabs += [(var, grp * per + s) for s in range(lo, hi)]
+            sizes.append(len(slabs))
+            assert [s for _, s in slabs] == list(range(slabs[0][1], slabs[0][1] + len(slabs))) if slabs else True, (case, t)
+            if swap:      # the first half of the share on the groups as built, the second on the swapped copy
+                assert [v for v, _ in slabs] == [0] * (len(slabs) // 2) + [1] * (len(slabs) - len(slabs) // 2), (case, t)
+        assert (seen == 1).all(), case                        # every (group, slab) exactly once
+        assert max(sizes) - min(sizes) <= 1, case
+
+
+def test_tn_team_shares_at_the_bench_shapes():
+    """... and the numbers the launches of the benchmark configurations have had since the static launch's swapped half shares
+    (recorded from StaticStreamTable.finalize before the cut moved to packing.py): C2 = 24 layers + the head's group, 8 x 8000, teams of
+    five on 256 CUs; the upper 8 layers + the head of hps/vqwae.json's shard (8 x 5120) beside the sweep on its 96 idle CUs."""
+    c2 = P.tn_team_shares(25, 8, 8000, 5, 256, True)
+    assert (c2.nteams, c2.nwg, len(c2.segs)) == (51, 256, 126)
+    c3 = P.tn_team_shares(9, 8, 5120, 5, 96, True)
+    assert (c3.nteams, c3.nwg, len(c3.segs)) == (19, 96, 46)
+    # CUs that are no multiple of eight, or fewer than a team: the launch is exactly its teams
+    assert P.tn_team_shares(3, 2, 64, 6, 250, False).nwg == 41 * 6 and P.tn_team_shares(3, 2, 64, 6, 4, False)[:2] == (1, 6)
+
+
+def test_tn_beside_split_and_job_groups():
+    """packing.tn_beside_split: which layers' weight gradients run beside an under-filled sweep (256 CUs); packing.tn_job_groups: a
+    layer's static jobs in equal groups of at most six."""
+    assert P.tn_beside_split(20, 8, 5120, 256) == (12, 96)        # hps/vqwae.json's shard: 160 workgroups per launch
+    assert P.tn_beside_split(10, 3, 1920, 256) == (4, 232)
+    assert P.tn_beside_split(24, 8, 8000, 256) is None            # C2 fills the machine
+    assert P.tn_beside_split(6, 3, 1920, 256) is None             # too few layers
+    for njobs, (ngrp, gsz) in {5: (1, 5), 18: (3, 6), 7: (2, 4), 6: (1, 6), 13: (3, 5)}.items():      # (7: one null job)
+        assert P.tn_job_groups(njobs) == (ngrp, gsz) and 0 <= ngrp * gsz - njobs < ngrp, njobs
+
+
+def test_tn_layer_contractions_records():
+    """packing.tn_layer_contractions: taps, conditioning (+ zb sums in its ones columns), conv1x1_out (+ bias) of one layer as the
+    argument records of TileTable.add / StreamTable.add."""
+    g = P.Geometry.from_cfg(dict(CFG, R=64, G=128, S=64, Cc=64))
+    Z2 = 2 * g.Hp
+    recs = list(P.tn_layer_contractions(g, 4, 0.5, 1000, 8 * Z2, 2000, 3000, 4000, 5000, 6000, 512, 7000, 192))
+    assert len(recs) == g.k + 2 and all(len(r) == 11 and r[4] == 0.5 for r in recs)
+    assert [r[2] for r in recs] == [-8, -4, 0, 0, 0] and [r[3] for r in recs] == [-1, -1, -1, g.Ccp, g.Hp]
+    assert [r[9] for r in recs[:4]] == [6000 + tap * g.Rp * 4 for tap in range(4)] and recs[4][5:] == (4000, g.Rp, 5000, g.Ku, 7000, 192)
+    assert all(r[:2] == (Z2, g.Rp) and r[5:9] == (1000, 8 * Z2, 2000, g.Rp) for r in recs[:3])
+    # no dx-hat above (the stack's top layer in the tile launches): no conv1x1_out record; 0: a placeholder that keeps the group's size
+    assert list(P.tn_layer_contractions(g, 4, 0.5, 1000, 8 * Z2, 2000, 3000, None, 5000, 6000, 512, 7000, 192)) == recs[:4]
+    assert list(P.tn_layer_contractions(g, 4, 0.5, 1000, 8 * Z2, 2000, 3000, 0, 5000, 6000, 512, 7000, 192))[4][5] == 0
+    # without local conditioning the last tap carries the ones column
+    g0 = P.Geometry.from_cfg(dict(CFG, R=64, G=128, S=64, Cc=0, upsample_scales=[]))
+    r0 = list(P.tn_layer_contractions(g0, 1, 1.0, 8, 8, 8, 0, None, 8, 8, 8, 8, 8))
+    assert len(r0) == g0.k and [r[3] for r in r0] == [-1, -1, g0.Rp]

@@ -13,9 +13,10 @@ layer's sqrt(.5):
 from __future__ import annotations
 
 import ctypes
+import dataclasses
 import math
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -111,27 +112,47 @@ def _arr(ctype, vals):
     return (ctype * len(vals))(*vals)
 
 
+def _tm_srcs(srcs):
+    """srcs: list of (device ptr int, row stride elems, cols, shift) -> the four arrays wae_gemm_tm / wae_gemm_tm_ce take"""
+    return (_arr(ctypes.c_void_p, [s[0] for s in srcs]), _arr(ctypes.c_int64, [s[1] for s in srcs]),
+            _arr(ctypes.c_int32, [s[2] for s in srcs]), _arr(ctypes.c_int32, [s[3] for s in srcs]))
+
+
 def _tm(eng, B, T, M, mode, alpha, srcs, w_ptr, out_ptr, out_stride, aux_ptr=None, aux_stride=0, flags=0, st=None):
     """srcs: list of (device ptr int, row stride elems, cols, shift)"""
     d = L.TmDesc(eng.dt, B, T, M, len(srcs), mode, alpha, flags)
-    ptrs = _arr(ctypes.c_void_p, [s[0] for s in srcs])
-    strides = _arr(ctypes.c_int64, [s[1] for s in srcs])
-    cols = _arr(ctypes.c_int32, [s[2] for s in srcs])
-    shifts = _arr(ctypes.c_int32, [s[3] for s in srcs])
-    L.check(eng.lib.wae_gemm_tm(ctypes.byref(d), ptrs, strides, cols, shifts, ctypes.c_void_p(w_ptr), ctypes.c_void_p(out_ptr),
+    L.check(eng.lib.wae_gemm_tm(ctypes.byref(d), *_tm_srcs(srcs), ctypes.c_void_p(w_ptr), ctypes.c_void_p(out_ptr),
                                 out_stride, ctypes.c_void_p(aux_ptr) if aux_ptr else None, aux_stride, st if st is not None else eng.stream()), "gemm_tm")
 
 
 def _tm_ce(eng, B, T, M, mode, srcs, w_ptr, out_ptr, out_stride, bias_ptr, ce):
     """wae_gemm_tm_ce (modes 5 / 6 of the wide head): ce is an L.TmCe"""
     d = L.TmDesc(eng.dt, B, T, M, len(srcs), mode, 1.0, 0)
-    ptrs = _arr(ctypes.c_void_p, [s[0] for s in srcs])
-    strides = _arr(ctypes.c_int64, [s[1] for s in srcs])
-    cols = _arr(ctypes.c_int32, [s[2] for s in srcs])
-    shifts = _arr(ctypes.c_int32, [s[3] for s in srcs])
-    L.check(eng.lib.wae_gemm_tm_ce(ctypes.byref(d), ptrs, strides, cols, shifts, ctypes.c_void_p(w_ptr),
+    L.check(eng.lib.wae_gemm_tm_ce(ctypes.byref(d), *_tm_srcs(srcs), ctypes.c_void_p(w_ptr),
                                    ctypes.c_void_p(out_ptr) if out_ptr else None, out_stride, ctypes.c_void_p(bias_ptr),
                                    ctypes.byref(ce), eng.stream()), "gemm_tm_ce")
+
+
+def _timed(eng, sink, fn):
+    """fn() -- with a list `sink` (bench.py's event hooks), between a pair of HIP events on the current stream, appended to it"""
+    if sink is None:
+        return fn()
+    cur = torch.cuda.current_stream(eng.device)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(cur)
+    fn()
+    e1.record(cur)
+    sink.append((e0, e1))
+
+
+def _await_packed_weights(eng):
+    """The backward's packed weights and cleared gradient accumulators: train_step queued that launch on a side stream right behind
+    weight norm (eng._early_pack: wait for it); any other caller packs here."""
+    early = eng.__dict__.pop("_early_pack", None)
+    if early is not None:
+        eng.join(early[0])
+    else:
+        pack_bwd_weights(eng)      # (also clears eng.d_eff and eng.cbuf)
 
 
 class TileTable:
@@ -167,21 +188,44 @@ class TileTable:
         L.check(eng.lib.wae_gemm_tn_tiles(eng.dt, L.ptr(self.dev), self.n, B, T, self.splits, eng.stream()), "gemm_tn_tiles")
 
 
-class StreamTable:
-    """Host builder for wae_gemm_tn_stream (csrc/gemm_tn_stream.hip): the weight-gradient contractions of every layer as
-    ONE launch.  A *group* is the list of jobs of one layer (every dilated-conv tap, the conditioning 1x1 with the per-clip
-    zb sums, conv1x1_out with its bias), each cut into 384 x 256 output regions; all groups have the same number of jobs.
-    The (group, 32-row time slab) list is cut into equal contiguous shares, one per *team* of len(group) workgroups."""
-    RM, RN, KT = 384, 256, 32
+def _ncu(eng):
+    return torch.cuda.get_device_properties(eng.device).multi_processor_count
+
+
+class _TeamTable:
+    """What the two team launches share: *groups* of equally many jobs, and the (group, 32-row time slab) list cut into equal
+    contiguous shares, one per *team* of len(group) workgroups (packing.tn_team_shares)."""
 
     def __init__(self, eng, B, T):
         self.eng, self.B, self.T = eng, B, T
-        self.groups = []          # list of lists of L.TsJob
-        self.lead_jobs = 0        # the first lead_jobs jobs of every group are full-size (the taps): the pacing reference
-        self.shifts = []          # most negative shift per group (slabs that pair only with rows before the clip are skipped)
+        self.groups = []          # list of lists of job records
 
     def begin_group(self):
         self.groups.append([])
+
+    def _upload(self, job_type, n_groups, ncu, swap=False):
+        """self.groups (swap: two variants of n_groups groups each) and their team shares on ncu CUs -> device arrays"""
+        gs = len(self.groups[0])
+        assert all(len(g) == gs for g in self.groups), "every layer must contribute the same list of jobs"
+        sh = P.tn_team_shares(n_groups, self.B, self.T, gs, ncu or _ncu(self.eng), swap)
+        self.team_size, self.nteams, self.nwg = gs, sh.nteams, sh.nwg
+        jobs = [j for g in self.groups for j in g]
+        segs = [L.TsSeg(*s) for s in sh.segs]
+        dev = self.eng.device
+        self.jobs_dev = torch.frombuffer(bytearray(bytes((job_type * len(jobs))(*jobs))), dtype=torch.uint8).to(dev)
+        self.segs_dev = torch.frombuffer(bytearray(bytes((L.TsSeg * len(segs))(*segs))), dtype=torch.uint8).to(dev)
+        self.team_seg_dev = torch.tensor(sh.team_seg, dtype=torch.int32, device=dev)
+
+
+class StreamTable(_TeamTable):
+    """Host builder for wae_gemm_tn_stream (csrc/gemm_tn_stream.hip): the weight-gradient contractions of every layer as
+    ONE launch.  A *group* is the list of jobs of one layer (every dilated-conv tap, the conditioning 1x1 with the per-clip
+    zb sums, conv1x1_out with its bias), each cut into 384 x 256 output regions; all groups have the same number of jobs."""
+    RM, RN, KT = 384, 256, 32
+
+    def __init__(self, eng, B, T):
+        super().__init__(eng, B, T)
+        self.lead_jobs = 0        # the first lead_jobs jobs of every group are full-size (the taps): the pacing reference
 
     def add(self, M, N, shift, ones_col, alpha, p_ptr, p_stride, q_ptr, q_stride, c_ptr, ldc):
         """C[M][N (+ B ones columns at ones_col)] += alpha * P^T Q ; p_ptr == 0: placeholder jobs that do nothing."""
@@ -202,34 +246,10 @@ class StreamTable:
                                                mv, nv, shift, oc, alpha, 0))
 
     def finalize(self):
-        eng, B, T = self.eng, self.B, self.T
-        gs = len(self.groups[0])
-        assert all(len(g) == gs for g in self.groups), "every layer must contribute the same list of jobs"
-        ncu = torch.cuda.get_device_properties(eng.device).multi_processor_count
-        spc = (T + self.KT - 1) // self.KT
-        segs, team_seg = [], [0]
-        self.team_size = gs
-        self.nteams = max(1, ncu // gs)
-        self.nwg = ncu if ncu % 8 == 0 and ncu >= self.nteams * gs else self.nteams * gs
-        # Every member of a team sweeps the same slab range; a slab is skipped by a member when all of its rows pair with
-        # rows before the clip (kernel: useful()).  Shares are cut on the raw slab count: the skipped slabs differ by tap.
-        total = len(self.groups) * B * spc
-        for t in range(self.nteams):
-            lo, hi = total * t // self.nteams, total * (t + 1) // self.nteams
-            while lo < hi:
-                grp = lo // (B * spc)
-                end = min(hi, (grp + 1) * B * spc)
-                segs.append(L.TsSeg(grp * gs, lo - grp * B * spc, end - grp * B * spc))
-                lo = end
-            team_seg.append(len(segs))
-        jobs = [j for g in self.groups for j in g]
-        dev = eng.device
-        self.jobs_dev = torch.frombuffer(bytearray(bytes((L.TsJob * len(jobs))(*jobs))), dtype=torch.uint8).to(dev)
-        self.segs_dev = torch.frombuffer(bytearray(bytes((L.TsSeg * len(segs))(*segs))), dtype=torch.uint8).to(dev)
-        self.team_seg_dev = torch.tensor(team_seg, dtype=torch.int32, device=dev)
+        self._upload(L.TsJob, len(self.groups), None)
         # (the kernel's team pacing and equal-time shares -- rounds 2-3, measured slower: profiles/EXPERIMENT_LOG.md -- stay reachable
         #  through wae_gemm_tn_stream's own arguments; the product launches unpaced teams)
-        self.pace = torch.zeros(self.nteams * 8, dtype=torch.int32, device=dev)
+        self.pace = torch.zeros(self.nteams * 8, dtype=torch.int32, device=self.eng.device)
         self.window, self.pace_from = 0, self.lead_jobs
         return self
 
@@ -292,17 +312,9 @@ def static_head(eng, B, T):
             and P._ru(g.O, 128) <= 384 and eng.opt_tn_static_head)
 
 
-class StaticStreamTable:
+class StaticStreamTable(_TeamTable):
     """Host builder for wae_gemm_tn_static: per layer one job per dilated-conv tap (TAPS), one for conv1x1c + the per-clip sums of
     dz (COND) and one for conv1x1_out + conv1x1_skip (OUTSKIP).  Teams and segments as StreamTable."""
-    KT = 32
-
-    def __init__(self, eng, B, T):
-        self.eng, self.B, self.T = eng, B, T
-        self.groups = []
-
-    def begin_group(self):
-        self.groups.append([])
 
     def add(self, **kw):
         f = dict(P=None, Q0=None, Q1=None, C0=None, C1=None, Cb=None, p_stride=0, q0_stride=0, q1_stride=0, ldc0=0, ldc1=0,
@@ -313,23 +325,13 @@ class StaticStreamTable:
 
     def finalize(self, ncu=None):
         """ncu: the CUs this launch may count on (default: all) -- a launch that runs BESIDE an under-filled sweep takes the idle ones"""
-        eng, B, T = self.eng, self.B, self.T
-        gs = len(self.groups[0])
-        assert all(len(g) == gs for g in self.groups), "every layer must contribute the same list of jobs"
-        ncu = ncu or torch.cuda.get_device_properties(eng.device).multi_processor_count
-        spc = (T + self.KT - 1) // self.KT
-        segs, team_seg = [], [0]
-        self.team_size = gs
-        self.nteams = max(1, ncu // gs)
-        self.nwg = ncu if ncu % 8 == 0 and ncu >= self.nteams * gs else self.nteams * gs
-        total = len(self.groups) * B * spc
         # The members of a team walk the same slabs, but a slab costs the out + skip member 704 operand columns (96 tiles), a tap member
         # 640 and the conditioning member 448 (36 tiles): by workgroup lives (tools/tq_member_lives.py, C2) 1 274 / 1 150-1 176 / 954 us,
         # and the launch ends with the slowest.  A member's job kind is a field of the job record, so the second half of every team's
         # share runs on a copy of the groups in which the last two slots have changed places: the two members each do half of both.
         # (One more segment per team = one more prologue + flush per member; the partial sums are added atomically either way.)
-        ng = len(self.groups)
-        swap = eng.opt.tn_swap and gs >= 2
+        ng, gs = len(self.groups), len(self.groups[0])
+        swap = bool(self.eng.opt.tn_swap and gs >= 2)
         if swap:
             def swapped(grp):
                 k = [j.kind if j.m_valid > 0 else -1 for j in grp]
@@ -337,27 +339,13 @@ class StaticStreamTable:
                     return grp[:-2] + [grp[-1], grp[-2]]
                 return grp
             self.groups = self.groups + [swapped(grp) for grp in self.groups]
-        for t in range(self.nteams):
-            lo, hi = total * t // self.nteams, total * (t + 1) // self.nteams
-            mid = (lo + hi) // 2 if swap else hi
-            for a, b_, var in ((lo, mid, 0), (mid, hi, 1)):
-                while a < b_:
-                    grp = a // (B * spc)
-                    end = min(b_, (grp + 1) * B * spc)
-                    segs.append(L.TsSeg((var * ng + grp) * gs, a - grp * B * spc, end - grp * B * spc))
-                    a = end
-            team_seg.append(len(segs))
-        jobs = [j for g in self.groups for j in g]
-        dev = eng.device
-        self.jobs_dev = torch.frombuffer(bytearray(bytes((L.TqJob * len(jobs))(*jobs))), dtype=torch.uint8).to(dev)
-        self.segs_dev = torch.frombuffer(bytearray(bytes((L.TsSeg * len(segs))(*segs))), dtype=torch.uint8).to(dev)
-        self.team_seg_dev = torch.tensor(team_seg, dtype=torch.int32, device=dev)
+        self._upload(L.TqJob, ng, ncu, swap)
         self.stamps = None          # diagnostic builds (-DWAE_TQ_STAMPS): an int64 [nwg][16][4] tensor, zeroed before the launch
         # (team pacing of the tap members -- round 4: 6.7 -> 4.7 GB of HBM traffic at identical time, profiles/r04_tq_experiments.txt --
         #  stays reachable through wae_gemm_tn_static's own arguments; the product launches unpaced: window 0)
         self.ntaps = gs - 2
         self.window = self.window_cond = 0
-        self.pace = torch.zeros(self.nteams, dtype=torch.int32, device=dev)
+        self.pace = torch.zeros(self.nteams, dtype=torch.int32, device=self.eng.device)
         return self
 
     def launch(self):
@@ -398,157 +386,141 @@ def bwd_workspace(eng, B, T):
     return ws
 
 
-def _build_stream_table(eng, ws, fw, B, T, l0, l1, ncu=None):
-    """The stream-K launch (csrc/gemm_tn_stream.hip) over the weight gradients of layers [l0, l1): dW1 taps, dWc + zb sums, dW_out +
-    bias of every layer of the range.  The whole stack is one launch; data-parallel steps cut it into an upper and a lower half so
-    that the upper half's slice of the gradient arena reaches the all-reduce in the middle of backward (decoder_backward)."""
+def _layer_operands(eng, ws, fw, l):
+    """Device addresses of layer l's weight-gradient operands: dz_l, the convolution's operand (dW1 contracts dz against it: the
+    masked one under dropout), u_l, and the layer's dense dW1 | dWc | zb tile"""
+    g, es, Z2 = eng.g, eng.w_glu.element_size(), 2 * eng.g.Hp
+    xl = fw["xd"][l] if "xd" in fw else fw["x"][l]
+    return (ws["dz"].data_ptr() + l * Z2 * es, xl.data_ptr(), fw["u"].data_ptr() + l * g.Hp * es,
+            eng.cview["c1"].data_ptr() + l * Z2 * eng.sm["ld1"] * 4)
+
+
+def _layer_contractions(eng, ws, fw, l, g_next):
+    """packing.tn_layer_contractions of layer l of the stack (g_next: address of dx-hat of layer l + 1, None or 0: see there)"""
     g, sm = eng.g, eng.sm
-    es = eng.w_glu.element_size()
-    Z2 = 2 * g.Hp
-    dzs = g.layers * Z2
-    c1, co = eng.cview["c1"], eng.cview["co"]
-    ia = 1.0 / eng.grad_scale
-    if static_tn_shape(eng, B, T):
-        coT, csT = eng.cview["coT"], eng.cview["csT"]
-        rows = sm["ldoT_rows"]
-        stt = StaticStreamTable(eng, B, T)
-        m_taps, n_taps = _cuts(Z2, 384, 64), _cuts(g.Rp, 256, 128)
-        m_cond = _cuts(Z2, 384, 32)
-        m_os, n_os0, n_os1 = _cuts(g.Hp, 192, 64), _cuts(g.Rp, 256, 128), _cuts(g.Sp, 256, 128)
+    dz, x, u, c1l = _layer_operands(eng, ws, fw, l)
+    return P.tn_layer_contractions(g, g.dilations[l], 1.0 / eng.grad_scale, dz, g.layers * 2 * g.Hp, x,
+                                   fw["c_up"].data_ptr() if g.Ccp else 0, g_next, u, c1l, sm["ld1"],
+                                   eng.cview["co"].data_ptr() + l * g.Rp * sm["ldo"] * 4, sm["ldo"])
 
-        def layer_jobs(l):
-            d = g.dilations[l]
-            dz_ptr = ws["dz"].data_ptr() + l * Z2 * es
-            c1l = c1.data_ptr() + l * Z2 * sm["ld1"] * 4
-            xl = fw["xd"][l] if "xd" in fw else fw["x"][l]      # dW1 contracts dz against the convolution's operand
-            jobs = []
-            for tap in range(g.k):
-                for m0, mw in m_taps:
-                    for n0, nw in n_taps:
-                        jobs.append(dict(kind=L.TQ_TAPS, P=dz_ptr + m0 * es, p_stride=dzs, m_valid=mw, Q0=xl.data_ptr() + n0 * es,
-                                         q0_stride=g.Rp, n0_valid=nw, shift=-(g.k - 1 - tap) * d,
-                                         C0=c1l + (m0 * sm["ld1"] + tap * g.Rp + n0) * 4, ldc0=sm["ld1"], alpha=ia))
-            for m0, mw in m_cond:
-                jobs.append(dict(kind=L.TQ_COND, P=dz_ptr + m0 * es, p_stride=dzs, m_valid=mw, Q0=fw["c_up"].data_ptr(), q0_stride=g.Ccp,
-                                 n0_valid=g.Ccp, ones_col=g.Ccp, C0=c1l + (m0 * sm["ld1"] + g.k * g.Rp) * 4, ldc0=sm["ld1"], alpha=ia))
-            has_out = l < g.layers - 1       # the last layer's x' is dead (wavenet.py:205-207): no conv1x1_out gradient
-            coTl = coT.data_ptr() + l * rows * g.Rp * 4
-            csTl = csT.data_ptr() + l * g.Hp * g.Sp * 4
-            u_ptr = fw["u"].data_ptr() + l * g.Hp * es
-            for m0, mw in m_os:
-                if has_out:
-                    for i in range(max(len(n_os0), len(n_os1))):
-                        j = dict(kind=L.TQ_OUTSKIP, P=u_ptr + m0 * es, p_stride=g.Ku, m_valid=mw, alpha=ia)
-                        if i < len(n_os0):
-                            n0, nw = n_os0[i]
-                            j.update(Q0=ws["gx"][l + 1].data_ptr() + n0 * es, q0_stride=g.Rp, n0_valid=nw,
-                                     C0=coTl + (m0 * g.Rp + n0) * 4, ldc0=g.Rp)
-                            if m0 == 0:          # the out bias: column sums of Ghat, formed by the job that holds rows 0..63 of u
-                                j.update(Cb=coTl + (g.Hp * g.Rp + n0) * 4)
-                        if i < len(n_os1):
-                            n1, nw1 = n_os1[i]
-                            j.update(Q1=ws["dskip"].data_ptr() + n1 * es, q1_stride=g.Sp, n1_valid=nw1,
-                                     C1=csTl + (m0 * g.Sp + n1) * 4, ldc1=g.Sp)
-                        jobs.append(j)
-                else:
-                    # ... which frees the job's first operand: dS takes its place, and the column sums the kernel forms of that operand
-                    # are the skip bias gradient (the same for every layer, modules.py:157-160)
-                    for n1, nw1 in n_os1:
-                        j = dict(kind=L.TQ_OUTSKIP, P=u_ptr + m0 * es, p_stride=g.Ku, m_valid=mw, Q0=ws["dskip"].data_ptr() + n1 * es,
-                                 q0_stride=g.Sp, n0_valid=nw1, C0=csTl + (m0 * g.Sp + n1) * 4, ldc0=g.Sp, alpha=ia)
-                        if m0 == 0:
-                            j.update(Cb=eng.cview["cbs"].data_ptr() + n1 * 4)
-                        jobs.append(j)
-            return jobs
 
-        # a layer's jobs form one group (a team of that many workgroups walks the layer's slabs) up to six jobs; more are dealt into
-        # equal groups of at most six -- jobs that share operands (the cuts of one tap) side by side --, padded with null jobs
-        njobs = max(len(layer_jobs(l)) for l in range(l0, l1))
-        ngrp = -(-njobs // 6) if njobs > 6 else 1
-        gsz = -(-njobs // ngrp)
+def _static_layer_jobs(eng, ws, fw, l):
+    """Layer l as job records of the static launch (StaticStreamTable.add's keywords): matrices wider than a region are cut"""
+    g, sm = eng.g, eng.sm
+    es, Z2, ia = eng.w_glu.element_size(), 2 * g.Hp, 1.0 / eng.grad_scale
+    dzs, d = g.layers * Z2, g.dilations[l]
+    dz_ptr, x_ptr, u_ptr, c1l = _layer_operands(eng, ws, fw, l)
+    m_taps, n_taps = _cuts(Z2, 384, 64), _cuts(g.Rp, 256, 128)
+    m_cond = _cuts(Z2, 384, 32)
+    m_os, n_os0, n_os1 = _cuts(g.Hp, 192, 64), _cuts(g.Rp, 256, 128), _cuts(g.Sp, 256, 128)
+    jobs = []
+    for tap in range(g.k):
+        for m0, mw in m_taps:
+            for n0, nw in n_taps:
+                jobs.append(dict(kind=L.TQ_TAPS, P=dz_ptr + m0 * es, p_stride=dzs, m_valid=mw, Q0=x_ptr + n0 * es,
+                                 q0_stride=g.Rp, n0_valid=nw, shift=-(g.k - 1 - tap) * d,
+                                 C0=c1l + (m0 * sm["ld1"] + tap * g.Rp + n0) * 4, ldc0=sm["ld1"], alpha=ia))
+    for m0, mw in m_cond:
+        jobs.append(dict(kind=L.TQ_COND, P=dz_ptr + m0 * es, p_stride=dzs, m_valid=mw, Q0=fw["c_up"].data_ptr(), q0_stride=g.Ccp,
+                         n0_valid=g.Ccp, ones_col=g.Ccp, C0=c1l + (m0 * sm["ld1"] + g.k * g.Rp) * 4, ldc0=sm["ld1"], alpha=ia))
+    has_out = l < g.layers - 1       # the last layer's x' is dead (wavenet.py:205-207): no conv1x1_out gradient
+    coTl = eng.cview["coT"].data_ptr() + l * sm["ldoT_rows"] * g.Rp * 4
+    csTl = eng.cview["csT"].data_ptr() + l * g.Hp * g.Sp * 4
+    for m0, mw in m_os:
+        if has_out:
+            for i in range(max(len(n_os0), len(n_os1))):
+                j = dict(kind=L.TQ_OUTSKIP, P=u_ptr + m0 * es, p_stride=g.Ku, m_valid=mw, alpha=ia)
+                if i < len(n_os0):
+                    n0, nw = n_os0[i]
+                    j.update(Q0=ws["gx"][l + 1].data_ptr() + n0 * es, q0_stride=g.Rp, n0_valid=nw,
+                             C0=coTl + (m0 * g.Rp + n0) * 4, ldc0=g.Rp)
+                    if m0 == 0:          # the out bias: column sums of Ghat, formed by the job that holds rows 0..63 of u
+                        j.update(Cb=coTl + (g.Hp * g.Rp + n0) * 4)
+                if i < len(n_os1):
+                    n1, nw1 = n_os1[i]
+                    j.update(Q1=ws["dskip"].data_ptr() + n1 * es, q1_stride=g.Sp, n1_valid=nw1,
+                             C1=csTl + (m0 * g.Sp + n1) * 4, ldc1=g.Sp)
+                jobs.append(j)
+        else:
+            # ... which frees the job's first operand: dS takes its place, and the column sums the kernel forms of that operand
+            # are the skip bias gradient (the same for every layer, modules.py:157-160)
+            for n1, nw1 in n_os1:
+                j = dict(kind=L.TQ_OUTSKIP, P=u_ptr + m0 * es, p_stride=g.Ku, m_valid=mw, Q0=ws["dskip"].data_ptr() + n1 * es,
+                         q0_stride=g.Sp, n0_valid=nw1, C0=csTl + (m0 * g.Sp + n1) * 4, ldc0=g.Sp, alpha=ia)
+                if m0 == 0:
+                    j.update(Cb=eng.cview["cbs"].data_ptr() + n1 * 4)
+                jobs.append(j)
+    return jobs
+
+
+def _static_head_group(eng, ws, fw, l0, l1):
+    """The group of jobs that rides with layers [l0, l1) of the static launch (static_head): the head's with the top layer, the first
+    conv's with the bottom one; [] when neither is in the range"""
+    g, sm, ia = eng.g, eng.sm, 1.0 / eng.grad_scale
+    gs = g.k + 2
+    first = None
+    if not g.scalar_input and l0 == 0:
+        W1 = P._ru(g.O, 128)
+        first = dict(kind=L.TQ_TAPS, P=ws["onehot"].data_ptr(), p_stride=W1, m_valid=W1, Q0=ws["gx"][0].data_ptr(),
+                     q0_stride=g.Rp, n0_valid=g.Rp, C0=eng.cview["ctab"].data_ptr(), ldc0=g.Rp, alpha=ia / RS)
+    if l1 < g.layers:
+        return ([first] + [{}] * (gs - 1)) if first else []
+    # the head: two contractions and two column-sum jobs (kind COND without a Q operand: per-clip sums of P's columns,
+    # the layout the ones columns of the tile launches had); the first conv's takes the free third slot
+    c3, c1h = eng.cview["c3"].data_ptr(), eng.cview["c1h"].data_ptr()
+    dy, dh1 = ws["dy"].data_ptr(), ws["dh1"].data_ptr()
+    return [dict(kind=L.TQ_TAPS, P=dy, p_stride=g.Op, m_valid=g.Op, Q0=fw["h1"].data_ptr(), q0_stride=g.Sp, n0_valid=g.Sp,
+                 C0=c3, ldc0=sm["ldh"], alpha=ia),
+            dict(kind=L.TQ_TAPS, P=dh1, p_stride=g.Sp, m_valid=g.Sp, Q0=fw["h0"].data_ptr(), q0_stride=g.Sp, n0_valid=g.Sp,
+                 C0=c1h, ldc0=sm["ldh"], alpha=ia),
+            first or {}] + [{}] * (gs - 5) + [
+            dict(kind=L.TQ_COND, P=dy, p_stride=g.Op, m_valid=g.Op, ones_col=g.Sp, C0=c3, ldc0=sm["ldh"], alpha=ia),
+            dict(kind=L.TQ_COND, P=dh1, p_stride=g.Sp, m_valid=g.Sp, ones_col=g.Sp, C0=c1h, ldc0=sm["ldh"], alpha=ia)]
+
+
+def _build_stream_table(eng, ws, fw, B, T, l0, l1, ncu=None):
+    """One team launch over the weight gradients of layers [l0, l1): dW1 taps, dWc + zb sums, dW_out + bias of every layer of the
+    range -- the static launch where it can address the shape (static_tn_shape), else the any-shape stream-K launch.  Which ranges
+    a step launches, and where: _tn_schedule."""
+    g = eng.g
+    if not static_tn_shape(eng, B, T):
+        assert ncu is None, "a CU budget is a feature of the static launch"
+        stt = StreamTable(eng, B, T)
         for l in range(l0, l1):
-            jobs = layer_jobs(l)
-            jobs += [{}] * (ngrp * gsz - len(jobs))
-            for gi in range(ngrp):
-                stt.begin_group()
-                for j in jobs[gi * gsz:(gi + 1) * gsz]:
-                    stt.add(**j)
-        if static_head(eng, B, T):
-            gs = g.k + 2
-            first = None
-            if not g.scalar_input and l0 == 0:
-                W1 = P._ru(g.O, 128)
-                first = dict(kind=L.TQ_TAPS, P=ws["onehot"].data_ptr(), p_stride=W1, m_valid=W1, Q0=ws["gx"][0].data_ptr(),
-                             q0_stride=g.Rp, n0_valid=g.Rp, C0=eng.cview["ctab"].data_ptr(), ldc0=g.Rp, alpha=ia / RS)
-            if l1 == g.layers:
-                # the head: two contractions and two column-sum jobs (kind COND without a Q operand: per-clip sums of P's columns,
-                # the layout the ones columns of the tile launches had); the first conv's takes the free third slot
-                c3, c1h = eng.cview["c3"].data_ptr(), eng.cview["c1h"].data_ptr()
-                dy, dh1 = ws["dy"].data_ptr(), ws["dh1"].data_ptr()
-                grp = [dict(kind=L.TQ_TAPS, P=dy, p_stride=g.Op, m_valid=g.Op, Q0=fw["h1"].data_ptr(), q0_stride=g.Sp, n0_valid=g.Sp,
-                            C0=c3, ldc0=sm["ldh"], alpha=ia),
-                       dict(kind=L.TQ_TAPS, P=dh1, p_stride=g.Sp, m_valid=g.Sp, Q0=fw["h0"].data_ptr(), q0_stride=g.Sp, n0_valid=g.Sp,
-                            C0=c1h, ldc0=sm["ldh"], alpha=ia)]
-                grp += [first or {}] + [{}] * (gs - 5)
-                grp += [dict(kind=L.TQ_COND, P=dy, p_stride=g.Op, m_valid=g.Op, ones_col=g.Sp, C0=c3, ldc0=sm["ldh"], alpha=ia),
-                        dict(kind=L.TQ_COND, P=dh1, p_stride=g.Sp, m_valid=g.Sp, ones_col=g.Sp, C0=c1h, ldc0=sm["ldh"], alpha=ia)]
-            else:
-                grp = ([first] + [{}] * (gs - 1)) if first else []
-            if grp:
-                stt.begin_group()
-                for j in grp:
-                    stt.add(**j)
-        return stt.finalize(ncu)
-    assert ncu is None, "a CU budget is a feature of the static launch"
-    stt = StreamTable(eng, B, T)
-    for l in range(l0, l1):
-        d = g.dilations[l]
-        stt.begin_group()
-        dz_ptr = ws["dz"].data_ptr() + l * Z2 * es
-        c1l = c1.data_ptr() + l * Z2 * sm["ld1"] * 4
-        xl = fw["xd"][l] if "xd" in fw else fw["x"][l]      # dW1 contracts dz against the convolution's operand
-        for tap in range(g.k):
-            last = tap == g.k - 1 and not g.Ccp
-            stt.add(Z2, g.Rp, -(g.k - 1 - tap) * d, (g.Rp if last else -1), ia, dz_ptr, dzs, xl.data_ptr(), g.Rp,
-                    c1l + tap * g.Rp * 4, sm["ld1"])
-        if g.Ccp:
-            stt.add(Z2, g.Ccp, 0, g.Ccp, ia, dz_ptr, dzs, fw["c_up"].data_ptr(), g.Ccp, c1l + g.k * g.Rp * 4, sm["ld1"])
-        has_out = l < g.layers - 1
-        stt.add(g.Rp, g.Hp, 0, g.Hp, ia, ws["gx"][l + 1].data_ptr() if has_out else 0, g.Rp,
-                fw["u"].data_ptr() + l * g.Hp * es, g.Ku, co.data_ptr() + l * g.Rp * sm["ldo"] * 4, sm["ldo"])
-    stt.lead_jobs = g.k
-    return stt.finalize()
+            stt.begin_group()
+            for rec in _layer_contractions(eng, ws, fw, l, ws["gx"][l + 1].data_ptr() if l < g.layers - 1 else 0):
+                stt.add(*rec)
+        stt.lead_jobs = g.k
+        return stt.finalize()
+    stt = StaticStreamTable(eng, B, T)
+    layers = [_static_layer_jobs(eng, ws, fw, l) for l in range(l0, l1)]
+    # jobs that share operands (the cuts of one tap) stay side by side in their group
+    ngrp, gsz = P.tn_job_groups(max(len(jobs) for jobs in layers))
+    groups = [(jobs + [{}] * (ngrp * gsz - len(jobs)))[gi * gsz:(gi + 1) * gsz] for jobs in layers for gi in range(ngrp)]
+    if static_head(eng, B, T):
+        groups.append(_static_head_group(eng, ws, fw, l0, l1))
+    for grp in groups:
+        if grp:
+            stt.begin_group()
+            for j in grp:
+                stt.add(**j)
+    return stt.finalize(ncu)
 
 
 def _build_tile_tables(eng, ws, fw, B, T):
     """All weight-gradient contractions of a step as two kinds of launches: one table per layer (dW1 taps, dWc + zb sums,
     dW_out + bias) and one global table (dW_skip of every layer + bias, head matrices + biases, first-conv table)."""
     g, sm = eng.g, eng.sm
-    es = eng.w_glu.element_size()
-    Z2 = 2 * g.Hp
-    dzs = g.layers * Z2
-    c1, co = eng.cview["c1"], eng.cview["co"]
     ia = 1.0 / eng.grad_scale       # fp16: the 16-bit gradients are loss-scaled, the fp32 weight gradients are not
     ws["tt_layer"] = []
     ws["stream"] = None
     if use_stream_tn(eng):
         ws["stream"] = _build_stream_table(eng, ws, fw, B, T, 0, g.layers)
     for l in range(g.layers if ws["stream"] is None else 0):
-        d = g.dilations[l]
         tt = TileTable(eng)
-        dz_ptr = ws["dz"].data_ptr() + l * Z2 * es
-        c1l = c1.data_ptr() + l * Z2 * sm["ld1"] * 4
-        xl = fw["xd"][l] if "xd" in fw else fw["x"][l]
-        for tap in range(g.k):
-            last = tap == g.k - 1 and not g.Ccp
-            tt.add(Z2, g.Rp, -(g.k - 1 - tap) * d, (g.Rp if last else -1), ia, dz_ptr, dzs, xl.data_ptr(), g.Rp,
-                   c1l + tap * g.Rp * 4, sm["ld1"])
-        if g.Ccp:
-            tt.add(Z2, g.Ccp, 0, g.Ccp, ia, dz_ptr, dzs, fw["c_up"].data_ptr(), g.Ccp, c1l + g.k * g.Rp * 4, sm["ld1"])
-        if l < g.layers - 1:
-            g_next = ws["gx"][(l + 1) % len(ws["gx"])]
-            tt.add(g.Rp, g.Hp, 0, g.Hp, ia, g_next.data_ptr(), g.Rp, fw["u"].data_ptr() + l * g.Hp * es, g.Ku,
-                   co.data_ptr() + l * g.Rp * sm["ldo"] * 4, sm["ldo"])
+        g_next = ws["gx"][(l + 1) % len(ws["gx"])].data_ptr() if l < g.layers - 1 else None
+        for rec in _layer_contractions(eng, ws, fw, l, g_next):
+            tt.add(*rec)
         ws["tt_layer"].append(tt.finalize(B))
     tt = TileTable(eng)
     c3, c1h, cs, ctab = eng.cview["c3"], eng.cview["c1h"], eng.cview["cs"], eng.cview["ctab"]
@@ -596,39 +568,302 @@ def _wn_bwd_range(eng, lo, hi):
                                               L.ptr(eng.wn_g), L.ptr(eng.wn_c), r0, r1, eng.stream()), "weight_norm_bwd")
 
 
-def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: Optional[torch.Tensor],
-                     gid: Optional[torch.Tensor], gvec: Optional[torch.Tensor] = None, ext_dy: Optional[torch.Tensor] = None,
-                     loss_scale: float = 1.0, grad_sync=None):
-    """Backward of the last ``decoder_forward(..., train=True)`` with the same (B, T).  Fills ``eng.grads`` (flat arena,
-    reference parameter layout incl. weight_g / weight_v) for every decoder parameter and returns dc (B,T,Ccp): the
-    gradient wrt the upsampled local conditioning.  ``ext_dy`` (B,T,Op): external d loss / d logits (DMoL).
-    ``grad_sync`` (distributed.GradSync): the layers' + head's slice of the gradient arena is finished (weight-norm backward
-    of that slice) and handed to the all-reduce BEFORE the conditioning / first-conv / front-end gradients are computed, so
-    the collective runs under them."""
-    _prepare_bwd(eng)
-    g, lib, lay, st = eng.g, eng.lib, eng.lay, eng.stream()
-    B, T = x_ids.shape
-    fw = eng._ws[(B, T, True)]
-    ws = bwd_workspace(eng, B, T)
-    es = eng.w_glu.element_size()
-    sm = eng.sm
-    early = eng.__dict__.pop("_early_pack", None)
-    if early is not None:          # train_step queued it on a side stream right behind weight norm
-        eng.join(early[0])
-    else:
-        pack_bwd_weights(eng)      # (also clears eng.d_eff and eng.cbuf)
-    if lengths is None:
-        count = B * (T - 1)
-    else:
-        count = int(torch.clamp(lengths.detach().to("cpu", torch.int64).clamp(max=T) - 1, min=0).sum())
-    inv_count = loss_scale * eng.grad_scale / max(count, 1)
-    xi = x_ids.to(torch.int32).contiguous() if not g.scalar_input else None
-    tg = targets.to(torch.int32).contiguous() if targets is not None else None
-    ln = lengths.to(torch.int32).to(eng.device).contiguous() if lengths is not None else None
-    keep = [xi, tg, ln]
+@dataclasses.dataclass
+class _Step:
+    """The per-call quantities of one backward, handed from phase to phase.  A *part* is (b0, nb, stc): the clips of a chain and its
+    stream -- every array of the sweep is clip-major, so a chain is the same call on its clips (engine.chain_plan); (0, B, None) = the
+    whole batch on the current stream."""
+    eng: object
+    ws: dict
+    fw: dict
+    B: int
+    T: int
+    es: int                       # bytes of a storage element
+    Z2: int                       # columns of one layer's z / dz
+    dzs: int                      # row stride of dz: every layer's columns side by side
+    us_off: int                   # bytes: the W_skip chunks follow the W_out chunks in the mode-2 stream
+    seeds: Optional[list] = None  # dropout: the mask seeds of the train-mode forward
+    fold_dc: bool = False
+    tm_ev: Optional[dict] = None  # bench.py: {"gate": [(e0, e1), ...], "res": [...], "pair": [...], "sweep": [...]}
+    tn_ev: Optional[list] = None  # bench.py: one (e0, e1) per weight-gradient launch
+    plan: Optional[tuple] = None  # engine.chain_plan
+    parts: tuple = ()
+    gid32: Optional[torch.Tensor] = None
+    use_gid: bool = False
+    gvec: Optional[torch.Tensor] = None
+    beside_done: Optional[list] = None
 
-    # ---- head --------------------------------------------------------------------------------------------------
-    hd = L.HeadDesc(eng.dt, B, T, g.Ku, g.Sp, g.Op, g.O, math.sqrt(1.0 / g.layers))
+    def sink(self, kind, stc=None):
+        """the event list of a launch family (HIP events bracket the current stream's launches only)"""
+        return None if self.tm_ev is None or stc is not None else self.tm_ev.setdefault(kind, [])
+
+
+def _step(eng, B, T, seeds=None):
+    g = eng.g
+    is16 = eng.dt in (L.WAE_BF16, L.WAE_F16)
+    # 16-bit fused sweep, three taps, 64 conditioning columns: dc = sum_l Wc_l^T dz_l is folded into the pair launches (phase A's
+    # shift-0 tap already holds dz_l[t] as MFMA operand): an fp32 running sum over the layers, written in the storage dtype by the
+    # launch of layer 0 (which runs the pair kernel's first half only) -- the K = L * 2Hp launch that re-read every dz is gone
+    fold_dc = bool(eng.fused_bwd and seeds is None and is16 and g.k == 3 and g.Ccp == 64 and eng.opt.bwd_fold_dc)
+    return _Step(eng, eng._ws[("bwd", B, T)], eng._ws[(B, T, True)], B, T, eng.w_glu.element_size(), 2 * g.Hp, g.layers * 2 * g.Hp,
+                 (g.Rp // (64 if is16 else 32)) * g.NP * 4 * 1024, seeds, fold_dc, getattr(eng, "_tm_events", None),
+                 getattr(eng, "_tn_events", None), parts=((0, B, None),))
+
+
+def _k_u(cx, l, gn, part, flags=0):
+    """du -> dz of layer l from gn = dx-hat of the layer above"""
+    eng, g, ws, T, es, Z2, dzs = cx.eng, cx.eng.g, cx.ws, cx.T, cx.es, cx.Z2, cx.dzs
+    b0, nb, stc = part
+    r = b0 * T * es
+    srcs, w = [(ws["dskip"].data_ptr() + r * g.Sp, g.Sp, g.Sp, 0)], eng.w_bu.data_ptr() + l * eng.n_bu * es
+    if gn.data_ptr() == ws["gzero"].data_ptr():
+        # the top layer: dx-hat above it is zero (its x' is dead), so W_out^T . 0 is left out -- the skip half of the weight stream
+        # on dS alone: the same sums (+ 0 exactly), half the chunks, 32 MB of zeros not read
+        w += cx.us_off
+    else:
+        srcs.insert(0, (gn.data_ptr() + r * g.Rp, g.Rp, g.Rp, 0))
+    _timed(eng, cx.sink("gate", stc), lambda: _tm(eng, nb, T, g.Hp, 2, 1.0, srcs, w, ws["dz"].data_ptr() + l * Z2 * es + r * dzs, dzs,
+                                                  cx.fw["z"][l].data_ptr() + r * Z2, Z2, flags=flags, st=stc))
+
+
+def _k_x(cx, l, gn, gc, part, flags=0):
+    """dx-hat of layer l into gc, from dz_l and gn = dx-hat of the layer above"""
+    eng, g, ws, B, T, es, Z2, dzs = cx.eng, cx.eng.g, cx.ws, cx.B, cx.T, cx.es, cx.Z2, cx.dzs
+    b0, nb, stc = part
+    r = b0 * T * es
+    srcs = [(ws["dz"].data_ptr() + l * Z2 * es + r * dzs, dzs, Z2, (g.k - 1 - tap) * g.dilations[l]) for tap in range(g.k)]
+    w = eng.w_bx.data_ptr() + l * eng.n_bx * es
+    if cx.seeds is None:
+        _timed(eng, cx.sink("res", stc), lambda: _tm(eng, nb, T, g.Rp, 1, RS, srcs, w, gc.data_ptr() + r * g.Rp, g.Rp,
+                                                     gn.data_ptr() + r * g.Rp, g.Rp, flags=P.TM_INTERLEAVE | flags, st=stc))
+    else:
+        # dropout: the tap contraction alone (mode 0), then out = sqrt(.5) * (g_next + keep * acc / (1 - p)) with the mask
+        # the forward applied to this layer's convolution operand
+        _tm(eng, B, T, g.Rp, 0, 1.0, srcs, w, ws["gtmp"].data_ptr(), g.Rp, flags=P.TM_INTERLEAVE)
+        L.check(eng.lib.wae_dropout_bwd(L.ptr(ws["gtmp"]), L.ptr(gn), L.ptr(gc), B * T * g.Rp, cx.seeds[l], eng.dropout, RS, eng.dt,
+                                        eng.stream()), "dropout_bwd")
+
+
+def _k_pair(cx, l, g_next, g_cur):
+    """K_X of layer l and K_U of layer l-1 in one launch per chain (csrc/glu_bwd.hip); layer 0 (fold_dc): K_X + the last dc term only"""
+    eng, g, ws, T, es, Z2, dzs = cx.eng, cx.eng.g, cx.ws, cx.T, cx.es, cx.Z2, cx.dzs
+    lib, lp = eng.lib, max(l - 1, 0)
+    cbytes = (Z2 // 64) * 8192                # bytes of one layer's chunks in the dc weight stream (packing.bwd_c_map)
+    for b0, nb, stc in cx.parts:
+        d = L.GluBwdDesc(eng.dt, nb, T, g.Rp, g.Hp, g.Sp, g.k, g.dilations[l], RS)
+        r = b0 * T * es
+        args = [ctypes.byref(d), ctypes.c_void_p(ws["dz"].data_ptr() + l * Z2 * es + r * dzs), dzs,
+                ctypes.c_void_p(g_next.data_ptr() + r * g.Rp), ctypes.c_void_p(g_cur.data_ptr() + r * g.Rp),
+                ctypes.c_void_p(ws["dskip"].data_ptr() + r * g.Sp), ctypes.c_void_p(cx.fw["z"][lp].data_ptr() + r * Z2),
+                ctypes.c_void_p(ws["dz"].data_ptr() + lp * Z2 * es + r * dzs),
+                ctypes.c_void_p((eng.w_bxf if hasattr(eng, "w_bxf") else eng.w_bx).data_ptr() + l * eng.n_bx * es),
+                ctypes.c_void_p(eng.w_buo.data_ptr() + lp * eng.n_buo * es),
+                ctypes.c_void_p(eng.w_bu.data_ptr() + lp * eng.n_bu * es + cx.us_off)]
+        sq = stc if stc is not None else eng.stream()
+        if cx.fold_dc:
+            mode = (0 if l == g.layers - 1 else 1) | (2 if l == 0 else 0) | (4 if getattr(eng, "bwd_pair4", False) else 0)
+            # (bit 2: keep the 4-wave kernel where the 8-wave one, csrc/glu_bwd8.hip, has an instantiation -- tests and tools)
+            args += [ctypes.c_void_p(eng.w_bc.data_ptr() + l * cbytes), ctypes.c_void_p(ws["dc32"].data_ptr() + b0 * T * 64 * 4),
+                     ctypes.c_void_p(ws["dc"].data_ptr() + r * ws["dc"].shape[-1]), mode, int(l == 0)]
+            _timed(eng, cx.sink("pair", stc), lambda: L.check(lib.wae_glu_bwd_fused_dc(*args, sq), "glu_bwd_fused_dc"))
+        else:
+            _timed(eng, cx.sink("pair", stc), lambda: L.check(lib.wae_glu_bwd_fused(*args, sq), "glu_bwd_fused"))
+
+
+class TnSchedule(NamedTuple):
+    """Where a step's weight-gradient launches go, decided once per (B, T) workspace and situation (_tn_schedule):
+        "tiles":  one tile launch per layer inside the sweep (fp32, WAE_TN_STREAM=0)
+        "whole":  `end` = every layer in one team launch behind the sweep
+        "split":  data parallel -- `mid` = layers [cut, L) and the head leave the sweep at layer cut, so that their slice of the
+                  gradient arena reaches the all-reduce in the middle of backward; `end` = layers [0, cut) behind the sweep
+        "beside": an under-filled sweep -- `mid` = layers [cut, L) start at layer cut on a side stream, sized for the idle CUs,
+                  `end` = layers [0, cut) behind the sweep"""
+    kind: str
+    cut: int          # the layer of the sweep behind which `mid` is launched; -1: nothing leaves the sweep
+    mid: object
+    end: object
+
+
+def _tn_schedule(cx, sync):
+    """The TnSchedule of this workspace for `sync` (a data-parallel step) and dropout; builds the tables it names on first use."""
+    eng, g, ws, fw, B, T = cx.eng, cx.eng.g, cx.ws, cx.fw, cx.B, cx.T
+    key = ("tn_schedule", sync, cx.seeds is not None)
+    sched = ws.get(key)
+    if sched is not None:
+        return sched
+    if ws["stream"] is None:
+        sched = TnSchedule("tiles", -1, None, None)
+    elif sync and g.layers >= 4 and eng.opt.dp_split:       # (WAE_DP_SPLIT=0: one hand-over at the end)
+        cut = g.layers // 2
+        if "stream_hi" not in ws:
+            ws["stream_hi"] = _build_stream_table(eng, ws, fw, B, T, cut, g.layers)
+            ws["stream_lo"] = _build_stream_table(eng, ws, fw, B, T, 0, cut)
+        sched = TnSchedule("split", cut, ws["stream_hi"], ws["stream_lo"])
+    else:
+        sched = TnSchedule("whole", -1, None, ws["stream"])
+        # ---- an UNDER-FILLED sweep (hps/vqwae.json's shard: 160 workgroups per launch on 256 CUs): the weight gradients of the upper
+        #      layers (+ the head's) run BESIDE the lower part of the sweep, as a launch sized for the idle CUs on a side stream; the lower
+        #      layers' follow the sweep as before.  Measured at that shard (20 layers, 96 idle CUs; ms per train step, one box): 6 / 8 /
+        #      10 / 12 / 14 layers beside the sweep 3.247 / 3.226-3.239 / 3.223-3.230 / 3.230 / 3.287 against 3.37-3.39 without.  The
+        #      side launch runs a layer's share in ~114 us on 96 CUs (all 256: 31 -- its teams no longer sit on one XCD each, and the
+        #      sweep's launches share L2 and HBM with it) and slows the sweep's launches by ~5 % (the rule: packing.tn_beside_split)
+        ncu = _ncu(eng)
+        up = P.tn_beside_split(g.layers, B, T, ncu)
+        if up is not None and not sync and eng.opt.side and isinstance(ws["stream"], StaticStreamTable) and cx.seeds is None:
+            if "stream_beside" not in ws:
+                ws["stream_beside"] = _build_stream_table(eng, ws, fw, B, T, up[0], g.layers, ncu=up[1])
+                # with an encoder in front, the front end's backward is a chain of ~20 small launches (~0.3 ms) that starts at the end of
+                # the sweep on its own side stream (engine.backward): the lower layers' launch leaves it 32 CUs instead of taking
+                # every SIMD's registers (0 / 32 / 48 / 64 CUs left: 3.20-3.21 / 3.08-3.14 / 3.10 / 3.11 ms per step at hps/vqwae.json)
+                ws["stream_below"] = _build_stream_table(eng, ws, fw, B, T, 0, up[0], ncu=(ncu - 32) if g.has_encoder else None)
+            sched = TnSchedule("beside", up[0], ws["stream_beside"], ws["stream_below"])
+    ws[key] = sched
+    return sched
+
+
+def _fork(cx):
+    """The sweep's parts from here on: the whole batch, or (engine.chain_plan) two chains, the second started late on a side stream"""
+    if cx.plan is None:
+        return ((0, cx.B, None),)
+    side = cx.eng.chain_fork(cx.plan[1])
+    return ((0, cx.plan[0], None), (cx.plan[0], cx.B - cx.plan[0], ctypes.c_void_p(side.cuda_stream)))
+
+
+def _leave_sweep(cx, work):
+    """The one place where launches that read the sweep's results start before its end: whatever work() enqueues (on the current
+    stream or on streams ordered behind it) reads rows of BOTH chains, so the chains are joined first and forked again behind it."""
+    if cx.plan is not None:
+        cx.eng.chain_join()
+    work()
+    cx.parts = _fork(cx)
+
+
+def _hand_over(cx, grad_sync, lo, hi):
+    """data parallel: the arena slice [lo, hi) is final -> its weight-norm backward, and its all-reduce starts"""
+    _wn_bwd_range(cx.eng, lo, hi)
+    grad_sync.ready_range(lo, hi)
+
+
+def _tn_mid_sweep(cx, sched, grad_sync):
+    """dz, dx-hat and the saved activations of layers [sched.cut, L) are complete: their weight gradients start"""
+    eng = cx.eng
+    if sched.kind == "beside":           # on the idle CUs
+        with eng.branch(1) as cx.beside_done:
+            _timed(eng, cx.tn_ev, sched.mid.launch)
+    else:                                # split: the head's and theirs into the arena, and the all-reduce of ~half the arena starts
+        _timed(eng, cx.tn_ev, sched.mid.launch)           # while the lower half of the sweep still runs
+        _finish_layers(cx, sched.cut, eng.g.layers, with_head=True)
+        _hand_over(cx, grad_sync, layer_segment_mid(eng), layer_segment(eng)[1])
+
+
+def _sweep(cx, sched, grad_sync):
+    """The gated stack below the top layer's K_U, last layer first; dx-hat of layer 0 lands in gx[0]"""
+    eng, g, ws = cx.eng, cx.eng.g, cx.ws
+    ngx = len(ws["gx"])
+    fused = eng.fused_bwd and cx.seeds is None
+    g_next = ws["gzero"]                      # dxhat_{L} = 0: the last layer's x' is dead (wavenet.py:205-207)
+    cx.parts = _fork(cx)
+    for l in range(g.layers - 1, -1, -1):
+        assert l == g.layers - 1 or g_next.data_ptr() == ws["gx"][(l + 1) % ngx].data_ptr()
+        if sched.kind == "tiles":              # needs dz_l and dx_{l+1}-hat
+            _timed(eng, cx.tn_ev, lambda: ws["tt_layer"][l].launch(cx.B, cx.T))
+        g_cur = ws["gx"][l % ngx]
+        if fused and (l > 0 or cx.fold_dc):
+            _k_pair(cx, l, g_next, g_cur)
+        else:
+            for part in cx.parts:
+                _k_x(cx, l, g_next, g_cur, part)
+                if l > 0:
+                    _k_u(cx, l - 1, g_cur, part)
+        g_next = g_cur
+        if l == sched.cut:
+            _leave_sweep(cx, lambda: _tn_mid_sweep(cx, sched, grad_sync))
+    if cx.plan is not None:
+        eng.chain_join()
+    assert g_next.data_ptr() == ws["gx"][0].data_ptr()
+
+
+def _scatter_jobs(cx, l0, l1, with_head):
+    """The wae_scatter_job array of _finish_layers(l0, l1, with_head): built once per workspace and range"""
+    eng, g, sm, Z2 = cx.eng, cx.eng.g, cx.eng.sm, cx.Z2
+    cv, OP = eng.cview, P.ONES_PAD
+    nb, ls = l1 - l0, eng.lay.layer_stride
+
+    def sjob(src, mp, rows, cols, ld, off=0, nb=1, ss=0, ds=0, unique=1, doff=0):
+        return L.ScatterJob(src.data_ptr() + off * 4, mp.data_ptr(), eng.d_eff.data_ptr() + doff * 4, rows * cols, ss, ds, ld, nb,
+                            cols, unique, 0)
+    per = dict(nb=nb, ds=ls, doff=l0 * ls)     # one block per layer of the range
+    static = isinstance(cx.ws["stream"], StaticStreamTable)
+    lst = [sjob(cv["c1"], sm["w1"], Z2, sm["ncol1"], sm["ld1"], off=l0 * Z2 * sm["ld1"], ss=Z2 * sm["ld1"], **per)]
+    if static:      # transposed dW_out (+ its bias row) and dW_skip blocks of the static stream launch, per layer
+        coT, csT, rows = cv["coT"], cv["csT"], sm["ldoT_rows"]
+        lst += [sjob(coT, sm["woT"], g.Hp, g.Rp, g.Rp, off=l0 * rows * g.Rp, ss=rows * g.Rp, **per),
+                sjob(coT, sm["boT"], 1, g.Rp, g.Rp, off=l0 * rows * g.Rp + g.Hp * g.Rp, ss=rows * g.Rp, **per),
+                sjob(csT, sm["wsT"], g.Hp, g.Sp, g.Sp, off=l0 * g.Hp * g.Sp, ss=g.Hp * g.Sp, **per),
+                sjob(cv["cbs"], sm["bsT"], 1, g.Sp, g.Sp, ss=0, **per)]
+    else:
+        co, cs = cv["co"], cv["cs"]
+        lst += [sjob(co, sm["wo"], g.Rp, g.Hp, sm["ldo"], off=l0 * g.Rp * sm["ldo"], ss=g.Rp * sm["ldo"], **per),
+                sjob(co, sm["bo"], g.Rp, OP, sm["ldo"], off=l0 * g.Rp * sm["ldo"] + g.Hp, ss=g.Rp * sm["ldo"], unique=2, **per),
+                sjob(cs, sm["bs"], g.Sp, OP, sm["lds"], off=g.Ku, ss=0, unique=2, **per)]
+    if with_head:
+        c3, c1h = cv["c3"], cv["c1h"]
+        if not static:
+            lst.append(sjob(cv["cs"], sm["ws"], g.Sp, g.Ku, sm["lds"]))
+        lst += [sjob(c3, sm["w3"], g.Op, g.Sp, sm["ldh"]),
+                sjob(c3, sm["b3"], g.Op, OP, sm["ldh"], off=g.Sp, unique=2),
+                sjob(c1h, sm["w1h"], g.Sp, g.Sp, sm["ldh"]),
+                sjob(c1h, sm["b1h"], g.Sp, OP, sm["ldh"], off=g.Sp, unique=2)]
+    return (L.ScatterJob * len(lst))(*lst)
+
+
+def _finish_layers(cx, l0, l1, with_head):
+    """Scatter the dense gradient tiles of layers [l0, l1) (and of the head) into the effective-weight arena, then the zb chain
+    (conv bias + hoisted global conditioning, modules.py:148-152) of those layers.  Disjoint slots; the tables never move."""
+    eng, g, lay, sm, ws, st = cx.eng, cx.eng.g, cx.eng.lay, cx.eng.sm, cx.ws, cx.eng.stream()
+    key = ("scatter_jobs", l0, l1, with_head)
+    jobs = ws.get(key)
+    if jobs is None:
+        jobs = ws[key] = _scatter_jobs(cx, l0, l1, with_head)
+    L.check(eng.lib.wae_unpack_scatter_add_multi(jobs, len(jobs), st), "scatter layer and head gradients")
+    wg_off = lay.off("wavenet.conv_layers.0.conv1x1g.weight_v") + l0 * lay.layer_stride if g.Cg > 0 else -1
+    L.check(eng.lib.wae_gproj_bwd(L.ptr(eng.eff), L.ptr(eng.d_eff), wg_off,
+                                  lay.off("wavenet.conv_layers.0.conv.bias") + l0 * lay.layer_stride, lay.layer_stride,
+                                  L.ptr(cx.gid32) if cx.use_gid else None, lay.offsets.get("wavenet.embed_speakers.weight", 0),
+                                  L.ptr(cx.gvec), ctypes.c_void_p(eng.cview["c1"].data_ptr() + l0 * cx.Z2 * sm["ld1"] * 4),
+                                  cx.Z2 * sm["ld1"], sm["ld1"], g.k * g.Rp + g.Ccp, cx.B, l1 - l0, g.G, g.Hp, max(g.Cg, 0),
+                                  int(g.n_speakers or 0), st),
+            "gproj_bwd")
+
+
+def _tn_behind_sweep(cx, sched, grad_sync):
+    """The weight-gradient launch behind the sweep (every layer's dW1 taps, dWc + zb sums, dW_out + bias in one launch, or the lower
+    layers' when the upper ones' left the sweep: TnSchedule), the scatter into the arena, and the data-parallel hand-over."""
+    eng = cx.eng
+    if sched.end is not None:
+        _timed(eng, cx.tn_ev, sched.end.launch)
+    if sched.kind == "beside":           # (the upper layers' launch has been running beside the sweep)
+        eng.join(cx.beside_done[0])
+    eng._grads_done = None
+    if sched.kind == "split":
+        _finish_layers(cx, 0, sched.cut, with_head=False)
+        seg = layer_segment(eng)
+        eng._grads_done = seg
+        _hand_over(cx, grad_sync, seg[0], layer_segment_mid(eng))
+        return
+    _finish_layers(cx, 0, eng.g.layers, with_head=True)
+    if grad_sync is not None:
+        # data parallel without the split (too few layers, or the per-layer tile launches of fp32): the layers' + head's gradients
+        # are final -> weight-norm backward of that slice, then the all-reduce starts on its side stream while the launches below
+        # (and the front end's backward) still run
+        seg = layer_segment(eng)
+        eng._grads_done = seg
+        _hand_over(cx, grad_sync, *seg)
+
+
+def _head_backward(cx, xi, tg, ln, inv_count, ext_dy):
+    """dy, dh1, dskip; the head's tile launch and the first conv's one-hot operand where the static launch does not carry them"""
+    eng, g, lib, ws, fw, B, T, st = cx.eng, cx.eng.g, cx.eng.lib, cx.ws, cx.fw, cx.B, cx.T, cx.eng.stream()
     b3 = ctypes.c_void_p(eng.b_head.data_ptr() + 2 * g.Sp * 4)
     if eng.wide_head:
         # the same three steps as csrc/head_bwd.hip, one wae_gemm_tm launch each (dy, dh1, dskip through HBM)
@@ -643,288 +878,22 @@ def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: O
         _tm(eng, B, T, g.Sp, 4, math.sqrt(1.0 / g.layers), [(ws["dh1"].data_ptr(), g.Sp, g.Sp, 0)], eng.w_hwide["w1t"].data_ptr(),
             ws["dskip"].data_ptr(), g.Sp, fw["h0"].data_ptr(), g.Sp)
     else:
+        hd = L.HeadDesc(eng.dt, B, T, g.Ku, g.Sp, g.Op, g.O, math.sqrt(1.0 / g.layers))
         L.check(lib.wae_head_bwd(ctypes.byref(hd), L.ptr(fw["h0"]), L.ptr(fw["h1"]), L.ptr(eng.w_hb), b3, L.ptr(fw["lse"]), L.ptr(tg),
                                  L.ptr(ln), inv_count, L.ptr(ext_dy), L.ptr(ws["dy"]), L.ptr(ws["dh1"]), L.ptr(ws["dskip"]), st),
                 "head_bwd")
         if ext_dy is not None:
             ws["dy"].copy_(ext_dy)                # the tile table points at ws["dy"]
-    c3, c1h, cs = eng.cview["c3"], eng.cview["c1h"], eng.cview["cs"]
     if ws["tt_head"] is not None:
         ws["tt_head"].launch(B, T)
     if ws["onehot"] is not None:        # operand of the first conv's weight gradient (a job of the stream launch)
         L.check(lib.wae_onehot_rows(L.ptr(xi), L.ptr(ws["onehot"]), B * T, ws["onehot"].shape[-1], eng.dt, st), "onehot_rows")
 
-    # ---- gated stack, last layer first ---------------------------------------------------------------------------
-    Z2 = 2 * g.Hp
-    dzs = g.layers * Z2
-    c1, co = eng.cview["c1"], eng.cview["co"]
-    g_next = ws["gzero"]                      # dxhat_{L} = 0: the last layer's x' is dead (wavenet.py:205-207)
-    ngx = len(ws["gx"])
-    ck = 64 if eng.dt in (L.WAE_BF16, L.WAE_F16) else 32
-    us_off = (g.Rp // ck) * g.NP * 4 * 1024   # bytes: the W_skip chunks follow the W_out chunks in the mode-2 stream
 
-    tm_ev = getattr(eng, "_tm_events", None)   # bench.py: {"gate": [(e0, e1), ...], "res": [...], "pair": [...]} -- HIP events around every launch
-
-    def timed(kind, fn, stc=None):
-        if tm_ev is None or stc is not None:   # (HIP events bracket the current stream's launches only)
-            return fn()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(torch.cuda.current_stream(eng.device))
-        fn()
-        e1.record(torch.cuda.current_stream(eng.device))
-        tm_ev.setdefault(kind, []).append((e0, e1))
-
-    # (b0, nb, stc): the clips of a chain and its stream -- every array of the sweep is clip-major, so a chain is the same call on its
-    #  clips (engine.chain_plan); (0, B, None) = the whole batch on the current stream
-    WHOLE = (0, B, None)
-
-    def k_u(l, gn, part=WHOLE):                # du -> dz of layer l
-        b0, nb, stc = part
-        r = b0 * T * es
-        if gn.data_ptr() == ws["gzero"].data_ptr():
-            # the top layer: dx-hat above it is zero (its x' is dead), so W_out^T . 0 is left out -- the skip half of the weight stream
-            # on dS alone: the same sums (+ 0 exactly), half the chunks, 32 MB of zeros not read
-            timed("gate", lambda: _tm(eng, nb, T, g.Hp, 2, 1.0, [(ws["dskip"].data_ptr() + r * g.Sp, g.Sp, g.Sp, 0)],
-                                      eng.w_bu.data_ptr() + l * eng.n_bu * es + us_off, ws["dz"].data_ptr() + l * Z2 * es + r * dzs, dzs,
-                                      fw["z"][l].data_ptr() + r * Z2, Z2, flags=0, st=stc), stc)
-            return
-        timed("gate", lambda: _tm(eng, nb, T, g.Hp, 2, 1.0, [(gn.data_ptr() + r * g.Rp, g.Rp, g.Rp, 0),
-                                                            (ws["dskip"].data_ptr() + r * g.Sp, g.Sp, g.Sp, 0)],
-                                  eng.w_bu.data_ptr() + l * eng.n_bu * es, ws["dz"].data_ptr() + l * Z2 * es + r * dzs, dzs,
-                                  fw["z"][l].data_ptr() + r * Z2, Z2, flags=0, st=stc), stc)
-
-    seeds = getattr(eng, "_drop_seeds", None)   # set by the train-mode forward when dropout is active
-
-    def k_x(l, gn, gc, part=WHOLE):            # dx-hat of layer l
-        b0, nb, stc = part
-        r = b0 * T * es
-        srcs = [(ws["dz"].data_ptr() + l * Z2 * es + r * dzs, dzs, Z2, (g.k - 1 - tap) * g.dilations[l]) for tap in range(g.k)]
-        if seeds is None:
-            timed("res", lambda: _tm(eng, nb, T, g.Rp, 1, RS, srcs, eng.w_bx.data_ptr() + l * eng.n_bx * es, gc.data_ptr() + r * g.Rp, g.Rp,
-                                     gn.data_ptr() + r * g.Rp, g.Rp, flags=P.TM_INTERLEAVE, st=stc), stc)
-        else:
-            # dropout: the tap contraction alone (mode 0), then out = sqrt(.5) * (g_next + keep * acc / (1 - p)) with the mask
-            # the forward applied to this layer's convolution operand
-            _tm(eng, B, T, g.Rp, 0, 1.0, srcs, eng.w_bx.data_ptr() + l * eng.n_bx * es, ws["gtmp"].data_ptr(), g.Rp,
-                flags=P.TM_INTERLEAVE)
-            L.check(lib.wae_dropout_bwd(L.ptr(ws["gtmp"]), L.ptr(gn), L.ptr(gc), B * T * g.Rp, seeds[l], eng.dropout, RS, eng.dt, st),
-                    "dropout_bwd")
-
-    def tn_layer(l):                           # per-layer weight gradients (fp32 path; bf16 takes them all at the end)
-        if ws["stream"] is not None:
-            return
-        ev = getattr(eng, "_tn_events", None)
-        if ev is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(eng.device))
-        ws["tt_layer"][l].launch(B, T)
-        if ev is not None:
-            e1.record(torch.cuda.current_stream(eng.device))
-            ev.append((e0, e1))
-
-    def launch_stream(tab):
-        ev = getattr(eng, "_tn_events", None)
-        if ev is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(torch.cuda.current_stream(eng.device))
-        tab.launch()
-        if ev is not None:
-            e1.record(torch.cuda.current_stream(eng.device))
-            ev.append((e0, e1))
-
-    OP = P.ONES_PAD
-
-    def finish_layers(l0, l1, with_head):
-        """Scatter the dense gradient tiles of layers [l0, l1) (and of the head) into the effective-weight arena, then the zb chain
-        (conv bias + hoisted global conditioning, modules.py:148-152) of those layers.  Disjoint slots; the tables never move."""
-        key = ("scatter_jobs", l0, l1, with_head)
-        jobs = ws.get(key)
-        static = isinstance(ws["stream"], StaticStreamTable)
-        if jobs is None:
-            nb, ls = l1 - l0, lay.layer_stride
-
-            def sjob(src, mp, rows, cols, ld, off=0, nb=1, ss=0, ds=0, unique=1, doff=0):
-                return L.ScatterJob(src.data_ptr() + off * 4, mp.data_ptr(), eng.d_eff.data_ptr() + doff * 4, rows * cols, ss, ds, ld, nb,
-                                    cols, unique, 0)
-            lst = [sjob(c1, sm["w1"], Z2, sm["ncol1"], sm["ld1"], off=l0 * Z2 * sm["ld1"], nb=nb, ss=Z2 * sm["ld1"], ds=ls, doff=l0 * ls)]
-            if static:      # transposed dW_out (+ its bias row) and dW_skip blocks of the static stream launch, per layer
-                coT, csT, cbs, rows = eng.cview["coT"], eng.cview["csT"], eng.cview["cbs"], sm["ldoT_rows"]
-                lst += [sjob(coT, sm["woT"], g.Hp, g.Rp, g.Rp, off=l0 * rows * g.Rp, nb=nb, ss=rows * g.Rp, ds=ls, doff=l0 * ls),
-                        sjob(coT, sm["boT"], 1, g.Rp, g.Rp, off=l0 * rows * g.Rp + g.Hp * g.Rp, nb=nb, ss=rows * g.Rp, ds=ls, doff=l0 * ls),
-                        sjob(csT, sm["wsT"], g.Hp, g.Sp, g.Sp, off=l0 * g.Hp * g.Sp, nb=nb, ss=g.Hp * g.Sp, ds=ls, doff=l0 * ls),
-                        sjob(cbs, sm["bsT"], 1, g.Sp, g.Sp, nb=nb, ss=0, ds=ls, doff=l0 * ls)]
-            else:
-                lst += [sjob(co, sm["wo"], g.Rp, g.Hp, sm["ldo"], off=l0 * g.Rp * sm["ldo"], nb=nb, ss=g.Rp * sm["ldo"], ds=ls, doff=l0 * ls),
-                        sjob(co, sm["bo"], g.Rp, OP, sm["ldo"], off=l0 * g.Rp * sm["ldo"] + g.Hp, nb=nb, ss=g.Rp * sm["ldo"], ds=ls, unique=2,
-                             doff=l0 * ls),
-                        sjob(cs, sm["bs"], g.Sp, OP, sm["lds"], off=g.Ku, nb=nb, ss=0, ds=ls, unique=2, doff=l0 * ls)]
-            if with_head:
-                if not static:
-                    lst.append(sjob(cs, sm["ws"], g.Sp, g.Ku, sm["lds"]))
-                lst += [sjob(c3, sm["w3"], g.Op, g.Sp, sm["ldh"]),
-                        sjob(c3, sm["b3"], g.Op, OP, sm["ldh"], off=g.Sp, unique=2),
-                        sjob(c1h, sm["w1h"], g.Sp, g.Sp, sm["ldh"]),
-                        sjob(c1h, sm["b1h"], g.Sp, OP, sm["ldh"], off=g.Sp, unique=2)]
-            jobs = ws[key] = (L.ScatterJob * len(lst))(*lst)
-        L.check(lib.wae_unpack_scatter_add_multi(jobs, len(jobs), st), "scatter layer and head gradients")
-        wg_off = lay.off("wavenet.conv_layers.0.conv1x1g.weight_v") + l0 * lay.layer_stride if g.Cg > 0 else -1
-        L.check(lib.wae_gproj_bwd(L.ptr(eng.eff), L.ptr(eng.d_eff), wg_off,
-                                  lay.off("wavenet.conv_layers.0.conv.bias") + l0 * lay.layer_stride, lay.layer_stride,
-                                  L.ptr(gid32) if use_gid else None, emb_off, L.ptr(gvec),
-                                  ctypes.c_void_p(c1.data_ptr() + l0 * Z2 * sm["ld1"] * 4), Z2 * sm["ld1"], sm["ld1"],
-                                  g.k * g.Rp + g.Ccp, B, l1 - l0, g.G, g.Hp, max(g.Cg, 0), int(g.n_speakers or 0), st),
-                "gproj_bwd")
-
-    emb_off = lay.offsets.get("wavenet.embed_speakers.weight", 0)
-    use_gid = gid is not None and "wavenet.embed_speakers.weight" in lay.offsets
-    gid32 = gid.to(torch.int32).contiguous() if gid is not None else None
-    keep.append(gid32)
-    # ---- data parallel: where the arena is cut.  [seg_lo, seg_hi) = the gated layers + the head (backward.layer_segment); with the
-    #      stream-K launch and >= 4 layers the sweep hands over [seg_mid, seg_hi) -- the upper half of the layers and the head -- as
-    #      soon as it has passed layer L/2, and [seg_lo, seg_mid) at its end (WAE_DP_SPLIT=0: one hand-over at the end)
-    eng._grads_done = None
-    seg_lo, seg_hi = layer_segment(eng)
-    split = None
-    if grad_sync is not None and ws["stream"] is not None and g.layers >= 4 and eng.opt.dp_split:
-        split = g.layers // 2
-        seg_mid = layer_segment_mid(eng)
-        if "stream_hi" not in ws:
-            ws["stream_hi"] = _build_stream_table(eng, ws, fw, B, T, split, g.layers)
-            ws["stream_lo"] = _build_stream_table(eng, ws, fw, B, T, 0, split)
-
-    # 16-bit fused sweep, three taps, 64 conditioning columns: dc = sum_l Wc_l^T dz_l is folded into the pair launches (phase A's
-    # shift-0 tap already holds dz_l[t] as MFMA operand): an fp32 running sum over the layers, written in the storage dtype by the
-    # launch of layer 0 (which runs the pair kernel's first half only) -- the K = L * 2Hp launch that re-read every dz is gone
-    fold_dc = bool(eng.fused_bwd and seeds is None and eng.dt in (L.WAE_BF16, L.WAE_F16) and g.k == 3 and g.Ccp == 64
-                   and eng.opt.bwd_fold_dc)
-    if fold_dc and "dc32" not in ws:
-        ws["dc32"] = torch.empty(B, T, 64, dtype=torch.float32, device=eng.device)
-    cbytes = (Z2 // 64) * 8192                # bytes of one layer's chunks in the dc weight stream (packing.bwd_c_map)
-    # ---- an UNDER-FILLED sweep (hps/vqwae.json's shard: 160 workgroups per launch on 256 CUs): the weight gradients of the upper layers
-    #      (+ the head's) run BESIDE the lower part of the sweep, as a launch sized for the idle CUs on a side stream; the lower layers'
-    #      follow the sweep as before.  `beside` = the first layer of the upper part.  Measured at that shard (20 layers, 96 idle CUs;
-    #      ms per train step, one box): 6 / 8 / 10 / 12 / 14 layers beside the sweep 3.247 / 3.226-3.239 / 3.223-3.230 / 3.230 / 3.287
-    #      against 3.37-3.39 without.  The side launch runs a layer's share in ~114 us on 96 CUs (all 256: 31 -- its teams no longer sit
-    #      on one XCD each, and the sweep's launches share L2 and HBM with it) and slows the sweep's launches by ~5 %; what it has not
-    #      finished when the sweep ends runs beside the lower layers' launch, so the split is not critical: L / (1 + ncu / (2 idle)).
-    beside = None
-    if (grad_sync is None and eng.opt.side and isinstance(ws["stream"], StaticStreamTable) and seeds is None and g.layers >= 8):
-        ncu_all = torch.cuda.get_device_properties(eng.device).multi_processor_count
-        idle = (ncu_all - B * ((T + 255) // 256)) // 8 * 8
-        if idle >= 64:
-            nup = int(g.layers / (1.0 + 0.5 * ncu_all / idle))
-            if nup >= 2:
-                beside = g.layers - nup
-                if "stream_beside" not in ws:
-                    ws["stream_beside"] = _build_stream_table(eng, ws, fw, B, T, beside, g.layers, ncu=idle)
-                    # with an encoder in front, the front end's backward is a chain of ~20 small launches (~0.3 ms) that starts at the end of
-                    # the sweep on its own side stream (engine.backward): the lower layers' launch leaves it 32 CUs instead of taking
-                    # every SIMD's registers (0 / 32 / 48 / 64 CUs left: 3.20-3.21 / 3.08-3.14 / 3.10 / 3.11 ms per step at hps/vqwae.json)
-                    reserve = 32 if g.has_encoder else 0
-                    ws["stream_below"] = _build_stream_table(eng, ws, fw, B, T, 0, beside, ncu=(ncu_all - reserve) if reserve else None)
-    beside_done = [None]
-    k_u(g.layers - 1, g_next)
-    # two half-batch chains of the sweep's launches (engine.chain_plan), the second half a launch late; not with dropout (its mask
-    # generator counts elements of the full batch) and not with per-layer weight-gradient launches (they read both chains' rows)
-    plan = eng.chain_plan(B, T, backward=True) if (seeds is None and ws["stream"] is not None) else None
-
-    def fork():
-        if plan is None:
-            return [WHOLE]
-        side = eng.chain_fork(plan[1])
-        return [(0, plan[0], None), (plan[0], B - plan[0], ctypes.c_void_p(side.cuda_stream))]
-
-    if tm_ev is not None:                      # bench.py: HIP events around the whole sweep (both chains)
-        sweep_e0, sweep_e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        sweep_e0.record(torch.cuda.current_stream(eng.device))
-    parts = fork()
-    for l in range(g.layers - 1, -1, -1):
-        assert l == g.layers - 1 or g_next.data_ptr() == ws["gx"][(l + 1) % ngx].data_ptr()
-        tn_layer(l)                            # needs dz_l and dx_{l+1}-hat
-        g_cur = ws["gx"][l % ngx]
-        if (l > 0 or fold_dc) and eng.fused_bwd and seeds is None:
-            # K_X of layer l and K_U of layer l-1 in one launch (csrc/glu_bwd.hip); layer 0 (fold_dc): K_X + the last dc term only
-            lp = max(l - 1, 0)
-            for b0, nb, stc in parts:
-                d = L.GluBwdDesc(eng.dt, nb, T, g.Rp, g.Hp, g.Sp, g.k, g.dilations[l], RS)
-                r = b0 * T * es
-                args = [ctypes.byref(d), ctypes.c_void_p(ws["dz"].data_ptr() + l * Z2 * es + r * dzs), dzs,
-                        ctypes.c_void_p(g_next.data_ptr() + r * g.Rp), ctypes.c_void_p(g_cur.data_ptr() + r * g.Rp),
-                        ctypes.c_void_p(ws["dskip"].data_ptr() + r * g.Sp), ctypes.c_void_p(fw["z"][lp].data_ptr() + r * Z2),
-                        ctypes.c_void_p(ws["dz"].data_ptr() + lp * Z2 * es + r * dzs),
-                        ctypes.c_void_p((eng.w_bxf if hasattr(eng, "w_bxf") else eng.w_bx).data_ptr() + l * eng.n_bx * es),
-                        ctypes.c_void_p(eng.w_buo.data_ptr() + lp * eng.n_buo * es),
-                        ctypes.c_void_p(eng.w_bu.data_ptr() + lp * eng.n_bu * es + us_off)]
-                sq = stc if stc is not None else st
-                if fold_dc:
-                    mode = (0 if l == g.layers - 1 else 1) | (2 if l == 0 else 0) | (4 if getattr(eng, "bwd_pair4", False) else 0)
-                    # (bit 2: keep the 4-wave kernel where the 8-wave one, csrc/glu_bwd8.hip, has an instantiation -- tests and tools)
-                    args += [ctypes.c_void_p(eng.w_bc.data_ptr() + l * cbytes), ctypes.c_void_p(ws["dc32"].data_ptr() + b0 * T * 64 * 4),
-                             ctypes.c_void_p(ws["dc"].data_ptr() + r * ws["dc"].shape[-1]), mode, int(l == 0)]
-                    timed("pair", lambda: L.check(lib.wae_glu_bwd_fused_dc(*args, sq), "glu_bwd_fused_dc"), stc)
-                else:
-                    timed("pair", lambda: L.check(lib.wae_glu_bwd_fused(*args, sq), "glu_bwd_fused"), stc)
-        else:
-            for part in parts:
-                k_x(l, g_next, g_cur, part)
-                if l > 0:
-                    k_u(l - 1, g_cur, part)
-        g_next = g_cur
-        if beside is not None and l == beside:
-            # dz, dx-hat and the saved activations of layers [beside, L) are complete: their weight gradients start on the idle CUs
-            with eng.branch(1) as beside_done:
-                launch_stream(ws["stream_beside"])
-        if split is not None and l == split:
-            # data parallel: dz, dx-hat and the saved activations of layers [split, L) are complete -> their weight gradients now
-            # (one stream-K launch over the upper half), the head's and theirs into the arena, weight-norm backward of that slice,
-            # and the all-reduce of ~half the arena starts while the lower half of the sweep still runs
-            if plan is not None:
-                eng.chain_join()
-            launch_stream(ws["stream_hi"])
-            finish_layers(split, g.layers, with_head=True)
-            _wn_bwd_range(eng, seg_mid, seg_hi)
-            grad_sync.ready_range(seg_mid, seg_hi)
-            parts = fork()
-    if plan is not None:
-        eng.chain_join()
-    if tm_ev is not None:
-        sweep_e1.record(torch.cuda.current_stream(eng.device))
-        tm_ev.setdefault("sweep", []).append((sweep_e0, sweep_e1))
-    if fold_dc and eng.opt.side:
-        # dc is complete: the front end's backward may start (engine.backward: a side stream).  Its launches then sit behind the
-        # weight-gradient launch below, which fills every SIMD's registers, and run in that launch's ragged end (its workgroups finish
-        # 60-90 us apart) and beside the scatters.  (Started behind the weight-gradient launch instead they ran beside the scatters
-        # only, and both took longer: 54 us per step gained instead of 90.)
-        eng._ev_dc = torch.cuda.Event()
-        eng._ev_dc.record(torch.cuda.current_stream(eng.device))
-    if split is not None:
-        launch_stream(ws["stream_lo"])
-    elif beside is not None:              # the lower layers' (the upper ones' launch has been running beside the sweep)
-        launch_stream(ws["stream_below"])
-        eng.join(beside_done[0])
-    elif ws["stream"] is not None:        # every layer's dW1 taps, dWc + zb sums, dW_out + bias: one launch
-        launch_stream(ws["stream"])
-    if split is not None:
-        finish_layers(0, split, with_head=False)
-        _wn_bwd_range(eng, seg_lo, seg_mid)
-        eng._grads_done = (seg_lo, seg_hi)
-        grad_sync.ready_range(seg_lo, seg_mid)
-    else:
-        finish_layers(0, g.layers, with_head=True)
-        # ---- data parallel without the split (too few layers, or the per-layer tile launches of fp32): the layers' + head's
-        #      gradients are final -> weight-norm backward of that slice, then the all-reduce starts on its side stream while the
-        #      launches below (and the front end's backward) still run
-        eng._grads_done = None
-        if grad_sync is not None:
-            _wn_bwd_range(eng, seg_lo, seg_hi)
-            eng._grads_done = (seg_lo, seg_hi)
-            grad_sync.ready_range(seg_lo, seg_hi)
-    # ---- local-conditioning gradient over all layers at once ---------------------------------------------------------
-    if g.Ccp and not fold_dc:
-        _tm(eng, B, T, g.Ccp, 0, 1.0, [(ws["dz"].data_ptr(), dzs, dzs, 0)], eng.w_bc.data_ptr(), ws["dc"].data_ptr(), g.Ccp)
-    # ---- first conv: dW[r][class] = sum_t dx0[t][r] onehot(id[t])[class];  dx0 = dxhat_0 / sqrt(.5) -----------------------
+def _first_conv_grads(cx, x_ids, xi):
+    """dW[r][class] = sum_t dx0[t][r] onehot(id[t])[class];  dx0 = dxhat_0 / sqrt(.5)"""
+    eng, g, lib, ws, sm, B, T, st = cx.eng, cx.eng.g, cx.eng.lib, cx.ws, cx.eng.sm, cx.B, cx.T, cx.eng.stream()
     ctab, fb = eng.cview["ctab"], eng.cview["fb"]
-    assert g_next.data_ptr() == ws["gx"][0].data_ptr()
     if g.scalar_input:
         ws["xs1"][:, :, 0] = x_ids.to(ws["xs1"].dtype)
         ws["xs1"][:, :, 1] = 1.0
@@ -942,9 +911,59 @@ def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: O
         lst = [sjob(ctab, sm["tab"], 1 if g.scalar_input else g.O, g.Rp, g.Rp), sjob(fb, sm["fb"], 1, g.Rp, g.Rp)]
         jobs = ws["scatter_jobs_first"] = (L.ScatterJob * len(lst))(*lst)
     L.check(lib.wae_unpack_scatter_add_multi(jobs, len(jobs), st), "scatter first-conv gradients")
-    eng._bwd_keep = keep
-    return ws["dc"]
 
+
+def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: Optional[torch.Tensor],
+                     gid: Optional[torch.Tensor], gvec: Optional[torch.Tensor] = None, ext_dy: Optional[torch.Tensor] = None,
+                     loss_scale: float = 1.0, grad_sync=None):
+    """Backward of the last ``decoder_forward(..., train=True)`` with the same (B, T).  Fills ``eng.grads`` (flat arena,
+    reference parameter layout incl. weight_g / weight_v) for every decoder parameter and returns dc (B,T,Ccp): the
+    gradient wrt the upsampled local conditioning.  ``ext_dy`` (B,T,Op): external d loss / d logits (DMoL).
+    ``grad_sync`` (distributed.GradSync): the layers' + head's slice of the gradient arena is finished (weight-norm backward
+    of that slice) and handed to the all-reduce BEFORE the conditioning / first-conv / front-end gradients are computed, so
+    the collective runs under them."""
+    _prepare_bwd(eng)
+    g = eng.g
+    B, T = x_ids.shape
+    bwd_workspace(eng, B, T)
+    _await_packed_weights(eng)
+    cx = _step(eng, B, T, getattr(eng, "_drop_seeds", None))   # (the seeds: set by the train-mode forward when dropout is active)
+    ws = cx.ws
+    if lengths is None:
+        count = B * (T - 1)
+    else:
+        count = int(torch.clamp(lengths.detach().to("cpu", torch.int64).clamp(max=T) - 1, min=0).sum())
+    xi = x_ids.to(torch.int32).contiguous() if not g.scalar_input else None
+    tg = targets.to(torch.int32).contiguous() if targets is not None else None
+    ln = lengths.to(torch.int32).to(eng.device).contiguous() if lengths is not None else None
+    _head_backward(cx, xi, tg, ln, loss_scale * eng.grad_scale / max(count, 1), ext_dy)
+    cx.use_gid = gid is not None and "wavenet.embed_speakers.weight" in eng.lay.offsets
+    cx.gid32 = gid.to(torch.int32).contiguous() if gid is not None else None
+    cx.gvec = gvec
+    sched = _tn_schedule(cx, grad_sync is not None)
+    if cx.fold_dc and "dc32" not in ws:
+        ws["dc32"] = torch.empty(B, T, 64, dtype=torch.float32, device=eng.device)
+    eng._grads_done = None
+    # ---- gated stack, last layer first ---------------------------------------------------------------------------
+    _k_u(cx, g.layers - 1, ws["gzero"], cx.parts[0])
+    # two half-batch chains of the sweep's launches (engine.chain_plan), the second half a launch late; not with dropout (its mask
+    # generator counts elements of the full batch) and not with per-layer weight-gradient launches (they read both chains' rows)
+    cx.plan = eng.chain_plan(B, T, backward=True) if (cx.seeds is None and sched.kind != "tiles") else None
+    _timed(eng, cx.sink("sweep"), lambda: _sweep(cx, sched, grad_sync))   # (bench.py: HIP events around both chains)
+    if cx.fold_dc and eng.opt.side:
+        # dc is complete: the front end's backward may start (engine.backward: a side stream).  Its launches then sit behind the
+        # weight-gradient launch below, which fills every SIMD's registers, and run in that launch's ragged end (its workgroups finish
+        # 60-90 us apart) and beside the scatters.  (Started behind the weight-gradient launch instead they ran beside the scatters
+        # only, and both took longer: 54 us per step gained instead of 90.)
+        eng._ev_dc = torch.cuda.Event()
+        eng._ev_dc.record(torch.cuda.current_stream(eng.device))
+    _tn_behind_sweep(cx, sched, grad_sync)
+    # ---- local-conditioning gradient over all layers at once ---------------------------------------------------------
+    if g.Ccp and not cx.fold_dc:
+        _tm(eng, B, T, g.Ccp, 0, 1.0, [(ws["dz"].data_ptr(), cx.dzs, cx.dzs, 0)], eng.w_bc.data_ptr(), ws["dc"].data_ptr(), g.Ccp)
+    _first_conv_grads(cx, x_ids, xi)
+    eng._bwd_keep = [xi, tg, ln, cx.gid32]
+    return ws["dc"]
 
 
 def layer_backward(eng, B, T, gx_hat, ds, gvec, drop_seed=None, lead=0):
@@ -964,7 +983,6 @@ def layer_backward(eng, B, T, gx_hat, ds, gvec, drop_seed=None, lead=0):
     g, lib, lay, st, sm = eng.g, eng.lib, eng.lay, eng.stream(), eng.sm
     assert g.layers == 1
     fw = eng._ws[(B, T, True)]
-    es = eng.w_glu.element_size()
     Z2 = 2 * g.Hp
     key = ("lbwd", B, T)
     ws = eng._ws.get(key)
@@ -976,27 +994,19 @@ def layer_backward(eng, B, T, gx_hat, ds, gvec, drop_seed=None, lead=0):
                   gn=torch.zeros(B * T + lead, g.Rp, dtype=td, device=dev)[:B * T].view(B, T, g.Rp),
                   dskip=torch.zeros(B, T, g.Sp, dtype=td, device=dev),
                   dc=torch.zeros(B, T, max(g.Ccp, 64), dtype=td, device=dev))
-        d = g.dilations[0]
         tt = TileTable(eng)
-        for tap in range(g.k):
-            last = tap == g.k - 1 and not g.Ccp
-            # dW1 contracts dz against the convolution's operand: the masked one, the non-causal layer's [x ; 0], or x itself
-            xop = fw["xd"][0] if "xd" in fw else (fw["xnc"] if lead else fw["x"][0])
-            tt.add(Z2, g.Rp, -(g.k - 1 - tap) * d, (g.Rp if last else -1), ia, ws["dz"].data_ptr(), Z2, xop.data_ptr(), g.Rp,
-                   c1.data_ptr() + tap * g.Rp * 4, sm["ld1"])
-        if g.Ccp:
-            tt.add(Z2, g.Ccp, 0, g.Ccp, ia, ws["dz"].data_ptr(), Z2, fw["c_up"].data_ptr(), g.Ccp, c1.data_ptr() + g.k * g.Rp * 4, sm["ld1"])
-        tt.add(g.Rp, g.Hp, 0, g.Hp, ia, ws["gn"].data_ptr(), g.Rp, fw["u"].data_ptr(), g.Ku, co.data_ptr(), sm["ldo"])
+        # dW1 contracts dz against the convolution's operand: the masked one, the non-causal layer's [x ; 0], or x itself
+        xop = fw["xd"][0] if "xd" in fw else (fw["xnc"] if lead else fw["x"][0])
+        for rec in P.tn_layer_contractions(g, g.dilations[0], ia, ws["dz"].data_ptr(), Z2, xop.data_ptr(),
+                                           fw["c_up"].data_ptr() if g.Ccp else 0, ws["gn"].data_ptr(), fw["u"].data_ptr(),
+                                           c1.data_ptr(), sm["ld1"], co.data_ptr(), sm["ldo"]):
+            tt.add(*rec)
         tt.add(g.Sp, g.Ku, 0, g.Ku, ia, ws["dskip"].data_ptr(), g.Sp, fw["u"].data_ptr(), g.Ku, cs.data_ptr(), sm["lds"])
         ws["tt"] = tt.finalize(B)
         eng._ws[key] = ws
     ws["gn"].copy_(gx_hat)
     ws["dskip"].copy_(ds)
-    early = eng.__dict__.pop("_early_pack", None)
-    if early is not None:          # train_step queued it on a side stream right behind weight norm
-        eng.join(early[0])
-    else:
-        pack_bwd_weights(eng)      # (also clears eng.d_eff and eng.cbuf)
+    _await_packed_weights(eng)
     _tm(eng, B, T, g.Hp, 2, 1.0, [(ws["gn"].data_ptr(), g.Rp, g.Rp, 0), (ws["dskip"].data_ptr(), g.Sp, g.Sp, 0)], eng.w_bu.data_ptr(),
         ws["dz"].data_ptr(), Z2, fw["z"][0].data_ptr(), Z2)
     ws["tt"].launch(B, T)
@@ -1033,25 +1043,15 @@ def layer_backward(eng, B, T, gx_hat, ds, gvec, drop_seed=None, lead=0):
     finish_grads(eng)
     return ws["gx"], (ws["dc"] if g.Ccp else None)
 
+
 def _debug_kernels(eng, B, T, l, flags_u=0, flags_x=0):
     """(du/dz launch, dx launch) of layer l as closures over the workspaces of the last train step (tools/ablate_tm.py,
     flags_*: extra wae_tm_desc flags (L.TM_ONE_WG)."""
-    g, ws, fw = eng.g, eng._ws[("bwd", B, T)], eng._ws[(B, T, True)]
-    es = eng.w_glu.element_size()
-    Z2 = 2 * g.Hp
-    dzs = g.layers * Z2
-    ngx = len(ws["gx"])
-    gn, gc = ws["gx"][(l + 1) % ngx], ws["gx"][l % ngx]
-
-    def k_u():
-        _tm(eng, B, T, g.Hp, 2, 1.0, [(gn.data_ptr(), g.Rp, g.Rp, 0), (ws["dskip"].data_ptr(), g.Sp, g.Sp, 0)],
-            eng.w_bu.data_ptr() + l * eng.n_bu * es, ws["dz"].data_ptr() + l * Z2 * es, dzs, fw["z"][l].data_ptr(), Z2, flags=flags_u)
-
-    def k_x():
-        srcs = [(ws["dz"].data_ptr() + l * Z2 * es, dzs, Z2, (g.k - 1 - tap) * g.dilations[l]) for tap in range(g.k)]
-        _tm(eng, B, T, g.Rp, 1, RS, srcs, eng.w_bx.data_ptr() + l * eng.n_bx * es, gc.data_ptr(), g.Rp, gn.data_ptr(), g.Rp,
-            flags=P.TM_INTERLEAVE | flags_x)
-    return k_u, k_x
+    cx = _step(eng, B, T)
+    cx.tm_ev = None
+    ngx = len(cx.ws["gx"])
+    gn, gc = cx.ws["gx"][(l + 1) % ngx], cx.ws["gx"][l % ngx]
+    return (lambda: _k_u(cx, l, gn, cx.parts[0], flags_u)), (lambda: _k_x(cx, l, gn, gc, cx.parts[0], flags_x))
 
 
 def finish_grads(eng):

@@ -477,6 +477,80 @@ def ar_list_plan(lengths, slots: int) -> ArListPlan:
 
 
 # ---------------------------------------------------------------------------------------------------
+# backward: where the weight-gradient launches go (backward.py builds the tables; the rules are here,
+# plain Python, so that they run without a device)
+# ---------------------------------------------------------------------------------------------------
+class TnShares(NamedTuple):
+    """tn_team_shares' answer.  segs: (first job of the group, first slab, end slab) in team order; team t owns
+    segs[team_seg[t]:team_seg[t + 1]]."""
+    nteams: int
+    nwg: int
+    segs: List[Tuple[int, int, int]]
+    team_seg: List[int]
+
+
+def tn_team_shares(n_groups: int, B: int, T: int, team_size: int, ncu: int, swap: bool = False) -> TnShares:
+    """The (group, 32-row time slab) list of a team launch (csrc/gemm_tn_stream.hip, csrc/gemm_tn_static.hip) cut into equal
+    contiguous shares, one per team of team_size workgroups; ncu: the CUs the launch may count on.  Every member of a team sweeps
+    the same slab range; shares are cut on the raw slab count (the slabs a member skips differ by tap).  swap: the second half of
+    every team's share points at a second copy of the groups that follows the first (backward.StaticStreamTable: the copy in which
+    the conditioning and the out + skip member have changed places)."""
+    KT = 32
+    per = B * ((T + KT - 1) // KT)            # slabs of one group
+    nteams = max(1, ncu // team_size)
+    nwg = ncu if ncu % 8 == 0 and ncu >= nteams * team_size else nteams * team_size
+    total = n_groups * per
+    segs, team_seg = [], [0]
+    for t in range(nteams):
+        lo, hi = total * t // nteams, total * (t + 1) // nteams
+        mid = (lo + hi) // 2 if swap else hi
+        for a, b, var in ((lo, mid, 0), (mid, hi, 1)):
+            while a < b:
+                grp = a // per
+                end = min(b, (grp + 1) * per)
+                segs.append(((var * n_groups + grp) * team_size, a - grp * per, end - grp * per))
+                a = end
+        team_seg.append(len(segs))
+    return TnShares(nteams, nwg, segs, team_seg)
+
+
+def tn_beside_split(layers: int, B: int, T: int, ncu: int) -> Optional[Tuple[int, int]]:
+    """An under-filled backward sweep (B * ceil(T / 256) workgroups per launch on ncu CUs): None, or (first upper layer, idle CUs) --
+    the weight gradients of layers [first, L) run beside the lower part of the sweep on the idle CUs.  What the side launch has not
+    finished when the sweep ends runs beside the lower layers' launch, so the cut is not critical: L / (1 + ncu / (2 idle)) upper
+    layers (measured: backward.py, _tn_schedule)."""
+    idle = (ncu - B * ((T + 255) // 256)) // 8 * 8
+    if idle < 64 or layers < 8:
+        return None
+    nup = int(layers / (1.0 + 0.5 * ncu / idle))
+    return (layers - nup, idle) if nup >= 2 else None
+
+
+def tn_job_groups(njobs: int) -> Tuple[int, int]:
+    """(groups, jobs per group) of a layer's static weight-gradient jobs: one group (a team of that many workgroups walks the layer's
+    slabs) up to six jobs; more are dealt into equal groups of at most six, the last padded with null jobs."""
+    ngrp = -(-njobs // 6) if njobs > 6 else 1
+    return ngrp, -(-njobs // ngrp)
+
+
+def tn_layer_contractions(g: Geometry, d: int, alpha: float, dz: int, dz_stride: int, x: int, c_up: int, g_next: Optional[int],
+                          u: int, c1: int, ld1: int, co: int, ldo: int):
+    """The weight-gradient contractions C[M][N (+ ones)] += alpha * P^T Q of one gated layer of dilation d, as records
+    (M, N, shift, ones_col, alpha, P, p_stride, Q, q_stride, C, ldc) -- the arguments of backward.TileTable.add / StreamTable.add:
+    one per dilated-conv tap (dz against the convolution's operand x), the conditioning 1x1 with the zb sums in its ones columns (the
+    last tap's without conditioning), conv1x1_out + bias (g_next = dx-hat of the layer above against u; None: no such contraction,
+    0: a placeholder job).  Operands are device addresses; c1 / co: the layer's dense fp32 gradient tiles."""
+    Z2 = 2 * g.Hp
+    for tap in range(g.k):
+        last = tap == g.k - 1 and not g.Ccp
+        yield (Z2, g.Rp, -(g.k - 1 - tap) * d, (g.Rp if last else -1), alpha, dz, dz_stride, x, g.Rp, c1 + tap * g.Rp * 4, ld1)
+    if g.Ccp:
+        yield (Z2, g.Ccp, 0, g.Ccp, alpha, dz, dz_stride, c_up, g.Ccp, c1 + g.k * g.Rp * 4, ld1)
+    if g_next is not None:
+        yield (g.Rp, g.Hp, 0, g.Hp, alpha, g_next, g.Rp, u, g.Ku, co, ldo)
+
+
+# ---------------------------------------------------------------------------------------------------
 # backward: transposed weight streams (csrc/gemm_tm.hip, csrc/head_bwd.hip) and the scatter maps that
 # bring the dense weight-gradient tiles of csrc/gemm_tn.hip back into the flat gradient arena
 # ---------------------------------------------------------------------------------------------------
