@@ -310,6 +310,25 @@ int wae_clip_adam_ema(float* params, const float* grads, float* exp_avg, float* 
                       double* scratch, float* grad_norm_out, int32_t step, double lr, double beta1, double beta2,
                       double eps, double weight_decay, double clip_thresh, double ema_decay, void* stream);
 
+/* the same step where `sqnorm` already holds the sum of the squares of all of grads (the wae_grad_finish launches added them while
+ * they wrote grads; the caller cleared it before those): no memset and no pass over grads for the norm are enqueued. */
+int wae_clip_adam_ema_summed(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* shadow, int64_t n,
+                             const double* sqnorm, float* grad_norm_out, int32_t step, double lr, double beta1, double beta2,
+                             double eps, double weight_decay, double clip_thresh, double ema_decay, void* stream);
+
+/* ---- gradient finish (csrc/grad_finish.hip): packed weight-gradient tiles -> grads in one pass.  A row is `cols` consecutive arena
+ * elements at `off`, owned by one 16-lane group: element i of its dW is tiles[base + pats[pat + i]] (pat >= 0, a multiple of 4:
+ * the inverse of the scatter maps, the pattern shared by the rows of a tensor) or d_eff[off + i] (pat < 0).  g_off >= 0: a
+ * weight-normed row -- grads[off..] = dv, grads[g_off] = dg, arithmetic of wae_weight_norm_bwd; g_off < 0: a plain parameter,
+ * passed through.  sqnorm_acc (or NULL): receives += the sum of the squares of everything written, in double.
+ * Rows [row_lo, row_hi) of the table are done; rows are disjoint, so any split of the table into calls gives the same grads. */
+typedef struct wae_finish_row {
+  int64_t off, g_off, base;
+  int32_t cols, pat;
+} wae_finish_row;
+int wae_grad_finish(const float* params, const float* tiles, const int32_t* pats, const float* d_eff, float* grads,
+                    const wae_finish_row* rows, int32_t row_lo, int32_t row_hi, double* sqnorm_acc, void* stream);
+
 /* ---- softmax over the channel dimension of (B, C, T) fp32 logits: WaveNet.forward(softmax=True) / VQVAE.forward(softmax=True)
  * (wavenet.py:214, vqvae_model.py:79-80: F.softmax(x, dim=1)) and its backward dx = p (dp - sum_c p dp).  p may alias x; dx may alias dp. */
 int wae_softmax_bct_fwd(const float* x, float* p, int32_t B, int32_t C, int32_t T, void* stream);

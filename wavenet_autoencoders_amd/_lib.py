@@ -81,6 +81,10 @@ class ScatterJob(ctypes.Structure):      # include/wae.h: wae_scatter_job (host 
 MULTI_MAX = 16
 
 
+class FinishRow(ctypes.Structure):       # include/wae.h: wae_finish_row (device array element of wae_grad_finish)
+    _fields_ = [("off", c_i64), ("g_off", c_i64), ("base", c_i64), ("cols", c_i32), ("pat", c_i32)]
+
+
 class HeadDesc(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in ("dtype", "B", "T", "Ku", "Sp", "Op", "O")] + [("scale", c_f32)]
 
@@ -145,6 +149,8 @@ SIGNATURES = {
     "wae_mog_loss_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp]),
     "wae_mog_sample": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "wae_clip_adam_ema": (c_i32, [c_vp] * 5 + [c_i64, c_vp, c_vp, c_i32] + [ctypes.c_double] * 7 + [c_vp]),
+    "wae_clip_adam_ema_summed": (c_i32, [c_vp] * 5 + [c_i64, c_vp, c_vp, c_i32] + [ctypes.c_double] * 7 + [c_vp]),
+    "wae_grad_finish": (c_i32, [c_vp] * 6 + [c_i32, c_i32, c_vp, c_vp]),
     "wae_ar_generate": (c_i32, _AR + [c_vp] * 5),
     "wae_ar_generate_scalar": (c_i32, _AR + [c_vp] * 3 + [c_f32, c_i32, c_vp, c_vp, c_vp]),
     "wae_ar_generate_scalar_mog": (c_i32, _AR + [c_vp] * 3 + [c_f32, c_vp, c_vp, c_vp]),

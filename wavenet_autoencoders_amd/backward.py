@@ -65,6 +65,8 @@ def _prepare_bwd(eng):
     eng.sm = {k: (up(v) if isinstance(v, np.ndarray) else v) for k, v in sm.items()}
     eng.d_eff = torch.zeros_like(eng.params)
     eng.grads = torch.zeros_like(eng.params)
+    # the squared norm of the step's gradients as wae_grad_finish sums it (one double; cleared with the gradient accumulators)
+    eng.gn_acc = torch.zeros(2, dtype=torch.float64, device=dev)
     # dense weight-gradient tiles (fp32), one allocation so a single memset clears them
     sizes = dict(c1=g.layers * 2 * g.Hp * sm["ld1"], co=g.layers * g.Rp * sm["ldo"], cs=g.Sp * sm["lds"],
                  c3=g.Op * sm["ldh"], c1h=g.Sp * sm["ldh"], ctab=P._ru(g.O, 128) * g.Rp, fb=g.Rp)
@@ -104,6 +106,7 @@ def pack_bwd_weights(eng):
         # ... and the step's two gradient accumulators cleared by the same launch (fill jobs: no map; round 5 cleared them with two
         # torch fills of 43 + 50 MB between launches, 19 us that this launch's idle store bandwidth absorbs)
         lst += [L.GatherJob(None, None, t_.data_ptr(), t_.numel(), 0, 0, 1, L.WAE_F32) for t_ in (eng.d_eff, eng.cbuf)]
+        lst.append(L.GatherJob(None, None, eng.gn_acc.data_ptr(), 2 * eng.gn_acc.numel(), 0, 0, 1, L.WAE_F32))
         jobs = eng._pack_bwd_jobs = (L.GatherJob * len(lst))(*lst)
     L.check(lib.wae_pack_gather_multi(jobs, len(jobs), st), "pack backward weights + clear the gradient accumulators")
 
@@ -592,6 +595,9 @@ class _Step:
     use_gid: bool = False
     gvec: Optional[torch.Tensor] = None
     beside_done: Optional[list] = None
+    finish: Optional[tuple] = None        # FinishPlan: the gather pass finishes the layers' gradients (_finish_layers); None: the split launches
+    finish_acc: bool = False              # ... and sums their squares (not data parallel: the all-reduce changes them afterwards)
+    small_done: Optional[list] = None     # completion events of those side launches, joined at the end of decoder_backward
 
     def sink(self, kind, stc=None):
         """the event list of a launch family (HIP events bracket the current stream's launches only)"""
@@ -739,8 +745,10 @@ def _leave_sweep(cx, work):
 
 
 def _hand_over(cx, grad_sync, lo, hi):
-    """data parallel: the arena slice [lo, hi) is final -> its weight-norm backward, and its all-reduce starts"""
-    _wn_bwd_range(cx.eng, lo, hi)
+    """data parallel: the arena slice [lo, hi) is final -> its weight-norm backward (the gather pass of _finish_layers has done it
+    already), and its all-reduce starts"""
+    if cx.finish is None:
+        _wn_bwd_range(cx.eng, lo, hi)
     grad_sync.ready_range(lo, hi)
 
 
@@ -752,7 +760,8 @@ def _tn_mid_sweep(cx, sched, grad_sync):
             _timed(eng, cx.tn_ev, sched.mid.launch)
     else:                                # split: the head's and theirs into the arena, and the all-reduce of ~half the arena starts
         _timed(eng, cx.tn_ev, sched.mid.launch)           # while the lower half of the sweep still runs
-        _finish_layers(cx, sched.cut, eng.g.layers, with_head=True)
+        done = _finish_layers(cx, sched.cut, eng.g.layers, with_head=True)
+        eng.join(done[0] if done else None)
         _hand_over(cx, grad_sync, layer_segment_mid(eng), layer_segment(eng)[1])
 
 
@@ -783,57 +792,221 @@ def _sweep(cx, sched, grad_sync):
     assert g_next.data_ptr() == ws["gx"][0].data_ptr()
 
 
-def _scatter_jobs(cx, l0, l1, with_head):
-    """The wae_scatter_job array of _finish_layers(l0, l1, with_head): built once per workspace and range"""
+def _scatter_specs(cx, l0, l1, with_head):
+    """What _finish_layers(l0, l1, with_head) moves from the weight-gradient tiles into the arena, one record per block:
+    (tile buffer, map, rows, cols, ld, off, nb, ss, ds, unique, doff) -- names of eng.cview / eng.sm and the fields of wae_scatter_job
+    (nb batch entries = layers, `ss` tile floats and `ds` arena floats apart, the first at tile float `off` and arena float `doff`)."""
     eng, g, sm, Z2 = cx.eng, cx.eng.g, cx.eng.sm, cx.Z2
-    cv, OP = eng.cview, P.ONES_PAD
+    OP = P.ONES_PAD
     nb, ls = l1 - l0, eng.lay.layer_stride
 
-    def sjob(src, mp, rows, cols, ld, off=0, nb=1, ss=0, ds=0, unique=1, doff=0):
-        return L.ScatterJob(src.data_ptr() + off * 4, mp.data_ptr(), eng.d_eff.data_ptr() + doff * 4, rows * cols, ss, ds, ld, nb,
-                            cols, unique, 0)
+    def spec(src, mp, rows, cols, ld, off=0, nb=1, ss=0, ds=0, unique=1, doff=0):
+        return (src, mp, rows, cols, ld, off, nb, ss, ds, unique, doff)
     per = dict(nb=nb, ds=ls, doff=l0 * ls)     # one block per layer of the range
     static = isinstance(cx.ws["stream"], StaticStreamTable)
-    lst = [sjob(cv["c1"], sm["w1"], Z2, sm["ncol1"], sm["ld1"], off=l0 * Z2 * sm["ld1"], ss=Z2 * sm["ld1"], **per)]
+    lst = [spec("c1", "w1", Z2, sm["ncol1"], sm["ld1"], off=l0 * Z2 * sm["ld1"], ss=Z2 * sm["ld1"], **per)]
     if static:      # transposed dW_out (+ its bias row) and dW_skip blocks of the static stream launch, per layer
-        coT, csT, rows = cv["coT"], cv["csT"], sm["ldoT_rows"]
-        lst += [sjob(coT, sm["woT"], g.Hp, g.Rp, g.Rp, off=l0 * rows * g.Rp, ss=rows * g.Rp, **per),
-                sjob(coT, sm["boT"], 1, g.Rp, g.Rp, off=l0 * rows * g.Rp + g.Hp * g.Rp, ss=rows * g.Rp, **per),
-                sjob(csT, sm["wsT"], g.Hp, g.Sp, g.Sp, off=l0 * g.Hp * g.Sp, ss=g.Hp * g.Sp, **per),
-                sjob(cv["cbs"], sm["bsT"], 1, g.Sp, g.Sp, ss=0, **per)]
+        rows = sm["ldoT_rows"]
+        lst += [spec("coT", "woT", g.Hp, g.Rp, g.Rp, off=l0 * rows * g.Rp, ss=rows * g.Rp, **per),
+                spec("coT", "boT", 1, g.Rp, g.Rp, off=l0 * rows * g.Rp + g.Hp * g.Rp, ss=rows * g.Rp, **per),
+                spec("csT", "wsT", g.Hp, g.Sp, g.Sp, off=l0 * g.Hp * g.Sp, ss=g.Hp * g.Sp, **per),
+                spec("cbs", "bsT", 1, g.Sp, g.Sp, ss=0, **per)]
     else:
-        co, cs = cv["co"], cv["cs"]
-        lst += [sjob(co, sm["wo"], g.Rp, g.Hp, sm["ldo"], off=l0 * g.Rp * sm["ldo"], ss=g.Rp * sm["ldo"], **per),
-                sjob(co, sm["bo"], g.Rp, OP, sm["ldo"], off=l0 * g.Rp * sm["ldo"] + g.Hp, ss=g.Rp * sm["ldo"], unique=2, **per),
-                sjob(cs, sm["bs"], g.Sp, OP, sm["lds"], off=g.Ku, ss=0, unique=2, **per)]
+        lst += [spec("co", "wo", g.Rp, g.Hp, sm["ldo"], off=l0 * g.Rp * sm["ldo"], ss=g.Rp * sm["ldo"], **per),
+                spec("co", "bo", g.Rp, OP, sm["ldo"], off=l0 * g.Rp * sm["ldo"] + g.Hp, ss=g.Rp * sm["ldo"], unique=2, **per),
+                spec("cs", "bs", g.Sp, OP, sm["lds"], off=g.Ku, ss=0, unique=2, **per)]
     if with_head:
-        c3, c1h = cv["c3"], cv["c1h"]
         if not static:
-            lst.append(sjob(cv["cs"], sm["ws"], g.Sp, g.Ku, sm["lds"]))
-        lst += [sjob(c3, sm["w3"], g.Op, g.Sp, sm["ldh"]),
-                sjob(c3, sm["b3"], g.Op, OP, sm["ldh"], off=g.Sp, unique=2),
-                sjob(c1h, sm["w1h"], g.Sp, g.Sp, sm["ldh"]),
-                sjob(c1h, sm["b1h"], g.Sp, OP, sm["ldh"], off=g.Sp, unique=2)]
-    return (L.ScatterJob * len(lst))(*lst)
+            lst.append(spec("cs", "ws", g.Sp, g.Ku, sm["lds"]))
+        lst += [spec("c3", "w3", g.Op, g.Sp, sm["ldh"]),
+                spec("c3", "b3", g.Op, OP, sm["ldh"], off=g.Sp, unique=2),
+                spec("c1h", "w1h", g.Sp, g.Sp, sm["ldh"]),
+                spec("c1h", "b1h", g.Sp, OP, sm["ldh"], off=g.Sp, unique=2)]
+    return lst
 
 
-def _finish_layers(cx, l0, l1, with_head):
-    """Scatter the dense gradient tiles of layers [l0, l1) (and of the head) into the effective-weight arena, then the zb chain
-    (conv bias + hoisted global conditioning, modules.py:148-152) of those layers.  Disjoint slots; the tables never move."""
-    eng, g, lay, sm, ws, st = cx.eng, cx.eng.g, cx.eng.lay, cx.eng.sm, cx.ws, cx.eng.stream()
-    key = ("scatter_jobs", l0, l1, with_head)
-    jobs = ws.get(key)
-    if jobs is None:
-        jobs = ws[key] = _scatter_jobs(cx, l0, l1, with_head)
-    L.check(eng.lib.wae_unpack_scatter_add_multi(jobs, len(jobs), st), "scatter layer and head gradients")
+def _scatter_jobs(cx, l0, l1, with_head, which="all"):
+    """The wae_scatter_job array of _finish_layers(l0, l1, with_head): built once per workspace and range.  which = "rowsum": the bias
+    sums (unique == 2) alone -- what the gather pass (_finish_plan) leaves to the scatter; "tiles": the others; None if there are none."""
+    eng = cx.eng
+    lst = [L.ScatterJob(eng.cview[src].data_ptr() + off * 4, eng.sm[mp].data_ptr(), eng.d_eff.data_ptr() + doff * 4, rows * cols, ss, ds,
+                        ld, nb, cols, unique, 0)
+           for src, mp, rows, cols, ld, off, nb, ss, ds, unique, doff in _scatter_specs(cx, l0, l1, with_head)
+           if which == "all" or (unique == 2) == (which == "rowsum")]
+    return (L.ScatterJob * len(lst))(*lst) if lst else None
+
+
+_FINISH_ROW = np.dtype([("off", "<i8"), ("g_off", "<i8"), ("base", "<i8"), ("cols", "<i4"), ("pat", "<i4")])    # wae_finish_row
+_FINISH_PLAIN = 64         # floats of a plain parameter per row of the table: one trip of its 16-lane group, four loads per lane
+
+
+class FinishPlan(NamedTuple):
+    """The row tables of wae_grad_finish over backward.layer_segment (csrc/grad_finish.hip), built once per engine:
+    `tile` = the rows whose dW the kernel gathers from the weight-gradient tiles (the inverse of the `unique == 1` scatter jobs),
+    `rest` = the rows other kernels leave in d_eff (gproj_bwd: conv1x1g and the conv bias; the row-sum scatter: bias sums).
+    Both sorted by arena offset (`*_off`, host), so an arena range is a row range.  `outer` = the rows of the arena outside the segment
+    (first conv, speaker embedding, upsampling network, encoder, codebook: all from d_eff), finished in one launch by finish_grads."""
+    tile: torch.Tensor
+    tile_off: np.ndarray
+    rest: torch.Tensor
+    rest_off: np.ndarray
+    pats: torch.Tensor
+    outer: torch.Tensor
+    outer_off: np.ndarray
+
+
+def _finish_recs(lay, lo, hi, inv=None):
+    """(off, g_off, cols) of the rows of wae_grad_finish that cover the arena range [lo, hi), sorted: its weight-normed rows, and what
+    lies between them except the g scalars (the rows write those) in pieces of at most _FINISH_PLAIN -- cut, with `inv` (slot - lo ->
+    tile float or -1), where the kind of source changes"""
+    r0, r1 = int(np.searchsorted(lay.wn_v_off, lo)), int(np.searchsorted(lay.wn_v_off, hi))
+    voff, goff, vcols = (np.asarray(a[r0:r1], dtype=np.int64) for a in (lay.wn_v_off, lay.wn_g_off, lay.wn_cols))
+    edge = np.zeros(hi - lo + 1, dtype=np.int32)
+    np.add.at(edge, voff - lo, 1)
+    np.add.at(edge, voff - lo + vcols, -1)
+    covered = np.cumsum(edge[:-1]) > 0
+    gall = np.asarray(lay.wn_g_off, dtype=np.int64)
+    covered[gall[(gall >= lo) & (gall < hi)] - lo] = True
+    plain = np.flatnonzero(~covered)
+    recs = [(int(o), int(go), int(c)) for o, go, c in zip(voff, goff, vcols)]
+    if plain.size:
+        brk = np.diff(plain) != 1
+        if inv is not None:
+            brk |= np.diff(inv[plain] >= 0) != 0
+        cut = np.flatnonzero(brk) + 1
+        for a, b in zip(np.concatenate(([0], cut)), np.concatenate((cut, [plain.size]))):
+            for p0 in range(int(plain[a]), int(plain[b - 1]) + 1, _FINISH_PLAIN):
+                recs.append((p0 + lo, -1, min(_FINISH_PLAIN, int(plain[b - 1]) + 1 - p0)))
+    recs.sort()
+    return recs
+
+
+def _build_finish_plan(cx):
+    """FinishPlan of this engine and kind of weight-gradient launch, or None where the gather pass has no form for the tiles: a slot
+    fed by more than one tile element, or a row only partly covered by tiles (the split launches stay in charge then)."""
+    eng, g, lay = cx.eng, cx.eng.g, cx.eng.lay
+    lo, hi = layer_segment(eng)
+    hm = P.grad_scatter_maps(g, lay)
+    base0 = eng.cbuf.data_ptr()
+    inv = np.full(hi - lo, -1, dtype=np.int64)          # arena slot of the segment -> float of eng.cbuf
+    for src, mp, rows, cols, ld, off, nb, ss, ds, unique, doff in _scatter_specs(cx, 0, g.layers, True):
+        if unique != 1:
+            continue
+        m = np.asarray(hm[mp], dtype=np.int64).reshape(-1)[:rows * cols]
+        i = np.arange(rows * cols, dtype=np.int64)
+        ok = m >= 0
+        si = ((i // cols) * ld + i % cols)[ok] + off + (eng.cview[src].data_ptr() - base0) // 4
+        m = m[ok] + doff - lo
+        for b in range(nb):
+            d = m + b * ds
+            if d.size == 0:
+                continue
+            if d.min() < 0 or d.max() >= hi - lo or np.unique(d).size != d.size or (inv[d] >= 0).any():
+                return None
+            inv[d] = si + b * ss
+    if inv.max() >= eng.cbuf.numel():
+        return None
+    recs = _finish_recs(lay, lo, hi, inv)
+    pats, pat_at, pool, tile, rest = {}, 0, [], [], []
+    for off, go, c in recs:
+        sl = inv[off - lo:off - lo + c]
+        if (sl < 0).all():
+            rest.append((off, go, 0, c, -1))
+            continue
+        if (sl < 0).any():
+            return None
+        b0 = int(sl.min())
+        rel = (sl - b0).astype(np.int32)
+        key = rel.tobytes()
+        at = pats.get(key)
+        if at is None:
+            at = pats[key] = pat_at
+            pool.append(np.concatenate((rel, np.zeros(-c % 4, dtype=np.int32))))        # (16-byte aligned patterns)
+            pat_at += pool[-1].size
+        tile.append((off, go, b0, c, at))
+    if not tile:
+        return None
+
+    def up(rows):
+        a = np.array(rows, dtype=_FINISH_ROW) if rows else np.zeros(0, dtype=_FINISH_ROW)
+        t = torch.from_numpy(a.view(np.uint8).copy()).to(eng.device) if rows else torch.zeros(32, dtype=torch.uint8, device=eng.device)
+        return t, a["off"].copy()
+    t_tile, o_tile = up(tile)
+    t_rest, o_rest = up(rest)
+    outer = [(off, go, 0, c, -1) for a, b in ((0, lo), (hi, lay.total)) if b > a for off, go, c in _finish_recs(lay, a, b)]
+    t_outer, o_outer = up(outer)
+    return FinishPlan(t_tile, o_tile, t_rest, o_rest, torch.from_numpy(np.concatenate(pool)).to(eng.device), t_outer, o_outer)
+
+
+def _finish_plan(cx):
+    """The FinishPlan that serves this step, or None: the split launches (EngineOptions.grad_finish off, or no form: _build_finish_plan)"""
+    eng = cx.eng
+    if not eng.opt.grad_finish:
+        return None
+    static = isinstance(cx.ws["stream"], StaticStreamTable)
+    plans = eng.__dict__.setdefault("_finish_plans", {})
+    if static not in plans:
+        plans[static] = _build_finish_plan(cx)
+    return plans[static]
+
+
+def _finish_rows(eng, plan, lo, hi, which, acc):
+    """wae_grad_finish over the rows of plan.tile / plan.rest (`which`) that start in the arena range [lo, hi); acc: their squares are
+    added to eng.gn_acc"""
+    rows, offs = {"tile": (plan.tile, plan.tile_off), "rest": (plan.rest, plan.rest_off), "outer": (plan.outer, plan.outer_off)}[which]
+    r0, r1 = int(np.searchsorted(offs, lo)), int(np.searchsorted(offs, hi))
+    if r1 > r0:
+        L.check(eng.lib.wae_grad_finish(L.ptr(eng.params), L.ptr(eng.cbuf), L.ptr(plan.pats), L.ptr(eng.d_eff), L.ptr(eng.grads),
+                                        L.ptr(rows), r0, r1, L.ptr(eng.gn_acc) if acc else None, eng.stream()), "grad_finish")
+
+
+def _gproj_bwd(cx, l0, l1):
+    """the zb chain (conv bias + hoisted global conditioning, modules.py:148-152) of layers [l0, l1) into d_eff"""
+    eng, g, lay, sm = cx.eng, cx.eng.g, cx.eng.lay, cx.eng.sm
     wg_off = lay.off("wavenet.conv_layers.0.conv1x1g.weight_v") + l0 * lay.layer_stride if g.Cg > 0 else -1
     L.check(eng.lib.wae_gproj_bwd(L.ptr(eng.eff), L.ptr(eng.d_eff), wg_off,
                                   lay.off("wavenet.conv_layers.0.conv.bias") + l0 * lay.layer_stride, lay.layer_stride,
                                   L.ptr(cx.gid32) if cx.use_gid else None, lay.offsets.get("wavenet.embed_speakers.weight", 0),
                                   L.ptr(cx.gvec), ctypes.c_void_p(eng.cview["c1"].data_ptr() + l0 * cx.Z2 * sm["ld1"] * 4),
                                   cx.Z2 * sm["ld1"], sm["ld1"], g.k * g.Rp + g.Ccp, cx.B, l1 - l0, g.G, g.Hp, max(g.Cg, 0),
-                                  int(g.n_speakers or 0), st),
+                                  int(g.n_speakers or 0), eng.stream()),
             "gproj_bwd")
+
+
+def _finish_layers(cx, l0, l1, with_head):
+    """The weight gradients of layers [l0, l1) (and of the head) leave the dense tiles.  Split launches: scattered into the
+    effective-weight arena d_eff, then the zb chain of those layers; disjoint slots, the tables never move -- the weight-norm
+    backward and the norm follow in launches of their own (_hand_over, finish_grads, wae_clip_adam_ema).
+    Gather pass (cx.finish, csrc/grad_finish.hip): ONE launch takes them from the tiles to eng.grads and sums their squares; the bias
+    sums, the zb chain and the finish of the few rows those two produce run beside it on a side stream (each far too small to fill the
+    machine, and none of them reads what the gather pass writes).  Returns that side work's completion event (a list, engine.branch)
+    or None.  d_eff keeps zeros in the slots the gather pass serves: nothing reads them."""
+    eng, ws, st = cx.eng, cx.ws, cx.eng.stream()
+    plan = cx.finish
+    key = ("scatter_jobs", l0, l1, with_head, plan is not None)
+    if key not in ws:
+        ws[key] = _scatter_jobs(cx, l0, l1, with_head, which="all" if plan is None else "rowsum")
+    jobs = ws[key]
+    if plan is None:
+        L.check(eng.lib.wae_unpack_scatter_add_multi(jobs, len(jobs), st), "scatter layer and head gradients")
+        _gproj_bwd(cx, l0, l1)
+        return None
+    ls, seg = eng.lay.layer_stride, layer_segment(eng)
+    lo, hi = seg[0] + l0 * ls, (seg[1] if with_head else seg[0] + l1 * ls)
+
+    def small():
+        if jobs is not None:
+            L.check(eng.lib.wae_unpack_scatter_add_multi(jobs, len(jobs), eng.stream()), "bias sums of the layer and head gradients")
+        _gproj_bwd(cx, l0, l1)
+        _finish_rows(eng, plan, lo, hi, "rest", cx.finish_acc)
+    if not eng.opt.side:
+        small()
+        _finish_rows(eng, plan, lo, hi, "tile", cx.finish_acc)
+        return None
+    with eng.branch(1) as done:
+        small()
+    _finish_rows(eng, plan, lo, hi, "tile", cx.finish_acc)
+    return done
 
 
 def _tn_behind_sweep(cx, sched, grad_sync):
@@ -846,13 +1019,20 @@ def _tn_behind_sweep(cx, sched, grad_sync):
         eng.join(cx.beside_done[0])
     eng._grads_done = None
     if sched.kind == "split":
-        _finish_layers(cx, 0, sched.cut, with_head=False)
+        done = _finish_layers(cx, 0, sched.cut, with_head=False)
+        eng.join(done[0] if done else None)
         seg = layer_segment(eng)
         eng._grads_done = seg
         _hand_over(cx, grad_sync, seg[0], layer_segment_mid(eng))
         return
-    _finish_layers(cx, 0, eng.g.layers, with_head=True)
-    if grad_sync is not None:
+    done = _finish_layers(cx, 0, eng.g.layers, with_head=True)
+    if grad_sync is None:
+        cx.small_done = done
+        if cx.finish is not None:      # finish_grads has the rest of the arena left (and, with finish_acc, the rest of the norm)
+            eng._grads_done = layer_segment(eng)
+            eng._norm_summed = cx.finish_acc
+    else:
+        eng.join(done[0] if done else None)
         # data parallel without the split (too few layers, or the per-layer tile launches of fp32): the layers' + head's gradients
         # are final -> weight-norm backward of that slice, then the all-reduce starts on its side stream while the launches below
         # (and the front end's backward) still run
@@ -941,6 +1121,9 @@ def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: O
     cx.gid32 = gid.to(torch.int32).contiguous() if gid is not None else None
     cx.gvec = gvec
     sched = _tn_schedule(cx, grad_sync is not None)
+    cx.finish = eng._finish_used = _finish_plan(cx)
+    cx.finish_acc = cx.finish is not None and grad_sync is None
+    eng._norm_summed = False
     if cx.fold_dc and "dc32" not in ws:
         ws["dc32"] = torch.empty(B, T, 64, dtype=torch.float32, device=eng.device)
     eng._grads_done = None
@@ -961,7 +1144,8 @@ def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: O
     # ---- local-conditioning gradient over all layers at once ---------------------------------------------------------
     if g.Ccp and not cx.fold_dc:
         _tm(eng, B, T, g.Ccp, 0, 1.0, [(ws["dz"].data_ptr(), cx.dzs, cx.dzs, 0)], eng.w_bc.data_ptr(), ws["dc"].data_ptr(), g.Ccp)
-    _first_conv_grads(cx, x_ids, xi)
+    _first_conv_grads(cx, x_ids, xi)          # (behind the gather pass, while the side stream's chain of small launches runs)
+    eng.join(cx.small_done[0] if cx.small_done else None)
     eng._bwd_keep = [xi, tg, ln, cx.gid32]
     return ws["dc"]
 
@@ -1039,7 +1223,8 @@ def layer_backward(eng, B, T, gx_hat, ds, gvec, drop_seed=None, lead=0):
     L.check(lib.wae_gproj_bwd(L.ptr(eng.eff), L.ptr(eng.d_eff), wg_off, lay.off("wavenet.conv_layers.0.conv.bias"), lay.layer_stride,
                               None, 0, L.ptr(gvec), L.ptr(c1), Z2 * sm["ld1"], sm["ld1"], g.k * g.Rp + g.Ccp, B, 1, g.G, g.Hp,
                               max(g.Cg, 0), 0, st), "gproj_bwd")
-    eng._grads_done = None
+    eng._grads_done = eng._finish_used = None
+    eng._norm_summed = False
     finish_grads(eng)
     return ws["gx"], (ws["dc"] if g.Ccp else None)
 
@@ -1059,7 +1244,13 @@ def finish_grads(eng):
     decoder_backward already finished for the all-reduce (eng._grads_done) is left alone."""
     lay = eng.lay
     done = getattr(eng, "_grads_done", None)
-    if done is None:
+    plan = getattr(eng, "_finish_used", None)
+    if plan is not None and done is not None and tuple(done) == tuple(layer_segment(eng)):
+        # the gather pass served the segment: the rest of the arena in ONE launch of the same kernel (its rows read d_eff), which adds
+        # their squares to the norm's accumulator as well -- instead of two launches per side of the segment and a pass for the norm
+        _finish_rows(eng, plan, 0, lay.total, "outer", getattr(eng, "_norm_summed", False))
+        eng._grads_done = None
+    elif done is None:
         _wn_bwd_range(eng, 0, lay.total)
     else:
         if done[0] > 0:

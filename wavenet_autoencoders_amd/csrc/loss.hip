@@ -333,6 +333,22 @@ extern "C" int wae_clip_adam_ema(float* params, const float* grads, float* exp_a
   return wae_check_launch("clip_adam_ema");
 }
 
+// The same step where `scratch` already holds the sum of the squares of ALL of grads: every wae_grad_finish launch of the backward
+// added the squares of the rows it wrote (csrc/grad_finish.hip), and the accumulator was cleared by the caller -- a fill job of the
+// launch that packs the backward weights.  No memset, no pass over grads for the norm.
+extern "C" int wae_clip_adam_ema_summed(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* shadow,
+                                        int64_t n, const double* sqnorm, float* grad_norm_out, int32_t step, double lr, double beta1,
+                                        double beta2, double eps, double weight_decay, double clip_thresh, double ema_decay,
+                                        void* stream) {
+  WAE_REQUIRE(params && grads && exp_avg && exp_avg_sq && sqnorm && n > 0 && step >= 1, "clip_adam_ema_summed: bad arguments");
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  hipLaunchKernelGGL(clip_adam_ema_kernel, dim3(2048), dim3(256), 0, as_stream(stream), params, grads, exp_avg, exp_avg_sq, shadow, n,
+                     sqnorm, grad_norm_out, (float)(lr / bc1), (float)beta1, (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2),
+                     (float)eps, (float)weight_decay, (float)sqrt(bc2), (float)clip_thresh, (float)(1.0 - ema_decay));
+  return wae_check_launch("clip_adam_ema_summed");
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Cross-entropy on explicit logits (the criterion object of vqwae_train.py:363-379 called on (B, C, T, 1) logits -- the
 // drop-in MaskedCrossEntropyLoss; the training path proper uses the CE fused into the head kernel) and the masked mean with an

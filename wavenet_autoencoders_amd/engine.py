@@ -1200,10 +1200,19 @@ class WaeEngine:
         if grad_hook is not None:
             grad_hook(grads)
         self.opt_step += 1
-        L.check(self.lib.wae_clip_adam_ema(L.ptr(self.params), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                                           L.ptr(self.shadow), self.lay.total, L.ptr(self.opt_scratch), L.ptr(self.grad_norm),
-                                           self.opt_step, lr, betas[0], betas[1], eps, weight_decay, clip_thresh, ema_decay,
-                                           self.stream()), "clip_adam_ema")
+        if getattr(self, "_norm_summed", False) and grad_sync is None and grad_hook is None:
+            # the gather passes of the backward (csrc/grad_finish.hip) summed the squares of every gradient while they wrote it, into
+            # an accumulator that the packing launch had cleared: no fill and no pass over the arena for the norm
+            L.check(self.lib.wae_clip_adam_ema_summed(L.ptr(self.params), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
+                                                      L.ptr(self.shadow), self.lay.total, L.ptr(self.gn_acc), L.ptr(self.grad_norm),
+                                                      self.opt_step, lr, betas[0], betas[1], eps, weight_decay, clip_thresh,
+                                                      ema_decay, self.stream()), "clip_adam_ema_summed")
+        else:
+            L.check(self.lib.wae_clip_adam_ema(L.ptr(self.params), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
+                                               L.ptr(self.shadow), self.lay.total, L.ptr(self.opt_scratch), L.ptr(self.grad_norm),
+                                               self.opt_step, lr, betas[0], betas[1], eps, weight_decay, clip_thresh, ema_decay,
+                                               self.stream()), "clip_adam_ema")
+        self._norm_summed = False
         self.weights_dirty = True
         res = dict(ce=out["loss"], grad_norm=self.grad_norm[0])
         if self.g.has_encoder:

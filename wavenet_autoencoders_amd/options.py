@@ -29,6 +29,11 @@ arguments (include/wae.h) from tools/.
                                      on two streams (engine.py: chain_plan): auto = 16-bit engines whose layer launch has >= 200 workgroups
                                      (forward: > 256); 1: always one chain of full-batch launches; 2: two chains in both directions whenever
                                      the batch has two clips
+
+The newest switch (its flip is checked in tests/test_grad_finish_host.py; bench.py and tools/ take it from the environment like the rest):
+  WAE_GRAD_FINISH          1         0: the step's gradients finished by the split launches (scatter into d_eff, weight-norm backward, a
+                                     pass over the arena for the norm) instead of the gather pass behind the weight-gradient launch
+                                     (csrc/grad_finish.hip; backward.py: _finish_plan says where the gather pass applies)
 """
 import os
 from dataclasses import dataclass
@@ -49,6 +54,7 @@ class EngineOptions:
     ar_coop_c: int = 32
     bwd_fused: str = "auto"
     bwd_fold_dc: bool = True
+    grad_finish: bool = True
     chains: str = "auto"
     side: bool = True
 
@@ -71,7 +77,7 @@ class EngineOptions:
                              tn_static_head=e("WAE_TN_STATIC_HEAD", "1") != "0", tn_swap=e("WAE_TN_SWAP", "1") != "0", head_split=e("WAE_HEAD_SPLIT", "1") != "0",
                              head_wide=e("WAE_HEAD_WIDE", "0") == "1", glu_pair=pair, dp_split=e("WAE_DP_SPLIT", "1") != "0",
                              ar_coop=e("WAE_AR_COOP", "1") != "0", ar_coop_c=int(e("WAE_AR_COOP_C", "32")),
-                             bwd_fused=fused, bwd_fold_dc=e("WAE_BWD_FOLD_DC", "1") != "0")
+                             bwd_fused=fused, bwd_fold_dc=e("WAE_BWD_FOLD_DC", "1") != "0", grad_finish=e("WAE_GRAD_FINISH", "1") != "0")
 
 
 def two_chains(mode: str, is16: bool, B: int, T: int, backward: bool) -> bool:
