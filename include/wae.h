@@ -459,6 +459,35 @@ int wae_ar_generate_coop(const wae_ar_desc* d, int32_t C, const int32_t* dilatio
                          const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
                          const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
                          uint64_t* msg, float* acc, int32_t* error, void* stream);
+/* A work list of utterances of unequal lengths on cooperative teams, in ONE launch (csrc/ar_coop.hip: the LIST forms): n_teams teams of
+ * C workgroups -- the grid is wae_ar_generate_coop's 8 * C workgroups, team = blockIdx.x & 7, teams >= n_teams leave at once -- empty the
+ * queue of wae_ar_generate_list: thread 0 of a team's member 0 takes the next item index with one returning atomic add on `next` (one
+ * int32_t the caller zeroes), the index reaches the team-mates through one {sequence, value} exchange on msg, the team decodes that
+ * item to its end on the kernels of wae_ar_generate_coop and comes back for the next; all members leave together when the index
+ * reaches n_items, an item with T <= 0 is skipped by the whole team.  No team waits for another.  An item's results are
+ * wae_ar_generate_coop's for that utterance alone (same C, same kernel form; w_fused = NULL), bit for bit, whichever team decodes it
+ * and in whatever order.  Items, the packed per-step operands (c_up (total, Ccp), inputs / uniforms / out_idx (total), out_logits one
+ * (O, T) block per item at float offset off * O), item.n_forced / init_idx / row and zb are wae_ar_generate_list's; `total` is the
+ * sum of the items' T (the length of the packed operands).  ring: (n_teams, C, ring_total) floats; the kernels do not depend on its
+ * contents (the constant-size kernels clear the team's shared ring before every item, the first included; the any-shape kernel reads a
+ * history row only behind its own write of it).  msg: (n_teams, 2, C, NV) granules, acc: n_teams x wae_ar_coop_acc_floats(d) floats,
+ * error: >= 64 ints; the caller zeroes msg, acc, error and next before the launch.  The exchange sequence numbers run on across a
+ * team's items (nothing is re-zeroed inside the launch).  error[0] != 0 afterwards: a wait timed out in some team and every team left
+ * at its next poll (the output is then invalid); error[1] = the placement word of team 0.
+ * d->B, d->T, d->n_forced and d->init_idx are not read; coop_generic, resident_lds and resident_regs select the kernel as for
+ * wae_ar_generate_coop: the reference's geometry on C = 32 takes the constant-size kernels with the same residency rules (the weight
+ * packets stay on chip across items; only the two zb words of a resident layer are rewritten per item), everything else the
+ * any-shape kernel.  Class-id decoders in modes 0 / 1 / 2, two hand-overs per layer (there is no list form of
+ * wae_ar_generate_coop_fused).  Refused before any launch: d->scalar_input and modes 3 / 4 (WAE_EUNSUPPORTED); t0 != 0, n_items < 1,
+ * n_teams outside 1..8, C outside 1..32, R, S or O > 256, NULL items, next, msg, acc or error, mode 0 without inputs, mode 2 without
+ * uniforms, and a list with (total + n_items + 1) * (L + 4) >= 2^31, whose sequence numbers could wrap (WAE_EINVAL). */
+int wae_ar_generate_coop_list(const wae_ar_desc* d, int32_t C, int32_t n_items, int32_t n_teams, const wae_ar_item* items,
+                              int32_t* next, int64_t total, const int32_t* dilations, const int64_t* ring_off, float* ring,
+                              int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
+                              const float* bias2, const float* zb, const float* first_tab, const float* first_bias,
+                              const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
+                              const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
+                              uint64_t* msg, float* acc, int32_t* error, void* stream);
 /* The same call with one more operand for the reference's geometry on 32 members: w_fused = (L, G, Hp) row-major in the model's element
  * type, row block l = sqrt(.5) * W1_cur[l] . W_out[l-1] (the current-tap columns of layer l's dilated convolution times the previous
  * layer's conv1x1_out; block 0 unused) -- formed once per weight update by the caller (a plain matrix product).  Because

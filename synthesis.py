@@ -139,7 +139,9 @@ def read_features(args, src):
 def batch_decode(eng, args, pairs, sp2ind, out_dir):
     """--batch-decode: the loop of main() with its decodes gathered into one WaeEngine.decode_list call.  Per pair, in the list's
     order: the seed (if any), the encoder, the quantizer and the draws of all its samples -- the order in which the loop consumes
-    the generator -- then one launch for all pairs, then the loop's post-processing and file names."""
+    the generator -- then one launch for all pairs, then the loop's post-processing and file names.  --batch-coop: that launch on
+    cooperative teams (decode_list(coop=True), --batch-teams of them): the loop's bytes where the loop decodes on the cooperative path
+    (WAE_AR_COOP=1, the default), as plain --batch-decode gives the loop's bytes under WAE_AR_COOP=0."""
     from scipy.io import wavfile
     device = eng.device
     if eng.weights_dirty:
@@ -157,7 +159,8 @@ def batch_decode(eng, args, pairs, sp2ind, out_dir):
         items.append(dict(c=quant[0].clone(), gid=sp2ind[tar], T=length, init_idx=int(args.initial_value),
                           uniforms=torch.rand(1, length, device=device)))
         names.append(f"{out_dir}{tar}_{fid}.wav")
-    for out, res in zip(names, eng.decode_list(items, mode="sample")):
+    how = dict(coop=True, teams=args.batch_teams) if args.batch_coop else {}
+    for out, res in zip(names, eng.decode_list(items, mode="sample", **how)):
         y = postprocess_indices(res["idx"].cpu().numpy(), hparams.quantize_channels, hparams.postprocess, hparams.global_gain_scale)
         wavfile.write(out, hparams.sample_rate, y)
         print("Finished! Check out {} for generated audio samples.".format(out), flush=True)
@@ -177,7 +180,15 @@ def main(argv=None):
     ap.add_argument("--stream-chunk", type=int)
     ap.add_argument("--seed", type=int)
     ap.add_argument("--batch-decode", action="store_true")
+    ap.add_argument("--batch-coop", action="store_true")
+    ap.add_argument("--batch-teams", type=int)
     args = ap.parse_args(argv)
+    if (args.batch_coop or args.batch_teams is not None) and not args.batch_decode:
+        ap.error("--batch-coop / --batch-teams choose how --batch-decode runs its list: they need --batch-decode")
+    if args.batch_coop and args.stream_chunk:
+        ap.error("--batch-coop decodes the whole list in one launch: it cannot be combined with --stream-chunk")
+    if args.batch_teams is not None and not args.batch_coop:
+        ap.error("--batch-teams sets the teams of --batch-coop")
     if args.batch_decode and args.stream_chunk:
         ap.error("--batch-decode decodes the whole list in one launch: it cannot be combined with --stream-chunk")
     if args.preset:

@@ -1,11 +1,14 @@
 #!/usr/bin/env python
 """Throughput of list decoding (WaeEngine.decode_list): hps/vqwae.json's decoder on a work list of unequal lengths.
 
-usage: bench_ar_list.py [--items N] [--dtypes bf16,fp32] [--slots cu[,2cu,N...]] [--loop K] [--min-len 8000] [--max-len 64000]
+usage: bench_ar_list.py [--items N] [--dtypes bf16,fp32] [--slots cu[,2cu,N...]] [--teams N[,N...]] [--loop K] [--min-len 8000]
+                        [--max-len 64000]
     --items N     clips in the list (default 512); lengths are drawn with numpy.random.default_rng(1234), uniform in
                   [--min-len, --max-len] samples, and rounded to whole latent frames (640 samples: the conditioning is upsampled per clip)
     --dtypes      storage types to run (default bf16,fp32)
     --slots       workgroups to launch, one run each: "cu" = the device's CU count (decode_list's default), "2cu" twice that, or a number
+    --teams N     also decode the list on N cooperative teams (decode_list(coop=True, teams=N); 1..8), one run each; "--slots none"
+                  skips the one-CU list
     --loop K      also decode the first K clips one after another with incremental_forward (what synthesis.py does without
                   --batch-decode, on whatever kernel WAE_AR_COOP selects) and print that aggregate rate; 0 (default) skips it
 Prints, per run, the wall time of the whole decode_list call (packing the operands, upsampling, the launch, synchronised) and the
@@ -35,6 +38,7 @@ def main():
     ap.add_argument("--items", type=int, default=512)
     ap.add_argument("--dtypes", default="bf16,fp32")
     ap.add_argument("--slots", default="cu")
+    ap.add_argument("--teams", default="")
     ap.add_argument("--loop", type=int, default=0)
     ap.add_argument("--min-len", type=int, default=8000)
     ap.add_argument("--max-len", type=int, default=64000)
@@ -43,7 +47,8 @@ def main():
     lens = rng.integers(args.min_len, args.max_len + 1, args.items)
     lens = (np.maximum(1, np.rint(lens / HOP)).astype(np.int64) * HOP).tolist()
     cus = torch.cuda.get_device_properties(0).multi_processor_count
-    slot_runs = [cus if s == "cu" else 2 * cus if s == "2cu" else int(s) for s in args.slots.split(",")]
+    slot_runs = [] if args.slots == "none" else [cus if s == "cu" else 2 * cus if s == "2cu" else int(s) for s in args.slots.split(",")]
+    team_runs = [int(t) for t in args.teams.split(",") if t]
     gen = torch.Generator(device="cuda").manual_seed(1234)
     items = [dict(T=T, c=torch.randn(64, T // HOP, device="cuda", generator=gen), gid=i % CFG["n_speakers"],
                   uniforms=torch.rand(T, device="cuda", generator=gen)) for i, T in enumerate(lens)]
@@ -68,6 +73,22 @@ def main():
                   f"{plan.efficiency:.3f} (busiest slot {plan.makespan} samples -> {plan.makespan / dt / 1e3:.2f} kHz per slot); "
                   f"{classes} distinct classes in clip 0", flush=True)
             record["runs"].append(dict(kind="decode_list", dtype=dtype, slots=plan.slots, seconds=dt, khz=total / dt / 1e3,
+                                       plan_efficiency=plan.efficiency, makespan=plan.makespan))
+            del out
+        if team_runs:
+            eng.decode_list([dict(it, T=HOP, c=it["c"][:, :1].contiguous(), uniforms=it["uniforms"][:HOP]) for it in items[:8]], coop=True)
+            torch.cuda.synchronize()
+        for teams in team_runs:
+            plan = ar_list_plan(lens, max(1, min(teams, 8)))
+            t0 = time.perf_counter()
+            out = eng.decode_list(items, mode="sample", coop=True, teams=teams)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            classes = int(torch.unique(out[0]["idx"]).numel())
+            print(f"decode_list(coop=True) {dtype} teams={plan.slots}: {dt:.2f} s -> {total / dt / 1e3:.1f} kHz aggregate; plan efficiency "
+                  f"{plan.efficiency:.3f} (busiest team {plan.makespan} samples -> {plan.makespan / dt / 1e3:.2f} kHz per team); "
+                  f"{classes} distinct classes in clip 0", flush=True)
+            record["runs"].append(dict(kind="decode_list_coop", dtype=dtype, teams=plan.slots, seconds=dt, khz=total / dt / 1e3,
                                        plan_efficiency=plan.efficiency, makespan=plan.makespan))
             del out
         if args.loop > 0:

@@ -91,7 +91,7 @@ class HeadDesc(ctypes.Structure):
 
 # the 16 arguments every wae_ar_generate* entry starts with: the descriptor, (dilations, ring_off, ring, ring_total, w_layers,
 # layer_stride_bytes, w2_off_bytes), (bias2, zb, first_tab, first_bias, w_head, head_bias, c_up), c_dtype; the cooperative entries
-# put C (and dist) behind the descriptor, the list entry (n_items, n_slots, items, next)
+# put C (and dist) behind the descriptor, the list entries (n_items, n_slots, items, next) / (C, n_items, n_teams, items, next, total)
 _AR = [ctypes.POINTER(ArDesc), c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64] + [c_vp] * 7 + [c_i32]
 
 # name -> (restype, argtypes); mirrors include/wae.h one to one
@@ -159,6 +159,7 @@ SIGNATURES = {
     "wae_ar_coop_acc_floats": (c_i64, [ctypes.POINTER(ArDesc)]),
     "wae_ar_generate_coop": (c_i32, _AR[:1] + [c_i32] + _AR[1:] + [c_vp] * 8),
     "wae_ar_generate_coop_fused": (c_i32, _AR[:1] + [c_i32] + _AR[1:] + [c_vp] * 9),
+    "wae_ar_generate_coop_list": (c_i32, _AR[:1] + [c_i32, c_i32, c_i32, c_vp, c_vp, c_i64] + _AR[1:] + [c_vp] * 8),
     "wae_ar_generate_coop_scalar": (c_i32, _AR[:1] + [c_i32, c_i32] + _AR[1:] + [c_vp] * 3 + [c_f32, c_i32] + [c_vp] * 6),
     "wae_ce_logits_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "wae_ce_logits_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),

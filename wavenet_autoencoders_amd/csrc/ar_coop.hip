@@ -68,6 +68,11 @@ struct ArcArgs {
   float* out_samples;        // (B, T) drawn samples, or null
   float* out_params;         // (B, O, T) mixture parameters of every step, or null
   int t0;                    // wae_ar_desc.t0: absolute index of this launch's first step; > 0: the rings hold steps [0, t0)
+  // the list forms (wae_ar_generate_coop_list; LIST instantiations only): B teams empty a queue of n_items utterances; T, n_forced, init_idx,
+  // the operands' base and the zb row come from the item a team has taken (B, T, n_forced and init_idx above are then unused)
+  const wae_ar_item* items;
+  int32_t* next;             // the queue counter, zeroed by the caller
+  int n_items;
 };
 
 template <typename E>
@@ -341,7 +346,8 @@ __device__ __forceinline__ float arc_gate(float a, float g) {
 }
 
 // ---- next input (wavenet.py:300-338) from the logits in lbuf: ibuf[0] <- the class fed back, out_idx[t] <- the class produced --------
-__device__ __forceinline__ void arc_draw(const ArcArgs& p, float* lbuf, float* psum, int* ibuf, int b, int m, int t) {
+//      ubase = the utterance's first step in the per-step operands (b * T; the item's off in the list forms), nforced its forced prefix
+__device__ __forceinline__ void arc_draw(const ArcArgs& p, float* lbuf, float* psum, int* ibuf, int64_t ubase, int nforced, int m, int t) {
   const int tid = threadIdx.x;
   // same arithmetic and summation order as csrc/ar_fwd.hip; the exponentials are evaluated by all threads, the order-dependent
   // sums by one
@@ -398,7 +404,7 @@ __device__ __forceinline__ void arc_draw(const ArcArgs& p, float* lbuf, float* p
       tot += dsum[w];
     }
     c += base;
-    const double thr = (double)p.uniforms[(int64_t)b * p.T + t] * tot;
+    const double thr = (double)p.uniforms[ubase + t] * tot;
     const unsigned long long below = __ballot(tid < p.O && c < thr);
     if ((tid & 63) == 0) ((int*)psum)[56 + (tid >> 6)] = __popcll(below);
     arc_barrier();
@@ -419,7 +425,7 @@ __device__ __forceinline__ void arc_draw(const ArcArgs& p, float* lbuf, float* p
       for (int i = 0; i < p.O; ++i) den += lbuf[i];
       double tot = 0.0;
       for (int i = 0; i < p.O; ++i) tot += (double)(lbuf[i] / den);
-      const double thr = (double)p.uniforms[(int64_t)b * p.T + t] * tot;
+      const double thr = (double)p.uniforms[ubase + t] * tot;
       double c = 0.0;
       int cnt = 0;
       for (int i = 0; i < p.O; ++i) {
@@ -428,8 +434,8 @@ __device__ __forceinline__ void arc_draw(const ArcArgs& p, float* lbuf, float* p
       }
       produced = min(cnt, p.O - 1);
     }
-    if (m == 0) p.out_idx[(int64_t)b * p.T + t] = produced;
-    ibuf[0] = t + 1 < p.n_forced ? p.inputs[(int64_t)b * p.T + t + 1] : produced;
+    if (m == 0) p.out_idx[ubase + t] = produced;
+    ibuf[0] = t + 1 < nforced ? p.inputs[ubase + t + 1] : produced;
   }
   arc_barrier();
 }
@@ -484,8 +490,11 @@ __device__ __forceinline__ int arc_uni(const int* q) { return __builtin_amdgcn_r
 
 // SCALAR: the scalar-input form (wae_ar_generate_coop_scalar).  The network is the same; the current input is a float in LDS, the first
 // conv is w * x + b (wavenet.py:311 on one input channel) and the draw is arc_draw_scalar.  The class-id instantiations are untouched.
-template <typename E, bool SCALAR = false>
-__global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
+// LIST: the work-list form (wae_ar_generate_coop_list; class ids only).  What is set up once per clip runs once per ITEM inside the item
+// loop below; what does not depend on the clip (placement verdict, per-thread constants, the head's packets) stays outside it.
+template <typename E, bool SCALAR, bool LIST>
+__device__ __forceinline__ void ar_coop_body(const ArcArgs& p) {
+  static_assert(!(LIST && SCALAR), "the list form decodes class ids");
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int EPL = ET<E>::EPL;
   constexpr int NWV = ARC_THREADS / 64;
@@ -516,22 +525,30 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
   int* lpos = lroff + p.L;
 
   float* ring = p.ring + ((int64_t)b * C + m) * p.ring_total;
+  // the utterance in hand: steps, forced prefix, start class, first step in the per-step operands, zb row (LIST: the item's, set per item)
+  int T = p.T, nforced = p.n_forced, init = p.init_idx;
+  int64_t base = (int64_t)b * p.T;
   const float* zb_b = p.zb + (int64_t)b * p.L * 2 * p.Hp;
   unsigned long long* msg_b = p.msg + (int64_t)b * 2 * C * p.NV;
   const int g_pad = (p.G + 63) & ~63, w_pad = (p.R + p.S + 63) & ~63, s_pad = (p.S + 63) & ~63, o_pad = (p.O + 63) & ~63;
 
-  for (int i = tid; i < NWV * 2 * EPL + K1p; i += ARC_THREADS) sm[i] = 0.f;
-  for (int i = tid; i < Sk; i += ARC_THREADS) { skipb[i] = 0.f; hbuf[i] = 0.f; }
-  if constexpr (SCALAR) {
-    // wavenet.py:284-285: the start value is zero; a forced first step overrides it (wavenet.py:300-302)
-    if (tid == 0) { ibuf[0] = 0; ibuf[1] = 0; fcur[0] = (p.inputs_f && p.n_forced > 0) ? p.inputs_f[(int64_t)b * p.T] : 0.f; }
-  } else {
-    if (tid == 0) { ibuf[0] = p.n_forced > 0 ? p.inputs[(int64_t)b * p.T] : p.init_idx; ibuf[1] = 0; }
-  }
-  for (int i = tid; i < p.L; i += ARC_THREADS) {
-    const int di = p.dil[i];
-    ldil[i] = di; lroff[i] = (int)p.ring_off[i]; lpos[i] = p.t0 % ((p.ktaps - 1) * di + 1);
-  }
+  // the LDS state a clip starts from: zeroed vectors, the first input, every ring's cursor at the clip's first step
+  auto item_reset = [&]() {
+    for (int i = tid; i < NWV * 2 * EPL + K1p; i += ARC_THREADS) sm[i] = 0.f;
+    for (int i = tid; i < Sk; i += ARC_THREADS) { skipb[i] = 0.f; hbuf[i] = 0.f; }
+    if constexpr (SCALAR) {
+      // wavenet.py:284-285: the start value is zero; a forced first step overrides it (wavenet.py:300-302)
+      if (tid == 0) { ibuf[0] = 0; ibuf[1] = 0; fcur[0] = (p.inputs_f && nforced > 0) ? p.inputs_f[base] : 0.f; }
+    } else {
+      if (tid == 0) { ibuf[0] = nforced > 0 ? p.inputs[base] : init; ibuf[1] = 0; }
+    }
+    for (int i = tid; i < p.L; i += ARC_THREADS) {
+      const int di = p.dil[i];
+      ldil[i] = di; lroff[i] = (int)p.ring_off[i]; lpos[i] = p.t0 % ((p.ktaps - 1) * di + 1);
+    }
+  };
+  if constexpr (LIST) { if (tid == 0) ibuf[1] = 0; }      // the abort flag: once; the rest when a team has taken an item
+  else item_reset();
   arc_barrier();
 
   unsigned long long* hbanks = (unsigned long long*)(p.acc + (int64_t)b * ARC_ACC_FLOATS(p.R, p.S, p.O));   // all-gather of h1 (head rows are split over the members)
@@ -594,8 +611,6 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
     return tt >= 0 ? ring[lroff[l] + (tt % rlen) * p.R + ch] : 0.f;
   };
   float hist[ARC_HP];
-#pragma unroll
-  for (int k = 0; k < ARC_HP; ++k) hist[k] = 0.f;   // layer 0 at t = 0: no history yet
   // request this thread's history elements of a layer whose ring starts at roff and whose current row is pos (of sample tq)
   auto request_hist = [&](int d, int roff, int pos, int tq) {
     const int rlen = (p.ktaps - 1) * d + 1;
@@ -666,8 +681,6 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
         if (tid < p.S) wsr[q] = *(const f32x4*)(w2 + q * (w_pad * 16u) + w2s_toff);
       }
   };
-  prefetch_gate(0);
-  prefetch_out(0);
   // the head's matrices never change: where a thread's share of a row slice is one packet it lives in a register for the whole clip
   // (before: two dependent L2 round trips per sample).  Thread -> (row tid / SL, k slice tid % SL), SL a power of two; the SL lanes
   // of a row fold by shuffles, lane 0 of the group ends up with the row.
@@ -704,10 +717,9 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
   };
   // conditioning row of sample t, element cc (requested one sample ahead)
   auto c_load = [&](int t, int cc) -> float {
-    const int64_t ci = ((int64_t)b * p.T + t) * p.Ccp + cc;
+    const int64_t ci = (base + t) * p.Ccp + cc;
     return p.c_dtype == WAE_BF16 ? (float)((const __bf16*)p.c_up)[ci] : (p.c_dtype == WAE_F16 ? (float)((const f16*)p.c_up)[ci] : ((const float*)p.c_up)[ci]);
   };
-  float creg = tid < p.Cc ? c_load(0, tid) : 0.f;
   const float fbias = tid < p.R ? p.first_bias[tid] : 0.f;
   // SCALAR: the first conv has one input channel -- its weight column stays in a register; the mixtures of the head
   const float fw = (SCALAR && tid < p.R) ? p.first_tab[tid] : 0.f;
@@ -721,8 +733,50 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
   // after this layer's GEMV -- are placed into vbuf after the gate; the all-reduce's own barrier is the one in front of the next GEMV.
   // Every wave gates for itself (lanes < nch, from the four waves' partial row sums) and passes u to its own lanes through its
   // private window of LDS, so nothing separates the gate from the x' / skip shares.
+  for (;;) {      // LIST: one turn per item the team takes; otherwise one turn
+  if constexpr (LIST) {
+    // ---- the item boundary -------------------------------------------------------------------------------------------------------------
+    // Every member keeps private rings here and reads a history row only behind its own write of it in the same clip (request_hist /
+    // hist_load test tq >= back), so nothing is cleared; the member drains its own stores of the finished clip before it reuses them.
+    // One {sequence, value} exchange on msg hands the team the next item index (thread 0 of member 0 took it with one returning atomic
+    // add) and is the team's rendezvous: every member publishes a granule, every member waits for all C.  The message sequence runs on
+    // from the placement handshake, bank = seq & 1; two banks suffice as in arc_allgather: a member publishes seq + 2 only after its
+    // gather of seq + 1 returned, which needs every member's granule of seq + 1, published after that member's gather of seq returned
+    // (both its polling pass and its re-read).  xuse / suse / huse / yuse run on across items as well: every member of a team decodes
+    // the same items with the same step counts, so it performs the same exchanges in the same order and the argument of arc_allgather /
+    // arc_allsum holds at the boundary unchanged (the host bounds the total so that no 32-bit sequence number wraps).
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ++seq;
+    unsigned long long* bank = msg_b + (int64_t)(seq & 1) * C * p.NV;
+    if (tid == 0) {
+      int took = 0;
+      if (m == 0) took = atomicAdd(p.next, 1);
+      // (an agent-scope store whatever the placement verdict, on purpose: once per item its cost does not matter, and the index then
+      // takes the path that is valid for every placement; the handshake's publish() is the per-exchange fast path)
+      __hip_atomic_store(bank + m * p.NV, arc_pack(seq, __int_as_float(took)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    float* ids = psum;
+    if (!arc_gather(bank, p.NV, C, 1, C, seq, p.error, &ibuf[1], [&](int i, float v) { ids[i] = v; })) return;
+    const int it = __builtin_amdgcn_readfirstlane(__float_as_int(ids[0]));      // member 0's granule: the same word on every member
+    arc_barrier();
+    if (it >= p.n_items) return;      // the team leaves together
+    const wae_ar_item w = p.items[it];
+    if (w.T <= 0) continue;           // skipped by the whole team
+    // as ar_list_kernel (csrc/ar_fwd.hip): mode 0 is teacher-forced throughout; a start class outside the table would read beyond first_tab
+    T = w.T; base = w.off;
+    nforced = !p.inputs ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
+    init = min(max(w.init_idx, 0), p.O - 1);
+    zb_b = p.zb + (int64_t)w.row * p.L * 2 * p.Hp;
+    item_reset();
+    arc_barrier();
+  }
+#pragma unroll
+  for (int k = 0; k < ARC_HP; ++k) hist[k] = 0.f;   // layer 0 at t = 0: no history yet
+  prefetch_gate(0);
+  prefetch_out(0);
+  float creg = tid < p.Cc ? c_load(0, tid) : 0.f;
   float xreg = 0.f;
-  for (int t = 0; t < p.T; ++t) {
+  for (int t = 0; t < T; ++t) {
     const int cur = ibuf[0];
     // SCALAR: this step's draws and the next forced input, requested here: they travel under the layers and wait in registers
     float d_um = 0.f, d_ud = 0.f, d_forced = 0.f;
@@ -736,15 +790,15 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
       }
     }
     if constexpr (SCALAR) {
-      const int64_t bt = (int64_t)b * p.T + t;
+      const int64_t bt = base + t;
       if (draw_mix && tid < Mx) d_um = p.u_mix[bt * Mx + tid];
       if (tid == 0 && draws) d_ud = draws[bt];
-      if (tid == 0 && p.inputs_f && t + 1 < p.n_forced) d_forced = p.inputs_f[bt + 1];
+      if (tid == 0 && p.inputs_f && t + 1 < nforced) d_forced = p.inputs_f[bt + 1];
     }
     // layer 0's history taps: zeros at t = 0, placed after the last gate of sample t - 1 after
     if (tid < p.Cc) vbuf[p.ktaps * p.R + tid] = creg;
     for (int cc = tid + ARC_THREADS; cc < p.Cc; cc += ARC_THREADS) vbuf[p.ktaps * p.R + cc] = c_load(t, cc);
-    if (tid < p.Cc && t + 1 < p.T) creg = c_load(t + 1, tid);
+    if (tid < p.Cc && t + 1 < T) creg = c_load(t + 1, tid);
     float skip_part = 0.f;   // this member's contribution to skip row tid, summed over the layers (the skip path is linear)
     arc_barrier();
 
@@ -881,15 +935,17 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
                          [&](float v) {
                            if (tid < p.O) {
                              lbuf[tid] = v;
-                             if (outl && m == 0) outl[((int64_t)b * p.O + tid) * p.T + t] = v;
+                             if (outl && m == 0) outl[base * p.O + (int64_t)tid * T + t] = v;
                            }
                          }))
         return;
     }
     ARC_TICK(5);
     if constexpr (SCALAR) arc_draw_scalar(p, lbuf, psum, fcur, b, m, t, d_um, d_ud, d_forced);
-    else arc_draw(p, lbuf, psum, ibuf, b, m, t);
+    else arc_draw(p, lbuf, psum, ibuf, base, nforced, m, t);
     ARC_TICK(6);
+  }
+  if constexpr (!LIST) break;
   }
 #ifdef WAE_ARC_PROFILE
   if (tid == 0 && b == 0 && m == 0) {
@@ -897,6 +953,15 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
     for (int i = 0; i < 14; ++i) o[i] = pc[i];
   }
 #endif
+}
+
+template <typename E, bool SCALAR = false>
+__global__ void __launch_bounds__(ARC_THREADS) ar_coop_kernel(ArcArgs p) {
+  ar_coop_body<E, SCALAR, false>(p);
+}
+template <typename E>
+__global__ void __launch_bounds__(ARC_THREADS) ar_coop_list_kernel(ArcArgs p) {
+  ar_coop_body<E, false, true>(p);
 }
 
 // ==== the reference's own geometry (hps/vqwae.json: 256 residual / skip / output channels, 256 gate rows, 3 taps) on 32 members =====
@@ -1128,8 +1193,12 @@ __device__ __forceinline__ void arc_bank_read(int k, float (&v)[ARC_NB]) {
 // LDSW (16-bit, two hand-overs per layer; round 5): the packets of the first p.nlds layers -- per thread NU W1 packets, its W_out / W_skip
 // shares and three scalars, (NU + 2) x 16 bytes -- live in LDS for the whole clip.  A layer whose weights are there issues no request
 // that can miss L2, so nothing sits in front of its exchange polls in the wave's in-order queue.
-template <typename E, int NU, bool FUSED, bool LDSW, bool VB>
+// LIST: the work-list form (wae_ar_generate_coop_list): a team of 32 decodes one item after another in the same launch.  The placement
+// verdict, the head's packets, sbias and the resident weight packets are set up once per launch; the item loop rebuilds what depends on
+// the clip (see "the item boundary" below).
+template <typename E, int NU, bool FUSED, bool LDSW, bool VB, bool LIST = false>
 __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
+  static_assert(!LIST || !FUSED, "the one-hand-over form has no prologue that can be re-entered");
   static_assert(!LDSW || ET<E>::EPL == 8, "LDS-resident layers: the 16-bit kernels");
   static_assert(!VB || (LDSW && NU == 4 && !FUSED), "the arch-VGPR bank belongs to ar_coop_fast_vb_kernel");
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -1171,21 +1240,10 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
   // fp32 and the one-hand-over form too.)
   float* ring = p.ring + (int64_t)b * C * p.ring_total;
   unsigned long long* msg_b = p.msg + (int64_t)b * 2 * C * p.NV;
-  for (int i = tid; i < 32 + K1p + 2 * S; i += ARC_THREADS) sm[i] = 0.f;
-  if (tid == 0) { ibuf[0] = p.n_forced > 0 ? p.inputs[(int64_t)b * p.T] : p.init_idx; ibuf[1] = 0; }
-  for (int i = tid; i < L; i += ARC_THREADS) {
-    const int di = p.dil[i];
-    ldil[i] = di; lroff[i] = (int)p.ring_off[i]; lpos[i] = p.t0 % (2 * di + 1);
-  }
-  if (p.t0 == 0) {      // a continuation keeps the rows of steps [0, t0) (and the zeros of the rows no step has written yet)
-    // (shared ring: member m zeroes its 32nd; the members meet in the XCC-id gather below before anyone reads a row)
-    const int64_t n4 = p.ring_total / 4, lo4 = n4 * m / C, hi4 = n4 * (m + 1) / C;
-    f32x4* r4 = (f32x4*)ring;
-    for (int64_t i = lo4 + tid; i < hi4; i += ARC_THREADS) r4[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int64_t i = n4 * 4 + tid; i < p.ring_total; i += ARC_THREADS) ring[i] = 0.f;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  arc_barrier();
+  // the utterance in hand: steps, forced prefix, start class, first step in the per-step operands (LIST: the item's, set per item)
+  int T = p.T, nforced = p.n_forced, init = p.init_idx;
+  int64_t base = (int64_t)b * p.T;
+  // the LDS state a clip starts from: zeroed vectors, the first input, every ring's cursor (and the tabulated rows) at the clip's first step
   auto tab_entry = [&](int l, int pos) -> int4 {
     const int d = ldil[l], rlen = 2 * d + 1, ro = lroff[l];
     int r1 = pos - d, r0 = pos - 2 * d;
@@ -1193,8 +1251,38 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
     r0 += r0 < 0 ? rlen : 0;
     return int4{ro + r0 * R, ro + r1 * R, ro + pos * R, 0};
   };
-  for (int i = tid; i < L; i += ARC_THREADS) ltab[i] = tab_entry(i, lpos[i]);
-  if (tid == 0) ltab[L] = tab_entry(0, lpos[0] + 1 == 2 * ldil[0] + 1 ? 0 : lpos[0] + 1);
+  // (ti: the thread index as an ARGUMENT.  The list form passes a copy the compiler cannot see through, so that nothing of the item
+  // boundary is hoisted out of the item loop and kept in registers across the sample loop -- these three lambdas must not use `tid`)
+  auto item_state = [&](int ti) {
+    for (int i = ti; i < 32 + K1p + 2 * S; i += ARC_THREADS) sm[i] = 0.f;
+    if (ti == 0) { ibuf[0] = nforced > 0 ? p.inputs[base] : init; ibuf[1] = 0; }
+    for (int i = ti; i < L; i += ARC_THREADS) {
+      const int di = p.dil[i];
+      ldil[i] = di; lroff[i] = (int)p.ring_off[i]; lpos[i] = p.t0 % (2 * di + 1);
+    }
+  };
+  // shared ring: member m zeroes its 32nd and drains; the members meet in a gather before anyone reads a row
+  auto ring_clear = [&](int ti) {
+    const int64_t n4 = p.ring_total / 4, lo4 = n4 * m / C, hi4 = n4 * (m + 1) / C;
+    f32x4* r4 = (f32x4*)ring;
+    for (int64_t i = lo4 + ti; i < hi4; i += ARC_THREADS) r4[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int64_t i = n4 * 4 + ti; i < p.ring_total; i += ARC_THREADS) ring[i] = 0.f;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  };
+  auto item_tab = [&](int ti) {
+    for (int i = ti; i < L; i += ARC_THREADS) ltab[i] = tab_entry(i, lpos[i]);
+    if (ti == 0) ltab[L] = tab_entry(0, lpos[0] + 1 == 2 * ldil[0] + 1 ? 0 : lpos[0] + 1);
+  };
+  if constexpr (LIST) {
+    if (tid == 0) ibuf[1] = 0;      // the abort flag: once; everything else when the team has taken an item
+    arc_barrier();
+  } else {
+    item_state(tid);
+    // a continuation keeps the rows of steps [0, t0) (and the zeros of the rows no step has written yet); the XCC-id gather below is the meeting
+    if (p.t0 == 0) ring_clear(tid);
+    arc_barrier();
+    item_tab(tid);
+  }
 
   unsigned long long* hbanks = (unsigned long long*)(p.acc + (int64_t)b * ARC_ACC_FLOATS(R, S, O));
   unsigned long long* ybanks = hbanks + 2 * S;
@@ -1235,7 +1323,7 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
   const unsigned w2sub = EPL == 8 ? (unsigned)(m & 1) * 8u : 0u;
   const unsigned w2xoff = (unsigned)((kb_a * W_PAD + tid) * 16) + w2sub, w2soff = (unsigned)((kb_a * W_PAD + R + tid) * 16) + w2sub;
   const int gch = ch0 + (lane & 3);                                       // the channel this lane gates
-  const float* zb_b = p.zb + (int64_t)b * L * 2 * p.Hp;
+  const float* zb_b = p.zb + (int64_t)b * L * 2 * p.Hp;      // (LIST: row item.row, set per item)
   f32x4 w1n[NU];
   typename W2::raw wxr, wsr;
   float zb_a, zb_g, b2_x, h0 = 0.f, h1 = 0.f;
@@ -1297,12 +1385,12 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
   if (m == 0)
     for (int l = 0; l < L; ++l) sbias += p.bias2[(int64_t)l * (R + S) + R + tid];
   auto c_load = [&](int t) -> float {
-    const int64_t ci = ((int64_t)b * p.T + t) * p.Ccp + tid;
+    const int64_t ci = (base + t) * p.Ccp + tid;
     return p.c_dtype == WAE_BF16 ? (float)((const __bf16*)p.c_up)[ci] : (p.c_dtype == WAE_F16 ? (float)((const f16*)p.c_up)[ci] : ((const float*)p.c_up)[ci]);
   };
-  float creg = tid < Cc ? c_load(0) : 0.f;
   const float fbias = p.first_bias[tid];
   if constexpr (LDSW) {
+    // (LIST: once per launch, with zeros where zb_a / zb_g go -- those two words are the item's and are written per item)
     for (int l = 0; l < nlds; ++l) {       // once per clip: what prefetch() fetches per layer and sample
       const char* wl = p.w_layers + (int64_t)l * p.layer_stride;
       char* q = wl0 + (size_t)l * PWL + tid * 16;
@@ -1311,7 +1399,8 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
       const f32x2_ wx2 = *(const f32x2_*)(wl + p.w2_off + w2xoff), ws2 = *(const f32x2_*)(wl + p.w2_off + w2soff);
       *(f32x4*)(q + NU * 16 * ARC_THREADS) = f32x4{wx2.x, wx2.y, ws2.x, ws2.y};
       const float* zbl = zb_b + (int64_t)l * 2 * p.Hp;
-      *(f32x4*)(q + (NU + 1) * 16 * ARC_THREADS) = f32x4{zbl[gch], zbl[p.Hp + gch], p.bias2[(int64_t)l * (R + S) + tid], 0.f};
+      *(f32x4*)(q + (NU + 1) * 16 * ARC_THREADS) =
+          f32x4{LIST ? 0.f : zbl[gch], LIST ? 0.f : zbl[p.Hp + gch], p.bias2[(int64_t)l * (R + S) + tid], 0.f};
     }
     if constexpr (NU == 4) {
       for (int k = 0; k < nbank; ++k) {
@@ -1326,12 +1415,88 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
         const f32x2_ wx2 = *(const f32x2_*)(wl + p.w2_off + w2xoff), ws2 = *(const f32x2_*)(wl + p.w2_off + w2soff);
         v[16] = wx2.x; v[17] = wx2.y; v[18] = ws2.x; v[19] = ws2.y;
         const float* zbl = zb_b + (int64_t)l * 2 * p.Hp;
-        v[20] = zbl[gch]; v[21] = zbl[p.Hp + gch]; v[22] = p.bias2[(int64_t)l * (R + S) + tid];
+        v[20] = LIST ? 0.f : zbl[gch]; v[21] = LIST ? 0.f : zbl[p.Hp + gch]; v[22] = p.bias2[(int64_t)l * (R + S) + tid];
         arc_bank_write<VB>(k, v);
       }
     }
     arc_barrier();
   }
+  [[maybe_unused]] unsigned mseq = 1;      // LIST: the message sequence runs on from the placement handshake (bank = mseq & 1)
+  for (;;) {      // LIST: one turn per item the team takes; otherwise one turn
+  if constexpr (LIST) {
+    // ---- the item boundary -------------------------------------------------------------------------------------------------------------
+    // The 32 members share one ring, every member writes every row without waiting for an acknowledgement, and a clip relies on zeros
+    // in the rows it reads before it has written them (the causal pad).  So between two clips:
+    //   1. every member drains its own stores of the finished clip (release fence: s_waitcnt vmcnt(0), and the write-back that makes
+    //      them visible beyond its XCD's L2 where the team is spread over several) and joins rendezvous A.  Behind A no store of
+    //      the finished clip is in flight any more: none can land on a row that has been cleared or rewritten for the next clip.
+    //   2. member m clears its 32nd of the ring and drains again (release fence).
+    //   3. rendezvous B -- the exchange that hands the team the next item index (thread 0 of member 0 took it with one returning atomic
+    //      add).  Behind B every 32nd is clear; the acquire fence drops what this CU's vector cache (and, where the team is spread, its
+    //      L2) still holds of the finished clip's rows, so the first history read of the new clip sees the zeros.
+    // The ring's contents at launch play no part: the first item is preceded by the same clearing.
+    // Sequence numbers.  A and B are arc_gather exchanges on msg in which every member publishes one granule and waits for all 32; the
+    // message sequence runs on from the placement handshake, bank = mseq & 1.  Two banks suffice as in arc_allgather: a member publishes
+    // mseq + 2 only after its gather of mseq + 1 returned, which needs every member's granule of mseq + 1, published after that member's
+    // gather of mseq returned (its polling pass and its re-read).  xuse / suse / huse / yuse run on across items too and nothing in acc is
+    // re-zeroed: every member of a team decodes the same items with the same step counts, hence performs the same exchanges in the same
+    // order, and the two-bank argument of arc_allgather / arc_allsum2 never looks at where a clip ends (the host bounds the list's total
+    // so that no 32-bit sequence number wraps).
+    int tl = tid;      // the thread index, opaque: what the boundary derives from it is worked out per item, not kept across the samples
+    asm volatile("" : "+v"(tl));
+    auto meet = [&](float mine, float* got) -> bool {
+      ++mseq;
+      unsigned long long* bank = msg_b + (int64_t)(mseq & 1) * C * p.NV;
+      if (tl == 0) __hip_atomic_store(bank + m * p.NV, arc_pack(mseq, mine), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return arc_gather(bank, p.NV, C, 1, C, mseq, p.error, &ibuf[1], [&](int i, float v) { got[i] = v; });
+    };
+    float* ids = psum;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (!meet(0.f, ids)) return;                                 // A
+    ring_clear(tl);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    int took = 0;
+    if (tl == 0 && m == 0) took = atomicAdd(p.next, 1);
+    if (!meet(__int_as_float(took), ids)) return;                // B
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    const int it = __builtin_amdgcn_readfirstlane(__float_as_int(ids[0]));      // member 0's granule: the same word on every member
+    arc_barrier();
+    if (it >= p.n_items) return;      // the team leaves together
+    const wae_ar_item w = p.items[it];
+    if (w.T <= 0) continue;           // skipped by the whole team
+    // as ar_list_kernel (csrc/ar_fwd.hip): mode 0 is teacher-forced throughout; a start class outside the table would read beyond first_tab
+    T = w.T; base = w.off;
+    nforced = !p.inputs ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
+    init = min(max(w.init_idx, 0), p.O - 1);
+    zb_b = p.zb + (int64_t)w.row * L * 2 * p.Hp;
+    item_state(tl);
+    if constexpr (LDSW) {
+      const int gl = ch0 + (tl & 3);      // gch
+      // the resident layers' zb_a / zb_g carry the speaker projection: the item's.  Each thread rewrites its own two words (LDS slot
+      // NU + 1, bank words 20 / 21) and leaves the weights where they are.
+      for (int l = 0; l < nlds; ++l) {
+        f32x4* q = (f32x4*)(wl0 + (size_t)l * PWL + tl * 16 + (NU + 1) * 16 * ARC_THREADS);
+        const float* zbl = zb_b + (int64_t)l * 2 * p.Hp;
+        f32x4 sc = *q;
+        sc.x = zbl[gl]; sc.y = zbl[p.Hp + gl];
+        *q = sc;
+      }
+      if constexpr (NU == 4) {
+        for (int k = 0; k < nbank; ++k) {
+          const float* zbl = zb_b + (int64_t)(nlds + k) * 2 * p.Hp;
+          float v[ARC_NB];
+          arc_bank_read<VB>(k, v);
+          v[20] = zbl[gl]; v[21] = zbl[p.Hp + gl];
+          arc_bank_write<VB>(k, v);
+        }
+      }
+    }
+    arc_barrier();
+    item_tab(tl);
+    arc_barrier();      // ltab: prefetch(0, 0) below reads ltab[0] on every thread (the single decode has the placement gather in between)
+  }
+  float creg = tid < Cc ? c_load(0) : 0.f;
   prefetch(0, 0);
   arc_barrier();      // ltab
   // Only the current tap of a layer's operand depends on the sample being computed: the packets of the two history taps and of the
@@ -1525,16 +1690,16 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
           return;
       }
       ARC_TICK(5);
-      arc_draw(p, lbuf, psum, ibuf, b, m, t);
+      arc_draw(p, lbuf, psum, ibuf, base, nforced, m, t);
       ARC_TICK(6);
     }
   } else
-  for (int t = 0; t < p.T; ++t) {
+  for (int t = 0; t < T; ++t) {
     const int cur = ibuf[0];
     xreg = p.first_tab[(int64_t)cur * p.Rp + tid] + fbias;
     vbuf[2 * R + tid] = xreg;
     ring[(unsigned)(ltab[0].z + tid)] = xreg;
-    if (tid < Cc && t + 1 < p.T) creg = c_load(t + 1);     // (this sample's row went into vbuf with layer 0's history taps)
+    if (tid < Cc && t + 1 < T) creg = c_load(t + 1);     // (this sample's row went into vbuf with layer 0's history taps)
     float skip_part = sbias;
     arc_barrier();
 
@@ -1621,13 +1786,15 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
       if (!arc_allgather(ybanks, O, yuse++, hsl == 0, 8 * m + hi, r2 + hb2, fast, p.error, &ibuf[1],
                          [&](float v) {
                            lbuf[tid] = v;
-                           if (p.out_logits && m == 0) p.out_logits[((int64_t)b * O + tid) * p.T + t] = v;
+                           if (p.out_logits && m == 0) p.out_logits[base * O + (int64_t)tid * T + t] = v;
                          }))
         return;
     }
     ARC_TICK(5);
-    arc_draw(p, lbuf, psum, ibuf, b, m, t);
+    arc_draw(p, lbuf, psum, ibuf, base, nforced, m, t);
     ARC_TICK(6);
+  }
+  if constexpr (!LIST) break;
   }
 #ifdef WAE_ARC_PROFILE
   if (tid == 0 && b == 0 && m == 0) {
@@ -1646,6 +1813,36 @@ __global__ void __launch_bounds__(ARC_THREADS) ar_coop_fast_kernel(ArcArgs p) {
 template <typename E>
 __global__ void __launch_bounds__(ARC_THREADS) __attribute__((amdgpu_num_vgpr(186))) ar_coop_fast_vb_kernel(ArcArgs p) {
   ar_coop_fast_body<E, 4, false, true, true>(p);
+}
+
+// the list forms (wae_ar_generate_coop_list): two hand-overs per layer only
+template <typename E, int NU, bool LDSW = false>
+__global__ void __launch_bounds__(ARC_THREADS) ar_coop_fast_list_kernel(ArcArgs p) {
+  ar_coop_fast_body<E, NU, false, LDSW, false, true>(p);
+}
+template <typename E>
+__global__ void __launch_bounds__(ARC_THREADS) __attribute__((amdgpu_num_vgpr(186))) ar_coop_fast_vb_list_kernel(ArcArgs p) {
+  ar_coop_fast_body<E, 4, false, true, true, true>(p);
+}
+
+template <typename E, int NU>
+static void launch_arc_fast_list(const ArcArgs& a, size_t lds, hipStream_t st) {
+  if constexpr (sizeof(E) == 2 && NU == 4) {
+    if (a.nlds > 0 && a.nbank > ARC_NBANK) {
+      (void)hipFuncSetAttribute((const void*)ar_coop_fast_vb_list_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((ar_coop_fast_vb_list_kernel<E>), dim3(8 * 32), dim3(ARC_THREADS), lds, st, a);
+      return;
+    }
+  }
+  if constexpr (sizeof(E) == 2) {
+    if (a.nlds > 0) {
+      (void)hipFuncSetAttribute((const void*)ar_coop_fast_list_kernel<E, NU, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((ar_coop_fast_list_kernel<E, NU, true>), dim3(8 * 32), dim3(ARC_THREADS), lds, st, a);
+      return;
+    }
+  }
+  (void)hipFuncSetAttribute((const void*)ar_coop_fast_list_kernel<E, NU, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((ar_coop_fast_list_kernel<E, NU, false>), dim3(8 * 32), dim3(ARC_THREADS), lds, st, a);
 }
 
 template <typename E, int NU>
@@ -1741,6 +1938,71 @@ static void launch_arc_generic(const ArcArgs& a, int dtype, size_t lds, hipStrea
   }
 }
 
+// Which kernel decodes geometry d on C members: the reference's own geometry on 32 members takes the kernels with the sizes as constants
+// (NU = W1 packets per GEMV thread; residency as wae_ar_desc.resident_lds / resident_regs say), everything else the any-shape kernel.
+// list: the work-list forms (a.w_fused is null there).
+static int arc_dispatch(const wae_ar_desc* d, int32_t C, ArcArgs& a, int64_t ring_total, const void* w_fused, bool list, hipStream_t st,
+                        const char* who) {
+  const int epl = wae_is16(d->dtype) ? 8 : 4;
+  const size_t lds = arc_generic_lds(d, C);
+  const int nu = ((3 * d->R + (d->Cc > 0 ? d->Cc : 0) + epl - 1) / epl + 31) / 32;
+  const bool fast_shape = C == 32 && d->R == 256 && d->S == 256 && d->O == 256 && d->G == 256 && d->ktaps == 3 && d->Cc <= 256 &&
+                          ring_total % 4 == 0 && !d->coop_generic;
+  if (fast_shape) {
+    a.w_fused = d->L >= 2 ? (const char*)w_fused : nullptr;     // the one-hand-over-per-layer kernel (else: ar_coop_fast_kernel's two)
+    size_t lds_f = sizeof(float) * (size_t)(32 + 4 * nu * 32 * epl / 4 + 4 * 256 + 8 + 4 * (d->L + 1) + 3 * d->L + epl);
+    // LDS-resident layers (16-bit, two hand-overs per layer): (nu + 2) x 16 B x 256 threads per layer behind the kernel's own arrays
+    a.nlds = 0;
+    if (wae_is16(d->dtype)) {
+      const size_t per = (size_t)(nu + 2) * 16 * ARC_THREADS;
+      int fit = (int)((160 * 1024 - lds_f - 64) / per);
+      a.nlds = resident_count(d->resident_lds, fit, fit);
+      if (a.nlds > fit) a.nlds = fit;
+      if (a.nlds > d->L) a.nlds = d->L;
+      if (a.nlds < 0) a.nlds = 0;
+      lds_f += 64 + per * a.nlds;
+      a.nbank = a.nlds > 0 ? resident_count(d->resident_regs, ARC_NBANK + ARC_NVB, ARC_NBANK + ARC_NVB) : 0;      // (the register banks belong to the LDS-resident instantiations)
+      if (a.w_fused && a.nbank > ARC_NBANK) a.nbank = ARC_NBANK;      // (the one-hand-over form has the accumulation registers only)
+      if (a.nbank > d->L - a.nlds) a.nbank = d->L - a.nlds > 0 ? d->L - a.nlds : 0;
+    }
+    bool done = true;
+    if (list) {
+      if (d->dtype == WAE_BF16 && nu == 3) launch_arc_fast_list<__bf16, 3>(a, lds_f, st);
+      else if (d->dtype == WAE_BF16 && nu == 4) launch_arc_fast_list<__bf16, 4>(a, lds_f, st);
+      else if (d->dtype == WAE_F16 && nu == 3) launch_arc_fast_list<f16, 3>(a, lds_f, st);
+      else if (d->dtype == WAE_F16 && nu == 4) launch_arc_fast_list<f16, 4>(a, lds_f, st);
+      else if (d->dtype == WAE_F32 && nu == 6) launch_arc_fast_list<float, 6>(a, lds_f, st);
+      else if (d->dtype == WAE_F32 && nu == 7) launch_arc_fast_list<float, 7>(a, lds_f, st);
+      else if (d->dtype == WAE_F32 && nu == 8) launch_arc_fast_list<float, 8>(a, lds_f, st);
+      else done = false;
+    }
+    else if (d->dtype == WAE_BF16 && nu == 3) launch_arc_fast<__bf16, 3>(a, lds_f, st);
+    else if (d->dtype == WAE_BF16 && nu == 4) launch_arc_fast<__bf16, 4>(a, lds_f, st);
+    else if (d->dtype == WAE_F16 && nu == 3) launch_arc_fast<f16, 3>(a, lds_f, st);
+    else if (d->dtype == WAE_F16 && nu == 4) launch_arc_fast<f16, 4>(a, lds_f, st);
+    else if (d->dtype == WAE_F32 && nu == 6) launch_arc_fast<float, 6>(a, lds_f, st);
+    else if (d->dtype == WAE_F32 && nu == 7) launch_arc_fast<float, 7>(a, lds_f, st);
+    else if (d->dtype == WAE_F32 && nu == 8) launch_arc_fast<float, 8>(a, lds_f, st);
+    else done = false;
+    if (done) return wae_check_launch(who);
+  }
+  if (list) {
+    if (d->dtype == WAE_BF16) {
+      (void)hipFuncSetAttribute((const void*)ar_coop_list_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((ar_coop_list_kernel<__bf16>), dim3(8 * a.C), dim3(ARC_THREADS), lds, st, a);
+    } else if (d->dtype == WAE_F16) {
+      (void)hipFuncSetAttribute((const void*)ar_coop_list_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((ar_coop_list_kernel<f16>), dim3(8 * a.C), dim3(ARC_THREADS), lds, st, a);
+    } else {
+      (void)hipFuncSetAttribute((const void*)ar_coop_list_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL((ar_coop_list_kernel<float>), dim3(8 * a.C), dim3(ARC_THREADS), lds, st, a);
+    }
+  } else {
+    launch_arc_generic<false>(a, d->dtype, lds, st);
+  }
+  return wae_check_launch(who);
+}
+
 static int ar_generate_coop_impl(const wae_ar_desc* d, int32_t C, const int32_t* dilations, const int64_t* ring_off, float* ring,
                                  int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
                                  const float* bias2, const float* zb, const float* first_tab, const float* first_bias,
@@ -1772,45 +2034,9 @@ static int ar_generate_coop_impl(const wae_ar_desc* d, int32_t C, const int32_t*
   a.inputs = inputs; a.init_idx = d->init_idx; a.uniforms = uniforms; a.out_idx = out_idx;
   a.n_forced = inputs ? (d->n_forced > 0 && d->n_forced < d->T ? d->n_forced : d->T) : 0;
   a.out_logits = out_logits;
-  const int epl = wae_is16(d->dtype) ? 8 : 4;
-  const size_t lds = arc_generic_lds(d, C);
   WAE_REQUIRE(ring_total < (int64_t)1 << 31, "ar_generate_coop: ring_total %lld does not fit 32-bit offsets", (long long)ring_total);
-  hipStream_t st = as_stream(stream);
   // the message banks must start with sequence numbers no exchange will use (0): the caller zeroes msg and error
-  // the reference's own geometry on 32 members: the kernel with the sizes as constants (NU = W1 packets per GEMV thread)
-  const int nu = ((3 * d->R + (d->Cc > 0 ? d->Cc : 0) + epl - 1) / epl + 31) / 32;
-  const bool fast_shape = C == 32 && d->R == 256 && d->S == 256 && d->O == 256 && d->G == 256 && d->ktaps == 3 && d->Cc <= 256 &&
-                          ring_total % 4 == 0 && !d->coop_generic;
-  if (fast_shape) {
-    a.w_fused = d->L >= 2 ? (const char*)w_fused : nullptr;     // the one-hand-over-per-layer kernel (else: ar_coop_fast_kernel's two)
-    size_t lds_f = sizeof(float) * (size_t)(32 + 4 * nu * 32 * epl / 4 + 4 * 256 + 8 + 4 * (d->L + 1) + 3 * d->L + epl);
-    // LDS-resident layers (16-bit, two hand-overs per layer): (nu + 2) x 16 B x 256 threads per layer behind the kernel's own arrays
-    a.nlds = 0;
-    if (wae_is16(d->dtype)) {
-      const size_t per = (size_t)(nu + 2) * 16 * ARC_THREADS;
-      int fit = (int)((160 * 1024 - lds_f - 64) / per);
-      a.nlds = resident_count(d->resident_lds, fit, fit);
-      if (a.nlds > fit) a.nlds = fit;
-      if (a.nlds > d->L) a.nlds = d->L;
-      if (a.nlds < 0) a.nlds = 0;
-      lds_f += 64 + per * a.nlds;
-      a.nbank = a.nlds > 0 ? resident_count(d->resident_regs, ARC_NBANK + ARC_NVB, ARC_NBANK + ARC_NVB) : 0;      // (the register banks belong to the LDS-resident instantiations)
-      if (a.w_fused && a.nbank > ARC_NBANK) a.nbank = ARC_NBANK;      // (the one-hand-over form has the accumulation registers only)
-      if (a.nbank > d->L - a.nlds) a.nbank = d->L - a.nlds > 0 ? d->L - a.nlds : 0;
-    }
-    bool done = true;
-    if (d->dtype == WAE_BF16 && nu == 3) launch_arc_fast<__bf16, 3>(a, lds_f, st);
-    else if (d->dtype == WAE_BF16 && nu == 4) launch_arc_fast<__bf16, 4>(a, lds_f, st);
-    else if (d->dtype == WAE_F16 && nu == 3) launch_arc_fast<f16, 3>(a, lds_f, st);
-    else if (d->dtype == WAE_F16 && nu == 4) launch_arc_fast<f16, 4>(a, lds_f, st);
-    else if (d->dtype == WAE_F32 && nu == 6) launch_arc_fast<float, 6>(a, lds_f, st);
-    else if (d->dtype == WAE_F32 && nu == 7) launch_arc_fast<float, 7>(a, lds_f, st);
-    else if (d->dtype == WAE_F32 && nu == 8) launch_arc_fast<float, 8>(a, lds_f, st);
-    else done = false;
-    if (done) return wae_check_launch("ar_generate_coop");
-  }
-  launch_arc_generic<false>(a, d->dtype, lds, st);
-  return wae_check_launch("ar_generate_coop");
+  return arc_dispatch(d, C, a, ring_total, w_fused, false, as_stream(stream), "ar_generate_coop");
 }
 
 extern "C" int wae_ar_generate_coop(const wae_ar_desc* d, int32_t C, const int32_t* dilations, const int64_t* ring_off, float* ring,
@@ -1833,6 +2059,56 @@ extern "C" int wae_ar_generate_coop_fused(const wae_ar_desc* d, int32_t C, const
   return ar_generate_coop_impl(d, C, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
                                first_bias, w_head, head_bias, c_up, c_dtype, inputs, uniforms, out_idx, out_logits, msg, acc, error, w_fused,
                                stream);
+}
+
+// A work list on cooperative teams: n_teams teams of C workgroups (team = blockIdx.x & 7, one XCD each where the dispatch is round-robin)
+// empty the queue of wae_ar_generate_list's items; the kernels are the LIST forms of wae_ar_generate_coop's (include/wae.h).
+extern "C" int wae_ar_generate_coop_list(const wae_ar_desc* d, int32_t C, int32_t n_items, int32_t n_teams, const wae_ar_item* items,
+                                         int32_t* next, int64_t total, const int32_t* dilations, const int64_t* ring_off, float* ring,
+                                         int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
+                                         const float* bias2, const float* zb, const float* first_tab, const float* first_bias,
+                                         const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
+                                         const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
+                                         uint64_t* msg, float* acc, int32_t* error, void* stream) {
+  WAE_REQUIRE(d && dilations && ring_off && ring && w_layers && bias2 && zb && first_tab && first_bias && w_head && head_bias && out_idx,
+              "ar_generate_coop_list: null pointer argument");
+  if (d->scalar_input) {
+    wae_set_error("ar_generate_coop_list: list decoding covers class-id decoders; scalar-input decoders go through wae_ar_generate_coop_scalar");
+    return WAE_EUNSUPPORTED;
+  }
+  if (d->mode == 3 || d->mode == 4) {
+    wae_set_error("ar_generate_coop_list: modes 3 / 4 (dense feedback) are not list-decoded; use wae_ar_generate");
+    return WAE_EUNSUPPORTED;
+  }
+  WAE_REQUIRE(items && next, "ar_generate_coop_list: the item array and the queue counter are required");
+  WAE_REQUIRE(msg && acc && error, "ar_generate_coop_list: the exchange buffers msg, acc and error are required");
+  WAE_REQUIRE(d->t0 == 0, "ar_generate_coop_list: t0 %d: a list decode cannot be continued", d->t0);
+  WAE_REQUIRE(n_items >= 1, "ar_generate_coop_list: n_items %d < 1", n_items);
+  WAE_REQUIRE(n_teams >= 1 && n_teams <= 8, "ar_generate_coop_list: n_teams %d outside 1..8 (one XCD each)", n_teams);
+  WAE_REQUIRE(C >= 1 && C <= ARC_CMAX, "ar_generate_coop_list: C %d outside 1..%d cooperating workgroups per team", C, ARC_CMAX);
+  WAE_REQUIRE(wae_dtype_ok(d->dtype), "ar_generate_coop_list: bad dtype");
+  WAE_REQUIRE(d->R <= ARC_THREADS && d->S <= ARC_THREADS && d->O <= ARC_THREADS, "ar_generate_coop_list: R, S and O <= %d (got %d, %d, %d)",
+              ARC_THREADS, d->R, d->S, d->O);
+  WAE_REQUIRE(d->L > 0 && d->R > 0 && d->G > 0 && d->G % 2 == 0 && d->S > 0 && d->O > 0, "ar_generate_coop_list: bad sizes");
+  WAE_REQUIRE(d->Cc <= 0 || c_up, "ar_generate_coop_list: Cc > 0 but c_up is null");
+  WAE_REQUIRE(d->mode >= 0 && d->mode <= 2, "ar_generate_coop_list: mode must be 0 (logits), 1 (argmax) or 2 (sample)");
+  WAE_REQUIRE(d->mode != 0 || inputs, "ar_generate_coop_list: mode 0 needs inputs for every step");
+  WAE_REQUIRE(d->mode != 2 || uniforms, "ar_generate_coop_list: sample mode needs uniforms");
+  // the exchange sequence numbers run on across a team's items: at most L per step (the x' sums), one per step for the skip sum and each
+  // of the head's gathers, two messages per item taken or refused -- all below (total + n_items + 1) * (L + 4), which must fit 31 bits
+  WAE_REQUIRE(total >= 0 && (total + n_items + 1) <= (((int64_t)1 << 31) - 1) / (d->L + 4),
+              "ar_generate_coop_list: %lld steps in %d items on %d layers: the exchange sequence numbers would not fit 31 bits",
+              (long long)total, n_items, d->L);
+  const int H = d->G / 2;
+  const int hc = (H + C - 1) / C, sc = (d->S + C - 1) / C;
+  WAE_REQUIRE(2 * hc <= ARC_THREADS && sc <= ARC_THREADS, "ar_generate_coop_list: too few workgroups for G=%d, S=%d", d->G, d->S);
+  WAE_REQUIRE(ring_total < (int64_t)1 << 31, "ar_generate_coop_list: ring_total %lld does not fit 32-bit offsets", (long long)ring_total);
+  ArcArgs a = arc_common_args(d, C, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
+                              first_bias, w_head, head_bias, c_up, c_dtype, msg, acc, error);
+  a.B = n_teams; a.T = 0; a.t0 = 0; a.n_forced = 0; a.init_idx = 0;      // per item
+  a.inputs = inputs; a.uniforms = uniforms; a.out_idx = out_idx; a.out_logits = out_logits;
+  a.items = items; a.next = next; a.n_items = n_items;
+  return arc_dispatch(d, C, a, ring_total, nullptr, true, as_stream(stream), "ar_generate_coop_list");
 }
 
 // Scalar-input decoders on the any-shape cooperative kernel (ar_coop_kernel<E, true>): the network, the split and the exchanges of

@@ -923,7 +923,7 @@ class WaeEngine:
         return item
 
     def decode_list(self, items, mode: str = "sample", slots: Optional[int] = None, want_logits: bool = False,
-                    c_is_upsampled: bool = False):
+                    c_is_upsampled: bool = False, coop: bool = False, teams: Optional[int] = None):
         """A work list of utterances of unequal lengths in ONE launch (include/wae.h: wae_ar_generate_list): `slots` persistent
         workgroups, one per CU, each decoding one item after another until the list is empty -- throughput decoding, where
         incremental_forward takes equal lengths only and a loop over it leaves most of the device idle.
@@ -940,11 +940,22 @@ class WaeEngine:
         Returns, in the caller's order, a list of dict(idx (T,) int32, logits (O, T) fp32 | None); every item is, bit for bit, what
         incremental_forward returns for that utterance alone on the one-CU kernel (WAE_AR_COOP=0).
         Always the list kernel: ar_path() and WAE_AR_COOP have no effect here.  Class-id decoders only: a scalar-input geometry
-        raises NotImplementedError, an empty list ValueError, both before any launch."""
+        raises NotImplementedError, an empty list ValueError, both before any launch.
+
+        coop=True: the same list on cooperative teams (include/wae.h: wae_ar_generate_coop_list) -- `teams` teams (default
+        min(len(items), 8); clamped to 1..8, one XCD each, and to the item count) of C = min(WAE_AR_COOP_C, 32, H, S) workgroups, each
+        team decoding one item after another on the cooperative kernels, longest first (packing.ar_list_plan(Ts, teams)); `slots` is
+        not used.  Every item is then, bit for bit, what incremental_forward returns for that utterance alone on the cooperative path
+        (WAE_AR_COOP=1, the same ar_path, no one_handover).  ar_path(generic=, lds_layers=, reg_layers=) is honoured as there;
+        one_handover is ignored (the one-hand-over kernel has no list form: the list runs two hand-overs per layer).  A wait between
+        team-mates that times out raises WaeError after the launch; R, S or O > 256 raises ValueError before any launch."""
         g = self.g
         if g.scalar_input:
             raise NotImplementedError("decode_list: list decoding covers class-id decoders; decode scalar-input models one batch at a "
                                       "time with incremental_forward")
+        if coop and max(g.R, g.S, g.O) > 256:
+            raise ValueError(f"decode_list(coop=True): the cooperative kernels take R, S and O <= 256 (got {g.R}, {g.S}, {g.O}); "
+                             "use the one-CU list (coop=False)")
         items = list(items)
         if not items:
             raise ValueError("decode_list: an empty list")
@@ -953,7 +964,9 @@ class WaeEngine:
         m = {"logits": 0, "argmax": 1, "sample": 2}[mode]
         lib, dev, n = self.lib, self.device, len(items)
         Ts = [int(it["T"]) for it in items]
-        if slots is None:
+        if coop:
+            slots = max(1, min(8 if teams is None else int(teams), 8))      # teams; the plan clamps them to the item count
+        elif slots is None:
             slots = torch.cuda.get_device_properties(dev).multi_processor_count
         plan = P.ar_list_plan(Ts, slots)
         total, off = plan.total, [int(o) for o in plan.offsets]
@@ -1025,22 +1038,39 @@ class WaeEngine:
             rec[k] = (off[i], Ts[i], nfs[i], inits[i], int(i))
         items_d = torch.from_numpy(rec.view(np.uint8)).to(dev)
         nxt = torch.zeros(1, dtype=torch.int32, device=dev)
-        # not zeroed: a decode reads a history row only behind its own write of it (csrc/ar_fwd.hip: ar_decode), in the first item of a
-        # slot as in every later one
-        ring = torch.empty(plan.slots * self.ar_ring_total, dtype=torch.float32, device=dev)
         out_idx = torch.empty(total, dtype=torch.int32, device=dev)
         want = want_logits or m == 0
         logits = torch.empty(total * g.O, dtype=torch.float32, device=dev) if want else None
+        path = (int(self.ar_generic), self.ar_resident[0], self.ar_resident[1]) if coop else ()
         d = L.ArDesc(self.dt, n, 0, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, 0, 0,
-                     math.sqrt(1.0 / g.layers), 0)
+                     math.sqrt(1.0 / g.layers), 0, *path)
         es = self.ar_w.element_size()
-        L.check(lib.wae_ar_generate_list(ctypes.byref(d), n, plan.slots, L.ptr(items_d), L.ptr(nxt), L.ptr(self.ar_dil),
-                                         L.ptr(self.ar_ring_off), L.ptr(ring), self.ar_ring_total, L.ptr(self.ar_w),
-                                         self.ar_layer_elems * es, self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(zb),
-                                         L.ptr(self.first_tab), L.ptr(self.first_bias), L.ptr(self.ar_wh), L.ptr(self.ar_hb),
-                                         L.ptr(c_up), self.dt, L.ptr(inputs), L.ptr(uni), L.ptr(out_idx), L.ptr(logits), st),
-                "ar_generate_list")
-        self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, uni)      # the launch's operands live until the stream has run
+        common = (L.ptr(self.ar_dil), L.ptr(self.ar_ring_off))
+        weights = (self.ar_ring_total, L.ptr(self.ar_w), self.ar_layer_elems * es, self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(zb),
+                   L.ptr(self.first_tab), L.ptr(self.first_bias), L.ptr(self.ar_wh), L.ptr(self.ar_hb), L.ptr(c_up), self.dt,
+                   L.ptr(inputs), L.ptr(uni), L.ptr(out_idx), L.ptr(logits))
+        if coop:
+            C = max(1, min(self.opt.ar_coop_c, 32, g.H, g.S))       # as _ar_open
+            nv = lib.wae_ar_coop_msg_values(ctypes.byref(d), C)
+            # the kernels do not depend on the ring's contents; msg, acc, error (and next) start from zero
+            ring = torch.empty(plan.slots * C * self.ar_ring_total, dtype=torch.float32, device=dev)
+            msg = torch.zeros(plan.slots * 2 * C * nv, dtype=torch.int64, device=dev)
+            acc = torch.zeros(plan.slots * lib.wae_ar_coop_acc_floats(ctypes.byref(d)), dtype=torch.float32, device=dev)
+            err = torch.zeros(64, dtype=torch.int32, device=dev)
+            L.check(lib.wae_ar_generate_coop_list(ctypes.byref(d), C, n, plan.slots, L.ptr(items_d), L.ptr(nxt), total, *common,
+                                                  L.ptr(ring), *weights, L.ptr(msg), L.ptr(acc), L.ptr(err), st),
+                    "ar_generate_coop_list")
+            self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, uni, msg, acc, err)
+            self._ar_profile = err
+            if int(err[0].item()) != 0:         # synchronises, once per launch, as _ar_launch
+                raise L.WaeError("ar_generate_coop_list: an exchange between the cooperating workgroups timed out")
+        else:
+            # not zeroed: a decode reads a history row only behind its own write of it (csrc/ar_fwd.hip: ar_decode), in the first item
+            # of a slot as in every later one
+            ring = torch.empty(plan.slots * self.ar_ring_total, dtype=torch.float32, device=dev)
+            L.check(lib.wae_ar_generate_list(ctypes.byref(d), n, plan.slots, L.ptr(items_d), L.ptr(nxt), *common, L.ptr(ring), *weights,
+                                             st), "ar_generate_list")
+            self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, uni)      # the launch's operands live until the stream has run
         return [dict(idx=out_idx[off[i]:off[i] + Ts[i]],
                      logits=logits[off[i] * g.O:(off[i] + Ts[i]) * g.O].view(g.O, Ts[i]) if want else None) for i in range(n)]
 
