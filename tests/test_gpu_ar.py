@@ -367,3 +367,63 @@ def test_start_class_per_utterance_against_oracle(kernel, monkeypatch):
         eng.incremental_forward(c_up.cuda(), ins["g"].cuda(), T, mode="argmax", init_idx=torch.tensor([0, cfg["O"]]), c_is_upsampled=True)
     with pytest.raises(ValueError):
         eng.incremental_forward(c_up.cuda(), ins["g"].cuda(), T, mode="argmax", init_idx=torch.tensor([0, 1, 2]), c_is_upsampled=True)
+
+
+@pytest.mark.parametrize("coop", [False, True], ids=["one_cu", "any_shape_c2"])
+def test_two_geometries_on_one_kernel_instantiation(coop, monkeypatch):
+    """The decode launches remember per kernel instantiation the dynamic LDS a device has granted (csrc/ar_host.hpp: ar_launch_dyn).  Two
+    engines in one process run the same instantiation (fp32, any shape) with different LDS sizes: greedy decodes in the order small,
+    large, small and then large, small, large; every decode of an engine is, bit for bit, that engine's decode in the other order.
+    Both sizes are a few KB, below the 64 KB a kernel gets without asking: this pins that the launches do not depend on their order,
+    not the cache itself -- test_resident_layers_grow_and_shrink_the_lds_of_one_instantiation asks for more than 64 KB."""
+    from wavenet_autoencoders_amd import Geometry
+    from wavenet_autoencoders_amd.engine import WaeEngine
+    monkeypatch.setenv("WAE_AR_COOP", "1" if coop else "0")
+    monkeypatch.setenv("WAE_AR_COOP_C", "2")
+    small = dict(layers=2, stacks=1, R=16, G=32, S=16, O=16, Cc=-1, Cg=-1, k=2, n_speakers=None, upsample_scales=None, cin_pad=0)
+    engines = []
+    for cfg in (small, dict(small, R=64, G=128, S=64, O=64)):
+        eng = WaeEngine(Geometry.from_cfg(cfg), dtype="fp32")
+        eng.load_state_dict(O.make_state_dict(dict(cfg), salt=11, with_encoder=False))
+        engines.append(eng)
+
+    def decode(eng):
+        out = eng.incremental_forward(None, None, 8, mode="argmax", init_idx=eng.g.O // 2 - 1, want_logits=True)
+        torch.cuda.synchronize()
+        assert (getattr(eng, "_ar_profile", None) is not None) == coop      # the path asked for really ran
+        return out["idx"].clone(), out["logits"].clone()
+
+    runs = [(i, decode(engines[i])) for i in (0, 1, 0, 1, 0, 1)]
+    for i, (idx, logits) in runs[2:]:
+        assert torch.equal(idx, runs[i][1][0]) and torch.equal(logits, runs[i][1][1]), i
+    assert runs[0][1][1].shape == (1, 16, 8) and runs[1][1][1].shape == (1, 64, 8)
+    assert bool(torch.isfinite(runs[1][1][1]).all()) and float(runs[1][1][1].abs().max()) > 0
+
+
+def test_resident_layers_grow_and_shrink_the_lds_of_one_instantiation(monkeypatch):
+    """The cache of ar_launch_dyn where it decides a launch: the sized bf16 kernel with LDS-resident layers (ar_coop_fast_kernel<__bf16, 4,
+    false, true>) takes 24 KB of dynamic LDS per resident layer, so 3 layers are about 82 KB and 6 about 156 KB, both beyond the 64 KB
+    a kernel gets without raising its limit.  One engine decodes with 3, 6, 3, 6 resident layers: a launch that skipped raising the limit
+    because a smaller size had been granted is refused by the runtime (WaeError).  Where a layer waits is not arithmetic: all four
+    decodes are the same, bit for bit."""
+    from wavenet_autoencoders_amd import Geometry
+    from wavenet_autoencoders_amd.engine import WaeEngine
+    monkeypatch.setenv("WAE_AR_COOP", "1")
+    monkeypatch.setenv("WAE_AR_COOP_C", "32")
+    cfg = dict(layers=20, stacks=2, R=256, G=256, S=256, O=256, Cc=64, Cg=32, k=3, n_speakers=153, upsample_scales=[4, 4, 8, 5], cin_pad=0)
+    eng = WaeEngine(Geometry.from_cfg(cfg), dtype="bf16")
+    eng.load_state_dict(O.make_state_dict(dict(cfg), salt=7, with_encoder=False))
+    T = 640
+    gen = torch.Generator().manual_seed(5)
+    lat = torch.randn(1, 64, T // 640, generator=gen).cuda()
+    gid = torch.tensor([3]).cuda()
+    uni = torch.rand(1, T, generator=gen).cuda()
+    got = []
+    for n in (3, 6, 3, 6):
+        eng.ar_path(lds_layers=n, reg_layers=0)
+        got.append(eng.incremental_forward(lat, gid, T, mode="sample", uniforms=uni)["idx"].clone())
+        torch.cuda.synchronize()
+        assert eng._ar_profile is not None
+    assert int(torch.unique(got[0]).numel()) > 50
+    for g_ in got[1:]:
+        assert torch.equal(g_, got[0])

@@ -1825,56 +1825,51 @@ __global__ void __launch_bounds__(ARC_THREADS) __attribute__((amdgpu_num_vgpr(18
   ar_coop_fast_body<E, 4, false, true, true, true>(p);
 }
 
-template <typename E, int NU>
-static void launch_arc_fast_list(const ArcArgs& a, size_t lds, hipStream_t st) {
-  if constexpr (sizeof(E) == 2 && NU == 4) {
-    if (a.nlds > 0 && a.nbank > ARC_NBANK) {
-      (void)hipFuncSetAttribute((const void*)ar_coop_fast_vb_list_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((ar_coop_fast_vb_list_kernel<E>), dim3(8 * 32), dim3(ARC_THREADS), lds, st, a);
-      return;
-    }
-  }
-  if constexpr (sizeof(E) == 2) {
-    if (a.nlds > 0) {
-      (void)hipFuncSetAttribute((const void*)ar_coop_fast_list_kernel<E, NU, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((ar_coop_fast_list_kernel<E, NU, true>), dim3(8 * 32), dim3(ARC_THREADS), lds, st, a);
-      return;
-    }
-  }
-  (void)hipFuncSetAttribute((const void*)ar_coop_fast_list_kernel<E, NU, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((ar_coop_fast_list_kernel<E, NU, false>), dim3(8 * 32), dim3(ARC_THREADS), lds, st, a);
-}
+#include "ar_host.hpp"
 
-template <typename E, int NU>
-static void launch_arc_fast(const ArcArgs& a, size_t lds, hipStream_t st) {
-  if (a.w_fused) {
-    if constexpr (sizeof(E) == 2) {
-      if (a.nlds > 0) {
-        (void)hipFuncSetAttribute((const void*)ar_coop_fast_kernel<E, NU, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((ar_coop_fast_kernel<E, NU, true, true>), dim3(8 * 32), dim3(ARC_THREADS), lds, st, a);
-        return;
+// The sized kernel of (E, NU) for what the arguments ask: the one-hand-over form where a.w_fused is set (never in a list), the bank of
+// ARC_NVB more register-resident layers where 16-bit NU = 4 has them, LDS-resident layers where 16-bit storage has any, else the plain one.
+#define ARC_FAST(...) AR_LAUNCH((__VA_ARGS__), dim3(8 * 32), dim3(ARC_THREADS), lds, st, a, who)
+template <typename E, int NU, bool LIST>
+static int launch_arc_fast(const ArcArgs& a, size_t lds, hipStream_t st, const char* who) {
+  if constexpr (!LIST) {
+    if (a.w_fused) {
+      if constexpr (sizeof(E) == 2) {
+        if (a.nlds > 0) ARC_FAST(ar_coop_fast_kernel<E, NU, true, true>);
       }
+      ARC_FAST(ar_coop_fast_kernel<E, NU, true>);
     }
-    (void)hipFuncSetAttribute((const void*)ar_coop_fast_kernel<E, NU, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((ar_coop_fast_kernel<E, NU, true>), dim3(8 * 32), dim3(ARC_THREADS), lds, st, a);
-    return;
   }
   if constexpr (sizeof(E) == 2 && NU == 4) {
     if (a.nlds > 0 && a.nbank > ARC_NBANK) {
-      (void)hipFuncSetAttribute((const void*)ar_coop_fast_vb_kernel<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((ar_coop_fast_vb_kernel<E>), dim3(8 * 32), dim3(ARC_THREADS), lds, st, a);
-      return;
+      if constexpr (LIST) ARC_FAST(ar_coop_fast_vb_list_kernel<E>);
+      else ARC_FAST(ar_coop_fast_vb_kernel<E>);
     }
   }
   if constexpr (sizeof(E) == 2) {
     if (a.nlds > 0) {
-      (void)hipFuncSetAttribute((const void*)ar_coop_fast_kernel<E, NU, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((ar_coop_fast_kernel<E, NU, false, true>), dim3(8 * 32), dim3(ARC_THREADS), lds, st, a);
-      return;
+      if constexpr (LIST) ARC_FAST(ar_coop_fast_list_kernel<E, NU, true>);
+      else ARC_FAST(ar_coop_fast_kernel<E, NU, false, true>);
     }
   }
-  (void)hipFuncSetAttribute((const void*)ar_coop_fast_kernel<E, NU, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL((ar_coop_fast_kernel<E, NU, false>), dim3(8 * 32), dim3(ARC_THREADS), lds, st, a);
+  if constexpr (LIST) ARC_FAST(ar_coop_fast_list_kernel<E, NU, false>);
+  else ARC_FAST(ar_coop_fast_kernel<E, NU, false>);
+}
+#undef ARC_FAST
+
+// the (dtype, NU) pairs that have sized kernels; for every other pair nothing is launched and `found` becomes false
+template <bool LIST>
+static int launch_arc_sized(int nu, const ArcArgs& a, size_t lds, hipStream_t st, const char* who, bool& found) {
+  found = true;
+  if (a.dtype == WAE_BF16 && nu == 3) return launch_arc_fast<__bf16, 3, LIST>(a, lds, st, who);
+  if (a.dtype == WAE_BF16 && nu == 4) return launch_arc_fast<__bf16, 4, LIST>(a, lds, st, who);
+  if (a.dtype == WAE_F16 && nu == 3) return launch_arc_fast<f16, 3, LIST>(a, lds, st, who);
+  if (a.dtype == WAE_F16 && nu == 4) return launch_arc_fast<f16, 4, LIST>(a, lds, st, who);
+  if (a.dtype == WAE_F32 && nu == 6) return launch_arc_fast<float, 6, LIST>(a, lds, st, who);
+  if (a.dtype == WAE_F32 && nu == 7) return launch_arc_fast<float, 7, LIST>(a, lds, st, who);
+  if (a.dtype == WAE_F32 && nu == 8) return launch_arc_fast<float, 8, LIST>(a, lds, st, who);
+  found = false;
+  return WAE_OK;
 }
 
 // how many layers stay resident (wae_ar_desc.resident_lds / resident_regs): 0 = the default, n > 0 = n, < 0 = none
@@ -1890,64 +1885,53 @@ extern "C" int64_t wae_ar_coop_acc_floats(const wae_ar_desc* d) {
 
 extern "C" int wae_ar_coop_msg_values(const wae_ar_desc* d, int32_t C) {
   if (!d || C <= 0) return WAE_EINVAL;
-  const int H = d->G / 2;
-  const int hc = (H + C - 1) / C, sc = (d->S + C - 1) / C;
-  return hc > sc ? hc : sc;
+  return ar_split(d, C).NV;
 }
 
+// the buffers the members meet in, zeroed by the caller (the message banks must start with sequence numbers no exchange will use: 0)
+struct ArcExchange {
+  uint64_t* msg;
+  float* acc;
+  int32_t* error;
+  bool ok() const { return msg && acc && error; }
+};
+
 // the arguments every cooperative kernel shares (everything else zero / null)
-static ArcArgs arc_common_args(const wae_ar_desc* d, int32_t C, const int32_t* dilations, const int64_t* ring_off, float* ring,
-                               int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
-                               const float* bias2, const float* zb, const float* first_tab, const float* first_bias, const void* w_head,
-                               const float* head_bias, const void* c_up, int32_t c_dtype, uint64_t* msg, float* acc, int32_t* error) {
+static ArcArgs arc_common_args(const wae_ar_desc* d, int32_t C, const ArNet& net, const ArcExchange& x) {
   ArcArgs a = {};
-  const int H = d->G / 2;
-  const int hc = (H + C - 1) / C, sc = (d->S + C - 1) / C;
-  a.dtype = d->dtype; a.B = d->B; a.T = d->T; a.L = d->L; a.R = d->R; a.G = d->G; a.S = d->S; a.O = d->O; a.Cc = d->Cc;
-  a.Ccp = d->Ccp; a.Hp = d->Hp; a.ktaps = d->ktaps; a.mode = d->mode; a.Rp = d->Rp; a.C = C; a.scale = d->scale; a.dil = dilations;
-  a.ring_off = ring_off; a.ring = ring; a.ring_total = ring_total; a.w_layers = (const char*)w_layers;
-  a.layer_stride = layer_stride_bytes; a.w2_off = w2_off_bytes; a.bias2 = bias2; a.zb = zb; a.first_tab = first_tab;
-  a.first_bias = first_bias; a.w_head = (const char*)w_head; a.head_bias = head_bias; a.c_up = (const char*)c_up;
-  a.c_dtype = c_dtype;
-  a.msg = (unsigned long long*)msg; a.NV = hc > sc ? hc : sc; a.acc = acc; a.error = error;
-  a.t0 = d->t0;
+  ar_fill_net(a, d, net);
+  a.C = C; a.msg = (unsigned long long*)x.msg; a.NV = ar_split(d, C).NV; a.acc = x.acc; a.error = x.error;
   return a;
 }
 
 // dynamic LDS of the any-shape kernel (ar_coop_kernel's carve, rounded up)
 static size_t arc_generic_lds(const wae_ar_desc* d, int32_t C) {
   const int epl = wae_is16(d->dtype) ? 8 : 4;
-  const int H = d->G / 2;
-  const int hc = (H + C - 1) / C, sc = (d->S + C - 1) / C;
   auto ru = [](int x, int mm) { return (x + mm - 1) / mm * mm; };
-  return sizeof(float) * (size_t)(ru(d->ktaps * d->R + (d->Cc > 0 ? d->Cc : 0), epl) + d->R + ru(H, epl) + 2 * ru(d->S, epl) + ru(d->O, 4) +
-                                  ARC_THREADS + ru(hc > sc ? hc : sc, 4) + 8 + 3 * d->L + 64);
+  return sizeof(float) * (size_t)(ru(d->ktaps * d->R + (d->Cc > 0 ? d->Cc : 0), epl) + d->R + ru(d->G / 2, epl) + 2 * ru(d->S, epl) +
+                                  ru(d->O, 4) + ARC_THREADS + ru(ar_split(d, C).NV, 4) + 8 + 3 * d->L + 64);
 }
 
-template <bool SCALAR>
-static void launch_arc_generic(const ArcArgs& a, int dtype, size_t lds, hipStream_t st) {
-  if (dtype == WAE_BF16) {
-    (void)hipFuncSetAttribute((const void*)ar_coop_kernel<__bf16, SCALAR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((ar_coop_kernel<__bf16, SCALAR>), dim3(8 * a.C), dim3(ARC_THREADS), lds, st, a);
-  } else if (dtype == WAE_F16) {
-    (void)hipFuncSetAttribute((const void*)ar_coop_kernel<f16, SCALAR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((ar_coop_kernel<f16, SCALAR>), dim3(8 * a.C), dim3(ARC_THREADS), lds, st, a);
-  } else {
-    (void)hipFuncSetAttribute((const void*)ar_coop_kernel<float, SCALAR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((ar_coop_kernel<float, SCALAR>), dim3(8 * a.C), dim3(ARC_THREADS), lds, st, a);
-  }
+// the any-shape kernels: class ids, a scalar draw, or the work list of class ids
+enum ArcForm { ARC_CLASS_IDS, ARC_SCALAR, ARC_LIST };
+template <ArcForm F>
+static int launch_arc_generic(const ArcArgs& a, size_t lds, hipStream_t st, const char* who) {
+  const dim3 grid(8 * a.C), block(ARC_THREADS);
+  return ar_by_dtype(a.dtype, [&](auto e) {
+    using E = typename decltype(e)::type;
+    if constexpr (F == ARC_LIST) AR_LAUNCH(ar_coop_list_kernel<E>, grid, block, lds, st, a, who);
+    else AR_LAUNCH((ar_coop_kernel<E, F == ARC_SCALAR>), grid, block, lds, st, a, who);
+  });
 }
 
 // Which kernel decodes geometry d on C members: the reference's own geometry on 32 members takes the kernels with the sizes as constants
 // (NU = W1 packets per GEMV thread; residency as wae_ar_desc.resident_lds / resident_regs say), everything else the any-shape kernel.
 // list: the work-list forms (a.w_fused is null there).
-static int arc_dispatch(const wae_ar_desc* d, int32_t C, ArcArgs& a, int64_t ring_total, const void* w_fused, bool list, hipStream_t st,
-                        const char* who) {
+static int arc_dispatch(const wae_ar_desc* d, int32_t C, ArcArgs& a, const void* w_fused, bool list, hipStream_t st, const char* who) {
   const int epl = wae_is16(d->dtype) ? 8 : 4;
-  const size_t lds = arc_generic_lds(d, C);
   const int nu = ((3 * d->R + (d->Cc > 0 ? d->Cc : 0) + epl - 1) / epl + 31) / 32;
   const bool fast_shape = C == 32 && d->R == 256 && d->S == 256 && d->O == 256 && d->G == 256 && d->ktaps == 3 && d->Cc <= 256 &&
-                          ring_total % 4 == 0 && !d->coop_generic;
+                          a.ring_total % 4 == 0 && !d->coop_generic;
   if (fast_shape) {
     a.w_fused = d->L >= 2 ? (const char*)w_fused : nullptr;     // the one-hand-over-per-layer kernel (else: ar_coop_fast_kernel's two)
     size_t lds_f = sizeof(float) * (size_t)(32 + 4 * nu * 32 * epl / 4 + 4 * 256 + 8 + 4 * (d->L + 1) + 3 * d->L + epl);
@@ -1965,89 +1949,12 @@ static int arc_dispatch(const wae_ar_desc* d, int32_t C, ArcArgs& a, int64_t rin
       if (a.w_fused && a.nbank > ARC_NBANK) a.nbank = ARC_NBANK;      // (the one-hand-over form has the accumulation registers only)
       if (a.nbank > d->L - a.nlds) a.nbank = d->L - a.nlds > 0 ? d->L - a.nlds : 0;
     }
-    bool done = true;
-    if (list) {
-      if (d->dtype == WAE_BF16 && nu == 3) launch_arc_fast_list<__bf16, 3>(a, lds_f, st);
-      else if (d->dtype == WAE_BF16 && nu == 4) launch_arc_fast_list<__bf16, 4>(a, lds_f, st);
-      else if (d->dtype == WAE_F16 && nu == 3) launch_arc_fast_list<f16, 3>(a, lds_f, st);
-      else if (d->dtype == WAE_F16 && nu == 4) launch_arc_fast_list<f16, 4>(a, lds_f, st);
-      else if (d->dtype == WAE_F32 && nu == 6) launch_arc_fast_list<float, 6>(a, lds_f, st);
-      else if (d->dtype == WAE_F32 && nu == 7) launch_arc_fast_list<float, 7>(a, lds_f, st);
-      else if (d->dtype == WAE_F32 && nu == 8) launch_arc_fast_list<float, 8>(a, lds_f, st);
-      else done = false;
-    }
-    else if (d->dtype == WAE_BF16 && nu == 3) launch_arc_fast<__bf16, 3>(a, lds_f, st);
-    else if (d->dtype == WAE_BF16 && nu == 4) launch_arc_fast<__bf16, 4>(a, lds_f, st);
-    else if (d->dtype == WAE_F16 && nu == 3) launch_arc_fast<f16, 3>(a, lds_f, st);
-    else if (d->dtype == WAE_F16 && nu == 4) launch_arc_fast<f16, 4>(a, lds_f, st);
-    else if (d->dtype == WAE_F32 && nu == 6) launch_arc_fast<float, 6>(a, lds_f, st);
-    else if (d->dtype == WAE_F32 && nu == 7) launch_arc_fast<float, 7>(a, lds_f, st);
-    else if (d->dtype == WAE_F32 && nu == 8) launch_arc_fast<float, 8>(a, lds_f, st);
-    else done = false;
-    if (done) return wae_check_launch(who);
+    bool found;
+    const int rc = list ? launch_arc_sized<true>(nu, a, lds_f, st, who, found) : launch_arc_sized<false>(nu, a, lds_f, st, who, found);
+    if (found) return rc;
   }
-  if (list) {
-    if (d->dtype == WAE_BF16) {
-      (void)hipFuncSetAttribute((const void*)ar_coop_list_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((ar_coop_list_kernel<__bf16>), dim3(8 * a.C), dim3(ARC_THREADS), lds, st, a);
-    } else if (d->dtype == WAE_F16) {
-      (void)hipFuncSetAttribute((const void*)ar_coop_list_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((ar_coop_list_kernel<f16>), dim3(8 * a.C), dim3(ARC_THREADS), lds, st, a);
-    } else {
-      (void)hipFuncSetAttribute((const void*)ar_coop_list_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL((ar_coop_list_kernel<float>), dim3(8 * a.C), dim3(ARC_THREADS), lds, st, a);
-    }
-  } else {
-    launch_arc_generic<false>(a, d->dtype, lds, st);
-  }
-  return wae_check_launch(who);
-}
-
-static int ar_generate_coop_impl(const wae_ar_desc* d, int32_t C, const int32_t* dilations, const int64_t* ring_off, float* ring,
-                                 int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
-                                 const float* bias2, const float* zb, const float* first_tab, const float* first_bias,
-                                 const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
-                                 const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
-                                 uint64_t* msg, float* acc, int32_t* error, const void* w_fused, void* stream) {
-  WAE_REQUIRE(d && dilations && ring_off && ring && w_layers && bias2 && zb && first_tab && first_bias && w_head && head_bias &&
-                  out_idx && msg && acc && error, "ar_generate_coop: null pointer argument");
-  WAE_REQUIRE(wae_dtype_ok(d->dtype), "ar_generate_coop: bad dtype");
-  WAE_REQUIRE(d->B > 0 && d->B <= 8, "ar_generate_coop: 1..8 utterances per launch (one XCD each); use wae_ar_generate for more");
-  WAE_REQUIRE(C >= 1 && C <= ARC_CMAX, "ar_generate_coop: 1..%d cooperating workgroups per utterance", ARC_CMAX);
-  WAE_REQUIRE(d->T > 0 && d->L > 0 && d->R > 0 && d->R <= ARC_THREADS && d->G > 0 && d->G % 2 == 0 && d->S > 0 &&
-                  d->S <= ARC_THREADS && d->O > 0 && d->O <= ARC_THREADS,
-              "ar_generate_coop: bad sizes (R, S, O <= %d)", ARC_THREADS);
-  WAE_REQUIRE(d->Cc <= 0 || c_up, "ar_generate_coop: Cc > 0 but c_up is null");
-  WAE_REQUIRE(d->mode >= 0 && d->mode <= 2, "ar_generate_coop: mode must be 0 (logits), 1 (argmax) or 2 (sample)");
-  WAE_REQUIRE(d->mode != 2 || uniforms, "ar_generate_coop: sample mode needs uniforms");
-  WAE_REQUIRE(d->mode != 0 || (inputs && (d->n_forced <= 0 || d->n_forced >= d->T)), "ar_generate_coop: mode 0 needs inputs for every step");
-  WAE_REQUIRE(inputs || (d->init_idx >= 0 && d->init_idx < d->O), "ar_generate_coop: init_idx %d is not a class (O = %d)", d->init_idx,
-              d->O);
-  WAE_REQUIRE(!d->scalar_input, "ar_generate_coop: scalar-input decoders go through wae_ar_generate_coop_scalar");
-  WAE_AR_REQUIRE_T0("ar_generate_coop", d, inputs);
-  WAE_REQUIRE(d->t0 == 0 || !w_fused, "ar_generate_coop_fused: the one-hand-over form (w_fused) cannot continue a decode (t0 > 0); pass w_fused = NULL");
-  const int H = d->G / 2;
-  const int hc = (H + C - 1) / C, sc = (d->S + C - 1) / C;
-  WAE_REQUIRE(2 * hc <= ARC_THREADS && sc <= ARC_THREADS, "ar_generate_coop: too few workgroups for G=%d, S=%d", d->G, d->S);
-  ArcArgs a = arc_common_args(d, C, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
-                              first_bias, w_head, head_bias, c_up, c_dtype, msg, acc, error);
-  a.inputs = inputs; a.init_idx = d->init_idx; a.uniforms = uniforms; a.out_idx = out_idx;
-  a.n_forced = inputs ? (d->n_forced > 0 && d->n_forced < d->T ? d->n_forced : d->T) : 0;
-  a.out_logits = out_logits;
-  WAE_REQUIRE(ring_total < (int64_t)1 << 31, "ar_generate_coop: ring_total %lld does not fit 32-bit offsets", (long long)ring_total);
-  // the message banks must start with sequence numbers no exchange will use (0): the caller zeroes msg and error
-  return arc_dispatch(d, C, a, ring_total, w_fused, false, as_stream(stream), "ar_generate_coop");
-}
-
-extern "C" int wae_ar_generate_coop(const wae_ar_desc* d, int32_t C, const int32_t* dilations, const int64_t* ring_off, float* ring,
-                                    int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
-                                    const float* bias2, const float* zb, const float* first_tab, const float* first_bias,
-                                    const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
-                                    const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
-                                    uint64_t* msg, float* acc, int32_t* error, void* stream) {
-  return ar_generate_coop_impl(d, C, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
-                               first_bias, w_head, head_bias, c_up, c_dtype, inputs, uniforms, out_idx, out_logits, msg, acc, error, nullptr,
-                               stream);
+  const size_t lds = arc_generic_lds(d, C);
+  return list ? launch_arc_generic<ARC_LIST>(a, lds, st, who) : launch_arc_generic<ARC_CLASS_IDS>(a, lds, st, who);
 }
 
 extern "C" int wae_ar_generate_coop_fused(const wae_ar_desc* d, int32_t C, const int32_t* dilations, const int64_t* ring_off, float* ring,
@@ -2056,9 +1963,29 @@ extern "C" int wae_ar_generate_coop_fused(const wae_ar_desc* d, int32_t C, const
                                           const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
                                           const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
                                           uint64_t* msg, float* acc, int32_t* error, const void* w_fused, void* stream) {
-  return ar_generate_coop_impl(d, C, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
-                               first_bias, w_head, head_bias, c_up, c_dtype, inputs, uniforms, out_idx, out_logits, msg, acc, error, w_fused,
-                               stream);
+  const char* who = "ar_generate_coop";   // (both entries of the class-id cooperative decode speak under this name)
+  const ArNet net = AR_NET_OF_ARGS;
+  const ArcExchange x = {msg, acc, error};
+  AR_TRY(ar_check_net(who, d, net, out_idx != nullptr, true, ARC_THREADS));
+  AR_TRY(ar_check_class_ids(who, d, inputs, uniforms, out_logits, 2, false, "wae_ar_generate_coop_scalar"));
+  AR_TRY(ar_check_t0(who, d, inputs, false));
+  WAE_REQUIRE(d->t0 == 0 || !w_fused, "ar_generate_coop_fused: the one-hand-over form (w_fused) cannot continue a decode (t0 > 0); pass w_fused = NULL");
+  AR_TRY(ar_check_split(who, d, C, ARC_CMAX, ARC_THREADS, ring_total, x.ok(), "wae_ar_generate"));
+  ArcArgs a = arc_common_args(d, C, net, x);
+  a.inputs = inputs; a.init_idx = d->init_idx; a.uniforms = uniforms; a.out_idx = out_idx; a.out_logits = out_logits;
+  a.n_forced = ar_n_forced(d, inputs);
+  return arc_dispatch(d, C, a, w_fused, false, as_stream(stream), who);
+}
+
+extern "C" int wae_ar_generate_coop(const wae_ar_desc* d, int32_t C, const int32_t* dilations, const int64_t* ring_off, float* ring,
+                                    int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
+                                    const float* bias2, const float* zb, const float* first_tab, const float* first_bias,
+                                    const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
+                                    const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
+                                    uint64_t* msg, float* acc, int32_t* error, void* stream) {
+  return wae_ar_generate_coop_fused(d, C, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb,
+                                    first_tab, first_bias, w_head, head_bias, c_up, c_dtype, inputs, uniforms, out_idx, out_logits, msg, acc,
+                                    error, nullptr, stream);
 }
 
 // A work list on cooperative teams: n_teams teams of C workgroups (team = blockIdx.x & 7, one XCD each where the dispatch is round-robin)
@@ -2070,45 +1997,23 @@ extern "C" int wae_ar_generate_coop_list(const wae_ar_desc* d, int32_t C, int32_
                                          const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
                                          const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
                                          uint64_t* msg, float* acc, int32_t* error, void* stream) {
-  WAE_REQUIRE(d && dilations && ring_off && ring && w_layers && bias2 && zb && first_tab && first_bias && w_head && head_bias && out_idx,
-              "ar_generate_coop_list: null pointer argument");
-  if (d->scalar_input) {
-    wae_set_error("ar_generate_coop_list: list decoding covers class-id decoders; scalar-input decoders go through wae_ar_generate_coop_scalar");
-    return WAE_EUNSUPPORTED;
-  }
-  if (d->mode == 3 || d->mode == 4) {
-    wae_set_error("ar_generate_coop_list: modes 3 / 4 (dense feedback) are not list-decoded; use wae_ar_generate");
-    return WAE_EUNSUPPORTED;
-  }
-  WAE_REQUIRE(items && next, "ar_generate_coop_list: the item array and the queue counter are required");
-  WAE_REQUIRE(msg && acc && error, "ar_generate_coop_list: the exchange buffers msg, acc and error are required");
-  WAE_REQUIRE(d->t0 == 0, "ar_generate_coop_list: t0 %d: a list decode cannot be continued", d->t0);
-  WAE_REQUIRE(n_items >= 1, "ar_generate_coop_list: n_items %d < 1", n_items);
-  WAE_REQUIRE(n_teams >= 1 && n_teams <= 8, "ar_generate_coop_list: n_teams %d outside 1..8 (one XCD each)", n_teams);
-  WAE_REQUIRE(C >= 1 && C <= ARC_CMAX, "ar_generate_coop_list: C %d outside 1..%d cooperating workgroups per team", C, ARC_CMAX);
-  WAE_REQUIRE(wae_dtype_ok(d->dtype), "ar_generate_coop_list: bad dtype");
-  WAE_REQUIRE(d->R <= ARC_THREADS && d->S <= ARC_THREADS && d->O <= ARC_THREADS, "ar_generate_coop_list: R, S and O <= %d (got %d, %d, %d)",
-              ARC_THREADS, d->R, d->S, d->O);
-  WAE_REQUIRE(d->L > 0 && d->R > 0 && d->G > 0 && d->G % 2 == 0 && d->S > 0 && d->O > 0, "ar_generate_coop_list: bad sizes");
-  WAE_REQUIRE(d->Cc <= 0 || c_up, "ar_generate_coop_list: Cc > 0 but c_up is null");
-  WAE_REQUIRE(d->mode >= 0 && d->mode <= 2, "ar_generate_coop_list: mode must be 0 (logits), 1 (argmax) or 2 (sample)");
-  WAE_REQUIRE(d->mode != 0 || inputs, "ar_generate_coop_list: mode 0 needs inputs for every step");
-  WAE_REQUIRE(d->mode != 2 || uniforms, "ar_generate_coop_list: sample mode needs uniforms");
+  const char* who = "ar_generate_coop_list";
+  const ArNet net = AR_NET_OF_ARGS;
+  const ArcExchange x = {msg, acc, error};
+  AR_TRY(ar_check_net(who, d, net, out_idx != nullptr, false, ARC_THREADS));
+  AR_TRY(ar_check_class_ids(who, d, inputs, uniforms, out_logits, 2, true, "wae_ar_generate_coop_scalar"));
+  AR_TRY(ar_check_queue(who, items, next, n_items, "n_teams", n_teams, 8));
+  AR_TRY(ar_check_t0(who, d, inputs, true));
   // the exchange sequence numbers run on across a team's items: at most L per step (the x' sums), one per step for the skip sum and each
   // of the head's gathers, two messages per item taken or refused -- all below (total + n_items + 1) * (L + 4), which must fit 31 bits
-  WAE_REQUIRE(total >= 0 && (total + n_items + 1) <= (((int64_t)1 << 31) - 1) / (d->L + 4),
-              "ar_generate_coop_list: %lld steps in %d items on %d layers: the exchange sequence numbers would not fit 31 bits",
-              (long long)total, n_items, d->L);
-  const int H = d->G / 2;
-  const int hc = (H + C - 1) / C, sc = (d->S + C - 1) / C;
-  WAE_REQUIRE(2 * hc <= ARC_THREADS && sc <= ARC_THREADS, "ar_generate_coop_list: too few workgroups for G=%d, S=%d", d->G, d->S);
-  WAE_REQUIRE(ring_total < (int64_t)1 << 31, "ar_generate_coop_list: ring_total %lld does not fit 32-bit offsets", (long long)ring_total);
-  ArcArgs a = arc_common_args(d, C, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
-                              first_bias, w_head, head_bias, c_up, c_dtype, msg, acc, error);
+  AR_REQUIRE(total >= 0 && (total + n_items + 1) <= (((int64_t)1 << 31) - 1) / (d->L + 4),
+             "%lld steps in %d items on %d layers: the exchange sequence numbers would not fit 31 bits", (long long)total, n_items, d->L);
+  AR_TRY(ar_check_split(who, d, C, ARC_CMAX, ARC_THREADS, ring_total, x.ok(), nullptr));
+  ArcArgs a = arc_common_args(d, C, net, x);
   a.B = n_teams; a.T = 0; a.t0 = 0; a.n_forced = 0; a.init_idx = 0;      // per item
   a.inputs = inputs; a.uniforms = uniforms; a.out_idx = out_idx; a.out_logits = out_logits;
   a.items = items; a.next = next; a.n_items = n_items;
-  return arc_dispatch(d, C, a, ring_total, nullptr, true, as_stream(stream), "ar_generate_coop_list");
+  return arc_dispatch(d, C, a, nullptr, true, as_stream(stream), who);
 }
 
 // Scalar-input decoders on the any-shape cooperative kernel (ar_coop_kernel<E, true>): the network, the split and the exchanges of
@@ -2120,38 +2025,17 @@ extern "C" int wae_ar_generate_coop_scalar(const wae_ar_desc* d, int32_t C, int3
                                            int32_t c_dtype, const float* inputs_f, const float* u_mix, const float* draws,
                                            float log_scale_min, int32_t clamp_log_scale, float* out_samples, float* out_params,
                                            uint64_t* msg, float* acc, int32_t* error, void* stream) {
-  WAE_REQUIRE(d && dilations && ring_off && ring && w_layers && bias2 && zb && first_tab && first_bias && w_head && head_bias && msg &&
-                  acc && error, "ar_generate_coop_scalar: null pointer argument");
-  WAE_REQUIRE(wae_dtype_ok(d->dtype), "ar_generate_coop_scalar: bad dtype");
-  WAE_REQUIRE(d->scalar_input, "ar_generate_coop_scalar: needs a scalar-input decoder (class ids go through wae_ar_generate_coop)");
-  WAE_REQUIRE(dist == 0 || dist == 1, "ar_generate_coop_scalar: dist must be 0 (mixture of logistics) or 1 (mixture of Gaussians)");
-  WAE_REQUIRE(dist != 0 || (d->O > 0 && d->O % 3 == 0), "ar_generate_coop_scalar: the mixture of logistics has 3M output channels (got %d)",
-              d->O);
-  WAE_REQUIRE(dist != 1 || d->O == 2 || (d->O > 0 && d->O % 3 == 0),
-              "ar_generate_coop_scalar: the mixture of Gaussians has 2 or 3M output channels (got %d)", d->O);
-  WAE_REQUIRE(d->B > 0 && d->B <= 8, "ar_generate_coop_scalar: 1..8 utterances per launch (one XCD each); use wae_ar_generate_scalar for more");
-  WAE_REQUIRE(C >= 1 && C <= ARC_CMAX, "ar_generate_coop_scalar: 1..%d cooperating workgroups per utterance", ARC_CMAX);
-  WAE_REQUIRE(d->T > 0 && d->L > 0 && d->R > 0 && d->R <= ARC_THREADS && d->G > 0 && d->G % 2 == 0 && d->S > 0 && d->S <= ARC_THREADS &&
-                  d->O <= ARC_THREADS, "ar_generate_coop_scalar: bad sizes (R, S, O <= %d)", ARC_THREADS);
-  WAE_REQUIRE(d->Cc <= 0 || c_up, "ar_generate_coop_scalar: Cc > 0 but c_up is null");
-  WAE_AR_REQUIRE_T0("ar_generate_coop_scalar", d, inputs_f);
-  WAE_REQUIRE(d->mode == 0 || d->mode == 2, "ar_generate_coop_scalar: mode must be 0 (teacher-forced parameters) or 2 (sample)");
+  const char* who = "ar_generate_coop_scalar";
+  const ArNet net = AR_NET_OF_ARGS;
+  const ArcExchange x = {msg, acc, error};
+  AR_TRY(ar_check_net(who, d, net, true, true, ARC_THREADS));
+  AR_TRY(ar_check_mixture(who, d, dist, {inputs_f, u_mix, draws, out_samples, out_params}, true));
+  AR_TRY(ar_check_t0(who, d, inputs_f, false));
+  AR_TRY(ar_check_split(who, d, C, ARC_CMAX, ARC_THREADS, ring_total, x.ok(), "wae_ar_generate_scalar"));
   const bool sampled = dist == 0 ? (u_mix && draws) : draws != nullptr;
-  WAE_REQUIRE(dist != 0 || !u_mix == !draws, "ar_generate_coop_scalar: u_mix and u_log come together");
-  WAE_REQUIRE(d->mode != 2 || sampled, "ar_generate_coop_scalar: sample mode needs its draws (%s)", dist == 0 ? "u_mix and u_log" : "z");
-  WAE_REQUIRE(dist != 1 || !sampled || d->O <= 3 || u_mix, "ar_generate_coop_scalar: %d mixtures need the uniforms u_mix", d->O / 3);
-  WAE_REQUIRE(d->mode != 0 || (inputs_f && (d->n_forced <= 0 || d->n_forced >= d->T)),
-              "ar_generate_coop_scalar: mode 0 needs teacher-forced inputs for every step");
-  WAE_REQUIRE(!out_samples || sampled, "ar_generate_coop_scalar: samples need the draws");
-  WAE_REQUIRE(out_samples || out_params, "ar_generate_coop_scalar: no output requested");
-  const int H = d->G / 2;
-  const int hc = (H + C - 1) / C, sc = (d->S + C - 1) / C;
-  WAE_REQUIRE(2 * hc <= ARC_THREADS && sc <= ARC_THREADS, "ar_generate_coop_scalar: too few workgroups for G=%d, S=%d", d->G, d->S);
-  WAE_REQUIRE(ring_total < (int64_t)1 << 31, "ar_generate_coop_scalar: ring_total %lld does not fit 32-bit offsets", (long long)ring_total);
-  ArcArgs a = arc_common_args(d, C, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
-                              first_bias, w_head, head_bias, c_up, c_dtype, msg, acc, error);
+  ArcArgs a = arc_common_args(d, C, net, x);
   a.inputs_f = inputs_f;
-  a.n_forced = inputs_f ? (d->n_forced > 0 && d->n_forced < d->T ? d->n_forced : d->T) : 0;
+  a.n_forced = ar_n_forced(d, inputs_f);
   a.dist = dist;
   a.u_mix = sampled ? u_mix : nullptr;
   a.u_log = dist == 0 && sampled ? draws : nullptr;
@@ -2160,7 +2044,5 @@ extern "C" int wae_ar_generate_coop_scalar(const wae_ar_desc* d, int32_t C, int3
   a.clamp_log_scale = dist == 0 ? clamp_log_scale : 0;
   a.out_samples = out_samples;
   a.out_params = out_params;
-  // (the caller zeroes msg, acc and error, as for wae_ar_generate_coop)
-  launch_arc_generic<true>(a, d->dtype, arc_generic_lds(d, C), as_stream(stream));
-  return wae_check_launch("ar_generate_coop_scalar");
+  return launch_arc_generic<ARC_SCALAR>(a, arc_generic_lds(d, C), as_stream(stream), who);
 }

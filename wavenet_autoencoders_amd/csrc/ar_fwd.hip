@@ -393,29 +393,33 @@ __global__ void __launch_bounds__(AR_THREADS) ar_list_kernel(ArListArgs q) {
   }
 }
 
+#include "ar_host.hpp"
+
 struct ArList {   // wae_ar_generate_list's own arguments
   const wae_ar_item* items;
   int32_t* next;
   int n_items, n_slots;
 };
 
-static int ar_launch(const wae_ar_desc* d, const int32_t* dilations, const int64_t* ring_off, float* ring, int64_t ring_total,
-                     const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes, const float* bias2, const float* zb,
-                     const float* first_tab, const float* first_bias, const void* w_head, const float* head_bias, const void* c_up,
-                     int32_t c_dtype, const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
-                     const float* inputs_f, const float* u_mix, const float* u_log, float* out_f, float log_scale_min,
-                     int clamp_log_scale, int dist, const float* z, void* stream, const ArList* list = nullptr) {
-  ArArgs a;
-  a.dtype = d->dtype; a.B = d->B; a.T = d->T; a.L = d->L; a.R = d->R; a.G = d->G; a.S = d->S; a.O = d->O; a.Cc = d->Cc;
-  a.Ccp = d->Ccp; a.Hp = d->Hp; a.ktaps = d->ktaps; a.mode = d->mode; a.Rp = d->Rp; a.scale = d->scale; a.dil = dilations;
-  a.ring_off = ring_off; a.ring = ring; a.ring_total = ring_total; a.w_layers = (const char*)w_layers;
-  a.layer_stride = layer_stride_bytes; a.w2_off = w2_off_bytes; a.bias2 = bias2; a.zb = zb; a.first_tab = first_tab;
-  a.first_bias = first_bias; a.w_head = (const char*)w_head; a.head_bias = head_bias; a.c_up = (const char*)c_up;
-  a.c_dtype = c_dtype; a.inputs = inputs; a.init_idx = d->init_idx;
-  a.n_forced = (inputs || inputs_f) ? (d->n_forced > 0 && d->n_forced < d->T ? d->n_forced : d->T) : 0; a.uniforms = uniforms; a.out_idx = out_idx;
-  a.out_logits = out_logits; a.scalar = d->scalar_input ? 1 : 0; a.inputs_f = inputs_f; a.u_mix = u_mix; a.u_log = u_log;
-  a.out_f = out_f; a.log_scale_min = log_scale_min; a.clamp_log_scale = clamp_log_scale; a.dist = dist; a.z = z;
-  a.t0 = d->t0;
+// The operands of one form of the decode; whatever a form does not have stays null / zero.  Class ids: inputs, uniforms, out_idx, and
+// out_logits.  A scalar draw: inputs_f, u_mix, u_log (dist 0) or z (dist 1), out_f, and the mixture parameters through out_logits.
+struct ArOps {
+  const int32_t* inputs;
+  const float* uniforms;
+  int32_t* out_idx;
+  float *out_logits, *out_f;
+  const float *inputs_f, *u_mix, *u_log, *z;
+  float log_scale_min;
+  int clamp_log_scale, dist;
+};
+
+static int ar_launch(const wae_ar_desc* d, const ArNet& net, const ArOps& o, void* stream, const ArList* list = nullptr) {
+  ArArgs a = {};
+  ar_fill_net(a, d, net);
+  a.inputs = o.inputs; a.init_idx = d->init_idx; a.n_forced = ar_n_forced(d, o.inputs ? (const void*)o.inputs : (const void*)o.inputs_f);
+  a.uniforms = o.uniforms; a.out_idx = o.out_idx; a.out_logits = o.out_logits; a.scalar = d->scalar_input ? 1 : 0;
+  a.inputs_f = o.inputs_f; a.u_mix = o.u_mix; a.u_log = o.u_log; a.out_f = o.out_f; a.log_scale_min = o.log_scale_min;
+  a.clamp_log_scale = o.clamp_log_scale; a.dist = o.dist; a.z = o.z;
   const int epl = wae_is16(d->dtype) ? 8 : 4;
   const int H = d->G / 2;
   auto ru = [](int x, int m) { return (x + m - 1) / m * m; };
@@ -428,30 +432,13 @@ static int ar_launch(const wae_ar_desc* d, const int32_t* dilations, const int64
   if (list) {
     // the queue word sits behind ar_decode's carve; per-utterance B, T, n_forced and init_idx come from the items
     const ArListArgs q = {a, list->items, list->next, list->n_items, (int)(lds / sizeof(float))};
-    const size_t ldq = lds + 16;
-    if (d->dtype == WAE_BF16) {
-      (void)hipFuncSetAttribute((const void*)ar_list_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldq);
-      hipLaunchKernelGGL(ar_list_kernel<__bf16>, dim3(list->n_slots), dim3(AR_THREADS), ldq, st, q);
-    } else if (d->dtype == WAE_F16) {
-      (void)hipFuncSetAttribute((const void*)ar_list_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldq);
-      hipLaunchKernelGGL(ar_list_kernel<f16>, dim3(list->n_slots), dim3(AR_THREADS), ldq, st, q);
-    } else {
-      (void)hipFuncSetAttribute((const void*)ar_list_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldq);
-      hipLaunchKernelGGL(ar_list_kernel<float>, dim3(list->n_slots), dim3(AR_THREADS), ldq, st, q);
-    }
-    return wae_check_launch("ar_generate_list");
+    return ar_by_dtype(d->dtype, [&](auto e) {
+      AR_LAUNCH(ar_list_kernel<typename decltype(e)::type>, dim3(list->n_slots), dim3(AR_THREADS), lds + 16, st, q, "ar_generate_list");
+    });
   }
-  if (d->dtype == WAE_BF16) {
-    (void)hipFuncSetAttribute((const void*)ar_kernel<__bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ar_kernel<__bf16>, dim3(d->B), dim3(AR_THREADS), lds, st, a);
-  } else if (d->dtype == WAE_F16) {
-    (void)hipFuncSetAttribute((const void*)ar_kernel<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ar_kernel<f16>, dim3(d->B), dim3(AR_THREADS), lds, st, a);
-  } else {
-    (void)hipFuncSetAttribute((const void*)ar_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(ar_kernel<float>, dim3(d->B), dim3(AR_THREADS), lds, st, a);
-  }
-  return wae_check_launch("ar_generate");
+  return ar_by_dtype(d->dtype, [&](auto e) {
+    AR_LAUNCH(ar_kernel<typename decltype(e)::type>, dim3(d->B), dim3(AR_THREADS), lds, st, a, "ar_generate");
+  });
 }
 
 extern "C" int wae_ar_generate(const wae_ar_desc* d, const int32_t* dilations, const int64_t* ring_off, float* ring,
@@ -460,25 +447,15 @@ extern "C" int wae_ar_generate(const wae_ar_desc* d, const int32_t* dilations, c
                                const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
                                const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
                                void* stream) {
-  WAE_REQUIRE(d && dilations && ring_off && ring && w_layers && bias2 && zb && first_tab && first_bias && w_head && head_bias &&
-                  out_idx, "ar_generate: null pointer argument");
-  WAE_REQUIRE(wae_dtype_ok(d->dtype), "ar_generate: bad dtype");
-  WAE_REQUIRE(d->B > 0 && d->T > 0 && d->L > 0 && d->R > 0 && d->G > 0 && d->G % 2 == 0 && d->S > 0 && d->O > 0,
-              "ar_generate: bad sizes");
-  WAE_REQUIRE(d->Cc <= 0 || c_up, "ar_generate: Cc > 0 but c_up is null");
-  WAE_REQUIRE(d->mode >= 0 && d->mode <= 4,
-              "ar_generate: mode must be 0 (logits), 1 (argmax), 2 (sample), 3 (feed probabilities back) or 4 (feed logits back)");
-  WAE_REQUIRE(d->mode != 2 || uniforms, "ar_generate: sample mode needs uniforms");
-  WAE_REQUIRE(d->mode != 0 || (inputs && (d->n_forced <= 0 || d->n_forced >= d->T)), "ar_generate: mode 0 needs inputs for every step");
-  WAE_REQUIRE(d->mode < 3 || out_logits, "ar_generate: modes 3 / 4 return their vectors through out_logits");
-  WAE_REQUIRE(!d->scalar_input, "ar_generate: scalar-input decoders go through wae_ar_generate_scalar");
-  WAE_AR_REQUIRE_T0("ar_generate", d, inputs);
-  WAE_REQUIRE(d->t0 == 0 || d->mode < 3, "ar_generate: a continuation (t0 > 0) cannot resume modes 3 / 4: the vector they feed back stays on chip");
-  // the start class indexes the first-conv table: wavenet.py:288 sets class 127, an IndexError there when O <= 127
-  WAE_REQUIRE(inputs || (d->init_idx >= 0 && d->init_idx < d->O), "ar_generate: init_idx %d is not a class (O = %d)", d->init_idx, d->O);
-  return ar_launch(d, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
-                   first_bias, w_head, head_bias, c_up, c_dtype, inputs, uniforms, out_idx, out_logits, nullptr, nullptr, nullptr,
-                   nullptr, -7.0f, 0, 0, nullptr, stream);
+  const char* who = "ar_generate";
+  const ArNet net = AR_NET_OF_ARGS;
+  AR_TRY(ar_check_net(who, d, net, out_idx != nullptr, true, 0));
+  AR_TRY(ar_check_class_ids(who, d, inputs, uniforms, out_logits, 4, false, "wae_ar_generate_scalar"));
+  AR_TRY(ar_check_t0(who, d, inputs, false));
+  AR_REQUIRE(d->t0 == 0 || d->mode < 3, "a continuation (t0 > 0) cannot resume modes 3 / 4: the vector they feed back stays on chip");
+  ArOps o = {};
+  o.inputs = inputs; o.uniforms = uniforms; o.out_idx = out_idx; o.out_logits = out_logits; o.log_scale_min = -7.0f;
+  return ar_launch(d, net, o, stream);
 }
 
 extern "C" int wae_ar_generate_list(const wae_ar_desc* d, int32_t n_items, int32_t n_slots, const wae_ar_item* items, int32_t* next,
@@ -487,30 +464,28 @@ extern "C" int wae_ar_generate_list(const wae_ar_desc* d, int32_t n_items, int32
                                     const float* zb, const float* first_tab, const float* first_bias, const void* w_head,
                                     const float* head_bias, const void* c_up, int32_t c_dtype, const int32_t* inputs,
                                     const float* uniforms, int32_t* out_idx, float* out_logits, void* stream) {
-  WAE_REQUIRE(d && dilations && ring_off && ring && w_layers && bias2 && zb && first_tab && first_bias && w_head && head_bias &&
-                  out_idx, "ar_generate_list: null pointer argument");
-  WAE_REQUIRE(items && next, "ar_generate_list: the item array and the queue counter are required");
-  WAE_REQUIRE(n_items >= 1, "ar_generate_list: n_items %d < 1", n_items);
-  WAE_REQUIRE(n_slots >= 1, "ar_generate_list: n_slots %d < 1", n_slots);
-  WAE_REQUIRE(wae_dtype_ok(d->dtype), "ar_generate_list: bad dtype");
-  WAE_REQUIRE(d->L > 0 && d->R > 0 && d->G > 0 && d->G % 2 == 0 && d->S > 0 && d->O > 0, "ar_generate_list: bad sizes");
-  WAE_REQUIRE(d->Cc <= 0 || c_up, "ar_generate_list: Cc > 0 but c_up is null");
-  if (d->scalar_input) {
-    wae_set_error("ar_generate_list: list decoding covers class-id decoders; scalar-input decoders go through wae_ar_generate_scalar");
-    return WAE_EUNSUPPORTED;
-  }
-  if (d->mode == 3 || d->mode == 4) {
-    wae_set_error("ar_generate_list: modes 3 / 4 (dense feedback) are not list-decoded; use wae_ar_generate");
-    return WAE_EUNSUPPORTED;
-  }
-  WAE_REQUIRE(d->mode >= 0 && d->mode <= 2, "ar_generate_list: mode must be 0 (logits), 1 (argmax) or 2 (sample)");
-  WAE_REQUIRE(d->t0 == 0, "ar_generate_list: t0 %d: a list decode cannot be continued", d->t0);
-  WAE_REQUIRE(d->mode != 0 || inputs, "ar_generate_list: mode 0 needs inputs for every step");
-  WAE_REQUIRE(d->mode != 2 || uniforms, "ar_generate_list: sample mode needs uniforms");
+  const char* who = "ar_generate_list";
+  const ArNet net = AR_NET_OF_ARGS;
+  AR_TRY(ar_check_net(who, d, net, out_idx != nullptr, false, 0));
+  AR_TRY(ar_check_queue(who, items, next, n_items, "n_slots", n_slots, 0));
+  AR_TRY(ar_check_class_ids(who, d, inputs, uniforms, out_logits, 2, true, "wae_ar_generate_scalar"));
+  AR_TRY(ar_check_t0(who, d, inputs, true));
+  ArOps o = {};
+  o.inputs = inputs; o.uniforms = uniforms; o.out_idx = out_idx; o.out_logits = out_logits; o.log_scale_min = -7.0f;
   const ArList list = {items, next, n_items, n_slots};
-  return ar_launch(d, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
-                   first_bias, w_head, head_bias, c_up, c_dtype, inputs, uniforms, out_idx, out_logits, nullptr, nullptr, nullptr,
-                   nullptr, -7.0f, 0, 0, nullptr, stream, &list);
+  return ar_launch(d, net, o, stream, &list);
+}
+
+// the two scalar entries: dist 0 draws from (u_mix, u_log), dist 1 from (u_mix, z)
+static int ar_generate_scalar(const char* who, const wae_ar_desc* d, const ArNet& net, int dist, const ArDraw& w, float log_scale_min,
+                              int clamp_log_scale, void* stream) {
+  AR_TRY(ar_check_net(who, d, net, true, true, 0));
+  AR_TRY(ar_check_mixture(who, d, dist, w, false));
+  AR_TRY(ar_check_t0(who, d, w.inputs_f, false));
+  ArOps o = {};
+  o.out_logits = w.out_params; o.inputs_f = w.inputs_f; o.u_mix = w.u_mix; (dist == 0 ? o.u_log : o.z) = w.draws; o.out_f = w.out_samples;
+  o.log_scale_min = log_scale_min; o.clamp_log_scale = clamp_log_scale; o.dist = dist;
+  return ar_launch(d, net, o, stream);
 }
 
 extern "C" int wae_ar_generate_scalar(const wae_ar_desc* d, const int32_t* dilations, const int64_t* ring_off, float* ring,
@@ -519,21 +494,8 @@ extern "C" int wae_ar_generate_scalar(const wae_ar_desc* d, const int32_t* dilat
                                       const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
                                       const float* inputs_f, const float* u_mix, const float* u_log, float log_scale_min,
                                       int32_t clamp_log_scale, float* out_samples, float* out_params, void* stream) {
-  WAE_REQUIRE(d && dilations && ring_off && ring && w_layers && bias2 && zb && first_tab && first_bias && w_head && head_bias,
-              "ar_generate_scalar: null pointer argument");
-  WAE_REQUIRE(wae_dtype_ok(d->dtype), "ar_generate_scalar: bad dtype");
-  WAE_REQUIRE(d->scalar_input && d->O > 0 && d->O % 3 == 0, "ar_generate_scalar: needs a scalar-input decoder with 3M output channels");
-  WAE_REQUIRE(d->B > 0 && d->T > 0 && d->L > 0 && d->R > 0 && d->G > 0 && d->G % 2 == 0 && d->S > 0, "ar_generate_scalar: bad sizes");
-  WAE_REQUIRE(d->Cc <= 0 || c_up, "ar_generate_scalar: Cc > 0 but c_up is null");
-  WAE_AR_REQUIRE_T0("ar_generate_scalar", d, inputs_f);
-  WAE_REQUIRE((inputs_f && (d->n_forced <= 0 || d->n_forced >= d->T)) || (u_mix && u_log),
-              "ar_generate_scalar: needs teacher-forced inputs for every step or the uniforms of the draws");
-  WAE_REQUIRE(!u_mix == !u_log, "ar_generate_scalar: u_mix and u_log come together");
-  WAE_REQUIRE(!out_samples || u_mix, "ar_generate_scalar: samples need the uniforms");
-  WAE_REQUIRE(out_samples || out_params, "ar_generate_scalar: no output requested");
-  return ar_launch(d, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
-                   first_bias, w_head, head_bias, c_up, c_dtype, nullptr, nullptr, nullptr, out_params, inputs_f, u_mix, u_log,
-                   out_samples, log_scale_min, clamp_log_scale, 0, nullptr, stream);
+  return ar_generate_scalar("ar_generate_scalar", d, AR_NET_OF_ARGS, 0, {inputs_f, u_mix, u_log, out_samples, out_params}, log_scale_min,
+                            clamp_log_scale, stream);
 }
 
 extern "C" int wae_ar_generate_scalar_mog(const wae_ar_desc* d, const int32_t* dilations, const int64_t* ring_off, float* ring,
@@ -542,20 +504,6 @@ extern "C" int wae_ar_generate_scalar_mog(const wae_ar_desc* d, const int32_t* d
                                           const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
                                           const float* inputs_f, const float* u_mix, const float* z, float log_scale_min,
                                           float* out_samples, float* out_params, void* stream) {
-  WAE_REQUIRE(d && dilations && ring_off && ring && w_layers && bias2 && zb && first_tab && first_bias && w_head && head_bias,
-              "ar_generate_scalar_mog: null pointer argument");
-  WAE_REQUIRE(wae_dtype_ok(d->dtype), "ar_generate_scalar_mog: bad dtype");
-  WAE_REQUIRE(d->scalar_input && (d->O == 2 || (d->O > 0 && d->O % 3 == 0)),
-              "ar_generate_scalar_mog: needs a scalar-input decoder with 2 or 3M output channels");
-  WAE_REQUIRE(d->B > 0 && d->T > 0 && d->L > 0 && d->R > 0 && d->G > 0 && d->G % 2 == 0 && d->S > 0, "ar_generate_scalar_mog: bad sizes");
-  WAE_REQUIRE(d->Cc <= 0 || c_up, "ar_generate_scalar_mog: Cc > 0 but c_up is null");
-  WAE_AR_REQUIRE_T0("ar_generate_scalar_mog", d, inputs_f);
-  WAE_REQUIRE((inputs_f && (d->n_forced <= 0 || d->n_forced >= d->T)) || z,
-              "ar_generate_scalar_mog: needs teacher-forced inputs for every step or the normal draws z");
-  WAE_REQUIRE(!z || d->O <= 3 || u_mix, "ar_generate_scalar_mog: %d mixtures need the uniforms u_mix", d->O / 3);
-  WAE_REQUIRE(!out_samples || z, "ar_generate_scalar_mog: samples need the draws");
-  WAE_REQUIRE(out_samples || out_params, "ar_generate_scalar_mog: no output requested");
-  return ar_launch(d, dilations, ring_off, ring, ring_total, w_layers, layer_stride_bytes, w2_off_bytes, bias2, zb, first_tab,
-                   first_bias, w_head, head_bias, c_up, c_dtype, nullptr, nullptr, nullptr, out_params, inputs_f, u_mix, nullptr,
-                   out_samples, log_scale_min, 0, 1, z, stream);
+  return ar_generate_scalar("ar_generate_scalar_mog", d, AR_NET_OF_ARGS, 1, {inputs_f, u_mix, z, out_samples, out_params}, log_scale_min, 0,
+                            stream);
 }

@@ -49,16 +49,6 @@ static inline int wae_ensure_lds(const void* kernel, WaeLdsCache& c, size_t lds,
     }                               \
   } while (0)
 
-// wae_ar_desc.t0 > 0 (a launch that continues an earlier launch's decode from the caller's ring): what every decode entry refuses
-// before it launches.  The first step of a continuation is forced -- the previous launch's last output comes in as inputs[b][0] --
-// so a continuation without inputs (n_forced resolving to 0) has nothing to start from.
-#define WAE_AR_REQUIRE_T0(name, d, forced_inputs)                                                                                     \
-  do {                                                                                                                                \
-    WAE_REQUIRE((d)->t0 >= 0, name ": t0 %d is negative", (d)->t0);                                                                    \
-    WAE_REQUIRE((d)->T <= 0 || (d)->t0 <= INT32_MAX - (d)->T, name ": t0 + T (%d + %d) does not fit int32_t", (d)->t0, (d)->T);        \
-    WAE_REQUIRE((d)->t0 == 0 || (forced_inputs), name ": a continuation (t0 > 0) needs inputs: its first step is forced (n_forced >= 1)"); \
-  } while (0)
-
 // ---------------------------------------------------------------------------------------------------
 // Element traits: one 16-byte MFMA operand fragment per lane = 8 bf16 (one 32x32x16 MFMA) or 4 f32
 // (four exact-fp32 32x32x2 MFMAs).  A fragment block is 64 lanes x 16 B = 1 KiB in both cases, so the

@@ -759,10 +759,9 @@ class WaeEngine:
         """What a decode of T steps fixes before its first launch, whatever its chunks (incremental_forward's arguments) -> the state
         _ar_launch runs steps of: the packed weights, the start classes, the forced prefix, the upsampled conditioning, the speaker
         rows, the kernel path, the zeroed ring, the draws of all T steps and the exchange buffers."""
-        g, lib, dev = self.g, self.lib, self.device
+        g, dev = self.g, self.device
         if not getattr(self, "_ar_packed", False) or self.weights_dirty:
             self.pack_ar_weights()
-        st = self.stream()
         T = int(T)
         B = c.shape[0] if c is not None else (test_inputs.shape[0] if test_inputs is not None else 1)
         m = {"logits": 0, "argmax": 1, "sample": 2, "probs": 3, "raw": 4}[mode]
@@ -791,22 +790,9 @@ class WaeEngine:
         c_up = None
         if g.Ccp:
             c_up = torch.zeros(B, T, g.Ccp, dtype=self.tdtype, device=dev)
-            if c_is_upsampled or not g.upsample_scales:
-                assert c.shape[-1] == T, f"c {tuple(c.shape)} != T {T}"       # wavenet.py:278
-                L.check(lib.wae_to_btc(L.ptr(c.contiguous().float()), L.ptr(c_up), B, g.Cc, T, g.Ccp, self.dt, st), "to_btc")
-            else:
-                assert (c.shape[-1] - 2 * g.cin_pad) * int(np.prod(g.upsample_scales)) == T, "c does not upsample to T"
-                self.upsample_forward(c.float(), c_up)
-        zb = torch.empty(B, g.layers, 2 * g.Hp, dtype=torch.float32, device=dev)
-        wg_off = self.lay.off("wavenet.conv_layers.0.conv1x1g.weight_v") if g.Cg > 0 else -1
-        emb_off = self.lay.offsets.get("wavenet.embed_speakers.weight", 0)
-        use_gid = gid is not None and "wavenet.embed_speakers.weight" in self.lay.offsets
+            self._ar_cond_rows(c.contiguous().float(), c_up, c_is_upsampled)
         gid32 = gid.to(torch.int32).contiguous() if gid is not None else None
-        L.check(lib.wae_gproj_fwd(L.ptr(self.eff), wg_off if (gid is not None or gvec is not None) else -1,
-                                  self.lay.off("wavenet.conv_layers.0.conv.bias"), self.lay.layer_stride,
-                                  L.ptr(gid32) if use_gid else None, emb_off, L.ptr(gvec) if gvec is not None else None,
-                                  L.ptr(zb), B, g.layers, g.G, g.Hp, max(g.Cg, 0), int(g.n_speakers or 0), L.ptr(self.err), st),
-                "gproj")
+        zb = self._ar_speaker_rows(B, gid32, gvec)
         # one utterance per XCD, its gate rows split over up to 32 CUs (csrc/ar_coop.hip); bigger batches run one
         # utterance per CU (csrc/ar_fwd.hip): better aggregate throughput, 3-4x lower speed per utterance
         # scalar-input decoders take that path on request only (ar_path(scalar_coop=True)), in the modes their kernel has
@@ -851,12 +837,8 @@ class WaeEngine:
             path = (int(self.ar_generic), self.ar_resident[0], self.ar_resident[1])
         d = L.ArDesc(self.dt, B, T, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, int(init_idx),
                      int(g.scalar_input), math.sqrt(1.0 / g.layers), nf, *path)
-        msg = acc = err = None
-        if coop:
-            nv = lib.wae_ar_coop_msg_values(ctypes.byref(d), C)
-            msg = torch.empty(B * 2 * C * nv, dtype=torch.int64, device=dev)
-            acc = torch.empty(B * lib.wae_ar_coop_acc_floats(ctypes.byref(d)), dtype=torch.float32, device=dev)
-            err = torch.empty(64, dtype=torch.int32, device=dev)   # [0] = time-out flag; the rest: profile counters of a -DWAE_ARC_PROFILE build
+        # (not zeroed here: _ar_launch zeroes them before every launch)
+        msg, acc, err = self._ar_exchange(d, C, B, torch.empty) if coop else (None, None, None)
         return _ArDecode(d=d, n_forced=nf, forced=forced, c_up=c_up, zb=zb, gid32=gid32, coop=coop, C=C, ring=ring, normal=normal,
                          uni=uni, u_mix=um, draw=draw, sampled=sampled, want=want_logits or m == 0 or m >= 3,
                          log_scale_min=float(log_scale_min), clamp=int(bool(clamp_log_scale)),
@@ -886,10 +868,7 @@ class WaeEngine:
             s.msg.zero_()
             s.acc.zero_()
             s.err.zero_()
-        es = self.ar_w.element_size()
-        common = (L.ptr(self.ar_dil), L.ptr(self.ar_ring_off), L.ptr(s.ring), self.ar_ring_total, L.ptr(self.ar_w),
-                  self.ar_layer_elems * es, self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(s.zb), L.ptr(self.first_tab),
-                  L.ptr(self.first_bias), L.ptr(self.ar_wh), L.ptr(self.ar_hb), L.ptr(cu), self.dt, L.ptr(inp))
+        common = self._ar_net_args(s.ring, s.zb, cu) + (L.ptr(inp),)
         if g.scalar_input:
             um, dr = sl(s.u_mix), sl(s.draw)
             xs = torch.empty(d.B, n, dtype=torch.float32, device=dev) if s.sampled else None
@@ -916,11 +895,53 @@ class WaeEngine:
             item, keep = dict(idx=out_idx, logits=logits), (uc,)
             s.last = out_idx[:, -1]
         if s.coop:
-            self._ar_profile = s.err
-            if int(s.err[0].item()) != 0:       # synchronises, once per launch: generation is a blocking call for its callers anyway
-                raise L.WaeError("ar_generate_coop: an exchange between the cooperating workgroups timed out")
+            self._ar_check_exchange(s.err, "ar_generate_coop")
         self._ar_keep = (s, cu, inp) + keep     # the launch's operands (and the decode's: ring, zb, ...) live until the stream has run
         return item
+
+    # ---- what every decode sets up the same way (_ar_open / _ar_launch and decode_list)
+    def _ar_cond_rows(self, c, out, c_is_upsampled, who=""):
+        """c (B, Cc, Tc) fp32, contiguous -> out (B, T, Ccp), zeroed, in the model's dtype: the per-sample features as they are
+        (already upsampled, or a geometry without an upsampling network), else the latent frames through the upsampling network."""
+        g, (B, T) = self.g, out.shape[:2]
+        if c_is_upsampled or not g.upsample_scales:
+            assert c.shape[-1] == T, f"{who}c {tuple(c.shape)} != T {T}"       # wavenet.py:278
+            L.check(self.lib.wae_to_btc(L.ptr(c), L.ptr(out), B, g.Cc, T, g.Ccp, self.dt, self.stream()), "to_btc")
+        else:
+            assert (c.shape[-1] - 2 * g.cin_pad) * int(np.prod(g.upsample_scales)) == T, f"{who}c does not upsample to T"
+            self.upsample_forward(c, out)
+
+    def _ar_speaker_rows(self, n, gid32, gvec=None):
+        """zb (n, layers, 2Hp) fp32: every layer's gate bias plus the projection of the speaker vector (gid32's embedding row or gvec)."""
+        g, zb = self.g, torch.empty(n, self.g.layers, 2 * self.g.Hp, dtype=torch.float32, device=self.device)
+        wg_off = self.lay.off("wavenet.conv_layers.0.conv1x1g.weight_v") if g.Cg > 0 else -1
+        use_gid = gid32 is not None and "wavenet.embed_speakers.weight" in self.lay.offsets
+        L.check(self.lib.wae_gproj_fwd(L.ptr(self.eff), wg_off if (gid32 is not None or gvec is not None) else -1,
+                                       self.lay.off("wavenet.conv_layers.0.conv.bias"), self.lay.layer_stride,
+                                       L.ptr(gid32) if use_gid else None, self.lay.offsets.get("wavenet.embed_speakers.weight", 0),
+                                       L.ptr(gvec) if gvec is not None else None, L.ptr(zb), n, g.layers, g.G, g.Hp, max(g.Cg, 0),
+                                       int(g.n_speakers or 0), L.ptr(self.err), self.stream()), "gproj")
+        return zb
+
+    def _ar_exchange(self, d, C, groups, alloc):
+        """(msg, acc, err) of `groups` utterances or teams of C workgroups from `alloc` (torch.zeros / torch.empty: a launch needs them
+        zeroed).  err[0] = the time-out flag; the rest: profile counters of a -DWAE_ARC_PROFILE build."""
+        nv = self.lib.wae_ar_coop_msg_values(ctypes.byref(d), C)
+        return (alloc(groups * 2 * C * nv, dtype=torch.int64, device=self.device),
+                alloc(groups * self.lib.wae_ar_coop_acc_floats(ctypes.byref(d)), dtype=torch.float32, device=self.device),
+                alloc(64, dtype=torch.int32, device=self.device))
+
+    def _ar_net_args(self, ring, zb, c_up):
+        """The 15 network arguments every wae_ar_generate* entry takes behind its descriptor (_lib._AR[1:])."""
+        es = self.ar_w.element_size()
+        return (L.ptr(self.ar_dil), L.ptr(self.ar_ring_off), L.ptr(ring), self.ar_ring_total, L.ptr(self.ar_w), self.ar_layer_elems * es,
+                self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(zb), L.ptr(self.first_tab), L.ptr(self.first_bias), L.ptr(self.ar_wh),
+                L.ptr(self.ar_hb), L.ptr(c_up), self.dt)
+
+    def _ar_check_exchange(self, err, who):
+        self._ar_profile = err
+        if int(err[0].item()) != 0:     # synchronises, once per launch: generation is a blocking call for its callers anyway
+            raise L.WaeError(f"{who}: an exchange between the cooperating workgroups timed out")
 
     def decode_list(self, items, mode: str = "sample", slots: Optional[int] = None, want_logits: bool = False,
                     c_is_upsampled: bool = False, coop: bool = False, teams: Optional[int] = None):
@@ -1004,26 +1025,14 @@ class WaeEngine:
         c_up = None
         if g.Ccp:
             c_up = torch.zeros(total, g.Ccp, dtype=self.tdtype, device=dev)
-            up = int(np.prod(g.upsample_scales)) if g.upsample_scales else 1
             for i, it in enumerate(items):
                 c = torch.as_tensor(it["c"]).to(dev, torch.float32)
                 c = (c if c.dim() == 3 else c[None]).contiguous()
-                out = c_up[off[i]:off[i] + Ts[i]].view(1, Ts[i], g.Ccp)      # the item's slice: one utterance of batch 1
-                if c_is_upsampled or not g.upsample_scales:
-                    assert c.shape[-1] == Ts[i], f"item {i}: c {tuple(c.shape)} != T {Ts[i]}"       # wavenet.py:278
-                    L.check(lib.wae_to_btc(L.ptr(c), L.ptr(out), 1, g.Cc, Ts[i], g.Ccp, self.dt, st), "to_btc")
-                else:
-                    assert (c.shape[-1] - 2 * g.cin_pad) * up == Ts[i], f"item {i}: c does not upsample to T"
-                    self.upsample_forward(c, out)
-        zb = torch.empty(n, g.layers, 2 * g.Hp, dtype=torch.float32, device=dev)
+                # the item's slice: one utterance of batch 1
+                self._ar_cond_rows(c, c_up[off[i]:off[i] + Ts[i]].view(1, Ts[i], g.Ccp), c_is_upsampled, f"item {i}: ")
         has_gid = gids[0] is not None
         gid32 = torch.tensor([int(torch.as_tensor(x).reshape(-1)[0]) for x in gids], dtype=torch.int32, device=dev) if has_gid else None
-        wg_off = self.lay.off("wavenet.conv_layers.0.conv1x1g.weight_v") if g.Cg > 0 else -1
-        use_gid = has_gid and "wavenet.embed_speakers.weight" in self.lay.offsets
-        L.check(lib.wae_gproj_fwd(L.ptr(self.eff), wg_off if has_gid else -1, self.lay.off("wavenet.conv_layers.0.conv.bias"),
-                                  self.lay.layer_stride, L.ptr(gid32) if use_gid else None,
-                                  self.lay.offsets.get("wavenet.embed_speakers.weight", 0), None, L.ptr(zb), n, g.layers, g.G, g.Hp,
-                                  max(g.Cg, 0), int(g.n_speakers or 0), L.ptr(self.err), st), "gproj")
+        zb = self._ar_speaker_rows(n, gid32)
         uni = None
         if m == 2:
             uni = torch.empty(total, dtype=torch.float32, device=dev)
@@ -1044,32 +1053,23 @@ class WaeEngine:
         path = (int(self.ar_generic), self.ar_resident[0], self.ar_resident[1]) if coop else ()
         d = L.ArDesc(self.dt, n, 0, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, 0, 0,
                      math.sqrt(1.0 / g.layers), 0, *path)
-        es = self.ar_w.element_size()
-        common = (L.ptr(self.ar_dil), L.ptr(self.ar_ring_off))
-        weights = (self.ar_ring_total, L.ptr(self.ar_w), self.ar_layer_elems * es, self.ar_w2_off * es, L.ptr(self.ar_b2), L.ptr(zb),
-                   L.ptr(self.first_tab), L.ptr(self.first_bias), L.ptr(self.ar_wh), L.ptr(self.ar_hb), L.ptr(c_up), self.dt,
-                   L.ptr(inputs), L.ptr(uni), L.ptr(out_idx), L.ptr(logits))
+        operands = (L.ptr(inputs), L.ptr(uni), L.ptr(out_idx), L.ptr(logits))
         if coop:
             C = max(1, min(self.opt.ar_coop_c, 32, g.H, g.S))       # as _ar_open
-            nv = lib.wae_ar_coop_msg_values(ctypes.byref(d), C)
             # the kernels do not depend on the ring's contents; msg, acc, error (and next) start from zero
             ring = torch.empty(plan.slots * C * self.ar_ring_total, dtype=torch.float32, device=dev)
-            msg = torch.zeros(plan.slots * 2 * C * nv, dtype=torch.int64, device=dev)
-            acc = torch.zeros(plan.slots * lib.wae_ar_coop_acc_floats(ctypes.byref(d)), dtype=torch.float32, device=dev)
-            err = torch.zeros(64, dtype=torch.int32, device=dev)
-            L.check(lib.wae_ar_generate_coop_list(ctypes.byref(d), C, n, plan.slots, L.ptr(items_d), L.ptr(nxt), total, *common,
-                                                  L.ptr(ring), *weights, L.ptr(msg), L.ptr(acc), L.ptr(err), st),
+            msg, acc, err = self._ar_exchange(d, C, plan.slots, torch.zeros)
+            L.check(lib.wae_ar_generate_coop_list(ctypes.byref(d), C, n, plan.slots, L.ptr(items_d), L.ptr(nxt), total,
+                                                  *self._ar_net_args(ring, zb, c_up), *operands, L.ptr(msg), L.ptr(acc), L.ptr(err), st),
                     "ar_generate_coop_list")
             self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, uni, msg, acc, err)
-            self._ar_profile = err
-            if int(err[0].item()) != 0:         # synchronises, once per launch, as _ar_launch
-                raise L.WaeError("ar_generate_coop_list: an exchange between the cooperating workgroups timed out")
+            self._ar_check_exchange(err, "ar_generate_coop_list")
         else:
             # not zeroed: a decode reads a history row only behind its own write of it (csrc/ar_fwd.hip: ar_decode), in the first item
             # of a slot as in every later one
             ring = torch.empty(plan.slots * self.ar_ring_total, dtype=torch.float32, device=dev)
-            L.check(lib.wae_ar_generate_list(ctypes.byref(d), n, plan.slots, L.ptr(items_d), L.ptr(nxt), *common, L.ptr(ring), *weights,
-                                             st), "ar_generate_list")
+            L.check(lib.wae_ar_generate_list(ctypes.byref(d), n, plan.slots, L.ptr(items_d), L.ptr(nxt),
+                                             *self._ar_net_args(ring, zb, c_up), *operands, st), "ar_generate_list")
             self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, uni)      # the launch's operands live until the stream has run
         return [dict(idx=out_idx[off[i]:off[i] + Ts[i]],
                      logits=logits[off[i] * g.O:(off[i] + Ts[i]) * g.O].view(g.O, Ts[i]) if want else None) for i in range(n)]
