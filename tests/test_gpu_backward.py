@@ -342,7 +342,7 @@ def test_dropout_forward_and_backward_against_oracle(p_drop):
     lengths = torch.tensor([T, T - 137])
     out = eng.decoder_forward(x.cuda(), c_up.cuda(), g.cuda(), targets=x.cuda(), lengths=lengths.cuda(), train=True,
                               c_is_upsampled=True, want_logits=True)
-    seeds = list(eng._drop_seeds)
+    seeds = list(eng.saved.drop_seeds)
     assert seeds == [eng.layer_drop_seed(1, l) for l in range(cfg["layers"])]
     keep0 = O.dropout_keep(seeds[0], B, cfg["R"], T, p_drop)
     assert abs(float(keep0.float().mean()) - (1 - p_drop)) < 0.01                      # Bernoulli(1 - p)

@@ -186,7 +186,7 @@ def test_vqwae_full_geometry_train_step_fp32():
     res = eng.train_step(x.cuda(), c.cuda(), g.cuda(), lengths=lengths.cuda(), lr=4e-4, clip_thresh=100.0, ema_decay=0.9999,
                          grad_hook=hook)
     torch.cuda.synchronize()
-    assert np.array_equal(eng._fe["idx"].cpu().numpy(), z["vq_idx"])
+    assert np.array_equal(eng.saved.idx.cpu().numpy(), z["vq_idx"])
     assert abs(float(res["ce"]) - float(z["ce"])) < 1e-4 * float(z["ce"])
     assert abs(float(res["vq_loss"]) - float(z["vq_loss"])) < 1e-5 * max(1.0, float(z["vq_loss"]))
     assert abs(float(res["perp"]) - float(z["perp"])) < 1e-3

@@ -40,7 +40,7 @@ for path in sys.argv[1:]:
         lp = l - 1
         args = [ctypes.byref(d), ctypes.c_void_p(ws["dz"].data_ptr() + l * Z2 * es), dzs, L.ptr(ws["gx"][(l + 1) % ngx]),
                 L.ptr(ws["gx"][l % ngx]), L.ptr(ws["dskip"]), L.ptr(fw["z"][lp]), ctypes.c_void_p(ws["dz"].data_ptr() + lp * Z2 * es),
-                ctypes.c_void_p((eng.w_bxf if hasattr(eng, "w_bxf") else eng.w_bx).data_ptr() + l * eng.n_bx * es),
+                ctypes.c_void_p((eng.w_bxf if eng.w_bxf is not None else eng.w_bx).data_ptr() + l * eng.n_bx * es),
                 ctypes.c_void_p(eng.w_buo.data_ptr() + lp * eng.n_buo * es),
                 ctypes.c_void_p(eng.w_bu.data_ptr() + lp * eng.n_bu * es + us_off),
                 ctypes.c_void_p(eng.w_bc.data_ptr() + l * cbytes), L.ptr(ws["dc32"]), L.ptr(ws["dc"]), 1 | four, 0, None]

@@ -109,7 +109,7 @@ def eval_model(eng, x, c, g, lengths, global_step, eval_dir, hp, use_ema, hop):
     ci = c[idx:idx + 1, :, :frames].contiguous().float()
     gi = g[idx:idx + 1].contiguous() if g is not None else None
     saved = None
-    if use_ema and getattr(eng, "shadow", None) is not None:
+    if use_ema and eng.shadow is not None:
         print("Using averaged model for evaluation")
         saved = eng.params.clone()
         eng.params.copy_(eng.shadow)
@@ -198,7 +198,7 @@ def main(argv=None):
         step, epoch, test_step = load_checkpoint(args.checkpoint, eng, args.reset_optimizer, ema=use_ema)
     eng.drop_calls = step        # the dropout masks follow the global step: a resumed run does not replay the first steps' masks
     D.broadcast_params(eng.params)
-    if not hasattr(eng, "exp_avg"):
+    if eng.exp_avg is None:
         eng.init_optimizer(ema=use_ema)
     elif use_ema:
         eng.shadow.copy_(eng.params)                 # the shadow registers the (broadcast) weights it starts from (:822-826)

@@ -23,12 +23,13 @@ import torch
 
 from . import _lib as L
 from . import packing as P
+from .step_state import saved_for
 
 RS = math.sqrt(0.5)
 
 
 def _prepare_bwd(eng):
-    if getattr(eng, "_bwd_ready", False):
+    if eng._bwd_ready:
         return
     g, dev, lay = eng.g, eng.device, eng.lay
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
@@ -47,6 +48,7 @@ def _prepare_bwd(eng):
     sup = eng.lib.wae_glu_bwd_fused_supported16(g.Rp, g.Hp) if is16 else eng.lib.wae_glu_bwd_fused_supported(g.Rp, g.Hp)
     want = eng.opt.bwd_fused == "1" or (eng.opt.bwd_fused == "auto" and is16)
     eng.fused_bwd = bool(sup) and g.Sp % (64 if is16 else 32) == 0 and want
+    eng.m_bxf = eng.w_bxf = None
     if eng.fused_bwd:
         eng.m_buo = up(P.bwd_uo_map(g, lay, eng.dt))
         eng.n_buo = eng.m_buo.numel()
@@ -87,7 +89,7 @@ def _prepare_bwd(eng):
 def pack_bwd_weights(eng):
     _prepare_bwd(eng)
     lib, st, g, lay = eng.lib, eng.stream(), eng.g, eng.lay
-    jobs = getattr(eng, "_pack_bwd_jobs", None)
+    jobs = eng._pack_bwd_jobs
     if jobs is None:
         eff = eng.eff.data_ptr()
         J = lambda mp, dst, n, nb, ss, ds: L.GatherJob(eff, mp.data_ptr(), dst.data_ptr(), n, ss, ds, nb, eng.dt)
@@ -95,7 +97,7 @@ def pack_bwd_weights(eng):
                J(eng.m_bx, eng.w_bx, eng.n_bx, g.layers, lay.layer_stride, eng.n_bx)]
         if eng.fused_bwd:
             lst.append(J(eng.m_buo, eng.w_buo, eng.n_buo, g.layers, lay.layer_stride, eng.n_buo))
-            if hasattr(eng, "m_bxf"):
+            if eng.m_bxf is not None:
                 lst.append(J(eng.m_bxf, eng.w_bxf, eng.n_bx, g.layers, lay.layer_stride, eng.n_bx))       # tap by tap (fp32)
         if g.Ccp:
             lst.append(J(eng.m_bc, eng.w_bc, eng.m_bc.numel(), 1, 0, 0))
@@ -150,10 +152,10 @@ def _timed(eng, sink, fn):
 
 def _await_packed_weights(eng):
     """The backward's packed weights and cleared gradient accumulators: train_step queued that launch on a side stream right behind
-    weight norm (eng._early_pack: wait for it); any other caller packs here."""
-    early = eng.__dict__.pop("_early_pack", None)
+    weight norm (eng.flight.early_pack: wait for it); any other caller packs here."""
+    early = eng.flight.take_early_pack()
     if early is not None:
-        eng.join(early[0])
+        eng.join(early)
     else:
         pack_bwd_weights(eng)      # (also clears eng.d_eff and eng.cbuf)
 
@@ -612,8 +614,8 @@ def _step(eng, B, T, seeds=None):
     # launch of layer 0 (which runs the pair kernel's first half only) -- the K = L * 2Hp launch that re-read every dz is gone
     fold_dc = bool(eng.fused_bwd and seeds is None and is16 and g.k == 3 and g.Ccp == 64 and eng.opt.bwd_fold_dc)
     return _Step(eng, eng._ws[("bwd", B, T)], eng._ws[(B, T, True)], B, T, eng.w_glu.element_size(), 2 * g.Hp, g.layers * 2 * g.Hp,
-                 (g.Rp // (64 if is16 else 32)) * g.NP * 4 * 1024, seeds, fold_dc, getattr(eng, "_tm_events", None),
-                 getattr(eng, "_tn_events", None), parts=((0, B, None),))
+                 (g.Rp // (64 if is16 else 32)) * g.NP * 4 * 1024, seeds, fold_dc, eng._tm_events, eng._tn_events,
+                 parts=((0, B, None),))
 
 
 def _k_u(cx, l, gn, part, flags=0):
@@ -662,12 +664,12 @@ def _k_pair(cx, l, g_next, g_cur):
                 ctypes.c_void_p(g_next.data_ptr() + r * g.Rp), ctypes.c_void_p(g_cur.data_ptr() + r * g.Rp),
                 ctypes.c_void_p(ws["dskip"].data_ptr() + r * g.Sp), ctypes.c_void_p(cx.fw["z"][lp].data_ptr() + r * Z2),
                 ctypes.c_void_p(ws["dz"].data_ptr() + lp * Z2 * es + r * dzs),
-                ctypes.c_void_p((eng.w_bxf if hasattr(eng, "w_bxf") else eng.w_bx).data_ptr() + l * eng.n_bx * es),
+                ctypes.c_void_p((eng.w_bxf if eng.w_bxf is not None else eng.w_bx).data_ptr() + l * eng.n_bx * es),
                 ctypes.c_void_p(eng.w_buo.data_ptr() + lp * eng.n_buo * es),
                 ctypes.c_void_p(eng.w_bu.data_ptr() + lp * eng.n_bu * es + cx.us_off)]
         sq = stc if stc is not None else eng.stream()
         if cx.fold_dc:
-            mode = (0 if l == g.layers - 1 else 1) | (2 if l == 0 else 0) | (4 if getattr(eng, "bwd_pair4", False) else 0)
+            mode = (0 if l == g.layers - 1 else 1) | (2 if l == 0 else 0) | (4 if eng.bwd_pair4 else 0)
             # (bit 2: keep the 4-wave kernel where the 8-wave one, csrc/glu_bwd8.hip, has an instantiation -- tests and tools)
             args += [ctypes.c_void_p(eng.w_bc.data_ptr() + l * cbytes), ctypes.c_void_p(ws["dc32"].data_ptr() + b0 * T * 64 * 4),
                      ctypes.c_void_p(ws["dc"].data_ptr() + r * ws["dc"].shape[-1]), mode, int(l == 0)]
@@ -944,7 +946,7 @@ def _finish_plan(cx):
     if not eng.opt.grad_finish:
         return None
     static = isinstance(cx.ws["stream"], StaticStreamTable)
-    plans = eng.__dict__.setdefault("_finish_plans", {})
+    plans = eng._finish_plans
     if static not in plans:
         plans[static] = _build_finish_plan(cx)
     return plans[static]
@@ -1017,27 +1019,28 @@ def _tn_behind_sweep(cx, sched, grad_sync):
         _timed(eng, cx.tn_ev, sched.end.launch)
     if sched.kind == "beside":           # (the upper layers' launch has been running beside the sweep)
         eng.join(cx.beside_done[0])
-    eng._grads_done = None
+    fl = eng.flight
+    fl.grads_done = None
     if sched.kind == "split":
         done = _finish_layers(cx, 0, sched.cut, with_head=False)
         eng.join(done[0] if done else None)
         seg = layer_segment(eng)
-        eng._grads_done = seg
+        fl.grads_done = seg
         _hand_over(cx, grad_sync, seg[0], layer_segment_mid(eng))
         return
     done = _finish_layers(cx, 0, eng.g.layers, with_head=True)
     if grad_sync is None:
         cx.small_done = done
         if cx.finish is not None:      # finish_grads has the rest of the arena left (and, with finish_acc, the rest of the norm)
-            eng._grads_done = layer_segment(eng)
-            eng._norm_summed = cx.finish_acc
+            fl.grads_done = layer_segment(eng)
+            fl.norm_summed = cx.finish_acc
     else:
         eng.join(done[0] if done else None)
         # data parallel without the split (too few layers, or the per-layer tile launches of fp32): the layers' + head's gradients
         # are final -> weight-norm backward of that slice, then the all-reduce starts on its side stream while the launches below
         # (and the front end's backward) still run
         seg = layer_segment(eng)
-        eng._grads_done = seg
+        fl.grads_done = seg
         _hand_over(cx, grad_sync, *seg)
 
 
@@ -1102,12 +1105,13 @@ def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: O
     ``grad_sync`` (distributed.GradSync): the layers' + head's slice of the gradient arena is finished (weight-norm backward
     of that slice) and handed to the all-reduce BEFORE the conditioning / first-conv / front-end gradients are computed, so
     the collective runs under them."""
+    B, T = x_ids.shape
+    sv = saved_for(eng, B, T)
     _prepare_bwd(eng)
     g = eng.g
-    B, T = x_ids.shape
     bwd_workspace(eng, B, T)
     _await_packed_weights(eng)
-    cx = _step(eng, B, T, getattr(eng, "_drop_seeds", None))   # (the seeds: set by the train-mode forward when dropout is active)
+    cx = _step(eng, B, T, sv.drop_seeds)
     ws = cx.ws
     if lengths is None:
         count = B * (T - 1)
@@ -1121,12 +1125,12 @@ def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: O
     cx.gid32 = gid.to(torch.int32).contiguous() if gid is not None else None
     cx.gvec = gvec
     sched = _tn_schedule(cx, grad_sync is not None)
-    cx.finish = eng._finish_used = _finish_plan(cx)
+    cx.finish = eng.flight.finish_used = _finish_plan(cx)
     cx.finish_acc = cx.finish is not None and grad_sync is None
-    eng._norm_summed = False
+    eng.flight.norm_summed = False
     if cx.fold_dc and "dc32" not in ws:
         ws["dc32"] = torch.empty(B, T, 64, dtype=torch.float32, device=eng.device)
-    eng._grads_done = None
+    eng.flight.grads_done = None
     # ---- gated stack, last layer first ---------------------------------------------------------------------------
     _k_u(cx, g.layers - 1, ws["gzero"], cx.parts[0])
     # two half-batch chains of the sweep's launches (engine.chain_plan), the second half a launch late; not with dropout (its mask
@@ -1138,19 +1142,19 @@ def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: O
         # weight-gradient launch below, which fills every SIMD's registers, and run in that launch's ragged end (its workgroups finish
         # 60-90 us apart) and beside the scatters.  (Started behind the weight-gradient launch instead they ran beside the scatters
         # only, and both took longer: 54 us per step gained instead of 90.)
-        eng._ev_dc = torch.cuda.Event()
-        eng._ev_dc.record(torch.cuda.current_stream(eng.device))
+        eng.flight.ev_dc = torch.cuda.Event()
+        eng.flight.ev_dc.record(torch.cuda.current_stream(eng.device))
     _tn_behind_sweep(cx, sched, grad_sync)
     # ---- local-conditioning gradient over all layers at once ---------------------------------------------------------
     if g.Ccp and not cx.fold_dc:
         _tm(eng, B, T, g.Ccp, 0, 1.0, [(ws["dz"].data_ptr(), cx.dzs, cx.dzs, 0)], eng.w_bc.data_ptr(), ws["dc"].data_ptr(), g.Ccp)
     _first_conv_grads(cx, x_ids, xi)          # (behind the gather pass, while the side stream's chain of small launches runs)
     eng.join(cx.small_done[0] if cx.small_done else None)
-    eng._bwd_keep = [xi, tg, ln, cx.gid32]
+    eng.hold("bwd", xi, tg, ln, cx.gid32)
     return ws["dc"]
 
 
-def layer_backward(eng, B, T, gx_hat, ds, gvec, drop_seed=None, lead=0):
+def layer_backward(eng, B, T, gx_hat, ds, gvec, lead=0):
     """Backward of ONE ResidualConv1dGLU layer (an engine of geometry layers == 1, wavenet_vocoder.modules.ResidualConv1dGLU) -- the
     autograd of modules.py:115-163 from the same kernels the stack uses, last train-mode forward of that (B, T):
         dz  = gate'(z) * (W_out^T gx_hat + W_skip^T ds)                   (wae_gemm_tm GATE_BWD)
@@ -1158,11 +1162,13 @@ def layer_backward(eng, B, T, gx_hat, ds, gvec, drop_seed=None, lead=0):
         dc  = Wc^T dz                                                     (wae_gemm_tm PLAIN)
         dW1, dWc, per-clip sums of dz, dW_out + bias, dW_skip + bias      (wae_gemm_tn_tiles), gproj / weight-norm backward
     gx_hat (B,T,Rp) = sqrt(.5) * d loss / d x' (x' = (conv1x1_out(u) + x) sqrt(.5)), ds (B,T,Sp) = d loss / d s, both in the engine's
-    storage dtype (times eng.grad_scale for fp16).  drop_seed: the seed of the dropout mask the forward applied to the convolution's
-    operand (modules.py:127-128), or None.  lead > 0: a causal=False layer run on a frame `lead` steps longer (modules.ResidualConv1dGLU):
+    storage dtype (times eng.grad_scale for fp16).  The dropout mask the forward applied to the convolution's operand (modules.py:127-128)
+    is regenerated from the seed in eng.saved.  lead > 0: a causal=False layer run on a frame `lead` steps longer (modules.ResidualConv1dGLU):
     the convolution operand's rows [0, T - lead) are x, the residual operand's rows [lead, T) are x, so the residual path's gradient of
     x[t] is gx_hat[t + lead] (gx_hat must own `lead` readable rows behind its end) and dx is returned in the convolution operand's frame.
     Fills eng.grads (finish_grads) and returns (dx (B,T,Rp), dc (B,T,Ccp) | None)."""
+    sv = saved_for(eng, B, T)
+    drop_seed = sv.drop_seeds[0] if sv.drop_seeds else None
     _prepare_bwd(eng)
     g, lib, lay, st, sm = eng.g, eng.lib, eng.lay, eng.stream(), eng.sm
     assert g.layers == 1
@@ -1223,8 +1229,8 @@ def layer_backward(eng, B, T, gx_hat, ds, gvec, drop_seed=None, lead=0):
     L.check(lib.wae_gproj_bwd(L.ptr(eng.eff), L.ptr(eng.d_eff), wg_off, lay.off("wavenet.conv_layers.0.conv.bias"), lay.layer_stride,
                               None, 0, L.ptr(gvec), L.ptr(c1), Z2 * sm["ld1"], sm["ld1"], g.k * g.Rp + g.Ccp, B, 1, g.G, g.Hp,
                               max(g.Cg, 0), 0, st), "gproj_bwd")
-    eng._grads_done = eng._finish_used = None
-    eng._norm_summed = False
+    eng.flight.grads_done = eng.flight.finish_used = None
+    eng.flight.norm_summed = False
     finish_grads(eng)
     return ws["gx"], (ws["dc"] if g.Ccp else None)
 
@@ -1241,15 +1247,14 @@ def _debug_kernels(eng, B, T, l, flags_u=0, flags_x=0):
 
 def finish_grads(eng):
     """d_eff (gradient wrt effective weights) -> grads (wrt weight_g / weight_v and plain parameters); the slice that
-    decoder_backward already finished for the all-reduce (eng._grads_done) is left alone."""
-    lay = eng.lay
-    done = getattr(eng, "_grads_done", None)
-    plan = getattr(eng, "_finish_used", None)
+    decoder_backward already finished for the all-reduce (eng.flight.grads_done) is left alone."""
+    lay, fl = eng.lay, eng.flight
+    done, plan = fl.grads_done, fl.finish_used
     if plan is not None and done is not None and tuple(done) == tuple(layer_segment(eng)):
         # the gather pass served the segment: the rest of the arena in ONE launch of the same kernel (its rows read d_eff), which adds
         # their squares to the norm's accumulator as well -- instead of two launches per side of the segment and a pass for the norm
-        _finish_rows(eng, plan, 0, lay.total, "outer", getattr(eng, "_norm_summed", False))
-        eng._grads_done = None
+        _finish_rows(eng, plan, 0, lay.total, "outer", fl.norm_summed)
+        fl.grads_done = None
     elif done is None:
         _wn_bwd_range(eng, 0, lay.total)
     else:
@@ -1257,19 +1262,20 @@ def finish_grads(eng):
             _wn_bwd_range(eng, 0, done[0])
         if done[1] < lay.total:
             _wn_bwd_range(eng, done[1], lay.total)
-        eng._grads_done = None
+        fl.grads_done = None
     return eng.grads
 
 
 def frontend_backward(eng, dc: torch.Tensor, loss_scale: float = 1.0, stop_at_quant: bool = False):
     """dc (B,T,Ccp) -> upsample stages -> conv_in -> [VQ straight-through + vq_loss -> encoder]; adds the weight
-    gradients into eng.d_eff.  Uses the activations kept by the last train-mode forward."""
+    gradients into eng.d_eff.  Uses the activations kept by the last train-mode forward (eng.saved)."""
     g, lib, lay, st = eng.g, eng.lib, eng.lay, eng.stream()
     B, T = dc.shape[0], dc.shape[1]
+    sv = saved_for(eng, B, T)
     dev = eng.device
     d = torch.empty(B, g.Cc, T, dtype=torch.float32, device=dev)
     L.check(lib.wae_from_btc_scaled(L.ptr(dc), L.ptr(d), B, g.Cc, T, g.Ccp, eng.dt, 1.0 / eng.grad_scale, st), "from_btc")
-    acts = eng._up_acts                      # [conv_in input | None, stage-0 input, stage-1 input, ...]
+    acts = sv.up_acts                        # [conv_in input | None, stage-0 input, stage-1 input, ...]
     keep = [d]
     if not g.conv_in and g.cin_pad > 0:      # plain UpsampleNetwork: the forward trimmed `indent` samples at either end (upsample.py:64-65)
         trim = g.cin_pad * int(np.prod(g.upsample_scales))
@@ -1281,7 +1287,7 @@ def frontend_backward(eng, dc: torch.Tensor, loss_scale: float = 1.0, stop_at_qu
         xin = acts[1 + i]
         name = P.up_stage_name(g, i) + ".weight_v"
         if act:        # through the stage's activation, whose output is the next stage's input (the last stage's: kept by the forward)
-            yout = acts[2 + i] if i + 1 < len(g.upsample_scales) else eng._up_last
+            yout = acts[2 + i] if i + 1 < len(g.upsample_scales) else sv.up_last
             d = d.contiguous()
             L.check(lib.wae_act_bwd(L.ptr(yout), L.ptr(d), d.numel(), act, float(g.up_act_slope), st), "upsample activation bwd")
         din = torch.empty_like(xin)
@@ -1299,18 +1305,17 @@ def frontend_backward(eng, dc: torch.Tensor, loss_scale: float = 1.0, stop_at_qu
     else:
         dq = d                               # no conv_in: the stages' input gradient IS the gradient of the features
     keep.append(dq)
-    eng._fe_keep = keep
-    fe = getattr(eng, "_fe", None)
+    eng.hold("fe", keep)      # (the list itself: the encoder's side below appends to it)
     if stop_at_quant:
         return dq
-    if fe is not None and g.has_encoder:
-        lat, quant, idx = fe["lat"], fe["quant"], fe["idx"]
+    if sv.lat is not None and g.has_encoder:
+        lat, quant, idx = sv.lat, sv.quant, sv.idx
         Tq = lat.shape[-1]
         dlat = torch.empty_like(lat)
         en = "vq.embedding.weight"
         L.check(lib.wae_vq_bwd(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(eng.d_eff[lay.off(en):]), B, g.Cc,
-                               Tq, fe["beta"], loss_scale, st), "vq_bwd")
-        ea = eng._enc_acts                   # ea[i] = input of block i, ea[10] = output of block 9
+                               Tq, sv.beta, loss_scale, st), "vq_bwd")
+        ea = sv.enc_acts                     # ea[i] = input of block i, ea[10] = output of block 9
         dx = torch.empty_like(ea[10])
         L.check(lib.wae_enc_conv_bwd(L.ptr(ea[10]), L.ptr(eng.eff[lay.off("encoder.lin.weight"):]), None, L.ptr(dlat), L.ptr(dx),
                                      L.ptr(eng.d_eff[lay.off("encoder.lin.weight"):]), L.ptr(eng.d_eff[lay.off("encoder.lin.bias"):]),
@@ -1328,5 +1333,4 @@ def frontend_backward(eng, dc: torch.Tensor, loss_scale: float = 1.0, stop_at_qu
                                          k, s, k // 2, 1, int(s == 1 and ci == co), st), "enc block bwd")
             keep.append(dxi)
             dcur = dxi
-    eng._fe_keep = keep
     return dq

@@ -20,7 +20,7 @@ def adam_state_dict(eng, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weigh
     lay = eng.lay
     keys = list(lay.offsets)
     state = {}
-    if getattr(eng, "opt_step", 0) > 0:
+    if eng.opt_step > 0:
         m, v = eng.exp_avg.detach().cpu(), eng.exp_avg_sq.detach().cpu()
         for i, k in enumerate(keys):
             off, n = lay.off(k), lay.numel(k)
@@ -36,7 +36,7 @@ def load_adam_state_dict(eng, opt: Optional[dict]) -> dict:
     """Restore Adam moments and the step count from a torch-format state dict (a reference checkpoint's ``optimizer``,
     vqwae_train.py:967-970) or from this repository's round-1 ``layout == "flat-arena"`` form.  Raises on anything it cannot
     map -- a state that is silently dropped would restart the moments at zero.  -> the first param group (lr, betas, ...)."""
-    if not hasattr(eng, "exp_avg"):
+    if eng.exp_avg is None:
         eng.init_optimizer()
     if opt is None:
         return {}
@@ -86,13 +86,13 @@ def save_checkpoint(eng, step: int, epoch: int, checkpoint_dir: str, hp, rank: i
     path = os.path.join(checkpoint_dir, "checkpoint_step{:09d}.pth".format(step))
     sd = {k: v.cpu() for k, v in eng.state_dict().items()}
     opt = None
-    if hp.save_optimizer_state and hasattr(eng, "exp_avg"):
+    if hp.save_optimizer_state and eng.exp_avg is not None:
         from .hparams import adam_settings
         op = adam_settings(hp)
         opt = adam_state_dict(eng, lr if lr is not None else op["lr"], betas=op["betas"], eps=op["eps"], weight_decay=op["weight_decay"])
     torch.save({"state_dict": sd, "optimizer": opt, "global_step": step, "global_epoch": epoch, "global_test_step": test_step}, path)
     shutil.copyfile(path, os.path.join(checkpoint_dir, "checkpoint_latest.pth"))
-    if getattr(eng, "shadow", None) is not None:
+    if eng.shadow is not None:
         ema_sd = {}
         for k in eng.lay.offsets:
             off, n = eng.lay.off(k), eng.lay.numel(k)

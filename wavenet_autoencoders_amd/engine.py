@@ -21,6 +21,7 @@ import torch
 from . import _lib as L
 from . import packing as P
 from .options import two_chains
+from .step_state import InFlight, Saved
 
 
 def _dt(dtype) -> int:
@@ -130,6 +131,28 @@ class WaeEngine:
         self.ar_scalar_coop = False
         self._param_gen, self._prep_gen, self._ar_gen = 1, 0, -1
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)      # sticky WAE_ERR_* bits set by the kernels (include/wae.h)
+        # ---- step state: every attribute a later call creates or replaces starts here
+        self.saved: Optional[Saved] = None      # the last train-mode forward's record; None: nothing to differentiate
+        self.flight = InFlight()
+        self._keep = {}                         # hold(): buffers passed by raw pointer, alive until their slot's next use
+        self._side_streams, self._side_stream, self._ev_wn = {}, None, None
+        self._pack_jobs = self._pack_bwd_jobs = None          # the packing launches' job tables (the pointers never change)
+        self._bwd_ready, self._finish_plans = False, {}       # backward.py: _prepare_bwd, _finish_plan
+        self._gid_src = self._gid_version = self._gid32 = None
+        # hooks that bench.py, tools/ and tests set from outside
+        self._layer_events = self._tn_events = self._tm_events = None
+        self.chain_delay_us, self.bwd_pair4, self._ar_profile = None, False, None
+        # the decode path's maps and packed weights (_prepare_ar, pack_ar_weights) and the last decode's operands
+        self._ar_ready, self._ar_keep = False, None
+        self.m_ar_layer = self.m_ar_b2 = self.m_ar_head = self.m_ar_hb = self.ar_ring_off = self.ar_dil = None
+        self.ar_w = self.ar_b2 = self.ar_wh = self.ar_hb = self.ar_wm = None
+        self.ar_w2_off = self.ar_layer_elems = self.ar_ring_total = 0
+        # optimizer state (init_optimizer)
+        self.exp_avg = self.exp_avg_sq = self.shadow = self.opt_scratch = self.grad_norm = None
+        self.opt_step = 0
+
+    def hold(self, slot: str, *tensors):
+        self._keep[slot] = tensors
 
     # Parameter generations.  Everything derived from the parameters -- the weight-normed arena and the fragment-packed buffers
     # (prepare_weights), the matrix-vector layout of the autoregressive kernels (pack_ar_weights) -- remembers the generation it was
@@ -180,7 +203,7 @@ class WaeEngine:
         ids = torch.empty(B, T, dtype=torch.int32, device=self.device)
         L.check(self.lib.wae_onehot_to_ids(L.ptr(x), B, C, T, x.stride(0), x.stride(1), x.stride(2), L.ptr(ids), L.ptr(self.err),
                                            L.ERR_NOT_ONEHOT, self.stream()), "onehot_to_ids")
-        self._onehot_keep = x
+        self.hold("onehot", x)
         return ids
 
     # ------------------------------------------------------------------ parameters
@@ -202,7 +225,7 @@ class WaeEngine:
         if not two_chains(self.opt.chains, self.dt in (L.WAE_BF16, L.WAE_F16), B, T, backward):      # (options.py: the rule and its numbers)
             return None
         g = self.g
-        delay = getattr(self, "chain_delay_us", None)        # (tools)
+        delay = self.chain_delay_us        # (tools)
         if delay is None:
             # The forward chains start together and stay in step (started half a launch apart they ran 64 us per layer at C2 until they
             # fell into step, 53 in step, 55.5 as one chain).  The backward sweep's second chain starts half a launch late: 35 us at
@@ -214,10 +237,9 @@ class WaeEngine:
         return (B + 1) // 2, float(delay)
 
     def side_stream(self, k: int = 0):
-        ss = self.__dict__.setdefault("_side_streams", {})
-        if k not in ss:
-            ss[k] = torch.cuda.Stream(self.device)
-        return ss[k]
+        if k not in self._side_streams:
+            self._side_streams[k] = torch.cuda.Stream(self.device)
+        return self._side_streams[k]
 
     @contextlib.contextmanager
     def branch(self, k: int, after=None):
@@ -291,13 +313,13 @@ class WaeEngine:
         if side and self.opt.side and self.device.type == "cuda":      # the effective weights exist: what only needs them may start
             self._ev_wn = torch.cuda.Event()
             self._ev_wn.record(torch.cuda.current_stream(self.device))
-        with (self.branch(1, after=self._ev_wn) if self._ev_wn is not None else contextlib.nullcontext([None])) as self._pack_done:
+        with (self.branch(1, after=self._ev_wn) if self._ev_wn is not None else contextlib.nullcontext([None])) as self.flight.pack_done:
             self._pack_weights()
         self.weights_dirty = False
 
     def _pack_weights(self):
         lib, st, g, lay = self.lib, self.stream(), self.g, self.lay
-        jobs = getattr(self, "_pack_jobs", None)
+        jobs = self._pack_jobs
         if jobs is None:       # the pointers never change: one host array, one launch for every family
             es = self.w_glu.element_size()
             eff = self.eff.data_ptr()
@@ -345,8 +367,9 @@ class WaeEngine:
         return ws
 
     # ------------------------------------------------------------------ front end
-    def encoder_forward(self, c: torch.Tensor) -> torch.Tensor:
-        """a1: c (B, c_in, F) fp32 -> latents (B, Cc, F')  (vqvae_model.py:48-51)."""
+    def encoder_forward(self, c: torch.Tensor, save: Optional[Saved] = None) -> torch.Tensor:
+        """a1: c (B, c_in, F) fp32 -> latents (B, Cc, F')  (vqvae_model.py:48-51).  save: the train-mode forward's record, which
+        takes the blocks' inputs; without it nothing outlives the call."""
         g, lib, st = self.g, self.lib, self.stream()
         x = c.contiguous().float()
         B = x.shape[0]
@@ -368,7 +391,8 @@ class WaeEngine:
         L.check(lib.wae_enc_conv_fwd(L.ptr(x), L.ptr(self.eff[self.lay.off("encoder.lin.weight"):]),
                                      L.ptr(self.eff[self.lay.off("encoder.lin.bias"):]), L.ptr(lat), B, g.encoder_hid, Tq,
                                      g.Cc, 1, 1, 0, 0, 0, st), "enc_lin")
-        self._enc_acts = acts          # inputs of every block (+ the last block's output): backward needs them
+        if save is not None:
+            save.enc_acts = acts       # inputs of every block (+ the last block's output): backward needs them
         return lat
 
     def vq_forward(self, lat: torch.Tensor, beta: float = 0.25):
@@ -384,10 +408,11 @@ class WaeEngine:
                 "vq_nearest")
         return quant, idx, stats
 
-    def upsample_forward(self, c: torch.Tensor, out: torch.Tensor):
+    def upsample_forward(self, c: torch.Tensor, out: torch.Tensor, save: Optional[Saved] = None):
         """a3: c (B,Cc,Tc) fp32 -> out (B, (Tc - 2 cin_pad) * prod(scales), Ccp) time-major compute dtype.  ConvInUpsampleNetwork
         (upsample.py:69-85): conv_in eats cin_pad frames at either end, then the stages; plain UpsampleNetwork (Geometry.conv_in False,
-        upsample.py:29-66): the stages on all Tc frames, then cin_pad * prod(scales) samples trimmed at either end."""
+        upsample.py:29-66): the stages on all Tc frames, then cin_pad * prod(scales) samples trimmed at either end.
+        save: the train-mode forward's record, which takes the stages' inputs; without it (eval, a decode) nothing outlives the call."""
         g, lib, st = self.g, self.lib, self.stream()
         B, Cc, Tc = c.shape
         c = c.contiguous()
@@ -400,11 +425,11 @@ class WaeEngine:
             x = torch.empty(B, Cc, Tin, dtype=torch.float32, device=self.device)
             L.check(lib.wae_enc_conv_fwd(L.ptr(c), L.ptr(self.eff[self.lay.off("wavenet.upsample_net.conv_in.weight"):]),
                                          None, L.ptr(x), B, Cc, Tc, Cc, kin, 1, 0, 0, 0, st), "conv_in")
-            self._up_acts = [c, x]          # conv_in input, then every stage's input
+            acts = [c, x]          # conv_in input, then every stage's input
         else:
             x, Tin = c, Tc
             trim = g.cin_pad * int(np.prod(g.upsample_scales))
-            self._up_acts = [None, x]
+            acts = [None, x]
         for i, s in enumerate(g.upsample_scales):
             w = self.eff[self.lay.off(P.up_stage_name(g, i) + ".weight_v"):]
             last = i == n - 1 and trim == 0 and not act    # the last stage writes the time-major operand itself, unless something follows
@@ -419,13 +444,14 @@ class WaeEngine:
             if act:
                 L.check(lib.wae_act_fwd(L.ptr(x), x.numel(), act, float(g.up_act_slope), st), "upsample activation")
             if i < n - 1:
-                self._up_acts.append(x)
-        self._up_last = x if act else None      # the last stage's activated output: backward forms act' from it
+                acts.append(x)
+        xt = None
         if trim or act:       # upsample.py:64-65: c[:, :, indent:-indent]
             assert out.shape[1] == Tin - 2 * trim, (out.shape, Tin, trim)
             xt = x[:, :, trim:Tin - trim].contiguous() if trim else x
             L.check(lib.wae_to_btc(L.ptr(xt), L.ptr(out), B, Cc, Tin - 2 * trim, g.Ccp, self.dt, st), "to_btc (c_up)")
-            self._up_keep = xt
+        if save is not None:
+            save.up_acts, save.up_last, save.up_keep = acts, (x if act else None), xt
         return out
 
     def layer_drop_seed(self, call: int, layer: int) -> int:
@@ -439,12 +465,15 @@ class WaeEngine:
     def decoder_forward(self, x: torch.Tensor, c: Optional[torch.Tensor], gid: Optional[torch.Tensor],
                         targets: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None,
                         want_logits: bool = True, train: bool = False, c_is_upsampled: bool = False,
-                        gvec: Optional[torch.Tensor] = None, layer_events: Optional[list] = None, dropout_on: bool = True):
+                        gvec: Optional[torch.Tensor] = None, layer_events: Optional[list] = None, dropout_on: bool = True,
+                        saved: Optional[Saved] = None):
         """WaveNet.forward (wavenet.py:164-216) on class ids.
 
         x: (B,T) int32 class ids (mulaw-quantize) or (B,T) fp32 scalars (scalar_input).
         c: (B,Cc,Tc) fp32 local conditioning (upsampled here) or, if c_is_upsampled, (B,Cc,T).
         gid: (B,) int32 speaker ids.  targets: (B,T) int32 -> fused shifted CE.
+        train: the activations stay in the (B, T, True) workspace and this forward's record becomes self.saved once it is complete
+        (saved: the record forward() began with the encoder's side; default: a new one).
         Returns dict(logits (B,O,T) | None, nll (B,T) | None, loss | None).
         """
         if self.weights_dirty:
@@ -452,6 +481,9 @@ class WaeEngine:
         g, lib, st = self.g, self.lib, self.stream()
         B, T = x.shape
         ws = self.workspace(B, T, train)
+        sv = None
+        if train:       # the launches below overwrite what the previous train-mode forward of this (B, T) saved
+            self.saved, sv = None, (saved if saved is not None else Saved(B, T))
         # global conditioning folded with the conv bias (first: in a train step the launches below run beside the weight packing)
         wg_off = self.lay.off("wavenet.conv_layers.0.conv1x1g.weight_v") if g.Cg > 0 else -1
         emb_off = self.lay.offsets.get("wavenet.embed_speakers.weight", 0)
@@ -475,9 +507,9 @@ class WaeEngine:
                 Tup = (c.shape[-1] - 2 * g.cin_pad) * int(np.prod(g.upsample_scales))
                 if Tup != T:
                     raise Exception(f"c {tuple(c.shape)} upsamples to {Tup} != T={T}")  # wavenet.py:198-200
-                self.upsample_forward(c.float(), ws["c_up"])
+                self.upsample_forward(c.float(), ws["c_up"], sv)
         # (train_step: the packing of the weights runs on a side stream beside the launches above -- prepare_weights(side=True))
-        self.join(self.__dict__.pop("_pack_done", [None])[0])
+        self.join(self.flight.take_pack_done())
         # first conv
         if g.scalar_input:
             xs = x.contiguous().float()
@@ -490,13 +522,10 @@ class WaeEngine:
         # gated residual stack
         es = self.w_glu.element_size()
         # dropout (modules.py:127-128) only in a train-mode forward of a model in training mode; eval is the identity
-        if train:
-            self.fwd_gen = getattr(self, "fwd_gen", 0) + 1       # the saved activations now belong to THIS forward
         drop = self.dropout if (train and dropout_on) else 0.0
-        self._drop_seeds = None
         if drop > 0:
             self.drop_calls += 1
-            self._drop_seeds = [self.layer_drop_seed(self.drop_calls, i) for i in range(g.layers)]
+            sv.drop_seeds = [self.layer_drop_seed(self.drop_calls, i) for i in range(g.layers)]
         if layer_events is not None:   # HIP events on the launch stream around the whole gated stack (bench.py)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record(torch.cuda.current_stream(self.device))
@@ -517,7 +546,7 @@ class WaeEngine:
             xconv = xin
             if drop > 0:
                 xconv = ws["xd"][i]
-                L.check(lib.wae_dropout_fwd(L.ptr(xin), L.ptr(xconv), B * T * g.Rp, self._drop_seeds[i], drop, self.dt, st), "dropout")
+                L.check(lib.wae_dropout_fwd(L.ptr(xin), L.ptr(xconv), B * T * g.Rp, sv.drop_seeds[i], drop, self.dt, st), "dropout")
             elif train and "xd" in ws:
                 # an engine built with dropout > 0 running a train-mode forward of a model in eval mode: the weight-gradient
                 # tables of this (B, T) point at xd, so it must hold the (undropped) operand
@@ -571,6 +600,8 @@ class WaeEngine:
             L.check(lib.wae_masked_mean(L.ptr(ws["nll"]), L.ptr(ln), L.ptr(ws["loss"]), B, T, st), "masked_mean")
             out["nll"] = ws["nll"]
             out["loss"] = ws["loss"][0]
+        if train:
+            self.saved = sv
         return out
 
     def _head_fwd_wide(self, ws, B, T, logits, tg, train):
@@ -588,11 +619,11 @@ class WaeEngine:
                     ws["lse"].data_ptr() if (train and tg is not None) else None, None, 0.0, g.O)
         BW._tm_ce(self, B, T, g.Op, 5, [(ws["h1"].data_ptr(), g.Sp, g.Sp, 0)], self.w_hwide["w3"].data_ptr(), None, 0,
                   bh + 2 * g.Sp * 4, ce)
-        self._ce_keep = (logits, tg)
+        self.hold("ce", logits, tg)
 
     # ------------------------------------------------------------------ autoregressive synthesis
     def _prepare_ar(self):
-        if getattr(self, "_ar_ready", False):
+        if self._ar_ready:
             return
         g, dev = self.g, self.device
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
@@ -670,7 +701,7 @@ class WaeEngine:
         a, b = w1c[1:].contiguous(), wout[:-1].contiguous()        # (L-1, G, R), (L-1, R, H)
         L.check(self.lib.wae_bmm_f32(L.ptr(a), L.ptr(b), L.ptr(wm[1:]), g.layers - 1, g.G, g.R, g.H, g.R, g.H, g.H, g.G * g.R, g.R * g.H,
                                      g.G * g.H, math.sqrt(0.5), self.stream()), "bmm_f32")
-        self._fused_keep = (a, b)
+        self.hold("fused", a, b)
         return wm.to(self.tdtype).contiguous()
 
     def incremental_forward(self, c: Optional[torch.Tensor], gid: Optional[torch.Tensor], T: int, mode: str = "sample",
@@ -751,7 +782,7 @@ class WaeEngine:
                 t0 += n
                 yield item
         finally:
-            if getattr(self, "_ar_keep", None) is mine:
+            if self._ar_keep is mine:
                 self._ar_keep = None    # closed (early or at the end): the ring and the operands go with the generator
 
     def _ar_open(self, c, gid, T, *, mode, test_inputs, uniforms, init_idx, c_is_upsampled, want_logits, gvec, u_mix, u_log,
@@ -760,7 +791,7 @@ class WaeEngine:
         _ar_launch runs steps of: the packed weights, the start classes, the forced prefix, the upsampled conditioning, the speaker
         rows, the kernel path, the zeroed ring, the draws of all T steps and the exchange buffers."""
         g, dev = self.g, self.device
-        if not getattr(self, "_ar_packed", False) or self.weights_dirty:
+        if not self._ar_packed or self.weights_dirty:
             self.pack_ar_weights()
         T = int(T)
         B = c.shape[0] if c is not None else (test_inputs.shape[0] if test_inputs is not None else 1)
@@ -1011,7 +1042,7 @@ class WaeEngine:
             inits.append(init if nfs[i] == 0 else 0)
             if g.Ccp and it.get("c") is None:
                 raise ValueError(f"decode_list: item {i} has no conditioning c, the decoder has {g.Cc} conditioning channels")
-        if not getattr(self, "_ar_packed", False) or self.weights_dirty:
+        if not self._ar_packed or self.weights_dirty:
             self.pack_ar_weights()
         st = self.stream()
         inputs = None
@@ -1080,11 +1111,14 @@ class WaeEngine:
         """VQVAE.forward (vqvae_model.py:66-72) -> dict(logits, vq_loss, perp, latents, idx, quant, loss)."""
         if self.weights_dirty:
             self.prepare_weights()
-        lat = self.encoder_forward(c)
+        sv = Saved(*x.shape) if train else None
+        lat = self.encoder_forward(c, sv)
         quant, idx, stats = self.vq_forward(lat, beta)
-        out = self.decoder_forward(x, quant, gid, targets, lengths, want_logits, train, dropout_on=dropout_on, layer_events=layer_events)
+        if train:
+            sv.lat, sv.quant, sv.idx, sv.beta = lat, quant, idx, beta
+        out = self.decoder_forward(x, quant, gid, targets, lengths, want_logits, train, dropout_on=dropout_on, layer_events=layer_events,
+                                   saved=sv)
         out.update(latents=lat, quant=quant, idx=idx, vq_loss=stats[0], perp=stats[1])
-        self._fe = dict(lat=lat, quant=quant, idx=idx, beta=beta)
         return out
 
     # ------------------------------------------------------------------ training step (vqwae_train.py:709-798)
@@ -1102,13 +1136,13 @@ class WaeEngine:
         train-mode forward -> self.grads (flat arena).  loss_scale multiplies the CE term, vq_scale (default: loss_scale) the
         vq_loss term; grad_sync: see backward.decoder_backward."""
         from . import backward as BW
-        self._ev_dc = None
+        self.flight.ev_dc = None
         dc = BW.decoder_backward(self, x, targets, lengths, gid, gvec, ext_dy=ext_dy, loss_scale=loss_scale, grad_sync=grad_sync)
         if self.g.Ccp and self.g.upsample_scales:
-            if self._ev_dc is not None:
+            if self.flight.ev_dc is not None:
                 # dc was complete when the sweep ended (the event): the front end's backward runs on a side stream beside the scatter of
                 # the layers' weight gradients that decoder_backward queued behind the sweep (disjoint slices of the gradient arena)
-                with self.branch(0, after=self._ev_dc) as tail:
+                with self.branch(0, after=self.flight.ev_dc) as tail:
                     BW.frontend_backward(self, dc, loss_scale if vq_scale is None else vq_scale)
                 self.join(tail[0])
             else:
@@ -1129,7 +1163,7 @@ class WaeEngine:
         L.check(lib.wae_dmol_loss_fwd(L.ptr(y_hat), L.ptr(yf), L.ptr(nll), L.ptr(dy), B, g.O // 3, T, int(num_classes),
                                       float(log_scale_min), 1, st), "dmol_loss")
         loss, dyt, ln = self._masked_step_loss(nll, dy, lengths, scale)
-        self._dmol_keep = (yf, nll, dy, ln)
+        self.hold("dmol", yf, nll, dy, ln)
         return loss, dyt
 
     def _masked_step_loss(self, nll, dy, lengths, scale):
@@ -1161,7 +1195,7 @@ class WaeEngine:
         dy = torch.empty_like(y_hat)
         L.check(lib.wae_mog_loss_fwd(L.ptr(y_hat), L.ptr(yf), L.ptr(nll), L.ptr(dy), B, C, T, float(log_scale_min), 1, st), "mog_loss")
         loss, dyt, ln = self._masked_step_loss(nll, dy, lengths, scale)
-        self._mog_keep = (yf, nll, dy, ln)
+        self.hold("mog", yf, nll, dy, ln)
         return loss, dyt
 
     def scalar_loss_and_grad(self, y_hat, y, lengths, quantize_channels: int = 65536, log_scale_min: float = -7.0,
@@ -1181,7 +1215,7 @@ class WaeEngine:
         the gradient of the global masked mean of vqwae_train.py:374-379); vq_loss keeps weight 1 (rank mean, :759).
         Class-id input: masked cross-entropy; scalar input (hparams input_type "raw" / "mulaw"): discretized mixture of logistics,
         or mixture of Gaussians with geometry output_distribution "Normal"."""
-        if not hasattr(self, "exp_avg"):
+        if self.exp_avg is None:
             self.init_optimizer()
         self.prepare_weights(side=True)
         # one int32 copy of the ids for forward, targets and backward (each of them converts what it is handed: four 5-us launches)
@@ -1190,7 +1224,7 @@ class WaeEngine:
         if gid is not None and gid.dtype != torch.int32:
             # (the same speaker-id tensor step after step -- a benchmark's fixture -- is converted once.  The cache holds the source
             #  tensor itself and compares by identity: an address comes back from the allocator with the next batch's ids in it)
-            if getattr(self, "_gid_src", None) is not gid or self._gid_version != gid._version:
+            if self._gid_src is not gid or self._gid_version != gid._version:
                 self._gid_src, self._gid_version = gid, gid._version
                 self._gid32 = gid.to(self.device, torch.int32).contiguous()
             gid = self._gid32
@@ -1201,36 +1235,32 @@ class WaeEngine:
             # decoder_backward waits for it.  (Queued when the first conv is enqueued instead -- beside the first layer -- it made that
             # layer's launch 45 us longer: 20 us per step worse.  Two side streams carry everything: a process has few hardware
             # queues, and streams that share one run one after the other -- four chains of layer launches ran at half the speed of two.)
-            with self.branch(1, after=self._ev_wn) as self._early_pack:
+            with self.branch(1, after=self._ev_wn) as self.flight.early_pack:
                 BW.pack_bwd_weights(self)
         try:
             if self.g.scalar_input:
                 fwd = self.forward if self.g.has_encoder else self.decoder_forward
                 out = fwd(x, c, gid, targets=None, lengths=None, want_logits=True, train=True)
-                if not self.g.has_encoder:
-                    self._fe = None
                 loss, dyt = self.scalar_loss_and_grad(out["logits"], x, lengths, quantize_channels, log_scale_min, scale=ce_scale)
                 out["loss"] = loss
                 grads = self.backward(x, gid, None, lengths, ext_dy=dyt, vq_scale=1.0, grad_sync=grad_sync)
             elif self.g.has_encoder:
                 out = self.forward(x, c, gid, targets=x, lengths=lengths, want_logits=False, train=True,
-                                   layer_events=getattr(self, "_layer_events", None))
+                                   layer_events=self._layer_events)
             else:
                 out = self.decoder_forward(x, c, gid, targets=x, lengths=lengths, want_logits=False, train=True,
-                                           layer_events=getattr(self, "_layer_events", None))
-                self._fe = None
+                                           layer_events=self._layer_events)
             if not self.g.scalar_input:
                 grads = self.backward(x, gid, x, lengths, loss_scale=ce_scale, vq_scale=1.0, grad_sync=grad_sync)
         except BaseException:
-            self.__dict__.pop("_early_pack", None)      # (a refused input: nothing of this step may be taken for the next call's)
-            self.join(self.__dict__.pop("_pack_done", [None])[0])
+            self.join(self.flight.abandon())
             raise
         if grad_sync is not None:
             grad_sync.finish()
         if grad_hook is not None:
             grad_hook(grads)
         self.opt_step += 1
-        if getattr(self, "_norm_summed", False) and grad_sync is None and grad_hook is None:
+        if self.flight.norm_summed and grad_sync is None and grad_hook is None:
             # the gather passes of the backward (csrc/grad_finish.hip) summed the squares of every gradient while they wrote it, into
             # an accumulator that the packing launch had cleared: no fill and no pass over the arena for the norm
             L.check(self.lib.wae_clip_adam_ema_summed(L.ptr(self.params), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
@@ -1242,7 +1272,7 @@ class WaeEngine:
                                                L.ptr(self.shadow), self.lay.total, L.ptr(self.opt_scratch), L.ptr(self.grad_norm),
                                                self.opt_step, lr, betas[0], betas[1], eps, weight_decay, clip_thresh, ema_decay,
                                                self.stream()), "clip_adam_ema")
-        self._norm_summed = False
+        self.flight.norm_summed = False
         self.weights_dirty = True
         res = dict(ce=out["loss"], grad_norm=self.grad_norm[0])
         if self.g.has_encoder:

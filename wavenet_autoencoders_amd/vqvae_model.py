@@ -5,7 +5,7 @@
 import torch
 
 from . import packing as P
-from .wavenet_vocoder._base import ArenaModel
+from .wavenet_vocoder._base import ArenaModel, check_saved, logits_grad_btc
 from .wavenet_vocoder.wavenet import WaveNet, _ids_from_input, _start_classes, softmax_bct, stream_post
 
 
@@ -15,27 +15,18 @@ class _VQVAEFn(torch.autograd.Function):
         eng = model.engine()
         out = eng.forward(ids, c, gid, want_logits=True, train=train, dropout_on=model.training)
         ctx.model, ctx.ids, ctx.gid = model, ids, gid
-        ctx.gen, ctx.train = getattr(eng, "fwd_gen", 0), train
+        ctx.gen, ctx.train = (eng.saved.gen if train else None), train
         eng.check_errors()     # IndexError for an id outside its table, like the reference's nn.Embedding (wavenet.py:185-187)
         return out["logits"], out["vq_loss"].reshape(()), out["perp"].reshape(())
 
     @staticmethod
     def backward(ctx, dy, dvq, dperp):
-        from . import _lib as L
         from . import backward as BW
         model = ctx.model
         eng = model._engine
-        if ctx.train and getattr(eng, "fwd_gen", 0) != ctx.gen:
-            raise RuntimeError("backward through a forward whose saved activations were overwritten by a later training-mode forward "
-                               "of the same model: call backward before the next forward")
-        g = eng.g
-        B, O, T = dy.shape
-        ext = torch.zeros(B, T, g.Op, dtype=eng.tdtype, device=dy.device)
-        dyc = dy.contiguous().float()
-        if eng.grad_scale != 1.0:               # fp16 stack: its backward runs on loss-scaled gradients (engine.py: grad_scale)
-            dyc = dyc * eng.grad_scale
-        L.check(eng.lib.wae_to_btc(L.ptr(dyc), L.ptr(ext), B, O, T, g.Op, eng.dt, eng.stream()), "to_btc")
-        dc = BW.decoder_backward(eng, ctx.ids, None, None, ctx.gid, None, ext_dy=ext)
+        if ctx.train:
+            check_saved(eng, ctx.gen)
+        dc = BW.decoder_backward(eng, ctx.ids, None, None, ctx.gid, None, ext_dy=logits_grad_btc(eng, dy))
         BW.frontend_backward(eng, dc, float(dvq) if dvq is not None else 0.0)
         BW.finish_grads(eng)
         _, views = model._grad_views(eng)

@@ -68,6 +68,26 @@ def register_params(root: nn.Module, geom: P.Geometry, strip: str = "", skip=Non
     return names
 
 
+def check_saved(eng, gen, what="model"):
+    """The autograd wrappers' guard: the activations live in the engine (its workspace and eng.saved), not in the autograd node, so a
+    backward is legal only while the train-mode forward it belongs to (generation `gen`) is still the engine's last one."""
+    if eng.saved is None or eng.saved.gen != gen:
+        raise RuntimeError("backward through a forward whose saved activations were overwritten by a later training-mode forward "
+                           f"of the same {what}: call backward before the next forward")
+
+
+def logits_grad_btc(eng, dy):
+    """d loss / d logits (B, O, T) -> decoder_backward's ext_dy: (B, T, Op) in the storage dtype, times eng.grad_scale"""
+    from .. import _lib as L
+    B, O, T = dy.shape
+    ext = torch.zeros(B, T, eng.g.Op, dtype=eng.tdtype, device=dy.device)
+    dyc = dy.contiguous().float()
+    if eng.grad_scale != 1.0:               # fp16 stack: its backward runs on loss-scaled gradients (engine.py: grad_scale)
+        dyc = dyc * eng.grad_scale
+    L.check(eng.lib.wae_to_btc(L.ptr(dyc), L.ptr(ext), B, O, T, eng.g.Op, eng.dt, eng.stream()), "to_btc")
+    return ext
+
+
 class ArenaModel(nn.Module):
     """Base of WaveNet / VQVAE: owns a WaeEngine once the parameters sit on a GPU."""
 

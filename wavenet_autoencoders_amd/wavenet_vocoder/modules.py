@@ -9,7 +9,8 @@ import torch
 
 from .. import _lib as L
 from .. import packing as P
-from ._base import ArenaModel
+from ..step_state import Saved
+from ._base import ArenaModel, check_saved
 
 
 class _LayerFn(torch.autograd.Function):
@@ -20,11 +21,9 @@ class _LayerFn(torch.autograd.Function):
     def forward(ctx, mod, x, c, g, *params):
         xo, so = mod._run(x, c, g, train=True)
         eng = mod._engine
-        eng.fwd_gen = getattr(eng, "fwd_gen", 0) + 1           # the saved activations now belong to THIS forward
-        ctx.mod, ctx.gen, ctx.shape, ctx.has_c = mod, eng.fwd_gen, tuple(x.shape), c is not None
+        ctx.mod, ctx.gen, ctx.shape, ctx.has_c = mod, eng.saved.gen, tuple(x.shape), c is not None
         ctx.gvec = mod._keep[1]
         ctx.has_g = g is not None and eng.g.g_local
-        ctx.seed = mod._keep[2]                 # dropout seed of THIS forward (None: no mask)
         return xo, so
 
     @staticmethod
@@ -32,9 +31,7 @@ class _LayerFn(torch.autograd.Function):
         from .. import backward as BW
         mod = ctx.mod
         eng = mod._engine
-        if getattr(eng, "fwd_gen", 0) != ctx.gen:
-            raise RuntimeError("backward through a forward whose saved activations were overwritten by a later training-mode forward "
-                               "of the same layer: call backward before the next forward")
+        check_saved(eng, ctx.gen, "layer")
         gm, lib, st = eng.g, eng.lib, eng.stream()
         B, R, T0 = ctx.shape
         lead = mod.lead                 # non-causal: the kernels' frame is `lead` steps longer, outputs sit at [lead, T0 + lead)
@@ -49,7 +46,7 @@ class _LayerFn(torch.autograd.Function):
             L.check(lib.wae_to_btc(L.ptr(late(dxo.float() * (math.sqrt(0.5) * eng.grad_scale)).contiguous()), L.ptr(gx), B, gm.R, T, gm.Rp, eng.dt, st), "to_btc dx'")
         if dso is not None:
             L.check(lib.wae_to_btc(L.ptr(late(dso.float() * eng.grad_scale).contiguous()), L.ptr(ds), B, gm.S, T, gm.Sp, eng.dt, st), "to_btc ds")
-        dx_btc, dc_btc = BW.layer_backward(eng, B, T, gx, ds, ctx.gvec, drop_seed=ctx.seed, lead=lead)
+        dx_btc, dc_btc = BW.layer_backward(eng, B, T, gx, ds, ctx.gvec, lead=lead)
         dx = torch.empty(B, gm.R, T, dtype=torch.float32, device=dev)
         L.check(lib.wae_from_btc_scaled(L.ptr(dx_btc), L.ptr(dx), B, gm.R, T, gm.Rp, eng.dt, 1.0 / eng.grad_scale, st), "from_btc dx")
         if lead:
@@ -150,6 +147,8 @@ class ResidualConv1dGLU(ArenaModel):
         T = T0 + lead
         eng.prepare_weights()
         ws = eng.workspace(B, T, train)
+        if train:       # the launches below overwrite what the previous train-mode forward of this (B, T) saved
+            eng.saved = None
         L.check(lib.wae_to_btc(L.ptr(x.contiguous().float()), L.ptr(ws["x"][0]), B, gm.R, T, gm.Rp, eng.dt, st), "to_btc x")
         if lead:
             if "xnc" not in ws:
@@ -183,7 +182,7 @@ class ResidualConv1dGLU(ArenaModel):
         ws["u"].zero_()
         d = L.GluDesc(eng.dt, B, T, gm.Rp, gm.Ccp, gm.Hp, gm.k, self.dilation, L.GLU_SAVE_Z if train else 0)
         # dropout (modules.py:127-128): F.dropout on the convolution's operand in training mode, the residual path keeps x.  One seed per
-        # forward call from the engine's call counter (engine.layer_drop_seed); backward regenerates the mask from the seed kept in ctx.
+        # forward call from the engine's call counter (engine.layer_drop_seed); backward regenerates the mask from the seed in eng.saved.
         seed = None
         xconv = xsrc = ws["xnc"] if lead else ws["x"][0]
         if self.training and self.dropout > 0:
@@ -218,7 +217,9 @@ class ResidualConv1dGLU(ArenaModel):
         so_ = torch.empty(B, gm.S, T, dtype=torch.float32, device=eng.device)
         L.check(lib.wae_from_btc(L.ptr(ws["x"][1]), L.ptr(xo), B, gm.R, T, gm.Rp, eng.dt, st), "from_btc x")
         L.check(lib.wae_from_btc(L.ptr(sbt), L.ptr(so_), B, gm.S, T, gm.Sp, eng.dt, st), "from_btc s")
-        self._keep = (sbt, gvec, seed)
+        self._keep = (sbt, gvec)
+        if train:
+            eng.saved = Saved(B, T, drop_seeds=[seed] if seed is not None else None)     # (backward regenerates the mask from it)
         if lead:
             xo, so_ = xo[:, :, lead:].contiguous(), so_[:, :, lead:].contiguous()
         if not self.bias:

@@ -9,7 +9,7 @@ import torch
 from torch import nn
 
 from .. import packing as P
-from ._base import ArenaModel
+from ._base import ArenaModel, check_saved, logits_grad_btc
 
 
 def softmax_bct(y):
@@ -76,7 +76,7 @@ class _DecoderFn(torch.autograd.Function):
         ctx.gid, ctx.gvec = gid, gvec
         out = eng.decoder_forward(ids, c, gid, want_logits=True, train=train, c_is_upsampled=c_is_up, gvec=gvec,
                                   dropout_on=model.training)
-        ctx.gen = getattr(eng, "fwd_gen", 0)
+        ctx.gen = eng.saved.gen if train else None
         eng.check_errors()     # an out-of-range class / speaker id raises IndexError here, as nn.Embedding / the one-hot encoder do
         return out["logits"]
 
@@ -86,18 +86,11 @@ class _DecoderFn(torch.autograd.Function):
         from .. import backward as BW
         model = ctx.model
         eng = model._engine
-        if ctx.train and getattr(eng, "fwd_gen", 0) != ctx.gen:
-            # the activations live in the engine's per-(B, T) workspace, not in this autograd node
-            raise RuntimeError("backward through a forward whose saved activations were overwritten by a later training-mode forward "
-                               "of the same model: call backward before the next forward")
+        if ctx.train:
+            check_saved(eng, ctx.gen)
         g = eng.g
         B, O, T = dy.shape
-        ext = torch.zeros(B, T, g.Op, dtype=eng.tdtype, device=dy.device)
-        dyc = dy.contiguous().float()
-        if eng.grad_scale != 1.0:               # fp16 stack: its backward runs on loss-scaled gradients (engine.py: grad_scale)
-            dyc = dyc * eng.grad_scale
-        L.check(eng.lib.wae_to_btc(L.ptr(dyc), L.ptr(ext), B, O, T, g.Op, eng.dt, eng.stream()), "to_btc")
-        dc = BW.decoder_backward(eng, ctx.ids, None, None, ctx.gid, ctx.gvec, ext_dy=ext)
+        dc = BW.decoder_backward(eng, ctx.ids, None, None, ctx.gid, ctx.gvec, ext_dy=logits_grad_btc(eng, dy))
         dc_in = None
         if ctx.c_shape is not None:
             if ctx.c_is_up or not g.upsample_scales:
