@@ -357,7 +357,7 @@ typedef struct wae_ar_desc {
   int32_t L, R, Rp, G, Hp, S, O, Cc, Ccp, ktaps;
   int32_t mode;
   int32_t init_idx;
-  int32_t scalar_input; /* 0: wae_ar_generate / wae_ar_generate_coop; 1: wae_ar_generate_scalar[_mog] / wae_ar_generate_coop_scalar */
+  int32_t scalar_input; /* 0: wae_ar_generate / wae_ar_generate_coop; 1: wae_ar_generate_scalar[_mog] / wae_ar_generate_coop_scalar / the two *_scalar_list entries */
   float scale;          /* sqrt(1/L) */
   int32_t n_forced;     /* with inputs: steps t < n_forced consume inputs[t], later steps the fed-back output
                            (test_inputs shorter than T, wavenet.py:300-305); <= 0 or >= T: every step is forced */
@@ -519,6 +519,42 @@ int wae_ar_generate_coop_scalar(const wae_ar_desc* d, int32_t C, int32_t dist, c
                                 int32_t c_dtype, const float* inputs_f, const float* u_mix, const float* draws,
                                 float log_scale_min, int32_t clamp_log_scale, float* out_samples, float* out_params,
                                 uint64_t* msg, float* acc, int32_t* error, void* stream);
+/* Work lists of scalar-input utterances: the queue of wae_ar_generate_list / wae_ar_generate_coop_list (items, `next`, slots or teams,
+ * rings never zero-filled, longest first) with the first conv and the draw of the scalar entries (wavenet.py:284-285, 300-305, 325-333;
+ * mixture.py:118-156, 225-270).  dist as for wae_ar_generate_coop_scalar: 0 = mixture of logistics on u_mix and draws = u_log, O = 3M,
+ * log scale clamped to log_scale_min when clamp_log_scale != 0; 1 = mixture of Gaussians on draws = z and u_mix (NULL allowed when
+ * M == 1), O == 2 or 3M, log scale unclamped.  The per-step operands are packed item after item by item.off: inputs_f, draws and
+ * out_samples (total), u_mix (total, M), out_params one (O, T) block per item at float offset off * O, c_up (total, Ccp); zb holds one
+ * (L, 2Hp) row per value of item.row.  Both entries read d->mode.  mode 0: teacher-forced parameters, inputs_f forces every step of
+ * every item.  mode 2: sample; the first item.n_forced steps (clamped to [0, T]; 0 with inputs_f == NULL) consume inputs_f[off + t], the
+ * rest the fed-back sample; an item whose step 0 is not forced starts from the value 0 (wavenet.py:284-285).  item.init_idx is not read,
+ * nor are d->B, d->T, d->n_forced and d->init_idx.
+ * wae_ar_generate_scalar_list (csrc/ar_fwd.hip: ar_list_kernel over scalar items): n_slots workgroups, ring n_slots x ring_total; an
+ * item's samples and parameters are wae_ar_generate_scalar's / wae_ar_generate_scalar_mog's for that utterance alone, bit for bit (the
+ * same device function), whichever slot decodes it and in whatever order.
+ * wae_ar_generate_coop_scalar_list (csrc/ar_coop.hip: ar_coop_scalar_list_kernel, always the any-shape kernel): n_teams teams of C
+ * workgroups; ring (n_teams, C, ring_total), msg (n_teams, 2, C, NV), acc n_teams x wae_ar_coop_acc_floats(d), error >= 64 ints, the
+ * caller zeroes msg, acc, error and next; `total` is the sum of the items' T; error[0] != 0 afterwards: a wait timed out (the output is
+ * then invalid).  An item's results are wae_ar_generate_coop_scalar's for that utterance alone at the same C, bit for bit.
+ * Refused before any launch (WAE_EINVAL): a class-id decoder; a mode other than 0 / 2; dist outside {0, 1} or O not matching it; mode 2
+ * without its draws; u_mix without u_log or the reverse (dist 0); more than one Gaussian without u_mix; mode 0 without inputs_f;
+ * out_samples without draws; no output requested; t0 != 0; n_items < 1; n_slots < 1 / n_teams outside 1..8; NULL items or next; and for
+ * the cooperative entry C outside 1..32, R, S or O > 256, NULL msg, acc or error, (total + n_items + 1) * (L + 4) >= 2^31. */
+int wae_ar_generate_scalar_list(const wae_ar_desc* d, int32_t dist, int32_t n_items, int32_t n_slots, const wae_ar_item* items,
+                                int32_t* next, const int32_t* dilations, const int64_t* ring_off, float* ring, int64_t ring_total,
+                                const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes, const float* bias2,
+                                const float* zb, const float* first_tab, const float* first_bias, const void* w_head,
+                                const float* head_bias, const void* c_up, int32_t c_dtype, const float* inputs_f,
+                                const float* u_mix, const float* draws, float log_scale_min, int32_t clamp_log_scale,
+                                float* out_samples, float* out_params, void* stream);
+int wae_ar_generate_coop_scalar_list(const wae_ar_desc* d, int32_t C, int32_t dist, int32_t n_items, int32_t n_teams,
+                                     const wae_ar_item* items, int32_t* next, int64_t total, const int32_t* dilations,
+                                     const int64_t* ring_off, float* ring, int64_t ring_total, const void* w_layers,
+                                     int64_t layer_stride_bytes, int64_t w2_off_bytes, const float* bias2, const float* zb,
+                                     const float* first_tab, const float* first_bias, const void* w_head, const float* head_bias,
+                                     const void* c_up, int32_t c_dtype, const float* inputs_f, const float* u_mix,
+                                     const float* draws, float log_scale_min, int32_t clamp_log_scale, float* out_samples,
+                                     float* out_params, uint64_t* msg, float* acc, int32_t* error, void* stream);
 
 /* ---- backward data path of the gated stack: C[t][M] = sum_s W_s . X_s[t + shift_s] on time-major operands ----
  * (autograd of modules.py:115-163; see csrc/gemm_tm.hip).  mode 0: out (t, M) = acc.  mode 1 (residual):

@@ -17,7 +17,8 @@ options:
     --batch-decode           Read every pair of <syn_list> first and decode them all in one launch (WaeEngine.decode_list: one
                              utterance per CU, the next one as soon as a CU is free) instead of one after another.  The wavs
                              written are the same files (with --seed: byte for byte those of the loop on the one-CU kernel,
-                             WAE_AR_COOP=0).  Class-id ("mulaw-quantize") models; not with --stream-chunk.
+                             WAE_AR_COOP=0).  Scalar-input ("raw" / "mulaw") models go through WaeEngine.decode_list_scalar; with
+                             --batch-coop their wavs are those of the loop run with --coop-scalar.  Not with --stream-chunk.
 """
 import argparse
 import json
@@ -137,7 +138,8 @@ def read_features(args, src):
 
 
 def batch_decode(eng, args, pairs, sp2ind, out_dir):
-    """--batch-decode: the loop of main() with its decodes gathered into one WaeEngine.decode_list call.  Per pair, in the list's
+    """--batch-decode: the loop of main() with its decodes gathered into one WaeEngine.decode_list call (decode_list_scalar for a
+    scalar-input model: "raw" / "mulaw", whose loop under --batch-coop is the one run with --coop-scalar).  Per pair, in the list's
     order: the seed (if any), the encoder, the quantizer and the draws of all its samples -- the order in which the loop consumes
     the generator -- then one launch for all pairs, then the loop's post-processing and file names.  --batch-coop: that launch on
     cooperative teams (decode_list(coop=True), --batch-teams of them): the loop's bytes where the loop decodes on the cooperative path
@@ -156,12 +158,23 @@ def batch_decode(eng, args, pairs, sp2ind, out_dir):
             torch.manual_seed(args.seed)
         ct = torch.from_numpy(np.ascontiguousarray(c.T[None]).astype(np.float32)).to(device)
         quant, _, _ = eng.vq_forward(eng.encoder_forward(ct))
-        items.append(dict(c=quant[0].clone(), gid=sp2ind[tar], T=length, init_idx=int(args.initial_value),
-                          uniforms=torch.rand(1, length, device=device)))
+        if eng.g.scalar_input:
+            u_mix, draw = eng.scalar_draws(length)
+            items.append(dict(c=quant[0].clone(), gid=sp2ind[tar], T=length, u_mix=u_mix,
+                              **{"z" if eng.g.output_distribution == "Normal" else "u_log": draw}))
+        else:
+            items.append(dict(c=quant[0].clone(), gid=sp2ind[tar], T=length, init_idx=int(args.initial_value),
+                              uniforms=torch.rand(1, length, device=device)))
         names.append(f"{out_dir}{tar}_{fid}.wav")
     how = dict(coop=True, teams=args.batch_teams) if args.batch_coop else {}
-    for out, res in zip(names, eng.decode_list(items, mode="sample", **how)):
-        y = postprocess_indices(res["idx"].cpu().numpy(), hparams.quantize_channels, hparams.postprocess, hparams.global_gain_scale)
+    if eng.g.scalar_input:
+        results = eng.decode_list_scalar(items, mode="sample", log_scale_min=hparams.log_scale_min, **how)
+    else:
+        results = eng.decode_list(items, mode="sample", **how)
+    for out, res in zip(names, results):
+        # decoded_wave takes a batch of one utterance
+        y = postprocess_wave(decoded_wave({k: v[None] for k, v in res.items() if v is not None}), hparams.postprocess,
+                             hparams.global_gain_scale)
         wavfile.write(out, hparams.sample_rate, y)
         print("Finished! Check out {} for generated audio samples.".format(out), flush=True)
     return 0

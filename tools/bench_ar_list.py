@@ -2,7 +2,7 @@
 """Throughput of list decoding (WaeEngine.decode_list): hps/vqwae.json's decoder on a work list of unequal lengths.
 
 usage: bench_ar_list.py [--items N] [--dtypes bf16,fp32] [--slots cu[,2cu,N...]] [--teams N[,N...]] [--loop K] [--min-len 8000]
-                        [--max-len 64000]
+                        [--max-len 64000] [--scalar]
     --items N     clips in the list (default 512); lengths are drawn with numpy.random.default_rng(1234), uniform in
                   [--min-len, --max-len] samples, and rounded to whole latent frames (640 samples: the conditioning is upsampled per clip)
     --dtypes      storage types to run (default bf16,fp32)
@@ -11,6 +11,9 @@ usage: bench_ar_list.py [--items N] [--dtypes bf16,fp32] [--slots cu[,2cu,N...]]
                   skips the one-CU list
     --loop K      also decode the first K clips one after another with incremental_forward (what synthesis.py does without
                   --batch-decode, on whatever kernel WAE_AR_COOP selects) and print that aggregate rate; 0 (default) skips it
+    --scalar      the scalar-input decoder of tools/bench_ar.py --scalar instead (the same decoder with an O = 30 mixture-of-logistics
+                  head) through WaeEngine.decode_list_scalar, on both list forms; --loop then runs twice: on the one-CU kernel and on
+                  the cooperative kernel (ar_path(scalar_coop=True), what synthesis.py --coop-scalar selects)
 Prints, per run, the wall time of the whole decode_list call (packing the operands, upsampling, the launch, synchronised) and the
 aggregate kHz = sum of lengths / time, beside the efficiency the launch plan predicts (packing.ar_list_plan), and one JSON line."""
 import argparse
@@ -42,7 +45,9 @@ def main():
     ap.add_argument("--loop", type=int, default=0)
     ap.add_argument("--min-len", type=int, default=8000)
     ap.add_argument("--max-len", type=int, default=64000)
+    ap.add_argument("--scalar", action="store_true")
     args = ap.parse_args()
+    cfg = dict(CFG, O=30, scalar_input=True, output_distribution="Logistic") if args.scalar else CFG
     rng = np.random.default_rng(1234)
     lens = rng.integers(args.min_len, args.max_len + 1, args.items)
     lens = (np.maximum(1, np.rint(lens / HOP)).astype(np.int64) * HOP).tolist()
@@ -50,56 +55,66 @@ def main():
     slot_runs = [] if args.slots == "none" else [cus if s == "cu" else 2 * cus if s == "2cu" else int(s) for s in args.slots.split(",")]
     team_runs = [int(t) for t in args.teams.split(",") if t]
     gen = torch.Generator(device="cuda").manual_seed(1234)
-    items = [dict(T=T, c=torch.randn(64, T // HOP, device="cuda", generator=gen), gid=i % CFG["n_speakers"],
-                  uniforms=torch.rand(T, device="cuda", generator=gen)) for i, T in enumerate(lens)]
+    unit = lambda *shape: torch.rand(*shape, device="cuda", generator=gen) * (1 - 2e-5) + 1e-5  # noqa: E731
+    draws = (lambda T: dict(u_mix=unit(T, 10), u_log=unit(T))) if args.scalar else (lambda T: dict(uniforms=torch.rand(T, device="cuda", generator=gen)))
+    items = [dict(T=T, c=torch.randn(64, T // HOP, device="cuda", generator=gen), gid=i % CFG["n_speakers"], **draws(T))
+             for i, T in enumerate(lens)]
+    # one latent frame of an item: the warm-up lists
+    short = lambda it: dict({k: (v[:HOP] if k in ("uniforms", "u_mix", "u_log") else v) for k, v in it.items()}, T=HOP,  # noqa: E731
+                            c=it["c"][:, :1].contiguous())
+    what = "decode_list_scalar" if args.scalar else "decode_list"
     total = sum(lens)
     print(f"list: {len(lens)} clips, {total} samples, lengths {min(lens)} .. {max(lens)} (mean {total / len(lens):.0f}); {cus} CUs")
-    record = dict(items=len(lens), samples=total, cus=cus, runs=[])
-    sd = O.make_state_dict(dict(CFG), salt=7, with_encoder=False)
+    record = dict(items=len(lens), samples=total, cus=cus, scalar=args.scalar, runs=[])
+    sd = O.make_state_dict(dict(cfg), salt=7, with_encoder=False)
     for dtype in args.dtypes.split(","):
-        eng = WaeEngine(Geometry.from_cfg(CFG), dtype=dtype)
+        eng = WaeEngine(Geometry.from_cfg(cfg), dtype=dtype)
         eng.load_state_dict(sd)
+        decode = eng.decode_list_scalar if args.scalar else eng.decode_list
+        # what tells a real roll-out from a constant: the classes of clip 0, or the spread of its samples
+        alive = ((lambda out: f"sample std of clip 0 {float(out[0]['x'].std()):.3f}") if args.scalar
+                 else (lambda out: f"{int(torch.unique(out[0]['idx']).numel())} distinct classes in clip 0"))
         # warm-up: the kernels' code objects and the packed weights, on a list short enough not to matter
-        eng.decode_list([dict(it, T=HOP, c=it["c"][:, :1].contiguous(), uniforms=it["uniforms"][:HOP]) for it in items[:cus]])
+        decode([short(it) for it in items[:cus]])
         torch.cuda.synchronize()
         for slots in slot_runs:
             plan = ar_list_plan(lens, slots)
             t0 = time.perf_counter()
-            out = eng.decode_list(items, mode="sample", slots=slots)
+            out = decode(items, mode="sample", slots=slots)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            classes = int(torch.unique(out[0]["idx"]).numel())
-            print(f"decode_list {dtype} slots={plan.slots}: {dt:.2f} s -> {total / dt / 1e3:.1f} kHz aggregate; plan efficiency "
+            print(f"{what} {dtype} slots={plan.slots}: {dt:.2f} s -> {total / dt / 1e3:.1f} kHz aggregate; plan efficiency "
                   f"{plan.efficiency:.3f} (busiest slot {plan.makespan} samples -> {plan.makespan / dt / 1e3:.2f} kHz per slot); "
-                  f"{classes} distinct classes in clip 0", flush=True)
-            record["runs"].append(dict(kind="decode_list", dtype=dtype, slots=plan.slots, seconds=dt, khz=total / dt / 1e3,
+                  f"{alive(out)}", flush=True)
+            record["runs"].append(dict(kind=what, dtype=dtype, slots=plan.slots, seconds=dt, khz=total / dt / 1e3,
                                        plan_efficiency=plan.efficiency, makespan=plan.makespan))
             del out
         if team_runs:
-            eng.decode_list([dict(it, T=HOP, c=it["c"][:, :1].contiguous(), uniforms=it["uniforms"][:HOP]) for it in items[:8]], coop=True)
+            decode([short(it) for it in items[:8]], coop=True)
             torch.cuda.synchronize()
         for teams in team_runs:
             plan = ar_list_plan(lens, max(1, min(teams, 8)))
             t0 = time.perf_counter()
-            out = eng.decode_list(items, mode="sample", coop=True, teams=teams)
+            out = decode(items, mode="sample", coop=True, teams=teams)
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
-            classes = int(torch.unique(out[0]["idx"]).numel())
-            print(f"decode_list(coop=True) {dtype} teams={plan.slots}: {dt:.2f} s -> {total / dt / 1e3:.1f} kHz aggregate; plan efficiency "
+            print(f"{what}(coop=True) {dtype} teams={plan.slots}: {dt:.2f} s -> {total / dt / 1e3:.1f} kHz aggregate; plan efficiency "
                   f"{plan.efficiency:.3f} (busiest team {plan.makespan} samples -> {plan.makespan / dt / 1e3:.2f} kHz per team); "
-                  f"{classes} distinct classes in clip 0", flush=True)
-            record["runs"].append(dict(kind="decode_list_coop", dtype=dtype, teams=plan.slots, seconds=dt, khz=total / dt / 1e3,
+                  f"{alive(out)}", flush=True)
+            record["runs"].append(dict(kind=what + "_coop", dtype=dtype, teams=plan.slots, seconds=dt, khz=total / dt / 1e3,
                                        plan_efficiency=plan.efficiency, makespan=plan.makespan))
             del out
-        if args.loop > 0:
+        for scalar_coop in ((False, True) if args.scalar else (False,)) if args.loop > 0 else ():
+            eng.ar_path(scalar_coop=scalar_coop)      # (no effect on class-id decoders)
             sub = items[:args.loop]
             first = sub[0]
             eng.incremental_forward(first["c"][None, :, :1].contiguous(), torch.tensor([0], device="cuda"), HOP, mode="sample")
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for it in sub:
+                eng._ar_profile = None
                 eng.incremental_forward(it["c"][None], torch.tensor([it["gid"]], device="cuda"), it["T"], mode="sample",
-                                        uniforms=it["uniforms"][None])
+                                        **{k: it[k][None] for k in ("uniforms", "u_mix", "u_log") if k in it})
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
             n = sum(it["T"] for it in sub)

@@ -91,7 +91,8 @@ class HeadDesc(ctypes.Structure):
 
 # the 16 arguments every wae_ar_generate* entry starts with: the descriptor, (dilations, ring_off, ring, ring_total, w_layers,
 # layer_stride_bytes, w2_off_bytes), (bias2, zb, first_tab, first_bias, w_head, head_bias, c_up), c_dtype; the cooperative entries
-# put C (and dist) behind the descriptor, the list entries (n_items, n_slots, items, next) / (C, n_items, n_teams, items, next, total)
+# put C (and dist) behind the descriptor, the list entries (n_items, n_slots, items, next) / (C, n_items, n_teams, items, next, total),
+# the scalar list entries dist in front of n_items
 _AR = [ctypes.POINTER(ArDesc), c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64] + [c_vp] * 7 + [c_i32]
 
 # name -> (restype, argtypes); mirrors include/wae.h one to one
@@ -161,6 +162,9 @@ SIGNATURES = {
     "wae_ar_generate_coop_fused": (c_i32, _AR[:1] + [c_i32] + _AR[1:] + [c_vp] * 9),
     "wae_ar_generate_coop_list": (c_i32, _AR[:1] + [c_i32, c_i32, c_i32, c_vp, c_vp, c_i64] + _AR[1:] + [c_vp] * 8),
     "wae_ar_generate_coop_scalar": (c_i32, _AR[:1] + [c_i32, c_i32] + _AR[1:] + [c_vp] * 3 + [c_f32, c_i32] + [c_vp] * 6),
+    "wae_ar_generate_scalar_list": (c_i32, _AR[:1] + [c_i32, c_i32, c_i32, c_vp, c_vp] + _AR[1:] + [c_vp] * 3 + [c_f32, c_i32] + [c_vp] * 3),
+    "wae_ar_generate_coop_scalar_list": (c_i32, _AR[:1] + [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64] + _AR[1:] + [c_vp] * 3
+                                         + [c_f32, c_i32] + [c_vp] * 6),
     "wae_ce_logits_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "wae_ce_logits_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "wae_weighted_mean": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),

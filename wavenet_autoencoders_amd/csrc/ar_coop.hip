@@ -445,10 +445,11 @@ __device__ __forceinline__ void arc_draw(const ArcArgs& p, float* lbuf, float* p
 //      mixture.py:118-156; sample_from_mix_gaussian, mixture.py:225-270 -- the arithmetic of dmol_sample_kernel / mog_sample_kernel,
 //      csrc/loss.hip), on every member: identical code on identical data, so every member feeds back the same bits.  The step's draws
 //      were requested at the top of the sample and wait in registers: um = u_mix[b, t, tid] (tid < M), ud = u_log[b, t] / z[b, t] and
-//      forced = inputs_f[b, t + 1] on thread 0.  The Gumbel scores are formed by M threads (each is one value's own expression), the
-//      first-maximum scan and the draw by thread 0, as the serial loop of csrc/ar_fwd.hip.
-__device__ __forceinline__ void arc_draw_scalar(const ArcArgs& p, const float* lbuf, float* psum, float* fcur, int b, int m, int t,
-                                                float um, float ud, float forced) {
+//      forced = inputs_f[b, t + 1] on thread 0 (ubase = the utterance's first step in the per-step operands, nforced its forced prefix, as
+//      for arc_draw: b * T and n_forced, or the item's in the list form).  The Gumbel scores are formed by M threads (each is one value's
+//      own expression), the first-maximum scan and the draw by thread 0, as the serial loop of csrc/ar_fwd.hip.
+__device__ __forceinline__ void arc_draw_scalar(const ArcArgs& p, const float* lbuf, float* psum, float* fcur, int64_t ubase, int nforced,
+                                                int m, int t, float um, float ud, float forced) {
   const int tid = threadIdx.x;
   const bool sampled = p.dist == 0 ? p.u_mix != nullptr : p.z != nullptr;
   const int M = p.O == 2 ? 1 : p.O / 3;
@@ -479,9 +480,9 @@ __device__ __forceinline__ void arc_draw_scalar(const ArcArgs& p, const float* l
         const int mu0 = p.O == 2 ? 0 : M, ls0 = p.O == 2 ? 1 : 2 * M;
         xs = fminf(fmaxf(lbuf[mu0 + arg] + expf(lbuf[ls0 + arg]) * ud, -1.f), 1.f);
       }
-      if (m == 0 && p.out_samples) p.out_samples[(int64_t)b * p.T + t] = xs;
+      if (m == 0 && p.out_samples) p.out_samples[ubase + t] = xs;
     }
-    fcur[0] = (p.inputs_f && t + 1 < p.n_forced) ? forced : xs;
+    fcur[0] = (p.inputs_f && t + 1 < nforced) ? forced : xs;
   }
   arc_barrier();
 }
@@ -490,11 +491,11 @@ __device__ __forceinline__ int arc_uni(const int* q) { return __builtin_amdgcn_r
 
 // SCALAR: the scalar-input form (wae_ar_generate_coop_scalar).  The network is the same; the current input is a float in LDS, the first
 // conv is w * x + b (wavenet.py:311 on one input channel) and the draw is arc_draw_scalar.  The class-id instantiations are untouched.
-// LIST: the work-list form (wae_ar_generate_coop_list; class ids only).  What is set up once per clip runs once per ITEM inside the item
-// loop below; what does not depend on the clip (placement verdict, per-thread constants, the head's packets) stays outside it.
+// LIST: the work-list form (wae_ar_generate_coop_list; with SCALAR wae_ar_generate_coop_scalar_list).  What is set up once per clip runs
+// once per ITEM inside the item loop below; what does not depend on the clip (placement verdict, per-thread constants, the head's packets,
+// the first conv's weight column) stays outside it.
 template <typename E, bool SCALAR, bool LIST>
 __device__ __forceinline__ void ar_coop_body(const ArcArgs& p) {
-  static_assert(!(LIST && SCALAR), "the list form decodes class ids");
   extern __shared__ __attribute__((aligned(16))) float sm[];
   constexpr int EPL = ET<E>::EPL;
   constexpr int NWV = ARC_THREADS / 64;
@@ -745,6 +746,10 @@ __device__ __forceinline__ void ar_coop_body(const ArcArgs& p) {
     // (both its polling pass and its re-read).  xuse / suse / huse / yuse run on across items as well: every member of a team decodes
     // the same items with the same step counts, so it performs the same exchanges in the same order and the argument of arc_allgather /
     // arc_allsum holds at the boundary unchanged (the host bounds the total so that no 32-bit sequence number wraps).
+    // SCALAR items change none of this: the rings, their writes and the `tq >= back` test are the network's, not the input's; the scalar
+    // draw adds workgroup barriers and loads of the caller's draws, no exchange and no ring access; a step's draws (d_um, d_ud, d_forced)
+    // are requested and consumed inside that step, so no register carries a value of the finished item over the boundary; and the
+    // out_samples / out_params stores of member 0 are drained with the ring stores by the wait below.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     ++seq;
     unsigned long long* bank = msg_b + (int64_t)(seq & 1) * C * p.NV;
@@ -764,7 +769,9 @@ __device__ __forceinline__ void ar_coop_body(const ArcArgs& p) {
     if (w.T <= 0) continue;           // skipped by the whole team
     // as ar_list_kernel (csrc/ar_fwd.hip): mode 0 is teacher-forced throughout; a start class outside the table would read beyond first_tab
     T = w.T; base = w.off;
-    nforced = !p.inputs ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
+    // (a scalar item takes its forced prefix from inputs_f and has no start class: item_reset starts it from 0)
+    const bool forced_in = SCALAR ? p.inputs_f != nullptr : p.inputs != nullptr;
+    nforced = !forced_in ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
     init = min(max(w.init_idx, 0), p.O - 1);
     zb_b = p.zb + (int64_t)w.row * p.L * 2 * p.Hp;
     item_reset();
@@ -941,7 +948,7 @@ __device__ __forceinline__ void ar_coop_body(const ArcArgs& p) {
         return;
     }
     ARC_TICK(5);
-    if constexpr (SCALAR) arc_draw_scalar(p, lbuf, psum, fcur, b, m, t, d_um, d_ud, d_forced);
+    if constexpr (SCALAR) arc_draw_scalar(p, lbuf, psum, fcur, base, nforced, m, t, d_um, d_ud, d_forced);
     else arc_draw(p, lbuf, psum, ibuf, base, nforced, m, t);
     ARC_TICK(6);
   }
@@ -1912,14 +1919,22 @@ static size_t arc_generic_lds(const wae_ar_desc* d, int32_t C) {
                                   ru(d->O, 4) + ARC_THREADS + ru(ar_split(d, C).NV, 4) + 8 + 3 * d->L + 64);
 }
 
-// the any-shape kernels: class ids, a scalar draw, or the work list of class ids
-enum ArcForm { ARC_CLASS_IDS, ARC_SCALAR, ARC_LIST };
+// the work list of scalar items on the any-shape body (wae_ar_generate_coop_scalar_list); defined and instantiated behind every other
+// kernel of this file
+template <typename E>
+__global__ void __launch_bounds__(ARC_THREADS) ar_coop_scalar_list_kernel(ArcArgs p) {
+  ar_coop_body<E, true, true>(p);
+}
+
+// the any-shape kernels: class ids, a scalar draw, the work list of class ids, or the work list of scalar draws
+enum ArcForm { ARC_CLASS_IDS, ARC_SCALAR, ARC_LIST, ARC_SCALAR_LIST };
 template <ArcForm F>
 static int launch_arc_generic(const ArcArgs& a, size_t lds, hipStream_t st, const char* who) {
   const dim3 grid(8 * a.C), block(ARC_THREADS);
   return ar_by_dtype(a.dtype, [&](auto e) {
     using E = typename decltype(e)::type;
-    if constexpr (F == ARC_LIST) AR_LAUNCH(ar_coop_list_kernel<E>, grid, block, lds, st, a, who);
+    if constexpr (F == ARC_SCALAR_LIST) AR_LAUNCH(ar_coop_scalar_list_kernel<E>, grid, block, lds, st, a, who);
+    else if constexpr (F == ARC_LIST) AR_LAUNCH(ar_coop_list_kernel<E>, grid, block, lds, st, a, who);
     else AR_LAUNCH((ar_coop_kernel<E, F == ARC_SCALAR>), grid, block, lds, st, a, who);
   });
 }
@@ -2001,19 +2016,30 @@ extern "C" int wae_ar_generate_coop_list(const wae_ar_desc* d, int32_t C, int32_
   const ArNet net = AR_NET_OF_ARGS;
   const ArcExchange x = {msg, acc, error};
   AR_TRY(ar_check_net(who, d, net, out_idx != nullptr, false, ARC_THREADS));
-  AR_TRY(ar_check_class_ids(who, d, inputs, uniforms, out_logits, 2, true, "wae_ar_generate_coop_scalar"));
+  AR_TRY(ar_check_class_ids(who, d, inputs, uniforms, out_logits, 2, true, "wae_ar_generate_coop_scalar_list"));
   AR_TRY(ar_check_queue(who, items, next, n_items, "n_teams", n_teams, 8));
   AR_TRY(ar_check_t0(who, d, inputs, true));
-  // the exchange sequence numbers run on across a team's items: at most L per step (the x' sums), one per step for the skip sum and each
-  // of the head's gathers, two messages per item taken or refused -- all below (total + n_items + 1) * (L + 4), which must fit 31 bits
-  AR_REQUIRE(total >= 0 && (total + n_items + 1) <= (((int64_t)1 << 31) - 1) / (d->L + 4),
-             "%lld steps in %d items on %d layers: the exchange sequence numbers would not fit 31 bits", (long long)total, n_items, d->L);
+  AR_TRY(ar_check_sequence(who, d, total, n_items));
   AR_TRY(ar_check_split(who, d, C, ARC_CMAX, ARC_THREADS, ring_total, x.ok(), nullptr));
   ArcArgs a = arc_common_args(d, C, net, x);
   a.B = n_teams; a.T = 0; a.t0 = 0; a.n_forced = 0; a.init_idx = 0;      // per item
   a.inputs = inputs; a.uniforms = uniforms; a.out_idx = out_idx; a.out_logits = out_logits;
   a.items = items; a.next = next; a.n_items = n_items;
   return arc_dispatch(d, C, a, nullptr, true, as_stream(stream), who);
+}
+
+// the operands of a scalar draw as the kernels read them: u_mix only where the decode samples, the draws under the name of their kind
+static void arc_fill_draw(ArcArgs& a, int dist, const ArDraw& w, float log_scale_min, int clamp_log_scale) {
+  const bool sampled = dist == 0 ? (w.u_mix && w.draws) : w.draws != nullptr;
+  a.inputs_f = w.inputs_f;
+  a.dist = dist;
+  a.u_mix = sampled ? w.u_mix : nullptr;
+  a.u_log = dist == 0 && sampled ? w.draws : nullptr;
+  a.z = dist == 1 ? w.draws : nullptr;
+  a.log_scale_min = log_scale_min;
+  a.clamp_log_scale = dist == 0 ? clamp_log_scale : 0;
+  a.out_samples = w.out_samples;
+  a.out_params = w.out_params;
 }
 
 // Scalar-input decoders on the any-shape cooperative kernel (ar_coop_kernel<E, true>): the network, the split and the exchanges of
@@ -2028,21 +2054,41 @@ extern "C" int wae_ar_generate_coop_scalar(const wae_ar_desc* d, int32_t C, int3
   const char* who = "ar_generate_coop_scalar";
   const ArNet net = AR_NET_OF_ARGS;
   const ArcExchange x = {msg, acc, error};
+  const ArDraw w = {inputs_f, u_mix, draws, out_samples, out_params};
   AR_TRY(ar_check_net(who, d, net, true, true, ARC_THREADS));
-  AR_TRY(ar_check_mixture(who, d, dist, {inputs_f, u_mix, draws, out_samples, out_params}, true));
+  AR_TRY(ar_check_mixture(who, d, dist, w, true));
   AR_TRY(ar_check_t0(who, d, inputs_f, false));
   AR_TRY(ar_check_split(who, d, C, ARC_CMAX, ARC_THREADS, ring_total, x.ok(), "wae_ar_generate_scalar"));
-  const bool sampled = dist == 0 ? (u_mix && draws) : draws != nullptr;
   ArcArgs a = arc_common_args(d, C, net, x);
-  a.inputs_f = inputs_f;
+  arc_fill_draw(a, dist, w, log_scale_min, clamp_log_scale);
   a.n_forced = ar_n_forced(d, inputs_f);
-  a.dist = dist;
-  a.u_mix = sampled ? u_mix : nullptr;
-  a.u_log = dist == 0 && sampled ? draws : nullptr;
-  a.z = dist == 1 ? draws : nullptr;
-  a.log_scale_min = log_scale_min;
-  a.clamp_log_scale = dist == 0 ? clamp_log_scale : 0;
-  a.out_samples = out_samples;
-  a.out_params = out_params;
   return launch_arc_generic<ARC_SCALAR>(a, arc_generic_lds(d, C), as_stream(stream), who);
+}
+
+// A work list of scalar-input utterances on cooperative teams: the queue, teams and exchanges of wae_ar_generate_coop_list, the network
+// form and the draw of wae_ar_generate_coop_scalar (always the any-shape body: ar_coop_body<E, true, true>).
+extern "C" int wae_ar_generate_coop_scalar_list(const wae_ar_desc* d, int32_t C, int32_t dist, int32_t n_items, int32_t n_teams,
+                                                const wae_ar_item* items, int32_t* next, int64_t total, const int32_t* dilations,
+                                                const int64_t* ring_off, float* ring, int64_t ring_total, const void* w_layers,
+                                                int64_t layer_stride_bytes, int64_t w2_off_bytes, const float* bias2, const float* zb,
+                                                const float* first_tab, const float* first_bias, const void* w_head,
+                                                const float* head_bias, const void* c_up, int32_t c_dtype, const float* inputs_f,
+                                                const float* u_mix, const float* draws, float log_scale_min, int32_t clamp_log_scale,
+                                                float* out_samples, float* out_params, uint64_t* msg, float* acc, int32_t* error,
+                                                void* stream) {
+  const char* who = "ar_generate_coop_scalar_list";
+  const ArNet net = AR_NET_OF_ARGS;
+  const ArcExchange x = {msg, acc, error};
+  const ArDraw w = {inputs_f, u_mix, draws, out_samples, out_params};
+  AR_TRY(ar_check_net(who, d, net, true, false, ARC_THREADS));
+  AR_TRY(ar_check_mixture(who, d, dist, w, true, true));
+  AR_TRY(ar_check_queue(who, items, next, n_items, "n_teams", n_teams, 8));
+  AR_TRY(ar_check_t0(who, d, inputs_f, true));
+  AR_TRY(ar_check_sequence(who, d, total, n_items));
+  AR_TRY(ar_check_split(who, d, C, ARC_CMAX, ARC_THREADS, ring_total, x.ok(), nullptr));
+  ArcArgs a = arc_common_args(d, C, net, x);
+  arc_fill_draw(a, dist, w, log_scale_min, clamp_log_scale);
+  a.B = n_teams; a.T = 0; a.t0 = 0; a.n_forced = 0; a.init_idx = 0;      // per item
+  a.items = items; a.next = next; a.n_items = n_items;
+  return launch_arc_generic<ARC_SCALAR_LIST>(a, arc_generic_lds(d, C), as_stream(stream), who);
 }

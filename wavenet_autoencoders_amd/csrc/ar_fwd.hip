@@ -360,9 +360,10 @@ __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
   ar_decode<E>(p, ut, sm);
 }
 
-// wae_ar_generate_list: n_slots persistent workgroups empty a queue of utterances of any lengths.  Thread 0 takes the next item index
-// with one returning atomic add on the caller-zeroed counter and hands it to the workgroup through LDS; the workgroup decodes that
-// item to its end in its own ring slot (blockIdx.x) and comes back for the next.  No workgroup ever waits for another.
+// wae_ar_generate_list / wae_ar_generate_scalar_list: n_slots persistent workgroups empty a queue of utterances of any lengths.
+// Thread 0 takes the next item index with one returning atomic add on the caller-zeroed counter and hands it to the workgroup through
+// LDS; the workgroup decodes that item to its end in its own ring slot (blockIdx.x) and comes back for the next.  No workgroup ever
+// waits for another.
 struct ArListArgs {
   ArArgs a;
   const wae_ar_item* items;
@@ -384,9 +385,11 @@ __global__ void __launch_bounds__(AR_THREADS) ar_list_kernel(ArListArgs q) {
     if (it >= q.n_items) return;   // the same word for every thread: the workgroup leaves together
     const wae_ar_item w = q.items[it];
     if (w.T > 0) {
-      // mode 0 is teacher-forced throughout; a start class outside the table would read beyond first_tab
-      const int nf = !p.inputs ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
-      const ArUtt ut = {ring, p.zb + (int64_t)w.row * p.L * 2 * p.Hp, w.off, w.T, nf, min(max(w.init_idx, 0), p.O - 1)};
+      // mode 0 is teacher-forced throughout; a start class outside the table would read beyond first_tab.  A scalar item
+      // (wae_ar_generate_scalar_list) takes its forced prefix from inputs_f and has no start class: its start value is 0
+      const bool forced = p.scalar ? p.inputs_f != nullptr : p.inputs != nullptr;
+      const int nf = !forced ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
+      const ArUtt ut = {ring, p.zb + (int64_t)w.row * p.L * 2 * p.Hp, w.off, w.T, nf, p.scalar ? 0 : min(max(w.init_idx, 0), p.O - 1)};
       ar_decode<E>(p, ut, sm);
     }
     __syncthreads();               // every thread has read the word before thread 0 writes the next
@@ -395,10 +398,11 @@ __global__ void __launch_bounds__(AR_THREADS) ar_list_kernel(ArListArgs q) {
 
 #include "ar_host.hpp"
 
-struct ArList {   // wae_ar_generate_list's own arguments
+struct ArList {   // the list entries' own arguments (who: the entry's name)
   const wae_ar_item* items;
   int32_t* next;
   int n_items, n_slots;
+  const char* who;
 };
 
 // The operands of one form of the decode; whatever a form does not have stays null / zero.  Class ids: inputs, uniforms, out_idx, and
@@ -433,7 +437,7 @@ static int ar_launch(const wae_ar_desc* d, const ArNet& net, const ArOps& o, voi
     // the queue word sits behind ar_decode's carve; per-utterance B, T, n_forced and init_idx come from the items
     const ArListArgs q = {a, list->items, list->next, list->n_items, (int)(lds / sizeof(float))};
     return ar_by_dtype(d->dtype, [&](auto e) {
-      AR_LAUNCH(ar_list_kernel<typename decltype(e)::type>, dim3(list->n_slots), dim3(AR_THREADS), lds + 16, st, q, "ar_generate_list");
+      AR_LAUNCH(ar_list_kernel<typename decltype(e)::type>, dim3(list->n_slots), dim3(AR_THREADS), lds + 16, st, q, list->who);
     });
   }
   return ar_by_dtype(d->dtype, [&](auto e) {
@@ -468,11 +472,11 @@ extern "C" int wae_ar_generate_list(const wae_ar_desc* d, int32_t n_items, int32
   const ArNet net = AR_NET_OF_ARGS;
   AR_TRY(ar_check_net(who, d, net, out_idx != nullptr, false, 0));
   AR_TRY(ar_check_queue(who, items, next, n_items, "n_slots", n_slots, 0));
-  AR_TRY(ar_check_class_ids(who, d, inputs, uniforms, out_logits, 2, true, "wae_ar_generate_scalar"));
+  AR_TRY(ar_check_class_ids(who, d, inputs, uniforms, out_logits, 2, true, "wae_ar_generate_scalar_list"));
   AR_TRY(ar_check_t0(who, d, inputs, true));
   ArOps o = {};
   o.inputs = inputs; o.uniforms = uniforms; o.out_idx = out_idx; o.out_logits = out_logits; o.log_scale_min = -7.0f;
-  const ArList list = {items, next, n_items, n_slots};
+  const ArList list = {items, next, n_items, n_slots, who};
   return ar_launch(d, net, o, stream, &list);
 }
 
@@ -506,4 +510,29 @@ extern "C" int wae_ar_generate_scalar_mog(const wae_ar_desc* d, const int32_t* d
                                           float* out_samples, float* out_params, void* stream) {
   return ar_generate_scalar("ar_generate_scalar_mog", d, AR_NET_OF_ARGS, 1, {inputs_f, u_mix, z, out_samples, out_params}, log_scale_min, 0,
                             stream);
+}
+
+// A work list of scalar-input utterances on the one-CU kernel: ar_list_kernel over scalar items (the same ar_decode as ar_kernel, so an
+// item is bit for bit its wae_ar_generate_scalar / _scalar_mog decode).  The entry reads wae_ar_desc.mode: 0 forces every step of every
+// item from inputs_f, 2 samples behind item.n_forced forced steps.
+extern "C" int wae_ar_generate_scalar_list(const wae_ar_desc* d, int32_t dist, int32_t n_items, int32_t n_slots, const wae_ar_item* items,
+                                           int32_t* next, const int32_t* dilations, const int64_t* ring_off, float* ring,
+                                           int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
+                                           const float* bias2, const float* zb, const float* first_tab, const float* first_bias,
+                                           const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
+                                           const float* inputs_f, const float* u_mix, const float* draws, float log_scale_min,
+                                           int32_t clamp_log_scale, float* out_samples, float* out_params, void* stream) {
+  const char* who = "ar_generate_scalar_list";
+  const ArNet net = AR_NET_OF_ARGS;
+  const ArDraw w = {inputs_f, u_mix, draws, out_samples, out_params};
+  AR_TRY(ar_check_net(who, d, net, true, false, 0));
+  AR_TRY(ar_check_mixture(who, d, dist, w, true, true));
+  AR_TRY(ar_check_queue(who, items, next, n_items, "n_slots", n_slots, 0));
+  AR_TRY(ar_check_t0(who, d, inputs_f, true));
+  const bool sampled = dist == 0 ? (u_mix && draws) : draws != nullptr;
+  ArOps o = {};
+  o.out_logits = out_params; o.inputs_f = inputs_f; o.u_mix = sampled ? u_mix : nullptr; (dist == 0 ? o.u_log : o.z) = draws;
+  o.out_f = out_samples; o.log_scale_min = log_scale_min; o.clamp_log_scale = dist == 0 ? clamp_log_scale : 0; o.dist = dist;
+  const ArList list = {items, next, n_items, n_slots, who};
+  return ar_launch(d, net, o, stream, &list);
 }

@@ -86,10 +86,12 @@ static int ar_check_class_ids(const char* who, const wae_ar_desc* d, const int32
 
 // The operands of a scalar draw.  dist 0: mixture of logistics (u_mix and draws = u_log, together); dist 1: mixture of Gaussians (draws =
 // z; u_mix where there is more than one).  moded: the entry reads wae_ar_desc.mode (0 teacher-forced parameters, 2 sample); the one-CU
-// entries do not: there a decode samples where it has its draws and is teacher-forced throughout where it has none.
+// entries do not: there a decode samples where it has its draws and is teacher-forced throughout where it has none.  list: a work list
+// (always moded; the forced prefix is per item, so mode 0 asks for inputs_f only, and d->T / d->n_forced are not read).
 struct ArDraw { const float *inputs_f, *u_mix, *draws; float *out_samples, *out_params; };
-static int ar_check_mixture(const char* who, const wae_ar_desc* d, int dist, const ArDraw& w, bool moded) {
-  AR_REQUIRE(d->scalar_input, "needs a scalar-input decoder (class ids go through wae_ar_generate / wae_ar_generate_coop)");
+static int ar_check_mixture(const char* who, const wae_ar_desc* d, int dist, const ArDraw& w, bool moded, bool list = false) {
+  AR_REQUIRE(d->scalar_input, "needs a scalar-input decoder (class ids go through %s)",
+             list ? "wae_ar_generate_list / wae_ar_generate_coop_list" : "wae_ar_generate / wae_ar_generate_coop");
   AR_REQUIRE(dist == 0 || dist == 1, "dist must be 0 (mixture of logistics) or 1 (mixture of Gaussians)");
   AR_REQUIRE(dist != 0 || (d->O > 0 && d->O % 3 == 0), "the mixture of logistics has 3M output channels (got %d)", d->O);
   AR_REQUIRE(dist != 1 || d->O == 2 || (d->O > 0 && d->O % 3 == 0), "the mixture of Gaussians has 2 or 3M output channels (got %d)", d->O);
@@ -99,7 +101,8 @@ static int ar_check_mixture(const char* who, const wae_ar_desc* d, int dist, con
   AR_REQUIRE(dist != 0 || !w.u_mix == !w.draws, "u_mix and u_log come together");
   AR_REQUIRE(!moded || d->mode != 2 || sampled, "sample mode needs its draws (%s)", names);
   AR_REQUIRE(dist != 1 || !sampled || d->O <= 3 || w.u_mix, "%d mixtures need the uniforms u_mix", d->O / 3);
-  if (moded) AR_REQUIRE(d->mode != 0 || ar_forced_all(d, w.inputs_f), "mode 0 needs teacher-forced inputs for every step");
+  if (list) AR_REQUIRE(d->mode != 0 || w.inputs_f, "mode 0 needs teacher-forced inputs for every step");
+  else if (moded) AR_REQUIRE(d->mode != 0 || ar_forced_all(d, w.inputs_f), "mode 0 needs teacher-forced inputs for every step");
   else AR_REQUIRE(sampled || ar_forced_all(d, w.inputs_f), "needs teacher-forced inputs for every step or its draws (%s)", names);
   AR_REQUIRE(!w.out_samples || sampled, "samples need the draws");
   AR_REQUIRE(w.out_samples || w.out_params, "no output requested");
@@ -137,6 +140,15 @@ static int ar_check_split(const char* who, const wae_ar_desc* d, int C, int cmax
   const ArSplit s = ar_split(d, C);
   AR_REQUIRE(2 * s.hc <= threads && s.sc <= threads, "too few workgroups for G=%d, S=%d", d->G, d->S);
   AR_REQUIRE(ring_total < (int64_t)1 << 31, "ring_total %lld does not fit 32-bit offsets", (long long)ring_total);
+  return WAE_OK;
+}
+
+// The exchange sequence numbers of a work list on cooperative teams run on across a team's items: at most L per step (the x' sums), one
+// per step for the skip sum and each of the head's gathers, two messages per item taken or refused -- all below
+// (total + n_items + 1) * (L + 4), which must fit 31 bits.  (A scalar draw adds workgroup barriers, not exchanges.)
+static int ar_check_sequence(const char* who, const wae_ar_desc* d, int64_t total, int n_items) {
+  AR_REQUIRE(total >= 0 && (total + n_items + 1) <= (((int64_t)1 << 31) - 1) / (d->L + 4),
+             "%lld steps in %d items on %d layers: the exchange sequence numbers would not fit 31 bits", (long long)total, n_items, d->L);
   return WAE_OK;
 }
 

@@ -954,6 +954,75 @@ class WaeEngine:
                                        int(g.n_speakers or 0), L.ptr(self.err), self.stream()), "gproj")
         return zb
 
+    # ---- what decode_list and decode_list_scalar set up the same way
+    def _ar_list_plan(self, who, items, coop, slots, teams):
+        """The launch plan of a work list -> (Ts, plan, offsets, gids): `slots` workgroups, or `teams` teams when coop (clamped to 1..8;
+        the plan clamps either to the item count), longest first (packing.ar_list_plan); every item has a gid or none has; every item
+        has its conditioning where the decoder takes any."""
+        g = self.g
+        Ts = [int(it["T"]) for it in items]
+        if coop:
+            slots = max(1, min(8 if teams is None else int(teams), 8))
+        elif slots is None:
+            slots = torch.cuda.get_device_properties(self.device).multi_processor_count
+        plan = P.ar_list_plan(Ts, slots)
+        gids = [it.get("gid") for it in items]
+        if any(x is None for x in gids) and not all(x is None for x in gids):
+            raise ValueError(f"{who}: give every item a gid, or none")
+        for i, it in enumerate(items):
+            if g.Ccp and it.get("c") is None:
+                raise ValueError(f"{who}: item {i} has no conditioning c, the decoder has {g.Cc} conditioning channels")
+        return Ts, plan, [int(o) for o in plan.offsets], gids
+
+    def _ar_list_forced(self, forced, nfs, off, total, dtype):
+        """The items' forced prefixes packed by their offsets (zeros behind them), or None where no item has one."""
+        if all(f is None for f in forced):
+            return None
+        inputs = torch.zeros(total, dtype=dtype, device=self.device)
+        for i, f in enumerate(forced):
+            if f is not None:
+                inputs[off[i]:off[i] + nfs[i]] = f
+        return inputs
+
+    def _ar_list_cond(self, items, Ts, off, total, c_is_upsampled):
+        """c_up (total, Ccp): every item's conditioning rows at its offset (one utterance of batch 1 each), or None without conditioning."""
+        g = self.g
+        if not g.Ccp:
+            return None
+        c_up = torch.zeros(total, g.Ccp, dtype=self.tdtype, device=self.device)
+        for i, it in enumerate(items):
+            c = torch.as_tensor(it["c"]).to(self.device, torch.float32)
+            c = (c if c.dim() == 3 else c[None]).contiguous()
+            self._ar_cond_rows(c, c_up[off[i]:off[i] + Ts[i]].view(1, Ts[i], g.Ccp), c_is_upsampled, f"item {i}: ")
+        return c_up
+
+    def _ar_list_speakers(self, gids):
+        """(gid32, zb): one speaker row per item, in the caller's order (item.row = the caller's index)."""
+        gid32 = None
+        if gids[0] is not None:
+            gid32 = torch.tensor([int(torch.as_tensor(x).reshape(-1)[0]) for x in gids], dtype=torch.int32, device=self.device)
+        return gid32, self._ar_speaker_rows(len(gids), gid32)
+
+    def _ar_list_records(self, plan, off, Ts, nfs, inits):
+        """(items, next) on the device: the wae_ar_item records in launch order (longest first; row = the caller's index) and the zeroed
+        queue counter."""
+        rec = np.zeros(len(Ts), dtype=np.dtype([("off", "<i8"), ("T", "<i4"), ("n_forced", "<i4"), ("init_idx", "<i4"), ("row", "<i4")]))
+        assert rec.dtype.itemsize == ctypes.sizeof(L.ArItem)
+        for k, i in enumerate(plan.order):
+            rec[k] = (off[i], Ts[i], nfs[i], inits[i], int(i))
+        return torch.from_numpy(rec.view(np.uint8)).to(self.device), torch.zeros(1, dtype=torch.int32, device=self.device)
+
+    def _ar_list_buffers(self, d, plan, coop):
+        """(C, ring, msg, acc, err) of a list launch: one ring per slot, or per member of every team with the zeroed exchange buffers.
+        The ring is not zeroed: a decode reads a history row only behind its own write of it (csrc/ar_fwd.hip: ar_decode; the any-shape
+        cooperative kernel likewise, the constant-size ones clear it per item), in the first item of a slot as in every later one."""
+        g = self.g
+        if not coop:
+            return 1, torch.empty(plan.slots * self.ar_ring_total, dtype=torch.float32, device=self.device), None, None, None
+        C = max(1, min(self.opt.ar_coop_c, 32, g.H, g.S))       # as _ar_open
+        ring = torch.empty(plan.slots * C * self.ar_ring_total, dtype=torch.float32, device=self.device)
+        return (C, ring) + self._ar_exchange(d, C, plan.slots, torch.zeros)
+
     def _ar_exchange(self, d, C, groups, alloc):
         """(msg, acc, err) of `groups` utterances or teams of C workgroups from `alloc` (torch.zeros / torch.empty: a launch needs them
         zeroed).  err[0] = the time-out flag; the rest: profile counters of a -DWAE_ARC_PROFILE build."""
@@ -992,7 +1061,7 @@ class WaeEngine:
         Returns, in the caller's order, a list of dict(idx (T,) int32, logits (O, T) fp32 | None); every item is, bit for bit, what
         incremental_forward returns for that utterance alone on the one-CU kernel (WAE_AR_COOP=0).
         Always the list kernel: ar_path() and WAE_AR_COOP have no effect here.  Class-id decoders only: a scalar-input geometry
-        raises NotImplementedError, an empty list ValueError, both before any launch.
+        raises NotImplementedError (its list is decode_list_scalar), an empty list ValueError, both before any launch.
 
         coop=True: the same list on cooperative teams (include/wae.h: wae_ar_generate_coop_list) -- `teams` teams (default
         min(len(items), 8); clamped to 1..8, one XCD each, and to the item count) of C = min(WAE_AR_COOP_C, 32, H, S) workgroups, each
@@ -1003,8 +1072,8 @@ class WaeEngine:
         team-mates that times out raises WaeError after the launch; R, S or O > 256 raises ValueError before any launch."""
         g = self.g
         if g.scalar_input:
-            raise NotImplementedError("decode_list: list decoding covers class-id decoders; decode scalar-input models one batch at a "
-                                      "time with incremental_forward")
+            raise NotImplementedError("decode_list: list decoding covers class-id decoders; scalar-input models: use decode_list_scalar "
+                                      "(or incremental_forward one batch at a time)")
         if coop and max(g.R, g.S, g.O) > 256:
             raise ValueError(f"decode_list(coop=True): the cooperative kernels take R, S and O <= 256 (got {g.R}, {g.S}, {g.O}); "
                              "use the one-CU list (coop=False)")
@@ -1015,16 +1084,8 @@ class WaeEngine:
             raise ValueError(f"decode_list: mode '{mode}' is not list-decoded; use 'logits', 'argmax' or 'sample'")
         m = {"logits": 0, "argmax": 1, "sample": 2}[mode]
         lib, dev, n = self.lib, self.device, len(items)
-        Ts = [int(it["T"]) for it in items]
-        if coop:
-            slots = max(1, min(8 if teams is None else int(teams), 8))      # teams; the plan clamps them to the item count
-        elif slots is None:
-            slots = torch.cuda.get_device_properties(dev).multi_processor_count
-        plan = P.ar_list_plan(Ts, slots)
-        total, off = plan.total, [int(o) for o in plan.offsets]
-        gids = [it.get("gid") for it in items]
-        if any(x is None for x in gids) and not all(x is None for x in gids):
-            raise ValueError("decode_list: give every item a gid, or none")
+        Ts, plan, off, gids = self._ar_list_plan("decode_list", items, coop, slots, teams)
+        total = plan.total
         flat = lambda a, dt: torch.as_tensor(a).reshape(-1).to(dev, dt)  # noqa: E731
         forced, nfs, inits = [], [], []
         for i, it in enumerate(items):
@@ -1040,30 +1101,14 @@ class WaeEngine:
                 # wavenet.py:288 writes a one at the start class of the start vector: the same IndexError when there are fewer classes
                 raise IndexError(f"index {init} is out of bounds for dimension 2 with size {g.O}")
             inits.append(init if nfs[i] == 0 else 0)
-            if g.Ccp and it.get("c") is None:
-                raise ValueError(f"decode_list: item {i} has no conditioning c, the decoder has {g.Cc} conditioning channels")
         if not self._ar_packed or self.weights_dirty:
             self.pack_ar_weights()
         st = self.stream()
-        inputs = None
-        if any(f is not None for f in forced):
-            inputs = torch.zeros(total, dtype=torch.int32, device=dev)
-            for i, f in enumerate(forced):
-                if f is not None:
-                    inputs[off[i]:off[i] + nfs[i]] = f
-            if int(inputs.min()) < 0 or int(inputs.max()) >= g.O:
-                raise IndexError(f"decode_list: test_inputs hold a class id outside [0, {g.O})")
-        c_up = None
-        if g.Ccp:
-            c_up = torch.zeros(total, g.Ccp, dtype=self.tdtype, device=dev)
-            for i, it in enumerate(items):
-                c = torch.as_tensor(it["c"]).to(dev, torch.float32)
-                c = (c if c.dim() == 3 else c[None]).contiguous()
-                # the item's slice: one utterance of batch 1
-                self._ar_cond_rows(c, c_up[off[i]:off[i] + Ts[i]].view(1, Ts[i], g.Ccp), c_is_upsampled, f"item {i}: ")
-        has_gid = gids[0] is not None
-        gid32 = torch.tensor([int(torch.as_tensor(x).reshape(-1)[0]) for x in gids], dtype=torch.int32, device=dev) if has_gid else None
-        zb = self._ar_speaker_rows(n, gid32)
+        inputs = self._ar_list_forced(forced, nfs, off, total, torch.int32)
+        if inputs is not None and (int(inputs.min()) < 0 or int(inputs.max()) >= g.O):
+            raise IndexError(f"decode_list: test_inputs hold a class id outside [0, {g.O})")
+        c_up = self._ar_list_cond(items, Ts, off, total, c_is_upsampled)
+        gid32, zb = self._ar_list_speakers(gids)
         uni = None
         if m == 2:
             uni = torch.empty(total, dtype=torch.float32, device=dev)
@@ -1072,12 +1117,7 @@ class WaeEngine:
                 u = torch.rand(1, Ts[i], device=dev) if u is None else flat(u, torch.float32)
                 assert u.numel() == Ts[i], f"item {i}: {u.numel()} uniforms for {Ts[i]} steps"
                 uni[off[i]:off[i] + Ts[i]] = u.reshape(-1)
-        rec = np.zeros(n, dtype=np.dtype([("off", "<i8"), ("T", "<i4"), ("n_forced", "<i4"), ("init_idx", "<i4"), ("row", "<i4")]))
-        assert rec.dtype.itemsize == ctypes.sizeof(L.ArItem)
-        for k, i in enumerate(plan.order):      # launch order: longest first; row = the caller's index
-            rec[k] = (off[i], Ts[i], nfs[i], inits[i], int(i))
-        items_d = torch.from_numpy(rec.view(np.uint8)).to(dev)
-        nxt = torch.zeros(1, dtype=torch.int32, device=dev)
+        items_d, nxt = self._ar_list_records(plan, off, Ts, nfs, inits)
         out_idx = torch.empty(total, dtype=torch.int32, device=dev)
         want = want_logits or m == 0
         logits = torch.empty(total * g.O, dtype=torch.float32, device=dev) if want else None
@@ -1085,25 +1125,134 @@ class WaeEngine:
         d = L.ArDesc(self.dt, n, 0, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, 0, 0,
                      math.sqrt(1.0 / g.layers), 0, *path)
         operands = (L.ptr(inputs), L.ptr(uni), L.ptr(out_idx), L.ptr(logits))
+        C, ring, msg, acc, err = self._ar_list_buffers(d, plan, coop)
         if coop:
-            C = max(1, min(self.opt.ar_coop_c, 32, g.H, g.S))       # as _ar_open
-            # the kernels do not depend on the ring's contents; msg, acc, error (and next) start from zero
-            ring = torch.empty(plan.slots * C * self.ar_ring_total, dtype=torch.float32, device=dev)
-            msg, acc, err = self._ar_exchange(d, C, plan.slots, torch.zeros)
             L.check(lib.wae_ar_generate_coop_list(ctypes.byref(d), C, n, plan.slots, L.ptr(items_d), L.ptr(nxt), total,
                                                   *self._ar_net_args(ring, zb, c_up), *operands, L.ptr(msg), L.ptr(acc), L.ptr(err), st),
                     "ar_generate_coop_list")
             self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, uni, msg, acc, err)
             self._ar_check_exchange(err, "ar_generate_coop_list")
         else:
-            # not zeroed: a decode reads a history row only behind its own write of it (csrc/ar_fwd.hip: ar_decode), in the first item
-            # of a slot as in every later one
-            ring = torch.empty(plan.slots * self.ar_ring_total, dtype=torch.float32, device=dev)
             L.check(lib.wae_ar_generate_list(ctypes.byref(d), n, plan.slots, L.ptr(items_d), L.ptr(nxt),
                                              *self._ar_net_args(ring, zb, c_up), *operands, st), "ar_generate_list")
             self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, uni)      # the launch's operands live until the stream has run
         return [dict(idx=out_idx[off[i]:off[i] + Ts[i]],
                      logits=logits[off[i] * g.O:(off[i] + Ts[i]) * g.O].view(g.O, Ts[i]) if want else None) for i in range(n)]
+
+    def scalar_draws(self, T: int):
+        """(u_mix (1, T, M) | None, u_log (1, T) or z (1, T)): the draws scalar incremental_forward makes for one utterance of T steps
+        where the caller passes none, by the same expressions in the same order (_ar_open; mixture.py:138,151 and :249,266) -- after
+        the same torch.manual_seed they are the same numbers."""
+        g, dev = self.g, self.device
+        if g.output_distribution == "Normal":
+            M = 1 if g.O == 2 else g.O // 3
+            u_mix = torch.rand(1, T, M, device=dev) * (1 - 2e-5) + 1e-5 if M > 1 else None
+            return u_mix, torch.randn(1, T, device=dev)
+        u_mix = torch.rand(1, T, g.O // 3, device=dev) * (1 - 2e-5) + 1e-5
+        return u_mix, torch.rand(1, T, device=dev) * (1 - 2e-5) + 1e-5
+
+    def decode_list_scalar(self, items, mode: str = "sample", slots: Optional[int] = None, want_logits: bool = False,
+                           c_is_upsampled: bool = False, coop: bool = False, teams: Optional[int] = None,
+                           log_scale_min: float = -7.0, clamp_log_scale: bool = False):
+        """decode_list for scalar-input decoders ("raw" / "mulaw" inputs; include/wae.h: wae_ar_generate_scalar_list and
+        wae_ar_generate_coop_scalar_list): a work list of utterances of unequal lengths in ONE launch, each step's sample drawn from the
+        mixture of logistics or, with geometry output_distribution "Normal", the mixture of Gaussians, as scalar incremental_forward.
+
+        items: mappings with `T`, `c` and `gid` as in decode_list, and optionally `test_inputs` (the float forced prefix, up to T
+        values), `u_mix` ((T, M)) together with `u_log` ((T,)) -- or, for "Normal" geometries, `z` ((T,)) and, where M > 1, `u_mix`.
+        Draws of the wrong kind for the geometry raise ValueError, as in incremental_forward.  mode "logits": every item is
+        teacher-forced on test_inputs of all T steps and its mixture parameters come back (its samples too where every item carries
+        draws); mode "sample": the steps behind an item's forced prefix feed the drawn sample back.  Where an item has no draws they
+        are made on the device item after item in the caller's order, with incremental_forward's expressions (Logistic:
+        torch.rand(1, T, M) * (1 - 2e-5) + 1e-5, then torch.rand(1, T) * (1 - 2e-5) + 1e-5; Normal: the u_mix line when M > 1, then
+        torch.randn(1, T)): with the same torch.manual_seed before every item this is what a loop of incremental_forward draws.
+        slots / coop / teams: as decode_list.  coop=True is itself the opt-in to the cooperative kernel: ar_path(scalar_coop=) is not
+        consulted.  Returns, in the caller's order, a list of dict(x (T,) fp32 | None, logits (O, T) fp32 | None) -- the keys of scalar
+        incremental_forward.  With coop=False every item is, bit for bit, incremental_forward for that utterance alone on the one-CU
+        kernel; with coop=True on the cooperative path (WAE_AR_COOP=1, ar_path(scalar_coop=True), the same C).  A wait between
+        team-mates that times out raises WaeError after the launch.  ValueError before any launch: a class-id geometry (use
+        decode_list), an empty list, a mode other than "logits" / "sample", coop=True with R, S or O > 256."""
+        g, who = self.g, "decode_list_scalar"
+        if not g.scalar_input:
+            raise ValueError(f"{who}: scalar-input decoders only; a class-id decoder goes through decode_list")
+        if coop and max(g.R, g.S, g.O) > 256:
+            raise ValueError(f"{who}(coop=True): the cooperative kernels take R, S and O <= 256 (got {g.R}, {g.S}, {g.O}); "
+                             "use the one-CU list (coop=False)")
+        items = list(items)
+        if not items:
+            raise ValueError(f"{who}: an empty list")
+        if mode not in ("logits", "sample"):
+            raise ValueError(f"{who}: mode '{mode}': scalar-input decoders feed the drawn sample back: modes 'logits' and 'sample' only")
+        m = {"logits": 0, "sample": 2}[mode]
+        lib, dev, n = self.lib, self.device, len(items)
+        normal = g.output_distribution == "Normal"
+        M = 1 if (normal and g.O == 2) else g.O // 3
+        Ts, plan, off, gids = self._ar_list_plan(who, items, coop, slots, teams)
+        total = plan.total
+        flat = lambda a: torch.as_tensor(a).reshape(-1).to(dev, torch.float32)  # noqa: E731
+        forced, nfs, given = [], [], []
+        for i, it in enumerate(items):
+            ti = it.get("test_inputs")
+            ti = flat(ti)[:Ts[i]] if ti is not None else None
+            nfs.append(0 if ti is None else int(ti.numel()))
+            forced.append(ti if nfs[i] else None)
+            if m == 0 and nfs[i] < Ts[i]:
+                raise ValueError(f"{who}: mode 'logits' is teacher-forced: test_inputs of item {i} must cover all {Ts[i]} steps")
+            um, ul, z = it.get("u_mix"), it.get("u_log"), it.get("z")
+            if normal and ul is not None:
+                raise ValueError(f"{who}: item {i}: output_distribution 'Normal' draws from u_mix and z, not u_log")
+            if not normal and z is not None:
+                raise ValueError(f"{who}: item {i}: output_distribution 'Logistic' draws from u_mix and u_log, not z")
+            if not normal and (um is None) != (ul is None):
+                raise ValueError(f"{who}: item {i}: u_mix and u_log come together")
+            if normal and z is not None and M > 1 and um is None:
+                raise ValueError(f"{who}: item {i}: {M} Gaussians need u_mix beside z")
+            given.append((z if normal else ul) is not None)
+        if m == 0 and any(given) and not all(given):
+            raise ValueError(f"{who}: mode 'logits': give every item its draws (then the samples come back too), or none")
+        sampled = m == 2 or all(given)
+        if not self._ar_packed or self.weights_dirty:
+            self.pack_ar_weights()
+        st = self.stream()
+        inputs = self._ar_list_forced(forced, nfs, off, total, torch.float32)
+        c_up = self._ar_list_cond(items, Ts, off, total, c_is_upsampled)
+        gid32, zb = self._ar_list_speakers(gids)
+        um_d = dr_d = None
+        if sampled:
+            um_d = torch.empty(total, M, dtype=torch.float32, device=dev) if (not normal or M > 1) else None
+            dr_d = torch.empty(total, dtype=torch.float32, device=dev)
+            for i, it in enumerate(items):
+                T = Ts[i]
+                um, dr = it.get("u_mix"), it.get("z" if normal else "u_log")
+                if not given[i]:
+                    um, dr = self.scalar_draws(T)
+                if um_d is not None:
+                    um = flat(um)
+                    assert um.numel() == T * M, f"item {i}: u_mix holds {um.numel()} values for {T} steps of {M} mixtures"
+                    um_d[off[i]:off[i] + T] = um.view(T, M)
+                dr = flat(dr)
+                assert dr.numel() == T, f"item {i}: {dr.numel()} draws for {T} steps"
+                dr_d[off[i]:off[i] + T] = dr
+        items_d, nxt = self._ar_list_records(plan, off, Ts, nfs, [0] * n)
+        xs = torch.empty(total, dtype=torch.float32, device=dev) if sampled else None
+        want = want_logits or m == 0
+        params = torch.empty(total * g.O, dtype=torch.float32, device=dev) if want else None
+        d = L.ArDesc(self.dt, n, 0, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, 0, 1,
+                     math.sqrt(1.0 / g.layers), 0)
+        operands = (L.ptr(inputs), L.ptr(um_d), L.ptr(dr_d), float(log_scale_min), int(bool(clamp_log_scale)), L.ptr(xs), L.ptr(params))
+        C, ring, msg, acc, err = self._ar_list_buffers(d, plan, coop)
+        if coop:
+            L.check(lib.wae_ar_generate_coop_scalar_list(ctypes.byref(d), C, int(normal), n, plan.slots, L.ptr(items_d), L.ptr(nxt), total,
+                                                         *self._ar_net_args(ring, zb, c_up), *operands, L.ptr(msg), L.ptr(acc),
+                                                         L.ptr(err), st), "ar_generate_coop_scalar_list")
+            self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, um_d, dr_d, msg, acc, err)
+            self._ar_check_exchange(err, "ar_generate_coop_scalar_list")
+        else:
+            L.check(lib.wae_ar_generate_scalar_list(ctypes.byref(d), int(normal), n, plan.slots, L.ptr(items_d), L.ptr(nxt),
+                                                    *self._ar_net_args(ring, zb, c_up), *operands, st), "ar_generate_scalar_list")
+            self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, um_d, dr_d)
+        return [dict(x=xs[off[i]:off[i] + Ts[i]] if sampled else None,
+                     logits=params[off[i] * g.O:(off[i] + Ts[i]) * g.O].view(g.O, Ts[i]) if want else None) for i in range(n)]
 
     # ------------------------------------------------------------------ full autoencoder
     def forward(self, x: torch.Tensor, c: torch.Tensor, gid: Optional[torch.Tensor], targets=None, lengths=None,
