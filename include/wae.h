@@ -556,6 +556,75 @@ int wae_ar_generate_coop_scalar_list(const wae_ar_desc* d, int32_t C, int32_t di
                                      const float* draws, float log_scale_min, int32_t clamp_log_scale, float* out_samples,
                                      float* out_params, uint64_t* msg, float* acc, int32_t* error, void* stream);
 
+/* Work lists of SPANS: the list entries' queue over clips that live longer than a launch (csrc/ar_fwd.hip: ar_span_kernel;
+ * csrc/ar_coop.hip: the LIST forms, branching once per record).  A span is a run of consecutive steps of one clip; a clip is decoded
+ * as a sequence of spans, in any chunking, over any number of launches, on whichever slot or team takes each span, and its spans'
+ * outputs, concatenated, are bit for bit the single decode of that clip -- wae_ar_generate, wae_ar_generate_scalar or
+ * wae_ar_generate_scalar_mog on the slots, wae_ar_generate_coop at the same C and kernel form on the teams (the same device
+ * functions).  What carries a clip from one span to the next is its own history ring, which belongs to the clip and not to a slot:
+ * `ring` is the base of the caller's ring storage and span.ring the float offset of the clip's ring in it (a multiple of 4).
+ * Ring per clip: ring_total floats on the one-CU kernels and on the constant-size cooperative kernels, C * ring_total on the
+ * any-shape cooperative kernel (wae_ar_coop_ring_floats says which for a cooperative launch).
+ * The queue is the list entries': `next` is one int32_t the caller zeroes, taken with one returning atomic add; spans are taken in
+ * array order (put the longest first) and no slot or team waits for another.  Ring rows, ring cursors and every "before the clip
+ * starts" test use span.t0 + t, exactly as under wae_ar_desc.t0; d->t0 itself must be 0.  The per-step operands of THIS launch
+ * (c_up, inputs / inputs_f, uniforms, u_mix, draws, out_idx, out_samples; out_logits / out_params one (O, span.T) block per span at
+ * float offset off * O) are indexed from span.off; zb holds one (L, 2Hp) row per value of span.row.
+ * The first step of a continuation (t0 > 0) is forced: the caller puts the previous span's last output, or the teacher-forced value,
+ * at inputs[off] / inputs_f[off]; a record with t0 > 0 and n_forced < 1 is read as n_forced = 1.  span.n_forced counts from the span's
+ * first step (clamped to [0, T]; mode 0 forces every step); span.init_idx is read only when t0 == 0 and nothing is forced.
+ * THE CALLER'S CONTRACT, which the entries cannot check because the records live in device memory: one launch holds at most one span
+ * of any clip (two spans of a clip in one launch could run at the same time on two slots); a span with t0 > 0 continues in the ring
+ * the clip's earlier spans -- same geometry, weights, dtype, C, kernel form -- left for steps [0, t0); span.reserved is 0.
+ * One-CU kernels and the any-shape cooperative kernel: nothing is cleared; a history row is read only behind its own write, by
+ * absolute index.  Constant-size cooperative kernels: a span with t0 == 0 gets the list form's clearing of its clip's ring (drain,
+ * rendezvous A -- which here also hands the team the span index --, clear, rendezvous B); a span with t0 > 0 keeps its rows and starts
+ * from the single decode's continuation prologue (cursors at t0 mod ring length, the first step's two history taps read from the
+ * ring); the weight packets stay on chip across spans and only the resident layers' two zb words are rewritten per span.  The
+ * exchange sequence numbers run on across a team's spans, as across items.
+ * wae_ar_generate_spans: class ids on n_slots one-CU workgroups, modes 0 / 1 / 2, the operands of wae_ar_generate_list.
+ * wae_ar_generate_scalar_spans: dist 0 / 1 on n_slots one-CU workgroups, modes 0 / 2, the operands of wae_ar_generate_scalar_list.
+ * wae_ar_generate_coop_spans: class ids on n_teams <= 8 teams of C workgroups, modes 0 / 1 / 2, the operands of
+ *   wae_ar_generate_coop_list (msg, acc, error and next zeroed by the caller per launch; error[0] != 0 afterwards: a wait timed out).
+ * Refused before any launch: whatever the list twin refuses (WAE_EUNSUPPORTED / WAE_EINVAL as there), d->t0 != 0 among it; the
+ * cooperative entry also (total + n_spans + 1) * (L + 4) >= 2^31, total being the length of the packed operands.
+ * Rates (profiles/ar_session.txt, all measured, bf16 at the reference's geometry): 8 clips on 8 teams in spans of 1600 steps 30.7 kHz per
+ * clip against 31 kHz in one launch, 16 clips on 8 teams 15.3 kHz per clip, a relaunch with its packing ~0.45 ms per round on the
+ * teams; fp32 sessions and scalar sessions have not been measured. */
+typedef struct wae_ar_span {
+  int64_t off;       /* first step of the span in THIS launch's packed per-step operands (as wae_ar_item.off) */
+  int64_t ring;      /* float offset of the clip's own history ring inside `ring` */
+  int32_t T;         /* steps of the span (<= 0: skipped) */
+  int32_t t0;        /* absolute index of the span's first step in its clip; the ring holds steps [0, t0) */
+  int32_t n_forced;  /* span-relative, as wae_ar_desc.n_forced under streaming: a span with t0 > 0 forces at least its first step */
+  int32_t init_idx;  /* read only when t0 == 0 and nothing is forced */
+  int32_t row;       /* row of zb */
+  int32_t reserved;  /* 0 */
+} wae_ar_span;       /* 40 bytes */
+int wae_ar_generate_spans(const wae_ar_desc* d, int32_t n_spans, int32_t n_slots, const wae_ar_span* spans, int32_t* next,
+                          const int32_t* dilations, const int64_t* ring_off, float* ring, int64_t ring_total,
+                          const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes, const float* bias2,
+                          const float* zb, const float* first_tab, const float* first_bias, const void* w_head,
+                          const float* head_bias, const void* c_up, int32_t c_dtype, const int32_t* inputs,
+                          const float* uniforms, int32_t* out_idx, float* out_logits, void* stream);
+int wae_ar_generate_scalar_spans(const wae_ar_desc* d, int32_t dist, int32_t n_spans, int32_t n_slots, const wae_ar_span* spans,
+                                 int32_t* next, const int32_t* dilations, const int64_t* ring_off, float* ring, int64_t ring_total,
+                                 const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes, const float* bias2,
+                                 const float* zb, const float* first_tab, const float* first_bias, const void* w_head,
+                                 const float* head_bias, const void* c_up, int32_t c_dtype, const float* inputs_f,
+                                 const float* u_mix, const float* draws, float log_scale_min, int32_t clamp_log_scale,
+                                 float* out_samples, float* out_params, void* stream);
+int wae_ar_generate_coop_spans(const wae_ar_desc* d, int32_t C, int32_t n_spans, int32_t n_teams, const wae_ar_span* spans,
+                               int32_t* next, int64_t total, const int32_t* dilations, const int64_t* ring_off, float* ring,
+                               int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
+                               const float* bias2, const float* zb, const float* first_tab, const float* first_bias,
+                               const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
+                               const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
+                               uint64_t* msg, float* acc, int32_t* error, void* stream);
+/* Floats of ONE clip's ring under wae_ar_generate_coop_spans for this descriptor, C and ring_total: ring_total where the launch takes
+ * the constant-size kernels (their members share one ring), C * ring_total on the any-shape kernel; < 0: bad arguments. */
+int64_t wae_ar_coop_ring_floats(const wae_ar_desc* d, int32_t C, int64_t ring_total);
+
 /* ---- backward data path of the gated stack: C[t][M] = sum_s W_s . X_s[t + shift_s] on time-major operands ----
  * (autograd of modules.py:115-163; see csrc/gemm_tm.hip).  mode 0: out (t, M) = acc.  mode 1 (residual):
  * out = alpha * (acc + aux[t]).  mode 2 (gate backward): acc = du over M = Hp rows, aux = z (t, 2Hp),

@@ -19,6 +19,11 @@ options:
                              written are the same files (with --seed: byte for byte those of the loop on the one-CU kernel,
                              WAE_AR_COOP=0).  Scalar-input ("raw" / "mulaw") models go through WaeEngine.decode_list_scalar; with
                              --batch-coop their wavs are those of the loop run with --coop-scalar.  Not with --stream-chunk.
+    --batch-stream=<N>       With --batch-decode: decode the list in rounds of N samples per clip (WaeEngine.decode_list_stream: one
+                             launch per round, every clip keeps its own history between the launches) and post-process every chunk as
+                             it arrives, as --stream-chunk does for one clip; prints the wall time until every clip has its first
+                             chunk.  With or without --batch-coop (class-id models; scalar-input models stream on the one-CU slots).
+                             The wavs written are the bytes of --batch-decode alone.
 """
 import argparse
 import json
@@ -167,6 +172,8 @@ def batch_decode(eng, args, pairs, sp2ind, out_dir):
                               uniforms=torch.rand(1, length, device=device)))
         names.append(f"{out_dir}{tar}_{fid}.wav")
     how = dict(coop=True, teams=args.batch_teams) if args.batch_coop else {}
+    if args.batch_stream:
+        return batch_stream(eng, args, items, names, how)
     if eng.g.scalar_input:
         results = eng.decode_list_scalar(items, mode="sample", log_scale_min=hparams.log_scale_min, **how)
     else:
@@ -176,6 +183,28 @@ def batch_decode(eng, args, pairs, sp2ind, out_dir):
         y = postprocess_wave(decoded_wave({k: v[None] for k, v in res.items() if v is not None}), hparams.postprocess,
                              hparams.global_gain_scale)
         wavfile.write(out, hparams.sample_rate, y)
+        print("Finished! Check out {} for generated audio samples.".format(out), flush=True)
+    return 0
+
+
+def batch_stream(eng, args, items, names, how):
+    """--batch-decode --batch-stream=N: batch_decode's list in rounds of N samples (WaeEngine.decode_list_stream).  Every clip has its
+    own ChunkPostprocess, so its chunks, concatenated, are the array batch_decode post-processes in one piece -- the same wav bytes."""
+    import time
+    from scipy.io import wavfile
+    kw = dict(log_scale_min=hparams.log_scale_min) if eng.g.scalar_input else {}
+    posts = [ChunkPostprocess(hparams.postprocess, hparams.global_gain_scale) for _ in items]
+    parts = [[] for _ in items]
+    t_start, first = time.perf_counter(), True
+    for rnd in eng.decode_list_stream(items, int(args.batch_stream), mode="sample", **how, **kw):
+        for i, res in enumerate(rnd):
+            if res is not None:
+                parts[i].append(posts[i](decoded_wave({k: v[None] for k, v in res.items() if k != "done" and v is not None})))
+        if first:
+            first = False
+            print(f"first audio of all {len(items)} clips after {(time.perf_counter() - t_start) * 1e3:.1f} ms", flush=True)
+    for out, p in zip(names, parts):
+        wavfile.write(out, hparams.sample_rate, np.concatenate(p))
         print("Finished! Check out {} for generated audio samples.".format(out), flush=True)
     return 0
 
@@ -195,7 +224,12 @@ def main(argv=None):
     ap.add_argument("--batch-decode", action="store_true")
     ap.add_argument("--batch-coop", action="store_true")
     ap.add_argument("--batch-teams", type=int)
+    ap.add_argument("--batch-stream", type=int)
     args = ap.parse_args(argv)
+    if args.batch_stream is not None and not args.batch_decode:
+        ap.error("--batch-stream sets the round length of --batch-decode: it needs --batch-decode")
+    if args.batch_stream is not None and args.batch_stream < 1:
+        ap.error("--batch-stream: a round has at least one sample")
     if (args.batch_coop or args.batch_teams is not None) and not args.batch_decode:
         ap.error("--batch-coop / --batch-teams choose how --batch-decode runs its list: they need --batch-decode")
     if args.batch_coop and args.stream_chunk:

@@ -3,6 +3,7 @@
 
 usage: bench_ar_list.py [--items N] [--dtypes bf16,fp32] [--slots cu[,2cu,N...]] [--teams N[,N...]] [--loop K] [--min-len 8000]
                         [--max-len 64000] [--scalar]
+       bench_ar_list.py --session [--session-clips 256]
     --items N     clips in the list (default 512); lengths are drawn with numpy.random.default_rng(1234), uniform in
                   [--min-len, --max-len] samples, and rounded to whole latent frames (640 samples: the conditioning is upsampled per clip)
     --dtypes      storage types to run (default bf16,fp32)
@@ -14,6 +15,12 @@ usage: bench_ar_list.py [--items N] [--dtypes bf16,fp32] [--slots cu[,2cu,N...]]
     --scalar      the scalar-input decoder of tools/bench_ar.py --scalar instead (the same decoder with an O = 30 mixture-of-logistics
                   head) through WaeEngine.decode_list_scalar, on both list forms; --loop then runs twice: on the one-CU kernel and on
                   the cooperative kernel (ar_path(scalar_coop=True), what synthesis.py --coop-scalar selects)
+    --session     decode sessions (WaeEngine.decode_session) against the list decode of the same clips, in bf16, in one run: 8 clips of
+                  16 000 steps on 8 teams in rounds of 160 and of 1600 steps against decode_list(coop=True); 16 such clips on 8 teams
+                  in rounds of 1600 (two clips per team); --session-clips clips of --min-len .. --max-len steps on the one-CU slots in
+                  rounds of 1600 against decode_list.  Every round's outputs are copied to the host, as a service would.  Per run: the
+                  aggregate kHz, the mean per-clip kHz (a clip's steps / the time from the start until its last chunk is on the
+                  host) and the time until every clip has its first chunk on the host.
 Prints, per run, the wall time of the whole decode_list call (packing the operands, upsampling, the launch, synchronised) and the
 aggregate kHz = sum of lengths / time, beside the efficiency the launch plan predicts (packing.ar_list_plan), and one JSON line."""
 import argparse
@@ -36,6 +43,74 @@ CFG = dict(layers=20, stacks=2, R=256, G=256, S=256, O=256, Cc=64, Cg=32, k=3, n
 HOP = 640
 
 
+def session_bench(args):
+    dtype = "bf16"
+    eng = WaeEngine(Geometry.from_cfg(CFG), dtype=dtype)
+    eng.load_state_dict(O.make_state_dict(dict(CFG), salt=7, with_encoder=False))
+    gen = torch.Generator(device="cuda").manual_seed(1234)
+    mk = lambda lens: [dict(T=T, c=torch.randn(64, T // HOP, device="cuda", generator=gen), gid=i % CFG["n_speakers"],  # noqa: E731
+                            uniforms=torch.rand(T, device="cuda", generator=gen)) for i, T in enumerate(lens)]
+    record = dict(session=True, dtype=dtype, runs=[])
+
+    def run_list(items, **how):
+        total = sum(it["T"] for it in items)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = eng.decode_list(items, mode="sample", **how)
+        host = [r["idx"].cpu() for r in out]
+        dt = time.perf_counter() - t0
+        print(f"  decode_list({how}): {dt:.3f} s -> {total / dt / 1e3:.1f} kHz aggregate; first audio of every clip after {dt * 1e3:.0f} ms "
+              f"(the whole launch)", flush=True)
+        record["runs"].append(dict(kind="decode_list", how=str(how), clips=len(items), samples=total, seconds=dt, khz=total / dt / 1e3))
+        return host
+
+    def run_session(items, chunk, ref=None, **how):
+        total = sum(it["T"] for it in items)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        first, done_at, parts = None, {}, [[] for _ in items]
+        for k, rnd in enumerate(eng.decode_list_stream(items, chunk, mode="sample", **how)):
+            for i, r in enumerate(rnd):
+                if r is not None:
+                    parts[i].append(r["idx"].cpu())
+                    if r["done"]:
+                        done_at[i] = None
+            now = time.perf_counter() - t0
+            first = now if first is None else first
+            done_at = {i: (now if v is None else v) for i, v in done_at.items()}
+        dt = time.perf_counter() - t0
+        per = float(np.mean([items[i]["T"] / done_at[i] for i in range(len(items))])) / 1e3
+        same = "" if ref is None else ("; bit for bit the list" if all(torch.equal(torch.cat(p), r) for p, r in zip(parts, ref))
+                                       else "; DIFFERS from the list")
+        print(f"  decode_session({how}) rounds of {chunk}: {k + 1} launches, {dt:.3f} s -> {total / dt / 1e3:.1f} kHz aggregate, "
+              f"{per:.2f} kHz per clip (mean); every clip's first chunk on the host after {first * 1e3:.1f} ms{same}", flush=True)
+        record["runs"].append(dict(kind="decode_session", how=str(how), chunk=chunk, clips=len(items), samples=total, launches=k + 1,
+                                   seconds=dt, khz=total / dt / 1e3, khz_per_clip=per, first_chunk_ms=first * 1e3))
+
+    warm = mk([HOP] * 8)
+    eng.decode_list(warm, mode="sample", coop=True)
+    eng.decode_list(warm, mode="sample")
+    list(eng.decode_list_stream(warm, 160, mode="sample", coop=True))
+    list(eng.decode_list_stream(warm, 160, mode="sample"))
+    torch.cuda.synchronize()
+    eight, sixteen = mk([16000] * 8), mk([16000] * 16)
+    print("8 clips of 16000 steps on 8 teams")
+    ref = run_list(eight, coop=True, teams=8)
+    run_session(eight, 160, ref, coop=True, teams=8)
+    run_session(eight, 1600, ref, coop=True, teams=8)
+    print("16 clips of 16000 steps on 8 teams (two clips per team)")
+    ref = run_list(sixteen, coop=True, teams=8)
+    run_session(sixteen, 1600, ref, coop=True, teams=8)
+    rng = np.random.default_rng(1234)
+    lens = rng.integers(args.min_len, args.max_len + 1, args.session_clips)
+    lens = (np.maximum(1, np.rint(lens / HOP)).astype(np.int64) * HOP).tolist()
+    many = mk(lens)
+    print(f"{len(lens)} clips of {min(lens)} .. {max(lens)} steps on the one-CU slots")
+    ref = run_list(many)
+    run_session(many, 1600, ref)
+    print(json.dumps(record))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--items", type=int, default=512)
@@ -46,7 +121,11 @@ def main():
     ap.add_argument("--min-len", type=int, default=8000)
     ap.add_argument("--max-len", type=int, default=64000)
     ap.add_argument("--scalar", action="store_true")
+    ap.add_argument("--session", action="store_true")
+    ap.add_argument("--session-clips", type=int, default=256)
     args = ap.parse_args()
+    if args.session:
+        return session_bench(args)
     cfg = dict(CFG, O=30, scalar_input=True, output_distribution="Logistic") if args.scalar else CFG
     rng = np.random.default_rng(1234)
     lens = rng.integers(args.min_len, args.max_len + 1, args.items)

@@ -32,6 +32,11 @@ class ArItem(ctypes.Structure):          # include/wae.h: wae_ar_item (device ar
     _fields_ = [("off", c_i64), ("T", c_i32), ("n_forced", c_i32), ("init_idx", c_i32), ("row", c_i32)]
 
 
+class ArSpan(ctypes.Structure):          # include/wae.h: wae_ar_span (device array element of the wae_ar_generate*_spans entries)
+    _fields_ = [("off", c_i64), ("ring", c_i64), ("T", c_i32), ("t0", c_i32), ("n_forced", c_i32), ("init_idx", c_i32), ("row", c_i32),
+                ("reserved", c_i32)]
+
+
 class TmDesc(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in ("dtype", "B", "T", "M", "nsrc", "mode")] + [("alpha", c_f32), ("flags", c_i32)]
 
@@ -165,6 +170,11 @@ SIGNATURES = {
     "wae_ar_generate_scalar_list": (c_i32, _AR[:1] + [c_i32, c_i32, c_i32, c_vp, c_vp] + _AR[1:] + [c_vp] * 3 + [c_f32, c_i32] + [c_vp] * 3),
     "wae_ar_generate_coop_scalar_list": (c_i32, _AR[:1] + [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64] + _AR[1:] + [c_vp] * 3
                                          + [c_f32, c_i32] + [c_vp] * 6),
+    # the span entries take their list twins' arguments (spans in place of items)
+    "wae_ar_generate_spans": (c_i32, _AR[:1] + [c_i32, c_i32, c_vp, c_vp] + _AR[1:] + [c_vp] * 5),
+    "wae_ar_generate_scalar_spans": (c_i32, _AR[:1] + [c_i32, c_i32, c_i32, c_vp, c_vp] + _AR[1:] + [c_vp] * 3 + [c_f32, c_i32] + [c_vp] * 3),
+    "wae_ar_generate_coop_spans": (c_i32, _AR[:1] + [c_i32, c_i32, c_i32, c_vp, c_vp, c_i64] + _AR[1:] + [c_vp] * 8),
+    "wae_ar_coop_ring_floats": (c_i64, [ctypes.POINTER(ArDesc), c_i32, c_i64]),
     "wae_ce_logits_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "wae_ce_logits_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),
     "wae_weighted_mean": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp]),

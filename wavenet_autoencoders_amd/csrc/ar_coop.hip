@@ -73,6 +73,8 @@ struct ArcArgs {
   const wae_ar_item* items;
   int32_t* next;             // the queue counter, zeroed by the caller
   int n_items;
+  // ... or of n_items spans (wae_ar_generate_coop_spans): records that also carry their clip's ring and their own t0; items is then null
+  const wae_ar_span* spans;
 };
 
 template <typename E>
@@ -528,6 +530,7 @@ __device__ __forceinline__ void ar_coop_body(const ArcArgs& p) {
   float* ring = p.ring + ((int64_t)b * C + m) * p.ring_total;
   // the utterance in hand: steps, forced prefix, start class, first step in the per-step operands, zb row (LIST: the item's, set per item)
   int T = p.T, nforced = p.n_forced, init = p.init_idx;
+  int t0 = p.t0;          // absolute index of the first step in hand (LIST: 0 for an item, the span's own for a span)
   int64_t base = (int64_t)b * p.T;
   const float* zb_b = p.zb + (int64_t)b * p.L * 2 * p.Hp;
   unsigned long long* msg_b = p.msg + (int64_t)b * 2 * C * p.NV;
@@ -545,7 +548,7 @@ __device__ __forceinline__ void ar_coop_body(const ArcArgs& p) {
     }
     for (int i = tid; i < p.L; i += ARC_THREADS) {
       const int di = p.dil[i];
-      ldil[i] = di; lroff[i] = (int)p.ring_off[i]; lpos[i] = p.t0 % ((p.ktaps - 1) * di + 1);
+      ldil[i] = di; lroff[i] = (int)p.ring_off[i]; lpos[i] = t0 % ((p.ktaps - 1) * di + 1);
     }
   };
   if constexpr (LIST) { if (tid == 0) ibuf[1] = 0; }      // the abort flag: once; the rest when a team has taken an item
@@ -630,11 +633,12 @@ __device__ __forceinline__ void ar_coop_body(const ArcArgs& p) {
     if (hist_more)
       for (int i = tid + ARC_HP * ARC_THREADS; i < (p.ktaps - 1) * p.R; i += ARC_THREADS) vbuf[i] = hist_load(l, t, i);
   };
-  if (p.t0 > 0) {
-    // a continuation: layer 0's history taps of the first step are rows an earlier launch wrote (a fresh decode has none: vbuf is zero)
-    request_hist(ldil[0], lroff[0], lpos[0], p.t0);
-    place_hist(0, p.t0);
-  }
+  // a continuation: layer 0's history taps of the first step are rows an earlier launch wrote (a fresh decode has none: vbuf is zero)
+  auto resume = [&]() {
+    request_hist(ldil[0], lroff[0], lpos[0], t0);
+    place_hist(0, t0);
+  };
+  if constexpr (!LIST) { if (t0 > 0) resume(); }      // (LIST: per span, at the boundary)
   // The weights a member needs for a layer -- ARC_W1P packets of its slice of one gate row, two packets of W_out row tid
   // and of W_skip row tid -- depend on nothing computed: they are requested one layer ahead and wait in registers.
   const int rw = 2 * nch;
@@ -765,17 +769,34 @@ __device__ __forceinline__ void ar_coop_body(const ArcArgs& p) {
     const int it = __builtin_amdgcn_readfirstlane(__float_as_int(ids[0]));      // member 0's granule: the same word on every member
     arc_barrier();
     if (it >= p.n_items) return;      // the team leaves together
-    const wae_ar_item w = p.items[it];
-    if (w.T <= 0) continue;           // skipped by the whole team
-    // as ar_list_kernel (csrc/ar_fwd.hip): mode 0 is teacher-forced throughout; a start class outside the table would read beyond first_tab
-    T = w.T; base = w.off;
     // (a scalar item takes its forced prefix from inputs_f and has no start class: item_reset starts it from 0)
     const bool forced_in = SCALAR ? p.inputs_f != nullptr : p.inputs != nullptr;
-    nforced = !forced_in ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
-    init = min(max(w.init_idx, 0), p.O - 1);
-    zb_b = p.zb + (int64_t)w.row * p.L * 2 * p.Hp;
+    if (p.spans) {
+      // ---- the span boundary: the item boundary with the clip's own rings and the span's own t0 -------------------------------------
+      // Member m's private rings of THIS CLIP are (p.ring + span.ring)[m * ring_total ..]: whichever team decoded the clip's earlier spans
+      // (in earlier launches: a launch holds one span of a clip) left there every row of steps [0, t0), and a row is still read only
+      // behind its write, by absolute index -- in this span or an earlier one -- so nothing is cleared here either.  A continuation
+      // starts from the single decode's prologue (resume); its first step is forced.
+      const wae_ar_span w = p.spans[it];
+      if (w.T <= 0) continue;
+      T = w.T; base = w.off; t0 = max(w.t0, 0);
+      nforced = !forced_in ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
+      if (forced_in && t0 > 0 && nforced < 1) nforced = 1;
+      init = min(max(w.init_idx, 0), p.O - 1);
+      zb_b = p.zb + (int64_t)w.row * p.L * 2 * p.Hp;
+      ring = p.ring + w.ring + (int64_t)m * p.ring_total;
+    } else {
+      const wae_ar_item w = p.items[it];
+      if (w.T <= 0) continue;           // skipped by the whole team
+      // as ar_list_kernel (csrc/ar_fwd.hip): mode 0 is teacher-forced throughout; a start class outside the table would read beyond first_tab
+      T = w.T; base = w.off;
+      nforced = !forced_in ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
+      init = min(max(w.init_idx, 0), p.O - 1);
+      zb_b = p.zb + (int64_t)w.row * p.L * 2 * p.Hp;
+    }
     item_reset();
     arc_barrier();
+    if (t0 > 0) resume();             // (a span only: an item's t0 is 0)
   }
 #pragma unroll
   for (int k = 0; k < ARC_HP; ++k) hist[k] = 0.f;   // layer 0 at t = 0: no history yet
@@ -891,7 +912,7 @@ __device__ __forceinline__ void ar_coop_body(const ArcArgs& p) {
       // load latency of the exchange, so the first polling pass usually finds every share; the history rows return in front of the
       // shares (loads return in order) and go into vbuf with the new current tap.
       {
-        const int ln = l + 1 < p.L ? l + 1 : 0, tn = p.t0 + (l + 1 < p.L ? t : t + 1);      // tn: absolute (ring rows, start of the clip)
+        const int ln = l + 1 < p.L ? l + 1 : 0, tn = t0 + (l + 1 < p.L ? t : t + 1);      // tn: absolute (ring rows, start of the clip)
         const float bx = b2_x;
         const int dN = arc_uni(ldil + ln), roffN = arc_uni(lroff + ln);
         int posN = arc_uni(lpos + ln);
@@ -1249,6 +1270,7 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
   unsigned long long* msg_b = p.msg + (int64_t)b * 2 * C * p.NV;
   // the utterance in hand: steps, forced prefix, start class, first step in the per-step operands (LIST: the item's, set per item)
   int T = p.T, nforced = p.n_forced, init = p.init_idx;
+  int t0 = p.t0;          // absolute index of the first step in hand (LIST: 0 for an item, the span's own for a span)
   int64_t base = (int64_t)b * p.T;
   // the LDS state a clip starts from: zeroed vectors, the first input, every ring's cursor (and the tabulated rows) at the clip's first step
   auto tab_entry = [&](int l, int pos) -> int4 {
@@ -1265,7 +1287,7 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
     if (ti == 0) { ibuf[0] = nforced > 0 ? p.inputs[base] : init; ibuf[1] = 0; }
     for (int i = ti; i < L; i += ARC_THREADS) {
       const int di = p.dil[i];
-      ldil[i] = di; lroff[i] = (int)p.ring_off[i]; lpos[i] = p.t0 % (2 * di + 1);
+      ldil[i] = di; lroff[i] = (int)p.ring_off[i]; lpos[i] = t0 % (2 * di + 1);
     }
   };
   // shared ring: member m zeroes its 32nd and drains; the members meet in a gather before anyone reads a row
@@ -1286,7 +1308,7 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
   } else {
     item_state(tid);
     // a continuation keeps the rows of steps [0, t0) (and the zeros of the rows no step has written yet); the XCC-id gather below is the meeting
-    if (p.t0 == 0) ring_clear(tid);
+    if (t0 == 0) ring_clear(tid);
     arc_barrier();
     item_tab(tid);
   }
@@ -1457,24 +1479,49 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
       if (tl == 0) __hip_atomic_store(bank + m * p.NV, arc_pack(mseq, mine), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       return arc_gather(bank, p.NV, C, 1, C, mseq, p.error, &ibuf[1], [&](int i, float v) { got[i] = v; });
     };
+    // Spans (p.spans; wae_ar_generate_coop_spans).  The ring belongs to the clip, so the team must know the span BEFORE it clears: the
+    // index travels in rendezvous A instead of B (taken by thread 0 of member 0 in front of A; A and B stay the two exchanges, in the
+    // same order, with the same two-bank argument).  A span with t0 == 0 then gets the clearing above for its clip's ring (step 2
+    // between A and B); a span with t0 > 0 skips step 2 and keeps its rows -- those of steps [0, t0), written in earlier launches (a
+    // launch holds one span of a clip), and the zeros the clip's first span left in the rows no step has written yet -- and starts from
+    // the single decode's continuation prologue below (cursors at t0 mod ring length, the first step's two history taps read from
+    // the ring by prefetch(0, 0)).  B and its acquire fence are kept for every span: behind B no member still reads a granule of A.
     float* ids = psum;
+    const bool sp = p.spans != nullptr;                          // uniform: a launch decodes items or spans
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (!meet(0.f, ids)) return;                                 // A
-    ring_clear(tl);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     int took = 0;
-    if (tl == 0 && m == 0) took = atomicAdd(p.next, 1);
-    if (!meet(__int_as_float(took), ids)) return;                // B
+    if (sp && tl == 0 && m == 0) took = atomicAdd(p.next, 1);
+    if (!meet(__int_as_float(took), ids)) return;                // A
+    int it = 0;
+    wae_ar_span w = {};
+    if (sp) {
+      it = __builtin_amdgcn_readfirstlane(__float_as_int(ids[0]));              // member 0's granule: the same word on every member
+      if (it >= p.n_items) return;    // the team leaves together
+      w = p.spans[it];
+      if (w.T > 0) {
+        ring = p.ring + w.ring;
+        if (w.t0 <= 0) ring_clear(tl);
+      }
+    } else {
+      ring_clear(tl);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    if (!sp && tl == 0 && m == 0) took = atomicAdd(p.next, 1);
+    if (!meet(sp ? 0.f : __int_as_float(took), ids)) return;     // B
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    const int it = __builtin_amdgcn_readfirstlane(__float_as_int(ids[0]));      // member 0's granule: the same word on every member
+    if (!sp) it = __builtin_amdgcn_readfirstlane(__float_as_int(ids[0]));
     arc_barrier();
-    if (it >= p.n_items) return;      // the team leaves together
-    const wae_ar_item w = p.items[it];
+    if (!sp) {
+      if (it >= p.n_items) return;    // the team leaves together
+      const wae_ar_item wi = p.items[it];
+      w.off = wi.off; w.T = wi.T; w.t0 = 0; w.n_forced = wi.n_forced; w.init_idx = wi.init_idx; w.row = wi.row;
+    }
     if (w.T <= 0) continue;           // skipped by the whole team
     // as ar_list_kernel (csrc/ar_fwd.hip): mode 0 is teacher-forced throughout; a start class outside the table would read beyond first_tab
-    T = w.T; base = w.off;
+    T = w.T; base = w.off; t0 = max(w.t0, 0);
     nforced = !p.inputs ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
+    if (p.inputs && t0 > 0 && nforced < 1) nforced = 1;         // a continuation's first step is forced
     init = min(max(w.init_idx, 0), p.O - 1);
     zb_b = p.zb + (int64_t)w.row * L * 2 * p.Hp;
     item_state(tl);
@@ -1523,7 +1570,7 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
   };
   float hp0, hp1;
   if (tid < Cc) vbuf[3 * R + tid] = creg;         // sample 0: no history (vbuf is zero), its conditioning row
-  if (p.t0 > 0) {                                 // a continuation: the first step's history taps are rows of earlier launches
+  if (t0 > 0) {                                   // a continuation: the first step's history taps are rows of earlier launches
     vbuf[tid] = h0;
     vbuf[R + tid] = h1;
   }
@@ -1939,15 +1986,25 @@ static int launch_arc_generic(const ArcArgs& a, size_t lds, hipStream_t st, cons
   });
 }
 
+// W1 packets per GEMV thread of the sized kernels, and whether geometry d on C members takes one of them (launch_arc_sized's pairs)
+static int arc_nu(const wae_ar_desc* d) {
+  const int epl = wae_is16(d->dtype) ? 8 : 4;
+  return ((3 * d->R + (d->Cc > 0 ? d->Cc : 0) + epl - 1) / epl + 31) / 32;
+}
+static bool arc_sized_shape(const wae_ar_desc* d, int32_t C, int64_t ring_total) {
+  const int nu = arc_nu(d);
+  const bool pair = wae_is16(d->dtype) ? (nu == 3 || nu == 4) : (d->dtype == WAE_F32 && nu >= 6 && nu <= 8);
+  return C == 32 && d->R == 256 && d->S == 256 && d->O == 256 && d->G == 256 && d->ktaps == 3 && d->Cc <= 256 && ring_total % 4 == 0 &&
+         !d->coop_generic && pair;
+}
+
 // Which kernel decodes geometry d on C members: the reference's own geometry on 32 members takes the kernels with the sizes as constants
 // (NU = W1 packets per GEMV thread; residency as wae_ar_desc.resident_lds / resident_regs say), everything else the any-shape kernel.
 // list: the work-list forms (a.w_fused is null there).
 static int arc_dispatch(const wae_ar_desc* d, int32_t C, ArcArgs& a, const void* w_fused, bool list, hipStream_t st, const char* who) {
   const int epl = wae_is16(d->dtype) ? 8 : 4;
-  const int nu = ((3 * d->R + (d->Cc > 0 ? d->Cc : 0) + epl - 1) / epl + 31) / 32;
-  const bool fast_shape = C == 32 && d->R == 256 && d->S == 256 && d->O == 256 && d->G == 256 && d->ktaps == 3 && d->Cc <= 256 &&
-                          a.ring_total % 4 == 0 && !d->coop_generic;
-  if (fast_shape) {
+  const int nu = arc_nu(d);
+  if (arc_sized_shape(d, C, a.ring_total)) {
     a.w_fused = d->L >= 2 ? (const char*)w_fused : nullptr;     // the one-hand-over-per-layer kernel (else: ar_coop_fast_kernel's two)
     size_t lds_f = sizeof(float) * (size_t)(32 + 4 * nu * 32 * epl / 4 + 4 * 256 + 8 + 4 * (d->L + 1) + 3 * d->L + epl);
     // LDS-resident layers (16-bit, two hand-overs per layer): (nu + 2) x 16 B x 256 threads per layer behind the kernel's own arrays
@@ -2026,6 +2083,36 @@ extern "C" int wae_ar_generate_coop_list(const wae_ar_desc* d, int32_t C, int32_
   a.inputs = inputs; a.uniforms = uniforms; a.out_idx = out_idx; a.out_logits = out_logits;
   a.items = items; a.next = next; a.n_items = n_items;
   return arc_dispatch(d, C, a, nullptr, true, as_stream(stream), who);
+}
+
+// A work list of spans on cooperative teams: wae_ar_generate_coop_list with wae_ar_span records -- each carries its clip's ring and its
+// own t0 (include/wae.h); the kernels are the same LIST forms, which branch once per record.
+extern "C" int wae_ar_generate_coop_spans(const wae_ar_desc* d, int32_t C, int32_t n_spans, int32_t n_teams, const wae_ar_span* spans,
+                                          int32_t* next, int64_t total, const int32_t* dilations, const int64_t* ring_off, float* ring,
+                                          int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
+                                          const float* bias2, const float* zb, const float* first_tab, const float* first_bias,
+                                          const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
+                                          const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
+                                          uint64_t* msg, float* acc, int32_t* error, void* stream) {
+  const char* who = "ar_generate_coop_spans";
+  const ArNet net = AR_NET_OF_ARGS;
+  const ArcExchange x = {msg, acc, error};
+  AR_TRY(ar_check_net(who, d, net, out_idx != nullptr, false, ARC_THREADS));
+  AR_TRY(ar_check_class_ids(who, d, inputs, uniforms, out_logits, 2, true, "wae_ar_generate_scalar_spans"));
+  AR_TRY(ar_check_queue(who, spans, next, n_spans, "n_teams", n_teams, 8, "span"));
+  AR_TRY(ar_check_span_t0(who, d));
+  AR_TRY(ar_check_sequence(who, d, total, n_spans));
+  AR_TRY(ar_check_split(who, d, C, ARC_CMAX, ARC_THREADS, ring_total, x.ok(), nullptr));
+  ArcArgs a = arc_common_args(d, C, net, x);
+  a.B = n_teams; a.T = 0; a.t0 = 0; a.n_forced = 0; a.init_idx = 0;      // per span
+  a.inputs = inputs; a.uniforms = uniforms; a.out_idx = out_idx; a.out_logits = out_logits;
+  a.spans = spans; a.next = next; a.n_items = n_spans;
+  return arc_dispatch(d, C, a, nullptr, true, as_stream(stream), who);
+}
+
+extern "C" int64_t wae_ar_coop_ring_floats(const wae_ar_desc* d, int32_t C, int64_t ring_total) {
+  if (!d || C <= 0 || ring_total <= 0) return WAE_EINVAL;
+  return arc_sized_shape(d, C, ring_total) ? ring_total : (int64_t)C * ring_total;
 }
 
 // the operands of a scalar draw as the kernels read them: u_mix only where the decode samples, the draws under the name of their kind

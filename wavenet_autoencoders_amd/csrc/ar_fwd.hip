@@ -135,17 +135,20 @@ __device__ __forceinline__ void load_w<f16>(const char* p, float (&w)[8]) {
 
 // What one utterance adds to the launch's arguments: its ring slot, its zb row, its first step in the per-step operands (c_up,
 // inputs, uniforms, out_idx, ...; out_logits holds its (O, T) block at base * O) and its own length, forced prefix and start class.
-// ar_kernel decodes utterance blockIdx.x (base = b * T); ar_list_kernel one queue item after another.
+// ar_kernel decodes utterance blockIdx.x (base = b * T); ar_list_kernel one queue item after another; ar_span_kernel one queue span
+// after another, each in its clip's own ring from its own t0.
 struct ArUtt {
   float* ring;
   const float* zb;
   int64_t base;
   int T, n_forced, init_idx;
+  int t0;   // absolute index of the first step (wae_ar_desc.t0; a span's own): the ring holds the rows of steps [0, t0)
 };
 
 // One utterance from its first step to its last, by the whole workgroup.  Every LDS word the steps read is written here first, and a
 // ring row is read only behind its write in this very decode (the `tt >= 0` test below; a layer's (k-1)d+1 rows cover exactly the
-// steps t-(k-1)d .. t), so a workgroup may run this again and again in the same LDS and the same ring slot.
+// steps t-(k-1)d .. t), so a workgroup may run this again and again in the same LDS and the same ring slot.  With ut.t0 > 0 the rows
+// behind the first step are those an earlier call left in ut.ring (an earlier launch's: wae_ar_desc.t0, or an earlier span's).
 template <typename E>
 __device__ __forceinline__ void ar_decode(const ArArgs& p, const ArUtt& ut, float* sm) {
   constexpr int EPL = ET<E>::EPL;
@@ -211,7 +214,7 @@ __device__ __forceinline__ void ar_decode(const ArArgs& p, const ArUtt& ut, floa
       const int64_t roff = p.ring_off[l];
       const int rlen = (p.ktaps - 1) * d + 1;
       float* rl = ring + roff;
-      const int ta = p.t0 + t;                 // the step's absolute index: ring rows and the start of the clip count from the first launch
+      const int ta = ut.t0 + t;                // the step's absolute index: ring rows and the start of the clip count from the first launch
       // ---- assemble [x[t-(k-1)d] .. x[t]] and push x[t] into the layer's ring (conv.py:35-44, O(1)) -------
       for (int i = tid; i < p.ktaps * p.R; i += AR_THREADS) {
         const int tap = i / p.R, ch = i - tap * p.R;
@@ -356,7 +359,7 @@ template <typename E>
 __global__ void __launch_bounds__(AR_THREADS) ar_kernel(ArArgs p) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int b = blockIdx.x;
-  const ArUtt ut = {p.ring + (int64_t)b * p.ring_total, p.zb + (int64_t)b * p.L * 2 * p.Hp, (int64_t)b * p.T, p.T, p.n_forced, p.init_idx};
+  const ArUtt ut = {p.ring + (int64_t)b * p.ring_total, p.zb + (int64_t)b * p.L * 2 * p.Hp, (int64_t)b * p.T, p.T, p.n_forced, p.init_idx, p.t0};
   ar_decode<E>(p, ut, sm);
 }
 
@@ -389,7 +392,44 @@ __global__ void __launch_bounds__(AR_THREADS) ar_list_kernel(ArListArgs q) {
       // (wae_ar_generate_scalar_list) takes its forced prefix from inputs_f and has no start class: its start value is 0
       const bool forced = p.scalar ? p.inputs_f != nullptr : p.inputs != nullptr;
       const int nf = !forced ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
-      const ArUtt ut = {ring, p.zb + (int64_t)w.row * p.L * 2 * p.Hp, w.off, w.T, nf, p.scalar ? 0 : min(max(w.init_idx, 0), p.O - 1)};
+      const ArUtt ut = {ring, p.zb + (int64_t)w.row * p.L * 2 * p.Hp, w.off, w.T, nf, p.scalar ? 0 : min(max(w.init_idx, 0), p.O - 1), p.t0};
+      ar_decode<E>(p, ut, sm);
+    }
+    __syncthreads();               // every thread has read the word before thread 0 writes the next
+  }
+}
+
+// wae_ar_generate_spans / wae_ar_generate_scalar_spans: the queue of ar_list_kernel over spans -- runs of consecutive steps of clips that
+// live longer than a launch.  A span is decoded in ITS CLIP'S ring (p.ring + span.ring), not in a ring of the slot, from its own t0: ring
+// rows and the "before the clip starts" test use span.t0 + t (ar_decode, as under wae_ar_desc.t0), the per-step operands are indexed from
+// span.off.  Nothing is cleared: a history row is read only behind its own write, by absolute index, in this span or an earlier one.  A
+// continuation's first step is forced (its input is the previous span's last output, put at inputs[off] by the caller).
+struct ArSpanArgs {
+  ArArgs a;
+  const wae_ar_span* spans;
+  int32_t* next;
+  int n_spans;
+  int qword;   // as ArListArgs
+};
+
+template <typename E>
+__global__ void __launch_bounds__(AR_THREADS) ar_span_kernel(ArSpanArgs q) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const ArArgs& p = q.a;
+  int* taken = (int*)sm + q.qword;
+  for (;;) {
+    if (threadIdx.x == 0) *taken = atomicAdd(q.next, 1);
+    __syncthreads();
+    const int it = *taken;
+    if (it >= q.n_spans) return;   // the same word for every thread: the workgroup leaves together
+    const wae_ar_span w = q.spans[it];
+    if (w.T > 0) {
+      const int t0 = max(w.t0, 0);
+      const bool forced = p.scalar ? p.inputs_f != nullptr : p.inputs != nullptr;
+      int nf = !forced ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
+      if (forced && t0 > 0 && nf < 1) nf = 1;
+      const ArUtt ut = {p.ring + w.ring, p.zb + (int64_t)w.row * p.L * 2 * p.Hp, w.off, w.T, nf, p.scalar ? 0 : min(max(w.init_idx, 0), p.O - 1),
+                        t0};
       ar_decode<E>(p, ut, sm);
     }
     __syncthreads();               // every thread has read the word before thread 0 writes the next
@@ -398,11 +438,12 @@ __global__ void __launch_bounds__(AR_THREADS) ar_list_kernel(ArListArgs q) {
 
 #include "ar_host.hpp"
 
-struct ArList {   // the list entries' own arguments (who: the entry's name)
+struct ArList {   // the list entries' own arguments (who: the entry's name); spans: the records of a *_spans entry instead of items
   const wae_ar_item* items;
   int32_t* next;
   int n_items, n_slots;
   const char* who;
+  const wae_ar_span* spans;
 };
 
 // The operands of one form of the decode; whatever a form does not have stays null / zero.  Class ids: inputs, uniforms, out_idx, and
@@ -433,6 +474,12 @@ static int ar_launch(const wae_ar_desc* d, const ArNet& net, const ArOps& o, voi
   const size_t lds = sizeof(float) * (size_t)(ru(d->ktaps * d->R + (d->Cc > 0 ? d->Cc : 0), epl) + d->R + ru(H, epl) +
                                               2 * ru(d->S, epl) + ru(d->O, 4) + psz + 4);
   hipStream_t st = as_stream(stream);
+  if (list && list->spans) {
+    const ArSpanArgs q = {a, list->spans, list->next, list->n_items, (int)(lds / sizeof(float))};
+    return ar_by_dtype(d->dtype, [&](auto e) {
+      AR_LAUNCH(ar_span_kernel<typename decltype(e)::type>, dim3(list->n_slots), dim3(AR_THREADS), lds + 16, st, q, list->who);
+    });
+  }
   if (list) {
     // the queue word sits behind ar_decode's carve; per-utterance B, T, n_forced and init_idx come from the items
     const ArListArgs q = {a, list->items, list->next, list->n_items, (int)(lds / sizeof(float))};
@@ -476,7 +523,26 @@ extern "C" int wae_ar_generate_list(const wae_ar_desc* d, int32_t n_items, int32
   AR_TRY(ar_check_t0(who, d, inputs, true));
   ArOps o = {};
   o.inputs = inputs; o.uniforms = uniforms; o.out_idx = out_idx; o.out_logits = out_logits; o.log_scale_min = -7.0f;
-  const ArList list = {items, next, n_items, n_slots, who};
+  const ArList list = {items, next, n_items, n_slots, who, nullptr};
+  return ar_launch(d, net, o, stream, &list);
+}
+
+// A work list of spans of class-id clips on the one-CU kernel (include/wae.h): wae_ar_generate_list's checks and operands, ar_span_kernel.
+extern "C" int wae_ar_generate_spans(const wae_ar_desc* d, int32_t n_spans, int32_t n_slots, const wae_ar_span* spans, int32_t* next,
+                                     const int32_t* dilations, const int64_t* ring_off, float* ring, int64_t ring_total,
+                                     const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes, const float* bias2,
+                                     const float* zb, const float* first_tab, const float* first_bias, const void* w_head,
+                                     const float* head_bias, const void* c_up, int32_t c_dtype, const int32_t* inputs,
+                                     const float* uniforms, int32_t* out_idx, float* out_logits, void* stream) {
+  const char* who = "ar_generate_spans";
+  const ArNet net = AR_NET_OF_ARGS;
+  AR_TRY(ar_check_net(who, d, net, out_idx != nullptr, false, 0));
+  AR_TRY(ar_check_queue(who, spans, next, n_spans, "n_slots", n_slots, 0, "span"));
+  AR_TRY(ar_check_class_ids(who, d, inputs, uniforms, out_logits, 2, true, "wae_ar_generate_scalar_spans"));
+  AR_TRY(ar_check_span_t0(who, d));
+  ArOps o = {};
+  o.inputs = inputs; o.uniforms = uniforms; o.out_idx = out_idx; o.out_logits = out_logits; o.log_scale_min = -7.0f;
+  const ArList list = {nullptr, next, n_spans, n_slots, who, spans};
   return ar_launch(d, net, o, stream, &list);
 }
 
@@ -533,6 +599,29 @@ extern "C" int wae_ar_generate_scalar_list(const wae_ar_desc* d, int32_t dist, i
   ArOps o = {};
   o.out_logits = out_params; o.inputs_f = inputs_f; o.u_mix = sampled ? u_mix : nullptr; (dist == 0 ? o.u_log : o.z) = draws;
   o.out_f = out_samples; o.log_scale_min = log_scale_min; o.clamp_log_scale = dist == 0 ? clamp_log_scale : 0; o.dist = dist;
-  const ArList list = {items, next, n_items, n_slots, who};
+  const ArList list = {items, next, n_items, n_slots, who, nullptr};
+  return ar_launch(d, net, o, stream, &list);
+}
+
+// ... and of spans of scalar-input clips: wae_ar_generate_scalar_list's checks and operands, ar_span_kernel.
+extern "C" int wae_ar_generate_scalar_spans(const wae_ar_desc* d, int32_t dist, int32_t n_spans, int32_t n_slots, const wae_ar_span* spans,
+                                            int32_t* next, const int32_t* dilations, const int64_t* ring_off, float* ring,
+                                            int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes, int64_t w2_off_bytes,
+                                            const float* bias2, const float* zb, const float* first_tab, const float* first_bias,
+                                            const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
+                                            const float* inputs_f, const float* u_mix, const float* draws, float log_scale_min,
+                                            int32_t clamp_log_scale, float* out_samples, float* out_params, void* stream) {
+  const char* who = "ar_generate_scalar_spans";
+  const ArNet net = AR_NET_OF_ARGS;
+  const ArDraw w = {inputs_f, u_mix, draws, out_samples, out_params};
+  AR_TRY(ar_check_net(who, d, net, true, false, 0));
+  AR_TRY(ar_check_mixture(who, d, dist, w, true, true));
+  AR_TRY(ar_check_queue(who, spans, next, n_spans, "n_slots", n_slots, 0, "span"));
+  AR_TRY(ar_check_span_t0(who, d));
+  const bool sampled = dist == 0 ? (u_mix && draws) : draws != nullptr;
+  ArOps o = {};
+  o.out_logits = out_params; o.inputs_f = inputs_f; o.u_mix = sampled ? u_mix : nullptr; (dist == 0 ? o.u_log : o.z) = draws;
+  o.out_f = out_samples; o.log_scale_min = log_scale_min; o.clamp_log_scale = dist == 0 ? clamp_log_scale : 0; o.dist = dist;
+  const ArList list = {nullptr, next, n_spans, n_slots, who, spans};
   return ar_launch(d, net, o, stream, &list);
 }

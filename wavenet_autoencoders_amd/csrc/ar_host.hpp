@@ -120,11 +120,12 @@ static int ar_check_t0(const char* who, const wae_ar_desc* d, const void* forced
   return WAE_OK;
 }
 
-// The queue of a work list.  max_slots > 0: the bound on `slots` (teams, one XCD each).
-static int ar_check_queue(const char* who, const wae_ar_item* items, const int32_t* next, int n_items, const char* slots_name, int n_slots,
-                          int max_slots) {
-  AR_REQUIRE(items && next, "the item array and the queue counter are required");
-  AR_REQUIRE(n_items >= 1, "n_items %d < 1", n_items);
+// The queue of a work list.  max_slots > 0: the bound on `slots` (teams, one XCD each).  what: the records' name ("item"; "span" for
+// the *_spans entries, whose records are wae_ar_span).
+static int ar_check_queue(const char* who, const void* items, const int32_t* next, int n_items, const char* slots_name, int n_slots,
+                          int max_slots, const char* what = "item") {
+  AR_REQUIRE(items && next, "the %s array and the queue counter are required", what);
+  AR_REQUIRE(n_items >= 1, "n_%ss %d < 1", what, n_items);
   if (max_slots > 0) AR_REQUIRE(n_slots >= 1 && n_slots <= max_slots, "%s %d outside 1..%d (one XCD each)", slots_name, n_slots, max_slots);
   else AR_REQUIRE(n_slots >= 1, "%s %d < 1", slots_name, n_slots);
   return WAE_OK;
@@ -149,6 +150,12 @@ static int ar_check_split(const char* who, const wae_ar_desc* d, int C, int cmax
 static int ar_check_sequence(const char* who, const wae_ar_desc* d, int64_t total, int n_items) {
   AR_REQUIRE(total >= 0 && (total + n_items + 1) <= (((int64_t)1 << 31) - 1) / (d->L + 4),
              "%lld steps in %d items on %d layers: the exchange sequence numbers would not fit 31 bits", (long long)total, n_items, d->L);
+  return WAE_OK;
+}
+
+// A work list of spans (wae_ar_generate_spans and its kin): every record carries its own t0, so the descriptor's stays 0.
+static int ar_check_span_t0(const char* who, const wae_ar_desc* d) {
+  AR_REQUIRE(d->t0 == 0, "t0 %d: every span carries its own t0; the descriptor's must be 0", d->t0);
   return WAE_OK;
 }
 

@@ -63,6 +63,304 @@ class _ArDecode:
     last: Optional[torch.Tensor] = None     # (B,) the previous launch's last output
 
 
+# include/wae.h: wae_ar_span, as the host packs it
+_AR_SPAN = np.dtype([("off", "<i8"), ("ring", "<i8"), ("T", "<i4"), ("t0", "<i4"), ("n_forced", "<i4"), ("init_idx", "<i4"),
+                     ("row", "<i4"), ("reserved", "<i4")])
+
+
+@dataclasses.dataclass
+class _ArClip:
+    """One clip of a DecodeSession between add() and its last step: what _ar_open fixes once per decode, kept per clip."""
+    T: int
+    slot: int                       # the clip's ring and zb row in the session's tables
+    c_up: Optional[torch.Tensor]    # (T, Ccp) conditioning rows of the whole clip
+    forced: Optional[torch.Tensor]  # the forced prefix (class ids, or floats of a scalar-input decoder)
+    n_forced: int
+    init: int
+    uni: Optional[torch.Tensor]     # (T,) uniforms of the categorical draw
+    u_mix: Optional[torch.Tensor]   # (T, M) / (T,) draws of a scalar-input decoder
+    draw: Optional[torch.Tensor]
+    pos: int = 0                    # steps decoded so far = t0 of the next span
+    last: Optional[torch.Tensor] = None     # (1,) the previous span's last output, on the device
+
+
+class DecodeSession:
+    """WaeEngine.decode_session: clips of any lengths that join at any time and decode in rounds, one launch per round (include/wae.h:
+    wae_ar_generate_spans, wae_ar_generate_scalar_spans, wae_ar_generate_coop_spans).  add() does once per clip what a decode does once
+    (the conditioning rows of the whole clip, the speaker row, the clip's own history ring, the draws of all its steps); step() decodes
+    the next span of every live clip in one launch and returns the spans' outputs; a clip's outputs, concatenated over the rounds, are
+    bit for bit its single decode (incremental_forward alone: on the one-CU kernel for coop=False, on the cooperative path for
+    coop=True), whatever the chunking and whichever slot or team took which span."""
+
+    def __init__(self, eng, mode="sample", coop=False, slots=None, teams=None, want_logits=False, c_is_upsampled=False,
+                 log_scale_min=-7.0, clamp_log_scale=False):
+        g = eng.g
+        if g.scalar_input and coop:
+            raise NotImplementedError("decode_session(coop=True): scalar-input decoders decode their sessions on the one-CU slots "
+                                      "(coop=False); the team form of the scalar span list does not exist yet")
+        if coop and max(g.R, g.S, g.O) > 256:
+            raise ValueError(f"decode_session(coop=True): the cooperative kernels take R, S and O <= 256 (got {g.R}, {g.S}, {g.O}); "
+                             "use the one-CU slots (coop=False)")
+        modes = {"logits": 0, "sample": 2} if g.scalar_input else {"logits": 0, "argmax": 1, "sample": 2}
+        if mode not in modes:
+            raise ValueError(f"decode_session: mode '{mode}' is not decoded in spans; use " + ", ".join(f"'{k}'" for k in modes))
+        self.eng, self.mode, self.coop, self.want = eng, modes[mode], bool(coop), bool(want_logits) or modes[mode] == 0
+        self.c_is_upsampled, self.log_scale_min, self.clamp = bool(c_is_upsampled), float(log_scale_min), int(bool(clamp_log_scale))
+        self._slots, self._teams = slots, teams
+        self.clips: Dict[int, _ArClip] = {}
+        self._next_handle, self._gids, self._closed, self._open = 0, None, False, False
+        self._keep = None
+
+    # ---- the session's device state: once, at the first add
+    def _open_device(self):
+        eng, g = self.eng, self.eng.g
+        if not eng._ar_packed or eng.weights_dirty:
+            eng.pack_ar_weights()
+        if self._open:
+            return
+        dev = eng.device
+        if self.coop:
+            self.nslots = max(1, min(8 if self._teams is None else int(self._teams), 8))
+        else:
+            self.nslots = (torch.cuda.get_device_properties(dev).multi_processor_count if self._slots is None
+                           else max(1, int(self._slots)))
+        path = (int(eng.ar_generic), eng.ar_resident[0], eng.ar_resident[1]) if self.coop else ()
+        self.d = L.ArDesc(eng.dt, 0, 0, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, self.mode, 0,
+                          int(g.scalar_input), math.sqrt(1.0 / g.layers), 0, *path)
+        self.C, per = 1, eng.ar_ring_total
+        self.msg = self.acc = self.err = None
+        if self.coop:
+            self.C = max(1, min(eng.opt.ar_coop_c, 32, g.H, g.S))       # as _ar_open
+            per = int(eng.lib.wae_ar_coop_ring_floats(ctypes.byref(self.d), self.C, eng.ar_ring_total))
+            assert per > 0, per
+            self.msg, self.acc, self.err = eng._ar_exchange(self.d, self.C, self.nslots, torch.empty)      # zeroed before every launch
+        self.ring_floats = (per + 3) // 4 * 4       # span.ring is a multiple of 4 floats
+        self.cap, self.free = 0, []
+        self.ring = torch.empty(0, dtype=torch.float32, device=dev)
+        self.zb = torch.empty(0, g.layers, 2 * g.Hp, dtype=torch.float32, device=dev)
+        self.normal = g.scalar_input and g.output_distribution == "Normal"
+        self.M = (1 if (self.normal and g.O == 2) else g.O // 3) if g.scalar_input else 0
+        self._open = True
+
+    def reserve(self, n):
+        """Room for n clips at once in the ring and speaker-row tables (they grow on demand; growing copies the live clips' rings)."""
+        self._open_device()
+        n = int(n)
+        if n <= self.cap:
+            return
+        # never zeroed: a span reads a history row only behind its own write of it, or -- the constant-size cooperative kernels -- behind
+        # the clearing its clip's first span makes
+        ring = torch.empty(n * self.ring_floats, dtype=torch.float32, device=self.eng.device)
+        zb = torch.empty(n, *self.zb.shape[1:], dtype=torch.float32, device=self.eng.device)
+        ring[:self.ring.numel()] = self.ring
+        zb[:self.cap] = self.zb
+        self.free += list(range(n - 1, self.cap - 1, -1))
+        self.ring, self.zb, self.cap = ring, zb, n
+
+    @property
+    def live(self):
+        """handles of the clips that still have steps to decode, in the order they were added"""
+        return list(self.clips)
+
+    def _check(self, item):
+        """decode_list's / decode_list_scalar's checks of one item, before anything is allocated -> (T, forced, n_forced, init, given)"""
+        eng, g, dev = self.eng, self.eng.g, self.eng.device
+        T = int(item["T"])
+        if T < 1:
+            raise ValueError(f"decode_session.add: every clip has at least one step (got {T})")
+        gid = item.get("gid")
+        if self._gids is not None and (gid is not None) != self._gids:
+            raise ValueError("decode_session.add: give every item a gid, or none")
+        if g.Ccp and item.get("c") is None:
+            raise ValueError(f"decode_session.add: the item has no conditioning c, the decoder has {g.Cc} conditioning channels")
+        ti = item.get("test_inputs")
+        if ti is not None:
+            ti = torch.as_tensor(ti).reshape(-1).to(dev, torch.float32 if g.scalar_input else torch.int32)[:T]
+        nf = 0 if ti is None else int(ti.numel())
+        if self.mode == 0 and nf < T:
+            raise ValueError(f"decode_session.add: mode 'logits' is teacher-forced: test_inputs must cover all {T} steps")
+        init, given = 0, False
+        if g.scalar_input:
+            normal = g.output_distribution == "Normal"
+            M = 1 if (normal and g.O == 2) else g.O // 3
+            um, ul, z = item.get("u_mix"), item.get("u_log"), item.get("z")
+            if normal and ul is not None:
+                raise ValueError("decode_session.add: output_distribution 'Normal' draws from u_mix and z, not u_log")
+            if not normal and z is not None:
+                raise ValueError("decode_session.add: output_distribution 'Logistic' draws from u_mix and u_log, not z")
+            if not normal and (um is None) != (ul is None):
+                raise ValueError("decode_session.add: u_mix and u_log come together")
+            if normal and z is not None and M > 1 and um is None:
+                raise ValueError(f"decode_session.add: {M} Gaussians need u_mix beside z")
+            given = (z if normal else ul) is not None
+        else:
+            init = item.get("init_idx")
+            init = 127 if init is None else int(torch.as_tensor(init).reshape(-1)[0])
+            if nf == 0 and not 0 <= init < g.O:
+                # wavenet.py:288 writes a one at the start class of the start vector: the same IndexError when there are fewer classes
+                raise IndexError(f"index {init} is out of bounds for dimension 2 with size {g.O}")
+            if nf and (int(ti.min()) < 0 or int(ti.max()) >= g.O):
+                raise IndexError(f"decode_session.add: test_inputs hold a class id outside [0, {g.O})")
+            init = init if nf == 0 else 0
+        return T, (ti if nf else None), nf, init, given
+
+    def add(self, item):
+        """A clip joins: `item` is decode_list's / decode_list_scalar's mapping (T, c, gid, test_inputs, uniforms or u_mix / u_log / z,
+        init_idx).  Legal at any time between two step() calls.  Returns the clip's handle."""
+        if self._closed:
+            raise RuntimeError("decode_session: the session is closed")
+        T, forced, nf, init, given = self._check(item)
+        eng, g, dev = self.eng, self.eng.g, self.eng.device
+        self._open_device()
+        gid = item.get("gid")
+        flat = lambda a: torch.as_tensor(a).reshape(-1).to(dev, torch.float32)  # noqa: E731
+        c_up = None
+        if g.Ccp:
+            c = torch.as_tensor(item["c"]).to(dev, torch.float32)
+            c = (c if c.dim() == 3 else c[None]).contiguous()
+            c_up = torch.zeros(T, g.Ccp, dtype=eng.tdtype, device=dev)
+            eng._ar_cond_rows(c, c_up.view(1, T, g.Ccp), self.c_is_upsampled, "decode_session.add: ")
+        gid32 = None
+        if gid is not None:
+            gid32 = torch.tensor([int(torch.as_tensor(gid).reshape(-1)[0])], dtype=torch.int32, device=dev)
+        zb = eng._ar_speaker_rows(1, gid32)
+        uni = um = dr = None
+        if g.scalar_input:
+            if self.mode == 2:
+                um, dr = item.get("u_mix"), item.get("z" if self.normal else "u_log")
+                if not given:
+                    um, dr = eng.scalar_draws(T)
+                if not self.normal or self.M > 1:
+                    um = flat(um)
+                    assert um.numel() == T * self.M, f"decode_session.add: u_mix holds {um.numel()} values for {T} steps of {self.M} mixtures"
+                    um = um.view(T, self.M).contiguous()
+                else:
+                    um = None
+                dr = flat(dr).contiguous()
+                assert dr.numel() == T, f"decode_session.add: {dr.numel()} draws for {T} steps"
+        elif self.mode == 2:
+            u = item.get("uniforms")
+            uni = (torch.rand(1, T, device=dev) if u is None else flat(u)).reshape(-1).contiguous()
+            assert uni.numel() == T, f"decode_session.add: {uni.numel()} uniforms for {T} steps"
+        if not self.free:
+            self.reserve(max(2 * self.cap, self.nslots, 8))
+        slot = self.free.pop()
+        self.zb[slot] = zb[0]
+        self._gids = gid is not None
+        h = self._next_handle
+        self._next_handle += 1
+        self.clips[h] = _ArClip(T=T, slot=slot, c_up=c_up, forced=forced, n_forced=nf, init=init, uni=uni, u_mix=um, draw=dr)
+        eng.hold("session_add", gid32, zb)
+        return h
+
+    def drop(self, handle):
+        """Cancels a clip: it leaves the session and its ring is free for the next add."""
+        c = self.clips.pop(handle)
+        self.free.append(c.slot)
+
+    def step(self, chunk):
+        """One launch: the next min(chunk, remaining) steps of every live clip (`chunk`: an int, or a mapping from handle to steps -- a
+        clip the mapping leaves out sits the round out).  Returns {handle: dict(idx | x, logits, done)} for the clips that decoded: the
+        span's class ids (n,) int32 or samples (n,) fp32, its logits / mixture parameters (O, n) where asked for, and whether the clip
+        has finished -- it has then left the session.  The forced first input of a continuation comes from the previous round's output
+        on the device; only the team path reads one word back per launch (the time-out flag)."""
+        if self._closed:
+            raise RuntimeError("decode_session: the session is closed")
+        handles = list(self.clips)
+        if not handles:
+            return {}
+        if not isinstance(chunk, (int, np.integer)):
+            chunk = {handles.index(h): int(n) for h, n in dict(chunk).items()}
+        clips = [self.clips[h] for h in handles]
+        plan = P.ar_round_plan([c.T - c.pos for c in clips], [c.pos for c in clips], chunk, self.nslots)
+        if plan.total == 0:
+            return {}
+        eng, g, dev, lib, d = self.eng, self.eng.g, self.eng.device, self.eng.lib, self.d
+        sel = [clips[int(i)] for i in plan.clips]
+        ns, offs, total = [int(x) for x in plan.lengths], [int(x) for x in plan.offsets], plan.total
+        cut = lambda name: torch.cat([getattr(c, name)[c.pos:c.pos + n] for c, n in zip(sel, ns)])  # noqa: E731
+        c_up = cut("c_up") if g.Ccp else None
+        # the forced steps: a clip's forced prefix where the span lies in it, else -- a continuation -- the previous span's last output
+        nfs, inputs = [], None
+        if any(c.pos > 0 or c.n_forced > 0 for c in sel):
+            inputs = torch.zeros(total, dtype=torch.float32 if g.scalar_input else torch.int32, device=dev)
+            dst, src = [], []
+            for c, n, off in zip(sel, ns, offs):
+                k = max(0, min(n, c.n_forced - c.pos))
+                if k > 0:
+                    inputs[off:off + k] = c.forced[c.pos:c.pos + k]
+                elif c.pos > 0:
+                    dst.append(off)
+                    src.append(c.last)
+                    k = 1
+                nfs.append(k)
+            if dst:
+                inputs.index_copy_(0, torch.tensor(dst, dtype=torch.int64, device=dev), torch.cat(src))
+        else:
+            nfs = [0] * len(sel)
+        rec = np.zeros(len(sel), dtype=_AR_SPAN)
+        assert rec.dtype.itemsize == ctypes.sizeof(L.ArSpan)
+        for k, j in enumerate(plan.order):
+            c = sel[int(j)]
+            rec[k] = (offs[j], c.slot * self.ring_floats, ns[j], c.pos, nfs[j], c.init, c.slot, 0)
+        spans = torch.from_numpy(rec.view(np.uint8)).to(dev)
+        nxt = torch.zeros(1, dtype=torch.int32, device=dev)
+        logits = torch.empty(total * g.O, dtype=torch.float32, device=dev) if self.want else None
+        st, net = eng.stream(), eng._ar_net_args(self.ring, self.zb, c_up)
+        if g.scalar_input:
+            sampled = self.mode == 2
+            um = cut("u_mix") if sampled and (not self.normal or self.M > 1) else None
+            dr = cut("draw") if sampled else None
+            out = torch.empty(total, dtype=torch.float32, device=dev) if sampled else None
+            L.check(lib.wae_ar_generate_scalar_spans(ctypes.byref(d), int(self.normal), len(sel), plan.slots, L.ptr(spans), L.ptr(nxt), *net,
+                                                     L.ptr(inputs), L.ptr(um), L.ptr(dr), self.log_scale_min, self.clamp, L.ptr(out),
+                                                     L.ptr(logits), st), "ar_generate_scalar_spans")
+            key, keep = "x", (um, dr)
+        else:
+            uni = cut("uni") if self.mode == 2 else None
+            out = torch.empty(total, dtype=torch.int32, device=dev)
+            operands = (L.ptr(inputs), L.ptr(uni), L.ptr(out), L.ptr(logits))
+            if self.coop:
+                self.msg.zero_()
+                self.acc.zero_()
+                self.err.zero_()
+                L.check(lib.wae_ar_generate_coop_spans(ctypes.byref(d), self.C, len(sel), plan.slots, L.ptr(spans), L.ptr(nxt), total, *net,
+                                                       *operands, L.ptr(self.msg), L.ptr(self.acc), L.ptr(self.err), st),
+                        "ar_generate_coop_spans")
+            else:
+                L.check(lib.wae_ar_generate_spans(ctypes.byref(d), len(sel), plan.slots, L.ptr(spans), L.ptr(nxt), *net, *operands, st),
+                        "ar_generate_spans")
+            key, keep = "idx", (uni,)
+        self._keep = (spans, nxt, c_up, inputs, out, logits) + keep     # the launch's operands live until the next round's
+        if self.coop:
+            eng._ar_check_exchange(self.err, "ar_generate_coop_spans")
+        res = {}
+        for i, c, n, off in zip(plan.clips, sel, ns, offs):
+            h = handles[int(i)]
+            c.pos += n
+            if out is not None:
+                c.last = out[off + n - 1:off + n]
+            done = c.pos >= c.T
+            res[h] = {key: None if out is None else out[off:off + n],
+                      "logits": logits[off * g.O:(off + n) * g.O].view(g.O, n) if self.want else None, "done": done}
+            if done:
+                self.drop(h)
+        return res
+
+    def close(self):
+        """Frees everything: the clips, their rings and the exchange buffers.  Results already returned stay valid."""
+        self.clips.clear()
+        self._closed = True
+        self.ring = self.zb = self.msg = self.acc = self.err = self._keep = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
 class WaeEngine:
     def __init__(self, geom: P.Geometry, dtype="bf16", device="cuda:0", dropout: float = 0.0, drop_seed: int = 0x5EED):
         """dtype: 'fp32' (exact, the parity mode), 'bf16' (default throughput mode) or 'fp16' (BASELINE config C5) storage of
@@ -1253,6 +1551,46 @@ class WaeEngine:
             self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, um_d, dr_d)
         return [dict(x=xs[off[i]:off[i] + Ts[i]] if sampled else None,
                      logits=params[off[i] * g.O:(off[i] + Ts[i]) * g.O].view(g.O, Ts[i]) if want else None) for i in range(n)]
+
+    def decode_session(self, mode: str = "sample", coop: bool = False, slots: Optional[int] = None, teams: Optional[int] = None,
+                       want_logits: bool = False, c_is_upsampled: bool = False, log_scale_min: float = -7.0,
+                       clamp_log_scale: bool = False) -> DecodeSession:
+        """A decode session: decode_list's ragged clips, streamed (include/wae.h: the wae_ar_generate*_spans entries).  Clips join with
+        sess.add(item) at any time between two rounds, sess.step(chunk) decodes the next `chunk` steps of every live clip in ONE launch
+        and returns them per clip, sess.drop(handle) cancels a clip, sess.close() (or leaving the `with` block) frees everything.
+        Every clip keeps its own history ring between the launches, so a span runs on whichever slot or team is free; a clip's chunks,
+        concatenated, are bit for bit decode_list's result for it -- that is incremental_forward for the clip alone, on the one-CU
+        kernel (coop=False) or on the cooperative path (coop=True, WAE_AR_COOP=1, the same ar_path; one_handover is ignored).
+        mode, slots, teams, want_logits, c_is_upsampled: as decode_list; log_scale_min / clamp_log_scale: as decode_list_scalar.
+        Class-id decoders decode on `slots` one-CU workgroups or, coop=True, on `teams` cooperative teams (ar_path(generic=,
+        lds_layers=, reg_layers=) honoured as in decode_list).  Scalar-input decoders decode on the slots in modes "logits" / "sample"
+        (in "logits" the mixture parameters come back and x is None); coop=True raises NotImplementedError there.  ValueError: R, S or
+        O > 256 with coop=True; a mode the matching list call does not take."""
+        return DecodeSession(self, mode=mode, coop=coop, slots=slots, teams=teams, want_logits=want_logits, c_is_upsampled=c_is_upsampled,
+                             log_scale_min=log_scale_min, clamp_log_scale=clamp_log_scale)
+
+    def decode_list_stream(self, items, chunk, **kw):
+        """decode_list / decode_list_scalar in rounds of `chunk` steps: a generator over the rounds of a decode_session(**kw) that holds
+        the fixed list `items`.  Every round yields a list in the caller's order: the clip's dict(idx | x, logits, done) for this
+        round, None for a clip that finished in an earlier round.  chunk: an int, or a mapping from list index to steps.  The draws of
+        clips that bring none are made when the generator starts, clip after clip in the caller's order -- a seeded stream equals the
+        seeded list.  Closing the generator early frees the session."""
+        items = list(items)
+        if not items:
+            raise ValueError("decode_list_stream: an empty list")
+        sess = self.decode_session(**kw)
+        return self._ar_list_rounds(sess, items, chunk)
+
+    def _ar_list_rounds(self, sess, items, chunk):
+        with sess:
+            sess.reserve(len(items))
+            hs = [sess.add(it) for it in items]
+            while sess.live:
+                n = chunk if isinstance(chunk, (int, np.integer)) else {hs[int(i)]: v for i, v in dict(chunk).items() if hs[int(i)] in sess.clips}
+                res = sess.step(n)
+                if not res:
+                    raise ValueError("decode_list_stream: the chunk mapping leaves every live clip out")
+                yield [res.get(h) for h in hs]
 
     # ------------------------------------------------------------------ full autoencoder
     def forward(self, x: torch.Tensor, c: torch.Tensor, gid: Optional[torch.Tensor], targets=None, lengths=None,

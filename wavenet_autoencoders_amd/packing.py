@@ -476,6 +476,53 @@ def ar_list_plan(lengths, slots: int) -> ArListPlan:
     return ArListPlan(order, offsets, int(n.sum()), slots, max(free))
 
 
+class ArRoundPlan(NamedTuple):
+    """ar_round_plan's answer: one span per clip that decodes in this round.  clips: the indices (into the planner's arguments) of those
+    clips, in the caller's order; lengths / t0: steps and absolute first step of each clip's span; offsets: first step of each span in
+    the round's packed per-step operands (contiguous, in `clips` order); order: positions in `clips` in launch order; total: the sum
+    of the lengths (the length of the packed operands); slots: workgroups or teams to launch."""
+    clips: np.ndarray
+    lengths: np.ndarray
+    t0: np.ndarray
+    offsets: np.ndarray
+    order: np.ndarray
+    total: int
+    slots: int
+
+
+def ar_round_plan(remaining, positions, chunk, slots: int) -> ArRoundPlan:
+    """One round of a decode session (include/wae.h: wae_ar_generate_spans): which clips get a span, how long, and in what order.
+    remaining[i] / positions[i]: steps clip i still has to decode and the absolute index of its next step.  chunk: steps per clip and
+    round -- an int for every clip, or a mapping from clip index to steps (a clip the mapping leaves out, or gives < 1, sits the round
+    out).  A clip gets min(chunk, remaining) steps; a finished clip (remaining < 1) gets no span and is absent from the plan.  The
+    launch order is longest span first, equal lengths in the caller's order (a stable sort, as ar_list_plan); slots is clamped to the
+    number of spans (at least 1)."""
+    rem = np.asarray(remaining, dtype=np.int64).reshape(-1)
+    pos = np.asarray(positions, dtype=np.int64).reshape(-1)
+    if rem.size != pos.size:
+        raise ValueError(f"ar_round_plan: {rem.size} remaining lengths for {pos.size} positions")
+    if int(slots) < 1:
+        raise ValueError(f"ar_round_plan: slots {int(slots)} < 1")
+    if pos.size and int(pos.min()) < 0:
+        raise ValueError("ar_round_plan: a negative position")
+    if isinstance(chunk, (int, np.integer)):
+        if int(chunk) < 1:
+            raise ValueError(f"ar_round_plan: chunk {int(chunk)} < 1")
+        want = np.full(rem.size, int(chunk), dtype=np.int64)
+    else:
+        want = np.zeros(rem.size, dtype=np.int64)
+        for i, n in dict(chunk).items():
+            if not 0 <= int(i) < rem.size:
+                raise ValueError(f"ar_round_plan: chunk names clip {int(i)} of {rem.size}")
+            want[int(i)] = max(int(n), 0)
+    n = np.minimum(want, np.maximum(rem, 0))
+    clips = np.nonzero(n > 0)[0].astype(np.int64)
+    n = n[clips]
+    order = np.argsort(-n, kind="stable").astype(np.int64)
+    offsets = (np.concatenate([[0], np.cumsum(n)[:-1]]) if n.size else np.zeros(0)).astype(np.int64)
+    return ArRoundPlan(clips, n, pos[clips], offsets, order, int(n.sum()), max(1, min(int(slots), int(n.size))))
+
+
 # ---------------------------------------------------------------------------------------------------
 # backward: where the weight-gradient launches go (backward.py builds the tables; the rules are here,
 # plain Python, so that they run without a device)
