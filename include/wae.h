@@ -357,7 +357,21 @@ typedef struct wae_ar_desc {
   int32_t L, R, Rp, G, Hp, S, O, Cc, Ccp, ktaps;
   int32_t mode;
   int32_t init_idx;
-  int32_t scalar_input; /* 0: wae_ar_generate / wae_ar_generate_coop; 1: wae_ar_generate_scalar[_mog] / wae_ar_generate_coop_scalar / the two *_scalar_list entries */
+  int32_t scalar_input; /* 0: wae_ar_generate / wae_ar_generate_coop; 1: wae_ar_generate_scalar[_mog] / wae_ar_generate_coop_scalar / the two *_scalar_list entries
+                         * 2: a scalar-input decoder, as 1, that asks for the constant-size scalar kernels ("scalar sized"; the struct keeps
+                         *    its size and its last field t0, so the request travels in this field).  Read by the scalar cooperative
+                         *    entries only (wae_ar_generate_coop_scalar, _coop_scalar_list, _coop_scalar_spans); every other entry reads 2 as 1
+                         *    and a class-id descriptor (0) has no such request: class-id entries ignore it.
+                         *    1: the any-shape kernel, always (the routing before the value existed).
+                         *    2: the constant-size scalar kernels (csrc/ar_coop.hip: ar_coop_fast_body<.., SCALAR>, two hand-overs per layer)
+                         *    where C == 32, R = G = S = 256, 3 taps, Cc <= 256, ring_total % 4 == 0, !coop_generic, O <= 256 and the (dtype,
+                         *    packets per thread) pair has one -- with resident_lds / resident_regs honoured as by wae_ar_generate_coop -- and
+                         *    silently the any-shape kernel otherwise.  The members then share ONE ring of ring_total floats
+                         *    (wae_ar_coop_ring_floats), which the launch clears when t0 == 0.
+                         *    The three entries dispatch by this one rule and run one device function, so a clip's items and spans are
+                         *    bit for bit its single decode at the same value; values 1 and 2 agree to rounding, not bitwise (the sums are
+                         *    split differently).  There is no one-hand-over (wae_ar_generate_coop_fused) scalar form and no constant-size kernel
+                         *    for C != 32 or other widths. */
   float scale;          /* sqrt(1/L) */
   int32_t n_forced;     /* with inputs: steps t < n_forced consume inputs[t], later steps the fed-back output
                            (test_inputs shorter than T, wavenet.py:300-305); <= 0 or >= T: every step is forced */
@@ -509,9 +523,10 @@ int wae_ar_generate_coop_fused(const wae_ar_desc* d, int32_t C, const int32_t* d
  * M == 1) and draws = z (B,T), O == 2 or 3M, log scale unclamped (log_scale_min and clamp_log_scale unused).  It is the arithmetic of
  * wae_dmol_sample / wae_mog_sample on the returned parameters, bit for bit.  mode 0: inputs_f (B,T) teacher-forces every step;
  * mode 2: the draws are required, inputs_f (optional) forces steps t < desc.n_forced and the start value is inputs_f[0] (0 without
- * it).  out_samples (B,T) and/or out_params (B,O,T), written by member 0.  Always the any-shape kernel: B <= 8, C in 1..32, R, S and
- * O <= 256; the split of the sums differs from the one-CU kernel's, so the two agree to rounding, not bitwise; error[0] != 0
- * afterwards means a wait timed out. */
+ * it).  out_samples (B,T) and/or out_params (B,O,T), written by member 0.  B <= 8, C in 1..32, R, S and O <= 256.  The any-shape kernel
+ * unless wae_ar_desc.scalar_input = 2 and the shape select the constant-size scalar kernels (see the field; t0 > 0 continuations go
+ * through their resume prologue); the split of the sums differs from the one-CU kernel's and between the two kernel forms, so these
+ * agree to rounding, not bitwise; error[0] != 0 afterwards means a wait timed out. */
 int wae_ar_generate_coop_scalar(const wae_ar_desc* d, int32_t C, int32_t dist, const int32_t* dilations, const int64_t* ring_off,
                                 float* ring, int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes,
                                 int64_t w2_off_bytes, const float* bias2, const float* zb, const float* first_tab,
@@ -532,10 +547,12 @@ int wae_ar_generate_coop_scalar(const wae_ar_desc* d, int32_t C, int32_t dist, c
  * wae_ar_generate_scalar_list (csrc/ar_fwd.hip: ar_list_kernel over scalar items): n_slots workgroups, ring n_slots x ring_total; an
  * item's samples and parameters are wae_ar_generate_scalar's / wae_ar_generate_scalar_mog's for that utterance alone, bit for bit (the
  * same device function), whichever slot decodes it and in whatever order.
- * wae_ar_generate_coop_scalar_list (csrc/ar_coop.hip: ar_coop_scalar_list_kernel, always the any-shape kernel): n_teams teams of C
+ * wae_ar_generate_coop_scalar_list (csrc/ar_coop.hip: ar_coop_scalar_list_kernel, the any-shape kernel, or with
+ * wae_ar_desc.scalar_input = 2 at the reference's shape the LIST forms of the constant-size scalar kernels): n_teams teams of C
  * workgroups; ring (n_teams, C, ring_total), msg (n_teams, 2, C, NV), acc n_teams x wae_ar_coop_acc_floats(d), error >= 64 ints, the
  * caller zeroes msg, acc, error and next; `total` is the sum of the items' T; error[0] != 0 afterwards: a wait timed out (the output is
- * then invalid).  An item's results are wae_ar_generate_coop_scalar's for that utterance alone at the same C, bit for bit.
+ * then invalid).  An item's results are wae_ar_generate_coop_scalar's for that utterance alone at the same C and the same
+ * scalar_input value, bit for bit.
  * Refused before any launch (WAE_EINVAL): a class-id decoder; a mode other than 0 / 2; dist outside {0, 1} or O not matching it; mode 2
  * without its draws; u_mix without u_log or the reverse (dist 0); more than one Gaussian without u_mix; mode 0 without inputs_f;
  * out_samples without draws; no output requested; t0 != 0; n_items < 1; n_slots < 1 / n_teams outside 1..8; NULL items or next; and for
@@ -586,11 +603,16 @@ int wae_ar_generate_coop_scalar_list(const wae_ar_desc* d, int32_t C, int32_t di
  * wae_ar_generate_scalar_spans: dist 0 / 1 on n_slots one-CU workgroups, modes 0 / 2, the operands of wae_ar_generate_scalar_list.
  * wae_ar_generate_coop_spans: class ids on n_teams <= 8 teams of C workgroups, modes 0 / 1 / 2, the operands of
  *   wae_ar_generate_coop_list (msg, acc, error and next zeroed by the caller per launch; error[0] != 0 afterwards: a wait timed out).
+ * wae_ar_generate_coop_scalar_spans: dist 0 / 1 on n_teams <= 8 teams of C workgroups, modes 0 / 2, the operands of
+ *   wae_ar_generate_coop_scalar_list with wae_ar_span records (msg, acc, error and next zeroed by the caller per launch); it
+ *   dispatches as its list twin does (wae_ar_desc.scalar_input), and a clip's spans, concatenated, are bit for bit
+ *   wae_ar_generate_coop_scalar's decode of that clip at the same C and the same scalar_input value.
  * Refused before any launch: whatever the list twin refuses (WAE_EUNSUPPORTED / WAE_EINVAL as there), d->t0 != 0 among it; the
- * cooperative entry also (total + n_spans + 1) * (L + 4) >= 2^31, total being the length of the packed operands.
+ * cooperative entries also (total + n_spans + 1) * (L + 4) >= 2^31, total being the length of the packed operands.
  * Rates (profiles/ar_session.txt, all measured, bf16 at the reference's geometry): 8 clips on 8 teams in spans of 1600 steps 30.7 kHz per
  * clip against 31 kHz in one launch, 16 clips on 8 teams 15.3 kHz per clip, a relaunch with its packing ~0.45 ms per round on the
- * teams; fp32 sessions and scalar sessions have not been measured. */
+ * teams; scalar team sessions on the constant-size kernels (profiles/ar_scalar_fast.txt, bf16): 8 clips 31.7 kHz per clip in spans of
+ * 1600 steps, 16 clips 15.9 kHz per clip; fp32 sessions have not been measured. */
 typedef struct wae_ar_span {
   int64_t off;       /* first step of the span in THIS launch's packed per-step operands (as wae_ar_item.off) */
   int64_t ring;      /* float offset of the clip's own history ring inside `ring` */
@@ -621,8 +643,17 @@ int wae_ar_generate_coop_spans(const wae_ar_desc* d, int32_t C, int32_t n_spans,
                                const void* w_head, const float* head_bias, const void* c_up, int32_t c_dtype,
                                const int32_t* inputs, const float* uniforms, int32_t* out_idx, float* out_logits,
                                uint64_t* msg, float* acc, int32_t* error, void* stream);
-/* Floats of ONE clip's ring under wae_ar_generate_coop_spans for this descriptor, C and ring_total: ring_total where the launch takes
- * the constant-size kernels (their members share one ring), C * ring_total on the any-shape kernel; < 0: bad arguments. */
+int wae_ar_generate_coop_scalar_spans(const wae_ar_desc* d, int32_t C, int32_t dist, int32_t n_spans, int32_t n_teams,
+                                      const wae_ar_span* spans, int32_t* next, int64_t total, const int32_t* dilations,
+                                      const int64_t* ring_off, float* ring, int64_t ring_total, const void* w_layers,
+                                      int64_t layer_stride_bytes, int64_t w2_off_bytes, const float* bias2, const float* zb,
+                                      const float* first_tab, const float* first_bias, const void* w_head, const float* head_bias,
+                                      const void* c_up, int32_t c_dtype, const float* inputs_f, const float* u_mix,
+                                      const float* draws, float log_scale_min, int32_t clamp_log_scale, float* out_samples,
+                                      float* out_params, uint64_t* msg, float* acc, int32_t* error, void* stream);
+/* Floats of ONE clip's ring under wae_ar_generate_coop_spans / wae_ar_generate_coop_scalar_spans for this descriptor, C and ring_total:
+ * ring_total where the launch takes the constant-size kernels (their members share one ring) -- for a scalar-input descriptor that
+ * needs scalar_input = 2 --, C * ring_total on the any-shape kernel; < 0: bad arguments. */
 int64_t wae_ar_coop_ring_floats(const wae_ar_desc* d, int32_t C, int64_t ring_total);
 
 /* ---- backward data path of the gated stack: C[t][M] = sum_s W_s . X_s[t + shift_s] on time-major operands ----

@@ -11,6 +11,8 @@ options:
     --dtype=<fp32|bf16>      Compute precision [default: fp32].
     --coop-scalar            Scalar-input models ("raw" / "mulaw"): decode on the cooperative kernel (up to 32 CUs per utterance)
                              instead of one CU.  No effect on class-id ("mulaw-quantize") models.
+    --coop-scalar-fast       --coop-scalar on the constant-size scalar kernels where the model has the reference's decoder sizes
+                             (WaeEngine.ar_path(scalar_fast=True); other sizes keep the any-shape kernel).  Implies --coop-scalar.
     --stream-chunk=<N>       Decode in resumable launches of N samples (WaeEngine.incremental_stream) and post-process every chunk as
                              it arrives; prints the wall time to the first chunk of audio.  The wav written is the same file.
     --seed=<n>               torch.manual_seed(n) before decoding: the same draws, hence the same wav, from run to run.
@@ -22,7 +24,8 @@ options:
     --batch-stream=<N>       With --batch-decode: decode the list in rounds of N samples per clip (WaeEngine.decode_list_stream: one
                              launch per round, every clip keeps its own history between the launches) and post-process every chunk as
                              it arrives, as --stream-chunk does for one clip; prints the wall time until every clip has its first
-                             chunk.  With or without --batch-coop (class-id models; scalar-input models stream on the one-CU slots).
+                             chunk.  With or without --batch-coop; a scalar-input model streams on the one-CU slots, or with
+                             --batch-coop and --coop-scalar[-fast] on cooperative teams.
                              The wavs written are the bytes of --batch-decode alone.
 """
 import argparse
@@ -219,6 +222,7 @@ def main(argv=None):
     ap.add_argument("--initial-value", type=int, default=127)
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--coop-scalar", action="store_true")
+    ap.add_argument("--coop-scalar-fast", action="store_true")
     ap.add_argument("--stream-chunk", type=int)
     ap.add_argument("--seed", type=int)
     ap.add_argument("--batch-decode", action="store_true")
@@ -226,6 +230,7 @@ def main(argv=None):
     ap.add_argument("--batch-teams", type=int)
     ap.add_argument("--batch-stream", type=int)
     args = ap.parse_args(argv)
+    args.coop_scalar = args.coop_scalar or args.coop_scalar_fast
     if args.batch_stream is not None and not args.batch_decode:
         ap.error("--batch-stream sets the round length of --batch-decode: it needs --batch-decode")
     if args.batch_stream is not None and args.batch_stream < 1:
@@ -248,7 +253,7 @@ def main(argv=None):
     ck = torch.load(args.checkpoint, map_location="cpu")
     eng.load_state_dict(ck["state_dict"])
     if args.coop_scalar:
-        eng.ar_path(scalar_coop=True)
+        eng.ar_path(scalar_coop=True, scalar_fast=args.coop_scalar_fast)
     with open(args.speaker2ind) as f:
         sp2ind = json.load(f)
     os.makedirs(args.dst_dir, exist_ok=True)

@@ -1,11 +1,14 @@
 #!/usr/bin/env python
 """AR synthesis speed (BASELINE config C4): hps/vqwae.json decoder, B utterances, T samples.
 
-usage: bench_ar.py [dtype] [B] [T] [--generic] [--scalar] [--chunk N[,N...]]
+usage: bench_ar.py [dtype] [B] [T] [--generic] [--scalar [--fast]] [--chunk N[,N...]]
     --generic   the class-id decode on the any-shape cooperative kernel (WaeEngine.ar_path(generic=True))
     --scalar    scalar-input decoders instead: the same decoder with a scalar head (O = 30 mixture of logistics, O = 2 "Normal"), the
                 one-CU path (the default routing) against the cooperative path (ar_path(scalar_coop=True)) on the same draws, the two
                 alternating, best of three decodes each
+    --fast      with --scalar: three paths on the same clips in one process, alternating -- one-CU, the any-shape cooperative kernel
+                and the constant-size cooperative kernels (ar_path(scalar_coop=True, scalar_fast=True)) -- and behind them the class-id
+                constant-size decode of the same decoder, by the same procedure (one warm-up, best of three)
     --chunk N[,N...]  streaming (WaeEngine.incremental_stream): the one-shot decode against the same decode in launches of N steps, for
                 every N listed, in one process -- kHz per utterance (best of three decodes each, after a warm-up) and the wall time from
                 opening the stream to the first chunk's samples on the host.  Without a dtype argument both bf16 and fp32 run; T defaults
@@ -43,8 +46,9 @@ def bench_scalar():
         cfg = dict(CFG, O=O_ch, scalar_input=True, output_distribution=dist)
         sd = O.make_state_dict(dict(cfg), salt=7, with_encoder=False)
         engs = {}
-        for path in ("one-CU", "cooperative"):
-            engs[path] = WaeEngine(Geometry.from_cfg(cfg), dtype=dtype).ar_path(scalar_coop=path == "cooperative")
+        for path in ("one-CU", "cooperative") + (("constant-size",) if "--fast" in flags else ()):
+            engs[path] = WaeEngine(Geometry.from_cfg(cfg), dtype=dtype).ar_path(scalar_coop=path != "one-CU",
+                                                                                  scalar_fast=path == "constant-size")
             engs[path].load_state_dict(sd)
         M = 1 if O_ch == 2 else O_ch // 3
         gen = torch.Generator(device="cuda").manual_seed(11)
@@ -59,7 +63,7 @@ def bench_scalar():
                 out = e.incremental_forward(lat, gid, T, mode="sample", **kw)
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
-                assert (e._ar_profile is not None) == (path == "cooperative"), f"{path}: the other path ran"
+                assert (e._ar_profile is not None) == (path != "one-CU"), f"{path}: the other path ran"
                 if rep > 0:
                     best[path] = min(best.get(path, dt), dt)
                 xs[path] = out["x"]
@@ -69,6 +73,23 @@ def bench_scalar():
                   f"{dt / T * 1e6:.1f} us/sample")
         print(f"  cooperative / one-CU = {best['one-CU'] / best['cooperative']:.2f}x; samples within 1e-2 of each other: {agree:.3f} "
               f"(free-running decodes part where a mixture pick ties)")
+        if "constant-size" in best:
+            print(f"  constant-size / any-shape cooperative = {best['cooperative'] / best['constant-size']:.2f}x "
+                  f"({T / best['constant-size'] / 1e3:.2f} against {T / best['cooperative'] / 1e3:.2f} kHz per utterance)")
+    if "--fast" in flags:      # the class-id decode of the same decoder on its constant-size kernels, in the same process
+        eng = WaeEngine(Geometry.from_cfg(CFG), dtype=dtype)
+        eng.load_state_dict(O.make_state_dict(dict(CFG), salt=7, with_encoder=False))
+        uni = torch.rand(B, T, device="cuda")
+        best = None
+        for rep in range(4):
+            t0 = time.perf_counter()
+            eng.incremental_forward(lat, gid, T, mode="sample", uniforms=uni)
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            if rep > 0:
+                best = dt if best is None else min(best, dt)
+        print(f"AR class ids O=256 {dtype} B={B} T={T} constant-size: {best:.3f} s -> {T / best / 1e3:.2f} kHz per utterance, "
+              f"{best / T * 1e6:.1f} us/sample")
 
 
 def bench_stream():

@@ -2,7 +2,7 @@
 """Throughput of list decoding (WaeEngine.decode_list): hps/vqwae.json's decoder on a work list of unequal lengths.
 
 usage: bench_ar_list.py [--items N] [--dtypes bf16,fp32] [--slots cu[,2cu,N...]] [--teams N[,N...]] [--loop K] [--min-len 8000]
-                        [--max-len 64000] [--scalar]
+                        [--max-len 64000] [--scalar [--fast] [--stream N[,N...]]]
        bench_ar_list.py --session [--session-clips 256]
     --items N     clips in the list (default 512); lengths are drawn with numpy.random.default_rng(1234), uniform in
                   [--min-len, --max-len] samples, and rounded to whole latent frames (640 samples: the conditioning is upsampled per clip)
@@ -15,6 +15,12 @@ usage: bench_ar_list.py [--items N] [--dtypes bf16,fp32] [--slots cu[,2cu,N...]]
     --scalar      the scalar-input decoder of tools/bench_ar.py --scalar instead (the same decoder with an O = 30 mixture-of-logistics
                   head) through WaeEngine.decode_list_scalar, on both list forms; --loop then runs twice: on the one-CU kernel and on
                   the cooperative kernel (ar_path(scalar_coop=True), what synthesis.py --coop-scalar selects)
+    --fast        with --scalar: the team runs on the constant-size scalar kernels (ar_path(scalar_coop=True, scalar_fast=True), what
+                  synthesis.py --coop-scalar-fast selects) instead of the any-shape kernel
+    --stream N    with --scalar and --teams: also decode the list as a team session (decode_list_stream(coop=True)) in rounds of N
+                  steps, one run per N and team count, every round's samples copied to the host; prints the aggregate kHz, the mean
+                  per-clip kHz (a clip's steps / the time until its last chunk is on the host) and whether every clip equals the
+                  team list bit for bit
     --session     decode sessions (WaeEngine.decode_session) against the list decode of the same clips, in bf16, in one run: 8 clips of
                   16 000 steps on 8 teams in rounds of 160 and of 1600 steps against decode_list(coop=True); 16 such clips on 8 teams
                   in rounds of 1600 (two clips per team); --session-clips clips of --min-len .. --max-len steps on the one-CU slots in
@@ -121,11 +127,15 @@ def main():
     ap.add_argument("--min-len", type=int, default=8000)
     ap.add_argument("--max-len", type=int, default=64000)
     ap.add_argument("--scalar", action="store_true")
+    ap.add_argument("--fast", action="store_true")
+    ap.add_argument("--stream", default="")
     ap.add_argument("--session", action="store_true")
     ap.add_argument("--session-clips", type=int, default=256)
     args = ap.parse_args()
     if args.session:
         return session_bench(args)
+    if (args.fast or args.stream) and not args.scalar:
+        ap.error("--fast and --stream belong to --scalar (class-id sessions: --session)")
     cfg = dict(CFG, O=30, scalar_input=True, output_distribution="Logistic") if args.scalar else CFG
     rng = np.random.default_rng(1234)
     lens = rng.integers(args.min_len, args.max_len + 1, args.items)
@@ -148,6 +158,8 @@ def main():
     sd = O.make_state_dict(dict(cfg), salt=7, with_encoder=False)
     for dtype in args.dtypes.split(","):
         eng = WaeEngine(Geometry.from_cfg(cfg), dtype=dtype)
+        if args.scalar:
+            eng.ar_path(scalar_coop=True, scalar_fast=args.fast)      # (decode_list_scalar(coop=False) stays on the one-CU slots)
         eng.load_state_dict(sd)
         decode = eng.decode_list_scalar if args.scalar else eng.decode_list
         # what tells a real roll-out from a constant: the classes of clip 0, or the spread of its samples
@@ -181,10 +193,29 @@ def main():
                   f"{plan.efficiency:.3f} (busiest team {plan.makespan} samples -> {plan.makespan / dt / 1e3:.2f} kHz per team); "
                   f"{alive(out)}", flush=True)
             record["runs"].append(dict(kind=what + "_coop", dtype=dtype, teams=plan.slots, seconds=dt, khz=total / dt / 1e3,
-                                       plan_efficiency=plan.efficiency, makespan=plan.makespan))
+                                       plan_efficiency=plan.efficiency, makespan=plan.makespan, fast=args.fast))
+            for chunk in [int(n) for n in args.stream.split(",") if n]:
+                ref = [r["x"].cpu() for r in out]
+                list(eng.decode_list_stream([short(it) for it in items[:8]], chunk, mode="sample", coop=True, teams=teams))
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                parts, done_at, k = [[] for _ in items], {}, 0
+                for k, rnd in enumerate(eng.decode_list_stream(items, chunk, mode="sample", coop=True, teams=teams)):
+                    for i, r in enumerate(rnd):
+                        if r is not None:
+                            parts[i].append(r["x"].cpu())
+                            if r["done"]:
+                                done_at[i] = time.perf_counter() - t0
+                dt = time.perf_counter() - t0
+                per = float(np.mean([lens[i] / done_at[i] for i in range(len(items))])) / 1e3
+                same = all(torch.equal(torch.cat(p), r) for p, r in zip(parts, ref))
+                print(f"decode_list_stream(coop=True) {dtype} teams={plan.slots} rounds of {chunk}: {k + 1} launches, {dt:.2f} s -> "
+                      f"{total / dt / 1e3:.1f} kHz aggregate, {per:.2f} kHz per clip (mean); bit for bit the team list: {same}", flush=True)
+                record["runs"].append(dict(kind="team_session", dtype=dtype, teams=plan.slots, chunk=chunk, launches=k + 1, seconds=dt,
+                                           khz=total / dt / 1e3, khz_per_clip=per, equal=same, fast=args.fast))
             del out
         for scalar_coop in ((False, True) if args.scalar else (False,)) if args.loop > 0 else ():
-            eng.ar_path(scalar_coop=scalar_coop)      # (no effect on class-id decoders)
+            eng.ar_path(scalar_coop=scalar_coop, scalar_fast=args.fast)      # (no effect on class-id decoders)
             sub = items[:args.loop]
             first = sub[0]
             eng.incremental_forward(first["c"][None, :, :1].contiguous(), torch.tensor([0], device="cuda"), HOP, mode="sample")

@@ -27,6 +27,17 @@ class ArDesc(ctypes.Structure):
                                                                        ("resident_lds", c_i32), ("resident_regs", c_i32),
                                                                        ("t0", c_i32)]      # t0: trailing, so every positional construction means 0
 
+    # include/wae.h: scalar_input = 2 is a scalar-input decoder that asks the cooperative entries for the constant-size scalar kernels.
+    # Read and written here as a flag of its own: 0 unless asked for; a class-id descriptor (scalar_input 0) has no such request.
+    @property
+    def scalar_sized(self):
+        return int(self.scalar_input == 2)
+
+    @scalar_sized.setter
+    def scalar_sized(self, on):
+        if self.scalar_input:
+            self.scalar_input = 2 if on else 1
+
 
 class ArItem(ctypes.Structure):          # include/wae.h: wae_ar_item (device array element of wae_ar_generate_list)
     _fields_ = [("off", c_i64), ("T", c_i32), ("n_forced", c_i32), ("init_idx", c_i32), ("row", c_i32)]
@@ -174,6 +185,8 @@ SIGNATURES = {
     "wae_ar_generate_spans": (c_i32, _AR[:1] + [c_i32, c_i32, c_vp, c_vp] + _AR[1:] + [c_vp] * 5),
     "wae_ar_generate_scalar_spans": (c_i32, _AR[:1] + [c_i32, c_i32, c_i32, c_vp, c_vp] + _AR[1:] + [c_vp] * 3 + [c_f32, c_i32] + [c_vp] * 3),
     "wae_ar_generate_coop_spans": (c_i32, _AR[:1] + [c_i32, c_i32, c_i32, c_vp, c_vp, c_i64] + _AR[1:] + [c_vp] * 8),
+    "wae_ar_generate_coop_scalar_spans": (c_i32, _AR[:1] + [c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_i64] + _AR[1:] + [c_vp] * 3
+                                          + [c_f32, c_i32] + [c_vp] * 6),
     "wae_ar_coop_ring_floats": (c_i64, [ctypes.POINTER(ArDesc), c_i32, c_i64]),
     "wae_ce_logits_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "wae_ce_logits_bwd": (c_i32, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),

@@ -1218,15 +1218,25 @@ __device__ __forceinline__ void arc_bank_read(int k, float (&v)[ARC_NB]) {
   if constexpr (VB) { switch (k) { ARC_BANK_CASES_A(ARC_BANK_RD) ARC_BANK_CASES_V(ARC_VBANK_RD) } }
   else { switch (k) { ARC_BANK_CASES(ARC_BANK_RD) } }
 }
+// what the scalar-input form of the fast kernel keeps in registers beside the class-id form's: the first conv's weight of this thread's
+// channel, and the step's draws (u_mix[b, t, tid], u_log / z [b, t] and the next forced input on thread 0); nothing for class ids
+template <bool SCALAR> struct ArcScalarRegs {};
+template <> struct ArcScalarRegs<true> { float fw, um, ud, forced; };
 // LDSW (16-bit, two hand-overs per layer; round 5): the packets of the first p.nlds layers -- per thread NU W1 packets, its W_out / W_skip
 // shares and three scalars, (NU + 2) x 16 bytes -- live in LDS for the whole clip.  A layer whose weights are there issues no request
 // that can miss L2, so nothing sits in front of its exchange polls in the wave's in-order queue.
 // LIST: the work-list form (wae_ar_generate_coop_list): a team of 32 decodes one item after another in the same launch.  The placement
 // verdict, the head's packets, sbias and the resident weight packets are set up once per launch; the item loop rebuilds what depends on
 // the clip (see "the item boundary" below).
-template <typename E, int NU, bool FUSED, bool LDSW, bool VB, bool LIST = false>
+// SCALAR: the scalar-input form (wae_ar_desc.scalar_input = 2; two hand-overs per layer only).  Network, split, exchanges, residency tiers,
+// ring clearing and the item / span boundaries are the class-id form's; what differs is what differs in ar_coop_body: the current input
+// is a float in LDS (ibuf[3]) and the first conv w * x + b; the step's draws are requested at the top of the sample and travel under the
+// layers; the head's second conv has p.O <= 256 rows (member m still owns rows 8m .. 8m+7: rows >= p.O load nothing and publish
+// nothing, the packed row stride and the acc carve follow p.O); the draw is arc_draw_scalar; member 0 writes out_samples / out_params.
+template <typename E, int NU, bool FUSED, bool LDSW, bool VB, bool LIST = false, bool SCALAR = false>
 __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
   static_assert(!LIST || !FUSED, "the one-hand-over form has no prologue that can be re-entered");
+  static_assert(!SCALAR || !FUSED, "the one-hand-over form decodes class ids only");
   static_assert(!LDSW || ET<E>::EPL == 8, "LDS-resident layers: the 16-bit kernels");
   static_assert(!VB || (LDSW && NU == 4 && !FUSED), "the arch-VGPR bank belongs to ar_coop_fast_vb_kernel");
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -1247,7 +1257,7 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
   float* hbuf = skipb + S;                // S
   float* lbuf = hbuf + S;                 // O
   float* psum = lbuf + O;                 // ARC_THREADS
-  int* ibuf = (int*)(psum + ARC_THREADS);  // [0] = current input id, [1] = abort flag, [2] = argmax
+  int* ibuf = (int*)(psum + ARC_THREADS);  // [0] = current input id, [1] = abort flag, [2] = argmax, [3] = current input value (SCALAR)
   int4* ltab = (int4*)(ibuf + 8);         // L + 1: ring offsets {tap t-2d, tap t-d, current row} of every layer for this sample;
                                           // entry L = layer 0 for the next sample
   int* ldil = (int*)(ltab + L + 1);
@@ -1259,6 +1269,8 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
   const int nlds = LDSW ? p.nlds : 0;
   // layers [nlds, nlds + nbank): packets in a[0:252] (and, VB, v[187:255])
   const int nbank = (LDSW && NU == 4) ? min(max(L - nlds, 0), min(p.nbank, ARC_NBANK + (VB ? ARC_NVB : 0))) : 0;
+  // the head's output rows: 256 as a constant for class ids, the mixture's parameter count (<= 256) for a scalar-input decoder
+  [[maybe_unused]] const int On = SCALAR ? p.O : O, on_pad = SCALAR ? ((p.O + 63) & ~63) : O_PAD;
 
   // Round 5: ONE ring per utterance (member 0's region), shared by its 32 members, instead of 32 private copies.  Every member still
   // writes every row -- the same bits (the exchange is bitwise reproducible), to the same addresses -- so a member's own cache can
@@ -1284,7 +1296,12 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
   // boundary is hoisted out of the item loop and kept in registers across the sample loop -- these three lambdas must not use `tid`)
   auto item_state = [&](int ti) {
     for (int i = ti; i < 32 + K1p + 2 * S; i += ARC_THREADS) sm[i] = 0.f;
-    if (ti == 0) { ibuf[0] = nforced > 0 ? p.inputs[base] : init; ibuf[1] = 0; }
+    if constexpr (SCALAR) {
+      // wavenet.py:284-285: the start value is zero; a forced first step overrides it (wavenet.py:300-302)
+      if (ti == 0) { ibuf[0] = 0; ibuf[1] = 0; ((float*)ibuf)[3] = (p.inputs_f && nforced > 0) ? p.inputs_f[base] : 0.f; }
+    } else {
+      if (ti == 0) { ibuf[0] = nforced > 0 ? p.inputs[base] : init; ibuf[1] = 0; }
+    }
     for (int i = ti; i < L; i += ARC_THREADS) {
       const int di = p.dil[i];
       ldil[i] = di; lroff[i] = (int)p.ring_off[i]; lpos[i] = t0 % (2 * di + 1);
@@ -1313,9 +1330,9 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
     item_tab(tid);
   }
 
-  unsigned long long* hbanks = (unsigned long long*)(p.acc + (int64_t)b * ARC_ACC_FLOATS(R, S, O));
+  unsigned long long* hbanks = (unsigned long long*)(p.acc + (int64_t)b * ARC_ACC_FLOATS(R, S, On));
   unsigned long long* ybanks = hbanks + 2 * S;
-  unsigned long long* xsum = ybanks + 2 * O;
+  unsigned long long* xsum = ybanks + 2 * On;
   unsigned long long* ssum = xsum + 2 * ARC_CMAX * R;
   unsigned long long* xtot = ssum + 2 * ARC_CMAX * S;      // round 2 of arc_allsum2
   unsigned long long* stot = xtot + 2 * R;
@@ -1407,9 +1424,14 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
 #pragma unroll
   for (int j = 0; j < NPK; ++j) {
     hw1[j] = *(const f32x4*)(p.w_head + ((int64_t)(hsl + 32 * j) * S_PAD + 8 * m + hi) * 16);
-    hw2[j] = *(const f32x4*)(p.w_head + ((int64_t)NKS * S_PAD + (int64_t)(hsl + 32 * j) * O_PAD + 8 * m + hi) * 16);
+    if constexpr (SCALAR) {      // rows >= p.O do not exist: no weight, no bias, nothing published
+      hw2[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (8 * m + hi < p.O) hw2[j] = *(const f32x4*)(p.w_head + ((int64_t)NKS * S_PAD + (int64_t)(hsl + 32 * j) * on_pad + 8 * m + hi) * 16);
+    } else {
+      hw2[j] = *(const f32x4*)(p.w_head + ((int64_t)NKS * S_PAD + (int64_t)(hsl + 32 * j) * O_PAD + 8 * m + hi) * 16);
+    }
   }
-  const float hb1 = p.head_bias[8 * m + hi], hb2 = p.head_bias[S + 8 * m + hi];
+  const float hb1 = p.head_bias[8 * m + hi], hb2 = (!SCALAR || 8 * m + hi < p.O) ? p.head_bias[S + 8 * m + hi] : 0.f;
   float sbias = 0.f;                      // conv1x1_skip biases of all layers: once, on member 0 (the skip path is linear)
   if (m == 0)
     for (int l = 0; l < L; ++l) sbias += p.bias2[(int64_t)l * (R + S) + R + tid];
@@ -1418,6 +1440,9 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
     return p.c_dtype == WAE_BF16 ? (float)((const __bf16*)p.c_up)[ci] : (p.c_dtype == WAE_F16 ? (float)((const f16*)p.c_up)[ci] : ((const float*)p.c_up)[ci]);
   };
   const float fbias = p.first_bias[tid];
+  // SCALAR: the first conv has one input channel -- its weight column stays in a register; the step's draws wait beside it
+  [[maybe_unused]] ArcScalarRegs<SCALAR> sr;
+  if constexpr (SCALAR) sr.fw = p.first_tab[tid];
   if constexpr (LDSW) {
     // (LIST: once per launch, with zeros where zb_a / zb_g go -- those two words are the item's and are written per item)
     for (int l = 0; l < nlds; ++l) {       // once per clip: what prefetch() fetches per layer and sample
@@ -1522,6 +1547,11 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
     T = w.T; base = w.off; t0 = max(w.t0, 0);
     nforced = !p.inputs ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
     if (p.inputs && t0 > 0 && nforced < 1) nforced = 1;         // a continuation's first step is forced
+    if constexpr (SCALAR) {
+      // (a scalar item takes its forced prefix from inputs_f -- p.inputs is null -- and has no start class: item_state starts it from 0)
+      nforced = !p.inputs_f ? 0 : (p.mode == 0 ? w.T : min(max(w.n_forced, 0), w.T));
+      if (p.inputs_f && t0 > 0 && nforced < 1) nforced = 1;
+    }
     init = min(max(w.init_idx, 0), p.O - 1);
     zb_b = p.zb + (int64_t)w.row * L * 2 * p.Hp;
     item_state(tl);
@@ -1750,7 +1780,20 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
   } else
   for (int t = 0; t < T; ++t) {
     const int cur = ibuf[0];
-    xreg = p.first_tab[(int64_t)cur * p.Rp + tid] + fbias;
+    if constexpr (SCALAR) {
+      // this step's draws and the next forced input, requested here: they travel under the layers and wait in registers
+      const int Mx = p.O == 2 ? 1 : p.O / 3;
+      const bool draw_mix = p.dist == 0 ? p.u_mix != nullptr : (p.z != nullptr && Mx > 1);
+      const float* const draws = p.dist == 0 ? (p.u_mix ? p.u_log : nullptr) : p.z;
+      xreg = fmaf(sr.fw, ((const float*)ibuf)[3], fbias);
+      const int64_t bt = base + t;
+      sr.um = sr.ud = sr.forced = 0.f;
+      if (draw_mix && tid < Mx) sr.um = p.u_mix[bt * Mx + tid];
+      if (tid == 0 && draws) sr.ud = draws[bt];
+      if (tid == 0 && p.inputs_f && t + 1 < nforced) sr.forced = p.inputs_f[bt + 1];
+    } else {
+      xreg = p.first_tab[(int64_t)cur * p.Rp + tid] + fbias;
+    }
     vbuf[2 * R + tid] = xreg;
     ring[(unsigned)(ltab[0].z + tid)] = xreg;
     if (tid < Cc && t + 1 < T) creg = c_load(t + 1);     // (this sample's row went into vbuf with layer 0's history taps)
@@ -1837,15 +1880,27 @@ __device__ __forceinline__ void ar_coop_fast_body(const ArcArgs& p) {
 #pragma unroll
       for (int j = 0; j < NPK; ++j) arc_packet_fma<E>(hw2[j], hbuf + (hsl + 32 * j) * EPL, a0, a1);
       const float r2 = arc_fold32(a0 + a1);
-      if (!arc_allgather(ybanks, O, yuse++, hsl == 0, 8 * m + hi, r2 + hb2, fast, p.error, &ibuf[1],
-                         [&](float v) {
-                           lbuf[tid] = v;
-                           if (p.out_logits && m == 0) p.out_logits[base * O + (int64_t)tid * T + t] = v;
-                         }))
-        return;
+      if constexpr (SCALAR) {
+        if (!arc_allgather(ybanks, On, yuse++, hsl == 0 && 8 * m + hi < On, 8 * m + hi, r2 + hb2, fast, p.error, &ibuf[1],
+                           [&](float v) {
+                             if (tid < On) {
+                               lbuf[tid] = v;
+                               if (p.out_params && m == 0) p.out_params[base * On + (int64_t)tid * T + t] = v;
+                             }
+                           }))
+          return;
+      } else {
+        if (!arc_allgather(ybanks, O, yuse++, hsl == 0, 8 * m + hi, r2 + hb2, fast, p.error, &ibuf[1],
+                           [&](float v) {
+                             lbuf[tid] = v;
+                             if (p.out_logits && m == 0) p.out_logits[base * O + (int64_t)tid * T + t] = v;
+                           }))
+          return;
+      }
     }
     ARC_TICK(5);
-    arc_draw(p, lbuf, psum, ibuf, base, nforced, m, t);
+    if constexpr (SCALAR) arc_draw_scalar(p, lbuf, psum, (float*)ibuf + 3, base, nforced, m, t, sr.um, sr.ud, sr.forced);
+    else arc_draw(p, lbuf, psum, ibuf, base, nforced, m, t);
     ARC_TICK(6);
   }
   if constexpr (!LIST) break;
@@ -1879,13 +1934,48 @@ __global__ void __launch_bounds__(ARC_THREADS) __attribute__((amdgpu_num_vgpr(18
   ar_coop_fast_body<E, 4, false, true, true, true>(p);
 }
 
+// the scalar-input forms (wae_ar_desc.scalar_input = 2): two hand-overs per layer, single and list; the names keep the ar_coop_fast
+// prefix and the register-bank forms the substring vb_kernel, which is what tools/check_ar_banks.py keys on
+template <typename E, int NU, bool LDSW = false>
+__global__ void __launch_bounds__(ARC_THREADS) ar_coop_fast_scalar_kernel(ArcArgs p) {
+  ar_coop_fast_body<E, NU, false, LDSW, false, false, true>(p);
+}
+template <typename E>
+__global__ void __launch_bounds__(ARC_THREADS) __attribute__((amdgpu_num_vgpr(186))) ar_coop_fast_scalar_vb_kernel(ArcArgs p) {
+  ar_coop_fast_body<E, 4, false, true, true, false, true>(p);
+}
+template <typename E, int NU, bool LDSW = false>
+__global__ void __launch_bounds__(ARC_THREADS) ar_coop_fast_scalar_list_kernel(ArcArgs p) {
+  ar_coop_fast_body<E, NU, false, LDSW, false, true, true>(p);
+}
+template <typename E>
+__global__ void __launch_bounds__(ARC_THREADS) __attribute__((amdgpu_num_vgpr(186))) ar_coop_fast_scalar_list_vb_kernel(ArcArgs p) {
+  ar_coop_fast_body<E, 4, false, true, true, true, true>(p);
+}
+
 #include "ar_host.hpp"
 
 // The sized kernel of (E, NU) for what the arguments ask: the one-hand-over form where a.w_fused is set (never in a list), the bank of
 // ARC_NVB more register-resident layers where 16-bit NU = 4 has them, LDS-resident layers where 16-bit storage has any, else the plain one.
 #define ARC_FAST(...) AR_LAUNCH((__VA_ARGS__), dim3(8 * 32), dim3(ARC_THREADS), lds, st, a, who)
-template <typename E, int NU, bool LIST>
+template <typename E, int NU, bool LIST, bool SCALAR = false>
 static int launch_arc_fast(const ArcArgs& a, size_t lds, hipStream_t st, const char* who) {
+  if constexpr (SCALAR) {      // the same choice among the two-hand-over forms (a.w_fused is null)
+    if constexpr (sizeof(E) == 2 && NU == 4) {
+      if (a.nlds > 0 && a.nbank > ARC_NBANK) {
+        if constexpr (LIST) ARC_FAST(ar_coop_fast_scalar_list_vb_kernel<E>);
+        else ARC_FAST(ar_coop_fast_scalar_vb_kernel<E>);
+      }
+    }
+    if constexpr (sizeof(E) == 2) {
+      if (a.nlds > 0) {
+        if constexpr (LIST) ARC_FAST(ar_coop_fast_scalar_list_kernel<E, NU, true>);
+        else ARC_FAST(ar_coop_fast_scalar_kernel<E, NU, true>);
+      }
+    }
+    if constexpr (LIST) ARC_FAST(ar_coop_fast_scalar_list_kernel<E, NU, false>);
+    else ARC_FAST(ar_coop_fast_scalar_kernel<E, NU, false>);
+  }
   if constexpr (!LIST) {
     if (a.w_fused) {
       if constexpr (sizeof(E) == 2) {
@@ -1912,16 +2002,16 @@ static int launch_arc_fast(const ArcArgs& a, size_t lds, hipStream_t st, const c
 #undef ARC_FAST
 
 // the (dtype, NU) pairs that have sized kernels; for every other pair nothing is launched and `found` becomes false
-template <bool LIST>
+template <bool LIST, bool SCALAR = false>
 static int launch_arc_sized(int nu, const ArcArgs& a, size_t lds, hipStream_t st, const char* who, bool& found) {
   found = true;
-  if (a.dtype == WAE_BF16 && nu == 3) return launch_arc_fast<__bf16, 3, LIST>(a, lds, st, who);
-  if (a.dtype == WAE_BF16 && nu == 4) return launch_arc_fast<__bf16, 4, LIST>(a, lds, st, who);
-  if (a.dtype == WAE_F16 && nu == 3) return launch_arc_fast<f16, 3, LIST>(a, lds, st, who);
-  if (a.dtype == WAE_F16 && nu == 4) return launch_arc_fast<f16, 4, LIST>(a, lds, st, who);
-  if (a.dtype == WAE_F32 && nu == 6) return launch_arc_fast<float, 6, LIST>(a, lds, st, who);
-  if (a.dtype == WAE_F32 && nu == 7) return launch_arc_fast<float, 7, LIST>(a, lds, st, who);
-  if (a.dtype == WAE_F32 && nu == 8) return launch_arc_fast<float, 8, LIST>(a, lds, st, who);
+  if (a.dtype == WAE_BF16 && nu == 3) return launch_arc_fast<__bf16, 3, LIST, SCALAR>(a, lds, st, who);
+  if (a.dtype == WAE_BF16 && nu == 4) return launch_arc_fast<__bf16, 4, LIST, SCALAR>(a, lds, st, who);
+  if (a.dtype == WAE_F16 && nu == 3) return launch_arc_fast<f16, 3, LIST, SCALAR>(a, lds, st, who);
+  if (a.dtype == WAE_F16 && nu == 4) return launch_arc_fast<f16, 4, LIST, SCALAR>(a, lds, st, who);
+  if (a.dtype == WAE_F32 && nu == 6) return launch_arc_fast<float, 6, LIST, SCALAR>(a, lds, st, who);
+  if (a.dtype == WAE_F32 && nu == 7) return launch_arc_fast<float, 7, LIST, SCALAR>(a, lds, st, who);
+  if (a.dtype == WAE_F32 && nu == 8) return launch_arc_fast<float, 8, LIST, SCALAR>(a, lds, st, who);
   found = false;
   return WAE_OK;
 }
@@ -1991,42 +2081,73 @@ static int arc_nu(const wae_ar_desc* d) {
   const int epl = wae_is16(d->dtype) ? 8 : 4;
   return ((3 * d->R + (d->Cc > 0 ? d->Cc : 0) + epl - 1) / epl + 31) / 32;
 }
-static bool arc_sized_shape(const wae_ar_desc* d, int32_t C, int64_t ring_total) {
+// (everything but the head's output rows: 256 for class ids, any O <= 256 for a scalar-input decoder that has opted in)
+static bool arc_sized_net(const wae_ar_desc* d, int32_t C, int64_t ring_total) {
   const int nu = arc_nu(d);
   const bool pair = wae_is16(d->dtype) ? (nu == 3 || nu == 4) : (d->dtype == WAE_F32 && nu >= 6 && nu <= 8);
-  return C == 32 && d->R == 256 && d->S == 256 && d->O == 256 && d->G == 256 && d->ktaps == 3 && d->Cc <= 256 && ring_total % 4 == 0 &&
+  return C == 32 && d->R == 256 && d->S == 256 && d->G == 256 && d->ktaps == 3 && d->Cc <= 256 && ring_total % 4 == 0 &&
          !d->coop_generic && pair;
+}
+static bool arc_sized_shape(const wae_ar_desc* d, int32_t C, int64_t ring_total) {
+  return arc_sized_net(d, C, ring_total) && d->O == 256;
+}
+// wae_ar_desc.scalar_input = 2: the scalar cooperative entries take the constant-size scalar kernels only where the caller asks for them
+static bool arc_sized_shape_scalar(const wae_ar_desc* d, int32_t C, int64_t ring_total) {
+  return d->scalar_input == 2 && arc_sized_net(d, C, ring_total) && d->O >= 1 && d->O <= 256;
+}
+
+// Dynamic LDS of the constant-size kernels for geometry d, and how many layers stay resident where (a.nlds, a.nbank) as
+// wae_ar_desc.resident_lds / resident_regs say; a.w_fused is read (the one-hand-over form has the accumulation registers only).
+static size_t arc_sized_plan(const wae_ar_desc* d, ArcArgs& a) {
+  const int epl = wae_is16(d->dtype) ? 8 : 4;
+  const int nu = arc_nu(d);
+  size_t lds_f = sizeof(float) * (size_t)(32 + 4 * nu * 32 * epl / 4 + 4 * 256 + 8 + 4 * (d->L + 1) + 3 * d->L + epl);
+  // LDS-resident layers (16-bit, two hand-overs per layer): (nu + 2) x 16 B x 256 threads per layer behind the kernel's own arrays
+  a.nlds = 0;
+  if (wae_is16(d->dtype)) {
+    const size_t per = (size_t)(nu + 2) * 16 * ARC_THREADS;
+    int fit = (int)((160 * 1024 - lds_f - 64) / per);
+    a.nlds = resident_count(d->resident_lds, fit, fit);
+    if (a.nlds > fit) a.nlds = fit;
+    if (a.nlds > d->L) a.nlds = d->L;
+    if (a.nlds < 0) a.nlds = 0;
+    lds_f += 64 + per * a.nlds;
+    a.nbank = a.nlds > 0 ? resident_count(d->resident_regs, ARC_NBANK + ARC_NVB, ARC_NBANK + ARC_NVB) : 0;      // (the register banks belong to the LDS-resident instantiations)
+    if (a.w_fused && a.nbank > ARC_NBANK) a.nbank = ARC_NBANK;      // (the one-hand-over form has the accumulation registers only)
+    if (a.nbank > d->L - a.nlds) a.nbank = d->L - a.nlds > 0 ? d->L - a.nlds : 0;
+  }
+  return lds_f;
 }
 
 // Which kernel decodes geometry d on C members: the reference's own geometry on 32 members takes the kernels with the sizes as constants
 // (NU = W1 packets per GEMV thread; residency as wae_ar_desc.resident_lds / resident_regs say), everything else the any-shape kernel.
 // list: the work-list forms (a.w_fused is null there).
 static int arc_dispatch(const wae_ar_desc* d, int32_t C, ArcArgs& a, const void* w_fused, bool list, hipStream_t st, const char* who) {
-  const int epl = wae_is16(d->dtype) ? 8 : 4;
   const int nu = arc_nu(d);
   if (arc_sized_shape(d, C, a.ring_total)) {
     a.w_fused = d->L >= 2 ? (const char*)w_fused : nullptr;     // the one-hand-over-per-layer kernel (else: ar_coop_fast_kernel's two)
-    size_t lds_f = sizeof(float) * (size_t)(32 + 4 * nu * 32 * epl / 4 + 4 * 256 + 8 + 4 * (d->L + 1) + 3 * d->L + epl);
-    // LDS-resident layers (16-bit, two hand-overs per layer): (nu + 2) x 16 B x 256 threads per layer behind the kernel's own arrays
-    a.nlds = 0;
-    if (wae_is16(d->dtype)) {
-      const size_t per = (size_t)(nu + 2) * 16 * ARC_THREADS;
-      int fit = (int)((160 * 1024 - lds_f - 64) / per);
-      a.nlds = resident_count(d->resident_lds, fit, fit);
-      if (a.nlds > fit) a.nlds = fit;
-      if (a.nlds > d->L) a.nlds = d->L;
-      if (a.nlds < 0) a.nlds = 0;
-      lds_f += 64 + per * a.nlds;
-      a.nbank = a.nlds > 0 ? resident_count(d->resident_regs, ARC_NBANK + ARC_NVB, ARC_NBANK + ARC_NVB) : 0;      // (the register banks belong to the LDS-resident instantiations)
-      if (a.w_fused && a.nbank > ARC_NBANK) a.nbank = ARC_NBANK;      // (the one-hand-over form has the accumulation registers only)
-      if (a.nbank > d->L - a.nlds) a.nbank = d->L - a.nlds > 0 ? d->L - a.nlds : 0;
-    }
+    const size_t lds_f = arc_sized_plan(d, a);
     bool found;
     const int rc = list ? launch_arc_sized<true>(nu, a, lds_f, st, who, found) : launch_arc_sized<false>(nu, a, lds_f, st, who, found);
     if (found) return rc;
   }
   const size_t lds = arc_generic_lds(d, C);
   return list ? launch_arc_generic<ARC_LIST>(a, lds, st, who) : launch_arc_generic<ARC_CLASS_IDS>(a, lds, st, who);
+}
+
+// ... and which one decodes a scalar-input geometry: the any-shape kernel unless wae_ar_desc.scalar_input = 2 asks for the constant-size
+// scalar kernels and the shape has one (the same residency rules; there is no one-hand-over scalar form).  list: items or spans.
+static int arc_dispatch_scalar(const wae_ar_desc* d, int32_t C, ArcArgs& a, bool list, hipStream_t st, const char* who) {
+  if (arc_sized_shape_scalar(d, C, a.ring_total)) {
+    a.w_fused = nullptr;
+    const size_t lds_f = arc_sized_plan(d, a);
+    bool found;
+    const int rc = list ? launch_arc_sized<true, true>(arc_nu(d), a, lds_f, st, who, found)
+                        : launch_arc_sized<false, true>(arc_nu(d), a, lds_f, st, who, found);
+    if (found) return rc;
+  }
+  const size_t lds = arc_generic_lds(d, C);
+  return list ? launch_arc_generic<ARC_SCALAR_LIST>(a, lds, st, who) : launch_arc_generic<ARC_SCALAR>(a, lds, st, who);
 }
 
 extern "C" int wae_ar_generate_coop_fused(const wae_ar_desc* d, int32_t C, const int32_t* dilations, const int64_t* ring_off, float* ring,
@@ -2112,7 +2233,8 @@ extern "C" int wae_ar_generate_coop_spans(const wae_ar_desc* d, int32_t C, int32
 
 extern "C" int64_t wae_ar_coop_ring_floats(const wae_ar_desc* d, int32_t C, int64_t ring_total) {
   if (!d || C <= 0 || ring_total <= 0) return WAE_EINVAL;
-  return arc_sized_shape(d, C, ring_total) ? ring_total : (int64_t)C * ring_total;
+  const bool sized = d->scalar_input ? arc_sized_shape_scalar(d, C, ring_total) : arc_sized_shape(d, C, ring_total);
+  return sized ? ring_total : (int64_t)C * ring_total;
 }
 
 // the operands of a scalar draw as the kernels read them: u_mix only where the decode samples, the draws under the name of their kind
@@ -2129,8 +2251,9 @@ static void arc_fill_draw(ArcArgs& a, int dist, const ArDraw& w, float log_scale
   a.out_params = w.out_params;
 }
 
-// Scalar-input decoders on the any-shape cooperative kernel (ar_coop_kernel<E, true>): the network, the split and the exchanges of
-// wae_ar_generate_coop; the first conv and the draw of wae_ar_generate_scalar (dist 0) / wae_ar_generate_scalar_mog (dist 1).
+// Scalar-input decoders on the cooperative kernels (ar_coop_kernel<E, true>, or with wae_ar_desc.scalar_input = 2 the constant-size
+// ar_coop_fast_scalar*_kernel): the network, the split and the exchanges of wae_ar_generate_coop; the first conv and the draw of
+// wae_ar_generate_scalar (dist 0) / wae_ar_generate_scalar_mog (dist 1).
 extern "C" int wae_ar_generate_coop_scalar(const wae_ar_desc* d, int32_t C, int32_t dist, const int32_t* dilations, const int64_t* ring_off,
                                            float* ring, int64_t ring_total, const void* w_layers, int64_t layer_stride_bytes,
                                            int64_t w2_off_bytes, const float* bias2, const float* zb, const float* first_tab,
@@ -2149,11 +2272,11 @@ extern "C" int wae_ar_generate_coop_scalar(const wae_ar_desc* d, int32_t C, int3
   ArcArgs a = arc_common_args(d, C, net, x);
   arc_fill_draw(a, dist, w, log_scale_min, clamp_log_scale);
   a.n_forced = ar_n_forced(d, inputs_f);
-  return launch_arc_generic<ARC_SCALAR>(a, arc_generic_lds(d, C), as_stream(stream), who);
+  return arc_dispatch_scalar(d, C, a, false, as_stream(stream), who);
 }
 
 // A work list of scalar-input utterances on cooperative teams: the queue, teams and exchanges of wae_ar_generate_coop_list, the network
-// form and the draw of wae_ar_generate_coop_scalar (always the any-shape body: ar_coop_body<E, true, true>).
+// form and the draw of wae_ar_generate_coop_scalar (ar_coop_body<E, true, true>, or the LIST forms of the constant-size scalar kernels).
 extern "C" int wae_ar_generate_coop_scalar_list(const wae_ar_desc* d, int32_t C, int32_t dist, int32_t n_items, int32_t n_teams,
                                                 const wae_ar_item* items, int32_t* next, int64_t total, const int32_t* dilations,
                                                 const int64_t* ring_off, float* ring, int64_t ring_total, const void* w_layers,
@@ -2177,5 +2300,33 @@ extern "C" int wae_ar_generate_coop_scalar_list(const wae_ar_desc* d, int32_t C,
   arc_fill_draw(a, dist, w, log_scale_min, clamp_log_scale);
   a.B = n_teams; a.T = 0; a.t0 = 0; a.n_forced = 0; a.init_idx = 0;      // per item
   a.items = items; a.next = next; a.n_items = n_items;
-  return launch_arc_generic<ARC_SCALAR_LIST>(a, arc_generic_lds(d, C), as_stream(stream), who);
+  return arc_dispatch_scalar(d, C, a, true, as_stream(stream), who);
+}
+
+// A work list of scalar spans on cooperative teams: wae_ar_generate_coop_scalar_list with wae_ar_span records, under
+// wae_ar_generate_coop_spans' contract (ring per clip, d->t0 == 0); the kernels are the same LIST forms, which branch once per record.
+extern "C" int wae_ar_generate_coop_scalar_spans(const wae_ar_desc* d, int32_t C, int32_t dist, int32_t n_spans, int32_t n_teams,
+                                                 const wae_ar_span* spans, int32_t* next, int64_t total, const int32_t* dilations,
+                                                 const int64_t* ring_off, float* ring, int64_t ring_total, const void* w_layers,
+                                                 int64_t layer_stride_bytes, int64_t w2_off_bytes, const float* bias2, const float* zb,
+                                                 const float* first_tab, const float* first_bias, const void* w_head,
+                                                 const float* head_bias, const void* c_up, int32_t c_dtype, const float* inputs_f,
+                                                 const float* u_mix, const float* draws, float log_scale_min, int32_t clamp_log_scale,
+                                                 float* out_samples, float* out_params, uint64_t* msg, float* acc, int32_t* error,
+                                                 void* stream) {
+  const char* who = "ar_generate_coop_scalar_spans";
+  const ArNet net = AR_NET_OF_ARGS;
+  const ArcExchange x = {msg, acc, error};
+  const ArDraw w = {inputs_f, u_mix, draws, out_samples, out_params};
+  AR_TRY(ar_check_net(who, d, net, true, false, ARC_THREADS));
+  AR_TRY(ar_check_mixture(who, d, dist, w, true, true));
+  AR_TRY(ar_check_queue(who, spans, next, n_spans, "n_teams", n_teams, 8, "span"));
+  AR_TRY(ar_check_span_t0(who, d));
+  AR_TRY(ar_check_sequence(who, d, total, n_spans));
+  AR_TRY(ar_check_split(who, d, C, ARC_CMAX, ARC_THREADS, ring_total, x.ok(), nullptr));
+  ArcArgs a = arc_common_args(d, C, net, x);
+  arc_fill_draw(a, dist, w, log_scale_min, clamp_log_scale);
+  a.B = n_teams; a.T = 0; a.t0 = 0; a.n_forced = 0; a.init_idx = 0;      // per span
+  a.spans = spans; a.next = next; a.n_items = n_spans;
+  return arc_dispatch_scalar(d, C, a, true, as_stream(stream), who);
 }

@@ -86,7 +86,7 @@ class _ArClip:
 
 class DecodeSession:
     """WaeEngine.decode_session: clips of any lengths that join at any time and decode in rounds, one launch per round (include/wae.h:
-    wae_ar_generate_spans, wae_ar_generate_scalar_spans, wae_ar_generate_coop_spans).  add() does once per clip what a decode does once
+    wae_ar_generate_spans, wae_ar_generate_scalar_spans, wae_ar_generate_coop_spans, wae_ar_generate_coop_scalar_spans).  add() does once per clip what a decode does once
     (the conditioning rows of the whole clip, the speaker row, the clip's own history ring, the draws of all its steps); step() decodes
     the next span of every live clip in one launch and returns the spans' outputs; a clip's outputs, concatenated over the rounds, are
     bit for bit its single decode (incremental_forward alone: on the one-CU kernel for coop=False, on the cooperative path for
@@ -95,7 +95,7 @@ class DecodeSession:
     def __init__(self, eng, mode="sample", coop=False, slots=None, teams=None, want_logits=False, c_is_upsampled=False,
                  log_scale_min=-7.0, clamp_log_scale=False):
         g = eng.g
-        if g.scalar_input and coop:
+        if g.scalar_input and coop and not eng.ar_scalar_coop:
             raise NotImplementedError("decode_session(coop=True): scalar-input decoders decode their sessions on the one-CU slots "
                                       "(coop=False); the team form of the scalar span list does not exist yet")
         if coop and max(g.R, g.S, g.O) > 256:
@@ -125,8 +125,12 @@ class DecodeSession:
             self.nslots = (torch.cuda.get_device_properties(dev).multi_processor_count if self._slots is None
                            else max(1, int(self._slots)))
         path = (int(eng.ar_generic), eng.ar_resident[0], eng.ar_resident[1]) if self.coop else ()
+        if g.scalar_input:
+            path = eng._ar_scalar_path() if self.coop else ()
         self.d = L.ArDesc(eng.dt, 0, 0, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, self.mode, 0,
                           int(g.scalar_input), math.sqrt(1.0 / g.layers), 0, *path)
+        if g.scalar_input and self.coop:
+            self.d.scalar_sized = int(eng.ar_scalar_fast)
         self.C, per = 1, eng.ar_ring_total
         self.msg = self.acc = self.err = None
         if self.coop:
@@ -312,9 +316,17 @@ class DecodeSession:
             um = cut("u_mix") if sampled and (not self.normal or self.M > 1) else None
             dr = cut("draw") if sampled else None
             out = torch.empty(total, dtype=torch.float32, device=dev) if sampled else None
-            L.check(lib.wae_ar_generate_scalar_spans(ctypes.byref(d), int(self.normal), len(sel), plan.slots, L.ptr(spans), L.ptr(nxt), *net,
-                                                     L.ptr(inputs), L.ptr(um), L.ptr(dr), self.log_scale_min, self.clamp, L.ptr(out),
-                                                     L.ptr(logits), st), "ar_generate_scalar_spans")
+            operands = (L.ptr(inputs), L.ptr(um), L.ptr(dr), self.log_scale_min, self.clamp, L.ptr(out), L.ptr(logits))
+            if self.coop:
+                self.msg.zero_()
+                self.acc.zero_()
+                self.err.zero_()
+                L.check(lib.wae_ar_generate_coop_scalar_spans(ctypes.byref(d), self.C, int(self.normal), len(sel), plan.slots, L.ptr(spans),
+                                                              L.ptr(nxt), total, *net, *operands, L.ptr(self.msg), L.ptr(self.acc),
+                                                              L.ptr(self.err), st), "ar_generate_coop_scalar_spans")
+            else:
+                L.check(lib.wae_ar_generate_scalar_spans(ctypes.byref(d), int(self.normal), len(sel), plan.slots, L.ptr(spans), L.ptr(nxt),
+                                                         *net, *operands, st), "ar_generate_scalar_spans")
             key, keep = "x", (um, dr)
         else:
             uni = cut("uni") if self.mode == 2 else None
@@ -333,7 +345,7 @@ class DecodeSession:
             key, keep = "idx", (uni,)
         self._keep = (spans, nxt, c_up, inputs, out, logits) + keep     # the launch's operands live until the next round's
         if self.coop:
-            eng._ar_check_exchange(self.err, "ar_generate_coop_spans")
+            eng._ar_check_exchange(self.err, "ar_generate_coop_scalar_spans" if g.scalar_input else "ar_generate_coop_spans")
         res = {}
         for i, c, n, off in zip(plan.clips, sel, ns, offs):
             h = handles[int(i)]
@@ -362,6 +374,10 @@ class DecodeSession:
 
 
 class WaeEngine:
+    # the scalar cooperative opt-ins (ar_path), off on the class: an engine whose __init__ has not run routes as one that never opted in
+    ar_scalar_coop = False
+    ar_scalar_fast = False
+
     def __init__(self, geom: P.Geometry, dtype="bf16", device="cuda:0", dropout: float = 0.0, drop_seed: int = 0x5EED):
         """dtype: 'fp32' (exact, the parity mode), 'bf16' (default throughput mode) or 'fp16' (BASELINE config C5) storage of
         activations and packed weights; accumulation, biases, losses, gradients of parameters and the optimizer are fp32.
@@ -427,6 +443,7 @@ class WaeEngine:
         # which form of the cooperative decode kernel runs (ar_path(); arguments of the C ABI, not environment variables)
         self.ar_generic, self.ar_one_handover, self.ar_resident = False, False, (0, 0)
         self.ar_scalar_coop = False
+        self.ar_scalar_fast = False
         self._param_gen, self._prep_gen, self._ar_gen = 1, 0, -1
         self.err = torch.zeros(1, dtype=torch.int32, device=dev)      # sticky WAE_ERR_* bits set by the kernels (include/wae.h)
         # ---- step state: every attribute a later call creates or replaces starts here
@@ -959,7 +976,7 @@ class WaeEngine:
         self._ar_packed = True
 
     def ar_path(self, generic: bool = False, one_handover: bool = False, lds_layers: Optional[int] = None,
-                reg_layers: Optional[int] = None, scalar_coop: bool = False):
+                reg_layers: Optional[int] = None, scalar_coop: bool = False, scalar_fast: bool = False):
         """Selects the form of the cooperative decode kernel (csrc/ar_coop.hip) for this engine's next incremental_forward calls -- the
         A/B and test handles that rounds 4-5 read from the environment inside the library: `generic` = the any-shape kernel on the
         reference's geometry too; `one_handover` = one exchange per layer on host-formed W1_cur . W_out products (measured slower:
@@ -968,13 +985,26 @@ class WaeEngine:
         `scalar_coop` = scalar-input decoders ("raw" / "mulaw" inputs) decode on the cooperative any-shape kernel too
         (wae_ar_generate_coop_scalar) where class-id decoders would (<= 8 utterances; R, S, O <= 256; WAE_AR_COOP on; modes "logits" /
         "sample"), else on the one-CU kernel as without it.  Opt-in: the split sums round differently from the one-CU kernel's, whose
-        roll-out tests/test_gpu_mog.py pins bit for bit.  No effect on class-id decoders."""
+        roll-out tests/test_gpu_mog.py pins bit for bit.  No effect on class-id decoders.
+        `scalar_fast` = wherever a scalar cooperative decode is routed (incremental_forward / incremental_stream under scalar_coop,
+        decode_list_scalar(coop=True), team sessions) it asks for the constant-size scalar kernels (wae_ar_desc.scalar_input = 2) and
+        passes this call's generic / lds_layers / reg_layers along; geometries those kernels do not cover (anything but R = G = S = 256,
+        3 taps, C = 32, O <= 256) keep the any-shape kernel.  It implies nothing on its own: incremental_forward still needs
+        scalar_coop=True to leave the one-CU kernel.  Results differ from the any-shape kernel's by rounding (the sums are split
+        differently) and are bitwise the same across single, streamed, list and session decodes at one setting."""
         enc = lambda v: 0 if v is None else (-1 if int(v) == 0 else int(v))  # noqa: E731  (wae_ar_desc: 0 = default, < 0 = none)
         if bool(one_handover) != self.ar_one_handover:
             self._ar_packed = False                    # the products are formed by pack_ar_weights
         self.ar_generic, self.ar_one_handover, self.ar_resident = bool(generic), bool(one_handover), (enc(lds_layers), enc(reg_layers))
-        self.ar_scalar_coop = bool(scalar_coop)
+        self.ar_scalar_coop, self.ar_scalar_fast = bool(scalar_coop), bool(scalar_fast)
         return self
+
+    def _ar_scalar_path(self):
+        """(coop_generic, resident_lds, resident_regs) of a scalar cooperative decode: the engine's own under ar_path(scalar_fast=True),
+        else zeros (the any-shape kernel reads none of them).  The caller sets ArDesc.scalar_sized (wae_ar_desc.scalar_input = 2) beside it."""
+        if self.ar_scalar_fast:
+            return (int(self.ar_generic), self.ar_resident[0], self.ar_resident[1])
+        return (0, 0, 0)
 
     def _pack_ar_fused(self):
         """include/wae.h: wae_ar_generate_coop_fused.  M_l = sqrt(.5) W1_cur[l] W_out[l-1] for the reference's own geometry (the one the
@@ -1153,7 +1183,7 @@ class WaeEngine:
             draw = z if normal else u_log
             draw = draw.to(dev, torch.float32).contiguous() if draw is not None else None
             sampled = (draw if normal else um) is not None
-            init_idx, path = 0, (0, 0, 0)
+            init_idx, path = 0, self._ar_scalar_path()
         else:
             forced = test_inputs.to(dev, torch.int32).contiguous() if test_inputs is not None else None
             if forced is None and not 0 <= int(init_idx) < g.O:
@@ -1166,6 +1196,7 @@ class WaeEngine:
             path = (int(self.ar_generic), self.ar_resident[0], self.ar_resident[1])
         d = L.ArDesc(self.dt, B, T, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, int(init_idx),
                      int(g.scalar_input), math.sqrt(1.0 / g.layers), nf, *path)
+        d.scalar_sized = int(g.scalar_input and coop and self.ar_scalar_fast)
         # (not zeroed here: _ar_launch zeroes them before every launch)
         msg, acc, err = self._ar_exchange(d, C, B, torch.empty) if coop else (None, None, None)
         return _ArDecode(d=d, n_forced=nf, forced=forced, c_up=c_up, zb=zb, gid32=gid32, coop=coop, C=C, ring=ring, normal=normal,
@@ -1467,7 +1498,8 @@ class WaeEngine:
         slots / coop / teams: as decode_list.  coop=True is itself the opt-in to the cooperative kernel: ar_path(scalar_coop=) is not
         consulted.  Returns, in the caller's order, a list of dict(x (T,) fp32 | None, logits (O, T) fp32 | None) -- the keys of scalar
         incremental_forward.  With coop=False every item is, bit for bit, incremental_forward for that utterance alone on the one-CU
-        kernel; with coop=True on the cooperative path (WAE_AR_COOP=1, ar_path(scalar_coop=True), the same C).  A wait between
+        kernel; with coop=True on the cooperative path (WAE_AR_COOP=1, ar_path(scalar_coop=True), the same C and the same
+        ar_path(scalar_fast=): with it the constant-size scalar kernels where the geometry has them).  A wait between
         team-mates that times out raises WaeError after the launch.  ValueError before any launch: a class-id geometry (use
         decode_list), an empty list, a mode other than "logits" / "sample", coop=True with R, S or O > 256."""
         g, who = self.g, "decode_list_scalar"
@@ -1536,7 +1568,8 @@ class WaeEngine:
         want = want_logits or m == 0
         params = torch.empty(total * g.O, dtype=torch.float32, device=dev) if want else None
         d = L.ArDesc(self.dt, n, 0, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, 0, 1,
-                     math.sqrt(1.0 / g.layers), 0)
+                     math.sqrt(1.0 / g.layers), 0, *(self._ar_scalar_path() if coop else ()))
+        d.scalar_sized = int(bool(coop) and self.ar_scalar_fast)
         operands = (L.ptr(inputs), L.ptr(um_d), L.ptr(dr_d), float(log_scale_min), int(bool(clamp_log_scale)), L.ptr(xs), L.ptr(params))
         C, ring, msg, acc, err = self._ar_list_buffers(d, plan, coop)
         if coop:
@@ -1563,8 +1596,10 @@ class WaeEngine:
         kernel (coop=False) or on the cooperative path (coop=True, WAE_AR_COOP=1, the same ar_path; one_handover is ignored).
         mode, slots, teams, want_logits, c_is_upsampled: as decode_list; log_scale_min / clamp_log_scale: as decode_list_scalar.
         Class-id decoders decode on `slots` one-CU workgroups or, coop=True, on `teams` cooperative teams (ar_path(generic=,
-        lds_layers=, reg_layers=) honoured as in decode_list).  Scalar-input decoders decode on the slots in modes "logits" / "sample"
-        (in "logits" the mixture parameters come back and x is None); coop=True raises NotImplementedError there.  ValueError: R, S or
+        lds_layers=, reg_layers=) honoured as in decode_list).  Scalar-input decoders decode in modes "logits" / "sample" (in "logits"
+        the mixture parameters come back and x is None): on the slots, or with coop=True on the teams once the engine has opted in with
+        ar_path(scalar_coop=True) -- without that opt-in coop=True raises NotImplementedError -- on the any-shape kernel or, under
+        ar_path(scalar_fast=True), the constant-size scalar kernels (wae_ar_generate_coop_scalar_spans).  ValueError: R, S or
         O > 256 with coop=True; a mode the matching list call does not take."""
         return DecodeSession(self, mode=mode, coop=coop, slots=slots, teams=teams, want_logits=want_logits, c_is_upsampled=c_is_upsampled,
                              log_scale_min=log_scale_min, clamp_log_scale=clamp_log_scale)
