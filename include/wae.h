@@ -114,6 +114,32 @@ int wae_enc_conv_fwd(const float* x, const float* w, const float* bias, float* y
                      int32_t Tin, int32_t Cout, int32_t k, int32_t stride, int32_t pad, int32_t relu,
                      int32_t residual, void* stream);
 
+/* ---- a1 over a LIST of utterances of unequal lengths (vqvae_model.py:17-23,48-51: the same block and Encoder.forward's chain of
+ * blocks + lin, for every utterance of a list in one launch per layer).  The reference encodes one dense (B,C,T) batch; zero-padding
+ * unequal utterances to a common length is NOT the same function (behind the first block bias + ReLU make the pad frames non-zero and
+ * the next k = 3 / k = 5 block reads them into the last valid frames), so a list is otherwise a loop of batch-1 calls.
+ * Packed layout: an activation of the list is channel-major and packed along time -- x (Cin, in_pitch) fp32, utterance i owning the
+ * columns [in_off_i, in_off_i + Tin_i); y (Cout, out_pitch) with out_off_i and Tout_i = (Tin_i + 2*pad - k)/stride + 1.  Every
+ * utterance is zero-padded at its own two ends: a tap outside [0, Tin_i) reads 0, never the neighbour's column.
+ * Tables (DEVICE arrays the host builds -- packing.encode_list_plan; nothing here allocates or synchronises): segs, nsegs records
+ * wae_seg; tiles, ntiles pairs (segment, to0): the workgroup (tile, channel block) computes outputs [to0, to0 + et) of that segment
+ * for 32 output channels.  The tiles of a segment start at multiples of et and cover [0, Tout_i) once.  Grid (ntiles, ceil(Cout/32)).
+ * et: 8, 16 or 32, the tile length the table was built for; the result does not depend on it.
+ * Every utterance's columns are, bit for bit, what wae_enc_conv_fwd writes for that utterance alone (B = 1): the value of an output
+ * is the same fixed sequence of fmaf and adds in both kernels (csrc/enc_list.hip), whatever else is in the list.  residual reads x at
+ * (oc, in_off_i + ot).  Columns of y that no segment owns are not written.
+ * Returns WAE_EINVAL for null x / w / y / segs / tiles, sizes < 1, nsegs or ntiles < 1, et outside {8, 16, 32}, a pitch < 1, or
+ * residual on a conv that is not same-shape (stride 1, Cin == Cout, 2*pad == k-1), as wae_enc_conv_fwd; WAE_EUNSUPPORTED for a
+ * (k, stride) other than (1,1), (3,1), (5,2), (5,1) -- the caller then loops wae_enc_conv_fwd.  A tile whose record does not fit the
+ * pitches, names no segment or contradicts the Tout formula is skipped by the kernel: nothing is read or written for it.
+ * The quantiser needs no list entry: wae_vq_nearest / wae_vq_slice with B = 1, Dtot = Cc, Tq = sum of Tq_i on the packed latents
+ * (Cc, sum Tq_i) -- the row of (b = 0, t) is the packed column t; idx and quant are per row (so per utterance, bit for bit the
+ * batch-1 call's), stats are the LIST's aggregate loss and perplexity. */
+typedef struct wae_seg { int32_t in_off, Tin, out_off, Tout; } wae_seg;
+int wae_enc_conv_fwd_list(const float* x, const float* w, const float* bias, float* y, const wae_seg* segs, int32_t nsegs,
+                          const int32_t* tiles, int32_t ntiles, int32_t et, int32_t in_pitch, int32_t out_pitch, int32_t Cin,
+                          int32_t Cout, int32_t k, int32_t stride, int32_t pad, int32_t relu, int32_t residual, void* stream);
+
 /* ---- a2 VectorQuantize.forward (vector_quantization.py:21-49) -----------------------------------------
  * lat (B,D,Tq) fp32, emb (K,D).  idx int64 (B*Tq) first-minimum of ||e||^2+||x||^2-2x.e; quant (B,D,Tq);
  * stats[0] = vq_loss = (beta+1)*mean((q-x)^2) forward value, stats[1] = perplexity; hist: (K+1) int32 scratch. */

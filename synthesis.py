@@ -148,30 +148,34 @@ def read_features(args, src):
 def batch_decode(eng, args, pairs, sp2ind, out_dir):
     """--batch-decode: the loop of main() with its decodes gathered into one WaeEngine.decode_list call (decode_list_scalar for a
     scalar-input model: "raw" / "mulaw", whose loop under --batch-coop is the one run with --coop-scalar).  Per pair, in the list's
-    order: the seed (if any), the encoder, the quantizer and the draws of all its samples -- the order in which the loop consumes
-    the generator -- then one launch for all pairs, then the loop's post-processing and file names.  --batch-coop: that launch on
-    cooperative teams (decode_list(coop=True), --batch-teams of them): the loop's bytes where the loop decodes on the cooperative path
+    order: the seed (if any) and the draws of all its samples -- the order in which the loop consumes the generator; the encoder and
+    the quantizer, which draw nothing, run before that as one WaeEngine.encode_list over all pairs -- then one launch for all pairs,
+    then the loop's post-processing and file names.  --batch-coop: that launch on cooperative teams (decode_list(coop=True), --batch-teams of them): the loop's bytes where the loop decodes on the cooperative path
     (WAE_AR_COOP=1, the default), as plain --batch-decode gives the loop's bytes under WAE_AR_COOP=0."""
     from scipy.io import wavfile
     device = eng.device
     if eng.weights_dirty:
         eng.prepare_weights()
-    items, names = [], []
+    # every pair's features first, then ONE encoder + quantiser call for the whole list (WaeEngine.encode_list: per pair the bytes of
+    # its own encoder_forward + vq_forward).  Neither draws random numbers, so the generator is consumed exactly as in the loop.
+    read = []
     for src, tar in pairs:
         src, fid, c = read_features(args, src)
         if tar not in sp2ind:
             raise KeyError(f"cant find sp {tar} in sp2ind {args.speaker2ind}")
+        read.append((tar, fid, c))
+    quants = [r["quant"] for r in eng.encode_list([np.ascontiguousarray(c.T).astype(np.float32) for _, _, c in read], want_idx=False)]
+    items, names = [], []
+    for (tar, fid, c), quant in zip(read, quants):
         length = c.shape[0] * int(args.up_factor)
         if args.seed is not None:
             torch.manual_seed(args.seed)
-        ct = torch.from_numpy(np.ascontiguousarray(c.T[None]).astype(np.float32)).to(device)
-        quant, _, _ = eng.vq_forward(eng.encoder_forward(ct))
         if eng.g.scalar_input:
             u_mix, draw = eng.scalar_draws(length)
-            items.append(dict(c=quant[0].clone(), gid=sp2ind[tar], T=length, u_mix=u_mix,
+            items.append(dict(c=quant.contiguous(), gid=sp2ind[tar], T=length, u_mix=u_mix,
                               **{"z" if eng.g.output_distribution == "Normal" else "u_log": draw}))
         else:
-            items.append(dict(c=quant[0].clone(), gid=sp2ind[tar], T=length, init_idx=int(args.initial_value),
+            items.append(dict(c=quant.contiguous(), gid=sp2ind[tar], T=length, init_idx=int(args.initial_value),
                               uniforms=torch.rand(1, length, device=device)))
         names.append(f"{out_dir}{tar}_{fid}.wav")
     how = dict(coop=True, teams=args.batch_teams) if args.batch_coop else {}

@@ -1,0 +1,101 @@
+#!/usr/bin/env python
+"""What the per-utterance encode loop costs and what list encoding (WaeEngine.encode_list) saves: the encoder and quantiser of
+hps/vqwae.json (39 MFCC channels, encoder_hid 256, 64 latent channels, 256 codes; fp32) on lists of unequal lengths.
+
+usage: bench_encode_list.py [--sizes 1,16,256,2048] [--repeats 5] [--min-frames 100] [--max-frames 1500]
+    --sizes     utterances per list, one measurement each
+    --repeats   timed repeats per measurement (at least 5); the median is reported with the fastest and the slowest
+Frame counts are drawn with numpy.random.default_rng(1234), uniform in [--min-frames, --max-frames]: the ZeroSpeech length distribution
+is not available to this tool, so the lengths are a stand-in, not the corpus.
+Per list size, two pairs, each in this one process, warmed, the two sides alternating repeat by repeat:
+  device to device   the loop of encoder_forward + vq_forward per utterance (what every caller did before the list form; this change
+                     does not touch that code) against one encode_list, inputs already on the device, outputs left there
+  host to host       inference_2019.encode_features per utterance against inference_2019.encode_features_list: the copies to the
+                     device and back to the host included
+Prints one line per measurement and one JSON line at the end.  The list's results are compared with the loop's bit for bit first."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import inference_2019 as inf  # noqa: E402
+from oracle import wae_oracle as O  # closed-form weights only  # noqa: E402
+from wavenet_autoencoders_amd import Geometry  # noqa: E402
+from wavenet_autoencoders_amd.engine import WaeEngine  # noqa: E402
+
+# hps/vqwae.json: the encoder (dim_in 39, encoder_hid 256, cin_channels 64, K 256); the decoder is not run here and is kept small
+CFG = dict(layers=4, stacks=2, R=32, G=48, S=32, O=64, Cc=64, Cg=8, k=3, n_speakers=5, upsample_scales=[4, 4, 8, 5], cin_pad=0,
+           c_in=39, encoder_hid=256, K=256)
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def pair(name, a, b, repeats):
+    """a, b alternating, one warm-up each -> {side: (median, min, max)} in seconds"""
+    a(), b()
+    ta, tb = [], []
+    for _ in range(repeats):
+        ta.append(timed(a))
+        tb.append(timed(b))
+    return {k: (statistics.median(v), min(v), max(v)) for k, v in (("loop", ta), ("list", tb))}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--sizes", default="1,16,256,2048")
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--min-frames", type=int, default=100)
+    ap.add_argument("--max-frames", type=int, default=1500)
+    args = ap.parse_args(argv)
+    if args.repeats < 5:
+        ap.error("--repeats: at least 5")
+    eng = WaeEngine(Geometry.from_cfg(CFG), dtype="fp32")
+    eng.load_state_dict(O.make_state_dict(dict(CFG), salt=7))
+    eng.prepare_weights()
+    rng = np.random.default_rng(1234)
+    gen = torch.Generator().manual_seed(1234)
+    record = dict(cfg="hps/vqwae.json encoder: c_in 39, encoder_hid 256, Cc 64, K 256, fp32", repeats=args.repeats,
+                  lengths=f"uniform {args.min_frames}..{args.max_frames} frames, numpy default_rng(1234) (a stand-in for ZeroSpeech)", runs=[])
+    print(record["cfg"] + "; " + record["lengths"], flush=True)
+    for n in [int(s) for s in args.sizes.split(",")]:
+        Fs = rng.integers(args.min_frames, args.max_frames + 1, n)
+        host = [(torch.randn(int(F), CFG["c_in"], generator=gen) * 1.7).numpy() for F in Fs]          # (N_i, c_in), as the .npy files
+        dev = [torch.from_numpy(np.ascontiguousarray(h.T)).cuda() for h in host]                      # (c_in, F_i)
+
+        def loop_dev():
+            return [eng.vq_forward(eng.encoder_forward(x[None]))[0] for x in dev]
+
+        def list_dev():
+            return eng.encode_list(dev, want_idx=False)
+
+        same = all(torch.equal(a[0], b["quant"]) for a, b in zip(loop_dev(), list_dev()))
+        same = same and all(np.array_equal(inf.encode_features(eng, h), g) for h, g in zip(host[:16], inf.encode_features_list(eng, host)[:16]))
+        runs = dict(d2d=pair("d2d", loop_dev, list_dev, args.repeats),
+                    h2h=pair("h2h", lambda: [inf.encode_features(eng, h) for h in host], lambda: inf.encode_features_list(eng, host),
+                             args.repeats))
+        frames = int(Fs.sum())
+        for kind, label in (("d2d", "device to device"), ("h2h", "host to host    ")):
+            lo, li = runs[kind]["loop"], runs[kind]["list"]
+            print(f"{n:5d} utterances, {frames:8d} frames, {label}: loop {lo[0] * 1e3:9.2f} ms ({lo[1] * 1e3:.2f} .. {lo[2] * 1e3:.2f}), "
+                  f"encode_list {li[0] * 1e3:9.2f} ms ({li[1] * 1e3:.2f} .. {li[2] * 1e3:.2f}), loop / list {lo[0] / li[0]:6.2f}; "
+                  f"per utterance {lo[0] / n * 1e6:8.1f} us against {li[0] / n * 1e6:8.1f} us; bit for bit: {same}", flush=True)
+            record["runs"].append(dict(utterances=n, frames=frames, kind=kind, loop_ms=[t * 1e3 for t in lo], list_ms=[t * 1e3 for t in li],
+                                       ratio=lo[0] / li[0], same=bool(same)))
+    print(json.dumps(record))
+    return 0 if all(r["same"] for r in record["runs"]) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

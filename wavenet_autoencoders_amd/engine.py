@@ -723,6 +723,76 @@ class WaeEngine:
                 "vq_nearest")
         return quant, idx, stats
 
+    def encode_list(self, feats, want_latents: bool = False, want_idx: bool = True, max_frames: Optional[int] = None):
+        """Encoder + quantiser for a LIST of utterances of unequal lengths (include/wae.h: wae_enc_conv_fwd_list): one launch per
+        encoder block, one for lin and one quantiser call for the whole list, where encoder_forward takes equal lengths only, a loop
+        over it is thirteen launches and two copies per utterance, and zero-padding to a common length gives other latents at the
+        clip ends (the pad frames stop being zero behind the first block).
+
+        feats: a sequence of (c_in, F_i) float tensors or arrays, on the host or on the device, F_i >= 1, lengths free.  They are
+        packed along time in the caller's order into ONE (c_in, sum F_i) input (one upload when they come from the host); two
+        ping-pong (encoder_hid, sum F_i) buffers carry the blocks, since nothing is saved for a backward; every layer's tables
+        (packing.encode_list_plan) go up as one int32 array.
+        max_frames: the most frames (sum F_i) of one group, by default packing.ENC_LIST_MAX_FRAMES = 32768, which keeps the two
+        activation buffers at 192 MiB for encoder_hid = 768; a longer list runs as consecutive groups (an utterance longer than
+        max_frames is a group of its own).  The bytes of every item are the same for every grouping and every order.
+        Returns, in the caller's order, a list of dict(quant (Cc, Tq_i) fp32, idx (Tq_i,) int64 | None (want_idx=False),
+        latents (Cc, Tq_i) fp32 | None (want_latents=False)); every item is, bit for bit, encoder_forward + vq_forward of that
+        utterance alone.  The tensors of an item are views of its group's packed (Cc, sum Tq_i) arrays (not contiguous).
+        ValueError, before any launch: an empty list, an item that is not (c_in, F_i) with F_i >= 1, an engine without an encoder."""
+        g = self.g
+        if not g.has_encoder:
+            raise ValueError("encode_list: this engine has no encoder (a decoder-only geometry: c_in is None)")
+        feats = list(feats)
+        if not feats:
+            raise ValueError("encode_list: an empty list")
+        for i, f in enumerate(feats):
+            shape = tuple(getattr(f, "shape", ()))
+            if len(shape) != 2 or shape[0] != g.c_in:
+                raise ValueError(f"encode_list: item {i} has shape {shape}; every item is (c_in, F) = ({g.c_in}, F)")
+            if shape[1] < 1:
+                raise ValueError(f"encode_list: item {i} has no frames (F >= 1)")
+        cap = P.ENC_LIST_MAX_FRAMES if max_frames is None else int(max_frames)
+        if cap < 1:
+            raise ValueError(f"encode_list: max_frames {cap} < 1")
+        if self.weights_dirty:
+            self.prepare_weights()
+        out = []
+        for lo, hi in P.encode_list_groups([f.shape[1] for f in feats], cap):
+            out += self._encode_group(feats[lo:hi], want_latents, want_idx)
+        return out
+
+    def _encode_group(self, feats, want_latents, want_idx):
+        """one group of encode_list: pack, eleven list launches, one quantiser call"""
+        g, lib, st, dev = self.g, self.lib, self.stream(), self.device
+        plan = P.encode_list_plan([f.shape[1] for f in feats])
+        if all(not (torch.is_tensor(f) and f.is_cuda) for f in feats):          # all on the host: pack there, one upload
+            x = torch.cat([torch.as_tensor(f).to(torch.float32) for f in feats], dim=1).to(dev)
+        else:
+            x = torch.cat([torch.as_tensor(f).to(dev, torch.float32) for f in feats], dim=1)
+        x = x.contiguous()
+        table = torch.from_numpy(plan.table).to(dev)
+        width = max(self.lay.shapes[f"encoder.net.{i}.conv.weight"][0] for i in range(len(P.ENCODER_BLOCKS)))
+        pong = [torch.empty(width * plan.total_F, dtype=torch.float32, device=dev) for _ in range(2)]
+        lat = torch.empty(g.Cc, plan.total_Tq, dtype=torch.float32, device=dev)
+        convs = [(f"encoder.net.{i}.conv", 1) for i in range(len(P.ENCODER_BLOCKS))] + [("encoder.lin", 0)]
+        for i, ((name, relu), ly) in enumerate(zip(convs, plan.layers)):
+            co, ci = self.lay.shapes[name + ".weight"][:2]
+            y = lat if not relu else pong[i & 1]
+            res = int(bool(relu) and ly.stride == 1 and ci == co)
+            rc = lib.wae_enc_conv_fwd_list(L.ptr(x), L.ptr(self.eff[self.lay.off(name + ".weight"):]),
+                                           L.ptr(self.eff[self.lay.off(name + ".bias"):]), L.ptr(y), L.ptr(table[ly.seg_off:]), ly.nsegs,
+                                           L.ptr(table[ly.tile_off:]), ly.ntiles, ly.et, ly.in_pitch, ly.out_pitch, ci, co, ly.k,
+                                           ly.stride, ly.pad, relu, res, st)
+            L.check(rc, "enc_conv_fwd_list")
+            x = y
+        # the quantiser on the packed latents as ONE clip of sum Tq_i frames: rows are per frame, so idx and quant are per utterance
+        # what vq_forward gives it alone; stats would be the list's aggregate and are not returned
+        quant, idx, _ = self.vq_forward(lat.view(1, g.Cc, plan.total_Tq))
+        quant = quant[0]
+        sl = [slice(int(o), int(o + t)) for o, t in zip(plan.q_offsets, plan.Tq)]
+        return [dict(quant=quant[:, s], idx=idx[s] if want_idx else None, latents=lat[:, s] if want_latents else None) for s in sl]
+
     def upsample_forward(self, c: torch.Tensor, out: torch.Tensor, save: Optional[Saved] = None):
         """a3: c (B,Cc,Tc) fp32 -> out (B, (Tc - 2 cin_pad) * prod(scales), Ccp) time-major compute dtype.  ConvInUpsampleNetwork
         (upsample.py:69-85): conv_in eats cin_pad frames at either end, then the stages; plain UpsampleNetwork (Geometry.conv_in False,

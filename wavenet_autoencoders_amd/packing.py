@@ -127,6 +127,122 @@ class Geometry:
 ENCODER_BLOCKS = [(3, 1), (3, 1), (5, 2), (5, 2), (3, 1), (3, 1), (1, 1), (1, 1), (1, 1), (1, 1)]  # vqvae_model.py:32-40
 
 
+ENC_LIST_ETS = (8, 16, 32)     # tile lengths of the list kernel (include/wae.h: wae_enc_conv_fwd_list)
+# Default cap on the frames of one group of WaeEngine.encode_list: the two ping-pong activation buffers of a group are
+# 2 x encoder_hid x sum F_i fp32, so 32768 frames keep them at 192 MiB for encoder_hid = 768 (the width VQVAE defaults to,
+# vqvae_model.py:54; 64 MiB at the 256 of hps/vqwae.json).
+ENC_LIST_MAX_FRAMES = 32768
+
+
+class EncListLayer(NamedTuple):
+    """One layer of an EncListPlan: (k, stride, pad) of the conv; et, its tile length; nsegs / ntiles and the int32 offsets seg_off /
+    tile_off of its segment records (nsegs x 4: in_off, Tin, out_off, Tout) and tile pairs (ntiles x 2: segment, to0) inside the plan's
+    one table; in_pitch / out_pitch, the columns of the packed input and output."""
+    k: int
+    stride: int
+    pad: int
+    et: int
+    nsegs: int
+    ntiles: int
+    seg_off: int
+    tile_off: int
+    in_pitch: int
+    out_pitch: int
+
+
+class EncListPlan(NamedTuple):
+    """encode_list_plan's answer.  layers: ENCODER_BLOCKS in order, then lin; table: every layer's tables in ONE int32 array (one
+    upload); Fs, Tq: frames and latent frames per utterance; in_offsets, q_offsets: the first column of every utterance in the packed
+    input and in the packed latents (running sums, the caller's order); total_F, total_Tq: the two pitches."""
+    layers: List[EncListLayer]
+    table: np.ndarray
+    Fs: np.ndarray
+    Tq: np.ndarray
+    in_offsets: np.ndarray
+    q_offsets: np.ndarray
+    total_F: int
+    total_Tq: int
+
+    def segs(self, i: int) -> np.ndarray:
+        ly = self.layers[i]
+        return self.table[ly.seg_off:ly.seg_off + 4 * ly.nsegs].reshape(ly.nsegs, 4)
+
+    def tiles(self, i: int) -> np.ndarray:
+        ly = self.layers[i]
+        return self.table[ly.tile_off:ly.tile_off + 2 * ly.ntiles].reshape(ly.ntiles, 2)
+
+
+def enc_list_tables(Tin, k: int, stride: int, pad: int, et: Optional[int] = None):
+    """Tables of ONE wae_enc_conv_fwd_list launch for utterances of Tin frames packed back to back, in the caller's order:
+    -> (segs (n, 4) int32, tiles (ntiles, 2) int32, et, Tout (n,)).  The offsets are the running sums of Tin and of Tout, so the
+    pitches are their totals.  The tiles of a segment start at 0, et, 2 et, ... below its Tout: they cover [0, Tout_i) exactly once and
+    none reaches into another segment (a tile belongs to one segment; the kernel masks its tail beyond Tout_i).
+    et None: the tile length of least modelled cost sum_i ceil(Tout_i / et) * (et + 32) -- a tile costs its et output columns plus a
+    fixed part (staging the window, one pass over its 32 channels' weights) put at 32 columns, the value with which a single
+    utterance gets exactly the rule of wae_enc_conv_fwd (8 up to 8 outputs, 16 up to 16, else 32); ties go to the longer tile.  A
+    model, not a measurement; the choice changes no result."""
+    Tin = np.asarray(Tin, dtype=np.int64).reshape(-1)
+    if Tin.size < 1:
+        raise ValueError("enc_list_tables: an empty list")
+    if int(Tin.min()) < 1:
+        raise ValueError(f"enc_list_tables: every utterance has at least one frame (got {int(Tin.min())})")
+    Tout = (Tin + 2 * pad - k) // stride + 1
+    if int(Tout.min()) < 1:
+        raise ValueError(f"enc_list_tables: an utterance of {int(Tin[np.argmin(Tout)])} frames has no output under k={k}, pad={pad}")
+    if max(int(Tin.sum()), int(Tout.sum())) >= 2 ** 31:
+        raise ValueError("enc_list_tables: the packed list does not fit 32-bit columns")
+    if et is None:
+        et = min(ENC_LIST_ETS, key=lambda e: (int((-(-Tout // e)).sum()) * (e + 32), -e))
+    if et not in ENC_LIST_ETS:
+        raise ValueError(f"enc_list_tables: et {et} is not one of {ENC_LIST_ETS}")
+    in_off = np.concatenate([[0], np.cumsum(Tin)[:-1]])
+    out_off = np.concatenate([[0], np.cumsum(Tout)[:-1]])
+    segs = np.stack([in_off, Tin, out_off, Tout], axis=1).astype(np.int32)
+    per = -(-Tout // et)                                           # tiles per segment
+    seg_of = np.repeat(np.arange(Tin.size), per)
+    first = np.concatenate([[0], np.cumsum(per)[:-1]])             # index of every segment's first tile
+    to0 = (np.arange(int(per.sum())) - np.repeat(first, per)) * et
+    tiles = np.stack([seg_of, to0], axis=1).astype(np.int32)
+    return segs, tiles, int(et), Tout
+
+
+def encode_list_plan(Fs, et: Optional[int] = None) -> EncListPlan:
+    """Launch plan of WaeEngine.encode_list for utterances of Fs feature frames (>= 1 each), packed in the caller's order: the tables
+    of every block of ENCODER_BLOCKS (pad k // 2, vqvae_model.py:17-23) and of lin (k = 1), each layer's output offsets being the next
+    layer's input offsets.  et: force one tile length (8, 16 or 32) on every layer; None: enc_list_tables chooses per layer.
+    Pure numpy: the plan is a function of the lengths alone."""
+    Fs = np.asarray(Fs, dtype=np.int64).reshape(-1)
+    if Fs.size < 1:
+        raise ValueError("encode_list_plan: an empty list")
+    if int(Fs.min()) < 1:
+        raise ValueError(f"encode_list_plan: every utterance has at least one frame (got {int(Fs.min())})")
+    layers, parts, off, T = [], [], 0, Fs
+    for k, s in list(ENCODER_BLOCKS) + [(1, 1)]:
+        segs, tiles, e, Tout = enc_list_tables(T, k, s, k // 2, et)
+        layers.append(EncListLayer(k, s, k // 2, e, len(segs), len(tiles), off, off + segs.size, int(T.sum()), int(Tout.sum())))
+        parts += [segs.reshape(-1), tiles.reshape(-1)]
+        off += segs.size + tiles.size
+        T = Tout
+    zero = np.zeros(1, dtype=np.int64)
+    return EncListPlan(layers, np.concatenate(parts).astype(np.int32), Fs, T, np.concatenate([zero, np.cumsum(Fs)[:-1]]),
+                       np.concatenate([zero, np.cumsum(T)[:-1]]), int(Fs.sum()), int(T.sum()))
+
+
+def encode_list_groups(Fs, max_frames: int) -> List[Tuple[int, int]]:
+    """Consecutive groups [lo, hi) of a list of Fs frames whose sums stay within max_frames; an utterance longer than max_frames is a
+    group of its own (an utterance is never split)."""
+    if int(max_frames) < 1:
+        raise ValueError(f"encode_list_groups: max_frames {int(max_frames)} < 1")
+    out, lo, tot = [], 0, 0
+    for i, f in enumerate(Fs):
+        if i > lo and tot + int(f) > max_frames:
+            out.append((lo, i))
+            lo, tot = i, 0
+        tot += int(f)
+    out.append((lo, len(Fs)))
+    return out
+
+
 UP_ACT_KINDS = {"ReLU": 1, "LeakyReLU": 2, "Tanh": 3, "Sigmoid": 4}      # include/wae.h: wae_act_fwd
 
 

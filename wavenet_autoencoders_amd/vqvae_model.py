@@ -116,3 +116,10 @@ class VQVAE(ArenaModel):
                 eng.prepare_weights()
             lat = eng.encoder_forward(x.float())
             return eng.vq_forward(lat)[0]
+
+    def encode_list(self, xs):
+        """encode for a list of utterances of unequal lengths: xs, a sequence of (c_in, F_i) features -> a list of (hid, F_i') quantised
+        latents, each bit for bit encode(x[None])[0] of that utterance alone, from one launch per encoder layer for the whole list
+        (WaeEngine.encode_list; the reference has no list form -- zero-padding to one length changes the latents at the clip ends)."""
+        with torch.no_grad():
+            return [r["quant"] for r in self.engine().encode_list(xs, want_idx=False)]
