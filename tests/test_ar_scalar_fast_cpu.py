@@ -240,11 +240,26 @@ def test_ar_path_takes_scalar_fast_and_the_scalar_routes_read_it():
     assert eng.ar_scalar_coop and eng._ar_scalar_path() == (0, 2, -1)
     eng.ar_path(scalar_coop=True, generic=True, lds_layers=2)
     assert eng.ar_scalar_fast is False and eng._ar_scalar_path() == (0, 0, 0)      # without the flag: today's zeros
-    for fn in (WaeEngine._ar_open, WaeEngine.decode_list_scalar, DecodeSession._open_device):
-        src = inspect.getsource(fn)
-        assert "_ar_scalar_path()" in src and "scalar_sized" in src, fn.__name__
-    assert "wae_ar_generate_coop_scalar_spans" in inspect.getsource(DecodeSession.step)
-    assert "_ar_check_exchange" in inspect.getsource(DecodeSession.step)
+    # every scalar route reads it in ONE place -- decode.ar_desc, the only constructor of a decode's descriptor
+    # (tests/test_decode_host_cpu.py: the structure on the sources, and the descriptor of every route on a device-less engine) -- and
+    # the team session's entry is in the launch table, whose launcher checks the exchange of every team entry
+    from wavenet_autoencoders_amd import Geometry, decode
+    assert decode.ENTRIES[("spans", True, True)] == "wae_ar_generate_coop_scalar_spans"
+    eng.g, eng.dt = Geometry.from_cfg(CFG), 1
+    for coop, fast, want in ((True, True, 2), (True, False, 1), (False, True, 1)):
+        eng.ar_path(scalar_coop=True, scalar_fast=fast, lds_layers=2)
+        d = decode.ar_desc(eng, B=1, T=8, mode=2, init_idx=0, n_forced=0, coop=coop)
+        assert d.scalar_input == want and d.resident_lds == (2 if want == 2 else 0), (coop, fast)
+    assert DecodeSession is decode.DecodeSession
+    seen, buf = [], type("Buf", (), {"data_ptr": lambda self: 0x1000})
+    msg, acc, err = buf(), buf(), buf()
+    eng.lib = type("Lib", (), {ENTRY: staticmethod(lambda *a: seen.append(len(a)) or 0)})()
+    eng.stream = lambda: None
+    eng._ar_check_exchange = lambda e, who: seen.append((e, who))
+    decode.launch(eng, ("spans", True, True), d, [None] * 15, (None, None, None, -7.0, 0, None, None), C=32, dist=0,
+                  queue=(1, 1, None, None), total=8, exchange=(msg, acc, err), hold=lambda: seen.append("hold"))
+    # the entry first, with all its arguments; the operands are stored while it runs; then its exchange check
+    assert seen == [34, "hold", (err, "ar_generate_coop_scalar_spans")]
 
 
 # ---- synthesis.py ----------------------------------------------------------------------------------------------------------------------

@@ -21,7 +21,7 @@ TWIN = {SLOTS: "wae_ar_generate_list", SCALAR: "wae_ar_generate_scalar_list", TE
 # ---- the record and the symbols --------------------------------------------------------------------------------------------------------
 def test_span_record_is_forty_bytes_and_matches_the_packed_dtype():
     from wavenet_autoencoders_amd import _lib
-    from wavenet_autoencoders_amd.engine import _AR_SPAN
+    from wavenet_autoencoders_amd.decode import _AR_SPAN
     names = ["off", "ring", "T", "t0", "n_forced", "init_idx", "row", "reserved"]
     assert [n for n, _ in _lib.ArSpan._fields_] == names == list(_AR_SPAN.names)
     assert ctypes.sizeof(_lib.ArSpan) == 40 == _AR_SPAN.itemsize
@@ -297,10 +297,22 @@ def test_decode_session_surface():
     assert list(inspect.signature(WaeEngine.decode_list_stream).parameters)[:3] == ["self", "items", "chunk"]
     for word in ("bit for bit", "NotImplementedError", "ar_path"):
         assert word in WaeEngine.decode_session.__doc__, word
-    # the per-clip set-up goes through the helpers every decode shares, the round through the planner
-    src = inspect.getsource(DecodeSession)
-    for helper in ("_ar_cond_rows", "_ar_speaker_rows", "_ar_net_args", "_ar_exchange", "_ar_check_exchange", "scalar_draws", "ar_round_plan"):
-        assert helper in src, helper
+    # the per-clip set-up and the round go through what every decode route shares (tests/test_decode_host_cpu.py checks that module's
+    # structure): which functions of the module each method calls, read off its syntax tree
+    import ast
+    import textwrap
+    from wavenet_autoencoders_amd import decode
+    assert DecodeSession is decode.DecodeSession
+
+    def calls(fn):
+        tree = ast.parse(textwrap.dedent(inspect.getsource(fn)))
+        return {ast.unparse(n.func) for n in ast.walk(tree) if isinstance(n, ast.Call)}
+    assert {"clip_intake", "clip_draws", "_clip_cond", "eng._ar_speaker_rows", "self._open_device"} <= calls(DecodeSession.add)
+    assert {"ar_desc", "team_width", "group_count", "mixture", "eng._ar_exchange"} <= calls(DecodeSession._open_device)
+    assert {"P.ar_round_plan", "launch", "eng._ar_net_args", "_operands"} <= calls(DecodeSession.step)
+    assert "refuse_wide" in calls(DecodeSession.__init__)
+    for name in ("clip_intake", "clip_draws", "ar_desc", "team_width", "group_count", "mixture", "launch", "refuse_wide"):
+        assert inspect.isfunction(getattr(decode, name)), name
 
 
 # ---- synthesis.py ----------------------------------------------------------------------------------------------------------------------

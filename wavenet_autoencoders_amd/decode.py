@@ -1,0 +1,666 @@
+"""Autoregressive decode, host side: every route from WaeEngine's decode methods to a wae_ar_generate* entry (include/wae.h).
+
+Three forms of launch -- "batch" (incremental_forward / incremental_stream: B equal-length utterances), "list" (decode_list /
+decode_list_scalar: a work list of ragged items in one launch) and "spans" (DecodeSession: the next span of every live clip) -- each
+for class-id and scalar-input decoders, on one-CU workgroups or on cooperative teams.  They share ONE of each of: the descriptor
+(ar_desc), the small routing rules (team_width, group_count, mixture, coop_sized / refuse_wide), the per-item checks (clip_intake),
+the per-clip draws (clip_draws), the list decode (decode_list) and the launch (ENTRIES, ar_args, launch).  The functions take the engine
+as `eng`, like backward.py's; WaeEngine keeps the public methods, the packed weights and the helpers that read them (_ar_cond_rows,
+_ar_speaker_rows, _ar_exchange, _ar_net_args, _ar_scalar_path, _ar_check_exchange).  What the routes do differently on purpose is
+listed in DESIGN.md ("Decode host path").
+"""
+from __future__ import annotations
+
+import ctypes
+import dataclasses
+import math
+
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import packing as P
+
+# include/wae.h: wae_ar_item and wae_ar_span, as the host packs them
+_AR_ITEM = np.dtype([("off", "<i8"), ("T", "<i4"), ("n_forced", "<i4"), ("init_idx", "<i4"), ("row", "<i4")])
+_AR_SPAN = np.dtype([("off", "<i8"), ("ring", "<i8"), ("T", "<i4"), ("t0", "<i4"), ("n_forced", "<i4"), ("init_idx", "<i4"),
+                     ("row", "<i4"), ("reserved", "<i4")])
+
+# (form, scalar, coop) -> entry.  scalar: False (class ids), True, or "normal" for the one entry that has the distribution in its
+# name instead of a `dist` argument: the one-CU batch decode of a "Normal" geometry.
+ENTRIES = {
+    ("batch", False, False): "wae_ar_generate",
+    ("batch", False, True): "wae_ar_generate_coop_fused",
+    ("batch", True, False): "wae_ar_generate_scalar",
+    ("batch", "normal", False): "wae_ar_generate_scalar_mog",
+    ("batch", True, True): "wae_ar_generate_coop_scalar",
+    ("list", False, False): "wae_ar_generate_list",
+    ("list", False, True): "wae_ar_generate_coop_list",
+    ("list", True, False): "wae_ar_generate_scalar_list",
+    ("list", True, True): "wae_ar_generate_coop_scalar_list",
+    ("spans", False, False): "wae_ar_generate_spans",
+    ("spans", False, True): "wae_ar_generate_coop_spans",
+    ("spans", True, False): "wae_ar_generate_scalar_spans",
+    ("spans", True, True): "wae_ar_generate_coop_scalar_spans",
+}
+
+
+def ar_args(key, d, net, operands, stream, *, C=1, dist=0, queue=(), total=0, exchange=(), w_fused=None):
+    """The positional arguments of ENTRIES[key], by the rule above _lib._AR: the descriptor; C on the team entries; dist on the scalar
+    entries that take one (all but the one-CU batch entries); a work list's `queue` = (n, slots or teams, records, next) and, on
+    the team entries, `total`; the 15 network arguments `net`; the operands -- (inputs, uniforms, out, logits), or (inputs, u_mix, draws,
+    log_scale_min, clamp, out, params), "normal" without the clamp --; on the team entries `exchange` = (msg, acc, err) and, batch
+    class-id only, w_fused; the stream."""
+    form, scalar, coop = key
+    head = (C,) if coop else ()
+    if scalar and (coop or form != "batch"):
+        head += (dist,)
+    if form != "batch":
+        head += tuple(queue) + ((total,) if coop else ())
+    if scalar == "normal":
+        operands = operands[:4] + operands[5:]
+    tail = (tuple(exchange) + ((w_fused,) if form == "batch" and not scalar else ())) if coop else ()
+    return (ctypes.byref(d),) + head + tuple(net) + tuple(operands) + tail + (stream,)
+
+
+def launch(eng, key, d, net, operands, *, hold=None, exchange=None, w_fused=None, **head):
+    """One launch of ENTRIES[key] on the engine's stream; on a team entry (`exchange`: the (msg, acc, err) tensors, zeroed) the
+    time-out word is then read back (eng._ar_check_exchange: one device read).  `hold`: called between the two, where the caller
+    stores the launch's operands -- which frees the previous launch's while the kernel runs, not in front of it."""
+    name = ENTRIES[key]
+    ex = () if exchange is None else tuple(L.ptr(t) for t in exchange)
+    L.check(getattr(eng.lib, name)(*ar_args(key, d, net, operands, eng.stream(), exchange=ex, w_fused=L.ptr(w_fused), **head)), name[4:])
+    if hold is not None:
+        hold()
+    if key[2]:
+        eng._ar_check_exchange(exchange[2], name[4:])
+
+
+# ---- the small rules every route reads
+def team_width(eng):
+    """C: workgroups of one cooperative team (one utterance's gate rows over up to 32 CUs of an XCD)"""
+    return max(1, min(eng.opt.ar_coop_c, 32, eng.g.H, eng.g.S))
+
+
+def group_count(eng, coop, slots, teams):
+    """Teams of a cooperative launch (`teams`, clamped to 1..8: one XCD each) or its one-CU workgroups (`slots`; default: one per CU)"""
+    if coop:
+        return max(1, min(8 if teams is None else int(teams), 8))
+    return torch.cuda.get_device_properties(eng.device).multi_processor_count if slots is None else int(slots)
+
+
+def mixture(g):
+    """(normal, M): whether a scalar-input decoder draws from Gaussians, and its mixture count (0 for a class-id decoder)"""
+    normal = g.scalar_input and g.output_distribution == "Normal"
+    return normal, ((1 if (normal and g.O == 2) else g.O // 3) if g.scalar_input else 0)
+
+
+def coop_sized(g):
+    return max(g.R, g.S, g.O) <= 256
+
+
+def refuse_wide(g, who, instead):
+    if not coop_sized(g):
+        raise ValueError(f"{who}(coop=True): the cooperative kernels take R, S and O <= 256 (got {g.R}, {g.S}, {g.O}); "
+                         f"use the one-CU {instead} (coop=False)")
+
+
+def ar_desc(eng, *, B, T, mode, init_idx, n_forced, coop):
+    """THE wae_ar_desc of a decode.  The kernel-form triple (coop_generic, resident_lds, resident_regs) is read by the cooperative
+    entries only: a class-id decoder passes the engine's own (ar_path), a scalar-input one what _ar_scalar_path() says, together with
+    the request for the constant-size scalar kernels (scalar_input = 2) under ar_path(scalar_fast=True)."""
+    g, path = eng.g, ()
+    if coop:
+        path = eng._ar_scalar_path() if g.scalar_input else (int(eng.ar_generic), eng.ar_resident[0], eng.ar_resident[1])
+    d = L.ArDesc(eng.dt, B, T, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, mode, int(init_idx),
+                 int(g.scalar_input), math.sqrt(1.0 / g.layers), n_forced, *path)
+    d.scalar_sized = int(bool(coop) and eng.ar_scalar_fast)
+    return d
+
+
+def _operands(g, inputs, uni, u_mix, draw, log_scale_min, clamp, out, logits):
+    if g.scalar_input:
+        return (L.ptr(inputs), L.ptr(u_mix), L.ptr(draw), log_scale_min, clamp, L.ptr(out), L.ptr(logits))
+    return (L.ptr(inputs), L.ptr(uni), L.ptr(out), L.ptr(logits))
+
+
+def _io(g):
+    """(dtype of the inputs and outputs, the outputs' key in the result)"""
+    return (torch.float32, "x") if g.scalar_input else (torch.int32, "idx")
+
+
+def _wrong_draws(normal, u_log, z, at=""):
+    if normal and u_log is not None:
+        raise ValueError(f"{at}output_distribution 'Normal' draws from u_mix and z, not u_log")
+    if not normal and z is not None:
+        raise ValueError(f"{at}output_distribution 'Logistic' draws from u_mix and u_log, not z")
+
+
+def scalar_draws(eng, T):
+    g, dev = eng.g, eng.device
+    normal, M = mixture(g)
+    if normal:      # mixture.py:249 (the mixture pick, M > 1 only), then Normal(...).sample() (:266)
+        u_mix = torch.rand(1, T, M, device=dev) * (1 - 2e-5) + 1e-5 if M > 1 else None
+        return u_mix, torch.randn(1, T, device=dev)
+    u_mix = torch.rand(1, T, M, device=dev) * (1 - 2e-5) + 1e-5          # mixture.py:138,151
+    return u_mix, torch.rand(1, T, device=dev) * (1 - 2e-5) + 1e-5
+
+
+# ---- one item of a list or a session
+def clip_intake(g, device, mode, item, who, index=None, check_ids=True):
+    """Every check of one item (decode_list's / decode_list_scalar's mapping) for `mode` (0 "logits", 1 "argmax", 2 "sample"), before
+    anything else is allocated -> (T, forced, n_forced, init_idx, given): the forced prefix on `device` (at most T values; None where
+    there is none), the start class (0 where a prefix is forced, and for scalar-input decoders) and whether the item brings its own
+    scalar draws.  check_ids=False leaves the class-id range of the prefix to the caller (decode_list reads its packed array once)."""
+    at = f"{who}: " if index is None else f"{who}: item {index}: "
+    T = int(item["T"])
+    if T < 1:
+        raise ValueError(f"{at}every clip has at least one step (got {T})")
+    if g.Ccp and item.get("c") is None:
+        raise ValueError(f"{at}no conditioning c, the decoder has {g.Cc} conditioning channels")
+    ti = item.get("test_inputs")
+    if ti is not None:
+        ti = torch.as_tensor(ti).reshape(-1).to(device, _io(g)[0])[:T]
+    nf = 0 if ti is None else int(ti.numel())
+    if mode == 0 and nf < T:
+        raise ValueError(f"{at}mode 'logits' is teacher-forced: test_inputs must cover all {T} steps")
+    init, given = 0, False
+    if g.scalar_input:
+        normal, M = mixture(g)
+        um, ul, z = item.get("u_mix"), item.get("u_log"), item.get("z")
+        _wrong_draws(normal, ul, z, at)
+        if not normal and (um is None) != (ul is None):
+            raise ValueError(f"{at}u_mix and u_log come together")
+        if normal and z is not None and M > 1 and um is None:
+            raise ValueError(f"{at}{M} Gaussians need u_mix beside z")
+        given = (z if normal else ul) is not None
+    else:
+        init = item.get("init_idx")
+        init = 127 if init is None else int(torch.as_tensor(init).reshape(-1)[0])
+        if nf == 0 and not 0 <= init < g.O:
+            # wavenet.py:288 writes a one at the start class of the start vector: the same IndexError when there are fewer classes
+            raise IndexError(f"index {init} is out of bounds for dimension 2 with size {g.O}")
+        if check_ids and nf and (int(ti.min()) < 0 or int(ti.max()) >= g.O):
+            raise IndexError(f"{at}test_inputs hold a class id outside [0, {g.O})")
+        init = init if nf == 0 else 0
+    return T, (ti if nf else None), nf, init, given
+
+
+def clip_draws(eng, item, T, given, at):
+    """(uni, u_mix, draw) of one clip that samples, flat on the device: the item's own draws, or -- where it brings none -- what
+    incremental_forward draws for that utterance alone, by the same expressions in the same order (torch.rand(1, T); scalar_draws)."""
+    g, dev = eng.g, eng.device
+    flat = lambda a: torch.as_tensor(a).reshape(-1).to(dev, torch.float32)  # noqa: E731
+    if not g.scalar_input:
+        u = item.get("uniforms")
+        uni = (torch.rand(1, T, device=dev) if u is None else flat(u)).reshape(-1).contiguous()
+        assert uni.numel() == T, f"{at}{uni.numel()} uniforms for {T} steps"
+        return uni, None, None
+    normal, M = mixture(g)
+    um, dr = (item.get("u_mix"), item.get("z" if normal else "u_log")) if given else eng.scalar_draws(T)
+    if not normal or M > 1:
+        um = flat(um)
+        assert um.numel() == T * M, f"{at}u_mix holds {um.numel()} values for {T} steps of {M} mixtures"
+        um = um.view(T, M).contiguous()
+    else:
+        um = None
+    dr = flat(dr).contiguous()
+    assert dr.numel() == T, f"{at}{dr.numel()} draws for {T} steps"
+    return None, um, dr
+
+
+def _clip_cond(eng, item, T, c_is_upsampled, out, at):
+    """the item's conditioning (one utterance of batch 1) -> out (T, Ccp), zeroed"""
+    c = torch.as_tensor(item["c"]).to(eng.device, torch.float32)
+    eng._ar_cond_rows((c if c.dim() == 3 else c[None]).contiguous(), out.view(1, T, eng.g.Ccp), c_is_upsampled, at)
+
+
+def _gid32(eng, gids):
+    return torch.tensor([int(torch.as_tensor(x).reshape(-1)[0]) for x in gids], dtype=torch.int32, device=eng.device)
+
+
+# ---- batch: incremental_forward / incremental_stream
+@dataclasses.dataclass
+class _ArDecode:
+    """One batch decode between ar_open and its launches (ar_launch): what does not depend on the chunk."""
+    # geometry, mode, start class, ar_path() settings.  ONE descriptor for all launches: ar_launch overwrites d.T, d.n_forced and d.t0
+    # with the chunk's before every call (the library reads it during the call, never later), so outside a launch those three are stale
+    d: L.ArDesc
+    n_forced: int               # steps of the clip that `forced` covers
+    forced: Optional[torch.Tensor]
+    c_up: Optional[torch.Tensor]
+    zb: torch.Tensor
+    gid32: Optional[torch.Tensor]   # (held only so that wae_gproj_fwd's operand outlives its launch)
+    coop: bool
+    C: int
+    ring: torch.Tensor          # the decode's state: every launch continues in it
+    normal: bool
+    uni: Optional[torch.Tensor]
+    u_mix: Optional[torch.Tensor]
+    draw: Optional[torch.Tensor]    # u_log, or z of a "Normal" decoder
+    sampled: bool
+    want: bool
+    log_scale_min: float
+    clamp: int
+    w_fused: Optional[torch.Tensor]
+    exchange: Optional[tuple]       # (msg, acc, err) of a cooperative decode
+    last: Optional[torch.Tensor] = None     # (B,) the previous launch's last output
+
+
+def ar_open(eng, c, gid, T, *, mode, test_inputs, uniforms, init_idx, c_is_upsampled, want_logits, gvec, u_mix, u_log,
+            log_scale_min, clamp_log_scale, n_forced, z):
+    """What a decode of T steps fixes before its first launch, whatever its chunks (incremental_forward's arguments) -> the state
+    ar_launch runs steps of: the packed weights, the start classes, the forced prefix, the upsampled conditioning, the speaker
+    rows, the kernel path, the zeroed ring, the draws of all T steps and the exchange buffers."""
+    g, dev = eng.g, eng.device
+    if not eng._ar_packed or eng.weights_dirty:
+        eng.pack_ar_weights()
+    T = int(T)
+    B = c.shape[0] if c is not None else (test_inputs.shape[0] if test_inputs is not None else 1)
+    m = {"logits": 0, "argmax": 1, "sample": 2, "probs": 3, "raw": 4}[mode]
+    if not isinstance(init_idx, int) and not g.scalar_input:
+        ii = torch.as_tensor(init_idx).reshape(-1).to("cpu", torch.int64)
+        if ii.numel() == 1:
+            init_idx = int(ii[0])
+        else:
+            if ii.numel() != B:
+                raise ValueError(f"init_idx: {ii.numel()} start classes for {B} utterances")
+            if int(ii.min()) < 0 or int(ii.max()) >= g.O:
+                raise IndexError(f"index {int(ii.max() if ii.max() >= g.O else ii.min())} is out of bounds for dimension 2 with size {g.O}")
+            if test_inputs is None:     # (forced steps override the start class anyway: wavenet.py:300-302)
+                test_inputs, n_forced = ii.to(dev, torch.int32).reshape(B, 1), 1
+            init_idx = int(ii[0])
+    nf = 0
+    if test_inputs is not None:
+        nf = int(test_inputs.shape[1]) if n_forced is None else int(n_forced)
+        nf = max(0, min(nf, int(test_inputs.shape[1]), T))
+        if nf == 0:
+            test_inputs = None
+    if m == 0 and nf < T:
+        raise ValueError("mode 'logits' is teacher-forced: test_inputs must cover all T steps (use 'raw' to feed logits back)")
+    if g.scalar_input and m not in (0, 2):
+        raise ValueError("scalar-input decoders feed the drawn sample back: modes 'logits' and 'sample' only")
+    c_up = None
+    if g.Ccp:
+        c_up = torch.zeros(B, T, g.Ccp, dtype=eng.tdtype, device=dev)
+        eng._ar_cond_rows(c.contiguous().float(), c_up, c_is_upsampled)
+    gid32 = gid.to(torch.int32).contiguous() if gid is not None else None
+    zb = eng._ar_speaker_rows(B, gid32, gvec)
+    # one utterance per XCD, its gate rows split over up to 32 CUs (csrc/ar_coop.hip); bigger batches run one
+    # utterance per CU (csrc/ar_fwd.hip): better aggregate throughput, 3-4x lower speed per utterance
+    # scalar-input decoders take that path on request only (ar_path(scalar_coop=True)), in the modes their kernel has
+    coop = (B <= 8 and coop_sized(g) and m <= 2 and eng.opt.ar_coop and (not g.scalar_input or (eng.ar_scalar_coop and m in (0, 2))))
+    C = team_width(eng) if coop else 1
+    # zeros: the rows read as history before their first write (t - d, t - 2d of the first samples) are the causal pad; the
+    # cooperative kernel zero-fills its ring itself, but only when its members share an XCD.  Every launch of the decode continues in it.
+    ring = torch.zeros(B * C * eng.ar_ring_total, dtype=torch.float32, device=dev)
+    normal, M = mixture(g)
+    uni = um = draw = None
+    if g.scalar_input:
+        _wrong_draws(normal, u_log, z)
+        if m == 2 and (z if normal else u_mix) is None:     # scalar_draws' expressions in its order, for B utterances at once
+            u_mix = torch.rand(B, T, M, device=dev) * (1 - 2e-5) + 1e-5 if (M > 1 or not normal) else None
+            if normal:
+                z = torch.randn(B, T, device=dev)
+            else:
+                u_log = torch.rand(B, T, device=dev) * (1 - 2e-5) + 1e-5
+        forced = test_inputs.to(dev, torch.float32).contiguous() if test_inputs is not None else None
+        um = u_mix.to(dev, torch.float32).contiguous() if u_mix is not None else None
+        draw = z if normal else u_log
+        draw = draw.to(dev, torch.float32).contiguous() if draw is not None else None
+        sampled = (draw if normal else um) is not None
+        init_idx = 0
+    else:
+        forced = test_inputs.to(dev, torch.int32).contiguous() if test_inputs is not None else None
+        if forced is None and not 0 <= int(init_idx) < g.O:
+            # wavenet.py:288 writes a one at class 127 of the start vector: the same IndexError when there are fewer classes
+            raise IndexError(f"index {int(init_idx)} is out of bounds for dimension 2 with size {g.O}")
+        if m == 2 and uniforms is None:
+            uniforms = torch.rand(B, T, device=dev)
+        uni = uniforms.to(dev).float().contiguous() if uniforms is not None else None
+        sampled = True
+    d = ar_desc(eng, B=B, T=T, mode=m, init_idx=init_idx, n_forced=nf, coop=coop)
+    # (not zeroed here: ar_launch zeroes them before every launch)
+    exchange = eng._ar_exchange(d, C, B, torch.empty) if coop else None
+    return _ArDecode(d=d, n_forced=nf, forced=forced, c_up=c_up, zb=zb, gid32=gid32, coop=coop, C=C, ring=ring, normal=normal,
+                     uni=uni, u_mix=um, draw=draw, sampled=sampled, want=want_logits or m == 0 or m >= 3,
+                     log_scale_min=float(log_scale_min), clamp=int(bool(clamp_log_scale)),
+                     w_fused=eng.ar_wm if eng.ar_one_handover else None, exchange=exchange)
+
+
+def ar_launch(eng, s, t0, n):
+    """Steps [t0, t0 + n) of the decode `s` (ar_open) as one launch -> the dict incremental_forward returns, for those steps."""
+    g, dev, d = eng.g, eng.device, s.d
+    dt, key = _io(g)
+    sl = lambda a: None if a is None else a[:, t0:t0 + n].contiguous()  # noqa: E731  (B == 1 or the whole clip: the slice itself, no copy)
+    k = max(0, min(n, s.n_forced - t0))         # steps of this launch that the caller's inputs force
+    if k > 0 or t0 > 0:
+        if k == n:
+            inp = sl(s.forced)
+        else:                                   # the kernels index inputs as (B, n)
+            inp = torch.zeros(d.B, n, dtype=dt, device=dev)
+            if k > 0:
+                inp[:, :k] = s.forced[:, t0:t0 + k]
+            else:
+                inp[:, 0] = s.last              # past the forced prefix a continuation starts from the previous launch's last output
+        d.n_forced = max(1, k)
+    else:
+        inp, d.n_forced = None, 0
+    d.T, d.t0 = n, t0
+    cu, uc, um, dr = sl(s.c_up), sl(s.uni), sl(s.u_mix), sl(s.draw)
+    logits = torch.empty(d.B, g.O, n, dtype=torch.float32, device=dev) if s.want else None
+    out = torch.empty(d.B, n, dtype=dt, device=dev) if s.sampled else None
+    if s.coop:
+        for t in s.exchange:
+            t.zero_()
+    scalar = ("normal" if s.normal and not s.coop else True) if g.scalar_input else False
+    launch(eng, ("batch", scalar, s.coop), d, eng._ar_net_args(s.ring, s.zb, cu),
+           _operands(g, inp, uc, um, dr, s.log_scale_min, s.clamp, out, logits), C=s.C, dist=int(s.normal), exchange=s.exchange,
+           w_fused=s.w_fused)
+    s.last = out[:, -1] if out is not None else None
+    eng._ar_keep = (s, cu, inp, uc, um, dr)     # the launch's operands (and the decode's: ring, zb, ...) live until the stream has run
+    return {key: out, "logits": logits}
+
+
+def ar_chunks(eng, s, chunks):
+    """The launches of an open incremental_stream: chunk k runs steps [t0, t0 + n) with wae_ar_desc.t0 = t0."""
+    t0, mine = 0, None
+    try:
+        for n in chunks:
+            item = ar_launch(eng, s, t0, n)
+            mine = eng._ar_keep
+            t0 += n
+            yield item
+    finally:
+        if eng._ar_keep is mine:
+            eng._ar_keep = None    # closed (early or at the end): the ring and the operands go with the generator
+
+
+# ---- list: decode_list / decode_list_scalar
+def decode_list(eng, who, items, m, *, slots, want_logits, c_is_upsampled, coop, teams, log_scale_min=-7.0, clamp_log_scale=False):
+    """WaeEngine.decode_list and decode_list_scalar behind their own refusals: `items` (not empty) in mode m, ONE launch.  Every item
+    is checked before anything is drawn or allocated; what differs between class-id and scalar-input decoders is data -- the dtype
+    of inputs and outputs, which draws there are, the operands and the result's key."""
+    g, dev, n = eng.g, eng.device, len(items)
+    (dt, key), (normal, M), scalar = _io(g), mixture(g), bool(g.scalar_input)
+    Ts = [int(it["T"]) for it in items]
+    plan = P.ar_list_plan(Ts, group_count(eng, coop, slots, teams))      # longest first; clamps slots / teams to the item count
+    off, total = [int(o) for o in plan.offsets], plan.total
+    gids = [it.get("gid") for it in items]
+    if any(x is None for x in gids) and not all(x is None for x in gids):
+        raise ValueError(f"{who}: give every item a gid, or none")
+    took = [clip_intake(g, dev, m, it, who, i, check_ids=False) for i, it in enumerate(items)]
+    forced, nfs, inits, given = ([t[k] for t in took] for k in (1, 2, 3, 4))
+    if scalar and m == 0 and any(given) and not all(given):
+        raise ValueError(f"{who}: mode 'logits': give every item its draws (then the samples come back too), or none")
+    draws = m == 2 or (scalar and all(given))
+    if not eng._ar_packed or eng.weights_dirty:
+        eng.pack_ar_weights()
+    inputs = None
+    if any(nfs):        # the forced prefixes at their items' offsets, zeros behind them
+        inputs = torch.zeros(total, dtype=dt, device=dev)
+        for o, f, k in zip(off, forced, nfs):
+            if k:
+                inputs[o:o + k] = f
+        if not scalar and (int(inputs.min()) < 0 or int(inputs.max()) >= g.O):
+            raise IndexError(f"{who}: test_inputs hold a class id outside [0, {g.O})")
+    c_up = None
+    if g.Ccp:           # every item's conditioning rows at its offset
+        c_up = torch.zeros(total, g.Ccp, dtype=eng.tdtype, device=dev)
+        for i, it in enumerate(items):
+            _clip_cond(eng, it, Ts[i], c_is_upsampled, c_up[off[i]:off[i] + Ts[i]], f"item {i}: ")
+    gid32 = _gid32(eng, gids) if gids[0] is not None else None
+    zb = eng._ar_speaker_rows(n, gid32)         # one row per item, in the caller's order (item.row = the caller's index)
+    uni = um_d = dr_d = None
+    if draws:
+        uni = torch.empty(total, dtype=torch.float32, device=dev) if not scalar else None
+        um_d = torch.empty(total, M, dtype=torch.float32, device=dev) if scalar and (not normal or M > 1) else None
+        dr_d = torch.empty(total, dtype=torch.float32, device=dev) if scalar else None
+        for i, it in enumerate(items):      # item after item in the caller's order: a seeded list is a seeded loop
+            for dst, src in zip((uni, um_d, dr_d), clip_draws(eng, it, Ts[i], given[i], f"item {i}: ")):
+                if dst is not None:
+                    dst[off[i]:off[i] + Ts[i]] = src
+    rec = np.zeros(n, dtype=_AR_ITEM)           # in launch order
+    assert rec.dtype.itemsize == ctypes.sizeof(L.ArItem)
+    for k, i in enumerate(plan.order):
+        rec[k] = (off[i], Ts[i], nfs[i], inits[i], int(i))
+    items_d, nxt = torch.from_numpy(rec.view(np.uint8)).to(dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    out = torch.empty(total, dtype=dt, device=dev) if draws or not scalar else None
+    want = want_logits or m == 0
+    logits = torch.empty(total * g.O, dtype=torch.float32, device=dev) if want else None
+    d = ar_desc(eng, B=n, T=0, mode=m, init_idx=0, n_forced=0, coop=coop)
+    # One ring per slot, or per member of every team.  Not zeroed: a decode reads a history row only behind its own write of it
+    # (csrc/ar_fwd.hip: ar_decode; the any-shape cooperative kernel likewise, the constant-size ones clear it per item), in the first
+    # item of a slot as in every later one.  The exchange buffers are allocated zeroed, for this one launch.
+    C = team_width(eng) if coop else 1
+    ring = torch.empty(plan.slots * C * eng.ar_ring_total, dtype=torch.float32, device=dev)
+    exchange = eng._ar_exchange(d, C, plan.slots, torch.zeros) if coop else None
+
+    def hold():     # the launch's operands live until the next decode
+        eng._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, uni, um_d, dr_d, exchange)
+    launch(eng, ("list", scalar, bool(coop)), d, eng._ar_net_args(ring, zb, c_up),
+           _operands(g, inputs, uni, um_d, dr_d, float(log_scale_min), int(bool(clamp_log_scale)), out, logits), hold=hold,
+           C=C, dist=int(normal), queue=(n, plan.slots, L.ptr(items_d), L.ptr(nxt)), total=total, exchange=exchange)
+    return [{key: None if out is None else out[o:o + T], "logits": logits[o * g.O:(o + T) * g.O].view(g.O, T) if want else None}
+            for o, T in zip(off, Ts)]
+
+
+# ---- spans: decode sessions
+@dataclasses.dataclass
+class _ArClip:
+    """One clip of a DecodeSession between add() and its last step: what ar_open fixes once per decode, kept per clip."""
+    T: int
+    slot: int                       # the clip's ring and zb row in the session's tables
+    c_up: Optional[torch.Tensor]    # (T, Ccp) conditioning rows of the whole clip
+    forced: Optional[torch.Tensor]  # the forced prefix (class ids, or floats of a scalar-input decoder)
+    n_forced: int
+    init: int
+    uni: Optional[torch.Tensor]     # (T,) uniforms of the categorical draw
+    u_mix: Optional[torch.Tensor]   # (T, M) / (T,) draws of a scalar-input decoder
+    draw: Optional[torch.Tensor]
+    pos: int = 0                    # steps decoded so far = t0 of the next span
+    last: Optional[torch.Tensor] = None     # (1,) the previous span's last output, on the device
+
+
+class DecodeSession:
+    """WaeEngine.decode_session: clips of any lengths that join at any time and decode in rounds, one launch per round (include/wae.h:
+    the four wae_ar_generate*_spans entries).  add() does once per clip what a decode does once
+    (the conditioning rows of the whole clip, the speaker row, the clip's own history ring, the draws of all its steps); step() decodes
+    the next span of every live clip in one launch and returns the spans' outputs; a clip's outputs, concatenated over the rounds, are
+    bit for bit its single decode (incremental_forward alone: on the one-CU kernel for coop=False, on the cooperative path for
+    coop=True), whatever the chunking and whichever slot or team took which span."""
+
+    def __init__(self, eng, mode="sample", coop=False, slots=None, teams=None, want_logits=False, c_is_upsampled=False,
+                 log_scale_min=-7.0, clamp_log_scale=False):
+        g = eng.g
+        if g.scalar_input and coop and not eng.ar_scalar_coop:
+            raise NotImplementedError("decode_session(coop=True): scalar-input decoders decode their sessions on the one-CU slots "
+                                      "(coop=False); the team form of the scalar span list does not exist yet")
+        if coop:
+            refuse_wide(g, "decode_session", "slots")
+        modes = {"logits": 0, "sample": 2} if g.scalar_input else {"logits": 0, "argmax": 1, "sample": 2}
+        if mode not in modes:
+            raise ValueError(f"decode_session: mode '{mode}' is not decoded in spans; use " + ", ".join(f"'{k}'" for k in modes))
+        self.eng, self.mode, self.coop, self.want = eng, modes[mode], bool(coop), bool(want_logits) or modes[mode] == 0
+        self.c_is_upsampled, self.log_scale_min, self.clamp = bool(c_is_upsampled), float(log_scale_min), int(bool(clamp_log_scale))
+        self._slots, self._teams = slots, teams
+        self.clips: Dict[int, _ArClip] = {}
+        self._next_handle, self._gids, self._closed, self._open = 0, None, False, False
+        self._keep = None
+
+    # ---- the session's device state: once, at the first add
+    def _open_device(self):
+        eng, g = self.eng, self.eng.g
+        if not eng._ar_packed or eng.weights_dirty:
+            eng.pack_ar_weights()
+        if self._open:
+            return
+        dev = eng.device
+        self.nslots = max(1, group_count(eng, self.coop, self._slots, self._teams))
+        self.d = ar_desc(eng, B=0, T=0, mode=self.mode, init_idx=0, n_forced=0, coop=self.coop)
+        self.C, per, self.exchange = 1, eng.ar_ring_total, None
+        if self.coop:
+            self.C = team_width(eng)
+            per = int(eng.lib.wae_ar_coop_ring_floats(ctypes.byref(self.d), self.C, eng.ar_ring_total))
+            assert per > 0, per
+            self.exchange = eng._ar_exchange(self.d, self.C, self.nslots, torch.empty)      # zeroed before every launch
+        self.ring_floats = (per + 3) // 4 * 4       # span.ring is a multiple of 4 floats
+        self.cap, self.free = 0, []
+        self.ring = torch.empty(0, dtype=torch.float32, device=dev)
+        self.zb = torch.empty(0, g.layers, 2 * g.Hp, dtype=torch.float32, device=dev)
+        self.normal, self.M = mixture(g)
+        self._open = True
+
+    def reserve(self, n):
+        """Room for n clips at once in the ring and speaker-row tables (they grow on demand; growing copies the live clips' rings)."""
+        self._open_device()
+        n = int(n)
+        if n <= self.cap:
+            return
+        # never zeroed: a span reads a history row only behind its own write of it, or -- the constant-size cooperative kernels -- behind
+        # the clearing its clip's first span makes
+        ring = torch.empty(n * self.ring_floats, dtype=torch.float32, device=self.eng.device)
+        zb = torch.empty(n, *self.zb.shape[1:], dtype=torch.float32, device=self.eng.device)
+        ring[:self.ring.numel()] = self.ring
+        zb[:self.cap] = self.zb
+        self.free += list(range(n - 1, self.cap - 1, -1))
+        self.ring, self.zb, self.cap = ring, zb, n
+
+    @property
+    def live(self):
+        """handles of the clips that still have steps to decode, in the order they were added"""
+        return list(self.clips)
+
+    def add(self, item):
+        """A clip joins: `item` is decode_list's / decode_list_scalar's mapping (T, c, gid, test_inputs, uniforms or u_mix / u_log / z,
+        init_idx).  Legal at any time between two step() calls.  Returns the clip's handle."""
+        if self._closed:
+            raise RuntimeError("decode_session: the session is closed")
+        eng, g, dev, who = self.eng, self.eng.g, self.eng.device, "decode_session.add"
+        gid = item.get("gid")
+        if self._gids is not None and (gid is not None) != self._gids:
+            raise ValueError(f"{who}: give every item a gid, or none")
+        T, forced, nf, init, given = clip_intake(g, dev, self.mode, item, who)      # (class ids checked per clip: one device read each)
+        self._open_device()
+        c_up = None
+        if g.Ccp:
+            c_up = torch.zeros(T, g.Ccp, dtype=eng.tdtype, device=dev)
+            _clip_cond(eng, item, T, self.c_is_upsampled, c_up, f"{who}: ")
+        gid32 = _gid32(eng, [gid]) if gid is not None else None
+        zb = eng._ar_speaker_rows(1, gid32)
+        uni, um, dr = clip_draws(eng, item, T, given, f"{who}: ") if self.mode == 2 else (None, None, None)
+        if not self.free:
+            self.reserve(max(2 * self.cap, self.nslots, 8))
+        slot = self.free.pop()
+        self.zb[slot] = zb[0]
+        self._gids = gid is not None
+        h = self._next_handle
+        self._next_handle += 1
+        self.clips[h] = _ArClip(T=T, slot=slot, c_up=c_up, forced=forced, n_forced=nf, init=init, uni=uni, u_mix=um, draw=dr)
+        eng.hold("session_add", gid32, zb)
+        return h
+
+    def drop(self, handle):
+        """Cancels a clip: it leaves the session and its ring is free for the next add."""
+        c = self.clips.pop(handle)
+        self.free.append(c.slot)
+
+    def step(self, chunk):
+        """One launch: the next min(chunk, remaining) steps of every live clip (`chunk`: an int, or a mapping from handle to steps -- a
+        clip the mapping leaves out sits the round out).  Returns {handle: dict(idx | x, logits, done)} for the clips that decoded: the
+        span's class ids (n,) int32 or samples (n,) fp32, its logits / mixture parameters (O, n) where asked for, and whether the clip
+        has finished -- it has then left the session.  The forced first input of a continuation comes from the previous round's output
+        on the device; only the team path reads one word back per launch (the time-out flag)."""
+        if self._closed:
+            raise RuntimeError("decode_session: the session is closed")
+        handles = list(self.clips)
+        if not handles:
+            return {}
+        if not isinstance(chunk, (int, np.integer)):
+            chunk = {handles.index(h): int(n) for h, n in dict(chunk).items()}
+        clips = [self.clips[h] for h in handles]
+        plan = P.ar_round_plan([c.T - c.pos for c in clips], [c.pos for c in clips], chunk, self.nslots)
+        if plan.total == 0:
+            return {}
+        eng, g, dev = self.eng, self.eng.g, self.eng.device
+        dt, key = _io(g)
+        sel = [clips[int(i)] for i in plan.clips]
+        ns, offs, total = [int(x) for x in plan.lengths], [int(x) for x in plan.offsets], plan.total
+        cut = lambda name, on=True: torch.cat([getattr(c, name)[c.pos:c.pos + n] for c, n in zip(sel, ns)]) if on else None  # noqa: E731
+        c_up = cut("c_up", g.Ccp)
+        # the forced steps: a clip's forced prefix where the span lies in it, else -- a continuation -- the previous span's last output
+        nfs, inputs = [0] * len(sel), None
+        if any(c.pos > 0 or c.n_forced > 0 for c in sel):
+            inputs = torch.zeros(total, dtype=dt, device=dev)
+            dst, src = [], []
+            for j, (c, n, off) in enumerate(zip(sel, ns, offs)):
+                k = max(0, min(n, c.n_forced - c.pos))
+                if k > 0:
+                    inputs[off:off + k] = c.forced[c.pos:c.pos + k]
+                elif c.pos > 0:
+                    dst.append(off)
+                    src.append(c.last)
+                    k = 1
+                nfs[j] = k
+            if dst:
+                inputs.index_copy_(0, torch.tensor(dst, dtype=torch.int64, device=dev), torch.cat(src))
+        rec = np.zeros(len(sel), dtype=_AR_SPAN)
+        assert rec.dtype.itemsize == ctypes.sizeof(L.ArSpan)
+        for k, j in enumerate(plan.order):
+            c = sel[int(j)]
+            rec[k] = (offs[j], c.slot * self.ring_floats, ns[j], c.pos, nfs[j], c.init, c.slot, 0)
+        spans = torch.from_numpy(rec.view(np.uint8)).to(dev)
+        nxt = torch.zeros(1, dtype=torch.int32, device=dev)
+        logits = torch.empty(total * g.O, dtype=torch.float32, device=dev) if self.want else None
+        sampled, scalar = self.mode == 2, bool(g.scalar_input)
+        uni = cut("uni", sampled and not scalar)
+        um, dr = cut("u_mix", sampled and scalar and (not self.normal or self.M > 1)), cut("draw", sampled and scalar)
+        out = torch.empty(total, dtype=dt, device=dev) if sampled or not scalar else None
+        for t in self.exchange or ():
+            t.zero_()
+
+        def hold():     # the launch's operands live until the next round's
+            self._keep = (spans, nxt, c_up, inputs, out, logits, uni, um, dr)
+        launch(eng, ("spans", scalar, self.coop), self.d, eng._ar_net_args(self.ring, self.zb, c_up),
+               _operands(g, inputs, uni, um, dr, self.log_scale_min, self.clamp, out, logits), hold=hold, C=self.C, dist=int(self.normal),
+               queue=(len(sel), plan.slots, L.ptr(spans), L.ptr(nxt)), total=total, exchange=self.exchange)
+        res = {}
+        for i, c, n, off in zip(plan.clips, sel, ns, offs):
+            h = handles[int(i)]
+            c.pos += n
+            if out is not None:
+                c.last = out[off + n - 1:off + n]
+            done = c.pos >= c.T
+            res[h] = {key: None if out is None else out[off:off + n],
+                      "logits": logits[off * g.O:(off + n) * g.O].view(g.O, n) if self.want else None, "done": done}
+            if done:
+                self.drop(h)
+        return res
+
+    def close(self):
+        """Frees everything: the clips, their rings and the exchange buffers.  Results already returned stay valid."""
+        self.clips.clear()
+        self._closed = True
+        self.ring = self.zb = self.exchange = self._keep = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+def list_rounds(sess, items, chunk):
+    """The rounds of decode_list_stream: the session `sess` holding the fixed list `items`."""
+    with sess:
+        sess.reserve(len(items))
+        hs = [sess.add(it) for it in items]
+        while sess.live:
+            n = chunk if isinstance(chunk, (int, np.integer)) else {hs[int(i)]: v for i, v in dict(chunk).items() if hs[int(i)] in sess.clips}
+            res = sess.step(n)
+            if not res:
+                raise ValueError("decode_list_stream: the chunk mapping leaves every live clip out")
+            yield [res.get(h) for h in hs]

@@ -10,7 +10,6 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
-import dataclasses
 import math
 
 from typing import Dict, Optional
@@ -19,7 +18,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import decode as D
 from . import packing as P
+from .decode import DecodeSession  # noqa: F401  (re-exported)
 from .options import two_chains
 from .step_state import InFlight, Saved
 
@@ -32,345 +33,6 @@ def _dt(dtype) -> int:
     if dtype in ("fp16", "f16", "half", torch.float16, L.WAE_F16) and not isinstance(dtype, bool):
         return L.WAE_F16
     raise ValueError(f"unsupported compute dtype {dtype!r} (use 'fp32', 'bf16' or 'fp16')")
-
-
-@dataclasses.dataclass
-class _ArDecode:
-    """One autoregressive decode between WaeEngine._ar_open and its launches (_ar_launch): what does not depend on the chunk."""
-    # geometry, mode, start class, ar_path() settings.  ONE descriptor for all launches: _ar_launch overwrites d.T, d.n_forced and d.t0
-    # with the chunk's before every call (the library reads it during the call, never later), so outside a launch those three are stale
-    d: L.ArDesc
-    n_forced: int               # steps of the clip that `forced` covers
-    forced: Optional[torch.Tensor]
-    c_up: Optional[torch.Tensor]
-    zb: torch.Tensor
-    gid32: Optional[torch.Tensor]   # (held only so that wae_gproj_fwd's operand outlives its launch)
-    coop: bool
-    C: int
-    ring: torch.Tensor          # the decode's state: every launch continues in it
-    normal: bool
-    uni: Optional[torch.Tensor]
-    u_mix: Optional[torch.Tensor]
-    draw: Optional[torch.Tensor]    # u_log, or z of a "Normal" decoder
-    sampled: bool
-    want: bool
-    log_scale_min: float
-    clamp: int
-    w_fused: Optional[torch.Tensor]
-    msg: Optional[torch.Tensor]
-    acc: Optional[torch.Tensor]
-    err: Optional[torch.Tensor]
-    last: Optional[torch.Tensor] = None     # (B,) the previous launch's last output
-
-
-# include/wae.h: wae_ar_span, as the host packs it
-_AR_SPAN = np.dtype([("off", "<i8"), ("ring", "<i8"), ("T", "<i4"), ("t0", "<i4"), ("n_forced", "<i4"), ("init_idx", "<i4"),
-                     ("row", "<i4"), ("reserved", "<i4")])
-
-
-@dataclasses.dataclass
-class _ArClip:
-    """One clip of a DecodeSession between add() and its last step: what _ar_open fixes once per decode, kept per clip."""
-    T: int
-    slot: int                       # the clip's ring and zb row in the session's tables
-    c_up: Optional[torch.Tensor]    # (T, Ccp) conditioning rows of the whole clip
-    forced: Optional[torch.Tensor]  # the forced prefix (class ids, or floats of a scalar-input decoder)
-    n_forced: int
-    init: int
-    uni: Optional[torch.Tensor]     # (T,) uniforms of the categorical draw
-    u_mix: Optional[torch.Tensor]   # (T, M) / (T,) draws of a scalar-input decoder
-    draw: Optional[torch.Tensor]
-    pos: int = 0                    # steps decoded so far = t0 of the next span
-    last: Optional[torch.Tensor] = None     # (1,) the previous span's last output, on the device
-
-
-class DecodeSession:
-    """WaeEngine.decode_session: clips of any lengths that join at any time and decode in rounds, one launch per round (include/wae.h:
-    wae_ar_generate_spans, wae_ar_generate_scalar_spans, wae_ar_generate_coop_spans, wae_ar_generate_coop_scalar_spans).  add() does once per clip what a decode does once
-    (the conditioning rows of the whole clip, the speaker row, the clip's own history ring, the draws of all its steps); step() decodes
-    the next span of every live clip in one launch and returns the spans' outputs; a clip's outputs, concatenated over the rounds, are
-    bit for bit its single decode (incremental_forward alone: on the one-CU kernel for coop=False, on the cooperative path for
-    coop=True), whatever the chunking and whichever slot or team took which span."""
-
-    def __init__(self, eng, mode="sample", coop=False, slots=None, teams=None, want_logits=False, c_is_upsampled=False,
-                 log_scale_min=-7.0, clamp_log_scale=False):
-        g = eng.g
-        if g.scalar_input and coop and not eng.ar_scalar_coop:
-            raise NotImplementedError("decode_session(coop=True): scalar-input decoders decode their sessions on the one-CU slots "
-                                      "(coop=False); the team form of the scalar span list does not exist yet")
-        if coop and max(g.R, g.S, g.O) > 256:
-            raise ValueError(f"decode_session(coop=True): the cooperative kernels take R, S and O <= 256 (got {g.R}, {g.S}, {g.O}); "
-                             "use the one-CU slots (coop=False)")
-        modes = {"logits": 0, "sample": 2} if g.scalar_input else {"logits": 0, "argmax": 1, "sample": 2}
-        if mode not in modes:
-            raise ValueError(f"decode_session: mode '{mode}' is not decoded in spans; use " + ", ".join(f"'{k}'" for k in modes))
-        self.eng, self.mode, self.coop, self.want = eng, modes[mode], bool(coop), bool(want_logits) or modes[mode] == 0
-        self.c_is_upsampled, self.log_scale_min, self.clamp = bool(c_is_upsampled), float(log_scale_min), int(bool(clamp_log_scale))
-        self._slots, self._teams = slots, teams
-        self.clips: Dict[int, _ArClip] = {}
-        self._next_handle, self._gids, self._closed, self._open = 0, None, False, False
-        self._keep = None
-
-    # ---- the session's device state: once, at the first add
-    def _open_device(self):
-        eng, g = self.eng, self.eng.g
-        if not eng._ar_packed or eng.weights_dirty:
-            eng.pack_ar_weights()
-        if self._open:
-            return
-        dev = eng.device
-        if self.coop:
-            self.nslots = max(1, min(8 if self._teams is None else int(self._teams), 8))
-        else:
-            self.nslots = (torch.cuda.get_device_properties(dev).multi_processor_count if self._slots is None
-                           else max(1, int(self._slots)))
-        path = (int(eng.ar_generic), eng.ar_resident[0], eng.ar_resident[1]) if self.coop else ()
-        if g.scalar_input:
-            path = eng._ar_scalar_path() if self.coop else ()
-        self.d = L.ArDesc(eng.dt, 0, 0, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, self.mode, 0,
-                          int(g.scalar_input), math.sqrt(1.0 / g.layers), 0, *path)
-        if g.scalar_input and self.coop:
-            self.d.scalar_sized = int(eng.ar_scalar_fast)
-        self.C, per = 1, eng.ar_ring_total
-        self.msg = self.acc = self.err = None
-        if self.coop:
-            self.C = max(1, min(eng.opt.ar_coop_c, 32, g.H, g.S))       # as _ar_open
-            per = int(eng.lib.wae_ar_coop_ring_floats(ctypes.byref(self.d), self.C, eng.ar_ring_total))
-            assert per > 0, per
-            self.msg, self.acc, self.err = eng._ar_exchange(self.d, self.C, self.nslots, torch.empty)      # zeroed before every launch
-        self.ring_floats = (per + 3) // 4 * 4       # span.ring is a multiple of 4 floats
-        self.cap, self.free = 0, []
-        self.ring = torch.empty(0, dtype=torch.float32, device=dev)
-        self.zb = torch.empty(0, g.layers, 2 * g.Hp, dtype=torch.float32, device=dev)
-        self.normal = g.scalar_input and g.output_distribution == "Normal"
-        self.M = (1 if (self.normal and g.O == 2) else g.O // 3) if g.scalar_input else 0
-        self._open = True
-
-    def reserve(self, n):
-        """Room for n clips at once in the ring and speaker-row tables (they grow on demand; growing copies the live clips' rings)."""
-        self._open_device()
-        n = int(n)
-        if n <= self.cap:
-            return
-        # never zeroed: a span reads a history row only behind its own write of it, or -- the constant-size cooperative kernels -- behind
-        # the clearing its clip's first span makes
-        ring = torch.empty(n * self.ring_floats, dtype=torch.float32, device=self.eng.device)
-        zb = torch.empty(n, *self.zb.shape[1:], dtype=torch.float32, device=self.eng.device)
-        ring[:self.ring.numel()] = self.ring
-        zb[:self.cap] = self.zb
-        self.free += list(range(n - 1, self.cap - 1, -1))
-        self.ring, self.zb, self.cap = ring, zb, n
-
-    @property
-    def live(self):
-        """handles of the clips that still have steps to decode, in the order they were added"""
-        return list(self.clips)
-
-    def _check(self, item):
-        """decode_list's / decode_list_scalar's checks of one item, before anything is allocated -> (T, forced, n_forced, init, given)"""
-        eng, g, dev = self.eng, self.eng.g, self.eng.device
-        T = int(item["T"])
-        if T < 1:
-            raise ValueError(f"decode_session.add: every clip has at least one step (got {T})")
-        gid = item.get("gid")
-        if self._gids is not None and (gid is not None) != self._gids:
-            raise ValueError("decode_session.add: give every item a gid, or none")
-        if g.Ccp and item.get("c") is None:
-            raise ValueError(f"decode_session.add: the item has no conditioning c, the decoder has {g.Cc} conditioning channels")
-        ti = item.get("test_inputs")
-        if ti is not None:
-            ti = torch.as_tensor(ti).reshape(-1).to(dev, torch.float32 if g.scalar_input else torch.int32)[:T]
-        nf = 0 if ti is None else int(ti.numel())
-        if self.mode == 0 and nf < T:
-            raise ValueError(f"decode_session.add: mode 'logits' is teacher-forced: test_inputs must cover all {T} steps")
-        init, given = 0, False
-        if g.scalar_input:
-            normal = g.output_distribution == "Normal"
-            M = 1 if (normal and g.O == 2) else g.O // 3
-            um, ul, z = item.get("u_mix"), item.get("u_log"), item.get("z")
-            if normal and ul is not None:
-                raise ValueError("decode_session.add: output_distribution 'Normal' draws from u_mix and z, not u_log")
-            if not normal and z is not None:
-                raise ValueError("decode_session.add: output_distribution 'Logistic' draws from u_mix and u_log, not z")
-            if not normal and (um is None) != (ul is None):
-                raise ValueError("decode_session.add: u_mix and u_log come together")
-            if normal and z is not None and M > 1 and um is None:
-                raise ValueError(f"decode_session.add: {M} Gaussians need u_mix beside z")
-            given = (z if normal else ul) is not None
-        else:
-            init = item.get("init_idx")
-            init = 127 if init is None else int(torch.as_tensor(init).reshape(-1)[0])
-            if nf == 0 and not 0 <= init < g.O:
-                # wavenet.py:288 writes a one at the start class of the start vector: the same IndexError when there are fewer classes
-                raise IndexError(f"index {init} is out of bounds for dimension 2 with size {g.O}")
-            if nf and (int(ti.min()) < 0 or int(ti.max()) >= g.O):
-                raise IndexError(f"decode_session.add: test_inputs hold a class id outside [0, {g.O})")
-            init = init if nf == 0 else 0
-        return T, (ti if nf else None), nf, init, given
-
-    def add(self, item):
-        """A clip joins: `item` is decode_list's / decode_list_scalar's mapping (T, c, gid, test_inputs, uniforms or u_mix / u_log / z,
-        init_idx).  Legal at any time between two step() calls.  Returns the clip's handle."""
-        if self._closed:
-            raise RuntimeError("decode_session: the session is closed")
-        T, forced, nf, init, given = self._check(item)
-        eng, g, dev = self.eng, self.eng.g, self.eng.device
-        self._open_device()
-        gid = item.get("gid")
-        flat = lambda a: torch.as_tensor(a).reshape(-1).to(dev, torch.float32)  # noqa: E731
-        c_up = None
-        if g.Ccp:
-            c = torch.as_tensor(item["c"]).to(dev, torch.float32)
-            c = (c if c.dim() == 3 else c[None]).contiguous()
-            c_up = torch.zeros(T, g.Ccp, dtype=eng.tdtype, device=dev)
-            eng._ar_cond_rows(c, c_up.view(1, T, g.Ccp), self.c_is_upsampled, "decode_session.add: ")
-        gid32 = None
-        if gid is not None:
-            gid32 = torch.tensor([int(torch.as_tensor(gid).reshape(-1)[0])], dtype=torch.int32, device=dev)
-        zb = eng._ar_speaker_rows(1, gid32)
-        uni = um = dr = None
-        if g.scalar_input:
-            if self.mode == 2:
-                um, dr = item.get("u_mix"), item.get("z" if self.normal else "u_log")
-                if not given:
-                    um, dr = eng.scalar_draws(T)
-                if not self.normal or self.M > 1:
-                    um = flat(um)
-                    assert um.numel() == T * self.M, f"decode_session.add: u_mix holds {um.numel()} values for {T} steps of {self.M} mixtures"
-                    um = um.view(T, self.M).contiguous()
-                else:
-                    um = None
-                dr = flat(dr).contiguous()
-                assert dr.numel() == T, f"decode_session.add: {dr.numel()} draws for {T} steps"
-        elif self.mode == 2:
-            u = item.get("uniforms")
-            uni = (torch.rand(1, T, device=dev) if u is None else flat(u)).reshape(-1).contiguous()
-            assert uni.numel() == T, f"decode_session.add: {uni.numel()} uniforms for {T} steps"
-        if not self.free:
-            self.reserve(max(2 * self.cap, self.nslots, 8))
-        slot = self.free.pop()
-        self.zb[slot] = zb[0]
-        self._gids = gid is not None
-        h = self._next_handle
-        self._next_handle += 1
-        self.clips[h] = _ArClip(T=T, slot=slot, c_up=c_up, forced=forced, n_forced=nf, init=init, uni=uni, u_mix=um, draw=dr)
-        eng.hold("session_add", gid32, zb)
-        return h
-
-    def drop(self, handle):
-        """Cancels a clip: it leaves the session and its ring is free for the next add."""
-        c = self.clips.pop(handle)
-        self.free.append(c.slot)
-
-    def step(self, chunk):
-        """One launch: the next min(chunk, remaining) steps of every live clip (`chunk`: an int, or a mapping from handle to steps -- a
-        clip the mapping leaves out sits the round out).  Returns {handle: dict(idx | x, logits, done)} for the clips that decoded: the
-        span's class ids (n,) int32 or samples (n,) fp32, its logits / mixture parameters (O, n) where asked for, and whether the clip
-        has finished -- it has then left the session.  The forced first input of a continuation comes from the previous round's output
-        on the device; only the team path reads one word back per launch (the time-out flag)."""
-        if self._closed:
-            raise RuntimeError("decode_session: the session is closed")
-        handles = list(self.clips)
-        if not handles:
-            return {}
-        if not isinstance(chunk, (int, np.integer)):
-            chunk = {handles.index(h): int(n) for h, n in dict(chunk).items()}
-        clips = [self.clips[h] for h in handles]
-        plan = P.ar_round_plan([c.T - c.pos for c in clips], [c.pos for c in clips], chunk, self.nslots)
-        if plan.total == 0:
-            return {}
-        eng, g, dev, lib, d = self.eng, self.eng.g, self.eng.device, self.eng.lib, self.d
-        sel = [clips[int(i)] for i in plan.clips]
-        ns, offs, total = [int(x) for x in plan.lengths], [int(x) for x in plan.offsets], plan.total
-        cut = lambda name: torch.cat([getattr(c, name)[c.pos:c.pos + n] for c, n in zip(sel, ns)])  # noqa: E731
-        c_up = cut("c_up") if g.Ccp else None
-        # the forced steps: a clip's forced prefix where the span lies in it, else -- a continuation -- the previous span's last output
-        nfs, inputs = [], None
-        if any(c.pos > 0 or c.n_forced > 0 for c in sel):
-            inputs = torch.zeros(total, dtype=torch.float32 if g.scalar_input else torch.int32, device=dev)
-            dst, src = [], []
-            for c, n, off in zip(sel, ns, offs):
-                k = max(0, min(n, c.n_forced - c.pos))
-                if k > 0:
-                    inputs[off:off + k] = c.forced[c.pos:c.pos + k]
-                elif c.pos > 0:
-                    dst.append(off)
-                    src.append(c.last)
-                    k = 1
-                nfs.append(k)
-            if dst:
-                inputs.index_copy_(0, torch.tensor(dst, dtype=torch.int64, device=dev), torch.cat(src))
-        else:
-            nfs = [0] * len(sel)
-        rec = np.zeros(len(sel), dtype=_AR_SPAN)
-        assert rec.dtype.itemsize == ctypes.sizeof(L.ArSpan)
-        for k, j in enumerate(plan.order):
-            c = sel[int(j)]
-            rec[k] = (offs[j], c.slot * self.ring_floats, ns[j], c.pos, nfs[j], c.init, c.slot, 0)
-        spans = torch.from_numpy(rec.view(np.uint8)).to(dev)
-        nxt = torch.zeros(1, dtype=torch.int32, device=dev)
-        logits = torch.empty(total * g.O, dtype=torch.float32, device=dev) if self.want else None
-        st, net = eng.stream(), eng._ar_net_args(self.ring, self.zb, c_up)
-        if g.scalar_input:
-            sampled = self.mode == 2
-            um = cut("u_mix") if sampled and (not self.normal or self.M > 1) else None
-            dr = cut("draw") if sampled else None
-            out = torch.empty(total, dtype=torch.float32, device=dev) if sampled else None
-            operands = (L.ptr(inputs), L.ptr(um), L.ptr(dr), self.log_scale_min, self.clamp, L.ptr(out), L.ptr(logits))
-            if self.coop:
-                self.msg.zero_()
-                self.acc.zero_()
-                self.err.zero_()
-                L.check(lib.wae_ar_generate_coop_scalar_spans(ctypes.byref(d), self.C, int(self.normal), len(sel), plan.slots, L.ptr(spans),
-                                                              L.ptr(nxt), total, *net, *operands, L.ptr(self.msg), L.ptr(self.acc),
-                                                              L.ptr(self.err), st), "ar_generate_coop_scalar_spans")
-            else:
-                L.check(lib.wae_ar_generate_scalar_spans(ctypes.byref(d), int(self.normal), len(sel), plan.slots, L.ptr(spans), L.ptr(nxt),
-                                                         *net, *operands, st), "ar_generate_scalar_spans")
-            key, keep = "x", (um, dr)
-        else:
-            uni = cut("uni") if self.mode == 2 else None
-            out = torch.empty(total, dtype=torch.int32, device=dev)
-            operands = (L.ptr(inputs), L.ptr(uni), L.ptr(out), L.ptr(logits))
-            if self.coop:
-                self.msg.zero_()
-                self.acc.zero_()
-                self.err.zero_()
-                L.check(lib.wae_ar_generate_coop_spans(ctypes.byref(d), self.C, len(sel), plan.slots, L.ptr(spans), L.ptr(nxt), total, *net,
-                                                       *operands, L.ptr(self.msg), L.ptr(self.acc), L.ptr(self.err), st),
-                        "ar_generate_coop_spans")
-            else:
-                L.check(lib.wae_ar_generate_spans(ctypes.byref(d), len(sel), plan.slots, L.ptr(spans), L.ptr(nxt), *net, *operands, st),
-                        "ar_generate_spans")
-            key, keep = "idx", (uni,)
-        self._keep = (spans, nxt, c_up, inputs, out, logits) + keep     # the launch's operands live until the next round's
-        if self.coop:
-            eng._ar_check_exchange(self.err, "ar_generate_coop_scalar_spans" if g.scalar_input else "ar_generate_coop_spans")
-        res = {}
-        for i, c, n, off in zip(plan.clips, sel, ns, offs):
-            h = handles[int(i)]
-            c.pos += n
-            if out is not None:
-                c.last = out[off + n - 1:off + n]
-            done = c.pos >= c.T
-            res[h] = {key: None if out is None else out[off:off + n],
-                      "logits": logits[off * g.O:(off + n) * g.O].view(g.O, n) if self.want else None, "done": done}
-            if done:
-                self.drop(h)
-        return res
-
-    def close(self):
-        """Frees everything: the clips, their rings and the exchange buffers.  Results already returned stay valid."""
-        self.clips.clear()
-        self._closed = True
-        self.ring = self.zb = self.msg = self.acc = self.err = self._keep = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-        return False
 
 
 class WaeEngine:
@@ -1123,10 +785,10 @@ class WaeEngine:
         u_log (B,T) (torch.rand in (1e-5, 1-1e-5) if None) -> dict(x (B,T) fp32, logits | None).  With geometry
         output_distribution "Normal" the draw is sample_from_mix_gaussian's (mixture.py:225-270) on u_mix (B,T,M) (M > 1 only) and
         standard normals z (B,T) (torch.rand / torch.randn if z is None); log_scale_min is unused there, as in the reference."""
-        s = self._ar_open(c, gid, T, mode=mode, test_inputs=test_inputs, uniforms=uniforms, init_idx=init_idx,
-                          c_is_upsampled=c_is_upsampled, want_logits=want_logits, gvec=gvec, u_mix=u_mix, u_log=u_log,
-                          log_scale_min=log_scale_min, clamp_log_scale=clamp_log_scale, n_forced=n_forced, z=z)
-        return self._ar_launch(s, 0, int(T))      # the one-chunk case of incremental_stream; _ar_keep holds the operands until the next decode
+        s = D.ar_open(self, c, gid, T, mode=mode, test_inputs=test_inputs, uniforms=uniforms, init_idx=init_idx,
+                      c_is_upsampled=c_is_upsampled, want_logits=want_logits, gvec=gvec, u_mix=u_mix, u_log=u_log,
+                      log_scale_min=log_scale_min, clamp_log_scale=clamp_log_scale, n_forced=n_forced, z=z)
+        return D.ar_launch(self, s, 0, int(T))      # the one-chunk case of incremental_stream; _ar_keep holds the operands until the next decode
 
     def incremental_stream(self, c: Optional[torch.Tensor], gid: Optional[torch.Tensor], T: int, chunk, mode: str = "sample",
                            test_inputs: Optional[torch.Tensor] = None, uniforms: Optional[torch.Tensor] = None,
@@ -1165,171 +827,12 @@ class WaeEngine:
                 raise ValueError("incremental_stream: every chunk has at least one step")
             if sum(chunks) != T:
                 raise ValueError(f"incremental_stream: the chunk lengths sum to {sum(chunks)}, not to T = {T}")
-        s = self._ar_open(c, gid, T, mode=mode, test_inputs=test_inputs, uniforms=uniforms, init_idx=init_idx,
-                          c_is_upsampled=c_is_upsampled, want_logits=want_logits, gvec=gvec, u_mix=u_mix, u_log=u_log,
-                          log_scale_min=log_scale_min, clamp_log_scale=clamp_log_scale, n_forced=n_forced, z=z)
-        return self._ar_chunks(s, chunks)
+        s = D.ar_open(self, c, gid, T, mode=mode, test_inputs=test_inputs, uniforms=uniforms, init_idx=init_idx,
+                      c_is_upsampled=c_is_upsampled, want_logits=want_logits, gvec=gvec, u_mix=u_mix, u_log=u_log,
+                      log_scale_min=log_scale_min, clamp_log_scale=clamp_log_scale, n_forced=n_forced, z=z)
+        return D.ar_chunks(self, s, chunks)
 
-    def _ar_chunks(self, s, chunks):
-        """The launches of an open incremental_stream: chunk k runs steps [t0, t0 + n) with wae_ar_desc.t0 = t0."""
-        t0, mine = 0, None
-        try:
-            for n in chunks:
-                item = self._ar_launch(s, t0, n)
-                mine = self._ar_keep
-                t0 += n
-                yield item
-        finally:
-            if self._ar_keep is mine:
-                self._ar_keep = None    # closed (early or at the end): the ring and the operands go with the generator
-
-    def _ar_open(self, c, gid, T, *, mode, test_inputs, uniforms, init_idx, c_is_upsampled, want_logits, gvec, u_mix, u_log,
-                 log_scale_min, clamp_log_scale, n_forced, z):
-        """What a decode of T steps fixes before its first launch, whatever its chunks (incremental_forward's arguments) -> the state
-        _ar_launch runs steps of: the packed weights, the start classes, the forced prefix, the upsampled conditioning, the speaker
-        rows, the kernel path, the zeroed ring, the draws of all T steps and the exchange buffers."""
-        g, dev = self.g, self.device
-        if not self._ar_packed or self.weights_dirty:
-            self.pack_ar_weights()
-        T = int(T)
-        B = c.shape[0] if c is not None else (test_inputs.shape[0] if test_inputs is not None else 1)
-        m = {"logits": 0, "argmax": 1, "sample": 2, "probs": 3, "raw": 4}[mode]
-        if not isinstance(init_idx, int) and not g.scalar_input:
-            ii = torch.as_tensor(init_idx).reshape(-1).to("cpu", torch.int64)
-            if ii.numel() == 1:
-                init_idx = int(ii[0])
-            else:
-                if ii.numel() != B:
-                    raise ValueError(f"init_idx: {ii.numel()} start classes for {B} utterances")
-                if int(ii.min()) < 0 or int(ii.max()) >= g.O:
-                    raise IndexError(f"index {int(ii.max() if ii.max() >= g.O else ii.min())} is out of bounds for dimension 2 with size {g.O}")
-                if test_inputs is None:     # (forced steps override the start class anyway: wavenet.py:300-302)
-                    test_inputs, n_forced = ii.to(dev, torch.int32).reshape(B, 1), 1
-                init_idx = int(ii[0])
-        nf = 0
-        if test_inputs is not None:
-            nf = int(test_inputs.shape[1]) if n_forced is None else int(n_forced)
-            nf = max(0, min(nf, int(test_inputs.shape[1]), T))
-            if nf == 0:
-                test_inputs = None
-        if m == 0 and nf < T:
-            raise ValueError("mode 'logits' is teacher-forced: test_inputs must cover all T steps (use 'raw' to feed logits back)")
-        if g.scalar_input and m not in (0, 2):
-            raise ValueError("scalar-input decoders feed the drawn sample back: modes 'logits' and 'sample' only")
-        c_up = None
-        if g.Ccp:
-            c_up = torch.zeros(B, T, g.Ccp, dtype=self.tdtype, device=dev)
-            self._ar_cond_rows(c.contiguous().float(), c_up, c_is_upsampled)
-        gid32 = gid.to(torch.int32).contiguous() if gid is not None else None
-        zb = self._ar_speaker_rows(B, gid32, gvec)
-        # one utterance per XCD, its gate rows split over up to 32 CUs (csrc/ar_coop.hip); bigger batches run one
-        # utterance per CU (csrc/ar_fwd.hip): better aggregate throughput, 3-4x lower speed per utterance
-        # scalar-input decoders take that path on request only (ar_path(scalar_coop=True)), in the modes their kernel has
-        coop = (B <= 8 and g.R <= 256 and g.S <= 256 and g.O <= 256 and m <= 2 and self.opt.ar_coop
-                and (not g.scalar_input or (self.ar_scalar_coop and m in (0, 2))))
-        C = max(1, min(self.opt.ar_coop_c, 32, g.H, g.S)) if coop else 1
-        # zeros: the rows read as history before their first write (t - d, t - 2d of the first samples) are the causal pad; the
-        # cooperative kernel zero-fills its ring itself, but only when its members share an XCD (round-5 advisor finding).  Every
-        # launch of the decode continues in it.
-        ring = torch.zeros(B * C * self.ar_ring_total, dtype=torch.float32, device=dev)
-        normal = g.scalar_input and g.output_distribution == "Normal"
-        uni = um = draw = None
-        if g.scalar_input:
-            M = 1 if (normal and g.O == 2) else g.O // 3
-            if normal:
-                if u_log is not None:
-                    raise ValueError("output_distribution 'Normal' draws from u_mix and z, not u_log")
-                if m == 2 and z is None:
-                    # mixture.py:249 (the mixture pick, M > 1 only), then Normal(...).sample() (:266)
-                    u_mix = torch.rand(B, T, M, device=dev) * (1 - 2e-5) + 1e-5 if M > 1 else None
-                    z = torch.randn(B, T, device=dev)
-            elif z is not None:
-                raise ValueError("output_distribution 'Logistic' draws from u_mix and u_log, not z")
-            elif m == 2 and u_mix is None:
-                u_mix = torch.rand(B, T, M, device=dev) * (1 - 2e-5) + 1e-5          # mixture.py:138,151
-                u_log = torch.rand(B, T, device=dev) * (1 - 2e-5) + 1e-5
-            forced = test_inputs.to(dev, torch.float32).contiguous() if test_inputs is not None else None
-            um = u_mix.to(dev, torch.float32).contiguous() if u_mix is not None else None
-            draw = z if normal else u_log
-            draw = draw.to(dev, torch.float32).contiguous() if draw is not None else None
-            sampled = (draw if normal else um) is not None
-            init_idx, path = 0, self._ar_scalar_path()
-        else:
-            forced = test_inputs.to(dev, torch.int32).contiguous() if test_inputs is not None else None
-            if forced is None and not 0 <= int(init_idx) < g.O:
-                # wavenet.py:288 writes a one at class 127 of the start vector: the same IndexError when there are fewer classes
-                raise IndexError(f"index {int(init_idx)} is out of bounds for dimension 2 with size {g.O}")
-            if m == 2 and uniforms is None:
-                uniforms = torch.rand(B, T, device=dev)
-            uni = uniforms.to(dev).float().contiguous() if uniforms is not None else None
-            sampled = True
-            path = (int(self.ar_generic), self.ar_resident[0], self.ar_resident[1])
-        d = L.ArDesc(self.dt, B, T, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, int(init_idx),
-                     int(g.scalar_input), math.sqrt(1.0 / g.layers), nf, *path)
-        d.scalar_sized = int(g.scalar_input and coop and self.ar_scalar_fast)
-        # (not zeroed here: _ar_launch zeroes them before every launch)
-        msg, acc, err = self._ar_exchange(d, C, B, torch.empty) if coop else (None, None, None)
-        return _ArDecode(d=d, n_forced=nf, forced=forced, c_up=c_up, zb=zb, gid32=gid32, coop=coop, C=C, ring=ring, normal=normal,
-                         uni=uni, u_mix=um, draw=draw, sampled=sampled, want=want_logits or m == 0 or m >= 3,
-                         log_scale_min=float(log_scale_min), clamp=int(bool(clamp_log_scale)),
-                         w_fused=self.ar_wm if self.ar_one_handover else None, msg=msg, acc=acc, err=err)
-
-    def _ar_launch(self, s, t0, n):
-        """Steps [t0, t0 + n) of the decode `s` (_ar_open) as one launch -> the dict incremental_forward returns, for those steps."""
-        g, lib, dev, d, st = self.g, self.lib, self.device, s.d, self.stream()
-        sl = lambda a: None if a is None else a[:, t0:t0 + n].contiguous()  # noqa: E731  (B == 1 or the whole clip: the slice itself, no copy)
-        k = max(0, min(n, s.n_forced - t0))         # steps of this launch that the caller's inputs force
-        if k > 0 or t0 > 0:
-            if k == n:
-                inp = sl(s.forced)
-            else:                                   # the kernels index inputs as (B, n)
-                inp = torch.zeros(d.B, n, dtype=torch.float32 if g.scalar_input else torch.int32, device=dev)
-                if k > 0:
-                    inp[:, :k] = s.forced[:, t0:t0 + k]
-                else:
-                    inp[:, 0] = s.last              # past the forced prefix a continuation starts from the previous launch's last output
-            d.n_forced = max(1, k)
-        else:
-            inp, d.n_forced = None, 0
-        d.T, d.t0 = n, t0
-        cu = sl(s.c_up)
-        logits = torch.empty(d.B, g.O, n, dtype=torch.float32, device=dev) if s.want else None
-        if s.coop:
-            s.msg.zero_()
-            s.acc.zero_()
-            s.err.zero_()
-        common = self._ar_net_args(s.ring, s.zb, cu) + (L.ptr(inp),)
-        if g.scalar_input:
-            um, dr = sl(s.u_mix), sl(s.draw)
-            xs = torch.empty(d.B, n, dtype=torch.float32, device=dev) if s.sampled else None
-            if s.coop:
-                L.check(lib.wae_ar_generate_coop_scalar(ctypes.byref(d), s.C, int(s.normal), *common, L.ptr(um), L.ptr(dr),
-                                                        s.log_scale_min, s.clamp, L.ptr(xs), L.ptr(logits), L.ptr(s.msg), L.ptr(s.acc),
-                                                        L.ptr(s.err), st), "ar_generate_coop_scalar")
-            elif s.normal:
-                L.check(lib.wae_ar_generate_scalar_mog(ctypes.byref(d), *common, L.ptr(um), L.ptr(dr), s.log_scale_min, L.ptr(xs),
-                                                       L.ptr(logits), st), "ar_generate_scalar_mog")
-            else:
-                L.check(lib.wae_ar_generate_scalar(ctypes.byref(d), *common, L.ptr(um), L.ptr(dr), s.log_scale_min, s.clamp,
-                                                   L.ptr(xs), L.ptr(logits), st), "ar_generate_scalar")
-            item, keep = dict(x=xs, logits=logits), (um, dr)
-            s.last = xs[:, -1] if xs is not None else None
-        else:
-            uc = sl(s.uni)
-            out_idx = torch.empty(d.B, n, dtype=torch.int32, device=dev)
-            if s.coop:
-                L.check(lib.wae_ar_generate_coop_fused(ctypes.byref(d), s.C, *common, L.ptr(uc), L.ptr(out_idx), L.ptr(logits),
-                                                       L.ptr(s.msg), L.ptr(s.acc), L.ptr(s.err), L.ptr(s.w_fused), st), "ar_generate_coop")
-            else:
-                L.check(lib.wae_ar_generate(ctypes.byref(d), *common, L.ptr(uc), L.ptr(out_idx), L.ptr(logits), st), "ar_generate")
-            item, keep = dict(idx=out_idx, logits=logits), (uc,)
-            s.last = out_idx[:, -1]
-        if s.coop:
-            self._ar_check_exchange(s.err, "ar_generate_coop")
-        self._ar_keep = (s, cu, inp) + keep     # the launch's operands (and the decode's: ring, zb, ...) live until the stream has run
-        return item
-
-    # ---- what every decode sets up the same way (_ar_open / _ar_launch and decode_list)
+    # ---- the engine state every decode route reads (decode.py)
     def _ar_cond_rows(self, c, out, c_is_upsampled, who=""):
         """c (B, Cc, Tc) fp32, contiguous -> out (B, T, Ccp), zeroed, in the model's dtype: the per-sample features as they are
         (already upsampled, or a geometry without an upsampling network), else the latent frames through the upsampling network."""
@@ -1352,75 +855,6 @@ class WaeEngine:
                                        L.ptr(gvec) if gvec is not None else None, L.ptr(zb), n, g.layers, g.G, g.Hp, max(g.Cg, 0),
                                        int(g.n_speakers or 0), L.ptr(self.err), self.stream()), "gproj")
         return zb
-
-    # ---- what decode_list and decode_list_scalar set up the same way
-    def _ar_list_plan(self, who, items, coop, slots, teams):
-        """The launch plan of a work list -> (Ts, plan, offsets, gids): `slots` workgroups, or `teams` teams when coop (clamped to 1..8;
-        the plan clamps either to the item count), longest first (packing.ar_list_plan); every item has a gid or none has; every item
-        has its conditioning where the decoder takes any."""
-        g = self.g
-        Ts = [int(it["T"]) for it in items]
-        if coop:
-            slots = max(1, min(8 if teams is None else int(teams), 8))
-        elif slots is None:
-            slots = torch.cuda.get_device_properties(self.device).multi_processor_count
-        plan = P.ar_list_plan(Ts, slots)
-        gids = [it.get("gid") for it in items]
-        if any(x is None for x in gids) and not all(x is None for x in gids):
-            raise ValueError(f"{who}: give every item a gid, or none")
-        for i, it in enumerate(items):
-            if g.Ccp and it.get("c") is None:
-                raise ValueError(f"{who}: item {i} has no conditioning c, the decoder has {g.Cc} conditioning channels")
-        return Ts, plan, [int(o) for o in plan.offsets], gids
-
-    def _ar_list_forced(self, forced, nfs, off, total, dtype):
-        """The items' forced prefixes packed by their offsets (zeros behind them), or None where no item has one."""
-        if all(f is None for f in forced):
-            return None
-        inputs = torch.zeros(total, dtype=dtype, device=self.device)
-        for i, f in enumerate(forced):
-            if f is not None:
-                inputs[off[i]:off[i] + nfs[i]] = f
-        return inputs
-
-    def _ar_list_cond(self, items, Ts, off, total, c_is_upsampled):
-        """c_up (total, Ccp): every item's conditioning rows at its offset (one utterance of batch 1 each), or None without conditioning."""
-        g = self.g
-        if not g.Ccp:
-            return None
-        c_up = torch.zeros(total, g.Ccp, dtype=self.tdtype, device=self.device)
-        for i, it in enumerate(items):
-            c = torch.as_tensor(it["c"]).to(self.device, torch.float32)
-            c = (c if c.dim() == 3 else c[None]).contiguous()
-            self._ar_cond_rows(c, c_up[off[i]:off[i] + Ts[i]].view(1, Ts[i], g.Ccp), c_is_upsampled, f"item {i}: ")
-        return c_up
-
-    def _ar_list_speakers(self, gids):
-        """(gid32, zb): one speaker row per item, in the caller's order (item.row = the caller's index)."""
-        gid32 = None
-        if gids[0] is not None:
-            gid32 = torch.tensor([int(torch.as_tensor(x).reshape(-1)[0]) for x in gids], dtype=torch.int32, device=self.device)
-        return gid32, self._ar_speaker_rows(len(gids), gid32)
-
-    def _ar_list_records(self, plan, off, Ts, nfs, inits):
-        """(items, next) on the device: the wae_ar_item records in launch order (longest first; row = the caller's index) and the zeroed
-        queue counter."""
-        rec = np.zeros(len(Ts), dtype=np.dtype([("off", "<i8"), ("T", "<i4"), ("n_forced", "<i4"), ("init_idx", "<i4"), ("row", "<i4")]))
-        assert rec.dtype.itemsize == ctypes.sizeof(L.ArItem)
-        for k, i in enumerate(plan.order):
-            rec[k] = (off[i], Ts[i], nfs[i], inits[i], int(i))
-        return torch.from_numpy(rec.view(np.uint8)).to(self.device), torch.zeros(1, dtype=torch.int32, device=self.device)
-
-    def _ar_list_buffers(self, d, plan, coop):
-        """(C, ring, msg, acc, err) of a list launch: one ring per slot, or per member of every team with the zeroed exchange buffers.
-        The ring is not zeroed: a decode reads a history row only behind its own write of it (csrc/ar_fwd.hip: ar_decode; the any-shape
-        cooperative kernel likewise, the constant-size ones clear it per item), in the first item of a slot as in every later one."""
-        g = self.g
-        if not coop:
-            return 1, torch.empty(plan.slots * self.ar_ring_total, dtype=torch.float32, device=self.device), None, None, None
-        C = max(1, min(self.opt.ar_coop_c, 32, g.H, g.S))       # as _ar_open
-        ring = torch.empty(plan.slots * C * self.ar_ring_total, dtype=torch.float32, device=self.device)
-        return (C, ring) + self._ar_exchange(d, C, plan.slots, torch.zeros)
 
     def _ar_exchange(self, d, C, groups, alloc):
         """(msg, acc, err) of `groups` utterances or teams of C workgroups from `alloc` (torch.zeros / torch.empty: a launch needs them
@@ -1473,82 +907,21 @@ class WaeEngine:
         if g.scalar_input:
             raise NotImplementedError("decode_list: list decoding covers class-id decoders; scalar-input models: use decode_list_scalar "
                                       "(or incremental_forward one batch at a time)")
-        if coop and max(g.R, g.S, g.O) > 256:
-            raise ValueError(f"decode_list(coop=True): the cooperative kernels take R, S and O <= 256 (got {g.R}, {g.S}, {g.O}); "
-                             "use the one-CU list (coop=False)")
+        if coop:
+            D.refuse_wide(g, "decode_list", "list")
         items = list(items)
         if not items:
             raise ValueError("decode_list: an empty list")
         if mode not in ("logits", "argmax", "sample"):
             raise ValueError(f"decode_list: mode '{mode}' is not list-decoded; use 'logits', 'argmax' or 'sample'")
-        m = {"logits": 0, "argmax": 1, "sample": 2}[mode]
-        lib, dev, n = self.lib, self.device, len(items)
-        Ts, plan, off, gids = self._ar_list_plan("decode_list", items, coop, slots, teams)
-        total = plan.total
-        flat = lambda a, dt: torch.as_tensor(a).reshape(-1).to(dev, dt)  # noqa: E731
-        forced, nfs, inits = [], [], []
-        for i, it in enumerate(items):
-            ti = it.get("test_inputs")
-            ti = flat(ti, torch.int32)[:Ts[i]] if ti is not None else None
-            nfs.append(0 if ti is None else int(ti.numel()))
-            forced.append(ti if nfs[i] else None)
-            if m == 0 and nfs[i] < Ts[i]:
-                raise ValueError(f"decode_list: mode 'logits' is teacher-forced: test_inputs of item {i} must cover all {Ts[i]} steps")
-            init = it.get("init_idx")
-            init = 127 if init is None else int(torch.as_tensor(init).reshape(-1)[0])
-            if nfs[i] == 0 and not 0 <= init < g.O:
-                # wavenet.py:288 writes a one at the start class of the start vector: the same IndexError when there are fewer classes
-                raise IndexError(f"index {init} is out of bounds for dimension 2 with size {g.O}")
-            inits.append(init if nfs[i] == 0 else 0)
-        if not self._ar_packed or self.weights_dirty:
-            self.pack_ar_weights()
-        st = self.stream()
-        inputs = self._ar_list_forced(forced, nfs, off, total, torch.int32)
-        if inputs is not None and (int(inputs.min()) < 0 or int(inputs.max()) >= g.O):
-            raise IndexError(f"decode_list: test_inputs hold a class id outside [0, {g.O})")
-        c_up = self._ar_list_cond(items, Ts, off, total, c_is_upsampled)
-        gid32, zb = self._ar_list_speakers(gids)
-        uni = None
-        if m == 2:
-            uni = torch.empty(total, dtype=torch.float32, device=dev)
-            for i, it in enumerate(items):
-                u = it.get("uniforms")
-                u = torch.rand(1, Ts[i], device=dev) if u is None else flat(u, torch.float32)
-                assert u.numel() == Ts[i], f"item {i}: {u.numel()} uniforms for {Ts[i]} steps"
-                uni[off[i]:off[i] + Ts[i]] = u.reshape(-1)
-        items_d, nxt = self._ar_list_records(plan, off, Ts, nfs, inits)
-        out_idx = torch.empty(total, dtype=torch.int32, device=dev)
-        want = want_logits or m == 0
-        logits = torch.empty(total * g.O, dtype=torch.float32, device=dev) if want else None
-        path = (int(self.ar_generic), self.ar_resident[0], self.ar_resident[1]) if coop else ()
-        d = L.ArDesc(self.dt, n, 0, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, 0, 0,
-                     math.sqrt(1.0 / g.layers), 0, *path)
-        operands = (L.ptr(inputs), L.ptr(uni), L.ptr(out_idx), L.ptr(logits))
-        C, ring, msg, acc, err = self._ar_list_buffers(d, plan, coop)
-        if coop:
-            L.check(lib.wae_ar_generate_coop_list(ctypes.byref(d), C, n, plan.slots, L.ptr(items_d), L.ptr(nxt), total,
-                                                  *self._ar_net_args(ring, zb, c_up), *operands, L.ptr(msg), L.ptr(acc), L.ptr(err), st),
-                    "ar_generate_coop_list")
-            self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, uni, msg, acc, err)
-            self._ar_check_exchange(err, "ar_generate_coop_list")
-        else:
-            L.check(lib.wae_ar_generate_list(ctypes.byref(d), n, plan.slots, L.ptr(items_d), L.ptr(nxt),
-                                             *self._ar_net_args(ring, zb, c_up), *operands, st), "ar_generate_list")
-            self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, uni)      # the launch's operands live until the stream has run
-        return [dict(idx=out_idx[off[i]:off[i] + Ts[i]],
-                     logits=logits[off[i] * g.O:(off[i] + Ts[i]) * g.O].view(g.O, Ts[i]) if want else None) for i in range(n)]
+        return D.decode_list(self, "decode_list", items, {"logits": 0, "argmax": 1, "sample": 2}[mode], slots=slots,
+                             want_logits=want_logits, c_is_upsampled=c_is_upsampled, coop=coop, teams=teams)
 
     def scalar_draws(self, T: int):
         """(u_mix (1, T, M) | None, u_log (1, T) or z (1, T)): the draws scalar incremental_forward makes for one utterance of T steps
         where the caller passes none, by the same expressions in the same order (_ar_open; mixture.py:138,151 and :249,266) -- after
         the same torch.manual_seed they are the same numbers."""
-        g, dev = self.g, self.device
-        if g.output_distribution == "Normal":
-            M = 1 if g.O == 2 else g.O // 3
-            u_mix = torch.rand(1, T, M, device=dev) * (1 - 2e-5) + 1e-5 if M > 1 else None
-            return u_mix, torch.randn(1, T, device=dev)
-        u_mix = torch.rand(1, T, g.O // 3, device=dev) * (1 - 2e-5) + 1e-5
-        return u_mix, torch.rand(1, T, device=dev) * (1 - 2e-5) + 1e-5
+        return D.scalar_draws(self, int(T))
 
     def decode_list_scalar(self, items, mode: str = "sample", slots: Optional[int] = None, want_logits: bool = False,
                            c_is_upsampled: bool = False, coop: bool = False, teams: Optional[int] = None,
@@ -1575,85 +948,16 @@ class WaeEngine:
         g, who = self.g, "decode_list_scalar"
         if not g.scalar_input:
             raise ValueError(f"{who}: scalar-input decoders only; a class-id decoder goes through decode_list")
-        if coop and max(g.R, g.S, g.O) > 256:
-            raise ValueError(f"{who}(coop=True): the cooperative kernels take R, S and O <= 256 (got {g.R}, {g.S}, {g.O}); "
-                             "use the one-CU list (coop=False)")
+        if coop:
+            D.refuse_wide(g, who, "list")
         items = list(items)
         if not items:
             raise ValueError(f"{who}: an empty list")
         if mode not in ("logits", "sample"):
             raise ValueError(f"{who}: mode '{mode}': scalar-input decoders feed the drawn sample back: modes 'logits' and 'sample' only")
-        m = {"logits": 0, "sample": 2}[mode]
-        lib, dev, n = self.lib, self.device, len(items)
-        normal = g.output_distribution == "Normal"
-        M = 1 if (normal and g.O == 2) else g.O // 3
-        Ts, plan, off, gids = self._ar_list_plan(who, items, coop, slots, teams)
-        total = plan.total
-        flat = lambda a: torch.as_tensor(a).reshape(-1).to(dev, torch.float32)  # noqa: E731
-        forced, nfs, given = [], [], []
-        for i, it in enumerate(items):
-            ti = it.get("test_inputs")
-            ti = flat(ti)[:Ts[i]] if ti is not None else None
-            nfs.append(0 if ti is None else int(ti.numel()))
-            forced.append(ti if nfs[i] else None)
-            if m == 0 and nfs[i] < Ts[i]:
-                raise ValueError(f"{who}: mode 'logits' is teacher-forced: test_inputs of item {i} must cover all {Ts[i]} steps")
-            um, ul, z = it.get("u_mix"), it.get("u_log"), it.get("z")
-            if normal and ul is not None:
-                raise ValueError(f"{who}: item {i}: output_distribution 'Normal' draws from u_mix and z, not u_log")
-            if not normal and z is not None:
-                raise ValueError(f"{who}: item {i}: output_distribution 'Logistic' draws from u_mix and u_log, not z")
-            if not normal and (um is None) != (ul is None):
-                raise ValueError(f"{who}: item {i}: u_mix and u_log come together")
-            if normal and z is not None and M > 1 and um is None:
-                raise ValueError(f"{who}: item {i}: {M} Gaussians need u_mix beside z")
-            given.append((z if normal else ul) is not None)
-        if m == 0 and any(given) and not all(given):
-            raise ValueError(f"{who}: mode 'logits': give every item its draws (then the samples come back too), or none")
-        sampled = m == 2 or all(given)
-        if not self._ar_packed or self.weights_dirty:
-            self.pack_ar_weights()
-        st = self.stream()
-        inputs = self._ar_list_forced(forced, nfs, off, total, torch.float32)
-        c_up = self._ar_list_cond(items, Ts, off, total, c_is_upsampled)
-        gid32, zb = self._ar_list_speakers(gids)
-        um_d = dr_d = None
-        if sampled:
-            um_d = torch.empty(total, M, dtype=torch.float32, device=dev) if (not normal or M > 1) else None
-            dr_d = torch.empty(total, dtype=torch.float32, device=dev)
-            for i, it in enumerate(items):
-                T = Ts[i]
-                um, dr = it.get("u_mix"), it.get("z" if normal else "u_log")
-                if not given[i]:
-                    um, dr = self.scalar_draws(T)
-                if um_d is not None:
-                    um = flat(um)
-                    assert um.numel() == T * M, f"item {i}: u_mix holds {um.numel()} values for {T} steps of {M} mixtures"
-                    um_d[off[i]:off[i] + T] = um.view(T, M)
-                dr = flat(dr)
-                assert dr.numel() == T, f"item {i}: {dr.numel()} draws for {T} steps"
-                dr_d[off[i]:off[i] + T] = dr
-        items_d, nxt = self._ar_list_records(plan, off, Ts, nfs, [0] * n)
-        xs = torch.empty(total, dtype=torch.float32, device=dev) if sampled else None
-        want = want_logits or m == 0
-        params = torch.empty(total * g.O, dtype=torch.float32, device=dev) if want else None
-        d = L.ArDesc(self.dt, n, 0, g.layers, g.R, g.Rp, g.G, g.Hp, g.S, g.O, max(g.Cc, 0), g.Ccp, g.k, m, 0, 1,
-                     math.sqrt(1.0 / g.layers), 0, *(self._ar_scalar_path() if coop else ()))
-        d.scalar_sized = int(bool(coop) and self.ar_scalar_fast)
-        operands = (L.ptr(inputs), L.ptr(um_d), L.ptr(dr_d), float(log_scale_min), int(bool(clamp_log_scale)), L.ptr(xs), L.ptr(params))
-        C, ring, msg, acc, err = self._ar_list_buffers(d, plan, coop)
-        if coop:
-            L.check(lib.wae_ar_generate_coop_scalar_list(ctypes.byref(d), C, int(normal), n, plan.slots, L.ptr(items_d), L.ptr(nxt), total,
-                                                         *self._ar_net_args(ring, zb, c_up), *operands, L.ptr(msg), L.ptr(acc),
-                                                         L.ptr(err), st), "ar_generate_coop_scalar_list")
-            self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, um_d, dr_d, msg, acc, err)
-            self._ar_check_exchange(err, "ar_generate_coop_scalar_list")
-        else:
-            L.check(lib.wae_ar_generate_scalar_list(ctypes.byref(d), int(normal), n, plan.slots, L.ptr(items_d), L.ptr(nxt),
-                                                    *self._ar_net_args(ring, zb, c_up), *operands, st), "ar_generate_scalar_list")
-            self._ar_keep = (items_d, nxt, ring, zb, gid32, c_up, inputs, um_d, dr_d)
-        return [dict(x=xs[off[i]:off[i] + Ts[i]] if sampled else None,
-                     logits=params[off[i] * g.O:(off[i] + Ts[i]) * g.O].view(g.O, Ts[i]) if want else None) for i in range(n)]
+        return D.decode_list(self, who, items, {"logits": 0, "sample": 2}[mode], slots=slots, want_logits=want_logits,
+                             c_is_upsampled=c_is_upsampled, coop=coop, teams=teams, log_scale_min=log_scale_min,
+                             clamp_log_scale=clamp_log_scale)
 
     def decode_session(self, mode: str = "sample", coop: bool = False, slots: Optional[int] = None, teams: Optional[int] = None,
                        want_logits: bool = False, c_is_upsampled: bool = False, log_scale_min: float = -7.0,
@@ -1684,18 +988,7 @@ class WaeEngine:
         if not items:
             raise ValueError("decode_list_stream: an empty list")
         sess = self.decode_session(**kw)
-        return self._ar_list_rounds(sess, items, chunk)
-
-    def _ar_list_rounds(self, sess, items, chunk):
-        with sess:
-            sess.reserve(len(items))
-            hs = [sess.add(it) for it in items]
-            while sess.live:
-                n = chunk if isinstance(chunk, (int, np.integer)) else {hs[int(i)]: v for i, v in dict(chunk).items() if hs[int(i)] in sess.clips}
-                res = sess.step(n)
-                if not res:
-                    raise ValueError("decode_list_stream: the chunk mapping leaves every live clip out")
-                yield [res.get(h) for h in hs]
+        return D.list_rounds(sess, items, chunk)
 
     # ------------------------------------------------------------------ full autoencoder
     def forward(self, x: torch.Tensor, c: torch.Tensor, gid: Optional[torch.Tensor], targets=None, lengths=None,
