@@ -172,6 +172,46 @@ int wae_vq_slice_bwd(const float* lat, const float* quant, const int64_t* idx, c
 int wae_upsample_stage_fwd(const float* in, const float* w, void* out, int32_t B, int32_t C, int32_t Tin,
                            int32_t s, int32_t out_btc, int32_t Cp, int32_t dtype, void* stream);
 
+/* ---- a3 over a LIST of utterances of unequal lengths (upsample.py:12-85, forward, inference: the upsampling network for every
+ * item of a decode list in one launch per stage).  The reference upsamples one dense (B,C,T) batch; a list is otherwise a loop of
+ * batch-1 chains -- a conv_in launch, one launch per stage and as many allocations per item, in front of the ONE launch that decodes
+ * the list (wae_ar_generate_list and its kin read every item's rows of one packed time-major c_up).
+ * Packed layout: an activation of the list is channel-major and packed along time, as in wae_enc_conv_fwd_list -- (C, pitch) fp32,
+ * item i owning the columns [off_i, off_i + T_i).  The final operand is time-major (rows, Cp) in `dtype`, item i owning the rows
+ * [out_off_i, out_off_i + Tout_i); its pad channels [C, Cp) are written as zeros, as wae_to_btc and the dense last stage do.  An
+ * item's row offset is free (the caller's order; not monotone in in_off).  Every item is zero-padded at its own two ends: a tap
+ * outside [0, Tout_i) contributes nothing, it never reads the neighbour's column.
+ * Table (a DEVICE array the host builds -- packing.upsample_list_plan; nothing here allocates or synchronises): nsegs records
+ * wae_ups_seg {in_off, Tin, out_off, tile0}, tile0 = the index of the item's first tile, and ONE closing record whose tile0 is the
+ * tile count (nsegs + 1 records in all).  The grid is the tile count; a workgroup finds its item by a workgroup-uniform binary search
+ * on tile0, so the table follows the number of items, not of samples.  A tile is WAE_UPS_LIST_TILE_BTC output steps of one item in
+ * the time-major forms, WAE_UPS_LIST_TILE_CT output columns (of 8 channel rows in turn) in the channel-major form, masked at the item's Tout_i.
+ * wae_upsample_stage_fwd_list, one stage by the scale s (Tout_i = Tin_i * s, w[2s+1]):
+ *   out_btc = 0: in (C, in_pitch) -> out (C, out_pitch_or_rows) fp32, tap by tap as wae_upsample_stage_fwd -- acc = fmaf(w[j], r[u / s], acc)
+ *     for j = 0..2s with u = t + j - s inside [0, Tout_i), the frame index kept incrementally (Cp and dtype unused);
+ *   out_btc = 1: the last stage, in (C, in_pitch) -> out (out_pitch_or_rows, Cp) in `dtype`, the input frames of a tile staged in LDS.
+ *     16-bit outputs use the three summed taps on the interior steps s <= t, t + s < Tout_i OF THE ITEM and the tap form on the s
+ *     steps at either end of every item; fp32 output uses the tap form everywhere -- exactly wae_upsample_stage_fwd's rule, taken
+ *     against the item's own length.
+ * wae_to_btc_list: in (C, in_pitch) fp32 -> out (rows, Cp) in `dtype` through the 64x64 LDS tile of wae_to_btc, rows
+ *   [out_off_i, out_off_i + Tin_i) <- columns [in_off_i, in_off_i + Tin_i); for the chains whose last stage does not write the operand
+ *   itself (an upsample_activation; the plain UpsampleNetwork, whose trim the host folds into in_off / Tin) and for conditioning that
+ *   arrives upsampled.  (This entry is not told the rows of out: the host's offsets are the bound of out_off_i + Tin_i.)
+ * Every item's rows are, bit for bit, what wae_upsample_stage_fwd / wae_to_btc write for that item alone (B = 1): both compile the
+ * same per-output functions (csrc/ups_fir.hpp).  Rows and columns that no item owns are not written.
+ * Returns WAE_EINVAL for null in / w / out / segs, C, s, nsegs, ntiles or a pitch < 1, Cp < C or a bad dtype (time-major forms);
+ * WAE_EUNSUPPORTED for the time-major stage with Cp > 256, 256 % Cp != 0, 3 s > 256 or more than 64 KiB of LDS -- the caller then
+ * loops wae_upsample_stage_fwd.  Every refusal returns before any launch.  A record that does not fit the pitches, or whose tile
+ * count contradicts Tout_i = Tin_i * s, is skipped by the kernel: nothing is read or written for it. */
+#define WAE_UPS_LIST_TILE_BTC 64
+#define WAE_UPS_LIST_TILE_CT 256
+typedef struct wae_ups_seg { int32_t in_off, Tin, out_off, tile0; } wae_ups_seg;
+int wae_upsample_stage_fwd_list(const float* in, const float* w, void* out, const wae_ups_seg* segs, int32_t nsegs, int32_t ntiles,
+                                int32_t in_pitch, int32_t out_pitch_or_rows, int32_t C, int32_t s, int32_t out_btc, int32_t Cp,
+                                int32_t dtype, void* stream);
+int wae_to_btc_list(const float* in, void* out, const wae_ups_seg* segs, int32_t nsegs, int32_t ntiles, int32_t in_pitch,
+                    int32_t C, int32_t Cp, int32_t dtype, void* stream);
+
 /* ---- a4/K5 hoisted global conditioning: zb[b][l][2Hp] = bias_l + Wg_l . g_b  (modules.py:148-152) ------
  * g_b = eff[emb_off + gid[b]*Cg ..] (Embedding lookup, wavenet.py:185-190) when gid != NULL, else gvec[b*Cg ..]
  * (external features); both NULL or wg_off < 0 = no global conditioning.  Layer l reads its conv bias at

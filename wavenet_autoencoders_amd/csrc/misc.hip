@@ -2,6 +2,7 @@
 // hoisted global conditioning, first-conv gather, layout converters, masked mean.  All fp32 arithmetic.
 #include <stdarg.h>
 #include "wae_common.hpp"
+#include "ups_fir.hpp"   // the upsample stages' per-output arithmetic, shared with csrc/ups_list.hip
 
 static thread_local char g_err[512] = "";
 
@@ -830,33 +831,21 @@ __global__ void __launch_bounds__(256) upsample_stage_kernel(const float* __rest
     const int c = blockIdx.y;
     if (t >= Tout) return;
     const float* r = in + ((int64_t)b * C + c) * Tin;
-    float acc = 0.f;
-    for (int j = 0; j <= 2 * s; ++j) {
-      const int u = t + j - s;
-      if (u >= 0 && u < Tout) acc = fmaf(w[j], r[u / s], acc);
-    }
-    ((float*)out)[((int64_t)b * C + c) * Tout + t] = acc;
+    ((float*)out)[((int64_t)b * C + c) * Tout + t] = ups_fir_taps(w, r, t, s, Tout);
   } else {
     // time-major output: thread -> (t, c) with c fastest so the stores coalesce
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int t = (int)(e / Cp), c = (int)(e % Cp);
     if (t >= Tout) return;
     float acc = 0.f;
-    if (c < C) {
-      const float* r = in + ((int64_t)b * C + c) * Tin;
-      for (int j = 0; j <= 2 * s; ++j) {
-        const int u = t + j - s;
-        if (u >= 0 && u < Tout) acc = fmaf(w[j], r[u / s], acc);
-      }
-    }
+    if (c < C) acc = ups_fir_taps(w, in + ((int64_t)b * C + c) * Tin, t, s, Tout);
     store_e<E>(out, ((int64_t)b * Tout + t) * Cp + c, acc);
   }
 }
 
 // Last stage (time-major output, audio rate): a block = UPT output steps of one clip.  The input frames those steps touch
 // ((UPT + 2s)/s + 2 per channel) are staged in LDS with reads that run along time, then thread (c, t) walks its 2s+1 taps
-// (the direct form's loads were one cache line per lane, 64 channel rows apart: 0.1 ms per step at C2).
-#define UPT 64
+// (the direct form's loads were one cache line per lane, 64 channel rows apart: 0.1 ms per step at C2).  UPT: csrc/ups_fir.hpp.
 template <typename E>
 __global__ void __launch_bounds__(256) upsample_last_kernel(const float* __restrict__ in, const float* __restrict__ w,
                                                             void* __restrict__ out, int C, int Tin, int s, int Cp, int nfp) {
@@ -876,32 +865,17 @@ __global__ void __launch_bounds__(256) upsample_last_kernel(const float* __restr
   // the reference's FIR additions -- 1e-7 relative, far below a 16-bit output's rounding -- so fp32 launches and the s steps at either end of a
   // clip keep the tap-by-tap form.)
   float* co3 = taps + 2 * s + 1;             // [3][s]
-  if (threadIdx.x < 3 * s) {
-    const int which = threadIdx.x / s, rr = threadIdx.x - which * s;
-    const int ja = which == 0 ? 0 : (which == 1 ? s - rr : 2 * s - rr), jb = which == 0 ? s - rr : (which == 1 ? 2 * s - rr : 2 * s + 1);
-    float a = 0.f;
-    for (int j = ja; j < jb; ++j) a += taps[j];
-    co3[threadIdx.x] = a;
-  }
+  if (threadIdx.x < 3 * s) co3[threadIdx.x] = ups_co3_entry(taps, threadIdx.x, s);
   __syncthreads();
   const int c = threadIdx.x % Cp, tl = threadIdx.x / Cp, tstep = 256 / Cp;
   const float* r = sm + c * nfp - fl;
   for (int t = t0 + tl; t < min(t0 + UPT, Tout); t += tstep) {
     float acc = 0.f;
     if (c < C) {
-      if (sizeof(E) == 2 && t >= s && t + s < Tout) {   // (fp32, the parity mode, keeps the reference's summation order everywhere)
-        const int f = t / s, rr = t - f * s;
-        acc = co3[rr] * r[f - 1];
-        acc = fmaf(co3[s + rr], r[f], acc);
-        acc = fmaf(co3[2 * s + rr], r[f + 1], acc);
-      } else {
-        int j0 = max(0, s - t), u = t + j0 - s;      // first tap with u >= 0
-        int q = u / s, rem = u - q * s;
-        for (int j = j0; j <= 2 * s && u < Tout; ++j, ++u) {
-          acc = fmaf(taps[j], r[q], acc);
-          if (++rem == s) { rem = 0; ++q; }
-        }
-      }
+      if (sizeof(E) == 2 && t >= s && t + s < Tout)   // (fp32, the parity mode, keeps the reference's summation order everywhere)
+        acc = ups_fir_sum3(co3, r, t, s);
+      else
+        acc = ups_fir_walk(taps, r, t, s, Tout);
     }
     store_e<E>(out, ((int64_t)b * Tout + t) * Cp + c, acc);
   }

@@ -4,8 +4,8 @@ Three forms of launch -- "batch" (incremental_forward / incremental_stream: B eq
 decode_list_scalar: a work list of ragged items in one launch) and "spans" (DecodeSession: the next span of every live clip) -- each
 for class-id and scalar-input decoders, on one-CU workgroups or on cooperative teams.  They share ONE of each of: the descriptor
 (ar_desc), the small routing rules (team_width, group_count, mixture, coop_sized / refuse_wide), the per-item checks (clip_intake),
-the per-clip draws (clip_draws), the list decode (decode_list) and the launch (ENTRIES, ar_args, launch).  The functions take the engine
-as `eng`, like backward.py's; WaeEngine keeps the public methods, the packed weights and the helpers that read them (_ar_cond_rows,
+the per-clip draws (clip_draws), the conditioning of a list (_list_cond), the list decode (decode_list) and the launch (ENTRIES,
+ar_args, launch).  The functions take the engine as `eng`, like backward.py's; WaeEngine keeps the public methods, the packed weights and the helpers that read them (_ar_cond_rows,
 _ar_speaker_rows, _ar_exchange, _ar_net_args, _ar_scalar_path, _ar_check_exchange).  What the routes do differently on purpose is
 listed in DESIGN.md ("Decode host path").
 """
@@ -217,6 +217,22 @@ def _clip_cond(eng, item, T, c_is_upsampled, out, at):
     eng._ar_cond_rows((c if c.dim() == 3 else c[None]).contiguous(), out.view(1, T, eng.g.Ccp), c_is_upsampled, at)
 
 
+def _list_cond(eng, items, Ts, c_is_upsampled, out, offsets, at):
+    """The conditioning of a whole list -> the rows [offsets_i, offsets_i + T_i) of out (rows, Ccp) through ONE upsample_list
+    (WaeEngine.upsample_list: a launch per stage for the list, not per item).  The length check of _ar_cond_rows runs here for every
+    item, with at(i) in front, before the first launch."""
+    g, cs = eng.g, [it["c"] if hasattr(it["c"], "shape") else torch.as_tensor(it["c"]) for it in items]
+    direct = c_is_upsampled or not g.upsample_scales
+    for i, (c, T) in enumerate(zip(cs, Ts)):
+        shape = tuple(c.shape)
+        shape = shape if len(shape) == 3 else (1,) + shape
+        if direct:
+            assert shape[-1] == T, f"{at(i)}c {shape} != T {T}"       # wavenet.py:278
+        else:
+            assert (shape[-1] - 2 * g.cin_pad) * int(np.prod(g.upsample_scales)) == T, f"{at(i)}c does not upsample to T"
+    eng.upsample_list(cs, out=out, offsets=offsets, c_is_upsampled=c_is_upsampled)
+
+
 def _gid32(eng, gids):
     return torch.tensor([int(torch.as_tensor(x).reshape(-1)[0]) for x in gids], dtype=torch.int32, device=eng.device)
 
@@ -409,8 +425,7 @@ def decode_list(eng, who, items, m, *, slots, want_logits, c_is_upsampled, coop,
     c_up = None
     if g.Ccp:           # every item's conditioning rows at its offset
         c_up = torch.zeros(total, g.Ccp, dtype=eng.tdtype, device=dev)
-        for i, it in enumerate(items):
-            _clip_cond(eng, it, Ts[i], c_is_upsampled, c_up[off[i]:off[i] + Ts[i]], f"item {i}: ")
+        _list_cond(eng, items, Ts, c_is_upsampled, c_up, off, lambda i: f"item {i}: ")
     gid32 = _gid32(eng, gids) if gids[0] is not None else None
     zb = eng._ar_speaker_rows(n, gid32)         # one row per item, in the caller's order (item.row = the caller's index)
     uni = um_d = dr_d = None
@@ -562,6 +577,50 @@ class DecodeSession:
         eng.hold("session_add", gid32, zb)
         return h
 
+    def add_list(self, items):
+        """Clips join together: equivalent to [sess.add(it) for it in items] -- the same checks, the same draws in the same order, the
+        same handles -- with the conditioning of all of them through ONE WaeEngine.upsample_list (a launch per stage for the list,
+        where add() runs the upsampling network per clip) and their speaker rows through one projection.  Every item is checked before
+        anything is launched or joins: a list with a bad item adds nothing.  Each clip keeps a row slice of the packed result: the
+        slices keep the group's buffer alive until its last clip ends.  Legal at any time between two step() calls.  Returns the
+        clips' handles in the items' order."""
+        if self._closed:
+            raise RuntimeError("decode_session: the session is closed")
+        items = list(items)
+        if not items:
+            return []
+        eng, g, dev, who = self.eng, self.eng.g, self.eng.device, "decode_session.add"
+        gids = [it.get("gid") for it in items]
+        for gid in gids:
+            if (gid is not None) != (self._gids if self._gids is not None else gids[0] is not None):
+                raise ValueError(f"{who}: give every item a gid, or none")
+        took = [clip_intake(g, dev, self.mode, it, who) for it in items]
+        self._open_device()
+        Ts = [t[0] for t in took]
+        offs, c_up = np.concatenate([[0], np.cumsum(Ts)]).astype(np.int64), None
+        if g.Ccp:
+            c_up = torch.empty(int(offs[-1]), g.Ccp, dtype=eng.tdtype, device=dev)      # every row is an item's: all written
+            _list_cond(eng, items, Ts, self.c_is_upsampled, c_up, offs[:-1], lambda i: f"{who}: ")
+        gid32 = _gid32(eng, gids) if gids[0] is not None else None
+        zb = eng._ar_speaker_rows(len(items), gid32)
+        # clip after clip in the items' order, as a loop of add() draws; before anything joins, since a count assert may refuse
+        draws = [clip_draws(eng, it, t[0], t[4], f"{who}: ") if self.mode == 2 else (None, None, None) for it, t in zip(items, took)]
+        need = len(items) - len(self.free)
+        if need > 0:
+            self.reserve(max(2 * self.cap, self.nslots, 8, self.cap + need))
+        slots = [self.free.pop() for _ in items]
+        self.zb[torch.tensor(slots, dtype=torch.int64, device=dev)] = zb
+        self._gids = gids[0] is not None
+        hs = []
+        for i, ((T, forced, nf, init, _), (uni, um, dr)) in enumerate(zip(took, draws)):
+            h = self._next_handle
+            self._next_handle += 1
+            self.clips[h] = _ArClip(T=T, slot=slots[i], c_up=None if c_up is None else c_up[int(offs[i]):int(offs[i + 1])],
+                                    forced=forced, n_forced=nf, init=init, uni=uni, u_mix=um, draw=dr)
+            hs.append(h)
+        eng.hold("session_add", gid32, zb)
+        return hs
+
     def drop(self, handle):
         """Cancels a clip: it leaves the session and its ring is free for the next add."""
         c = self.clips.pop(handle)
@@ -657,7 +716,7 @@ def list_rounds(sess, items, chunk):
     """The rounds of decode_list_stream: the session `sess` holding the fixed list `items`."""
     with sess:
         sess.reserve(len(items))
-        hs = [sess.add(it) for it in items]
+        hs = sess.add_list(items)
         while sess.live:
             n = chunk if isinstance(chunk, (int, np.integer)) else {hs[int(i)]: v for i, v in dict(chunk).items() if hs[int(i)] in sess.clips}
             res = sess.step(n)

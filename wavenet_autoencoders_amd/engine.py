@@ -501,6 +501,115 @@ class WaeEngine:
             save.up_acts, save.up_last, save.up_keep = acts, (x if act else None), xt
         return out
 
+    def upsample_list(self, cs, out: Optional[torch.Tensor] = None, offsets=None, c_is_upsampled: bool = False,
+                      max_samples: Optional[int] = None):
+        """The conditioning rows of a LIST of utterances of unequal lengths (include/wae.h: wae_upsample_stage_fwd_list,
+        wae_to_btc_list): one launch for conv_in, one per stage and, where the last stage does not write the operand itself (an
+        upsample_activation, the plain UpsampleNetwork's trim), one wae_to_btc_list -- per list, where a loop of upsample_forward is
+        that many launches and allocations per item.  The launches, the allocations and the one table upload do not grow with the list.
+
+        cs: a sequence of (Cc, Tc_i) or (1, Cc, Tc_i) arrays -- host arrays, CPU tensors or device tensors, mixed: the latent frames, or
+        the (Cc, T_i) per-sample features when c_is_upsampled or the geometry has no upsampling network.  Host items are packed on the
+        host and go up in one copy; device items are concatenated on the device.
+        out: the packed time-major operand (rows, Ccp) in the model's dtype that the list and span decode kernels read, or None: a new
+        one of sum T_i rows.  offsets: the first row of every item in `out` (free: the caller's order), or None: running sums.
+        max_samples: the most output samples (sum T_i) of one group, by default packing.UPS_LIST_MAX_SAMPLES = 2^22, which keeps the
+        largest fp32 intermediate at 205 MiB for Cc 64 and a last scale of 5; a longer list runs as consecutive groups (an item longer
+        than max_samples is a group of its own).
+        Returns (c_up, offsets).  Every item's rows [offsets_i, offsets_i + T_i), pad channels included, are bit for bit what
+        upsample_forward (or wae_to_btc) writes for that item alone, for every order and every grouping.  Geometries the list kernels do
+        not cover (conv_in with cin_pad > 2, a time-major last stage with Ccp not dividing 256 or 3 s > 256) run that loop into the same
+        rows.  ValueError, before any launch and with the item's index: an empty list, an item that is not (Cc, Tc), an item with no
+        output frame, rows outside `out`."""
+        g, dev = self.g, self.device
+        cs = list(cs)
+        if not cs:
+            raise ValueError("upsample_list: an empty list")
+        if g.Cc <= 0:
+            raise ValueError("upsample_list: this engine has no local conditioning (Cc <= 0)")
+        Tcs = []
+        for i, c in enumerate(cs):
+            shape = tuple(getattr(c, "shape", ()))
+            if len(shape) == 3 and shape[0] == 1:
+                shape = shape[1:]
+            if len(shape) != 2 or shape[0] != g.Cc:
+                raise ValueError(f"upsample_list: item {i} has shape {tuple(getattr(c, 'shape', ()))}; every item is (Cc, Tc) or "
+                                 f"(1, Cc, Tc) with Cc = {g.Cc}")
+            Tcs.append(int(shape[1]))
+        cap = P.UPS_LIST_MAX_SAMPLES if max_samples is None else int(max_samples)
+        if cap < 1:
+            raise ValueError(f"upsample_list: max_samples {cap} < 1")
+        whole = P.upsample_list_plan(Tcs, g, offsets, c_is_upsampled)       # the lengths, the rows and their refusals; not launched
+        Ts, offs = [int(t) for t in whole.Ts], [int(o) for o in whole.offsets]
+        if out is None:
+            out = torch.empty(whole.rows, g.Ccp, dtype=self.tdtype, device=dev)
+        elif (out.dim() != 2 or out.shape[1] != g.Ccp or out.dtype != self.tdtype or not out.is_contiguous() or not out.is_cuda
+              or out.shape[0] < whole.rows):
+            raise ValueError(f"upsample_list: out is {tuple(out.shape)} {out.dtype}; the items need a contiguous ({whole.rows}+, {g.Ccp}) "
+                             f"{self.tdtype} operand on {dev}")
+        if self.weights_dirty:
+            self.prepare_weights()
+        if not P.upsample_list_supported(g, c_is_upsampled):
+            for i, c in enumerate(cs):
+                ci = torch.as_tensor(c).to(dev, torch.float32).reshape(1, g.Cc, Tcs[i]).contiguous()
+                self._ar_cond_rows(ci, out[offs[i]:offs[i] + Ts[i]].view(1, Ts[i], g.Ccp), c_is_upsampled, f"item {i}: ")
+            return out, whole.offsets
+        keep, groups = [], P.upsample_list_groups(Ts, cap)
+        for lo, hi in groups:
+            plan = whole if len(groups) == 1 else P.upsample_list_plan(Tcs[lo:hi], g, offs[lo:hi], c_is_upsampled)
+            keep += self._upsample_group(cs[lo:hi], plan, out, c_is_upsampled)
+        self.hold("upsample_list", *keep)       # the tables and intermediates, passed by raw pointer, until the next list
+        return out, whole.offsets
+
+    def _pack_cond_list(self, cs):
+        """(Cc, sum Tc_i) fp32 on the device, the items side by side in order: the host items in one upload, the rest by one cat"""
+        g, dev = self.g, self.device
+        host = [i for i, c in enumerate(cs) if not (torch.is_tensor(c) and c.is_cuda)]
+        parts = [c.to(dev, torch.float32).reshape(g.Cc, -1) if torch.is_tensor(c) and c.is_cuda else None for c in cs]
+        if host:
+            up = torch.cat([torch.as_tensor(cs[i]).to(torch.float32).reshape(g.Cc, -1) for i in host], dim=1).to(dev)
+            if len(host) == len(cs):
+                return up.contiguous()
+            at = 0
+            for i in host:
+                n = int(cs[i].shape[-1])
+                parts[i] = up[:, at:at + n]
+                at += n
+        return torch.cat(parts, dim=1).contiguous()
+
+    def _upsample_group(self, cs, plan, out, c_is_upsampled):
+        """one group of upsample_list: pack, one table, the chain's launches; -> the tensors the launches read by raw pointer"""
+        g, lib, st, dev = self.g, self.lib, self.stream(), self.device
+        x = self._pack_cond_list(cs)
+        table = torch.from_numpy(plan.table).to(dev)
+        act = 0 if c_is_upsampled else P.UP_ACT_KINDS.get(g.up_act, 0)
+        keep, stage = [table, x], 0
+        for ln in plan.launches:
+            if ln.kind == "conv_in":
+                y = torch.empty(g.Cc, ln.out_pitch, dtype=torch.float32, device=dev)
+                w = self.eff[self.lay.off("wavenet.upsample_net.conv_in.weight"):]
+                L.check(lib.wae_enc_conv_fwd_list(L.ptr(x), L.ptr(w), None, L.ptr(y), L.ptr(table[ln.seg_off:]), ln.nsegs,
+                                                  L.ptr(table[ln.tile_off:]), ln.ntiles, ln.et, ln.in_pitch, ln.out_pitch, g.Cc, g.Cc,
+                                                  ln.s, 1, 0, 0, 0, st), "conv_in (list)")
+            elif ln.kind == "to_btc":
+                y = out
+                L.check(lib.wae_to_btc_list(L.ptr(x), L.ptr(out), L.ptr(table[ln.seg_off:]), ln.nsegs, ln.ntiles, ln.in_pitch, g.Cc,
+                                            g.Ccp, self.dt, st), "to_btc_list (c_up)")
+            else:
+                last = ln.kind == "last"
+                w = self.eff[self.lay.off(P.up_stage_name(g, stage) + ".weight_v"):]
+                stage += 1
+                y = out if last else torch.empty(g.Cc, ln.out_pitch, dtype=torch.float32, device=dev)
+                L.check(lib.wae_upsample_stage_fwd_list(L.ptr(x), L.ptr(w), L.ptr(y), L.ptr(table[ln.seg_off:]), ln.nsegs, ln.ntiles,
+                                                        ln.in_pitch, out.shape[0] if last else ln.out_pitch, g.Cc, ln.s, int(last),
+                                                        g.Ccp, self.dt, st), "upsample_stage (list)")
+                if act:
+                    L.check(lib.wae_act_fwd(L.ptr(y), y.numel(), act, float(g.up_act_slope), st), "upsample activation")
+            if y is not out:
+                keep.append(y)
+            x = y
+        return keep
+
     def layer_drop_seed(self, call: int, layer: int) -> int:
         """64-bit seed of layer `layer`'s dropout mask in the call-th train-mode forward (csrc/misc.hip: dropout_keep)"""
         # distinct (drop_seed, call, layer) triples give distinct seeds; the kernel finalises the seed (dropout_key) before it meets

@@ -246,6 +246,159 @@ def encode_list_groups(Fs, max_frames: int) -> List[Tuple[int, int]]:
 UP_ACT_KINDS = {"ReLU": 1, "LeakyReLU": 2, "Tanh": 3, "Sigmoid": 4}      # include/wae.h: wae_act_fwd
 
 
+# ---- the upsampling network over a list (include/wae.h: wae_upsample_stage_fwd_list, wae_to_btc_list)
+UPS_LIST_TILE_BTC = 64     # output steps of a time-major tile   (include/wae.h: WAE_UPS_LIST_TILE_BTC)
+UPS_LIST_TILE_CT = 256     # output columns of a channel-major tile (include/wae.h: WAE_UPS_LIST_TILE_CT)
+# Default cap on the output samples (sum T_i) of one group of WaeEngine.upsample_list: the intermediates of a group are fp32
+# (Cc, samples / last scale) and smaller ones before it, so at the reference's geometry (Cc 64, last scale 5: hps/vqwae.json) 2^22
+# samples keep the largest at 64 x 2^22 / 5 x 4 B = 205 MiB and the one before it at an eighth of that (scale 8).
+UPS_LIST_MAX_SAMPLES = 1 << 22
+
+
+class UpsListLaunch(NamedTuple):
+    """One launch of an UpsListPlan.  kind: "conv_in" (wae_enc_conv_fwd_list with k = 2 cin_pad + 1, pad 0: seg_off / tile_off are
+    its wae_seg records and (segment, to0) pairs, et its tile length), "stage" (wae_upsample_stage_fwd_list, channel-major), "last"
+    (the same entry, time-major) or "to_btc" (wae_to_btc_list): for these three seg_off is the offset of nsegs + 1 wae_ups_seg records
+    {in_off, Tin, out_off, tile0}, the last one closing (tile0 = ntiles), and tile_off is -1.  s: the stage's scale (conv_in: k;
+    to_btc: 1).  in_pitch / out_pitch: columns of the packed input and output; out_pitch of "last" / "to_btc": the rows of c_up that
+    the records may reach."""
+    kind: str
+    s: int
+    et: int
+    nsegs: int
+    ntiles: int
+    seg_off: int
+    tile_off: int
+    in_pitch: int
+    out_pitch: int
+
+
+class UpsListPlan(NamedTuple):
+    """upsample_list_plan's answer.  launches: the chain in order; table: every launch's records in ONE int32 array (one upload);
+    Tcs, Ts: conditioning frames and output rows per item; in_offsets: the first column of every item in the packed input (running
+    sums, the caller's order); offsets: the first row of every item in c_up (running sums unless the caller gave them); rows: the rows
+    of c_up the plan reaches (max offsets + Ts); in_pitch: sum Tcs; closes_with_to_btc: whether a to_btc launch closes the chain
+    (an upsample_activation, the plain UpsampleNetwork's trim, conditioning that is already upsampled, no network)."""
+    launches: List[UpsListLaunch]
+    table: np.ndarray
+    Tcs: np.ndarray
+    Ts: np.ndarray
+    in_offsets: np.ndarray
+    offsets: np.ndarray
+    rows: int
+    in_pitch: int
+    closes_with_to_btc: bool
+
+    def records(self, i: int) -> np.ndarray:
+        ln = self.launches[i]
+        per = ln.nsegs + (0 if ln.kind == "conv_in" else 1)
+        return self.table[ln.seg_off:ln.seg_off + 4 * per].reshape(per, 4)
+
+
+def _running(x: np.ndarray) -> np.ndarray:
+    return np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(x)[:-1]])
+
+
+def ups_list_records(in_off, Tin, out_off, Tout, tile: int) -> Tuple[np.ndarray, int]:
+    """(n + 1, 4) int32 records {in_off, Tin, out_off, tile0} of one list launch whose items have Tout outputs in tiles of `tile`
+    (tile0: running sums of ceil(Tout_i / tile); the closing record carries the tile count), and that count.  The tiles of an item
+    are tile0_i + 0, 1, ...: they cover [0, Tout_i) once and a tile belongs to one item."""
+    per = -(-np.asarray(Tout, dtype=np.int64) // tile)
+    n = int(per.sum())
+    rec = np.zeros((len(per) + 1, 4), dtype=np.int64)
+    rec[:-1, 0], rec[:-1, 1], rec[:-1, 2], rec[:-1, 3] = in_off, Tin, out_off, _running(per)
+    rec[-1, 3] = n
+    return rec.astype(np.int32), n
+
+
+def upsample_list_supported(g: Geometry, c_is_upsampled: bool = False) -> bool:
+    """Whether the list kernels cover this geometry's conditioning chain; where not, WaeEngine.upsample_list loops upsample_forward.
+    conv_in has list kernels for cin_pad <= 2 (k = 1, 3, 5); a last stage that writes the time-major operand itself needs Ccp dividing
+    256, 3 s <= 256 and its frames in 64 KiB of LDS (csrc/ups_list.hip)."""
+    if c_is_upsampled or not g.upsample_scales:
+        return True
+    if g.conv_in and g.cin_pad > 2:
+        return False
+    if (g.cin_pad == 0 or g.conv_in) and g.up_act == "none":       # the last stage is time-major
+        s = int(g.upsample_scales[-1])
+        nfp = (UPS_LIST_TILE_BTC // s + 5) | 1
+        return g.Ccp <= 256 and 256 % g.Ccp == 0 and 3 * s <= 256 and (g.Ccp * nfp + 5 * s + 1) * 4 <= 65536
+    return True
+
+
+def upsample_list_plan(Tcs, g: Geometry, offsets=None, c_is_upsampled: bool = False) -> UpsListPlan:
+    """Launch plan of WaeEngine.upsample_list for items of Tcs conditioning frames, packed along time in the caller's order: conv_in
+    (ConvInUpsampleNetwork: it eats cin_pad frames at either end), one launch per stage -- the last one time-major straight into c_up
+    unless something follows it --, and where something does (an upsample_activation, the plain UpsampleNetwork's trim of
+    cin_pad * prod(scales) samples at either end, folded into the records' in_off / Tin) a closing to_btc launch.  c_is_upsampled, or
+    a geometry without a network: the to_btc launch alone.  offsets: the first row of every item in c_up (free: the caller's order);
+    None: running sums of the items' rows.  Pure numpy: the plan is a function of the lengths alone.
+    ValueError, with the item's index: an empty list, an item with no output frame, totals at or above 2^31."""
+    Tcs = np.asarray(Tcs, dtype=np.int64).reshape(-1)
+    if Tcs.size < 1:
+        raise ValueError("upsample_list_plan: an empty list")
+    scales = [] if c_is_upsampled else [int(s) for s in (g.upsample_scales or [])]
+    prod = int(np.prod(scales)) if scales else 1
+    pad = g.cin_pad if scales else 0
+    T0 = Tcs - 2 * pad
+    if int(T0.min()) < 1:
+        i = int(np.argmax(T0 < 1))
+        raise ValueError(f"upsample_list_plan: item {i} has no output frame ({int(Tcs[i])} frames"
+                         + (f" under cin_pad {pad})" if pad else ")"))
+    Ts = T0 * prod
+    full = Tcs * prod if (scales and not g.conv_in) else Ts       # columns of the last channel-major activation
+    over = np.cumsum(np.maximum(full, Tcs)) >= 2 ** 31
+    if over.any():
+        raise ValueError(f"upsample_list_plan: item {int(np.argmax(over))}: the packed list reaches 2^31 samples; split it "
+                         "(upsample_list_groups)")
+    offs = _running(Ts) if offsets is None else np.asarray(offsets, dtype=np.int64).reshape(-1)
+    if offs.size != Tcs.size or int(offs.min()) < 0 or int((offs + Ts).max()) >= 2 ** 31:
+        raise ValueError("upsample_list_plan: offsets: one row offset in [0, 2^31) per item")
+    rows = int((offs + Ts).max())
+    launches, parts, at = [], [], 0
+
+    def put(kind, s, et, nsegs, ntiles, arrays, in_pitch, out_pitch):
+        nonlocal at
+        tile_off = at + arrays[0].size if len(arrays) > 1 else -1
+        launches.append(UpsListLaunch(kind, s, et, nsegs, ntiles, at, tile_off, in_pitch, out_pitch))
+        for a in arrays:
+            parts.append(a.reshape(-1))
+            at += a.size
+
+    in_off, Tin, in_pitch = _running(Tcs), Tcs, int(Tcs.sum())
+    if scales and g.conv_in:
+        k = 2 * g.cin_pad + 1
+        segs, tiles, et, To = enc_list_tables(Tcs, k, 1, 0)
+        put("conv_in", k, et, len(segs), len(tiles), [segs, tiles], in_pitch, int(To.sum()))
+        in_off, Tin, in_pitch = _running(To), To, int(To.sum())
+    act = g.up_act != "none"
+    trim = 0 if (not scales or g.conv_in) else g.cin_pad * prod
+    for i, s in enumerate(scales):
+        To = Tin * s
+        if i == len(scales) - 1 and trim == 0 and not act:
+            rec, nt = ups_list_records(in_off, Tin, offs, To, UPS_LIST_TILE_BTC)
+            put("last", s, 0, Tcs.size, nt, [rec], in_pitch, rows)
+        else:
+            out_off = _running(To)
+            rec, nt = ups_list_records(in_off, Tin, out_off, To, UPS_LIST_TILE_CT)
+            put("stage", s, 0, Tcs.size, nt, [rec], in_pitch, int(To.sum()))
+            in_off, in_pitch = out_off, int(To.sum())
+        Tin = To
+    closes = not launches or launches[-1].kind != "last"
+    if closes:
+        rec, nt = ups_list_records(in_off + trim, Tin - 2 * trim, offs, Tin - 2 * trim, UPS_LIST_TILE_BTC)
+        put("to_btc", 1, 0, Tcs.size, nt, [rec], in_pitch, rows)
+    return UpsListPlan(launches, np.concatenate(parts).astype(np.int32), Tcs, Ts, _running(Tcs), offs, rows, int(Tcs.sum()), closes)
+
+
+def upsample_list_groups(Ts, max_samples: int = UPS_LIST_MAX_SAMPLES) -> List[Tuple[int, int]]:
+    """Consecutive groups [lo, hi) of a list of Ts output samples whose sums stay within max_samples; an item longer than max_samples
+    is a group of its own (an item is never split)."""
+    if int(max_samples) < 1:
+        raise ValueError(f"upsample_list_groups: max_samples {int(max_samples)} < 1")
+    return encode_list_groups(Ts, int(max_samples))
+
+
 def up_stage_name(g: Geometry, i: int) -> str:
     """state_dict prefix of upsampling stage i's smoothing FIR: the ModuleList holds [Stretch2d, Conv2d] per stage (upsample.py:38-44),
     under `.upsample` when ConvInUpsampleNetwork wraps it (upsample.py:80-82)"""
