@@ -212,6 +212,32 @@ int wae_upsample_stage_fwd_list(const float* in, const float* w, void* out, cons
 int wae_to_btc_list(const float* in, void* out, const wae_ups_seg* segs, int32_t nsegs, int32_t ntiles, int32_t in_pitch,
                     int32_t C, int32_t Cp, int32_t dtype, void* stream);
 
+/* ---- a3 over ROW RANGES of clips that are still growing (a decode session's open clips: DecodeSession.open / feed / end).
+ * wae_upsample_stage_fwd_list computes every row of every item; this entry computes the rows [t_lo, t_hi) of every record, from the
+ * input columns that are valid NOW.  Output row t of a stage reads the input frames t/s - 1 .. t/s + 1 and nothing else, so with Tin
+ * frames of a clip final, rows t < (Tin - 1) * s are final whatever arrives later: for them every tap u = t + j - s lies below Tin * s,
+ * and the per-output functions (csrc/ups_fir.hpp), called with Tout = Tin * s, run the operations they will run against the clip's
+ * true, longer Tout -- the tap walk stops at 2s either way and the 16-bit interior test s <= t && t + s < Tout gives the same answer.
+ * Once a clip has ended, Tin * s IS its Tout and all rows are final.  The kernels carry no "open" flag; the HOST guarantees
+ * t_hi <= (Tin - 1) * s while a clip is open and t_hi <= Tin * s once it has ended (packing.session_feed_plan).
+ * Record wae_ups_range {in_off, Tin, out_off, t_lo, t_hi, tile0}: in_off, Tin -- the clip's input columns [in_off, in_off + Tin) of
+ * `in` (C, in_pitch) fp32 that are valid now; out_off -- the column (out_btc = 0: out (C, out_pitch_or_rows) fp32) or the row
+ * (out_btc = 1: out (out_pitch_or_rows, Cp) in `dtype`) of the clip's output row 0; t_lo, t_hi -- the rows to compute, in the clip's
+ * own numbering; tile0 -- the index of the record's first tile.  nrecs records and ONE closing record whose tile0 is the tile count,
+ * a DEVICE array.  The tiles of a record count from t_lo: tile k is the rows [t_lo + k * tile, min(t_lo + (k + 1) * tile, t_hi)),
+ * tile = WAE_UPS_LIST_TILE_CT (channel-major) or WAE_UPS_LIST_TILE_BTC (time-major); a workgroup finds its record by the
+ * workgroup-uniform binary search of the list kernels.  Both forms are the list entry's: tap by tap in fp32 channel-major; the
+ * time-major last stage with a tile's frames staged in LDS, pad channels [C, Cp) written as zeros and the three summed taps on the
+ * interior steps of 16-bit outputs.  Rows outside every [t_lo, t_hi) are not written.
+ * The kernel does not trust the table with memory: a record with Tin < 1, t_lo < 0, t_lo >= t_hi, t_hi > Tin * s, a tile count other
+ * than ceil((t_hi - t_lo) / tile), in_off + Tin beyond in_pitch or out_off + t_hi beyond out_pitch_or_rows is skipped, nothing read or
+ * written for it.  Returns WAE_EINVAL / WAE_EUNSUPPORTED exactly where wae_upsample_stage_fwd_list does, before any launch; nothing
+ * allocates or synchronises. */
+typedef struct wae_ups_range { int32_t in_off, Tin, out_off, t_lo, t_hi, tile0; } wae_ups_range;
+int wae_upsample_stage_fwd_ranges(const float* in, const float* w, void* out, const wae_ups_range* recs, int32_t nrecs, int32_t ntiles,
+                                  int32_t in_pitch, int32_t out_pitch_or_rows, int32_t C, int32_t s, int32_t out_btc, int32_t Cp,
+                                  int32_t dtype, void* stream);
+
 /* ---- a4/K5 hoisted global conditioning: zb[b][l][2Hp] = bias_l + Wg_l . g_b  (modules.py:148-152) ------
  * g_b = eff[emb_off + gid[b]*Cg ..] (Embedding lookup, wavenet.py:185-190) when gid != NULL, else gvec[b*Cg ..]
  * (external features); both NULL or wg_off < 0 = no global conditioning.  Layer l reads its conv bias at

@@ -27,6 +27,10 @@ options:
                              chunk.  With or without --batch-coop; a scalar-input model streams on the one-CU slots, or with
                              --batch-coop and --coop-scalar[-fast] on cooperative teams.
                              The wavs written are the bytes of --batch-decode alone.
+    --feed-frames=<K>        With --batch-decode --batch-stream: every clip joins the session open, without its conditioning, and gets
+                             K latent frames in front of every round, as if the speech arrived while it is converted
+                             (DecodeSession.open / feed_list / end); a round decodes the samples whose conditioning is final.  The
+                             wavs written are the bytes of --batch-decode --batch-stream alone, also with --seed.
 """
 import argparse
 import json
@@ -179,6 +183,8 @@ def batch_decode(eng, args, pairs, sp2ind, out_dir):
                               uniforms=torch.rand(1, length, device=device)))
         names.append(f"{out_dir}{tar}_{fid}.wav")
     how = dict(coop=True, teams=args.batch_teams) if args.batch_coop else {}
+    if args.feed_frames:
+        return batch_feed(eng, args, items, names, how)
     if args.batch_stream:
         return batch_stream(eng, args, items, names, how)
     if eng.g.scalar_input:
@@ -216,6 +222,53 @@ def batch_stream(eng, args, items, names, how):
     return 0
 
 
+def batch_feed(eng, args, items, names, how):
+    """--batch-decode --batch-stream=N --feed-frames=K: batch_stream's rounds with every clip OPEN -- it joins without its
+    conditioning (DecodeSession.open) and gets K latent frames in front of every round (feed_list: one launch per upsampling stage for
+    all clips), as if the speech arrived while it is converted; a clip ends with its last frame.  The draws batch_decode made go with
+    the frames they belong to, so a clip decodes bit for bit as in batch_stream: the same wav bytes, also with --seed."""
+    import time
+    from scipy.io import wavfile
+    kw = dict(log_scale_min=hparams.log_scale_min) if eng.g.scalar_input else {}
+    hop = int(np.prod(eng.g.upsample_scales))
+    names_of = ("u_mix", "z" if eng.g.output_distribution == "Normal" else "u_log") if eng.g.scalar_input else ("uniforms",)
+    posts = [ChunkPostprocess(hparams.postprocess, hparams.global_gain_scale) for _ in items]
+    parts, fed = [[] for _ in items], [0] * len(items)
+    t_start, first = time.perf_counter(), True
+    with eng.decode_session(mode="sample", **how, **kw) as sess:
+        sess.reserve(len(items))
+        sess.reserve_frames(sum(int(it["c"].shape[-1]) for it in items))
+        hs = [sess.open({k: it[k] for k in ("gid", "init_idx") if k in it}, max_T=it["T"]) for it in items]
+        while sess.live:
+            feeds, draws, ends = {}, {k: {} for k in names_of}, []
+            for i, (h, it) in enumerate(zip(hs, items)):
+                F = int(it["c"].shape[-1])
+                if fed[i] < F:
+                    n = min(int(args.feed_frames), F - fed[i])
+                    feeds[h] = it["c"][:, fed[i]:fed[i] + n]
+                    for k in names_of:
+                        if it.get(k) is not None:
+                            draws[k][h] = it[k].reshape(it["T"], -1)[fed[i] * hop:(fed[i] + n) * hop]
+                    fed[i] += n
+                    if fed[i] == F:
+                        ends.append(h)
+            sess.feed_list(feeds, **{k: v for k, v in draws.items() if v})
+            for h in ends:
+                sess.end(h)
+            rnd = sess.step(int(args.batch_stream))
+            for i, h in enumerate(hs):
+                res = rnd.get(h)
+                if res is not None:
+                    parts[i].append(posts[i](decoded_wave({k: v[None] for k, v in res.items() if k in ("idx", "x") and v is not None})))
+            if first and all(parts):
+                first = False
+                print(f"first audio of all {len(items)} clips after {(time.perf_counter() - t_start) * 1e3:.1f} ms", flush=True)
+    for out, p in zip(names, parts):
+        wavfile.write(out, hparams.sample_rate, np.concatenate(p))
+        print("Finished! Check out {} for generated audio samples.".format(out), flush=True)
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     for a in ("dump_root", "checkpoint", "dst_dir", "syn_list", "speaker2ind", "lan", "up_factor", "frame_rate", "start_ind"):
@@ -233,12 +286,15 @@ def main(argv=None):
     ap.add_argument("--batch-coop", action="store_true")
     ap.add_argument("--batch-teams", type=int)
     ap.add_argument("--batch-stream", type=int)
+    ap.add_argument("--feed-frames", type=int)
     args = ap.parse_args(argv)
     args.coop_scalar = args.coop_scalar or args.coop_scalar_fast
     if args.batch_stream is not None and not args.batch_decode:
         ap.error("--batch-stream sets the round length of --batch-decode: it needs --batch-decode")
     if args.batch_stream is not None and args.batch_stream < 1:
         ap.error("--batch-stream: a round has at least one sample")
+    if args.feed_frames is not None and (args.batch_stream is None or args.feed_frames < 1):
+        ap.error("--feed-frames feeds that many latent frames (>= 1) per round of --batch-decode --batch-stream: it needs both")
     if (args.batch_coop or args.batch_teams is not None) and not args.batch_decode:
         ap.error("--batch-coop / --batch-teams choose how --batch-decode runs its list: they need --batch-decode")
     if args.batch_coop and args.stream_chunk:

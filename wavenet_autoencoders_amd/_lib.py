@@ -129,6 +129,8 @@ SIGNATURES = {
     "wae_upsample_stage_fwd": (c_i32, [c_vp, c_vp, c_vp] + [c_i32] * 7 + [c_vp]),
     # in, w, out, segs, nsegs, ntiles, in_pitch, out_pitch_or_rows, C, s, out_btc, Cp, dtype, stream
     "wae_upsample_stage_fwd_list": (c_i32, [c_vp] * 4 + [c_i32] * 9 + [c_vp]),
+    # the list entry's arguments, records wae_ups_range in the place of wae_ups_seg
+    "wae_upsample_stage_fwd_ranges": (c_i32, [c_vp] * 4 + [c_i32] * 9 + [c_vp]),
     # in, out, segs, nsegs, ntiles, in_pitch, C, Cp, dtype, stream
     "wae_to_btc_list": (c_i32, [c_vp] * 3 + [c_i32] * 6 + [c_vp]),
     "wae_gproj_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp] + [c_i32] * 6 + [c_vp, c_vp]),

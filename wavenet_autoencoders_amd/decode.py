@@ -149,22 +149,24 @@ def scalar_draws(eng, T):
 
 
 # ---- one item of a list or a session
-def clip_intake(g, device, mode, item, who, index=None, check_ids=True):
+def clip_intake(g, device, mode, item, who, index=None, check_ids=True, open_clip=False):
     """Every check of one item (decode_list's / decode_list_scalar's mapping) for `mode` (0 "logits", 1 "argmax", 2 "sample"), before
     anything else is allocated -> (T, forced, n_forced, init_idx, given): the forced prefix on `device` (at most T values; None where
     there is none), the start class (0 where a prefix is forced, and for scalar-input decoders) and whether the item brings its own
-    scalar draws.  check_ids=False leaves the class-id range of the prefix to the caller (decode_list reads its packed array once)."""
+    scalar draws.  check_ids=False leaves the class-id range of the prefix to the caller (decode_list reads its packed array once).
+    open_clip (DecodeSession.open): the item has no T and no c yet -- T comes back None, the forced prefix whole, and what depends on
+    T (the teacher-forced cover of mode "logits") is DecodeSession.end's to check."""
     at = f"{who}: " if index is None else f"{who}: item {index}: "
-    T = int(item["T"])
-    if T < 1:
+    T = None if open_clip else int(item["T"])
+    if not open_clip and T < 1:
         raise ValueError(f"{at}every clip has at least one step (got {T})")
-    if g.Ccp and item.get("c") is None:
+    if not open_clip and g.Ccp and item.get("c") is None:
         raise ValueError(f"{at}no conditioning c, the decoder has {g.Cc} conditioning channels")
     ti = item.get("test_inputs")
     if ti is not None:
         ti = torch.as_tensor(ti).reshape(-1).to(device, _io(g)[0])[:T]
     nf = 0 if ti is None else int(ti.numel())
-    if mode == 0 and nf < T:
+    if not open_clip and mode == 0 and nf < T:
         raise ValueError(f"{at}mode 'logits' is teacher-forced: test_inputs must cover all {T} steps")
     init, given = 0, False
     if g.scalar_input:
@@ -477,6 +479,23 @@ class _ArClip:
     draw: Optional[torch.Tensor]
     pos: int = 0                    # steps decoded so far = t0 of the next span
     last: Optional[torch.Tensor] = None     # (1,) the previous span's last output, on the device
+    feed: Optional["_Feed"] = None  # a clip joined with open(): its conditioning arrives while it decodes
+
+
+@dataclasses.dataclass
+class _Feed:
+    """What an open clip has beside _ArClip, whose T stays 0 until end() and whose c_up is a view of the session's c_up rows (bound
+    again whenever the arenas move)."""
+    base: int = 0                   # the clip's first column in stage 0's arena, in latent frames
+    cap: int = 0                    # latent frames the clip has room for in the arenas
+    frames: int = 0                 # latent frames fed so far
+    planned: int = 0                # ... when the clip's ranges last ran
+    ended: bool = False
+    ended_planned: bool = False
+    ready: int = 0                  # audio-rate rows of c_up that are final
+    max_frames: Optional[int] = None
+    given: Optional[bool] = None    # whether the draws come with the feeds (fixed by the first feed)
+    drawn: int = 0                  # steps the draws cover
 
 
 class DecodeSession:
@@ -485,7 +504,11 @@ class DecodeSession:
     (the conditioning rows of the whole clip, the speaker row, the clip's own history ring, the draws of all its steps); step() decodes
     the next span of every live clip in one launch and returns the spans' outputs; a clip's outputs, concatenated over the rounds, are
     bit for bit its single decode (incremental_forward alone: on the one-CU kernel for coop=False, on the cooperative path for
-    coop=True), whatever the chunking and whichever slot or team took which span."""
+    coop=True), whatever the chunking and whichever slot or team took which span.
+    A clip may also join before its conditioning exists: open() / feed() / feed_list() / end() ("Clips that are fed while
+    they decode").  step() then decodes min(chunk, ready - pos) steps of it, `ready` being the audio-rate conditioning rows that no
+    later frame can change; its result dict carries `ready`, and `done` is true only once the clip has ended and pos == T.  The bits
+    are those of the clip decoded whole, whatever the feeding."""
 
     def __init__(self, eng, mode="sample", coop=False, slots=None, teams=None, want_logits=False, c_is_upsampled=False,
                  log_scale_min=-7.0, clamp_log_scale=False):
@@ -504,6 +527,8 @@ class DecodeSession:
         self.clips: Dict[int, _ArClip] = {}
         self._next_handle, self._gids, self._closed, self._open = 0, None, False, False
         self._keep = None
+        # open clips (open / feed / end): per-stage channel-major arenas and the time-major c_up rows, in latent frames of room
+        self._fa, self._fa_cup, self._fa_mul, self._fa_cap, self._fa_top, self._fa_pending = None, None, None, 0, 0, False
 
     # ---- the session's device state: once, at the first add
     def _open_device(self):
@@ -621,26 +646,326 @@ class DecodeSession:
         eng.hold("session_add", gid32, zb)
         return hs
 
+    # ---- clips whose conditioning arrives while they decode
+    def _avail(self, c):
+        """steps of clip c that can be decoded now: all of a clip that was added whole, the final rows of an open one (in mode
+        "logits" no further than its forced inputs)"""
+        if c.feed is None:
+            return c.T
+        return min(c.feed.ready, c.n_forced) if self.mode == 0 else c.feed.ready
+
+    def _feed_geometry(self, who):
+        g = self.eng.g
+        if self.c_is_upsampled:
+            raise NotImplementedError(f"{who}: c_is_upsampled conditioning has no upsampling to extend; join the clip whole with add")
+        if not g.Ccp or not g.upsample_scales:
+            raise NotImplementedError(f"{who}: this decoder has no upsampling network to feed; join the clip whole with add")
+        if g.cin_pad > 0:
+            raise NotImplementedError(f"{who}: cin_pad {g.cin_pad} > 0 makes conv_in read neighbouring frames; join the clip whole with add")
+        if g.up_act != "none":
+            raise NotImplementedError(f"{who}: an upsample_activation ({g.up_act}) is not fed in pieces; join the clip whole with add")
+        if not P.upsample_list_supported(g):
+            raise NotImplementedError(f"{who}: the time-major ranges kernel takes Ccp dividing 256 and 3 s <= 256 (got Ccp {g.Ccp}, "
+                                      f"last scale {g.upsample_scales[-1]}); join the clip whole with add")
+        return [int(s) for s in g.upsample_scales]
+
+    def reserve_frames(self, n):
+        """Room for n latent frames of open clips in all: the per-stage channel-major arenas ((Cc, n * prod(scales[:i])) fp32, stage
+        i's input) and the time-major c_up rows ((n * prod(scales), Ccp) in the model's dtype).  They grow on demand, geometrically;
+        growing copies what the open clips have so far.  Retained intermediates are not trimmed."""
+        scales = self._feed_geometry("decode_session.reserve_frames")
+        self._open_device()
+        n = int(n)
+        if n <= self._fa_cap:
+            return
+        eng, g, dev = self.eng, self.eng.g, self.eng.device
+        mul = [int(np.prod(scales[:i])) for i in range(len(scales) + 1)]
+        if n * mul[-1] >= 2 ** 31:
+            raise ValueError(f"decode_session: {n} latent frames of open clips reach 2^31 rows")
+        fa = [torch.empty(g.Cc, n * m, dtype=torch.float32, device=dev) for m in mul[:-1]]
+        cup = torch.empty(n * mul[-1], g.Ccp, dtype=eng.tdtype, device=dev)
+        if self._fa_cap:
+            for new, old in zip(fa, self._fa):
+                new[:, :old.shape[1]] = old
+            cup[:self._fa_cup.shape[0]] = self._fa_cup
+        self._fa, self._fa_cup, self._fa_cap, self._fa_mul = fa, cup, n, mul
+        for c in self.clips.values():
+            self._bind(c)
+
+    def _bind(self, c):
+        if c.feed is not None and self._fa_cup is not None:
+            P_ = self._fa_mul[-1]
+            c.c_up = self._fa_cup[c.feed.base * P_:(c.feed.base + c.feed.cap) * P_]
+
+    def _place(self, c, need):
+        """room for `need` latent frames of clip c: where it lies if it fits (or is the last and can stretch), else at the top of the
+        arenas with what it has so far copied there"""
+        f = c.feed
+        if need <= f.cap:
+            return
+        cap = need if f.max_frames is not None else max(2 * f.cap, need, 8)
+        if f.max_frames is not None:
+            cap = max(cap, f.max_frames)
+        if f.cap and f.base + f.cap == self._fa_top:
+            self._fa_top = f.base
+        base, top = self._fa_top, self._fa_top + cap
+        if top > self._fa_cap:
+            self.reserve_frames(max(2 * self._fa_cap, top))
+        if base != f.base and f.frames:
+            for a, m in zip(self._fa, self._fa_mul):
+                a[:, base * m:(base + f.frames) * m] = a[:, f.base * m:(f.base + f.frames) * m].clone()
+            P_ = self._fa_mul[-1]
+            self._fa_cup[base * P_:base * P_ + f.ready] = self._fa_cup[f.base * P_:f.base * P_ + f.ready].clone()
+        f.base, f.cap, self._fa_top = base, cap, top
+        self._bind(c)
+
+    def open(self, item, max_T=None):
+        """A clip joins before its conditioning exists: `item` is add's mapping (gid, init_idx, test_inputs) without T and without c.
+        The latent frames come with feed() / feed_list(), the clip decodes the rows that are final (step), and end() fixes its length.
+        max_T: the most steps the clip will have -- its room in the arenas is taken once, and a feed beyond it is refused.  Draws (a
+        uniforms / u_mix / u_log / z entry of `item`) are refused here: they come with the feeds.  NotImplementedError, naming add:
+        c_is_upsampled sessions, cin_pad > 0, an upsample_activation, a decoder without an upsampling network.  Returns the handle."""
+        if self._closed:
+            raise RuntimeError("decode_session: the session is closed")
+        eng, g, dev, who = self.eng, self.eng.g, self.eng.device, "decode_session.open"
+        scales = self._feed_geometry(who)
+        if item.get("T") is not None or item.get("c") is not None:
+            raise ValueError(f"{who}: an open clip has no T and no c yet (feed its frames; a whole clip joins with add)")
+        if any(item.get(k) is not None for k in ("uniforms", "u_mix", "u_log", "z")):
+            raise ValueError(f"{who}: the draws of an open clip come with its feeds")
+        gid = item.get("gid")
+        if self._gids is not None and (gid is not None) != self._gids:
+            raise ValueError(f"{who}: give every item a gid, or none")
+        prod = int(np.prod(scales))
+        if max_T is not None and int(max_T) < prod:
+            raise ValueError(f"{who}: max_T {int(max_T)} is less than one latent frame ({prod} steps)")
+        _, forced, nf, init, _ = clip_intake(g, dev, self.mode, item, who, open_clip=True)
+        self._open_device()
+        gid32 = _gid32(eng, [gid]) if gid is not None else None
+        zb = eng._ar_speaker_rows(1, gid32)
+        if not self.free:
+            self.reserve(max(2 * self.cap, self.nslots, 8))
+        slot = self.free.pop()
+        self.zb[slot] = zb[0]
+        self._gids = gid is not None
+        h = self._next_handle
+        self._next_handle += 1
+        c = _ArClip(T=0, slot=slot, c_up=None, forced=forced, n_forced=nf, init=init, uni=None, u_mix=None, draw=None,
+                    feed=_Feed(max_frames=None if max_T is None else int(max_T) // prod))
+        self.clips[h] = c
+        if c.feed.max_frames is not None:
+            self._place(c, c.feed.max_frames)
+        eng.hold("session_add", gid32, zb)
+        return h
+
+    def feed(self, handle, c, uniforms=None, u_mix=None, u_log=None, z=None):
+        """Appends the latent frames c (Cc, f) to one open clip: feed_list({handle: c}, ...) with this clip's draws."""
+        one = lambda a: None if a is None else {handle: a}  # noqa: E731
+        return self.feed_list({handle: c}, uniforms=one(uniforms), u_mix=one(u_mix), u_log=one(u_log), z=one(z))
+
+    def end(self, handle):
+        """The clip has all its frames: T = F * prod(scales), and the rows that waited for a next frame become final -- the closing
+        ranges run with the next feed_list() or step().  ValueError: a clip that is not open, that has ended, that has no frames, whose
+        supplied draws or -- mode "logits" -- forced inputs do not cover T."""
+        who = "decode_session.end"
+        c = self.clips[handle]
+        f = c.feed
+        if f is None:
+            raise ValueError(f"{who}: clip {handle} joined whole (add); only open clips end")
+        if f.ended:
+            raise ValueError(f"{who}: clip {handle} has ended")
+        if f.frames < 1:
+            raise ValueError(f"{who}: clip {handle} has no frames: every clip has at least one step")
+        T = f.frames * self._fa_mul[-1]
+        if self.mode == 2 and f.given and f.drawn < T:
+            raise ValueError(f"{who}: clip {handle} ends at {T} steps beyond the {f.drawn} draws supplied")
+        if self.mode == 0 and c.n_forced < T:
+            raise ValueError(f"{who}: mode 'logits' is teacher-forced: test_inputs must cover all {T} steps")
+        f.ended, c.T, self._fa_pending = True, T, True
+
+    def _feed_draws(self, who, h, c, frames, after, draws):
+        """the draws that come with a feed of `frames` frames to clip h, flat on the device, checked against the rows final `after`
+        it: (uni, u_mix, draw, steps they cover), or None where the engine draws.  The first feed that brings frames or draws fixes
+        which of the two the clip does."""
+        g, f = self.eng.g, c.feed
+        uni, um, ul, z = (None if d is None else d.get(h) for d in draws)
+        if self.mode != 2:
+            if any(a is not None for a in (uni, um, ul, z)):
+                raise ValueError(f"{who}: clip {h}: draws are for mode 'sample'")
+            return None
+        flat = lambda a: torch.as_tensor(a).reshape(-1).to(self.eng.device, torch.float32)  # noqa: E731
+        if not g.scalar_input:
+            if um is not None or ul is not None or z is not None:
+                raise ValueError(f"{who}: clip {h}: a class-id decoder draws from uniforms")
+            given, got = uni is not None, None if uni is None else (flat(uni), None, None)
+        else:
+            if uni is not None:
+                raise ValueError(f"{who}: clip {h}: a scalar-input decoder draws from u_mix and u_log or z, not uniforms")
+            _wrong_draws(self.normal, ul, z, f"{who}: clip {h}: ")
+            dr = z if self.normal else ul
+            if (not self.normal or self.M > 1) and (um is None) != (dr is None):
+                raise ValueError(f"{who}: clip {h}: u_mix and {'z' if self.normal else 'u_log'} come together")
+            given, got = dr is not None, None
+            if given:
+                dr, um = flat(dr), (flat(um) if um is not None and (not self.normal or self.M > 1) else None)
+                if um is not None:
+                    if um.numel() != dr.numel() * self.M:
+                        raise ValueError(f"{who}: clip {h}: u_mix holds {um.numel()} values for {dr.numel()} steps of {self.M} mixtures")
+                    um = um.view(-1, self.M)
+                got = (None, um, dr)
+        if f.given is not None and given != f.given and (frames or given):
+            raise ValueError(f"{who}: clip {h}: the draws come with every feed of a clip, or with none")
+        if not given:
+            return None
+        n = int((got[0] if got[0] is not None else got[2]).numel())
+        if after > f.drawn + n:
+            raise ValueError(f"{who}: clip {h}: this feed makes {after} steps final, beyond the {f.drawn + n} draws supplied")
+        return got + (n,)
+
+    def feed_list(self, feeds, uniforms=None, u_mix=None, u_log=None, z=None):
+        """Latent frames for many open clips: `feeds` maps handle -> c (Cc, f) or (1, Cc, f), f >= 0, host or device.  ONE conv_in
+        launch on the new frames (wae_enc_conv_fwd_list; pointwise at cin_pad 0), ONE wae_upsample_stage_fwd_ranges launch per stage
+        and ONE table upload per call, however many clips are fed (packing.session_feed_plan); clips that have ended since the last
+        call get their closing ranges in the same launches.  The rows a clip has final are, bit for bit, the rows upsample_forward
+        writes for the whole clip, whatever the feeding.
+        Draws of mode "sample": mappings handle -> draws, as add's item entries.  A clip brings draws with every feed or with none.
+        With them, the clip decodes bit for bit as its single decode on the concatenated draws; a feed must not make more rows final
+        than the draws supplied so far cover (f * prod(scales) draws with f frames always do).  Without them the engine's generator
+        draws at feed time, clip after clip in the order of this call's plan (the session's order of joining), for the rows this feed
+        makes final -- NOT add's order, which draws a clip's T steps at once: a seeded fed clip differs from the seeded added clip.
+        Refused before anything is launched (ValueError): a handle that is not an open clip, a feed after end, frames that are not
+        (Cc, f), a feed beyond max_T or beyond the draws supplied.  Returns {handle: ready} for the clips whose rows moved."""
+        if self._closed:
+            raise RuntimeError("decode_session: the session is closed")
+        eng, g, dev, who = self.eng, self.eng.g, self.eng.device, "decode_session.feed"
+        feeds, draws = dict(feeds), (uniforms, u_mix, u_log, z)
+        for d in draws:
+            for h in (d or {}):
+                if h not in feeds:
+                    raise ValueError(f"{who}: draws for clip {h}, which this call does not feed")
+        scales = self._feed_geometry(who) if feeds else None
+        prod, look = P.feed_lookahead(scales) if feeds else (0, 0)
+        new, got = {}, {}
+        for h, c in feeds.items():
+            clip = self.clips.get(h)
+            if clip is None or clip.feed is None:
+                raise ValueError(f"{who}: clip {h} is not an open clip of this session")
+            f = clip.feed
+            if f.ended:
+                raise ValueError(f"{who}: clip {h} has ended: no feed after end")
+            shape = tuple(getattr(c, "shape", ()))
+            shape = shape[1:] if len(shape) == 3 and shape[0] == 1 else shape
+            if len(shape) != 2 or shape[0] != g.Cc:
+                raise ValueError(f"{who}: clip {h}: frames of shape {tuple(getattr(c, 'shape', ()))}; a feed is (Cc, f) or (1, Cc, f) "
+                                 f"with Cc = {g.Cc}")
+            n = int(shape[1])
+            if f.max_frames is not None and f.frames + n > f.max_frames:
+                raise ValueError(f"{who}: clip {h}: {f.frames + n} frames are beyond max_T ({f.max_frames} frames)")
+            new[h] = n
+            if self.mode == 2 or any(d is not None for d in draws):     # (the rows final after this feed: packing.feed_ready)
+                got[h] = self._feed_draws(who, h, clip, n, max(0, prod * (f.frames + n - 1) - look), draws)
+        # everything is checked: room, then the plan over every open clip with rows to run
+        for h, n in new.items():
+            if n:
+                self._place(self.clips[h], self.clips[h].feed.frames + n)
+        todo = [(h, c) for h, c in self.clips.items() if c.feed is not None
+                and (new.get(h, 0) or c.feed.frames != c.feed.planned or c.feed.ended != c.feed.ended_planned)]
+        self._fa_pending = False
+        if not todo:
+            return {}
+        scales = scales or self._feed_geometry(who)
+        if eng.weights_dirty:
+            eng.prepare_weights()
+        plan = P.session_feed_plan(scales, [(c.feed.base, c.feed.planned, c.feed.ended_planned, c.feed.frames + new.get(h, 0), c.feed.ended)
+                                            for h, c in todo])
+        fed = [(h, self.clips[h]) for h, n in new.items() if n]
+        parts, conv = [plan.table], None
+        if fed:     # the new frames, packed in this call's order, and where they go in stage 0's arena
+            ns = [new[h] for h, _ in fed]
+            segs, tiles, et, _ = P.enc_list_tables(ns, 1, 1, 0)
+            segs[:, 2] = [c.feed.base + c.feed.frames for _, c in fed]
+            conv = (plan.table.size, plan.table.size + segs.size, len(segs), len(tiles), et, int(sum(ns)))
+            parts += [segs.reshape(-1), tiles.reshape(-1)]
+            if not g.conv_in:       # the plain network: the frames are stage 0's input as they are
+                parts.append(np.concatenate([np.arange(o, o + n) for o, n in zip(segs[:, 2], ns)]).astype(np.int32))
+        table = torch.from_numpy(np.concatenate(parts)).to(dev)        # ONE upload
+        x = None
+        if fed:
+            x = eng._pack_cond_list([feeds[h] for h, _ in fed])
+            seg_off, tile_off, nsegs, ntiles, et, pitch = conv
+            if g.conv_in:
+                w = eng.eff[eng.lay.off("wavenet.upsample_net.conv_in.weight"):]
+                L.check(eng.lib.wae_enc_conv_fwd_list(L.ptr(x), L.ptr(w), None, L.ptr(self._fa[0]), L.ptr(table[seg_off:]), nsegs,
+                                                      L.ptr(table[tile_off:]), ntiles, et, pitch, self._fa[0].shape[1], g.Cc, g.Cc, 1, 1,
+                                                      0, 0, 0, eng.stream()), "conv_in (feed)")
+            else:
+                self._fa[0].index_copy_(1, table[tile_off + 2 * ntiles:].long(), x)
+        for ln in plan.launches:
+            w = eng.eff[eng.lay.off(P.up_stage_name(g, ln.stage) + ".weight_v"):]
+            out = self._fa_cup if ln.last else self._fa[ln.stage + 1]
+            L.check(eng.lib.wae_upsample_stage_fwd_ranges(L.ptr(self._fa[ln.stage]), L.ptr(w), L.ptr(out), L.ptr(table[ln.rec_off:]),
+                                                          ln.nrecs, ln.ntiles, self._fa[ln.stage].shape[1],
+                                                          out.shape[0] if ln.last else out.shape[1], g.Cc, ln.s, int(ln.last), g.Ccp,
+                                                          eng.dt, eng.stream()), "upsample_stage (ranges)")
+        eng.hold("session_feed", table, x)
+        moved = {}
+        for (h, c), ready in zip(todo, plan.ready):
+            f, ready = c.feed, int(ready)
+            f.frames += new.get(h, 0)
+            f.planned, f.ended_planned = f.frames, f.ended
+            if self.mode == 2:
+                if f.given is None and (new.get(h, 0) or got.get(h) is not None):
+                    f.given = got.get(h) is not None
+                self._append_draws(c, got.get(h), ready)
+            if ready != f.ready:
+                moved[h] = ready
+            f.ready = ready
+        return moved
+
+    def _append_draws(self, c, got, ready):
+        """the clip's draws grow: by what came with the feed, or -- the engine's generator -- by clip_draws' expressions for the rows
+        that became final"""
+        f = c.feed
+        if got is not None:
+            uni, um, dr, n = got
+        else:
+            n = ready - f.drawn
+            if f.given or n < 1:
+                return
+            uni, um, dr = clip_draws(self.eng, {}, n, False, "decode_session.feed: ")
+        cat = lambda old, a: a if old is None or a is None else torch.cat([old, a])  # noqa: E731
+        c.uni, c.u_mix, c.draw, f.drawn = cat(c.uni, uni), cat(c.u_mix, um), cat(c.draw, dr), f.drawn + n
+
     def drop(self, handle):
         """Cancels a clip: it leaves the session and its ring is free for the next add."""
         c = self.clips.pop(handle)
         self.free.append(c.slot)
+        if c.feed is not None:      # the clip's columns: the top of the arenas falls back where it was the last, and to 0 with the last open clip
+            if c.feed.base + c.feed.cap == self._fa_top:
+                self._fa_top = c.feed.base
+            if not any(k.feed is not None for k in self.clips.values()):
+                self._fa_top = 0
 
     def step(self, chunk):
         """One launch: the next min(chunk, remaining) steps of every live clip (`chunk`: an int, or a mapping from handle to steps -- a
         clip the mapping leaves out sits the round out).  Returns {handle: dict(idx | x, logits, done)} for the clips that decoded: the
         span's class ids (n,) int32 or samples (n,) fp32, its logits / mixture parameters (O, n) where asked for, and whether the clip
         has finished -- it has then left the session.  The forced first input of a continuation comes from the previous round's output
-        on the device; only the team path reads one word back per launch (the time-out flag)."""
+        on the device; only the team path reads one word back per launch (the time-out flag).
+        A clip joined with open() decodes min(chunk, ready - pos) steps, `ready` being its conditioning rows that are final: with
+        ready == pos it sits the round out (absent from the result, not done).  Its dict also carries `ready`, and `done` is true only
+        once the clip has ended and pos == T.  Clips that ended since the last feed get their closing ranges first."""
         if self._closed:
             raise RuntimeError("decode_session: the session is closed")
         handles = list(self.clips)
         if not handles:
             return {}
+        if self._fa_pending:        # clips that ended since the last feed: their closing ranges
+            self.feed_list({})
         if not isinstance(chunk, (int, np.integer)):
             chunk = {handles.index(h): int(n) for h, n in dict(chunk).items()}
         clips = [self.clips[h] for h in handles]
-        plan = P.ar_round_plan([c.T - c.pos for c in clips], [c.pos for c in clips], chunk, self.nslots)
+        plan = P.ar_round_plan([self._avail(c) - c.pos for c in clips], [c.pos for c in clips], chunk, self.nslots)
         if plan.total == 0:
             return {}
         eng, g, dev = self.eng, self.eng.g, self.eng.device
@@ -691,9 +1016,11 @@ class DecodeSession:
             c.pos += n
             if out is not None:
                 c.last = out[off + n - 1:off + n]
-            done = c.pos >= c.T
+            done = c.pos >= c.T and (c.feed is None or c.feed.ended)
             res[h] = {key: None if out is None else out[off:off + n],
                       "logits": logits[off * g.O:(off + n) * g.O].view(g.O, n) if self.want else None, "done": done}
+            if c.feed is not None:
+                res[h]["ready"] = c.feed.ready
             if done:
                 self.drop(h)
         return res
@@ -702,7 +1029,7 @@ class DecodeSession:
         """Frees everything: the clips, their rings and the exchange buffers.  Results already returned stay valid."""
         self.clips.clear()
         self._closed = True
-        self.ring = self.zb = self.exchange = self._keep = None
+        self.ring = self.zb = self.exchange = self._keep = self._fa = self._fa_cup = None
 
     def __enter__(self):
         return self

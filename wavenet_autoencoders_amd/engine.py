@@ -1083,7 +1083,13 @@ class WaeEngine:
         the mixture parameters come back and x is None): on the slots, or with coop=True on the teams once the engine has opted in with
         ar_path(scalar_coop=True) -- without that opt-in coop=True raises NotImplementedError -- on the any-shape kernel or, under
         ar_path(scalar_fast=True), the constant-size scalar kernels (wae_ar_generate_coop_scalar_spans).  ValueError: R, S or
-        O > 256 with coop=True; a mode the matching list call does not take."""
+        O > 256 with coop=True; a mode the matching list call does not take.
+        A clip whose conditioning arrives while it decodes joins with h = sess.open(item) (add's mapping without T and c; optional
+        max_T), gets latent frames with sess.feed(h, c) / sess.feed_list({h: c, ...}) -- one conv_in launch, one
+        wae_upsample_stage_fwd_ranges launch per stage and one table upload per call -- and ends with sess.end(h); step() decodes the
+        rows of it that no later frame can change (`ready` in its result).  Its bits are those of the clip decoded whole (DESIGN.md
+        3.4.3); cin_pad > 0, an upsample_activation and c_is_upsampled sessions are refused there with NotImplementedError.  In mode
+        "logits" an open clip decodes no further than its forced inputs, which must cover T by the time it ends."""
         return DecodeSession(self, mode=mode, coop=coop, slots=slots, teams=teams, want_logits=want_logits, c_is_upsampled=c_is_upsampled,
                              log_scale_min=log_scale_min, clamp_log_scale=clamp_log_scale)
 

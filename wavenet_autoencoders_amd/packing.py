@@ -399,6 +399,110 @@ def upsample_list_groups(Ts, max_samples: int = UPS_LIST_MAX_SAMPLES) -> List[Tu
     return encode_list_groups(Ts, int(max_samples))
 
 
+# ---- clips whose conditioning arrives while they decode (include/wae.h: wae_upsample_stage_fwd_ranges; DecodeSession.open / feed)
+def feed_final_rows(frames: int, scales, ended: bool) -> List[int]:
+    """Rows of a clip that are FINAL at every level of the upsampling chain once `frames` latent frames have arrived: entry 0 is the
+    frames themselves (stage 0's input), entry i + 1 the output of stage i, the last one audio-rate rows (`ready`).  Output row t of a
+    stage by s reads its input frames t/s - 1 .. t/s + 1, so n final input rows make (n - 1) * s output rows final while the clip is
+    open and n * s once it has ended."""
+    rows = [max(int(frames), 0)]
+    for s in scales:
+        rows.append(rows[-1] * int(s) if ended else max(rows[-1] - 1, 0) * int(s))
+    return rows
+
+
+def feed_ready(frames: int, scales, ended: bool) -> int:
+    """feed_final_rows' last entry in closed form: prod * (F - 1) - sum_{i >= 1} prod(scales[i:]) while open (0 where that is
+    negative), prod * F once ended.  hps/vqwae.json's [4, 4, 8, 5]: 640 (F - 1) - 205, a lookahead of 845 samples."""
+    prod, look = feed_lookahead(scales)
+    return max(int(frames), 0) * prod if ended else max(0, prod * (int(frames) - 1) - look)
+
+
+def feed_lookahead(scales) -> Tuple[int, int]:
+    """(prod(scales), sum_{i >= 1} prod(scales[i:])): the audio-rate rows of a latent frame, and the rows beyond one frame that an
+    open clip holds back"""
+    sc = [int(s) for s in scales]
+    return int(np.prod(sc)), sum(int(np.prod(sc[i:])) for i in range(1, len(sc)))
+
+
+class FeedClip(NamedTuple):
+    """One clip of a session_feed_plan.  base: the clip's first column in stage 0's arena, in latent frames -- its first column at
+    stage i is base * prod(scales[:i]), its first c_up row base * prod(scales); frames_before / ended_before: the frames that had
+    arrived, and whether the clip had ended, when its ranges last ran; frames / ended: now."""
+    base: int
+    frames_before: int
+    ended_before: bool
+    frames: int
+    ended: bool
+
+
+class FeedLaunch(NamedTuple):
+    """One wae_upsample_stage_fwd_ranges launch of a FeedPlan: stage index and scale, last (time-major into c_up), nrecs records
+    {in_off, Tin, out_off, t_lo, t_hi, tile0} and a closing one at rec_off of the table, ntiles."""
+    stage: int
+    s: int
+    last: bool
+    nrecs: int
+    ntiles: int
+    rec_off: int
+
+
+class FeedPlan(NamedTuple):
+    """session_feed_plan's answer.  launches: the stages that have a record, in order (a stage without one is not launched); table:
+    every launch's records in ONE int32 array (one upload); ready: audio-rate rows final per clip after this feed."""
+    launches: List[FeedLaunch]
+    table: np.ndarray
+    ready: np.ndarray
+
+    def records(self, i: int) -> np.ndarray:
+        ln = self.launches[i]
+        return self.table[ln.rec_off:ln.rec_off + 6 * (ln.nrecs + 1)].reshape(ln.nrecs + 1, 6)
+
+
+def session_feed_plan(scales, clips) -> FeedPlan:
+    """The range records of one DecodeSession.feed_list for `clips` (FeedClip, or its five fields as a tuple, per open clip): per
+    stage and clip, the output rows that this feed (or this end) makes final
+    -- [final before, final now) of feed_final_rows -- computed from the input rows final now.  While a clip is open its record has
+    t_hi = (Tin - 1) * s, once ended t_hi = Tin * s: the guarantee wae_upsample_stage_fwd_ranges asks of the host.  Records with empty
+    ranges are left out.  Over the feeds of a clip the ranges of a stage tile [0, T) exactly once.  Pure numpy: a function of the
+    counts alone.  ValueError: no scales, a clip that shrinks or reopens, columns or rows at or above 2^31."""
+    sc = [int(s) for s in scales]
+    if not sc or min(sc) < 1:
+        raise ValueError(f"session_feed_plan: scales {sc}: at least one stage, every scale >= 1")
+    cols = np.asarray([tuple(c) for c in clips], dtype=np.int64).reshape(-1, 5)
+    base, f0, e0, f1, e1 = (cols[:, k] for k in range(5))
+    e0, e1 = e0 != 0, e1 != 0
+    mul = [int(np.prod(sc[:i])) for i in range(len(sc) + 1)]
+    bad = (f1 < f0) | (f0 < 0) | (base < 0) | (e0 & (~e1 | (f1 != f0)))
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(f"session_feed_plan: clip {i}: frames {int(f0[i])} -> {int(f1[i])}, ended {bool(e0[i])} -> {bool(e1[i])}")
+    over = (base + np.maximum(f1, 1)) * mul[-1] >= 2 ** 31
+    if over.any():
+        raise ValueError(f"session_feed_plan: clip {int(np.argmax(over))}: its rows reach 2^31")
+    before, now = [f0], [f1]         # feed_final_rows for all clips at once
+    for s in sc:
+        before.append(np.where(e0, before[-1], np.maximum(before[-1] - 1, 0)) * s)
+        now.append(np.where(e1, now[-1], np.maximum(now[-1] - 1, 0)) * s)
+    launches, parts, at = [], [], 0
+    for i, s in enumerate(sc):
+        last = i == len(sc) - 1
+        tile = UPS_LIST_TILE_BTC if last else UPS_LIST_TILE_CT
+        k = np.nonzero(now[i + 1] > before[i + 1])[0]
+        if not k.size:
+            continue
+        lo, hi = before[i + 1][k], now[i + 1][k]
+        per = -(-(hi - lo) // tile)
+        rec = np.zeros((k.size + 1, 6), dtype=np.int64)
+        rec[:-1] = np.stack([base[k] * mul[i], now[i][k], base[k] * mul[i + 1], lo, hi, _running(per)], axis=1)
+        rec[-1, 5] = int(per.sum())
+        launches.append(FeedLaunch(i, s, last, int(k.size), int(per.sum()), at))
+        parts.append(rec.reshape(-1))
+        at += rec.size
+    table = np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, dtype=np.int32)
+    return FeedPlan(launches, table, now[-1])
+
+
 def up_stage_name(g: Geometry, i: int) -> str:
     """state_dict prefix of upsampling stage i's smoothing FIR: the ModuleList holds [Stretch2d, Conv2d] per stage (upsample.py:38-44),
     under `.upsample` when ConvInUpsampleNetwork wraps it (upsample.py:80-82)"""
