@@ -140,6 +140,33 @@ int wae_enc_conv_fwd_list(const float* x, const float* w, const float* bias, flo
                           const int32_t* tiles, int32_t ntiles, int32_t et, int32_t in_pitch, int32_t out_pitch, int32_t Cin,
                           int32_t Cout, int32_t k, int32_t stride, int32_t pad, int32_t relu, int32_t residual, void* stream);
 
+/* ---- a1 over COLUMN RANGES of utterances that are still growing (an encode session's open clips: EncodeSession.open / feed / end).
+ * wae_enc_conv_fwd_list computes every output of every utterance; this entry computes the outputs [t_lo, t_hi) of every record, from
+ * the input columns that are valid NOW.  Output t of a block (k, stride s, pad p = k/2) reads the inputs t s - p .. t s - p + k - 1
+ * and nothing else, so with n input columns of a clip final, the outputs t <= (n - k + p) / s -- floor((n - k + p) / s) + 1 of them, 0
+ * where n - k + p < 0 -- are final whatever arrives later: none of their taps reaches column n.  Once the clip has ended, all
+ * (n + 2p - k) / s + 1 outputs are final, the taps at or beyond n being the clip's own zero padding.  Through ENCODER_BLOCKS and lin,
+ * F feature frames make max(0, (F - 13) / 4) latent frames final while the clip is open and (F + 3) / 4 once it has ended.  The kernel
+ * carries no "open" flag; the HOST guarantees t_hi <= the open count while a clip is open and t_hi <= Tout once it has ended
+ * (packing.enc_feed_plan).  Inside that bound no tap of an open clip reaches Tin, and a tap outside [0, Tin) reads 0.
+ * Record wae_enc_range {in_off, Tin, out_col, t_lo, t_hi, tile0}: in_off, Tin -- the clip's input columns [in_off, in_off + Tin) of
+ * x (Cin, in_pitch) fp32 that are valid now; t_lo, t_hi -- the outputs to compute, in the clip's own numbering; out_col -- the column
+ * of y (Cout, out_pitch) that receives t_lo (a per-clip arena: base + t_lo; a packed buffer of this call's new columns: its running
+ * offset); tile0 -- the index of the record's first tile.  nrecs records and ONE closing record whose tile0 is the tile count, a
+ * DEVICE array.  Tile j of a record is the outputs [t_lo + j et, min(t_lo + (j + 1) et, t_hi)); a workgroup finds its record by the
+ * workgroup-uniform binary search of the upsampling list kernels.  Grid (ntiles, ceil(Cout/32)); et: 8, 16 or 32.
+ * Every output is, bit for bit, what wae_enc_conv_fwd writes for the whole clip (B = 1): the value of an output is the same fixed
+ * sequence of fmaf and adds (csrc/enc_list.hip: one kernel template, which the list entry launches too), and nothing in it depends on the tile's
+ * origin or length.  residual reads x at (oc, in_off + ot).  Columns of y outside every range are not written.
+ * The kernel does not trust the table with memory: a record with Tin < 1, t_lo < 0, t_lo >= t_hi, t_hi > (Tin + 2 pad - k) / stride + 1,
+ * a tile count other than ceil((t_hi - t_lo) / et), in_off < 0, in_off + Tin > in_pitch, out_col < 0 or out_col + (t_hi - t_lo) >
+ * out_pitch is skipped as a whole, nothing read or written for it.  Returns WAE_EINVAL / WAE_EUNSUPPORTED exactly where
+ * wae_enc_conv_fwd_list does, before any launch; nothing allocates or synchronises. */
+typedef struct wae_enc_range { int32_t in_off, Tin, out_col, t_lo, t_hi, tile0; } wae_enc_range;
+int wae_enc_conv_fwd_ranges(const float* x, const float* w, const float* bias, float* y, const wae_enc_range* recs, int32_t nrecs,
+                            int32_t ntiles, int32_t et, int32_t in_pitch, int32_t out_pitch, int32_t Cin, int32_t Cout, int32_t k,
+                            int32_t stride, int32_t pad, int32_t relu, int32_t residual, void* stream);
+
 /* ---- a2 VectorQuantize.forward (vector_quantization.py:21-49) -----------------------------------------
  * lat (B,D,Tq) fp32, emb (K,D).  idx int64 (B*Tq) first-minimum of ||e||^2+||x||^2-2x.e; quant (B,D,Tq);
  * stats[0] = vq_loss = (beta+1)*mean((q-x)^2) forward value, stats[1] = perplexity; hist: (K+1) int32 scratch. */

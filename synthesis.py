@@ -31,6 +31,11 @@ options:
                              K latent frames in front of every round, as if the speech arrived while it is converted
                              (DecodeSession.open / feed_list / end); a round decodes the samples whose conditioning is final.  The
                              wavs written are the bytes of --batch-decode --batch-stream alone, also with --seed.
+    --feed-features=<K>      With --batch-decode --batch-stream: every clip joins an encode session AND the decode session open and
+                             gets K feature frames in front of every round (EncodeSession.open / feed_list); the latent frames that
+                             call makes final go straight into DecodeSession.feed_list, and the clip ends in both sessions behind its
+                             last frames -- the whole conversion fed incrementally.  The wavs written are the bytes of --batch-decode
+                             --batch-stream alone, also with --seed.  Not with --feed-frames.
 """
 import argparse
 import json
@@ -168,7 +173,9 @@ def batch_decode(eng, args, pairs, sp2ind, out_dir):
         if tar not in sp2ind:
             raise KeyError(f"cant find sp {tar} in sp2ind {args.speaker2ind}")
         read.append((tar, fid, c))
-    quants = [r["quant"] for r in eng.encode_list([np.ascontiguousarray(c.T).astype(np.float32) for _, _, c in read], want_idx=False)]
+    feats = [np.ascontiguousarray(c.T).astype(np.float32) for _, _, c in read]
+    # (--feed-features: the encoder runs inside the rounds, on the frames as they are fed)
+    quants = [None] * len(read) if args.feed_features else [r["quant"] for r in eng.encode_list(feats, want_idx=False)]
     items, names = [], []
     for (tar, fid, c), quant in zip(read, quants):
         length = c.shape[0] * int(args.up_factor)
@@ -176,13 +183,15 @@ def batch_decode(eng, args, pairs, sp2ind, out_dir):
             torch.manual_seed(args.seed)
         if eng.g.scalar_input:
             u_mix, draw = eng.scalar_draws(length)
-            items.append(dict(c=quant.contiguous(), gid=sp2ind[tar], T=length, u_mix=u_mix,
+            items.append(dict(c=None if quant is None else quant.contiguous(), gid=sp2ind[tar], T=length, u_mix=u_mix,
                               **{"z" if eng.g.output_distribution == "Normal" else "u_log": draw}))
         else:
-            items.append(dict(c=quant.contiguous(), gid=sp2ind[tar], T=length, init_idx=int(args.initial_value),
+            items.append(dict(c=None if quant is None else quant.contiguous(), gid=sp2ind[tar], T=length, init_idx=int(args.initial_value),
                               uniforms=torch.rand(1, length, device=device)))
         names.append(f"{out_dir}{tar}_{fid}.wav")
     how = dict(coop=True, teams=args.batch_teams) if args.batch_coop else {}
+    if args.feed_features:
+        return batch_feed_features(eng, args, items, feats, names, how)
     if args.feed_frames:
         return batch_feed(eng, args, items, names, how)
     if args.batch_stream:
@@ -269,6 +278,65 @@ def batch_feed(eng, args, items, names, how):
     return 0
 
 
+def batch_feed_features(eng, args, items, feats, names, how):
+    """--batch-decode --batch-stream=N --feed-features=K: batch_feed's rounds with the encoder inside them.  Every clip joins an encode
+    session and the decode session open; a round feeds K feature frames per clip to the encode session (EncodeSession.feed_list: one
+    launch per encoder layer for all clips), hands the quantised latents that call made final to DecodeSession.feed_list with the
+    draws of their samples, and decodes; a clip ends in both sessions behind its last frames.  The latents are bit for bit
+    encode_list's and the draws are batch_decode's, so the wavs are batch_stream's bytes, also with --seed."""
+    import time
+    from scipy.io import wavfile
+    kw = dict(log_scale_min=hparams.log_scale_min) if eng.g.scalar_input else {}
+    hop = int(np.prod(eng.g.upsample_scales))
+    names_of = ("u_mix", "z" if eng.g.output_distribution == "Normal" else "u_log") if eng.g.scalar_input else ("uniforms",)
+    posts = [ChunkPostprocess(hparams.postprocess, hparams.global_gain_scale) for _ in items]
+    parts, fed, got = [[] for _ in items], [0] * len(items), [0] * len(items)
+    t_start, first = time.perf_counter(), True
+    with eng.encode_session() as enc, eng.decode_session(mode="sample", **how, **kw) as sess:
+        sess.reserve(len(items))
+        sess.reserve_frames(sum(it["T"] // hop for it in items))
+        enc.reserve_frames(sum(-(-f.shape[1] // 4) * 4 for f in feats))
+        hs = [sess.open({k: it[k] for k in ("gid", "init_idx") if k in it}, max_T=it["T"]) for it in items]
+        es = [enc.open(max_frames=f.shape[1]) for f in feats]
+        while sess.live:
+            feeds, last = {}, []
+            for i, (e, f) in enumerate(zip(es, feats)):
+                if fed[i] < f.shape[1]:
+                    n = min(int(args.feed_features), f.shape[1] - fed[i])
+                    feeds[e] = f[:, fed[i]:fed[i] + n]
+                    fed[i] += n
+                    if fed[i] == f.shape[1]:
+                        last.append(e)
+            new = enc.feed_list(feeds, ended=last) if feeds else {}
+            lat, draws, ends = {}, {k: {} for k in names_of}, []
+            for i, (h, e, it) in enumerate(zip(hs, es, items)):
+                res = new.get(e)
+                n = 0 if res is None else int(res["quant"].shape[1])
+                if n:
+                    lat[h] = res["quant"]
+                    for k in names_of:
+                        if it.get(k) is not None:
+                            draws[k][h] = it[k].reshape(it["T"], -1)[got[i] * hop:(got[i] + n) * hop]
+                    got[i] += n
+                if res is not None and res["done"]:
+                    ends.append(h)
+            sess.feed_list(lat, **{k: v for k, v in draws.items() if v})
+            for h in ends:
+                sess.end(h)
+            rnd = sess.step(int(args.batch_stream))
+            for i, h in enumerate(hs):
+                res = rnd.get(h)
+                if res is not None:
+                    parts[i].append(posts[i](decoded_wave({k: v[None] for k, v in res.items() if k in ("idx", "x") and v is not None})))
+            if first and all(parts):
+                first = False
+                print(f"first audio of all {len(items)} clips after {(time.perf_counter() - t_start) * 1e3:.1f} ms", flush=True)
+    for out, p in zip(names, parts):
+        wavfile.write(out, hparams.sample_rate, np.concatenate(p))
+        print("Finished! Check out {} for generated audio samples.".format(out), flush=True)
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     for a in ("dump_root", "checkpoint", "dst_dir", "syn_list", "speaker2ind", "lan", "up_factor", "frame_rate", "start_ind"):
@@ -287,6 +355,7 @@ def main(argv=None):
     ap.add_argument("--batch-teams", type=int)
     ap.add_argument("--batch-stream", type=int)
     ap.add_argument("--feed-frames", type=int)
+    ap.add_argument("--feed-features", type=int)
     args = ap.parse_args(argv)
     args.coop_scalar = args.coop_scalar or args.coop_scalar_fast
     if args.batch_stream is not None and not args.batch_decode:
@@ -295,6 +364,10 @@ def main(argv=None):
         ap.error("--batch-stream: a round has at least one sample")
     if args.feed_frames is not None and (args.batch_stream is None or args.feed_frames < 1):
         ap.error("--feed-frames feeds that many latent frames (>= 1) per round of --batch-decode --batch-stream: it needs both")
+    if args.feed_features is not None and (args.batch_stream is None or args.feed_features < 1):
+        ap.error("--feed-features feeds that many feature frames (>= 1) per round of --batch-decode --batch-stream: it needs both")
+    if args.feed_features is not None and args.feed_frames is not None:
+        ap.error("--feed-features feeds the encoder, --feed-frames the decoder: they cannot be combined")
     if (args.batch_coop or args.batch_teams is not None) and not args.batch_decode:
         ap.error("--batch-coop / --batch-teams choose how --batch-decode runs its list: they need --batch-decode")
     if args.batch_coop and args.stream_chunk:

@@ -125,6 +125,8 @@ SIGNATURES = {
     "wae_enc_conv_fwd": (c_i32, [c_vp, c_vp, c_vp, c_vp] + [c_i32] * 9 + [c_vp]),
     # x, w, bias, y, segs, nsegs, tiles, ntiles, et, in_pitch, out_pitch, Cin, Cout, k, stride, pad, relu, residual, stream
     "wae_enc_conv_fwd_list": (c_i32, [c_vp] * 5 + [c_i32, c_vp] + [c_i32] * 11 + [c_vp]),
+    # x, w, bias, y, recs, nrecs, ntiles, et, in_pitch, out_pitch, Cin, Cout, k, stride, pad, relu, residual, stream
+    "wae_enc_conv_fwd_ranges": (c_i32, [c_vp] * 5 + [c_i32] * 12 + [c_vp]),
     "wae_vq_nearest": (c_i32, [c_vp] * 6 + [c_i32] * 4 + [c_f32, c_vp]),
     "wae_upsample_stage_fwd": (c_i32, [c_vp, c_vp, c_vp] + [c_i32] * 7 + [c_vp]),
     # in, w, out, segs, nsegs, ntiles, in_pitch, out_pitch_or_rows, C, s, out_btc, Cp, dtype, stream

@@ -21,6 +21,7 @@ from . import _lib as L
 from . import decode as D
 from . import packing as P
 from .decode import DecodeSession  # noqa: F401  (re-exported)
+from .encode import EncodeSession
 from .options import two_chains
 from .step_state import InFlight, Saved
 
@@ -454,6 +455,17 @@ class WaeEngine:
         quant = quant[0]
         sl = [slice(int(o), int(o + t)) for o, t in zip(plan.q_offsets, plan.Tq)]
         return [dict(quant=quant[:, s], idx=idx[s] if want_idx else None, latents=lat[:, s] if want_latents else None) for s in sl]
+
+    def encode_session(self, want_latents: bool = False) -> EncodeSession:
+        """An encode session: encode_list for utterances whose feature frames still arrive (include/wae.h: wae_enc_conv_fwd_ranges).
+        h = sess.open(max_frames=None) joins an open utterance; sess.feed_list({h: feats (c_in, f), ...}, ended=()) appends frames
+        and returns, per utterance, the latent frames no later frame can change -- dict(quant, idx, latents | None, final, done); with
+        F frames that is max(0, (F - 13) // 4) of them while the utterance is open, all (F + 3) // 4 once it has ended (sess.end(h), or
+        its handle in `ended`).  One call is one upload of the new frames, one table upload, at most eleven range launches and one
+        quantiser call, whatever the number of utterances.  An utterance's chunks, concatenated, are bit for bit
+        encode_list([whole])[0]; the `quant` chunks are what DecodeSession.feed_list takes.  sess.drop(h) cancels, sess.close() (or
+        leaving the `with` block) frees everything.  ValueError: an engine without an encoder."""
+        return EncodeSession(self, want_latents=want_latents)
 
     def upsample_forward(self, c: torch.Tensor, out: torch.Tensor, save: Optional[Saved] = None):
         """a3: c (B,Cc,Tc) fp32 -> out (B, (Tc - 2 cin_pad) * prod(scales), Ccp) time-major compute dtype.  ConvInUpsampleNetwork

@@ -172,6 +172,13 @@ class EncListPlan(NamedTuple):
         return self.table[ly.tile_off:ly.tile_off + 2 * ly.ntiles].reshape(ly.ntiles, 2)
 
 
+def enc_list_et(Tout) -> int:
+    """The tile length of least modelled cost for one launch whose clips (or ranges) have Tout outputs each:
+    sum_i ceil(Tout_i / et) * (et + 32); ties go to the longer tile (enc_list_tables explains the model)."""
+    Tout = np.asarray(Tout, dtype=np.int64).reshape(-1)
+    return int(min(ENC_LIST_ETS, key=lambda e: (int((-(-Tout // e)).sum()) * (e + 32), -e)))
+
+
 def enc_list_tables(Tin, k: int, stride: int, pad: int, et: Optional[int] = None):
     """Tables of ONE wae_enc_conv_fwd_list launch for utterances of Tin frames packed back to back, in the caller's order:
     -> (segs (n, 4) int32, tiles (ntiles, 2) int32, et, Tout (n,)).  The offsets are the running sums of Tin and of Tout, so the
@@ -192,7 +199,7 @@ def enc_list_tables(Tin, k: int, stride: int, pad: int, et: Optional[int] = None
     if max(int(Tin.sum()), int(Tout.sum())) >= 2 ** 31:
         raise ValueError("enc_list_tables: the packed list does not fit 32-bit columns")
     if et is None:
-        et = min(ENC_LIST_ETS, key=lambda e: (int((-(-Tout // e)).sum()) * (e + 32), -e))
+        et = enc_list_et(Tout)
     if et not in ENC_LIST_ETS:
         raise ValueError(f"enc_list_tables: et {et} is not one of {ENC_LIST_ETS}")
     in_off = np.concatenate([[0], np.cumsum(Tin)[:-1]])
@@ -241,6 +248,117 @@ def encode_list_groups(Fs, max_frames: int) -> List[Tuple[int, int]]:
         tot += int(f)
     out.append((lo, len(Fs)))
     return out
+
+
+# ---- utterances whose features arrive while they are encoded (include/wae.h: wae_enc_conv_fwd_ranges; EncodeSession.open / feed)
+ENC_LAYERS = list(ENCODER_BLOCKS) + [(1, 1)]       # the blocks, then lin: (k, stride), pad k // 2
+# columns of a layer's INPUT per feature frame, as a divisor: cap frames of room are cap, cap, cap, ceil(cap / 2) and then
+# ceil(cap / 4) columns (the two stride-2 blocks); the last entry is the latents'
+ENC_ARENA_DIV = [int(np.prod([s for _, s in ENC_LAYERS[:i]])) for i in range(len(ENC_LAYERS) + 1)]
+ENC_ROOM = ENC_ARENA_DIV[-1]       # a clip's room and base are multiples of this many frames, so base / div is exact at every layer
+
+
+def _enc_final(n, ended, k: int, s: int):
+    """output columns of a block (k, s, pad k // 2) that n final input columns make final (numpy arrays or ints): while open
+    floor((n - k + p) / s) + 1, 0 where n - k + p < 0 -- output t reads inputs t s - p .. t s - p + k - 1, all below n; once ended
+    (n + 2p - k) / s + 1, every output of the clip"""
+    p = k // 2
+    n = np.asarray(n, dtype=np.int64)
+    opened = np.where(n - k + p >= 0, (n - k + p) // s + 1, 0)
+    closed = np.where(n >= 1, (n + 2 * p - k) // s + 1, 0)
+    return np.where(ended, closed, opened)
+
+
+def enc_final_rows(frames: int, ended: bool) -> List[int]:
+    """Columns of an utterance that are FINAL at the input of every layer of the encoder once `frames` feature frames have arrived:
+    entry l is the input of ENC_LAYERS[l] (entry 0 the frames themselves), the last of the 12 entries the latents."""
+    rows = [max(int(frames), 0)]
+    for k, s in ENC_LAYERS:
+        rows.append(int(_enc_final(rows[-1], bool(ended), k, s)))
+    return rows
+
+
+def enc_ready(frames: int, ended: bool) -> int:
+    """enc_final_rows' last entry in closed form: max(0, (F - 13) // 4) latent frames while the utterance is open -- latent frame q
+    needs 4 q + 17 feature frames -- and (F + 3) // 4 once it has ended."""
+    f = max(int(frames), 0)
+    return (f + 3) // 4 if ended else max(0, (f - 13) // 4)
+
+
+class EncFeedLaunch(NamedTuple):
+    """One wae_enc_conv_fwd_ranges launch of an EncFeedPlan: layer index into ENC_LAYERS, its (k, stride, pad), the tile length et,
+    nrecs records {in_off, Tin, out_col, t_lo, t_hi, tile0} and a closing one at rec_off of the table, ntiles."""
+    layer: int
+    k: int
+    stride: int
+    pad: int
+    et: int
+    nrecs: int
+    ntiles: int
+    rec_off: int
+
+
+class EncFeedPlan(NamedTuple):
+    """enc_feed_plan's answer.  launches: the layers that have a record, in order (a layer without one is not launched); table: every
+    launch's records in ONE int32 array (one upload); ready: latent frames final per clip after this feed; q_off, q_cnt: per clip,
+    the first column and the count of its NEW latents in the call's packed output of total_new columns."""
+    launches: List[EncFeedLaunch]
+    table: np.ndarray
+    ready: np.ndarray
+    q_off: np.ndarray
+    q_cnt: np.ndarray
+    total_new: int
+
+    def records(self, i: int) -> np.ndarray:
+        ln = self.launches[i]
+        return self.table[ln.rec_off:ln.rec_off + 6 * (ln.nrecs + 1)].reshape(ln.nrecs + 1, 6)
+
+
+def enc_feed_plan(clips) -> EncFeedPlan:
+    """The range records of one EncodeSession.feed_list for `clips`, each (base, frames_before, ended_before, frames, ended): base,
+    the clip's first column in layer 0's arena, in feature frames and a multiple of ENC_ROOM -- its first column at layer l's input
+    is base / ENC_ARENA_DIV[l]; frames_before / ended_before, the state its ranges last ran for; frames / ended, now.  Per layer and
+    clip, the output columns this feed (or this end) makes final -- [final before, final now) of enc_final_rows -- computed from the
+    input columns final now: while a clip is open no tap of such an output reaches Tin, the guarantee wae_enc_conv_fwd_ranges asks of
+    the host.  A block writes at base / div + t_lo of the next layer's arena; lin writes this call's new latents packed, clip after
+    clip in the order given.  Empty ranges are left out.  et per launch: enc_list_tables' cost model (enc_list_et) on the ranges' lengths.  Over
+    the feeds of a clip the ranges of a layer tile [0, Tout) exactly once.  Pure numpy: a function of the counts alone.
+    ValueError: a clip that shrinks or reopens, a base that is negative or no multiple of ENC_ROOM, columns at or above 2^31."""
+    cols = np.asarray([tuple(c) for c in clips], dtype=np.int64).reshape(-1, 5)
+    base, f0, e0, f1, e1 = (cols[:, j] for j in range(5))
+    e0, e1 = e0 != 0, e1 != 0
+    bad = (f1 < f0) | (f0 < 0) | (base < 0) | (base % ENC_ROOM != 0) | (e0 & (~e1 | (f1 != f0))) | (e1 & (f1 < 1))
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(f"enc_feed_plan: clip {i}: base {int(base[i])}, frames {int(f0[i])} -> {int(f1[i])}, "
+                         f"ended {bool(e0[i])} -> {bool(e1[i])}")
+    over = base + np.maximum(f1, 1) >= 2 ** 31
+    if over.any():
+        raise ValueError(f"enc_feed_plan: clip {int(np.argmax(over))}: its columns reach 2^31")
+    before, now = [f0], [f1]         # enc_final_rows for all clips at once
+    for k, s in ENC_LAYERS:
+        before.append(_enc_final(before[-1], e0, k, s))
+        now.append(_enc_final(now[-1], e1, k, s))
+    q_cnt = now[-1] - before[-1]
+    q_off = _running(q_cnt)
+    launches, parts, at = [], [], 0
+    for l, (k, s) in enumerate(ENC_LAYERS):
+        j = np.nonzero(now[l + 1] > before[l + 1])[0]
+        if not j.size:
+            continue
+        lo, hi = before[l + 1][j], now[l + 1][j]
+        et = enc_list_et(hi - lo)
+        per = -(-(hi - lo) // et)
+        last = l == len(ENC_LAYERS) - 1
+        out_col = q_off[j] if last else base[j] // ENC_ARENA_DIV[l + 1] + lo
+        rec = np.zeros((j.size + 1, 6), dtype=np.int64)
+        rec[:-1] = np.stack([base[j] // ENC_ARENA_DIV[l], now[l][j], out_col, lo, hi, _running(per)], axis=1)
+        rec[-1, 5] = int(per.sum())
+        launches.append(EncFeedLaunch(l, k, s, k // 2, int(et), int(j.size), int(per.sum()), at))
+        parts.append(rec.reshape(-1))
+        at += rec.size
+    table = np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, dtype=np.int32)
+    return EncFeedPlan(launches, table, now[-1], q_off, q_cnt, int(q_cnt.sum()))
 
 
 UP_ACT_KINDS = {"ReLU": 1, "LeakyReLU": 2, "Tanh": 3, "Sigmoid": 4}      # include/wae.h: wae_act_fwd

@@ -123,3 +123,8 @@ class VQVAE(ArenaModel):
         (WaeEngine.encode_list; the reference has no list form -- zero-padding to one length changes the latents at the clip ends)."""
         with torch.no_grad():
             return [r["quant"] for r in self.engine().encode_list(xs, want_idx=False)]
+
+    def encode_session(self, want_latents=False):
+        """encode for utterances whose features still arrive: WaeEngine.encode_session (open / feed_list / end), whose `quant` chunks,
+        concatenated per utterance, are bit for bit encode_list([x])[0]."""
+        return self.engine().encode_session(want_latents=want_latents)
