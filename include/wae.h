@@ -349,6 +349,47 @@ int wae_dropout_bwd(const void* acc, const void* g_next, void* out, int64_t n, u
                     void* stream);
 int64_t wae_glu_packed_bytes(const wae_glu_desc* d);
 
+/* ---- a6 over a LIST of utterances of unequal lengths (teacher-forced, inference): one launch per layer for the whole list.
+ * The activations of a list are time-major and packed along time -- x_in, x_out (rows, Rp), c_up (rows, Ccp), u_out (rows, u_stride)
+ * in `dtype` -- item i owning the rows [row_off_i, row_off_i + T_i): the operand wae_upsample_stage_fwd_list writes.
+ * Table (a DEVICE array the host builds -- packing.glu_list_plan; nothing here allocates or synchronises): nsegs records
+ * wae_glu_seg {row_off, T, zb_row, tile0} and ONE closing record whose tile0 is the tile count (the pattern of wae_ups_seg).  zb_row
+ * is the item's row of zb (B rows of zb_stride floats: d->B counts the rows of zb, d->T is not read).  The grid is ntiles; a workgroup
+ * finds its record by the workgroup-uniform binary search of the other list kernels; tile j of a record is the item's columns
+ * [j * TW, min((j + 1) * TW, T_i)), TW = wae_glu_list_tile(dtype) (128 for fp32, 256 for bf16 / fp16).
+ * The kernel is wae_glu_layer_fwd's generic kernel template (csrc/glu_fwd_kernel.hpp) compiled with the item's record in the place of
+ * (b, d->T): the causal zero fill, the row clamp of the operand requests, the valid rows of both epilogues and the residual read are
+ * taken against the item's own T_i and row_off_i.  A tap before the item's t = 0 reads zero, never the previous item's rows, and the
+ * per-column instruction sequence is the dense kernel's: every item's rows of x_out and u_out are, bit for bit, what
+ * wae_glu_layer_fwd writes for that item alone (B = 1), static-schedule instantiations included (bit-identical by their own
+ * contract).  Rows no record owns are not written.
+ * Inference only: WAE_GLU_SAVE_Z returns WAE_EUNSUPPORTED, and there is no x_conv (dropout) form; WAE_GLU_CG2 / WAE_GLU_WAVES4 are
+ * ignored (the list has the 8-wave 16-bit and the 4-wave fp32 shapes only); WAE_GLU_NO_OUT and WAE_GLU_PAIR are honoured.
+ * The kernel does not trust the table with memory: a record with T < 1, row_off < 0, row_off + T > rows, zb_row outside [0, B) or a
+ * tile count other than ceil(T / TW) is skipped whole, nothing read or written for it.  WAE_EINVAL / WAE_EUNSUPPORTED come back
+ * before any launch for the argument errors of wae_glu_layer_fwd, and WAE_EINVAL for a null table, nsegs, ntiles or rows < 1. */
+typedef struct wae_glu_seg { int32_t row_off, T, zb_row, tile0; } wae_glu_seg;
+int32_t wae_glu_list_tile(int32_t dtype);      /* the tile width the table must be built for; WAE_EINVAL for a bad dtype */
+int wae_glu_layer_fwd_list(const wae_glu_desc* d, const wae_glu_seg* segs, int32_t nsegs, int32_t ntiles, int32_t rows,
+                           const void* x_in, void* x_out, const void* c_up, void* u_out, int64_t u_stride, const float* zb,
+                           int64_t zb_stride, const void* w_packed, const float* bias_out, void* stream);
+
+/* ---- the shifted CE of a packed list, per utterance (vqwae_train.py:363-379,:764 for every item as a batch of one).
+ * The head kernels are per column: on the packed rows they run as B = 1, T = rows, and wae_head_fwd's nll (rows) then takes the last
+ * row of item i against the first id of item i + 1.  This entry, from that nll and the list's wae_glu_seg table (zb_row and tile0 are
+ * not read): zeroes nll[row_off_i + T_i - 1] in place (what the item's own forward reports at t = T_i - 1), writes
+ * nll_sum[first + i] = sum of the item's rows t < T_i - 1 and count[first + i] = T_i - 1, and out[0] = sum nll_sum / sum count (defined as 0 when the
+ * total count is 0: a list of one-sample items has no shifted target), out[1] = sum_i count[i] as a float.
+ * Deterministic: one workgroup per item adds its rows in a fixed order by a fixed tree (an item's nll_sum depends on nothing but the
+ * item's rows), and one workgroup then walks nll_sum in table order; no floating-point atomics.  Two launches on `stream`.
+ * A record with T < 1, row_off < 0 or row_off + T > rows gets nll_sum = 0, count = 0 and nothing of nll is touched for it.
+ * first: a list that runs as consecutive groups (each with its own packed arrays and table) keeps ONE nll_sum / count of all its items;
+ * the group whose items are first .. first + nsegs - 1 of the list writes those entries, and out is taken over the entries
+ * [0, first + nsegs): behind the last group it is the whole list's mean, walked in list order.  One group: first = 0.
+ * WAE_EINVAL for a null pointer, nsegs < 1, rows < 1 or first < 0. */
+int wae_nll_segments(float* nll, const wae_glu_seg* segs, int32_t nsegs, int32_t rows, int32_t first, float* nll_sum, int32_t* count,
+                     float* out, void* stream);
+
 /* ---- a7+a8+a9 skip sum + head (wavenet.py:204-214) + MaskedCrossEntropyLoss (vqwae_train.py:363-379,:764) ---
  * skips = sum_l (W_skip_l u_l + b_skip_l);  h0 = relu(skips * scale);  h1 = relu(W1 h0 + b1);  logits = W3 h1 + b3.
  * u (B,T,Ku) dtype holds all layers' gated activations, Ku = L*Hp rounded up to 64 (pad columns zero).

@@ -69,12 +69,31 @@ def build_geometry(hp) -> Geometry:
                     up_act=up_act, up_act_slope=up_slope, output_distribution=hp.output_distribution)
 
 
-def evaluate(eng, loader, device, hp):
+def evaluate(eng, loader, device, hp, packed=False):
     """The dev phase of train_loop (vqwae_train.py:829-870 with train=False: model.eval(), forward and loss only, no update):
-    -> (loss, vq_loss, perplexity) averaged over the phase's batches as the reference's per-epoch log does."""
+    -> (loss, vq_loss, perplexity) averaged over the phase's batches as the reference's per-epoch log does.
+    packed (--dev-packed; presets with max_time_steps null, whose batches are whole utterances zero-padded to the longest): every batch
+    is scored as a LIST of its utterances at their own lengths (WaeEngine.forward_list) -- no pad rows computed, and every utterance's
+    latents and conditioning are those of the utterance alone, which the padded batch's are not at the utterance ends.  The batch's
+    loss is then sum nll_sum / sum count, the cross-entropy alone: the list form returns no commitment loss and no perplexity, they
+    are reported as nan.  Class-id decoders only (NotImplementedError otherwise)."""
     tot, n = torch.zeros(3, dtype=torch.float64), 0
+    packed = packed and hp.max_time_steps is None
+    if packed and eng.g.scalar_input:
+        raise NotImplementedError("--dev-packed: the mixture losses over a list are not implemented (class-id decoders only)")
     for x, c, g, lengths in loader:
         T = x.shape[1]
+        if packed:
+            items = []
+            for i in range(x.shape[0]):
+                ni = int(lengths[i])
+                fi = ni // hp.hop_size + 2 * hp.cin_pad if eng.g.upsample_scales else ni
+                items.append(dict(x=x[i, :ni], feats=c[i, :, :fi], gid=g[i]))
+            _, ce = eng.forward_list(items, want_logits=False, want_latents=False)
+            tot += torch.stack([ce.double().cpu(), torch.tensor(float("nan"), dtype=torch.float64),
+                                torch.tensor(float("nan"), dtype=torch.float64)])
+            n += 1
+            continue
         ln = None if bool((lengths == T).all()) else lengths
         if eng.g.scalar_input:
             out = eng.forward(x.to(device), c.to(device), g.to(device), want_logits=True, train=False)
@@ -162,6 +181,9 @@ def main(argv=None):
     ap.add_argument("--dtype", default="bf16", choices=["fp32", "bf16", "fp16"])
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--max-steps", type=int)
+    ap.add_argument("--dev-packed", action="store_true",
+                    help="presets with max_time_steps null: score the dev utterances as packed lists at their own lengths "
+                         "(evaluate(packed=True)); off: zero-padded batches")
     args = ap.parse_args(argv)
 
     if args.preset:
@@ -284,7 +306,7 @@ def main(argv=None):
                             eval_model(eng, xd, cd, gd, ld, step, os.path.join(args.checkpoint_dir, "intermediate", "dev_eval"), hp,
                                        use_ema, hop)
                         break
-                dl, dvq, dperp = evaluate(eng, Prefetcher(dev_loader, device), device, hp)
+                dl, dvq, dperp = evaluate(eng, Prefetcher(dev_loader, device), device, hp, packed=args.dev_packed)
                 test_step += len(dev_loader)
                 if rank == 0:
                     print("Step {} [dev] Loss: {} vq: {} perp {}".format(step, dl, dvq, dperp))

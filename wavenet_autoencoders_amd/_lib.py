@@ -48,6 +48,10 @@ class ArSpan(ctypes.Structure):          # include/wae.h: wae_ar_span (device ar
                 ("reserved", c_i32)]
 
 
+class GluSeg(ctypes.Structure):          # include/wae.h: wae_glu_seg (device array element of wae_glu_layer_fwd_list, wae_nll_segments)
+    _fields_ = [(n, c_i32) for n in ("row_off", "T", "zb_row", "tile0")]
+
+
 class TmDesc(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in ("dtype", "B", "T", "M", "nsrc", "mode")] + [("alpha", c_f32), ("flags", c_i32)]
 
@@ -153,6 +157,12 @@ SIGNATURES = {
     "wae_bmm_f32": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, ctypes.c_float, c_vp]),
     "wae_glu_layer_fwd": (c_i32, [ctypes.POINTER(GluDesc), c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "wae_glu_layer_fwd_drop": (c_i32, [ctypes.POINTER(GluDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    # d, segs, nsegs, ntiles, rows, x_in, x_out, c_up, u_out, u_stride, zb, zb_stride, w_packed, bias_out, stream
+    "wae_glu_layer_fwd_list": (c_i32, [ctypes.POINTER(GluDesc), c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64,
+                                       c_vp, c_vp, c_vp]),
+    "wae_glu_list_tile": (c_i32, [c_i32]),
+    # nll, segs, nsegs, rows, first, nll_sum, count, out, stream
+    "wae_nll_segments": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "wae_dropout_fwd": (c_i32, [c_vp, c_vp, c_i64, ctypes.c_uint64, c_f32, c_i32, c_vp]),
     "wae_dropout_bwd": (c_i32, [c_vp, c_vp, c_vp, c_i64, ctypes.c_uint64, c_f32, c_f32, c_i32, c_vp]),
     "wae_glu_packed_bytes": (c_i64, [ctypes.POINTER(GluDesc)]),

@@ -742,6 +742,22 @@ class WaeEngine:
         tg = targets.to(torch.int32).contiguous() if targets is not None else None
         if tg is not None and tg.data_ptr() != (xi.data_ptr() if not g.scalar_input else 0):   # targets = inputs: already checked
             L.check(lib.wae_check_ids(L.ptr(tg), B * T, 0, g.O, L.ptr(self.err), L.ERR_TARGET_ID, st), "check targets")
+        self._head_fwd(ws, B, T, logits, tg, train)
+        out = dict(logits=logits, nll=None, loss=None)
+        if tg is not None:
+            ln = lengths.to(self.device, torch.int32).contiguous() if lengths is not None else None
+            L.check(lib.wae_masked_mean(L.ptr(ws["nll"]), L.ptr(ln), L.ptr(ws["loss"]), B, T, st), "masked_mean")
+            out["nll"] = ws["nll"]
+            out["loss"] = ws["loss"][0]
+        if train:
+            self.saved = sv
+        return out
+
+    def _head_fwd(self, ws, B, T, logits, tg, train):
+        """wavenet.py:204-214 (+ the shifted CE against tg) on the (B, T) rows of ws["u"]: the head this engine runs -- wide, split or
+        the one kernel; ws holds u and, where that head passes them through memory, h0 / h1, nll and lse."""
+        g, lib, st = self.g, self.lib, self.stream()
+        hd = L.HeadDesc(self.dt, B, T, g.Ku, g.Sp, g.Op, g.O, math.sqrt(1.0 / g.layers))
         if self.wide_head:
             self._head_fwd_wide(ws, B, T, logits, tg, train)
         elif self.split_head:
@@ -762,15 +778,6 @@ class WaeEngine:
                                      L.ptr(tg), L.ptr(ws["nll"]) if tg is not None else None,
                                      L.ptr(ws["lse"]) if (train and tg is not None) else None,
                                      L.ptr(ws["h0"]) if train else None, L.ptr(ws["h1"]) if train else None, st), "head")
-        out = dict(logits=logits, nll=None, loss=None)
-        if tg is not None:
-            ln = lengths.to(self.device, torch.int32).contiguous() if lengths is not None else None
-            L.check(lib.wae_masked_mean(L.ptr(ws["nll"]), L.ptr(ln), L.ptr(ws["loss"]), B, T, st), "masked_mean")
-            out["nll"] = ws["nll"]
-            out["loss"] = ws["loss"][0]
-        if train:
-            self.saved = sv
-        return out
 
     def _head_fwd_wide(self, ws, B, T, logits, tg, train):
         """wavenet.py:204-214 (+ the shifted CE of vqwae_train.py:363-379,:764) for skip widths above 256: three launches of
@@ -788,6 +795,155 @@ class WaeEngine:
         BW._tm_ce(self, B, T, g.Op, 5, [(ws["h1"].data_ptr(), g.Sp, g.Sp, 0)], self.w_hwide["w3"].data_ptr(), None, 0,
                   bh + 2 * g.Sp * 4, ce)
         self.hold("ce", logits, tg)
+
+    # ------------------------------------------------------------------ teacher-forced forward of a list
+    def decoder_forward_list(self, items, want_logits: bool = True, want_nll: bool = True, max_rows: Optional[int] = None,
+                             c_is_upsampled: bool = False):
+        """WaveNet.forward (wavenet.py:164-216) for a LIST of utterances of unequal lengths (include/wae.h: wae_glu_layer_fwd_list,
+        wae_nll_segments): logits and the shifted cross-entropy of every utterance, where decoder_forward takes one (B, T) batch, a
+        loop of batch-1 forwards is 20+ launches, a workspace and a round trip per utterance, and a zero-padded batch computes every
+        pad row of every layer.
+
+        items: a sequence of mappings with `x` ((T_i,) class ids, or floats for a scalar-input decoder), `c` ((Cc, Tc_i) latent frames,
+        upsampled here, or the (Cc, T_i) per-sample features when c_is_upsampled or the geometry has no upsampling network; None
+        without local conditioning) and `gid` (speaker id or None; all items or none).  Host or device arrays.
+        The activations are time-major and packed along time in the caller's order.  A group of the list runs as: wae_gproj_fwd with
+        one zb row per item, upsample_list into the packed c_up, ONE wae_first_conv_fwd over all rows, ONE list launch per layer on two
+        ping-pong x buffers, the head on the packed rows (it is per column: B = 1, T = rows) and wae_nll_segments.  The launches, the
+        allocations and the table uploads (one for the stack, upsample_list's own) do not grow with the number of items.
+        max_rows: the most rows (sum T_i) of one group, by default packing.FWD_LIST_MAX_ROWS = 2^20, which keeps the group's u buffer
+        (rows x Ku) at 5 GiB in bf16 / 10 GiB in fp32 at hps/vqwae.json's geometry; a longer list runs as consecutive groups (an item
+        longer than max_rows is a group of its own).  The bytes of every item are the same for every grouping and every order.
+        Returns (results, loss): in the caller's order a list of dict(logits (O, T_i) fp32 | None, nll (T_i,) fp32 | None,
+        nll_sum, count) -- views of the group's arrays; nll[t] is taken against x[t + 1], 0 at t = T_i - 1, nll_sum its sum and
+        count = T_i - 1 -- and loss = sum nll_sum / sum count over the list (vqwae_train.py:379 with the list as one batch; None
+        without want_nll).  logits and nll are, bit for bit, decoder_forward of that utterance alone.
+        Scalar-input decoders get logits (the distribution's parameters); with want_nll they raise NotImplementedError (the mixture
+        losses over a list are not built).  ValueError, before any launch: an empty list, an item with T_i < 1, gid on some items
+        only, a c that does not upsample to T_i."""
+        g, who = self.g, "decoder_forward_list"
+        items = list(items)
+        if not items:
+            raise ValueError(f"{who}: an empty list")
+        if g.scalar_input and want_nll:
+            raise NotImplementedError(f"{who}: the mixture losses over a list are not implemented; pass want_nll=False for the "
+                                      "distribution parameters, or score one utterance at a time")
+        Ts = []
+        for i, it in enumerate(items):
+            shape = tuple(getattr(it["x"], "shape", ()))
+            if len(shape) != 1 or shape[0] < 1:
+                raise ValueError(f"{who}: item {i}: x has shape {shape}; every item is (T,) with T >= 1")
+            Ts.append(int(shape[0]))
+        has_gid = [it.get("gid") is not None for it in items]
+        if any(has_gid) and not all(has_gid):
+            raise ValueError(f"{who}: gid on all items or on none")
+        if g.Ccp:
+            if any(it.get("c") is None for it in items):
+                raise ValueError(f"{who}: model has local conditioning but an item has no c")
+            Tcs = [int(it["c"].shape[-1]) for it in items]
+            Tup = P.upsample_list_plan(Tcs, g, None, c_is_upsampled).Ts       # refuses what upsample_list refuses; not launched
+            for i, (a, b) in enumerate(zip(Tup, Ts)):
+                if int(a) != b:
+                    raise ValueError(f"{who}: item {i}: c {tuple(items[i]['c'].shape)} gives {int(a)} rows != T = {b}")
+        cap = P.FWD_LIST_MAX_ROWS if max_rows is None else int(max_rows)
+        if cap < 1:
+            raise ValueError(f"{who}: max_rows {cap} < 1")
+        if self.weights_dirty:
+            self.prepare_weights()
+        n = len(items)
+        sums = torch.zeros(n, dtype=torch.float32, device=self.device) if want_nll else None
+        counts = torch.zeros(n, dtype=torch.int32, device=self.device) if want_nll else None
+        loss = torch.zeros(2, dtype=torch.float32, device=self.device) if want_nll else None
+        out, keep = [], []
+        for lo, hi in P.forward_list_groups(Ts, cap):
+            out += self._forward_list_group(items[lo:hi], Ts[lo:hi], lo, want_logits, want_nll, c_is_upsampled, sums, counts, loss, keep)
+        self.hold("forward_list", *keep)       # the tables and operands passed by raw pointer, until the next list
+        return out, (loss[0] if want_nll else None)
+
+    def _forward_list_group(self, items, Ts, first, want_logits, want_nll, c_is_upsampled, sums, counts, loss, keep):
+        """one group of decoder_forward_list: its packed arrays, one table, the launches; -> the items' dicts"""
+        g, lib, st, dev, td = self.g, self.lib, self.stream(), self.device, self.tdtype
+        n = len(items)
+        plan = P.glu_list_plan(Ts, P.GLU_LIST_TILES[self.dt])
+        rows = plan.rows
+        table = torch.from_numpy(plan.table).to(dev)
+        gid32 = None
+        if items[0].get("gid") is not None:
+            gid32 = torch.as_tensor(np.asarray([int(it["gid"]) for it in items], dtype=np.int32)).to(dev)
+        zb = self._ar_speaker_rows(n, gid32)
+        c_up = None
+        if g.Ccp:
+            c_up, _ = self.upsample_list([it["c"] for it in items], c_is_upsampled=c_is_upsampled)
+        self.join(self.flight.take_pack_done())
+        # the inputs side by side in order: the host items in one upload
+        xdt = torch.float32 if g.scalar_input else torch.int32
+        if all(not (torch.is_tensor(it["x"]) and it["x"].is_cuda) for it in items):
+            xi = torch.cat([torch.as_tensor(it["x"]).to(xdt) for it in items]).to(dev)
+        else:
+            xi = torch.cat([torch.as_tensor(it["x"]).to(dev, xdt) for it in items])
+        xi = xi.contiguous()
+        xs = [torch.empty(rows, g.Rp, dtype=td, device=dev) for _ in range(2)]
+        u = torch.empty(rows, g.Ku, dtype=td, device=dev)       # all layers' gated activations
+        if g.Ku > g.layers * g.Hp:
+            u[:, g.layers * g.Hp:].zero_()                       # the pad columns the head's skip contraction reads
+        if g.scalar_input:
+            L.check(lib.wae_first_conv_fwd(None, L.ptr(xi), L.ptr(self.first_tab), L.ptr(self.first_bias), L.ptr(xs[0]), rows, g.Rp, 1,
+                                           self.dt, None, st), "first_conv")
+        else:
+            L.check(lib.wae_first_conv_fwd(L.ptr(xi), None, L.ptr(self.first_tab), L.ptr(self.first_bias), L.ptr(xs[0]), rows, g.Rp, g.O,
+                                           self.dt, L.ptr(self.err), st), "first_conv")
+        es = self.w_glu.element_size()
+        for i, dil in enumerate(g.dilations):
+            last = i == g.layers - 1
+            flags = (L.GLU_NO_OUT if last else 0) | self.glu_flags | (L.GLU_PAIR if self.glu_pair == "inference" else 0)
+            dd = L.GluDesc(self.dt, n, 0, g.Rp, g.Ccp, g.Hp, g.k, dil, flags)
+            L.check(lib.wae_glu_layer_fwd_list(ctypes.byref(dd), L.ptr(table), n, plan.ntiles, rows, L.ptr(xs[i % 2]),
+                                               None if last else L.ptr(xs[(i + 1) % 2]), L.ptr(c_up),
+                                               ctypes.c_void_p(u.data_ptr() + i * g.Hp * es), g.Ku,
+                                               ctypes.c_void_p(zb.data_ptr() + i * 2 * g.Hp * 4), g.layers * 2 * g.Hp,
+                                               ctypes.c_void_p(self.w_glu.data_ptr() + i * self.glu_elems * es),
+                                               ctypes.c_void_p(self.b_glu.data_ptr() + i * g.Rp * 4), st), f"glu layer {i} (list)")
+        # the head is per column: the packed rows as one clip of `rows` steps; its CE shift crosses the items' ends, wae_nll_segments
+        # puts that right
+        ws = dict(u=u)
+        if self.wide_head or self.split_head:
+            ws["h0"] = torch.empty(rows, g.Sp, dtype=td, device=dev)
+        if self.wide_head:
+            ws["h1"] = torch.empty(rows, g.Sp, dtype=td, device=dev)
+        logits = torch.empty(1, g.O, rows, dtype=torch.float32, device=dev) if want_logits else None
+        nll = None
+        if want_nll:
+            nll = ws["nll"] = torch.empty(rows, dtype=torch.float32, device=dev)
+        self._head_fwd(ws, 1, rows, logits, xi if want_nll else None, False)
+        if want_nll:
+            L.check(lib.wae_nll_segments(L.ptr(nll), L.ptr(table), n, rows, first, L.ptr(sums), L.ptr(counts), L.ptr(loss), st),
+                    "nll_segments")
+        # the small operands passed by raw pointer stay until the next list; the group's activations (x, u, c_up, h0 / h1: gigabytes)
+        # go back to the allocator here -- every launch above is on the current stream, and so is whatever takes their memory next
+        keep += [table, zb, xi]
+        res = []
+        for i, (o, T) in enumerate(zip(plan.offsets, Ts)):
+            o = int(o)
+            res.append(dict(logits=logits[0, :, o:o + T] if want_logits else None, nll=nll[o:o + T] if want_nll else None,
+                            nll_sum=sums[first + i] if want_nll else None, count=counts[first + i] if want_nll else None))
+        return res
+
+    def forward_list(self, items, want_logits: bool = True, want_nll: bool = True, max_rows: Optional[int] = None,
+                     want_latents: bool = True):
+        """VQVAE.forward (vqvae_model.py:66-72) in eval mode for a LIST of utterances of unequal lengths: encode_list, then
+        decoder_forward_list on the quantised latents.  items: mappings with `x` ((T_i,) class ids), `feats` ((c_in, F_i) features)
+        and `gid`.  Returns (results, loss) as decoder_forward_list, every dict with quant (Cc, Tq_i), idx (Tq_i,) and latents
+        (Cc, Tq_i) | None (want_latents=False) besides.  Every item is, bit for bit, forward() of that utterance alone -- which a
+        zero-padded batch is not at the utterance ends (encode_list, upsample_list).  ValueError as the two list calls."""
+        items = list(items)
+        if not items:
+            raise ValueError("forward_list: an empty list")
+        enc = self.encode_list([it["feats"] for it in items], want_latents=want_latents)
+        dec, loss = self.decoder_forward_list([dict(x=it["x"], c=e["quant"], gid=it.get("gid")) for it, e in zip(items, enc)],
+                                              want_logits=want_logits, want_nll=want_nll, max_rows=max_rows)
+        for d, e in zip(dec, enc):
+            d.update(quant=e["quant"], idx=e["idx"], latents=e["latents"])
+        return dec, loss
 
     # ------------------------------------------------------------------ autoregressive synthesis
     def _prepare_ar(self):

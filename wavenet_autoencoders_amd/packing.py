@@ -517,6 +517,92 @@ def upsample_list_groups(Ts, max_samples: int = UPS_LIST_MAX_SAMPLES) -> List[Tu
     return encode_list_groups(Ts, int(max_samples))
 
 
+# ---- the teacher-forced gated stack over a list (include/wae.h: wae_glu_layer_fwd_list, wae_nll_segments)
+GLU_LIST_TILES = {0: 128, 1: 256, 2: 256}      # dtype (WAE_F32, WAE_BF16, WAE_F16) -> time columns of a tile: wae_glu_list_tile()
+# Default cap on the rows (sum T_i) of one group of WaeEngine.decoder_forward_list.  The largest array of a group is u, all layers'
+# gated activations, (rows, Ku): at hps/vqwae.json's geometry (20 layers of Hp 128: Ku 2560) 2^20 rows keep it at 5 GiB in bf16 /
+# fp16 and 10 GiB in fp32; the (O 256, rows) fp32 logits are 1 GiB beside it.  The reference's utterances are 16 000 .. 240 000
+# samples, so a group holds four or more of them.
+FWD_LIST_MAX_ROWS = 1 << 20
+
+
+class GluListPlan(NamedTuple):
+    """glu_list_plan's answer.  table: (n + 1, 4) int32 records {row_off, T, zb_row, tile0} (include/wae.h: wae_glu_seg), the last one
+    closing (tile0 = ntiles); ntiles: the grid of a layer launch; offsets: the first row of every item; rows: the packed rows the
+    records reach (max offsets + Ts); Ts: the lengths."""
+    table: np.ndarray
+    ntiles: int
+    offsets: np.ndarray
+    rows: int
+    Ts: np.ndarray
+
+
+def glu_list_plan(Ts, tile: int, offsets=None, zb_rows=None) -> GluListPlan:
+    """The table of one list launch of the gated layer for items of Ts steps: item i owns the rows [offsets_i, offsets_i + T_i) of the
+    packed time-major arrays (offsets None: running sums, the caller's order -- the rows upsample_list writes) and the tiles
+    tile0_i + 0, 1, ..., tile j being its columns [j * tile, min((j + 1) * tile, T_i)); zb_rows: every item's row of zb (None: its
+    index).  tile: WaeEngine's dtype decides it (GLU_LIST_TILES / wae_glu_list_tile).  Pure numpy, no loop per item.
+    ValueError: an empty list, an item with T < 1 (with its index), a tile < 1, rows at or above 2^31."""
+    Ts = np.asarray(Ts, dtype=np.int64).reshape(-1)
+    if Ts.size < 1:
+        raise ValueError("glu_list_plan: an empty list")
+    if int(tile) < 1:
+        raise ValueError(f"glu_list_plan: tile {tile} < 1")
+    if int(Ts.min()) < 1:
+        raise ValueError(f"glu_list_plan: item {int(np.argmax(Ts < 1))} has T < 1")
+    offs = _running(Ts) if offsets is None else np.asarray(offsets, dtype=np.int64).reshape(-1)
+    zrow = np.arange(Ts.size, dtype=np.int64) if zb_rows is None else np.asarray(zb_rows, dtype=np.int64).reshape(-1)
+    if offs.size != Ts.size or zrow.size != Ts.size or int(offs.min()) < 0 or int(zrow.min()) < 0 or int((offs + Ts).max()) >= 2 ** 31:
+        raise ValueError("glu_list_plan: one row offset in [0, 2^31) and one zb row >= 0 per item")
+    per = -(-Ts // int(tile))
+    rec = np.zeros((Ts.size + 1, 4), dtype=np.int64)
+    rec[:-1, 0], rec[:-1, 1], rec[:-1, 2], rec[:-1, 3] = offs, Ts, zrow, _running(per)
+    rec[-1, 3] = int(per.sum())
+    return GluListPlan(rec.astype(np.int32), int(per.sum()), offs, int((offs + Ts).max()), Ts)
+
+
+def forward_list_groups(Ts, max_rows: int = FWD_LIST_MAX_ROWS) -> List[Tuple[int, int]]:
+    """Consecutive groups [lo, hi) of a list of Ts steps whose sums stay within max_rows; an item longer than max_rows is a group of
+    its own (an item is never split).  The default keeps a group's u buffer at the size FWD_LIST_MAX_ROWS states."""
+    if int(max_rows) < 1:
+        raise ValueError(f"forward_list_groups: max_rows {int(max_rows)} < 1")
+    return encode_list_groups(Ts, int(max_rows))
+
+
+def nll_segments_restated(nll, table):
+    """numpy restatement of wae_nll_segments (csrc/nll_list.hip) on a COPY of nll (rows,) fp32 and glu_list_plan's table (its closing
+    record is not an item): thread j of 256 adds the item's rows j, j + 256, ... below T - 1 in fp64, the 64 lanes of a wave meet by a xor
+    butterfly, the four waves add in order; the item's last row becomes 0; the list's mean walks nll_sum in table order and is 0 for
+    a total count of 0.  -> (nll, nll_sum (n,) fp32, count (n,) int32, loss fp32)."""
+    nll = np.array(nll, dtype=np.float32).reshape(-1)
+    recs = np.asarray(table).reshape(-1, 4)[:-1]         # without the closing record
+    sums, cnts = np.zeros(len(recs), dtype=np.float32), np.zeros(len(recs), dtype=np.int32)
+    for i, (off, T, _, _) in enumerate(recs):
+        if T < 1 or off < 0 or off + T > nll.size:
+            continue
+        lane = np.zeros(256, dtype=np.float64)
+        body = nll[off:off + T - 1].astype(np.float64)
+        full = (len(body) // 256) * 256
+        for r in body[:full].reshape(-1, 256):           # one row of the strided walk at a time: every thread's own order
+            lane += r
+        lane[:len(body) - full] += body[full:]
+        w = lane.reshape(4, 64)
+        o = 32
+        while o:                                         # s += shfl_xor(s, o): every lane ends with the same tree's sum
+            w = w + w[:, np.arange(64) ^ o]
+            o >>= 1
+        tot = 0.0
+        for k in range(4):
+            tot += w[k, 0]
+        sums[i], cnts[i] = np.float32(tot), T - 1
+        nll[off + T - 1] = 0.0
+    tot = cnt = 0.0
+    for s, c in zip(sums, cnts):
+        tot += float(s)
+        cnt += float(c)
+    return nll, sums, cnts, np.float32(tot / cnt) if cnt > 0 else np.float32(0.0)
+
+
 # ---- clips whose conditioning arrives while they decode (include/wae.h: wae_upsample_stage_fwd_ranges; DecodeSession.open / feed)
 def feed_final_rows(frames: int, scales, ended: bool) -> List[int]:
     """Rows of a clip that are FINAL at every level of the upsampling chain once `frames` latent frames have arrived: entry 0 is the

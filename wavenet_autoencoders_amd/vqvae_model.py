@@ -124,6 +124,17 @@ class VQVAE(ArenaModel):
         with torch.no_grad():
             return [r["quant"] for r in self.engine().encode_list(xs, want_idx=False)]
 
+    def forward_list(self, items, want_nll=None):
+        """forward (no gradients, eval) for a list of utterances of unequal lengths: items, a sequence of mappings with `x` ((T_i,)
+        class ids), `c` ((c_in, F_i) features) and `g` (a speaker id or None) -> (results, loss): per utterance dict(logits
+        (out_channels, T_i), nll (T_i,) | None, nll_sum, count, quant, idx, latents) and the list's masked mean of the shifted
+        cross-entropy.  Every utterance is bit for bit its own forward(x[None], c[None], g[None]) -- which a zero-padded batch is not
+        at the utterance ends (WaeEngine.forward_list).  want_nll: by default on for class-id models."""
+        want_nll = (not self.scalar_input) if want_nll is None else bool(want_nll)
+        its = [dict(x=it["x"], feats=it["c"], gid=it.get("g")) for it in items]
+        with torch.no_grad():
+            return self.engine().forward_list(its, want_nll=want_nll)
+
     def encode_session(self, want_latents=False):
         """encode for utterances whose features still arrive: WaeEngine.encode_session (open / feed_list / end), whose `quant` chunks,
         concatenated per utterance, are bit for bit encode_list([x])[0]."""

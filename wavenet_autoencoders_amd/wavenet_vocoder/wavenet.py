@@ -194,6 +194,17 @@ class WaveNet(ArenaModel):
         y = _DecoderFn.apply(self, ids, c, g, c_is_up, train, *params)
         return softmax_bct(y) if softmax else y
 
+    def forward_list(self, items, want_nll=None):
+        """forward (no gradients, eval) for a list of utterances of unequal lengths: items, a sequence of mappings with `x` ((T_i,)
+        class ids or scalars), `c` ((Cc, Tc_i) or None) and `g` (a speaker id or None) -> (results, loss): per utterance
+        dict(logits (out_channels, T_i), nll (T_i,) | None, nll_sum, count) and the list's masked mean of the shifted cross-entropy,
+        each bit for bit forward(x[None], c[None], g[None]) of that utterance alone, from one launch per layer for the whole list
+        (WaeEngine.decoder_forward_list; the reference has no list form).  want_nll: by default on for class-id models."""
+        want_nll = (not self.scalar_input) if want_nll is None else bool(want_nll)
+        its = [dict(x=it["x"], c=it.get("c"), gid=it.get("g")) for it in items]
+        with torch.no_grad():
+            return self.engine().decoder_forward_list(its, want_nll=want_nll, c_is_upsampled=not bool(self.geom.upsample_scales))
+
     def incremental_forward(self, initial_input=None, c=None, g=None, T=100, test_inputs=None, tqdm=lambda x: x,
                             softmax=True, quantize=True, log_scale_min=-50.0):
         """wavenet.py:218-346 as one persistent kernel launch: sampling (quantize=True) -> one-hot (B, C, T); quantize=False ->
