@@ -134,7 +134,8 @@ int wae_enc_conv_fwd(const float* x, const float* w, const float* bias, float* y
  * pitches, names no segment or contradicts the Tout formula is skipped by the kernel: nothing is read or written for it.
  * The quantiser needs no list entry: wae_vq_nearest / wae_vq_slice with B = 1, Dtot = Cc, Tq = sum of Tq_i on the packed latents
  * (Cc, sum Tq_i) -- the row of (b = 0, t) is the packed column t; idx and quant are per row (so per utterance, bit for bit the
- * batch-1 call's), stats are the LIST's aggregate loss and perplexity. */
+ * batch-1 call's), stats are the LIST's aggregate loss and perplexity; per utterance, and for the list in a fixed order, they come
+ * from wae_vq_stats_segments below. */
 typedef struct wae_seg { int32_t in_off, Tin, out_off, Tout; } wae_seg;
 int wae_enc_conv_fwd_list(const float* x, const float* w, const float* bias, float* y, const wae_seg* segs, int32_t nsegs,
                           const int32_t* tiles, int32_t ntiles, int32_t et, int32_t in_pitch, int32_t out_pitch, int32_t Cin,
@@ -192,6 +193,33 @@ int wae_vq_ema_update(const float* lat, const int64_t* idx, const int32_t* hist,
 int wae_vq_slice_bwd(const float* lat, const float* quant, const int64_t* idx, const float* dquant, float* dlat,
                      float* demb, int32_t B, int32_t Dtot, int32_t d0, int32_t D, int32_t Tq, float c_lat, float c_emb,
                      void* stream);
+
+/* ---- the quantiser's statistics of a packed list, per utterance and for the list as one batch (vector_quantization.py:41-47 for
+ * every item as a batch of one; csrc/vq_list.hip).  wae_vq_nearest on the packed latents of a list (B = 1, Tq = pitch) gives idx and
+ * quant per frame; its stats are the aggregate of whatever was packed, and its squared error a chain of float atomics in arrival order.
+ * lat, quant: channel-major (D, pitch) fp32; idx: (pitch) int64; segs: a device array of nsegs records wae_vq_seg {q_off, Tq}, item
+ * i owning the columns [q_off, q_off + Tq).  Written for this call's items, entries first .. first + nsegs - 1 of the list's arrays:
+ *   hist[i] (K int32): the counts of the item's idx -- LDS integer atomics, exact; an idx outside [0, K) is counted nowhere;
+ *   sqerr[i]: sum over the item's columns and every d < D of (quant - lat)^2, each difference and the sum in fp64 in a fixed order
+ *     (thread j of 256 takes the columns j, j + 256, ..., the channels of a column in turn; a xor butterfly over the 64 lanes, the
+ *     four waves in wave order), rounded to fp32 once;
+ *   item_stats[i] (2 floats): [0] = c_loss * (sqerr[i] / ((float)Tq * (float)D)), the item's vq_loss for c_loss = beta + 1;
+ *     [1] = the perplexity of the item's counts, bit for bit the stats[1] of the search entry above, mode 1, on the item alone.
+ * out (4 floats), over the entries [0, first + nsegs) in list order: [0] = c_loss * sum sqerr / (D * sum Tq), [1] = the perplexity of
+ * the counts added per code with N = sum Tq (what the dense search reports for the packed latents as one clip), [2] = sum Tq,
+ * [3] = sum sqerr; the sums of sqerr in fp64.  Tq of an entry is read back as the sum of its counts (the entry keeps no array of
+ * them between groups: equal to Tq for indices inside the codebook); all four are 0 when no entry has a frame.
+ * Deterministic: no floating-point atomics; an item's numbers depend on the item's columns alone, the list's on the items' numbers
+ * and their order.  Two launches on `stream`; nothing allocates or synchronises.
+ * A record with Tq < 1, q_off < 0 or q_off + Tq > pitch gets sqerr = 0, K zero counts and zero stats; nothing is read for it.
+ * first: a list that runs as consecutive groups (each with its own packed arrays and table) keeps ONE sqerr / hist / item_stats of
+ * all its items; one group: first = 0.
+ * WAE_EINVAL before any launch for a null pointer, nsegs < 1, D < 1, K < 1, pitch < 1 or first < 0; WAE_EUNSUPPORTED for K > 8192
+ * (the counts of an item live in 32 KiB of LDS). */
+typedef struct wae_vq_seg { int32_t q_off, Tq; } wae_vq_seg;
+int wae_vq_stats_segments(const float* lat, const float* quant, const int64_t* idx, const wae_vq_seg* segs, int32_t nsegs, int32_t D,
+                          int32_t pitch, int32_t K, float c_loss, int32_t first, float* sqerr, int32_t* hist, float* item_stats,
+                          float* out, void* stream);
 
 /* ---- a3 one upsample stage (upsample.py:19-21 stretch + :39-46 FIR) ------------------------------------
  * in (B,C,Tin) fp32 -> nearest-stretch by s, FIR w[2s+1] zero-padded.  If out_btc != 0 the result is written

@@ -2,9 +2,12 @@
 """What the per-utterance encode loop costs and what list encoding (WaeEngine.encode_list) saves: the encoder and quantiser of
 hps/vqwae.json (39 MFCC channels, encoder_hid 256, 64 latent channels, 256 codes; fp32) on lists of unequal lengths.
 
-usage: bench_encode_list.py [--sizes 1,16,256,2048] [--repeats 5] [--min-frames 100] [--max-frames 1500]
+usage: bench_encode_list.py [--sizes 1,16,256,2048] [--repeats 5] [--min-frames 100] [--max-frames 1500] [--stats]
     --sizes     utterances per list, one measurement each
     --repeats   timed repeats per measurement (at least 5); the median is reported with the fastest and the slowest
+    --stats     measure what the quantiser's statistics cost instead (WaeEngine.encode_list_stats; default sizes 16,256,2048): per list
+                size, encode_list against encode_list_stats, and the quantiser calls of the list's groups (wae_vq_nearest on the packed
+                latents) against the statistics calls behind them (wae_vq_stats_segments), each pair alternating in this one process
 Frame counts are drawn with numpy.random.default_rng(1234), uniform in [--min-frames, --max-frames]: the ZeroSpeech length distribution
 is not available to this tool, so the lengths are a stand-in, not the corpus.
 Per list size, two pairs, each in this one process, warmed, the two sides alternating repeat by repeat:
@@ -52,15 +55,64 @@ def pair(name, a, b, repeats):
     return {k: (statistics.median(v), min(v), max(v)) for k, v in (("loop", ta), ("list", tb))}
 
 
+def stats_cost(eng, dev, Fs, repeats):
+    """encode_list against encode_list_stats on the device-resident list `dev`, and the groups' quantiser calls against the statistics
+    calls behind them, both pairs alternating; prints one line and returns the record"""
+    from wavenet_autoencoders_amd import _lib as L
+    from wavenet_autoencoders_amd import packing as P
+    g, n = eng.g, len(dev)
+    plain = eng.encode_list(dev, want_latents=True)
+    full = eng.encode_list_stats(dev)
+    same = all(torch.equal(a["quant"], b["quant"]) and torch.equal(a["idx"], b["idx"]) for a, b in zip(plain, full))
+    same = same and all(torch.equal(b["hist"].long(), torch.bincount(b["idx"], minlength=g.K)) for b in full[:16])
+    whole = pair("whole", lambda: eng.encode_list(dev), lambda: eng.encode_list_stats(dev), repeats)
+    # the two calls alone, on the groups' packed latents as _encode_group holds them
+    groups = []
+    for lo, hi in P.encode_list_groups([int(F) for F in Fs], P.ENC_LIST_MAX_FRAMES):
+        lat = torch.cat([r["latents"] for r in plain[lo:hi]], dim=1).contiguous()
+        Tq = [int(r["latents"].shape[1]) for r in plain[lo:hi]]
+        quant, idx, _ = eng.vq_forward(lat[None])
+        segs = torch.from_numpy(P.vq_seg_table(np.cumsum([0] + Tq[:-1]), Tq)).cuda()
+        groups.append((lo, hi - lo, lat, quant[0].contiguous(), idx, segs))
+    sq = torch.zeros(n, device="cuda")
+    hist = torch.zeros(n, g.K, dtype=torch.int32, device="cuda")
+    item = torch.zeros(n, 2, device="cuda")
+    out = torch.zeros(4, device="cuda")
+
+    def nearest():
+        for _, _, lat, _, _, _ in groups:
+            eng.vq_forward(lat[None])
+
+    def stats():
+        for lo, m, lat, quant, idx, segs in groups:
+            L.check(eng.lib.wae_vq_stats_segments(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(segs), m, g.Cc, lat.shape[1], g.K, 1.25, lo,
+                                                  L.ptr(sq), L.ptr(hist), L.ptr(item), L.ptr(out), eng.stream()), "vq_stats_segments")
+
+    calls = pair("calls", nearest, stats, repeats)
+    a, b, c, d = whole["loop"], whole["list"], calls["loop"], calls["list"]
+    frames = int(np.sum(Fs))
+    print(f"{n:5d} utterances, {frames:8d} frames, {len(groups):3d} groups: encode_list {a[0] * 1e3:9.3f} ms ({a[1] * 1e3:.3f} .. {a[2] * 1e3:.3f}), "
+          f"encode_list_stats {b[0] * 1e3:9.3f} ms ({b[1] * 1e3:.3f} .. {b[2] * 1e3:.3f}), difference {(b[0] - a[0]) * 1e3:8.3f} ms "
+          f"({(b[0] / a[0] - 1) * 100:+.1f} %); alone: wae_vq_nearest calls {c[0] * 1e3:8.3f} ms ({c[1] * 1e3:.3f} .. {c[2] * 1e3:.3f}), "
+          f"wae_vq_stats_segments calls {d[0] * 1e3:8.3f} ms ({d[1] * 1e3:.3f} .. {d[2] * 1e3:.3f}), stats / nearest {d[0] / c[0]:5.2f}; "
+          f"outputs unchanged, histograms exact: {same}", flush=True)
+    return dict(utterances=n, frames=frames, groups=len(groups), kind="stats", encode_list_ms=[t * 1e3 for t in a],
+                encode_list_stats_ms=[t * 1e3 for t in b], vq_nearest_calls_ms=[t * 1e3 for t in c],
+                vq_stats_calls_ms=[t * 1e3 for t in d], same=bool(same))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--sizes", default="1,16,256,2048")
+    ap.add_argument("--sizes")
+    ap.add_argument("--stats", action="store_true")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--min-frames", type=int, default=100)
     ap.add_argument("--max-frames", type=int, default=1500)
     args = ap.parse_args(argv)
     if args.repeats < 5:
         ap.error("--repeats: at least 5")
+    if args.sizes is None:
+        args.sizes = "16,256,2048" if args.stats else "1,16,256,2048"
     eng = WaeEngine(Geometry.from_cfg(CFG), dtype="fp32")
     eng.load_state_dict(O.make_state_dict(dict(CFG), salt=7))
     eng.prepare_weights()
@@ -73,6 +125,9 @@ def main(argv=None):
         Fs = rng.integers(args.min_frames, args.max_frames + 1, n)
         host = [(torch.randn(int(F), CFG["c_in"], generator=gen) * 1.7).numpy() for F in Fs]          # (N_i, c_in), as the .npy files
         dev = [torch.from_numpy(np.ascontiguousarray(h.T)).cuda() for h in host]                      # (c_in, F_i)
+        if args.stats:
+            record["runs"].append(stats_cost(eng, dev, Fs, args.repeats))
+            continue
 
         def loop_dev():
             return [eng.vq_forward(eng.encoder_forward(x[None]))[0] for x in dev]

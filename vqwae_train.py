@@ -69,18 +69,20 @@ def build_geometry(hp) -> Geometry:
                     up_act=up_act, up_act_slope=up_slope, output_distribution=hp.output_distribution)
 
 
-def evaluate(eng, loader, device, hp, packed=False):
+def evaluate(eng, loader, device, hp, packed=False, packed_total=False):
     """The dev phase of train_loop (vqwae_train.py:829-870 with train=False: model.eval(), forward and loss only, no update):
     -> (loss, vq_loss, perplexity) averaged over the phase's batches as the reference's per-epoch log does.
     packed (--dev-packed; presets with max_time_steps null, whose batches are whole utterances zero-padded to the longest): every batch
-    is scored as a LIST of its utterances at their own lengths (WaeEngine.forward_list) -- no pad rows computed, and every utterance's
+    is scored as a LIST of its utterances at their own lengths (WaeEngine.score_list) -- no pad rows computed, and every utterance's
     latents and conditioning are those of the utterance alone, which the padded batch's are not at the utterance ends.  The batch's
-    loss is then sum nll_sum / sum count, the cross-entropy alone: the list form returns no commitment loss and no perplexity, they
-    are reported as nan.  Class-id decoders only (NotImplementedError otherwise)."""
+    numbers are those of the list as one batch: ce = sum nll_sum / sum count (the cross-entropy, or the mixture loss of a "raw" /
+    "mulaw" model with hp.quantize_channels and hp.log_scale_min), vq_loss = 1.25 sum sqerr / (Cc sum Tq) and the perplexity of the
+    code counts added over the utterances.
+    packed_total (what --dev-packed passes): the first number is ce + vq_loss, exactly what the padded branch adds, so that the two
+    dev curves compare; without it the first number stays the cross-entropy alone, the value this form has returned since it
+    exists, and vq_loss and the perplexity stand beside it."""
     tot, n = torch.zeros(3, dtype=torch.float64), 0
     packed = packed and hp.max_time_steps is None
-    if packed and eng.g.scalar_input:
-        raise NotImplementedError("--dev-packed: the mixture losses over a list are not implemented (class-id decoders only)")
     for x, c, g, lengths in loader:
         T = x.shape[1]
         if packed:
@@ -89,9 +91,8 @@ def evaluate(eng, loader, device, hp, packed=False):
                 ni = int(lengths[i])
                 fi = ni // hp.hop_size + 2 * hp.cin_pad if eng.g.upsample_scales else ni
                 items.append(dict(x=x[i, :ni], feats=c[i, :, :fi], gid=g[i]))
-            _, ce = eng.forward_list(items, want_logits=False, want_latents=False)
-            tot += torch.stack([ce.double().cpu(), torch.tensor(float("nan"), dtype=torch.float64),
-                                torch.tensor(float("nan"), dtype=torch.float64)])
+            _, t = eng.score_list(items, quantize_channels=hp.quantize_channels, log_scale_min=hp.log_scale_min)
+            tot += torch.stack([t["loss"] if packed_total else t["ce"], t["vq_loss"], t["perp"]]).double().cpu()
             n += 1
             continue
         ln = None if bool((lengths == T).all()) else lengths
@@ -183,7 +184,8 @@ def main(argv=None):
     ap.add_argument("--max-steps", type=int)
     ap.add_argument("--dev-packed", action="store_true",
                     help="presets with max_time_steps null: score the dev utterances as packed lists at their own lengths "
-                         "(evaluate(packed=True)); off: zero-padded batches")
+                         "(evaluate(packed=True, packed_total=True): loss = NLL + commitment loss, commitment loss and perplexity "
+                         "of every batch as one list, for class-id and scalar-input models); off: zero-padded batches")
     args = ap.parse_args(argv)
 
     if args.preset:
@@ -306,7 +308,8 @@ def main(argv=None):
                             eval_model(eng, xd, cd, gd, ld, step, os.path.join(args.checkpoint_dir, "intermediate", "dev_eval"), hp,
                                        use_ema, hop)
                         break
-                dl, dvq, dperp = evaluate(eng, Prefetcher(dev_loader, device), device, hp, packed=args.dev_packed)
+                dl, dvq, dperp = evaluate(eng, Prefetcher(dev_loader, device), device, hp, packed=args.dev_packed,
+                                          packed_total=args.dev_packed)
                 test_step += len(dev_loader)
                 if rank == 0:
                     print("Step {} [dev] Loss: {} vq: {} perp {}".format(step, dl, dvq, dperp))

@@ -52,6 +52,10 @@ class GluSeg(ctypes.Structure):          # include/wae.h: wae_glu_seg (device ar
     _fields_ = [(n, c_i32) for n in ("row_off", "T", "zb_row", "tile0")]
 
 
+class VqSeg(ctypes.Structure):           # include/wae.h: wae_vq_seg (device array element of wae_vq_stats_segments)
+    _fields_ = [(n, c_i32) for n in ("q_off", "Tq")]
+
+
 class TmDesc(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in ("dtype", "B", "T", "M", "nsrc", "mode")] + [("alpha", c_f32), ("flags", c_i32)]
 
@@ -132,6 +136,8 @@ SIGNATURES = {
     # x, w, bias, y, recs, nrecs, ntiles, et, in_pitch, out_pitch, Cin, Cout, k, stride, pad, relu, residual, stream
     "wae_enc_conv_fwd_ranges": (c_i32, [c_vp] * 5 + [c_i32] * 12 + [c_vp]),
     "wae_vq_nearest": (c_i32, [c_vp] * 6 + [c_i32] * 4 + [c_f32, c_vp]),
+    # lat, quant, idx, segs, nsegs, D, pitch, K, c_loss, first, sqerr, hist, item_stats, out, stream
+    "wae_vq_stats_segments": (c_i32, [c_vp] * 4 + [c_i32] * 4 + [c_f32, c_i32] + [c_vp] * 5),
     "wae_upsample_stage_fwd": (c_i32, [c_vp, c_vp, c_vp] + [c_i32] * 7 + [c_vp]),
     # in, w, out, segs, nsegs, ntiles, in_pitch, out_pitch_or_rows, C, s, out_btc, Cp, dtype, stream
     "wae_upsample_stage_fwd_list": (c_i32, [c_vp] * 4 + [c_i32] * 9 + [c_vp]),

@@ -3,6 +3,7 @@
 #include <stdarg.h>
 #include "wae_common.hpp"
 #include "ups_fir.hpp"   // the upsample stages' per-output arithmetic, shared with csrc/ups_list.hip
+#include "vq_stats.hpp"  // wave_sum and the perplexity from code counts, shared with csrc/vq_list.hip
 
 static thread_local char g_err[512] = "";
 
@@ -22,12 +23,6 @@ int wae_check_launch(const char* what) {
 }
 extern "C" const char* wae_version(void) { return "wae-hip 0.1 (gfx950)"; }
 extern "C" const char* wae_last_error(void) { return g_err; }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 template <typename E>
 __device__ __forceinline__ void store_e(void* p, int64_t i, float v);
@@ -728,20 +723,11 @@ __global__ void __launch_bounds__(256) vq_nearest_kernel(const float* __restrict
 __global__ void __launch_bounds__(256) vq_stats_kernel(const float* __restrict__ sqerr, const int32_t* __restrict__ hist,
                                                        float* __restrict__ stats, int K, int N, int D, float c_loss, int mode) {
   __shared__ float part[4];
-  float s = 0.f;
-  if (mode != 2)
-    for (int k = threadIdx.x; k < K; k += 256) {
-      const float pk = (float)hist[k] / (float)N;
-      s += pk * logf(pk + 1e-10f);
-    }
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-  __syncthreads();
+  const float perp = vq_perplexity(hist, K, (float)N, part, mode != 2);      // csrc/vq_stats.hpp
   if (threadIdx.x == 0) {
-    const float tot = part[0] + part[1] + part[2] + part[3];
     const float mse = sqerr[0] / ((float)N * (float)D);
     if (mode != 1) stats[0] = c_loss * mse;
-    if (mode != 2) stats[1] = expf(-tot);
+    if (mode != 2) stats[1] = perp;
   }
 }
 

@@ -113,6 +113,9 @@ class WaeEngine:
         self.saved: Optional[Saved] = None      # the last train-mode forward's record; None: nothing to differentiate
         self.flight = InFlight()
         self._keep = {}                         # hold(): buffers passed by raw pointer, alive until their slot's next use
+        # encode_list_stats: the list's quantiser totals over all its groups, (4,) fp32 on the device --
+        # [vq_loss, perplexity, sum Tq, sum sqerr] (include/wae.h: wae_vq_stats_segments `out`); None before the first such call
+        self.last_list_stats: Optional[torch.Tensor] = None
         self._side_streams, self._side_stream, self._ev_wn = {}, None, None
         self._pack_jobs = self._pack_bwd_jobs = None          # the packing launches' job tables (the pointers never change)
         self._bwd_ready, self._finish_plans = False, {}       # backward.py: _prepare_bwd, _finish_plan
@@ -402,7 +405,25 @@ class WaeEngine:
         Returns, in the caller's order, a list of dict(quant (Cc, Tq_i) fp32, idx (Tq_i,) int64 | None (want_idx=False),
         latents (Cc, Tq_i) fp32 | None (want_latents=False)); every item is, bit for bit, encoder_forward + vq_forward of that
         utterance alone.  The tensors of an item are views of its group's packed (Cc, sum Tq_i) arrays (not contiguous).
+        The quantiser's statistics are not computed here: encode_list_stats is this call with them.
         ValueError, before any launch: an empty list, an item that is not (c_in, F_i) with F_i >= 1, an engine without an encoder."""
+        return self._encode_list(feats, want_latents, want_idx, max_frames, None)
+
+    def encode_list_stats(self, feats, beta: float = 0.25, want_latents: bool = False, want_idx: bool = True,
+                          max_frames: Optional[int] = None):
+        """encode_list with the quantiser's numbers besides (include/wae.h: wae_vq_stats_segments, one call per group behind the
+        quantiser's, c_loss = beta + 1): the same launches in front of it, the same quant, idx and latents.  Every item's dict gains
+        sqerr (sum of (quant - latents)^2), vq_loss (what vq_forward reports for the utterance alone, here from a fixed-order fp64 sum:
+        reproducible to the bit), perp (bit for bit vq_forward's perplexity of the utterance alone) -- 0-d views -- and hist, a (K,)
+        int32 view: how often the utterance used every code.  The list's totals over all groups go to self.last_list_stats, a (4,)
+        device tensor [vq_loss, perplexity, sum Tq, sum sqerr] of the list as ONE batch: vq_loss = (beta + 1) sum sqerr / (Cc sum Tq),
+        the perplexity that of the counts added per code -- what vq_forward reports on the packed latents.  All of it is the same
+        for every grouping, and per item for every order.  ValueError as encode_list."""
+        return self._encode_list(feats, want_latents, want_idx, max_frames, float(beta))
+
+    def _encode_list(self, feats, want_latents, want_idx, max_frames, beta):
+        """encode_list (beta None) / encode_list_stats: the checks, the groups, the per-list arrays of the statistics"""
+        want_stats = beta is not None
         g = self.g
         if not g.has_encoder:
             raise ValueError("encode_list: this engine has no encoder (a decoder-only geometry: c_in is None)")
@@ -420,13 +441,26 @@ class WaeEngine:
             raise ValueError(f"encode_list: max_frames {cap} < 1")
         if self.weights_dirty:
             self.prepare_weights()
-        out = []
+        out, stats = [], None
+        if want_stats:
+            n, dev = len(feats), self.device
+            stats = dict(c_loss=float(beta) + 1.0, keep=[], sqerr=torch.zeros(n, dtype=torch.float32, device=dev),
+                         hist=torch.zeros(n, g.K, dtype=torch.int32, device=dev), item=torch.zeros(n, 2, dtype=torch.float32, device=dev),
+                         out=torch.zeros(4, dtype=torch.float32, device=dev))
         for lo, hi in P.encode_list_groups([f.shape[1] for f in feats], cap):
-            out += self._encode_group(feats[lo:hi], want_latents, want_idx)
+            out += self._encode_group(feats[lo:hi], want_latents, want_idx, stats, lo)
+        if want_stats:
+            self.last_list_stats = stats["out"]
+            self.hold("encode_list_stats", *stats["keep"])       # the tables passed by raw pointer, until the next list
+            # the items' views by four unbind calls for the whole list: indexing per item cost more than the kernels (about 10 us an item)
+            cols = (stats["sqerr"].unbind(0), stats["item"][:, 0].unbind(0), stats["item"][:, 1].unbind(0), stats["hist"].unbind(0))
+            for r, sq, vq, pp, h in zip(out, *cols):
+                r.update(sqerr=sq, vq_loss=vq, perp=pp, hist=h)
         return out
 
-    def _encode_group(self, feats, want_latents, want_idx):
-        """one group of encode_list: pack, eleven list launches, one quantiser call"""
+    def _encode_group(self, feats, want_latents, want_idx, stats=None, first=0):
+        """one group of encode_list: pack, eleven list launches, one quantiser call; stats: encode_list's per-list arrays, whose
+        entries first .. first + n - 1 this group fills with one more call"""
         g, lib, st, dev = self.g, self.lib, self.stream(), self.device
         plan = P.encode_list_plan([f.shape[1] for f in feats])
         if all(not (torch.is_tensor(f) and f.is_cuda) for f in feats):          # all on the host: pack there, one upload
@@ -434,7 +468,12 @@ class WaeEngine:
         else:
             x = torch.cat([torch.as_tensor(f).to(dev, torch.float32) for f in feats], dim=1)
         x = x.contiguous()
-        table = torch.from_numpy(plan.table).to(dev)
+        tab, vq_off = plan.table, plan.table.size
+        if stats is not None:
+            # the statistics' records ride behind the layers' in the one upload: a copy of their own behind the quantiser's call would
+            # make the host wait for the group's launches and the groups stop overlapping (0.4 ms a group)
+            tab = np.concatenate([tab, P.vq_seg_table(plan.q_offsets, plan.Tq).reshape(-1)])
+        table = torch.from_numpy(tab).to(dev)
         width = max(self.lay.shapes[f"encoder.net.{i}.conv.weight"][0] for i in range(len(P.ENCODER_BLOCKS)))
         pong = [torch.empty(width * plan.total_F, dtype=torch.float32, device=dev) for _ in range(2)]
         lat = torch.empty(g.Cc, plan.total_Tq, dtype=torch.float32, device=dev)
@@ -454,7 +493,13 @@ class WaeEngine:
         quant, idx, _ = self.vq_forward(lat.view(1, g.Cc, plan.total_Tq))
         quant = quant[0]
         sl = [slice(int(o), int(o + t)) for o, t in zip(plan.q_offsets, plan.Tq)]
-        return [dict(quant=quant[:, s], idx=idx[s] if want_idx else None, latents=lat[:, s] if want_latents else None) for s in sl]
+        res = [dict(quant=quant[:, s], idx=idx[s] if want_idx else None, latents=lat[:, s] if want_latents else None) for s in sl]
+        if stats is not None:
+            L.check(lib.wae_vq_stats_segments(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(table[vq_off:]), len(feats), g.Cc, plan.total_Tq,
+                                              g.K, stats["c_loss"], first, L.ptr(stats["sqerr"]), L.ptr(stats["hist"]), L.ptr(stats["item"]),
+                                              L.ptr(stats["out"]), st), "vq_stats_segments")
+            stats["keep"].append(table)
+        return res
 
     def encode_session(self, want_latents: bool = False) -> EncodeSession:
         """An encode session: encode_list for utterances whose feature frames still arrive (include/wae.h: wae_enc_conv_fwd_ranges).
@@ -798,7 +843,7 @@ class WaeEngine:
 
     # ------------------------------------------------------------------ teacher-forced forward of a list
     def decoder_forward_list(self, items, want_logits: bool = True, want_nll: bool = True, max_rows: Optional[int] = None,
-                             c_is_upsampled: bool = False):
+                             c_is_upsampled: bool = False, quantize_channels: int = 65536, log_scale_min: float = -7.0):
         """WaveNet.forward (wavenet.py:164-216) for a LIST of utterances of unequal lengths (include/wae.h: wae_glu_layer_fwd_list,
         wae_nll_segments): logits and the shifted cross-entropy of every utterance, where decoder_forward takes one (B, T) batch, a
         loop of batch-1 forwards is 20+ launches, a workspace and a round trip per utterance, and a zero-padded batch computes every
@@ -818,16 +863,18 @@ class WaeEngine:
         nll_sum, count) -- views of the group's arrays; nll[t] is taken against x[t + 1], 0 at t = T_i - 1, nll_sum its sum and
         count = T_i - 1 -- and loss = sum nll_sum / sum count over the list (vqwae_train.py:379 with the list as one batch; None
         without want_nll).  logits and nll are, bit for bit, decoder_forward of that utterance alone.
-        Scalar-input decoders get logits (the distribution's parameters); with want_nll they raise NotImplementedError (the mixture
-        losses over a list are not built).  ValueError, before any launch: an empty list, an item with T_i < 1, gid on some items
-        only, a c that does not upsample to T_i."""
+        Scalar-input decoders: logits are the distribution's parameters and nll the mixture loss after the geometry's
+        output_distribution, as scalar_loss_and_grad chooses it -- wae_mog_loss_fwd ("Normal") or wae_dmol_loss_fwd with
+        quantize_channels, both with log_scale_min -- on the packed (1, O, rows) logits against the packed x with B = 1, T = rows,
+        shift = 1 and no gradient.  Those kernels are per column too (T is an address stride and the t + shift >= T test), so every
+        row but an item's last is the item's own value bit for bit, and wae_nll_segments zeroes the last rows as it does for the
+        cross-entropy.  The logits buffer is internal when want_logits=False.
+        ValueError, before any launch: an empty list, an item with T_i < 1, gid on some items only, a c that does not upsample to
+        T_i."""
         g, who = self.g, "decoder_forward_list"
         items = list(items)
         if not items:
             raise ValueError(f"{who}: an empty list")
-        if g.scalar_input and want_nll:
-            raise NotImplementedError(f"{who}: the mixture losses over a list are not implemented; pass want_nll=False for the "
-                                      "distribution parameters, or score one utterance at a time")
         Ts = []
         for i, it in enumerate(items):
             shape = tuple(getattr(it["x"], "shape", ()))
@@ -856,12 +903,15 @@ class WaeEngine:
         loss = torch.zeros(2, dtype=torch.float32, device=self.device) if want_nll else None
         out, keep = [], []
         for lo, hi in P.forward_list_groups(Ts, cap):
-            out += self._forward_list_group(items[lo:hi], Ts[lo:hi], lo, want_logits, want_nll, c_is_upsampled, sums, counts, loss, keep)
+            out += self._forward_list_group(items[lo:hi], Ts[lo:hi], lo, want_logits, want_nll, c_is_upsampled, sums, counts, loss, keep,
+                                            (int(quantize_channels), float(log_scale_min)))
         self.hold("forward_list", *keep)       # the tables and operands passed by raw pointer, until the next list
         return out, (loss[0] if want_nll else None)
 
-    def _forward_list_group(self, items, Ts, first, want_logits, want_nll, c_is_upsampled, sums, counts, loss, keep):
-        """one group of decoder_forward_list: its packed arrays, one table, the launches; -> the items' dicts"""
+    def _forward_list_group(self, items, Ts, first, want_logits, want_nll, c_is_upsampled, sums, counts, loss, keep,
+                            mix=(65536, -7.0)):
+        """one group of decoder_forward_list: its packed arrays, one table, the launches; -> the items' dicts.
+        mix: (quantize_channels, log_scale_min) of a scalar-input decoder's mixture loss"""
         g, lib, st, dev, td = self.g, self.lib, self.stream(), self.device, self.tdtype
         n = len(items)
         plan = P.glu_list_plan(Ts, P.GLU_LIST_TILES[self.dt])
@@ -910,11 +960,19 @@ class WaeEngine:
             ws["h0"] = torch.empty(rows, g.Sp, dtype=td, device=dev)
         if self.wide_head:
             ws["h1"] = torch.empty(rows, g.Sp, dtype=td, device=dev)
-        logits = torch.empty(1, g.O, rows, dtype=torch.float32, device=dev) if want_logits else None
+        mixture = g.scalar_input and want_nll       # the head has no fused mixture loss: it runs into logits, the loss kernel behind it
+        logits = torch.empty(1, g.O, rows, dtype=torch.float32, device=dev) if (want_logits or mixture) else None
         nll = None
         if want_nll:
             nll = ws["nll"] = torch.empty(rows, dtype=torch.float32, device=dev)
-        self._head_fwd(ws, 1, rows, logits, xi if want_nll else None, False)
+        self._head_fwd(ws, 1, rows, logits, xi if (want_nll and not mixture) else None, False)
+        if mixture:
+            # per column as the head's cross-entropy: row t against x[t + 1] of the packed rows, 0 at the last row of all
+            if g.output_distribution == "Normal":
+                L.check(lib.wae_mog_loss_fwd(L.ptr(logits), L.ptr(xi), L.ptr(nll), None, 1, g.O, rows, mix[1], 1, st), "mog_loss (list)")
+            else:
+                L.check(lib.wae_dmol_loss_fwd(L.ptr(logits), L.ptr(xi), L.ptr(nll), None, 1, g.O // 3, rows, mix[0], mix[1], 1, st),
+                        "dmol_loss (list)")
         if want_nll:
             L.check(lib.wae_nll_segments(L.ptr(nll), L.ptr(table), n, rows, first, L.ptr(sums), L.ptr(counts), L.ptr(loss), st),
                     "nll_segments")
@@ -929,21 +987,50 @@ class WaeEngine:
         return res
 
     def forward_list(self, items, want_logits: bool = True, want_nll: bool = True, max_rows: Optional[int] = None,
-                     want_latents: bool = True):
+                     want_latents: bool = True, want_stats: bool = False, beta: float = 0.25, quantize_channels: int = 65536,
+                     log_scale_min: float = -7.0):
         """VQVAE.forward (vqvae_model.py:66-72) in eval mode for a LIST of utterances of unequal lengths: encode_list, then
-        decoder_forward_list on the quantised latents.  items: mappings with `x` ((T_i,) class ids), `feats` ((c_in, F_i) features)
-        and `gid`.  Returns (results, loss) as decoder_forward_list, every dict with quant (Cc, Tq_i), idx (Tq_i,) and latents
-        (Cc, Tq_i) | None (want_latents=False) besides.  Every item is, bit for bit, forward() of that utterance alone -- which a
-        zero-padded batch is not at the utterance ends (encode_list, upsample_list).  ValueError as the two list calls."""
+        decoder_forward_list on the quantised latents.  items: mappings with `x` ((T_i,) class ids, or floats for a scalar-input
+        decoder), `feats` ((c_in, F_i) features) and `gid`.  Returns (results, loss) as decoder_forward_list, every dict with quant
+        (Cc, Tq_i), idx (Tq_i,) and latents (Cc, Tq_i) | None (want_latents=False) besides.  Every item is, bit for bit, forward() of
+        that utterance alone -- which a zero-padded batch is not at the utterance ends (encode_list, upsample_list).
+        want_stats: every dict gains vq_loss, perp and hist as encode_list_stats(beta=beta) gives them, and the list's
+        quantiser totals are in self.last_list_stats; loss stays the NLL mean.  quantize_channels, log_scale_min: the mixture loss of
+        a scalar-input decoder (decoder_forward_list).  ValueError as the two list calls."""
         items = list(items)
         if not items:
             raise ValueError("forward_list: an empty list")
-        enc = self.encode_list([it["feats"] for it in items], want_latents=want_latents)
+        feats = [it["feats"] for it in items]
+        enc = (self.encode_list_stats(feats, beta=beta, want_latents=want_latents) if want_stats
+               else self.encode_list(feats, want_latents=want_latents))
         dec, loss = self.decoder_forward_list([dict(x=it["x"], c=e["quant"], gid=it.get("gid")) for it, e in zip(items, enc)],
-                                              want_logits=want_logits, want_nll=want_nll, max_rows=max_rows)
+                                              want_logits=want_logits, want_nll=want_nll, max_rows=max_rows,
+                                              quantize_channels=quantize_channels, log_scale_min=log_scale_min)
         for d, e in zip(dec, enc):
             d.update(quant=e["quant"], idx=e["idx"], latents=e["latents"])
+            if want_stats:
+                d.update(vq_loss=e["vq_loss"], perp=e["perp"], hist=e["hist"])
         return dec, loss
+
+    def score_list(self, items, beta: float = 0.25, quantize_channels: int = 65536, log_scale_min: float = -7.0,
+                   max_rows: Optional[int] = None):
+        """What forward() reports for a batch -- loss, commitment loss, perplexity -- for a LIST of utterances of unequal lengths, per
+        utterance and for the list as one batch: forward_list without logits and without latents, with the quantiser's statistics.
+        items: as forward_list.  Returns (results, totals): results as forward_list(want_stats=True) (nll, nll_sum, count, quant, idx,
+        vq_loss, perp, hist per utterance); totals, a dict of 0-d device tensors:
+          ce      sum nll_sum / sum count, the masked mean of vqwae_train.py:379 with the list as one batch (cross-entropy, or the
+                  mixture loss of a scalar-input decoder);
+          vq_loss (beta + 1) sum sqerr / (Cc sum Tq);  perp: the perplexity of the code counts added over the list;
+          loss    ce + vq_loss, the number the reference's dev phase logs;
+          count   sum (T_i - 1);  frames: sum Tq_i (both as floats).
+        Nothing synchronises: the numbers are read when the caller reads them."""
+        res, ce = self.forward_list(items, want_logits=False, want_latents=False, want_stats=True, beta=beta, max_rows=max_rows,
+                                    quantize_channels=quantize_channels, log_scale_min=log_scale_min)
+        st = self.last_list_stats
+        count = sum(int(r["nll"].shape[0]) - 1 for r in res)       # the lengths are host numbers: no read-back
+        totals = dict(ce=ce, vq_loss=st[0], perp=st[1], loss=ce + st[0],
+                      count=torch.tensor(float(count), dtype=torch.float32, device=self.device), frames=st[2])
+        return res, totals
 
     # ------------------------------------------------------------------ autoregressive synthesis
     def _prepare_ar(self):

@@ -250,6 +250,38 @@ def encode_list_groups(Fs, max_frames: int) -> List[Tuple[int, int]]:
     return out
 
 
+def vq_seg_table(q_offsets, Tq) -> np.ndarray:
+    """(n, 2) int32 records {q_off, Tq} of wae_vq_stats_segments (include/wae.h: wae_vq_seg): item i owns the columns
+    [q_off_i, q_off_i + Tq_i) of the packed latents -- encode_list_plan's q_offsets and Tq.  The entry takes no closing record.
+    ValueError: an empty list, arrays of unequal sizes, an item with Tq < 1 (with its index), a negative offset, columns at or above
+    2^31."""
+    offs = np.asarray(q_offsets, dtype=np.int64).reshape(-1)
+    Tq = np.asarray(Tq, dtype=np.int64).reshape(-1)
+    if Tq.size < 1:
+        raise ValueError("vq_seg_table: an empty list")
+    if offs.size != Tq.size:
+        raise ValueError(f"vq_seg_table: {offs.size} offsets for {Tq.size} items")
+    if int(Tq.min()) < 1:
+        raise ValueError(f"vq_seg_table: item {int(np.argmax(Tq < 1))} has Tq < 1")
+    if int(offs.min()) < 0 or int((offs + Tq).max()) >= 2 ** 31:
+        raise ValueError("vq_seg_table: one column offset in [0, 2^31) per item")
+    return np.stack([offs, Tq], axis=1).astype(np.int32)
+
+
+def vq_list_totals(sqerr, hist, D: int, c_loss: float):
+    """float64 restatement of wae_vq_stats_segments' `out` from the per-item results (sqerr (n,), hist (n, K)): "the list as one
+    batch", the quantiser's counterpart of loss = sum nll_sum / sum count.  -> (vq_loss = c_loss sum sqerr / (D sum Tq), perplexity of
+    the counts added per code with N = sum Tq (vector_quantization.py:45-47), sum Tq, sum sqerr); Tq_i is the sum of item i's
+    counts."""
+    sq = np.asarray(sqerr, dtype=np.float64).reshape(-1)
+    h = np.asarray(hist, dtype=np.int64).reshape(sq.size, -1)
+    frames = int(h.sum())
+    if frames < 1:
+        return 0.0, 0.0, 0, 0.0
+    p = h.sum(axis=0).astype(np.float64) / frames
+    return float(c_loss) * float(sq.sum()) / (D * frames), float(np.exp(-np.sum(p * np.log(p + 1e-10)))), frames, float(sq.sum())
+
+
 # ---- utterances whose features arrive while they are encoded (include/wae.h: wae_enc_conv_fwd_ranges; EncodeSession.open / feed)
 ENC_LAYERS = list(ENCODER_BLOCKS) + [(1, 1)]       # the blocks, then lin: (k, stride), pad k // 2
 # columns of a layer's INPUT per feature frame, as a divisor: cap frames of room are cap, cap, cap, ceil(cap / 2) and then

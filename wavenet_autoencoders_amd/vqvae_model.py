@@ -124,16 +124,26 @@ class VQVAE(ArenaModel):
         with torch.no_grad():
             return [r["quant"] for r in self.engine().encode_list(xs, want_idx=False)]
 
-    def forward_list(self, items, want_nll=None):
+    def forward_list(self, items, want_nll=True, want_stats=False, beta=0.25, quantize_channels=65536, log_scale_min=-7.0):
         """forward (no gradients, eval) for a list of utterances of unequal lengths: items, a sequence of mappings with `x` ((T_i,)
-        class ids), `c` ((c_in, F_i) features) and `g` (a speaker id or None) -> (results, loss): per utterance dict(logits
+        class ids or scalars), `c` ((c_in, F_i) features) and `g` (a speaker id or None) -> (results, loss): per utterance dict(logits
         (out_channels, T_i), nll (T_i,) | None, nll_sum, count, quant, idx, latents) and the list's masked mean of the shifted
-        cross-entropy.  Every utterance is bit for bit its own forward(x[None], c[None], g[None]) -- which a zero-padded batch is not
-        at the utterance ends (WaeEngine.forward_list).  want_nll: by default on for class-id models."""
-        want_nll = (not self.scalar_input) if want_nll is None else bool(want_nll)
+        cross-entropy (scalar inputs: of the mixture loss, with quantize_channels and log_scale_min).  Every utterance is bit for bit
+        its own forward(x[None], c[None], g[None]) -- which a zero-padded batch is not at the utterance ends
+        (WaeEngine.forward_list).  want_nll: on by default for every model.  want_stats: vq_loss, perp and hist per utterance besides."""
         its = [dict(x=it["x"], feats=it["c"], gid=it.get("g")) for it in items]
         with torch.no_grad():
-            return self.engine().forward_list(its, want_nll=want_nll)
+            return self.engine().forward_list(its, want_nll=bool(want_nll), want_stats=want_stats, beta=beta,
+                                              quantize_channels=quantize_channels, log_scale_min=log_scale_min)
+
+    def score_list(self, items, beta=0.25, quantize_channels=65536, log_scale_min=-7.0):
+        """What forward returns besides the logits -- loss, vq_loss, perplexity -- for a list of utterances of unequal lengths, per
+        utterance and for the list as one batch (WaeEngine.score_list): items as forward_list -> (results, totals), totals a dict of
+        0-d tensors ce, vq_loss, perp, loss = ce + vq_loss, count, frames; every dict of results carries nll, nll_sum, count, vq_loss,
+        perp and hist (how often the utterance used every code)."""
+        its = [dict(x=it["x"], feats=it["c"], gid=it.get("g")) for it in items]
+        with torch.no_grad():
+            return self.engine().score_list(its, beta=beta, quantize_channels=quantize_channels, log_scale_min=log_scale_min)
 
     def encode_session(self, want_latents=False):
         """encode for utterances whose features still arrive: WaeEngine.encode_session (open / feed_list / end), whose `quant` chunks,

@@ -194,16 +194,17 @@ class WaveNet(ArenaModel):
         y = _DecoderFn.apply(self, ids, c, g, c_is_up, train, *params)
         return softmax_bct(y) if softmax else y
 
-    def forward_list(self, items, want_nll=None):
+    def forward_list(self, items, want_nll=True, quantize_channels=65536, log_scale_min=-7.0):
         """forward (no gradients, eval) for a list of utterances of unequal lengths: items, a sequence of mappings with `x` ((T_i,)
         class ids or scalars), `c` ((Cc, Tc_i) or None) and `g` (a speaker id or None) -> (results, loss): per utterance
-        dict(logits (out_channels, T_i), nll (T_i,) | None, nll_sum, count) and the list's masked mean of the shifted cross-entropy,
+        dict(logits (out_channels, T_i), nll (T_i,) | None, nll_sum, count) and the list's masked mean of the shifted cross-entropy
+        (scalar inputs: of the mixture loss after output_distribution, with quantize_channels and log_scale_min),
         each bit for bit forward(x[None], c[None], g[None]) of that utterance alone, from one launch per layer for the whole list
-        (WaeEngine.decoder_forward_list; the reference has no list form).  want_nll: by default on for class-id models."""
-        want_nll = (not self.scalar_input) if want_nll is None else bool(want_nll)
+        (WaeEngine.decoder_forward_list; the reference has no list form).  want_nll: on by default for every model."""
         its = [dict(x=it["x"], c=it.get("c"), gid=it.get("g")) for it in items]
         with torch.no_grad():
-            return self.engine().decoder_forward_list(its, want_nll=want_nll, c_is_upsampled=not bool(self.geom.upsample_scales))
+            return self.engine().decoder_forward_list(its, want_nll=bool(want_nll), c_is_upsampled=not bool(self.geom.upsample_scales),
+                                                      quantize_channels=quantize_channels, log_scale_min=log_scale_min)
 
     def incremental_forward(self, initial_input=None, c=None, g=None, T=100, test_inputs=None, tqdm=lambda x: x,
                             softmax=True, quantize=True, log_scale_min=-50.0):
