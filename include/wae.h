@@ -168,6 +168,27 @@ int wae_enc_conv_fwd_ranges(const float* x, const float* w, const float* bias, f
                             int32_t ntiles, int32_t et, int32_t in_pitch, int32_t out_pitch, int32_t Cin, int32_t Cout, int32_t k,
                             int32_t stride, int32_t pad, int32_t relu, int32_t residual, void* stream);
 
+/* ---- a1 over column ranges of utterances that live in RINGS (a windowed encode session: EncodeSession(window=W)).
+ * The ring-addressed twin of wae_enc_conv_fwd_ranges: the same ranges, the same guarantee asked of the host, the same bits.  What
+ * differs is where a column lies.  Record wae_enc_ring {in_off, in_period, Tin, out_off, out_period, t_lo, t_hi, tile0}:
+ * Tin -- as in wae_enc_range, the clip's input columns that are valid now, in the clip's own numbering; only the last in_period of
+ * them are held, column u at in_off + u % in_period of x (Cin, in_pitch).  A tap with u < 0 or u >= Tin is the clip's zero padding.
+ * Output t goes to column out_off + t % out_period of y (Cout, out_pitch); out_period == 0 means a linear output, out_off
+ * receiving t_lo (a packed buffer of this call's new columns).  t_lo, t_hi, tile0, the closing record, the binary search, the grid
+ * and et are wae_enc_conv_fwd_ranges'.  The ring is mapped where a tile's input window is staged, at the residual read and at the
+ * store, and nowhere in the arithmetic: every output is, bit for bit, what wae_enc_conv_fwd writes for the whole clip (B = 1),
+ * whatever the periods (csrc/enc_ring.hip).
+ * The kernel does not trust the table with memory: it is skipped as a whole, nothing read or written for it, a record that
+ * wae_enc_conv_fwd_ranges would skip for its Tin, t_lo, t_hi or tile count, and one with in_period < 1, in_off < 0,
+ * in_off + in_period > in_pitch, out_period < 0, out_off < 0, out_off + out_period (out_period == 0: out_off + (t_hi - t_lo)) >
+ * out_pitch, t_hi - t_lo > out_period > 0, or -- aliasing -- a first tap t_lo * stride - pad older than Tin - in_period: that column is
+ * gone and its slot holds a newer one.  Returns WAE_EINVAL / WAE_EUNSUPPORTED exactly where wae_enc_conv_fwd_ranges does,
+ * before any launch; nothing allocates or synchronises. */
+typedef struct wae_enc_ring { int32_t in_off, in_period, Tin, out_off, out_period, t_lo, t_hi, tile0; } wae_enc_ring;
+int wae_enc_conv_fwd_rings(const float* x, const float* w, const float* bias, float* y, const wae_enc_ring* recs, int32_t nrecs,
+                           int32_t ntiles, int32_t et, int32_t in_pitch, int32_t out_pitch, int32_t Cin, int32_t Cout, int32_t k,
+                           int32_t stride, int32_t pad, int32_t relu, int32_t residual, void* stream);
+
 /* ---- a2 VectorQuantize.forward (vector_quantization.py:21-49) -----------------------------------------
  * lat (B,D,Tq) fp32, emb (K,D).  idx int64 (B*Tq) first-minimum of ||e||^2+||x||^2-2x.e; quant (B,D,Tq);
  * stats[0] = vq_loss = (beta+1)*mean((q-x)^2) forward value, stats[1] = perplexity; hist: (K+1) int32 scratch. */
@@ -292,6 +313,26 @@ typedef struct wae_ups_range { int32_t in_off, Tin, out_off, t_lo, t_hi, tile0; 
 int wae_upsample_stage_fwd_ranges(const float* in, const float* w, void* out, const wae_ups_range* recs, int32_t nrecs, int32_t ntiles,
                                   int32_t in_pitch, int32_t out_pitch_or_rows, int32_t C, int32_t s, int32_t out_btc, int32_t Cp,
                                   int32_t dtype, void* stream);
+
+/* ---- a3 over row ranges of clips that live in RINGS: the ring-addressed twin of wae_upsample_stage_fwd_ranges.
+ * Record wae_ups_ring {in_off, in_period, Tin, out_off, out_period, t_lo, t_hi, tile0}: Tin -- as in wae_ups_range, the clip's input
+ * frames that are valid now; only the last in_period are held, frame u at column in_off + u % in_period of `in` (C, in_pitch).
+ * Output row t goes to the column (out_btc = 0) or the row (out_btc = 1) out_off + t % out_period, out_period >= 1.  Everything else
+ * -- ranges, tiles, the closing record, the binary search, both forms, the guarantee t_hi <= (Tin - 1) * s asked of the host while a
+ * clip is open -- is wae_upsample_stage_fwd_ranges'.  The ring is an address only: the time-major last stage maps it where it stages
+ * a tile's frames in LDS, the channel-major stage reads the three frames t/s - 1 .. t/s + 1 of an output into registers, and both
+ * then run the per-output functions of csrc/ups_fir.hpp on that linear copy: every row is the ranges entry's and the dense stage's,
+ * bit for bit, whatever the periods (csrc/ups_ring.hip).
+ * The kernel does not trust the table with memory: it is skipped as a whole, nothing read or written for it, a record that
+ * wae_upsample_stage_fwd_ranges would skip for its Tin, t_lo, t_hi or tile count, and one with in_period < 1, in_off < 0,
+ * in_off + in_period > in_pitch, out_period < 1, out_off < 0, out_off + out_period > out_pitch_or_rows, t_hi - t_lo > out_period,
+ * or -- aliasing -- a first frame max(t_lo - s, 0) / s older than Tin - in_period: that frame is gone and its slot holds a newer one.
+ * Returns WAE_EINVAL / WAE_EUNSUPPORTED exactly where wae_upsample_stage_fwd_ranges does, before any launch; nothing allocates or
+ * synchronises. */
+typedef struct wae_ups_ring { int32_t in_off, in_period, Tin, out_off, out_period, t_lo, t_hi, tile0; } wae_ups_ring;
+int wae_upsample_stage_fwd_rings(const float* in, const float* w, void* out, const wae_ups_ring* recs, int32_t nrecs, int32_t ntiles,
+                                 int32_t in_pitch, int32_t out_pitch_or_rows, int32_t C, int32_t s, int32_t out_btc, int32_t Cp,
+                                 int32_t dtype, void* stream);
 
 /* ---- a4/K5 hoisted global conditioning: zb[b][l][2Hp] = bias_l + Wg_l . g_b  (modules.py:148-152) ------
  * g_b = eff[emb_off + gid[b]*Cg ..] (Embedding lookup, wavenet.py:185-190) when gid != NULL, else gvec[b*Cg ..]

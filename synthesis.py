@@ -36,6 +36,10 @@ options:
                              call makes final go straight into DecodeSession.feed_list, and the clip ends in both sessions behind its
                              last frames -- the whole conversion fed incrementally.  The wavs written are the bytes of --batch-decode
                              --batch-stream alone, also with --seed.  Not with --feed-frames.
+    --batch-window=<W>       With --feed-frames or --feed-features: the sessions run in constant memory, every clip in a ring of W
+                             latent frames (DecodeSession(window=W); the encode session's window is 4 W feature frames plus what
+                             its layers retain).  A clip gets no more frames per round than its ring has room for.  The wavs
+                             written are the bytes of the same command without the flag.
 """
 import argparse
 import json
@@ -235,35 +239,41 @@ def batch_feed(eng, args, items, names, how):
     """--batch-decode --batch-stream=N --feed-frames=K: batch_stream's rounds with every clip OPEN -- it joins without its
     conditioning (DecodeSession.open) and gets K latent frames in front of every round (feed_list: one launch per upsampling stage for
     all clips), as if the speech arrived while it is converted; a clip ends with its last frame.  The draws batch_decode made go with
-    the frames they belong to, so a clip decodes bit for bit as in batch_stream: the same wav bytes, also with --seed."""
+    the frames they belong to, so a clip decodes bit for bit as in batch_stream: the same wav bytes, also with --seed.
+    --batch-window=W: the session holds every clip in a ring of W latent frames; a clip gets no more frames than it has room for
+    (DecodeSession.room) and ends once its last rows fit -- other feeds, the same bytes."""
     import time
     from scipy.io import wavfile
     kw = dict(log_scale_min=hparams.log_scale_min) if eng.g.scalar_input else {}
     hop = int(np.prod(eng.g.upsample_scales))
+    W = args.batch_window
     names_of = ("u_mix", "z" if eng.g.output_distribution == "Normal" else "u_log") if eng.g.scalar_input else ("uniforms",)
     posts = [ChunkPostprocess(hparams.postprocess, hparams.global_gain_scale) for _ in items]
     parts, fed = [[] for _ in items], [0] * len(items)
     t_start, first = time.perf_counter(), True
-    with eng.decode_session(mode="sample", **how, **kw) as sess:
+    with eng.decode_session(mode="sample", **how, **kw, **({} if W is None else {"window": W})) as sess:
         sess.reserve(len(items))
-        sess.reserve_frames(sum(int(it["c"].shape[-1]) for it in items))
+        sess.reserve_frames(len(items) * W if W else sum(int(it["c"].shape[-1]) for it in items))
         hs = [sess.open({k: it[k] for k in ("gid", "init_idx") if k in it}, max_T=it["T"]) for it in items]
+        ends = []
         while sess.live:
-            feeds, draws, ends = {}, {k: {} for k in names_of}, []
+            feeds, draws = {}, {k: {} for k in names_of}
             for i, (h, it) in enumerate(zip(hs, items)):
                 F = int(it["c"].shape[-1])
-                if fed[i] < F:
-                    n = min(int(args.feed_frames), F - fed[i])
+                n = min(int(args.feed_frames), F - fed[i], sess.room(h) if W and fed[i] < F else F)
+                if n > 0:
                     feeds[h] = it["c"][:, fed[i]:fed[i] + n]
                     for k in names_of:
                         if it.get(k) is not None:
                             draws[k][h] = it[k].reshape(it["T"], -1)[fed[i] * hop:(fed[i] + n) * hop]
                     fed[i] += n
                     if fed[i] == F:
-                        ends.append(h)
+                        ends.append((h, it["T"]))
             sess.feed_list(feeds, **{k: v for k, v in draws.items() if v})
-            for h in ends:
-                sess.end(h)
+            for h, T in ends:       # (a windowed clip ends once its last rows fit behind the rows it has decoded)
+                if not W or T - sess.clips[h].pos <= W * hop:
+                    sess.end(h)
+            ends = [(h, T) for h, T in ends if not sess.clips[h].feed.ended]
             rnd = sess.step(int(args.batch_stream))
             for i, h in enumerate(hs):
                 res = rnd.get(h)
@@ -283,46 +293,65 @@ def batch_feed_features(eng, args, items, feats, names, how):
     session and the decode session open; a round feeds K feature frames per clip to the encode session (EncodeSession.feed_list: one
     launch per encoder layer for all clips), hands the quantised latents that call made final to DecodeSession.feed_list with the
     draws of their samples, and decodes; a clip ends in both sessions behind its last frames.  The latents are bit for bit
-    encode_list's and the draws are batch_decode's, so the wavs are batch_stream's bytes, also with --seed."""
+    encode_list's and the draws are batch_decode's, so the wavs are batch_stream's bytes, also with --seed.
+    --batch-window=W: both sessions in constant memory -- the decode session with rings of W latent frames, the encode session with
+    a window of 4 W feature frames plus what its layers retain.  Latent frames the decode session has no room for yet wait on the
+    device for the next round; a clip ends once its last rows fit.  Other feeds, the same bytes."""
     import time
+    import torch
     from scipy.io import wavfile
+    from wavenet_autoencoders_amd import packing as PK
     kw = dict(log_scale_min=hparams.log_scale_min) if eng.g.scalar_input else {}
     hop = int(np.prod(eng.g.upsample_scales))
+    W = args.batch_window
+    enc_kw = {} if W is None else {"window": PK.ENC_ROOM * W + PK.enc_window_min() - PK.ENC_ROOM}
     names_of = ("u_mix", "z" if eng.g.output_distribution == "Normal" else "u_log") if eng.g.scalar_input else ("uniforms",)
     posts = [ChunkPostprocess(hparams.postprocess, hparams.global_gain_scale) for _ in items]
     parts, fed, got = [[] for _ in items], [0] * len(items), [0] * len(items)
     t_start, first = time.perf_counter(), True
-    with eng.encode_session() as enc, eng.decode_session(mode="sample", **how, **kw) as sess:
+    with eng.encode_session(**enc_kw) as enc, eng.decode_session(mode="sample", **how, **kw, **({} if W is None else {"window": W})) as sess:
         sess.reserve(len(items))
-        sess.reserve_frames(sum(it["T"] // hop for it in items))
-        enc.reserve_frames(sum(-(-f.shape[1] // 4) * 4 for f in feats))
+        sess.reserve_frames(len(items) * W if W else sum(it["T"] // hop for it in items))
+        if W:
+            enc.reserve_slots(len(feats))
+        else:
+            enc.reserve_frames(sum(-(-f.shape[1] // 4) * 4 for f in feats))
         hs = [sess.open({k: it[k] for k in ("gid", "init_idx") if k in it}, max_T=it["T"]) for it in items]
         es = [enc.open(max_frames=f.shape[1]) for f in feats]
+        wait, ends = [None] * len(items), []        # windowed: latent frames the decode session has no room for yet
         while sess.live:
             feeds, last = {}, []
             for i, (e, f) in enumerate(zip(es, feats)):
                 if fed[i] < f.shape[1]:
-                    n = min(int(args.feed_features), f.shape[1] - fed[i])
+                    n = min(int(args.feed_features), f.shape[1] - fed[i], enc.max_feed if W else f.shape[1])
                     feeds[e] = f[:, fed[i]:fed[i] + n]
                     fed[i] += n
                     if fed[i] == f.shape[1]:
                         last.append(e)
             new = enc.feed_list(feeds, ended=last) if feeds else {}
-            lat, draws, ends = {}, {k: {} for k in names_of}, []
+            lat, draws = {}, {k: {} for k in names_of}
             for i, (h, e, it) in enumerate(zip(hs, es, items)):
                 res = new.get(e)
-                n = 0 if res is None else int(res["quant"].shape[1])
+                q = None if res is None or not res["quant"].shape[1] else res["quant"]
+                if W and h in sess.clips and not sess.clips[h].feed.ended:
+                    q = q if wait[i] is None else wait[i] if q is None else torch.cat([wait[i], q], dim=1)
+                    n = 0 if q is None else min(int(q.shape[1]), sess.room(h))
+                    wait[i] = None if q is None or n == q.shape[1] else q[:, n:]
+                    q = None if not n else q[:, :n]
+                n = 0 if q is None else int(q.shape[1])
                 if n:
-                    lat[h] = res["quant"]
+                    lat[h] = q
                     for k in names_of:
                         if it.get(k) is not None:
                             draws[k][h] = it[k].reshape(it["T"], -1)[got[i] * hop:(got[i] + n) * hop]
                     got[i] += n
                 if res is not None and res["done"]:
-                    ends.append(h)
+                    ends.append((i, h, it["T"]))
             sess.feed_list(lat, **{k: v for k, v in draws.items() if v})
-            for h in ends:
-                sess.end(h)
+            for i, h, T in ends:    # (a windowed clip ends once all its frames are fed and its last rows fit)
+                if not W or (wait[i] is None and T - sess.clips[h].pos <= W * hop):
+                    sess.end(h)
+            ends = [(i, h, T) for i, h, T in ends if not sess.clips[h].feed.ended]
             rnd = sess.step(int(args.batch_stream))
             for i, h in enumerate(hs):
                 res = rnd.get(h)
@@ -356,6 +385,7 @@ def main(argv=None):
     ap.add_argument("--batch-stream", type=int)
     ap.add_argument("--feed-frames", type=int)
     ap.add_argument("--feed-features", type=int)
+    ap.add_argument("--batch-window", type=int)
     args = ap.parse_args(argv)
     args.coop_scalar = args.coop_scalar or args.coop_scalar_fast
     if args.batch_stream is not None and not args.batch_decode:
@@ -366,6 +396,8 @@ def main(argv=None):
         ap.error("--feed-frames feeds that many latent frames (>= 1) per round of --batch-decode --batch-stream: it needs both")
     if args.feed_features is not None and (args.batch_stream is None or args.feed_features < 1):
         ap.error("--feed-features feeds that many feature frames (>= 1) per round of --batch-decode --batch-stream: it needs both")
+    if args.batch_window is not None and (args.batch_window < 1 or (args.feed_frames is None and args.feed_features is None)):
+        ap.error("--batch-window holds the fed clips in rings of that many latent frames (>= 1): it needs --feed-frames or --feed-features")
     if args.feed_features is not None and args.feed_frames is not None:
         ap.error("--feed-features feeds the encoder, --feed-frames the decoder: they cannot be combined")
     if (args.batch_coop or args.batch_teams is not None) and not args.batch_decode:

@@ -86,6 +86,48 @@ def feed_rounds(eng, args, record):
             torch.cuda.empty_cache()
 
 
+def window_rounds(eng, args, record):
+    """--window W: a round of the windowed session (EncodeSession(window=W): rings, constant arenas) against the same round of the
+    unwindowed one, alternating in one process, and the bytes of both sessions' arenas"""
+    W = args.window
+    for n in [int(s) for s in args.sizes.split(",")]:
+        for K in [int(s) for s in args.feeds.split(",")]:
+            rng = np.random.default_rng(1234)
+            gen = torch.Generator().manual_seed(1234)
+            rounds = args.repeats + 1
+            Fs = [int(f) for f in rng.integers(args.min_frames, args.max_frames + 1, n)]
+            xs = [torch.randn(CFG["c_in"], f + rounds * K, generator=gen).cuda() for f in Fs]
+            tw, tf, same = [], [], True
+            with eng.encode_session(window=W) as ring, eng.encode_session() as flat:
+                if K > ring.max_feed:
+                    print(f"fp32 {n:4d} utterances, {K} frames per round: beyond max_feed {ring.max_feed} of window {W}: not measured", flush=True)
+                    continue
+                ring.reserve_slots(n)
+                flat.reserve_frames(sum(-(-(f + rounds * K) // 4) * 4 for f in Fs))
+                hr, hf = [ring.open() for _ in Fs], [flat.open(max_frames=f + rounds * K) for f in Fs]
+                flat.feed_list({h: x[:, :f] for h, x, f in zip(hf, xs, Fs)})
+                for lo in range(0, max(Fs), ring.max_feed):      # the prefix, max_feed frames per call
+                    ring.feed_list({h: x[:, lo:min(lo + ring.max_feed, f)] for h, x, f in zip(hr, xs, Fs) if lo < f})
+                for r in range(rounds):       # round 0 warms both sides
+                    have = [f + r * K for f in Fs]
+                    a, b = {}, {}
+                    t1 = timed(lambda: a.update(ring.feed_list({h: x[:, k:k + K] for h, x, k in zip(hr, xs, have)})))
+                    t2 = timed(lambda: b.update(flat.feed_list({h: x[:, k:k + K] for h, x, k in zip(hf, xs, have)})))
+                    if r:
+                        tw.append(t1)
+                        tf.append(t2)
+                    for x_, y_ in zip(hr, hf):
+                        same = same and bool(torch.equal(a[x_]["quant"], b[y_]["quant"])) and bool(torch.equal(a[x_]["idx"], b[y_]["idx"]))
+                bytes_ring, bytes_flat = ring.arena_bytes, flat.arena_bytes
+            w, f = stats(tw), stats(tf)
+            print(f"fp32 {n:4d} open utterances holding {sum(Fs)} frames, {K:2d} frames each per round: window {W} {w[0]:8.2f} ms "
+                  f"({w[1]:.2f} .. {w[2]:.2f}), no window {f[0]:8.2f} ms ({f[1]:.2f} .. {f[2]:.2f}); windowed slower than the unwindowed "
+                  f"runs' slowest: {w[0] > f[2]}; arenas {bytes_ring} B against {bytes_flat} B; bit for bit: {same}", flush=True)
+            record["runs"].append(dict(kind="window_round", dtype="fp32", clips=n, frames_per_feed=K, window=W, window_ms=w, flat_ms=f,
+                                       slower=bool(w[0] > f[2]), arena_bytes=bytes_ring, flat_arena_bytes=bytes_flat, same=same))
+            torch.cuda.empty_cache()
+
+
 def first_latent(eng, args, record):
     gen = torch.Generator().manual_seed(77)
     F = args.clip_frames
@@ -130,6 +172,7 @@ def main(argv=None):
     ap.add_argument("--min-frames", type=int, default=100)
     ap.add_argument("--max-frames", type=int, default=1500)
     ap.add_argument("--clip-frames", type=int, default=200)
+    ap.add_argument("--window", type=int, help="measure EncodeSession(window=W) against the unwindowed session instead")
     args = ap.parse_args(argv)
     if args.repeats < 5:
         ap.error("--repeats: at least 5")
@@ -143,8 +186,11 @@ def main(argv=None):
                   lengths=f"uniform {args.min_frames}..{args.max_frames} frames, numpy default_rng(1234) (a stand-in for a corpus)",
                   repeats=args.repeats, runs=[])
     print(record["cfg"] + "; arrival model: " + record["arrival_model"], flush=True)
-    first_latent(eng, args, record)
-    feed_rounds(eng, args, record)
+    if args.window is not None:
+        window_rounds(eng, args, record)
+    else:
+        first_latent(eng, args, record)
+        feed_rounds(eng, args, record)
     print(json.dumps(record))
     return 0 if all(r["same"] for r in record["runs"]) else 1
 

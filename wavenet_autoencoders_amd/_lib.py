@@ -135,6 +135,8 @@ SIGNATURES = {
     "wae_enc_conv_fwd_list": (c_i32, [c_vp] * 5 + [c_i32, c_vp] + [c_i32] * 11 + [c_vp]),
     # x, w, bias, y, recs, nrecs, ntiles, et, in_pitch, out_pitch, Cin, Cout, k, stride, pad, relu, residual, stream
     "wae_enc_conv_fwd_ranges": (c_i32, [c_vp] * 5 + [c_i32] * 12 + [c_vp]),
+    # the ranges entry's arguments, records wae_enc_ring (8 x int32) in the place of wae_enc_range
+    "wae_enc_conv_fwd_rings": (c_i32, [c_vp] * 5 + [c_i32] * 12 + [c_vp]),
     "wae_vq_nearest": (c_i32, [c_vp] * 6 + [c_i32] * 4 + [c_f32, c_vp]),
     # lat, quant, idx, segs, nsegs, D, pitch, K, c_loss, first, sqerr, hist, item_stats, out, stream
     "wae_vq_stats_segments": (c_i32, [c_vp] * 4 + [c_i32] * 4 + [c_f32, c_i32] + [c_vp] * 5),
@@ -143,6 +145,8 @@ SIGNATURES = {
     "wae_upsample_stage_fwd_list": (c_i32, [c_vp] * 4 + [c_i32] * 9 + [c_vp]),
     # the list entry's arguments, records wae_ups_range in the place of wae_ups_seg
     "wae_upsample_stage_fwd_ranges": (c_i32, [c_vp] * 4 + [c_i32] * 9 + [c_vp]),
+    # the ranges entry's arguments, records wae_ups_ring (8 x int32) in the place of wae_ups_range
+    "wae_upsample_stage_fwd_rings": (c_i32, [c_vp] * 4 + [c_i32] * 9 + [c_vp]),
     # in, out, segs, nsegs, ntiles, in_pitch, C, Cp, dtype, stream
     "wae_to_btc_list": (c_i32, [c_vp] * 3 + [c_i32] * 6 + [c_vp]),
     "wae_gproj_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp] + [c_i32] * 6 + [c_vp, c_vp]),

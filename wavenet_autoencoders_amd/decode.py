@@ -496,6 +496,8 @@ class _Feed:
     max_frames: Optional[int] = None
     given: Optional[bool] = None    # whether the draws come with the feeds (fixed by the first feed)
     drawn: int = 0                  # steps the draws cover
+    slot: int = -1                  # a windowed session: the clip's ring in every arena (base = slot * window, cap = window)
+    doff: int = 0                   # ... and the step of the first draw still held: uni / u_mix / draw are [doff, drawn)
 
 
 class DecodeSession:
@@ -508,10 +510,17 @@ class DecodeSession:
     A clip may also join before its conditioning exists: open() / feed() / feed_list() / end() ("Clips that are fed while
     they decode").  step() then decodes min(chunk, ready - pos) steps of it, `ready` being the audio-rate conditioning rows that no
     later frame can change; its result dict carries `ready`, and `done` is true only once the clip has ended and pos == T.  The bits
-    are those of the clip decoded whole, whatever the feeding."""
+    are those of the clip decoded whole, whatever the feeding.
+    window=W (latent frames, at least packing.feed_window_min(scales)): the clips joined with open() live in constant memory
+    (include/wae.h: wae_upsample_stage_fwd_rings).  Every open clip owns a RING of W * prod(scales[:i]) columns in
+    stage i's arena and of W * prod(scales) c_up rows, column u at slot * period + u % period; nothing is copied when a clip grows,
+    and the ring of any clip that left goes to the next one.  One call feeds a clip at most max_feed frames, and -- back-pressure --
+    never rows that would overwrite c_up rows it has not decoded: room(h) says how many frames it can take now, and grows as step()
+    advances.  The draws step() has consumed are dropped.  Clips joined with add / add_list are untouched.  The bits do not depend
+    on the window: the ring is an address, never an operand."""
 
     def __init__(self, eng, mode="sample", coop=False, slots=None, teams=None, want_logits=False, c_is_upsampled=False,
-                 log_scale_min=-7.0, clamp_log_scale=False):
+                 log_scale_min=-7.0, clamp_log_scale=False, window=None):
         g = eng.g
         if g.scalar_input and coop and not eng.ar_scalar_coop:
             raise NotImplementedError("decode_session(coop=True): scalar-input decoders decode their sessions on the one-CU slots "
@@ -529,6 +538,14 @@ class DecodeSession:
         self._keep = None
         # open clips (open / feed / end): per-stage channel-major arenas and the time-major c_up rows, in latent frames of room
         self._fa, self._fa_cup, self._fa_mul, self._fa_cap, self._fa_top, self._fa_pending = None, None, None, 0, 0, False
+        self.window, self.max_feed, self._fa_free = None if window is None else int(window), None, []
+        if self.window is not None:
+            scales = self._feed_geometry("decode_session(window=)")
+            if self.window < P.feed_window_min(scales):
+                prod, look = P.feed_lookahead(scales)
+                raise ValueError(f"decode_session: window {self.window} is below the minimum of {P.feed_window_min(scales)} latent frames "
+                                 f"(the c_up ring holds the {look} rows an open clip holds back and at least one frame of {prod})")
+            self.max_feed = P.feed_window_max_feed(scales, self.window)
 
     # ---- the session's device state: once, at the first add
     def _open_device(self):
@@ -676,6 +693,8 @@ class DecodeSession:
         scales = self._feed_geometry("decode_session.reserve_frames")
         self._open_device()
         n = int(n)
+        if self.window is not None:     # whole rings: slot j is the frames [j W, (j + 1) W) of room
+            n = -(-n // self.window) * self.window
         if n <= self._fa_cap:
             return
         eng, g, dev = self.eng, self.eng.g, self.eng.device
@@ -688,9 +707,60 @@ class DecodeSession:
             for new, old in zip(fa, self._fa):
                 new[:, :old.shape[1]] = old
             cup[:self._fa_cup.shape[0]] = self._fa_cup
+        if self.window is not None:
+            self._fa_free += list(range(n // self.window - 1, self._fa_cap // self.window - 1, -1))
         self._fa, self._fa_cup, self._fa_cap, self._fa_mul = fa, cup, n, mul
         for c in self.clips.values():
             self._bind(c)
+
+    @property
+    def arena_bytes(self):
+        """bytes of the arenas of the open clips (windowed: nslots rings, whatever the clips' lengths)"""
+        return sum(a.numel() * a.element_size() for a in (self._fa or []) + ([self._fa_cup] if self._fa_cup is not None else []))
+
+    def _ring(self, c):
+        """a windowed session: the ring of clip c -- the one freed last, else the arenas grow by rings, geometrically"""
+        if not self._fa_free:
+            self.reserve_frames(max(2 * self._fa_cap, 4 * self.window))
+        f = c.feed
+        f.slot = self._fa_free.pop()
+        f.base, f.cap = f.slot * self.window, self.window
+        self._bind(c)
+
+    def room(self, handle):
+        """A windowed session: the latent frames the open clip can take in one call now -- at most max_feed, and no more than keep
+        its final rows within window * prod(scales) of the rows it has decoded; grows as step() advances."""
+        c = self.clips[handle]
+        if c.feed is None or self.window is None:
+            raise ValueError(f"decode_session.room: clip {handle} is not an open clip of a windowed session")
+        prod, look = P.feed_lookahead(self._feed_geometry("decode_session.room"))
+        f = c.feed      # the rows final after n frames: prod (frames + n - 1) - look <= pos + window prod
+        return 0 if f.ended else max(0, min(self.max_feed, (c.pos + self.window * prod + look) // prod + 1 - f.frames))
+
+    def cond_rows(self, handle, lo, hi):
+        """A copy of the rows [lo, hi) of an open clip's conditioning (c_up) while they are held: rows that are final and, in a
+        windowed session, not yet overwritten -- the last window * prod(scales) of them.  ValueError once they are not."""
+        c = self.clips[handle]
+        if c.feed is None:
+            raise ValueError(f"decode_session.cond_rows: clip {handle} joined whole (add)")
+        if self._fa_pending:
+            self.feed_list({})
+        lo, hi, ready = int(lo), int(hi), c.feed.ready
+        period = c.c_up.shape[0]
+        first = max(0, ready - period) if self.window is not None else 0
+        if not first <= lo <= hi <= ready:
+            raise ValueError(f"decode_session.cond_rows: clip {handle} holds the rows [{first}, {ready}), not [{lo}, {hi})")
+        return self._cup_rows(c, lo, hi - lo).clone()
+
+    def _cup_rows(self, c, lo, n):
+        """rows [lo, lo + n) of clip c's conditioning: a slice, or -- a ring -- two pieces where they wrap"""
+        if c.feed is None or self.window is None:
+            return c.c_up[lo:lo + n]
+        period = c.c_up.shape[0]
+        a = lo % period
+        if a + n <= period:
+            return c.c_up[a:a + n]
+        return torch.cat([c.c_up[a:], c.c_up[:a + n - period]])
 
     def _bind(self, c):
         if c.feed is not None and self._fa_cup is not None:
@@ -753,7 +823,9 @@ class DecodeSession:
         c = _ArClip(T=0, slot=slot, c_up=None, forced=forced, n_forced=nf, init=init, uni=None, u_mix=None, draw=None,
                     feed=_Feed(max_frames=None if max_T is None else int(max_T) // prod))
         self.clips[h] = c
-        if c.feed.max_frames is not None:
+        if self.window is not None:
+            self._ring(c)
+        elif c.feed.max_frames is not None:
             self._place(c, c.feed.max_frames)
         eng.hold("session_add", gid32, zb)
         return h
@@ -781,6 +853,9 @@ class DecodeSession:
             raise ValueError(f"{who}: clip {handle} ends at {T} steps beyond the {f.drawn} draws supplied")
         if self.mode == 0 and c.n_forced < T:
             raise ValueError(f"{who}: mode 'logits' is teacher-forced: test_inputs must cover all {T} steps")
+        if self.window is not None and T - c.pos > self.window * self._fa_mul[-1]:
+            raise ValueError(f"{who}: clip {handle}: its {T} rows with {c.pos} decoded do not fit the {self.window * self._fa_mul[-1]} "
+                             f"rows of its c_up ring: step first")
         f.ended, c.T, self._fa_pending = True, T, True
 
     def _feed_draws(self, who, h, c, frames, after, draws):
@@ -861,12 +936,23 @@ class DecodeSession:
             n = int(shape[1])
             if f.max_frames is not None and f.frames + n > f.max_frames:
                 raise ValueError(f"{who}: clip {h}: {f.frames + n} frames are beyond max_T ({f.max_frames} frames)")
+            if self.window is not None and n:
+                if (f.frames + n) * prod >= 2 ** 31:
+                    raise ValueError(f"{who}: clip {h}: {f.frames + n} frames reach 2^31 rows")
+                if n > self.max_feed:
+                    raise ValueError(f"{who}: clip {h}: a feed of {n} frames; a window of {self.window} admits max_feed = {self.max_feed} "
+                                     f"per call")
+                if n > self.room(h):
+                    raise ValueError(f"{who}: clip {h}: a feed of {n} frames would overwrite conditioning rows it has not decoded "
+                                     f"(room {self.room(h)}: {max(0, prod * (f.frames + n - 1) - look)} final rows, {clip.pos} decoded, a ring "
+                                     f"of {self.window * prod}); step first")
             new[h] = n
             if self.mode == 2 or any(d is not None for d in draws):     # (the rows final after this feed: packing.feed_ready)
                 got[h] = self._feed_draws(who, h, clip, n, max(0, prod * (f.frames + n - 1) - look), draws)
         # everything is checked: room, then the plan over every open clip with rows to run
+        ring = self.window is not None
         for h, n in new.items():
-            if n:
+            if n and not ring:
                 self._place(self.clips[h], self.clips[h].feed.frames + n)
         todo = [(h, c) for h, c in self.clips.items() if c.feed is not None
                 and (new.get(h, 0) or c.feed.frames != c.feed.planned or c.feed.ended != c.feed.ended_planned)]
@@ -876,14 +962,26 @@ class DecodeSession:
         scales = scales or self._feed_geometry(who)
         if eng.weights_dirty:
             eng.prepare_weights()
-        plan = P.session_feed_plan(scales, [(c.feed.base, c.feed.planned, c.feed.ended_planned, c.feed.frames + new.get(h, 0), c.feed.ended)
-                                            for h, c in todo])
+        if ring:    # the planner refuses what a ring cannot hold, before anything is launched
+            plan = P.session_feed_plan_rings(scales, [(c.feed.slot, c.feed.planned, c.feed.ended_planned, c.feed.frames + new.get(h, 0),
+                                                       c.feed.ended, c.pos) for h, c in todo], self.window)
+        else:
+            plan = P.session_feed_plan(scales, [(c.feed.base, c.feed.planned, c.feed.ended_planned, c.feed.frames + new.get(h, 0),
+                                                 c.feed.ended) for h, c in todo])
         fed = [(h, self.clips[h]) for h, n in new.items() if n]
         parts, conv = [plan.table], None
         if fed:     # the new frames, packed in this call's order, and where they go in stage 0's arena
             ns = [new[h] for h, _ in fed]
+            dst = [c.feed.base + c.feed.frames for _, c in fed]
+            if ring:    # a feed that crosses its ring's end is two segments (conv_in is pointwise at cin_pad 0: any split, the same bytes)
+                W, pieces = self.window, []
+                for (_, c), n in zip(fed, ns):
+                    a = c.feed.frames % W
+                    first = min(n, W - a)
+                    pieces += [(c.feed.base + a, first)] + ([(c.feed.base, n - first)] if n > first else [])
+                dst, ns = [p[0] for p in pieces], [p[1] for p in pieces]
             segs, tiles, et, _ = P.enc_list_tables(ns, 1, 1, 0)
-            segs[:, 2] = [c.feed.base + c.feed.frames for _, c in fed]
+            segs[:, 2] = dst
             conv = (plan.table.size, plan.table.size + segs.size, len(segs), len(tiles), et, int(sum(ns)))
             parts += [segs.reshape(-1), tiles.reshape(-1)]
             if not g.conv_in:       # the plain network: the frames are stage 0's input as they are
@@ -903,10 +1001,10 @@ class DecodeSession:
         for ln in plan.launches:
             w = eng.eff[eng.lay.off(P.up_stage_name(g, ln.stage) + ".weight_v"):]
             out = self._fa_cup if ln.last else self._fa[ln.stage + 1]
-            L.check(eng.lib.wae_upsample_stage_fwd_ranges(L.ptr(self._fa[ln.stage]), L.ptr(w), L.ptr(out), L.ptr(table[ln.rec_off:]),
-                                                          ln.nrecs, ln.ntiles, self._fa[ln.stage].shape[1],
-                                                          out.shape[0] if ln.last else out.shape[1], g.Cc, ln.s, int(ln.last), g.Ccp,
-                                                          eng.dt, eng.stream()), "upsample_stage (ranges)")
+            entry = eng.lib.wae_upsample_stage_fwd_rings if ring else eng.lib.wae_upsample_stage_fwd_ranges
+            L.check(entry(L.ptr(self._fa[ln.stage]), L.ptr(w), L.ptr(out), L.ptr(table[ln.rec_off:]), ln.nrecs, ln.ntiles,
+                          self._fa[ln.stage].shape[1], out.shape[0] if ln.last else out.shape[1], g.Cc, ln.s, int(ln.last), g.Ccp, eng.dt,
+                          eng.stream()), "upsample_stage (rings)" if ring else "upsample_stage (ranges)")
         eng.hold("session_feed", table, x)
         moved = {}
         for (h, c), ready in zip(todo, plan.ready):
@@ -936,11 +1034,23 @@ class DecodeSession:
         cat = lambda old, a: a if old is None or a is None else torch.cat([old, a])  # noqa: E731
         c.uni, c.u_mix, c.draw, f.drawn = cat(c.uni, uni), cat(c.u_mix, um), cat(c.draw, dr), f.drawn + n
 
+    def _drop_draws(self, c):
+        """a windowed clip's draws that step() has consumed go: uni / u_mix / draw keep [pos, drawn) -- copied out of the longer
+        tensor once the consumed part outweighs the rest, so the memory held stays within twice the live draws"""
+        f = c.feed
+        gone = c.pos - f.doff
+        if gone < max(f.drawn - c.pos, 256):
+            return
+        keep = lambda a: None if a is None else a[gone:].clone()  # noqa: E731
+        c.uni, c.u_mix, c.draw, f.doff = keep(c.uni), keep(c.u_mix), keep(c.draw), c.pos
+
     def drop(self, handle):
         """Cancels a clip: it leaves the session and its ring is free for the next add."""
         c = self.clips.pop(handle)
         self.free.append(c.slot)
-        if c.feed is not None:      # the clip's columns: the top of the arenas falls back where it was the last, and to 0 with the last open clip
+        if c.feed is not None and self.window is not None:
+            self._fa_free.append(c.feed.slot)
+        elif c.feed is not None:    # the clip's columns: the top of the arenas falls back where it was the last, and to 0 with the last open clip
             if c.feed.base + c.feed.cap == self._fa_top:
                 self._fa_top = c.feed.base
             if not any(k.feed is not None for k in self.clips.values()):
@@ -972,8 +1082,10 @@ class DecodeSession:
         dt, key = _io(g)
         sel = [clips[int(i)] for i in plan.clips]
         ns, offs, total = [int(x) for x in plan.lengths], [int(x) for x in plan.offsets], plan.total
-        cut = lambda name, on=True: torch.cat([getattr(c, name)[c.pos:c.pos + n] for c, n in zip(sel, ns)]) if on else None  # noqa: E731
-        c_up = cut("c_up", g.Ccp)
+        # (the draws of a windowed clip start at its feed.doff: the consumed ones are dropped)
+        at = lambda c: c.pos - (c.feed.doff if c.feed is not None else 0)  # noqa: E731
+        cut = lambda name, on=True: torch.cat([getattr(c, name)[at(c):at(c) + n] for c, n in zip(sel, ns)]) if on else None  # noqa: E731
+        c_up = torch.cat([self._cup_rows(c, c.pos, n) for c, n in zip(sel, ns)]) if g.Ccp else None
         # the forced steps: a clip's forced prefix where the span lies in it, else -- a continuation -- the previous span's last output
         nfs, inputs = [0] * len(sel), None
         if any(c.pos > 0 or c.n_forced > 0 for c in sel):
@@ -1014,6 +1126,8 @@ class DecodeSession:
         for i, c, n, off in zip(plan.clips, sel, ns, offs):
             h = handles[int(i)]
             c.pos += n
+            if self.window is not None and c.feed is not None:
+                self._drop_draws(c)
             if out is not None:
                 c.last = out[off + n - 1:off + n]
             done = c.pos >= c.T and (c.feed is None or c.feed.ended)
@@ -1030,6 +1144,7 @@ class DecodeSession:
         self.clips.clear()
         self._closed = True
         self.ring = self.zb = self.exchange = self._keep = self._fa = self._fa_cup = None
+        self._fa_free = []
 
     def __enter__(self):
         return self

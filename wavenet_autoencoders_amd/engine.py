@@ -501,7 +501,7 @@ class WaeEngine:
             stats["keep"].append(table)
         return res
 
-    def encode_session(self, want_latents: bool = False) -> EncodeSession:
+    def encode_session(self, want_latents: bool = False, window: Optional[int] = None) -> EncodeSession:
         """An encode session: encode_list for utterances whose feature frames still arrive (include/wae.h: wae_enc_conv_fwd_ranges).
         h = sess.open(max_frames=None) joins an open utterance; sess.feed_list({h: feats (c_in, f), ...}, ended=()) appends frames
         and returns, per utterance, the latent frames no later frame can change -- dict(quant, idx, latents | None, final, done); with
@@ -509,8 +509,11 @@ class WaeEngine:
         its handle in `ended`).  One call is one upload of the new frames, one table upload, at most eleven range launches and one
         quantiser call, whatever the number of utterances.  An utterance's chunks, concatenated, are bit for bit
         encode_list([whole])[0]; the `quant` chunks are what DecodeSession.feed_list takes.  sess.drop(h) cancels, sess.close() (or
-        leaving the `with` block) frees everything.  ValueError: an engine without an encoder."""
-        return EncodeSession(self, want_latents=want_latents)
+        leaving the `with` block) frees everything.  ValueError: an engine without an encoder.
+        window=W (feature frames): a session in constant memory -- every open utterance lives in a ring of about W / ENC_ARENA_DIV[l]
+        columns per layer (include/wae.h: wae_enc_conv_fwd_rings), nothing is copied when it grows, one call feeds
+        an utterance at most sess.max_feed frames, and the chunks are the same bits.  ValueError: a window below the minimum."""
+        return EncodeSession(self, want_latents=want_latents, window=window)
 
     def upsample_forward(self, c: torch.Tensor, out: torch.Tensor, save: Optional[Saved] = None):
         """a3: c (B,Cc,Tc) fp32 -> out (B, (Tc - 2 cin_pad) * prod(scales), Ccp) time-major compute dtype.  ConvInUpsampleNetwork
@@ -1325,7 +1328,7 @@ class WaeEngine:
 
     def decode_session(self, mode: str = "sample", coop: bool = False, slots: Optional[int] = None, teams: Optional[int] = None,
                        want_logits: bool = False, c_is_upsampled: bool = False, log_scale_min: float = -7.0,
-                       clamp_log_scale: bool = False) -> DecodeSession:
+                       clamp_log_scale: bool = False, window: Optional[int] = None) -> DecodeSession:
         """A decode session: decode_list's ragged clips, streamed (include/wae.h: the wae_ar_generate*_spans entries).  Clips join with
         sess.add(item) at any time between two rounds, sess.step(chunk) decodes the next `chunk` steps of every live clip in ONE launch
         and returns them per clip, sess.drop(handle) cancels a clip, sess.close() (or leaving the `with` block) frees everything.
@@ -1344,9 +1347,12 @@ class WaeEngine:
         wae_upsample_stage_fwd_ranges launch per stage and one table upload per call -- and ends with sess.end(h); step() decodes the
         rows of it that no later frame can change (`ready` in its result).  Its bits are those of the clip decoded whole (DESIGN.md
         3.4.3); cin_pad > 0, an upsample_activation and c_is_upsampled sessions are refused there with NotImplementedError.  In mode
-        "logits" an open clip decodes no further than its forced inputs, which must cover T by the time it ends."""
+        "logits" an open clip decodes no further than its forced inputs, which must cover T by the time it ends.
+        window=W (latent frames): the open clips in constant memory -- a ring of W frames per clip at every stage and of
+        W * prod(scales) c_up rows (include/wae.h: wae_upsample_stage_fwd_rings), the same bits; a call feeds a clip
+        at most sess.max_feed frames and never over rows it has not decoded (sess.room(h)); ValueError: a window below the minimum."""
         return DecodeSession(self, mode=mode, coop=coop, slots=slots, teams=teams, want_logits=want_logits, c_is_upsampled=c_is_upsampled,
-                             log_scale_min=log_scale_min, clamp_log_scale=clamp_log_scale)
+                             log_scale_min=log_scale_min, clamp_log_scale=clamp_log_scale, window=window)
 
     def decode_list_stream(self, items, chunk, **kw):
         """decode_list / decode_list_scalar in rounds of `chunk` steps: a generator over the rounds of a decode_session(**kw) that holds

@@ -393,6 +393,128 @@ def enc_feed_plan(clips) -> EncFeedPlan:
     return EncFeedPlan(launches, table, now[-1], q_off, q_cnt, int(q_cnt.sum()))
 
 
+# ---- the same utterances in RINGS of constant size (include/wae.h: wae_enc_conv_fwd_rings; EncodeSession(window=W))
+def _enc_final_forms():
+    """(A_l, D_l) per layer input l = 0..11 with enc_final_rows(F, False)[l] == max(0, (F - A_l) // D_l + 1): a block (k, s, pad k // 2)
+    maps max(0, (F - A) // D + 1) final inputs to max(0, (F - A - D (k - k // 2 - 1)) // (D s) + 1) final outputs, floors of floors
+    composing.  The last entry is enc_ready's (17, 4).  Once ended the counts are (F - 1) // D_l + 1: the form with A = 1."""
+    forms = [(1, 1)]
+    for k, s in ENC_LAYERS:
+        A, D = forms[-1]
+        forms.append((A + D * (k - k // 2 - 1), D * s))
+    assert [D for _, D in forms] == ENC_ARENA_DIV
+    return forms
+
+
+def enc_window_lag() -> List[int]:
+    """Columns of its INPUT that layer l of ENC_LAYERS must still hold between two feeds of an open utterance, at the worst phase:
+    with n input columns final, the next output that is not is t = (n - k + p) // s + 1 and its first tap t s - p = n - (k - s) -
+    (n - k + p) % s, so k - 1 columns at most -- [2, 2, 4, 4, 2, 2, 0, ...] for ENCODER_BLOCKS.  The residual's column t is the same
+    or later."""
+    return [k - 1 for k, _ in ENC_LAYERS]
+
+
+def enc_window_tail() -> List[int]:
+    """Columns that the END of an utterance adds at layer l's input beyond those final while it was open, at the worst phase:
+    ((F - 1) // D + 1) - ((F - A) // D + 1) <= ceil((A - 1) / D) with _enc_final_forms' (A, D).  The closing ranges write them while
+    the layer still reads its retained columns, so every ring has that many columns beyond its share of the window."""
+    return [-(-(A - 1) // D) for A, D in _enc_final_forms()[:-1]]
+
+
+def enc_window_span(n: int) -> int:
+    """Feature frames of window that a feed of n frames to an OPEN utterance needs, at the worst phase and layer: layer l's input gains
+    at most ceil(n / D_l) columns while its first enc_window_lag()[l] are still read -- max over l of D_l (ceil(n / D_l) + k_l - 1);
+    for ENCODER_BLOCKS 4 ceil(n / 4) + 8."""
+    n = int(n)
+    return max(D * (-(-n // D) + lag) for D, lag in zip(ENC_ARENA_DIV, enc_window_lag()))
+
+
+def enc_window_min() -> int:
+    """The smallest window of an encode session, in feature frames: the retained columns of the worst layer and one ENC_ROOM of feed"""
+    return max(D * lag for D, lag in zip(ENC_ARENA_DIV, enc_window_lag())) + ENC_ROOM
+
+
+def enc_window_max_feed(window: int) -> int:
+    """The most feature frames one call may feed an utterance of a session with this window: the largest n with enc_window_span(n) <=
+    window (the span grows with n).  ValueError: a window that is no multiple of ENC_ROOM or below enc_window_min()."""
+    W = int(window)
+    if W % ENC_ROOM != 0 or W < enc_window_min():
+        raise ValueError(f"encode window {W}: a multiple of {ENC_ROOM} feature frames, at least {enc_window_min()}")
+    n = W
+    while enc_window_span(n) > W:
+        n -= 1
+    return n
+
+
+def enc_ring_periods(window: int) -> List[int]:
+    """Columns of an utterance's ring at the input of every layer: window / ENC_ARENA_DIV[l] + enc_window_tail()[l]"""
+    enc_window_max_feed(window)
+    return [int(window) // D + t for D, t in zip(ENC_ARENA_DIV, enc_window_tail())]
+
+
+def enc_feed_plan_rings(clips, window: int) -> EncFeedPlan:
+    """enc_feed_plan for utterances that live in rings (EncodeSession(window=W)): `clips` are (slot, frames_before, ended_before,
+    frames, ended).  The same ranges per layer and clip, in records of 8 (include/wae.h: wae_enc_ring) {in_off, in_period, Tin,
+    out_off, out_period, t_lo, t_hi, tile0}: layer l's input ring of slot i is the columns [i P_l, (i + 1) P_l) of its arena,
+    P = enc_ring_periods(window); lin's output is linear (out_period 0), this call's new latents packed.  EncFeedPlan.records
+    does not apply: use ring_records(plan, i).
+    The planner checks, not the caller: ValueError before anything is launched for a feed of more than enc_window_max_feed(window)
+    frames, and for any layer where the columns final after this feed, less the first column its next output still reads (the first
+    tap of the first output that was not final BEFORE this feed: this call's own records read from there), exceed the ring."""
+    periods = enc_ring_periods(window)
+    max_feed = enc_window_max_feed(window)
+    cols = np.asarray([tuple(c) for c in clips], dtype=np.int64).reshape(-1, 5)
+    slot, f0, e0, f1, e1 = (cols[:, j] for j in range(5))
+    e0, e1 = e0 != 0, e1 != 0
+    bad = (f1 < f0) | (f0 < 0) | (slot < 0) | (e0 & (~e1 | (f1 != f0))) | (e1 & (f1 < 1))
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(f"enc_feed_plan_rings: clip {i}: slot {int(slot[i])}, frames {int(f0[i])} -> {int(f1[i])}, "
+                         f"ended {bool(e0[i])} -> {bool(e1[i])}")
+    if (f1 - f0 > max_feed).any():
+        i = int(np.argmax(f1 - f0 > max_feed))
+        raise ValueError(f"enc_feed_plan_rings: clip {i}: a feed of {int(f1[i] - f0[i])} frames; a window of {int(window)} admits "
+                         f"{max_feed} per call")
+    if ((slot + 1) * max(periods) >= 2 ** 31).any() or (f1 >= 2 ** 31).any():
+        raise ValueError("enc_feed_plan_rings: columns reach 2^31")
+    before, now = [f0], [f1]
+    for k, s in ENC_LAYERS:
+        before.append(_enc_final(before[-1], e0, k, s))
+        now.append(_enc_final(now[-1], e1, k, s))
+    for l, (k, s) in enumerate(ENC_LAYERS):
+        held = now[l] - np.maximum(before[l + 1] * s - k // 2, 0)
+        if (held > periods[l]).any():
+            i = int(np.argmax(held > periods[l]))
+            raise ValueError(f"enc_feed_plan_rings: clip {i}: layer {l} would hold {int(held[i])} columns in a ring of {periods[l]}")
+    q_cnt = now[-1] - before[-1]
+    q_off = _running(q_cnt)
+    launches, parts, at = [], [], 0
+    for l, (k, s) in enumerate(ENC_LAYERS):
+        j = np.nonzero(now[l + 1] > before[l + 1])[0]
+        if not j.size:
+            continue
+        lo, hi = before[l + 1][j], now[l + 1][j]
+        et = enc_list_et(hi - lo)
+        per = -(-(hi - lo) // et)
+        last = l == len(ENC_LAYERS) - 1
+        rec = np.zeros((j.size + 1, 8), dtype=np.int64)
+        rec[:-1, 0], rec[:-1, 1], rec[:-1, 2] = slot[j] * periods[l], periods[l], now[l][j]
+        rec[:-1, 3], rec[:-1, 4] = (q_off[j], 0) if last else (slot[j] * periods[l + 1], periods[l + 1])
+        rec[:-1, 5], rec[:-1, 6], rec[:-1, 7] = lo, hi, _running(per)
+        rec[-1, 7] = int(per.sum())
+        launches.append(EncFeedLaunch(l, k, s, k // 2, int(et), int(j.size), int(per.sum()), at))
+        parts.append(rec.reshape(-1))
+        at += rec.size
+    table = np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, dtype=np.int32)
+    return EncFeedPlan(launches, table, now[-1], q_off, q_cnt, int(q_cnt.sum()))
+
+
+def ring_records(plan, i: int) -> np.ndarray:
+    """the (nrecs + 1, 8) records of launch i of a ring plan (enc_feed_plan_rings, session_feed_plan_rings)"""
+    ln = plan.launches[i]
+    return plan.table[ln.rec_off:ln.rec_off + 8 * (ln.nrecs + 1)].reshape(ln.nrecs + 1, 8)
+
+
 UP_ACT_KINDS = {"ReLU": 1, "LeakyReLU": 2, "Tanh": 3, "Sigmoid": 4}      # include/wae.h: wae_act_fwd
 
 
@@ -732,6 +854,106 @@ def session_feed_plan(scales, clips) -> FeedPlan:
         rec = np.zeros((k.size + 1, 6), dtype=np.int64)
         rec[:-1] = np.stack([base[k] * mul[i], now[i][k], base[k] * mul[i + 1], lo, hi, _running(per)], axis=1)
         rec[-1, 5] = int(per.sum())
+        launches.append(FeedLaunch(i, s, last, int(k.size), int(per.sum()), at))
+        parts.append(rec.reshape(-1))
+        at += rec.size
+    table = np.concatenate(parts).astype(np.int32) if parts else np.zeros(0, dtype=np.int32)
+    return FeedPlan(launches, table, now[-1])
+
+
+# ---- the same clips in RINGS of constant size (include/wae.h: wae_upsample_stage_fwd_rings; DecodeSession(window=W))
+def feed_window_lag(scales) -> List[int]:
+    """Input frames that stage i must still hold between two feeds of an open clip: with n of them final the first output row that
+    is not is (n - 1) s, which reads the frames n - 2 .. n -- two, at every stage."""
+    return [2 for _ in scales]
+
+
+def feed_window_held(scales, k: int) -> List[int]:
+    """The most columns stage i's input ring holds during one call that feeds an open clip k frames and may end it, at the worst
+    phase: the columns final after the call less the first one its records read.  Stage 0: the k new frames and the 2 retained.
+    Stage i >= 1: its input grows by mul_i per frame, and the end adds the mul_i + look_i columns that waited for a next frame
+    (look_i = sum_{1 <= j < i} prod(scales[j:i])): mul_i (k + 1) + look_i + 2."""
+    sc = [int(s) for s in scales]
+    mul = [int(np.prod(sc[:i])) for i in range(len(sc))]
+    look = [sum(int(np.prod(sc[j:i])) for j in range(1, i)) for i in range(len(sc))]
+    return [int(k) + 2] + [mul[i] * (int(k) + 1) + look[i] + 2 for i in range(1, len(sc))]
+
+
+def feed_window_max_feed(scales, window: int) -> int:
+    """The most latent frames one call may feed a clip of a decode session with this window (0: the window is too small): the largest
+    k whose feed_window_held fits the rings of window * prod(scales[:i]) columns."""
+    sc, W = [int(s) for s in scales], int(window)
+    mul = [int(np.prod(sc[:i])) for i in range(len(sc))]
+    k = max(W, 0)
+    while k > 0 and any(h > W * m for h, m in zip(feed_window_held(sc, k), mul)):
+        k -= 1
+    return k
+
+
+def feed_window_min(scales) -> int:
+    """The smallest window of a decode session, in latent frames: one frame of feed at every stage, and c_up rows for the lookahead
+    an open clip holds back plus one frame (feed_lookahead)."""
+    prod, look = feed_lookahead(scales)
+    W = -(-(look + prod) // prod)
+    while feed_window_max_feed(scales, W) < 1:
+        W += 1
+    return W
+
+
+def session_feed_plan_rings(scales, clips, window: int) -> FeedPlan:
+    """session_feed_plan for clips that live in rings (DecodeSession(window=W)): `clips` are (slot, frames_before, ended_before,
+    frames, ended, pos), pos being the audio-rate rows the clip has decoded.  The same ranges per stage and clip, in records of 8
+    (include/wae.h: wae_ups_ring) {in_off, in_period, Tin, out_off, out_period, t_lo, t_hi, tile0}: stage i's input ring of slot j is
+    the columns [j P_i, (j + 1) P_i) of its arena, P_i = window * prod(scales[:i]); the c_up ring, window * prod(scales) rows.
+    FeedPlan.records does not apply: use ring_records(plan, i).
+    The planner checks, not the caller -- ValueError before anything is launched: a window below feed_window_min, a stage whose
+    columns final after this call, less the first frame its records read (input frame final_out / s - 1 of BEFORE this call), exceed
+    its ring, and -- back-pressure -- c_up rows final after this call that would overwrite rows the clip has not decoded
+    (ready - pos > window * prod(scales))."""
+    sc, W = [int(s) for s in scales], int(window)
+    if not sc or min(sc) < 1:
+        raise ValueError(f"session_feed_plan_rings: scales {sc}: at least one stage, every scale >= 1")
+    if W < feed_window_min(sc):
+        raise ValueError(f"session_feed_plan_rings: window {W} is below the minimum of {feed_window_min(sc)} latent frames")
+    cols = np.asarray([tuple(c) for c in clips], dtype=np.int64).reshape(-1, 6)
+    slot, f0, e0, f1, e1, pos = (cols[:, k] for k in range(6))
+    e0, e1 = e0 != 0, e1 != 0
+    mul = [int(np.prod(sc[:i])) for i in range(len(sc) + 1)]
+    bad = (f1 < f0) | (f0 < 0) | (slot < 0) | (pos < 0) | (e0 & (~e1 | (f1 != f0)))
+    if bad.any():
+        i = int(np.argmax(bad))
+        raise ValueError(f"session_feed_plan_rings: clip {i}: frames {int(f0[i])} -> {int(f1[i])}, ended {bool(e0[i])} -> {bool(e1[i])}")
+    over = (np.maximum(f1, 1) * mul[-1] >= 2 ** 31) | ((slot + 1) * W * mul[-1] >= 2 ** 31)
+    if over.any():
+        raise ValueError(f"session_feed_plan_rings: clip {int(np.argmax(over))}: its rows reach 2^31")
+    before, now = [f0], [f1]
+    for s in sc:
+        before.append(np.where(e0, before[-1], np.maximum(before[-1] - 1, 0)) * s)
+        now.append(np.where(e1, now[-1], np.maximum(now[-1] - 1, 0)) * s)
+    for i, s in enumerate(sc):
+        held = now[i] - np.maximum(before[i + 1] // s - 1, 0)
+        if (held > W * mul[i]).any():
+            j = int(np.argmax(held > W * mul[i]))
+            raise ValueError(f"session_feed_plan_rings: clip {j}: stage {i} would hold {int(held[j])} columns in a ring of {W * mul[i]} "
+                             f"(a window of {W} admits {feed_window_max_feed(sc, W)} frames per call)")
+    full = now[-1] - pos > W * mul[-1]
+    if full.any():
+        j = int(np.argmax(full))
+        raise ValueError(f"session_feed_plan_rings: clip {j}: {int(now[-1][j])} final rows with {int(pos[j])} decoded do not fit the "
+                         f"{W * mul[-1]} rows of its c_up ring: step first")
+    launches, parts, at = [], [], 0
+    for i, s in enumerate(sc):
+        last = i == len(sc) - 1
+        tile = UPS_LIST_TILE_BTC if last else UPS_LIST_TILE_CT
+        k = np.nonzero(now[i + 1] > before[i + 1])[0]
+        if not k.size:
+            continue
+        lo, hi = before[i + 1][k], now[i + 1][k]
+        per = -(-(hi - lo) // tile)
+        rec = np.zeros((k.size + 1, 8), dtype=np.int64)
+        rec[:-1] = np.stack([slot[k] * W * mul[i], np.full(k.size, W * mul[i]), now[i][k], slot[k] * W * mul[i + 1],
+                             np.full(k.size, W * mul[i + 1]), lo, hi, _running(per)], axis=1)
+        rec[-1, 7] = int(per.sum())
         launches.append(FeedLaunch(i, s, last, int(k.size), int(per.sum()), at))
         parts.append(rec.reshape(-1))
         at += rec.size

@@ -145,7 +145,8 @@ class VQVAE(ArenaModel):
         with torch.no_grad():
             return self.engine().score_list(its, beta=beta, quantize_channels=quantize_channels, log_scale_min=log_scale_min)
 
-    def encode_session(self, want_latents=False):
+    def encode_session(self, want_latents=False, window=None):
         """encode for utterances whose features still arrive: WaeEngine.encode_session (open / feed_list / end), whose `quant` chunks,
-        concatenated per utterance, are bit for bit encode_list([x])[0]."""
-        return self.engine().encode_session(want_latents=want_latents)
+        concatenated per utterance, are bit for bit encode_list([x])[0].  window: the session in constant memory (rings of `window`
+        feature frames per open utterance), the same bits."""
+        return self.engine().encode_session(want_latents=want_latents, window=window)
