@@ -350,6 +350,32 @@ int wae_gproj_bwd(const float* eff, float* d_eff, int64_t wg_off, int64_t bias_o
                   int64_t ld, int32_t ones_col, int32_t B, int32_t L, int32_t G, int32_t Hp, int32_t Cg,
                   int32_t n_speakers, void* stream);
 
+/* ---- gradient accumulation (csrc/accum.hip; engine.py: accumulate / apply_step) ---------------------------
+ * wae_gproj_bwd that CONSUMES what it reads: wae_gproj_bwd's arguments and, statement for statement, its arithmetic -- d_eff gets
+ * the same bits from the same tiles -- and every element c1[l][row][ones_col + b], row < 2Hp, b < B, is 0.0f afterwards (a plain
+ * store by the thread that read it; nothing else of c1 is written).  Inside an accumulation window the weight-gradient tiles are
+ * not cleared between micro-batches: those columns are per CLIP (clip b's sum_t dz, chained here into conv1x1g and the embedding row
+ * of speaker gid[b]), so clip b of the next micro-batch must start from zero; every other tile element is a sum over clips and
+ * simply keeps growing.  One launch per 32 clips, no pass over the tiles.
+ * WAE_EINVAL before any launch for wae_gproj_bwd's refusals and for columns that do not fit: ld < ones_col + B, or
+ * c_layer_stride < 2Hp * ld. */
+int wae_gproj_bwd_consume(const float* eff, float* d_eff, int64_t wg_off, int64_t bias_off, int64_t layer_stride,
+                          const int32_t* gid, int64_t emb_off, const float* gvec, float* c1, int64_t c_layer_stride,
+                          int64_t ld, int32_t ones_col, int32_t B, int32_t L, int32_t G, int32_t Hp, int32_t Cg,
+                          int32_t n_speakers, void* stream);
+
+/* The logged numbers of an accumulation window, kept on the device.  sums (3 doubles): [0] = sum_i ce_weight_i * ce_i,
+ * [1] = sum_i vq_weight_i * vq_loss_i, [2] = the number of micro-batches; counts (K int32, or NULL without a quantiser): the
+ * micro-batches' code histograms added per code.  The caller zeroes both when it opens the window.
+ * out == NULL: one micro-batch is added -- ce / vq_loss (one float each on the device, NULL = absent) times their weights in
+ * double, hist (K counts, what wae_vq_nearest leaves) into counts.
+ * out != NULL (5 floats): the window is closed -- out = [ce, vq_loss, ce + vq_loss, perplexity, micro-batches]; the perplexity is
+ * that of the added counts with N = their sum, by the one function the dense search and wae_vq_stats_segments use
+ * (csrc/vq_stats.hpp): bit for bit what the search reports for the concatenated batch.  0 without counts.
+ * One workgroup, one launch, a fixed order of additions and no floating-point atomics: the same numbers from run to run. */
+int wae_accum_stats(double* sums, int32_t* counts, int32_t K, const float* ce, double ce_weight, const float* vq_loss,
+                    double vq_weight, const int32_t* hist, float* out, void* stream);
+
 /* ---- a5 first_conv on one-hot input = column gather + bias (wavenet.py:119-122,203) --------------------
  * idx (B*T) int32 class ids; table (O,Rp) fp32 = W^T ; x0 (B,T,Rp) dtype.  scalar mode: xs (B*T) fp32,
  * table (1,Rp). */

@@ -18,6 +18,7 @@ options:
     --dtype=<fp32|bf16|fp16>     Storage precision of the decoder stack [default: bf16].
     --synthetic                  Train on synthetic batches (no dataset needed).
     --max-steps=<N>              Stop after N steps (overrides max_train_steps).
+    --accum-steps=<M>            Loader batches per optimizer step (gradient accumulation) [default: 1].
 
 One process per GPU: launch with ``python -m torch.distributed.run --nproc-per-node N vqwae_train.py ...`` for data
 parallel training (gradients are all-reduced over RCCL; every rank reads its own shard).
@@ -166,7 +167,7 @@ def eval_model(eng, x, c, g, lengths, global_step, eval_dir, hp, use_ema, hop):
     return y_hat, y_target
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--dump-root")
     ap.add_argument("--checkpoint-dir", default="checkpoints")
@@ -186,7 +187,18 @@ def main(argv=None):
                     help="presets with max_time_steps null: score the dev utterances as packed lists at their own lengths "
                          "(evaluate(packed=True, packed_total=True): loss = NLL + commitment loss, commitment loss and perplexity "
                          "of every batch as one list, for class-id and scalar-input models); off: zero-padded batches")
+    ap.add_argument("--accum-steps", type=int, default=1,
+                    help="M loader batches per optimizer step (WaeEngine.train_step_accum): each is a micro-batch padded to its own "
+                         "longest clip (max_time_steps null), weighted so that the step is the one on all M as one batch; the learning-"
+                         "rate schedule, the checkpoint / eval intervals and global_step count optimizer steps.  1: one batch per step")
     args = ap.parse_args(argv)
+    if args.accum_steps < 1:
+        ap.error(f"--accum-steps {args.accum_steps}: at least 1 loader batch per optimizer step")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     if args.preset:
         with open(args.preset) as f:
@@ -253,6 +265,7 @@ def main(argv=None):
     t0, step0 = time.time(), step
     adam = adam_settings(hp)               # raises for anything the fused update is not (vqwae_train.py:1119-1120)
     lr = adam["lr"]
+    accum, pending, batches_seen = args.accum_steps, [], 0      # --accum-steps: the window's micro-batches (it may span two epochs)
     try:
         while epoch < hp.nepochs and step < max_steps:
             run = torch.zeros(3, dtype=torch.float64, device=device)
@@ -263,13 +276,25 @@ def main(argv=None):
                     lr = sched(lr, step, **hp.lr_schedule_kwargs)                     # vqwae_train.py:729-735
                 T = x.shape[1]
                 ln = None if bool((lengths == T).all()) else lengths
-                # ragged shards: the CE is normalised by the mask sum of the GLOBAL batch (vqwae_train.py:374-379 after :705)
-                # (every rank enters the mask-sum all-reduce or none does: decided by the preset, not by this rank's shard)
-                ce_scale, n_glob = D.step_ce_scale(lengths, T, x.shape[0], variable_length=hp.max_time_steps is None)
-                res = eng.train_step(x, c, g, lengths=ln, lr=lr, betas=adam["betas"], eps=adam["eps"],
-                                     weight_decay=adam["weight_decay"], clip_thresh=hp.clip_thresh,
-                                     ema_decay=hp.ema_decay, grad_sync=sync, ce_scale=ce_scale,
-                                     quantize_channels=hp.quantize_channels, log_scale_min=hp.log_scale_min)
+                batches_seen += 1
+                if accum > 1:
+                    # M loader batches are the micro-batches of one optimizer step; its numbers are the window's (apply_step), already
+                    # weighted -- the global masked mean over every rank's window, one mask-sum all-reduce per window
+                    pending.append((x, c, g, ln))
+                    if len(pending) < accum:
+                        continue
+                    res = eng.train_step_accum(pending, lr=lr, betas=adam["betas"], eps=adam["eps"], weight_decay=adam["weight_decay"],
+                                               clip_thresh=hp.clip_thresh, ema_decay=hp.ema_decay, grad_sync=sync,
+                                               quantize_channels=hp.quantize_channels, log_scale_min=hp.log_scale_min)
+                    pending, ce_scale = [], 1.0
+                else:
+                    # ragged shards: the CE is normalised by the mask sum of the GLOBAL batch (vqwae_train.py:374-379 after :705)
+                    # (every rank enters the mask-sum all-reduce or none does: decided by the preset, not by this rank's shard)
+                    ce_scale, n_glob = D.step_ce_scale(lengths, T, x.shape[0], variable_length=hp.max_time_steps is None)
+                    res = eng.train_step(x, c, g, lengths=ln, lr=lr, betas=adam["betas"], eps=adam["eps"],
+                                         weight_decay=adam["weight_decay"], clip_thresh=hp.clip_thresh,
+                                         ema_decay=hp.ema_decay, grad_sync=sync, ce_scale=ce_scale,
+                                         quantize_channels=hp.quantize_channels, log_scale_min=hp.log_scale_min)
                 step += 1
                 ce = res["ce"].float() * ce_scale               # rank mean of this = the global masked mean
                 vq = res.get("vq_loss", torch.zeros((), device=device)).float()
@@ -282,7 +307,7 @@ def main(argv=None):
                     if rank == 0:
                         dt = (time.time() - t0) / max(step - step0, 1)
                         print(f"step {step} loss {float(stats[0]):.4f} vq {float(stats[1]):.4f} perp {float(stats[2]):.2f} "
-                              f"gnorm {float(res['grad_norm']):.3f} lr {lr:.2e} {hp.batch_size * T / dt / 1e6:.2f} Msamples/s")
+                              f"gnorm {float(res['grad_norm']):.3f} lr {lr:.2e} {hp.batch_size * accum * T / dt / 1e6:.2f} Msamples/s")
                 if step > 0 and step % hp.train_eval_interval == 0 and rank == 0:                  # vqwae_train.py:834-836,772-774
                     print("[train_no_dev] Eval at train step {}".format(step))
                     eval_model(eng, x, c, g, lengths, step, os.path.join(args.checkpoint_dir, "intermediate", "train_no_dev_eval"),
@@ -319,6 +344,9 @@ def main(argv=None):
     finally:
         save_checkpoint(eng, step, epoch, args.checkpoint_dir, hp, rank, test_step, lr)   # vqwae_train.py:1140-1145
     if rank == 0:
+        if accum > 1:
+            print(f"{step - step0} optimizer steps of {accum} micro-batches: {batches_seen} batches consumed, "
+                  f"{len(pending)} of them not yet in a step")
         print("Finished")
     return 0
 

@@ -151,6 +151,9 @@ SIGNATURES = {
     "wae_to_btc_list": (c_i32, [c_vp] * 3 + [c_i32] * 6 + [c_vp]),
     "wae_gproj_fwd": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp] + [c_i32] * 6 + [c_vp, c_vp]),
     "wae_gproj_bwd": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64] + [c_i32] * 7 + [c_vp]),
+    "wae_gproj_bwd_consume": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64] + [c_i32] * 7 + [c_vp]),
+    # sums, counts, K, ce, ce_weight, vq_loss, vq_weight, hist, out, stream
+    "wae_accum_stats": (c_i32, [c_vp, c_vp, c_i32, c_vp, ctypes.c_double, c_vp, ctypes.c_double, c_vp, c_vp, c_vp]),
     "wae_check_ids": (c_i32, [c_vp, c_i64, c_i32, c_i32, c_vp, c_i32, c_vp]),
     "wae_onehot_to_ids": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp]),
     "wae_stream_delay": (c_i32, [ctypes.c_double, c_vp]),

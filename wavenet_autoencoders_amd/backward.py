@@ -962,27 +962,29 @@ def _finish_rows(eng, plan, lo, hi, which, acc):
                                         L.ptr(rows), r0, r1, L.ptr(eng.gn_acc) if acc else None, eng.stream()), "grad_finish")
 
 
-def _gproj_bwd(cx, l0, l1):
-    """the zb chain (conv bias + hoisted global conditioning, modules.py:148-152) of layers [l0, l1) into d_eff"""
+def _gproj_bwd(cx, l0, l1, consume=False):
+    """the zb chain (conv bias + hoisted global conditioning, modules.py:148-152) of layers [l0, l1) into d_eff; consume (a
+    micro-batch of an accumulation window): the entry that zeroes the per-clip columns it has read (csrc/accum.hip)"""
     eng, g, lay, sm = cx.eng, cx.eng.g, cx.eng.lay, cx.eng.sm
     wg_off = lay.off("wavenet.conv_layers.0.conv1x1g.weight_v") + l0 * lay.layer_stride if g.Cg > 0 else -1
-    L.check(eng.lib.wae_gproj_bwd(L.ptr(eng.eff), L.ptr(eng.d_eff), wg_off,
-                                  lay.off("wavenet.conv_layers.0.conv.bias") + l0 * lay.layer_stride, lay.layer_stride,
-                                  L.ptr(cx.gid32) if cx.use_gid else None, lay.offsets.get("wavenet.embed_speakers.weight", 0),
-                                  L.ptr(cx.gvec), ctypes.c_void_p(eng.cview["c1"].data_ptr() + l0 * cx.Z2 * sm["ld1"] * 4),
-                                  cx.Z2 * sm["ld1"], sm["ld1"], g.k * g.Rp + g.Ccp, cx.B, l1 - l0, g.G, g.Hp, max(g.Cg, 0),
-                                  int(g.n_speakers or 0), eng.stream()),
-            "gproj_bwd")
+    entry = eng.lib.wae_gproj_bwd_consume if consume else eng.lib.wae_gproj_bwd
+    L.check(entry(L.ptr(eng.eff), L.ptr(eng.d_eff), wg_off, lay.off("wavenet.conv_layers.0.conv.bias") + l0 * lay.layer_stride,
+                  lay.layer_stride, L.ptr(cx.gid32) if cx.use_gid else None, lay.offsets.get("wavenet.embed_speakers.weight", 0),
+                  L.ptr(cx.gvec), ctypes.c_void_p(eng.cview["c1"].data_ptr() + l0 * cx.Z2 * sm["ld1"] * 4),
+                  cx.Z2 * sm["ld1"], sm["ld1"], g.k * g.Rp + g.Ccp, cx.B, l1 - l0, g.G, g.Hp, max(g.Cg, 0),
+                  int(g.n_speakers or 0), eng.stream()),
+            "gproj_bwd_consume" if consume else "gproj_bwd")
 
 
-def _finish_layers(cx, l0, l1, with_head):
+def _finish_layers(cx, l0, l1, with_head, zb=True):
     """The weight gradients of layers [l0, l1) (and of the head) leave the dense tiles.  Split launches: scattered into the
     effective-weight arena d_eff, then the zb chain of those layers; disjoint slots, the tables never move -- the weight-norm
     backward and the norm follow in launches of their own (_hand_over, finish_grads, wae_clip_adam_ema).
     Gather pass (cx.finish, csrc/grad_finish.hip): ONE launch takes them from the tiles to eng.grads and sums their squares; the bias
     sums, the zb chain and the finish of the few rows those two produce run beside it on a side stream (each far too small to fill the
     machine, and none of them reads what the gather pass writes).  Returns that side work's completion event (a list, engine.branch)
-    or None.  d_eff keeps zeros in the slots the gather pass serves: nothing reads them."""
+    or None.  d_eff keeps zeros in the slots the gather pass serves: nothing reads them.
+    zb=False (the close of an accumulation window): the zb chain has run, consuming, behind every micro-batch."""
     eng, ws, st = cx.eng, cx.ws, cx.eng.stream()
     plan = cx.finish
     key = ("scatter_jobs", l0, l1, with_head, plan is not None)
@@ -991,7 +993,8 @@ def _finish_layers(cx, l0, l1, with_head):
     jobs = ws[key]
     if plan is None:
         L.check(eng.lib.wae_unpack_scatter_add_multi(jobs, len(jobs), st), "scatter layer and head gradients")
-        _gproj_bwd(cx, l0, l1)
+        if zb:
+            _gproj_bwd(cx, l0, l1)
         return None
     ls, seg = eng.lay.layer_stride, layer_segment(eng)
     lo, hi = seg[0] + l0 * ls, (seg[1] if with_head else seg[0] + l1 * ls)
@@ -999,7 +1002,8 @@ def _finish_layers(cx, l0, l1, with_head):
     def small():
         if jobs is not None:
             L.check(eng.lib.wae_unpack_scatter_add_multi(jobs, len(jobs), eng.stream()), "bias sums of the layer and head gradients")
-        _gproj_bwd(cx, l0, l1)
+        if zb:
+            _gproj_bwd(cx, l0, l1)
         _finish_rows(eng, plan, lo, hi, "rest", cx.finish_acc)
     if not eng.opt.side:
         small()
@@ -1021,6 +1025,11 @@ def _tn_behind_sweep(cx, sched, grad_sync):
         eng.join(cx.beside_done[0])
     fl = eng.flight
     fl.grads_done = None
+    if fl.accum is not None:
+        # a micro-batch of an accumulation window: the tiles keep adding up until finish_window -- nothing is scattered and nothing
+        # reaches eng.grads.  The zb chain alone is per micro-batch (its columns are per clip, under this batch's speaker ids)
+        _gproj_bwd(cx, 0, eng.g.layers, consume=True)
+        return
     if sched.kind == "split":
         done = _finish_layers(cx, 0, sched.cut, with_head=False)
         eng.join(done[0] if done else None)
@@ -1073,19 +1082,28 @@ def _head_backward(cx, xi, tg, ln, inv_count, ext_dy):
         L.check(lib.wae_onehot_rows(L.ptr(xi), L.ptr(ws["onehot"]), B * T, ws["onehot"].shape[-1], eng.dt, st), "onehot_rows")
 
 
-def _first_conv_grads(cx, x_ids, xi):
-    """dW[r][class] = sum_t dx0[t][r] onehot(id[t])[class];  dx0 = dxhat_0 / sqrt(.5)"""
-    eng, g, lib, ws, sm, B, T, st = cx.eng, cx.eng.g, cx.eng.lib, cx.ws, cx.eng.sm, cx.B, cx.T, cx.eng.stream()
-    ctab, fb = eng.cview["ctab"], eng.cview["fb"]
+def _first_conv_grads(cx, x_ids, xi, tile_only=False):
+    """dW[r][class] = sum_t dx0[t][r] onehot(id[t])[class];  dx0 = dxhat_0 / sqrt(.5).  tile_only (a micro-batch of an accumulation
+    window): the contraction into the tile alone; _first_conv_finish takes the tile to d_eff once, when the window closes."""
+    eng, g, ws, B, T = cx.eng, cx.eng.g, cx.ws, cx.B, cx.T
     if g.scalar_input:
         ws["xs1"][:, :, 0] = x_ids.to(ws["xs1"].dtype)
         ws["xs1"][:, :, 1] = 1.0
         ws["tt_first"].launch(B, T)
+    elif ws["tt_first"] is not None:
+        ws["ids"].copy_(xi)
+        ws["tt_first"].launch(B, T)
+    if not tile_only:
+        _first_conv_finish(cx)
+
+
+def _first_conv_finish(cx):
+    """the first conv's tile -> its bias gradient and both into d_eff"""
+    eng, g, lib, ws, sm, st = cx.eng, cx.eng.g, cx.eng.lib, cx.ws, cx.eng.sm, cx.eng.stream()
+    ctab, fb = eng.cview["ctab"], eng.cview["fb"]
+    if g.scalar_input:
         fb.copy_(ctab[g.Rp:2 * g.Rp])            # row 1: bias gradient; row 0 (weight) is scattered below
     else:
-        if ws["tt_first"] is not None:
-            ws["ids"].copy_(xi)
-            ws["tt_first"].launch(B, T)
         L.check(lib.wae_sum_rows(L.ptr(ctab), 0, g.Rp, g.O, g.Rp, g.Rp, L.ptr(fb), st), "first bias grad")
     jobs = ws.get("scatter_jobs_first")
     if jobs is None:
@@ -1098,19 +1116,30 @@ def _first_conv_grads(cx, x_ids, xi):
 
 def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: Optional[torch.Tensor],
                      gid: Optional[torch.Tensor], gvec: Optional[torch.Tensor] = None, ext_dy: Optional[torch.Tensor] = None,
-                     loss_scale: float = 1.0, grad_sync=None):
+                     loss_scale: float = 1.0, grad_sync=None, dy_factor: Optional[float] = None):
     """Backward of the last ``decoder_forward(..., train=True)`` with the same (B, T).  Fills ``eng.grads`` (flat arena,
     reference parameter layout incl. weight_g / weight_v) for every decoder parameter and returns dc (B,T,Ccp): the
     gradient wrt the upsampled local conditioning.  ``ext_dy`` (B,T,Op): external d loss / d logits (DMoL).
     ``grad_sync`` (distributed.GradSync): the layers' + head's slice of the gradient arena is finished (weight-norm backward
     of that slice) and handed to the all-reduce BEFORE the conditioning / first-conv / front-end gradients are computed, so
-    the collective runs under them."""
+    the collective runs under them.
+    ``dy_factor``: the factor on d loss / d logits, in place of loss_scale * grad_scale / count (a window's micro-batch: grad_scale over
+    the WINDOW's count, formed once).
+    Deferred finishing (``eng.flight.accum``, a step_state.Window): this backward is a micro-batch of an accumulation window.  The first
+    one packs the backward's weights and clears the accumulators as a plain step does; from the second on that launch is skipped
+    altogether (the weights, and so their packings, are the window's).  The sweep, the weight-gradient launches (`beside` included), the
+    zb chain -- which consumes its per-clip columns -- and the first conv's contraction run as now; nothing is scattered from the tiles,
+    eng.grads and the norm's accumulator are not touched.  finish_window does all that once."""
     B, T = x_ids.shape
     sv = saved_for(eng, B, T)
     _prepare_bwd(eng)
     g = eng.g
+    win = eng.flight.accum
+    if win is not None and grad_sync is not None:
+        raise ValueError("a micro-batch of an accumulation window takes no grad_sync: the arena goes out once, in apply_step")
     bwd_workspace(eng, B, T)
-    _await_packed_weights(eng)
+    if win is None or win.n == 0:
+        _await_packed_weights(eng)
     cx = _step(eng, B, T, sv.drop_seeds)
     ws = cx.ws
     if lengths is None:
@@ -1120,7 +1149,7 @@ def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: O
     xi = x_ids.to(torch.int32).contiguous() if not g.scalar_input else None
     tg = targets.to(torch.int32).contiguous() if targets is not None else None
     ln = lengths.to(torch.int32).to(eng.device).contiguous() if lengths is not None else None
-    _head_backward(cx, xi, tg, ln, loss_scale * eng.grad_scale / max(count, 1), ext_dy)
+    _head_backward(cx, xi, tg, ln, loss_scale * eng.grad_scale / max(count, 1) if dy_factor is None else dy_factor, ext_dy)
     cx.use_gid = gid is not None and "wavenet.embed_speakers.weight" in eng.lay.offsets
     cx.gid32 = gid.to(torch.int32).contiguous() if gid is not None else None
     cx.gvec = gvec
@@ -1128,6 +1157,8 @@ def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: O
     cx.finish = eng.flight.finish_used = _finish_plan(cx)
     cx.finish_acc = cx.finish is not None and grad_sync is None
     eng.flight.norm_summed = False
+    if win is not None:
+        win.static, win.shape = isinstance(ws["stream"], StaticStreamTable), (B, T)
     if cx.fold_dc and "dc32" not in ws:
         ws["dc32"] = torch.empty(B, T, 64, dtype=torch.float32, device=eng.device)
     eng.flight.grads_done = None
@@ -1148,7 +1179,7 @@ def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: O
     # ---- local-conditioning gradient over all layers at once ---------------------------------------------------------
     if g.Ccp and not cx.fold_dc:
         _tm(eng, B, T, g.Ccp, 0, 1.0, [(ws["dz"].data_ptr(), cx.dzs, cx.dzs, 0)], eng.w_bc.data_ptr(), ws["dc"].data_ptr(), g.Ccp)
-    _first_conv_grads(cx, x_ids, xi)          # (behind the gather pass, while the side stream's chain of small launches runs)
+    _first_conv_grads(cx, x_ids, xi, tile_only=win is not None)          # (behind the gather pass, while the side stream's chain of small launches runs)
     eng.join(cx.small_done[0] if cx.small_done else None)
     eng.hold("bwd", xi, tg, ln, cx.gid32)
     return ws["dc"]
@@ -1243,6 +1274,31 @@ def _debug_kernels(eng, B, T, l, flags_u=0, flags_x=0):
     ngx = len(cx.ws["gx"])
     gn, gc = cx.ws["gx"][(l + 1) % ngx], cx.ws["gx"][l % ngx]
     return (lambda: _k_u(cx, l, gn, cx.parts[0], flags_u)), (lambda: _k_x(cx, l, gn, gc, cx.parts[0], flags_x))
+
+
+def window_kind(eng, B, T):
+    """Which weight-gradient launch a (B, T) micro-batch fills the tiles with -- True: the static launch's transposed dW_out / dW_skip
+    blocks.  The gather pass reads ONE layout, so a window holds micro-batches of one kind."""
+    _prepare_bwd(eng)
+    return bool(use_stream_tn(eng) and static_tn_shape(eng, B, T))
+
+
+def finish_window(eng, win, grad_sync=None):
+    """The close of an accumulation window: everything _finish_layers / finish_grads do for a plain step, ONCE, on the tiles and d_eff
+    that the window's micro-batches added into -- the first conv's tile to d_eff, the bias row-sum scatter, the gather pass over tiles,
+    rest and outer rows (or the split launches: scatter, weight-norm backward), and with the gather pass the norm.  The tables are
+    those of the last micro-batch's workspace: they address engine-level buffers only.  -> eng.grads"""
+    cx = _step(eng, *win.shape)
+    fl = eng.flight
+    cx.finish = fl.finish_used = _finish_plan(cx)
+    cx.finish_acc = cx.finish is not None and grad_sync is None
+    _first_conv_finish(cx)
+    done = _finish_layers(cx, 0, eng.g.layers, with_head=True, zb=False)
+    eng.join(done[0] if done else None)
+    fl.grads_done, fl.norm_summed = None, False
+    if cx.finish is not None:
+        fl.grads_done, fl.norm_summed = layer_segment(eng), cx.finish_acc
+    return finish_grads(eng)
 
 
 def finish_grads(eng):

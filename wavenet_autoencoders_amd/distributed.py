@@ -261,6 +261,41 @@ def step_ce_scale(lengths: Optional[torch.Tensor], T: int, batch: int, variable_
     return ragged_ce_scale(lengths, T, batch, group)
 
 
+def accum_weights(metas, world: int = 1, group=None, total=None):
+    """The loss weights of an accumulation window (WaeEngine.accumulate): metas holds one (B_i, T_i, lengths_i | None,
+    latent_elements_i) per micro-batch -> ([(ce_weight_i, vq_weight_i), ...], N).
+    n_i = sum_b max(min(len_b, T_i) - 1, 0) loss positions (B_i (T_i - 1) without lengths: WaeEngine._masked_step_loss), N = sum n_i;
+    e_i = latent_elements_i, E = sum e_i; ce_weight_i = n_i / N, vq_weight_i = e_i / E (0 where the sum is 0).  Each micro-batch's
+    loss is a mean over its own n_i positions / e_i elements, so under these weights the window's loss is the masked mean over ALL
+    loss positions plus the mean over ALL latent elements: where the micro-batches share T, the loss of one step on the
+    concatenated batch.
+    world > 1: N is the all-reduced count of every rank's window and ce_weight_i = n_i * world / N, so that the rank MEAN of the
+    gradients is the gradient of the global masked mean (ragged_ce_scale's rule); vq_weight_i stays local (the rank mean of the
+    vq_loss terms, vqwae_train.py:759).  ONE collective per window for all its micro-batches, entered by every rank whatever its
+    shard looks like (step_ce_scale's global rule: never decided by what one rank observes).  total: the collective, a callable
+    local N -> global N (tests stub it); default: a 1-element all-reduce over `group`."""
+    ns, es = [], []
+    for B, T, lengths, elems in metas:
+        if lengths is None:
+            n = int(B) * max(int(T) - 1, 0)
+        else:
+            n = int(torch.clamp(torch.as_tensor(lengths).detach().to("cpu", torch.int64).clamp(max=int(T)) - 1, min=0).sum())
+        ns.append(n)
+        es.append(int(elems))
+    N = float(sum(ns))
+    if world > 1:
+        if total is not None:
+            N = float(total(N))
+        else:
+            tot = torch.tensor([N], dtype=torch.float64)
+            if dist.get_backend(group) == "nccl":
+                tot = tot.cuda()
+            dist.all_reduce(tot, op=dist.ReduceOp.SUM, group=group)
+            N = float(tot.item())
+    E = float(sum(es))
+    return [((n * world / N) if N > 0 else 0.0, (e / E) if E > 0 else 0.0) for n, e in zip(ns, es)], N
+
+
 def all_reduce_scalars(values: torch.Tensor, group=None, average: bool = True) -> torch.Tensor:
     """Logged per-rank scalars (loss, vq_loss, perplexity): the reference averages the per-replica values
     (vqwae_train.py:759 `torch.mean(vq_loss), torch.mean(perp)`), so the mean over ranks reproduces it."""

@@ -23,7 +23,7 @@ from . import packing as P
 from .decode import DecodeSession  # noqa: F401  (re-exported)
 from .encode import EncodeSession
 from .options import two_chains
-from .step_state import InFlight, Saved
+from .step_state import InFlight, Saved, Window
 
 
 def _dt(dtype) -> int:
@@ -112,6 +112,8 @@ class WaeEngine:
         # ---- step state: every attribute a later call creates or replaces starts here
         self.saved: Optional[Saved] = None      # the last train-mode forward's record; None: nothing to differentiate
         self.flight = InFlight()
+        self.window: Optional[Window] = None    # an open accumulation window (accumulate .. apply_step / discard_step)
+        self._vq_hist = None                    # the code counts of the last vq_forward (K + 1 int32; accumulate adds them to the window's)
         self._keep = {}                         # hold(): buffers passed by raw pointer, alive until their slot's next use
         # encode_list_stats: the list's quantiser totals over all its groups, (4,) fp32 on the device --
         # [vq_loss, perplexity, sum Tq, sum sqerr] (include/wae.h: wae_vq_stats_segments `out`); None before the first such call
@@ -147,6 +149,7 @@ class WaeEngine:
     @weights_dirty.setter
     def weights_dirty(self, dirty: bool):
         if dirty:
+            self._refuse_in_window("a change of the parameters")
             self._param_gen += 1
         else:
             self._prep_gen = self._param_gen
@@ -158,6 +161,13 @@ class WaeEngine:
     @_ar_packed.setter
     def _ar_packed(self, ok: bool):
         self._ar_gen = self._param_gen if ok else -1
+
+    def _refuse_in_window(self, what: str):
+        """Inside an accumulation window the weights, their packings and the gradient accumulators belong to the window: whatever would
+        change them is refused here, before any launch."""
+        if self.window is not None:
+            raise RuntimeError(f"{what} while an accumulation window is open ({self.window.n} micro-batch(es) accumulated): close it "
+                               "with apply_step() or drop it with discard_step() first")
 
     def check_errors(self):
         """Turn the kernels' sticky id-range flags into the IndexError the reference raises on the spot (nn.Embedding for a
@@ -265,6 +275,7 @@ class WaeEngine:
         return self.params[off:off + self.lay.numel(name)].view(self.lay.shapes[name])
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
+        self._refuse_in_window("load_state_dict")
         missing = [k for k in self.lay.offsets if k not in sd]
         extra = [k for k in sd if k not in self.lay.offsets]
         if strict and (missing or extra):
@@ -383,7 +394,7 @@ class WaeEngine:
         idx = torch.empty(B * Tq, dtype=torch.int64, device=self.device)
         quant = torch.empty_like(lat)
         stats = torch.empty(2, dtype=torch.float32, device=self.device)
-        hist = torch.empty(g.K + 1, dtype=torch.int32, device=self.device)
+        hist = self._vq_hist = torch.empty(g.K + 1, dtype=torch.int32, device=self.device)
         L.check(self.lib.wae_vq_nearest(L.ptr(lat), L.ptr(self.eff[self.lay.off("vq.embedding.weight"):]), L.ptr(idx),
                                         L.ptr(quant), L.ptr(stats), L.ptr(hist), B, D, Tq, g.K, beta, self.stream()),
                 "vq_nearest")
@@ -692,6 +703,8 @@ class WaeEngine:
         (saved: the record forward() began with the encoder's side; default: a new one).
         Returns dict(logits (B,O,T) | None, nll (B,T) | None, loss | None).
         """
+        if train and self.flight.accum is None:
+            self._refuse_in_window("a train-mode decoder_forward outside accumulate()")
         if self.weights_dirty:
             self.prepare_weights()
         g, lib, st = self.g, self.lib, self.stream()
@@ -1370,6 +1383,8 @@ class WaeEngine:
     def forward(self, x: torch.Tensor, c: torch.Tensor, gid: Optional[torch.Tensor], targets=None, lengths=None,
                 want_logits=True, train=False, beta: float = 0.25, dropout_on: bool = True, layer_events: Optional[list] = None):
         """VQVAE.forward (vqvae_model.py:66-72) -> dict(logits, vq_loss, perp, latents, idx, quant, loss)."""
+        if train and self.flight.accum is None:
+            self._refuse_in_window("a train-mode forward outside accumulate()")
         if self.weights_dirty:
             self.prepare_weights()
         sv = Saved(*x.shape) if train else None
@@ -1392,13 +1407,17 @@ class WaeEngine:
         self.opt_step = 0
 
     def backward(self, x, gid, targets, lengths, gvec=None, loss_scale: float = 1.0, ext_dy=None, vq_scale: float = None,
-                 grad_sync=None):
+                 grad_sync=None, dy_factor: Optional[float] = None):
         """Gradients of (masked CE or, with ext_dy (B,T,Op) = d loss / d logits, any output loss [+ vq_loss]) of the last
         train-mode forward -> self.grads (flat arena).  loss_scale multiplies the CE term, vq_scale (default: loss_scale) the
-        vq_loss term; grad_sync: see backward.decoder_backward."""
+        vq_loss term; grad_sync, dy_factor: see backward.decoder_backward.  Inside accumulate() (flight.accum) the gradients stay in the
+        accumulators and None is returned."""
         from . import backward as BW
+        if self.flight.accum is None:
+            self._refuse_in_window("backward outside accumulate()")
         self.flight.ev_dc = None
-        dc = BW.decoder_backward(self, x, targets, lengths, gid, gvec, ext_dy=ext_dy, loss_scale=loss_scale, grad_sync=grad_sync)
+        dc = BW.decoder_backward(self, x, targets, lengths, gid, gvec, ext_dy=ext_dy, loss_scale=loss_scale, grad_sync=grad_sync,
+                                 dy_factor=dy_factor)
         if self.g.Ccp and self.g.upsample_scales:
             if self.flight.ev_dc is not None:
                 # dc was complete when the sweep ended (the event): the front end's backward runs on a side stream beside the scatter of
@@ -1408,10 +1427,12 @@ class WaeEngine:
                 self.join(tail[0])
             else:
                 BW.frontend_backward(self, dc, loss_scale if vq_scale is None else vq_scale)
+        if self.flight.accum is not None:
+            return None
         return BW.finish_grads(self)
 
     def dmol_loss_and_grad(self, y_hat: torch.Tensor, y: torch.Tensor, lengths, num_classes: int = 65536,
-                           log_scale_min: float = -7.0, scale: float = 1.0):
+                           log_scale_min: float = -7.0, scale: float = 1.0, factor: Optional[float] = None):
         """DiscretizedMixturelogisticLoss (vqwae_train.py:382-401 with the shift of :766): y_hat (B,3M,T) fp32, y (B,T) fp32
         -> (masked mean loss, scale * d loss / d y_hat as (B,T,Op) in the compute dtype for decoder_backward's ext_dy).
         Per-step loss and its gradient: wae_dmol_loss_fwd; masked mean: wae_masked_mean; mask, 1/count and the transposition
@@ -1423,13 +1444,14 @@ class WaeEngine:
         dy = torch.empty_like(y_hat)
         L.check(lib.wae_dmol_loss_fwd(L.ptr(y_hat), L.ptr(yf), L.ptr(nll), L.ptr(dy), B, g.O // 3, T, int(num_classes),
                                       float(log_scale_min), 1, st), "dmol_loss")
-        loss, dyt, ln = self._masked_step_loss(nll, dy, lengths, scale)
+        loss, dyt, ln = self._masked_step_loss(nll, dy, lengths, scale, factor)
         self.hold("dmol", yf, nll, dy, ln)
         return loss, dyt
 
-    def _masked_step_loss(self, nll, dy, lengths, scale):
+    def _masked_step_loss(self, nll, dy, lengths, scale, factor=None):
         """Per-step losses nll (B,T) and their gradient dy (B,O,T) -> (masked mean over the shifted steps, scale * gradient of
-        that mean as (B,T,Op) in the compute dtype, device lengths): wae_masked_mean, wae_to_btc_masked."""
+        that mean as (B,T,Op) in the compute dtype, device lengths): wae_masked_mean, wae_to_btc_masked.  factor: the factor on the
+        masked gradient in place of scale * grad_scale / count (accumulate: grad_scale over the window's count)."""
         g, lib, st = self.g, self.lib, self.stream()
         B, T = nll.shape
         if lengths is None:
@@ -1441,11 +1463,12 @@ class WaeEngine:
         L.check(lib.wae_masked_mean(L.ptr(nll), L.ptr(ln), L.ptr(loss), B, T, st), "masked_mean")
         dyt = torch.zeros(B, T, g.Op, dtype=self.tdtype, device=self.device)
         L.check(lib.wae_to_btc_masked(L.ptr(dy), L.ptr(dyt), B, g.O, T, g.Op, self.dt, L.ptr(ln),
-                                      float(scale) * self.grad_scale / max(count, 1), st),
+                                      float(scale) * self.grad_scale / max(count, 1) if factor is None else float(factor), st),
                 "to_btc dy")
         return loss[0], dyt, ln
 
-    def mog_loss_and_grad(self, y_hat: torch.Tensor, y: torch.Tensor, lengths, log_scale_min: float = -7.0, scale: float = 1.0):
+    def mog_loss_and_grad(self, y_hat: torch.Tensor, y: torch.Tensor, lengths, log_scale_min: float = -7.0, scale: float = 1.0,
+                          factor: Optional[float] = None):
         """MixtureGaussianLoss (vqwae_train.py:404-422 with the shift of :766): y_hat (B,C,T) fp32 (C = 2 or 3M), y (B,T) fp32
         -> (masked mean loss, scale * d loss / d y_hat as (B,T,Op) in the compute dtype for decoder_backward's ext_dy).
         Per-step loss and its gradient: wae_mog_loss_fwd; masked mean and transposition as in dmol_loss_and_grad."""
@@ -1455,16 +1478,16 @@ class WaeEngine:
         nll = torch.empty(B, T, dtype=torch.float32, device=self.device)
         dy = torch.empty_like(y_hat)
         L.check(lib.wae_mog_loss_fwd(L.ptr(y_hat), L.ptr(yf), L.ptr(nll), L.ptr(dy), B, C, T, float(log_scale_min), 1, st), "mog_loss")
-        loss, dyt, ln = self._masked_step_loss(nll, dy, lengths, scale)
+        loss, dyt, ln = self._masked_step_loss(nll, dy, lengths, scale, factor)
         self.hold("mog", yf, nll, dy, ln)
         return loss, dyt
 
     def scalar_loss_and_grad(self, y_hat, y, lengths, quantize_channels: int = 65536, log_scale_min: float = -7.0,
-                             scale: float = 1.0):
+                             scale: float = 1.0, factor: Optional[float] = None):
         """The criterion of a scalar-input decoder after its output_distribution (vqwae_train.py:802-812)."""
         if self.g.output_distribution == "Normal":
-            return self.mog_loss_and_grad(y_hat, y, lengths, log_scale_min, scale=scale)
-        return self.dmol_loss_and_grad(y_hat, y, lengths, quantize_channels, log_scale_min, scale=scale)
+            return self.mog_loss_and_grad(y_hat, y, lengths, log_scale_min, scale=scale, factor=factor)
+        return self.dmol_loss_and_grad(y_hat, y, lengths, quantize_channels, log_scale_min, scale=scale, factor=factor)
 
     def train_step(self, x, c, gid, lengths=None, lr: float = 4e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                    weight_decay: float = 0.0, clip_thresh: float = 100.0, ema_decay: float = 0.9999, grad_hook=None,
@@ -1476,6 +1499,7 @@ class WaeEngine:
         the gradient of the global masked mean of vqwae_train.py:374-379); vq_loss keeps weight 1 (rank mean, :759).
         Class-id input: masked cross-entropy; scalar input (hparams input_type "raw" / "mulaw"): discretized mixture of logistics,
         or mixture of Gaussians with geometry output_distribution "Normal"."""
+        self._refuse_in_window("train_step")
         if self.exp_avg is None:
             self.init_optimizer()
         self.prepare_weights(side=True)
@@ -1541,3 +1565,172 @@ class WaeEngine:
         else:
             res["loss"] = out["loss"]
         return res
+
+    # ------------------------------------------------------------------ gradient accumulation: micro-batches into one optimizer step
+    def latent_elements(self, B: int, frames: int) -> int:
+        """Elements of the latents the encoder makes of (B, c_in, frames) features -- what one micro-batch's vq_loss is a mean over
+        (distributed.accum_weights); 0 without an encoder."""
+        if not self.g.has_encoder:
+            return 0
+        Tq = int(frames)
+        for k, s in P.ENCODER_BLOCKS:
+            Tq = (Tq + 2 * (k // 2) - k) // s + 1
+        return int(B) * self.g.Cc * Tq
+
+    def accumulate(self, x, c, gid, lengths=None, *, ce_weight: float = 1.0, vq_weight: float = 1.0, quantize_channels: int = 65536,
+                   log_scale_min: float = -7.0, ce_count: Optional[float] = None):
+        """One micro-batch of an accumulation window: train-mode forward and backward INTO the open window (the first call opens it);
+        apply_step() closes it with one finish and one optimizer step, discard_step() drops it.  Returns the micro-batch's own numbers
+        as device tensors, without a host sync: dict(ce) and, with an encoder, vq_loss and perp.
+        ce_weight: the factor on this micro-batch's masked-mean CE (or mixture loss) and its gradient -- train_step's ce_scale;
+        vq_weight: the factor on its vq_loss term -- backward's vq_scale.  distributed.accum_weights gives the pair under which the
+        window's gradient is that of one step on the concatenated batch.
+        ce_count: the window's count of loss positions N where ce_weight = n_i / N.  Given, the factor that reaches d loss / d logits
+        is grad_scale / ce_count, formed in double and cast once -- the bits the concatenated batch's backward multiplies by -- instead
+        of the product of ce_weight and grad_scale / n_i; ce_weight then only weights the logged loss.
+        Micro-batches of one window may differ in B and T (the accumulators are the engine's, the workspaces per shape), but all take
+        the same weight-gradient launch (16-bit: B <= 32 and the static launch's clip size, or neither).
+        Deferred finishing (backward.decoder_backward): the first micro-batch packs the weights and clears the accumulators; later
+        ones skip both; every one runs the sweep, the weight-gradient launches, the consuming zb chain and the front end's backward;
+        nothing is scattered, finished or applied before apply_step."""
+        from . import backward as BW
+        if self.flight.accum is not None:
+            raise RuntimeError("accumulate() inside accumulate()")
+        g = self.g
+        B, T = x.shape
+        kind = BW.window_kind(self, B, T)
+        win = self.window
+        if win is not None and win.n and win.static != kind:
+            raise ValueError(f"accumulate: a ({B}, {T}) micro-batch takes {'the static' if kind else 'another'} weight-gradient launch "
+                             "than the window's earlier ones, whose tiles the one finish reads: keep B <= 32 (and clips of one size "
+                             "class) within a window, or close it with apply_step() first")
+        if self.exp_avg is None:
+            self.init_optimizer()
+        early = False
+        if win is None:
+            if self.weights_dirty:
+                self.prepare_weights(side=True)
+                early = self._ev_wn is not None
+            dev = self.device
+            win = self.window = Window(sums=torch.zeros(3, dtype=torch.float64, device=dev),
+                                       counts=torch.zeros(g.K, dtype=torch.int32, device=dev) if g.has_encoder else None,
+                                       drop_calls=self.drop_calls)
+        if not g.scalar_input and x.dtype != torch.int32:
+            x = x.to(self.device, torch.int32).contiguous()
+        if gid is not None and gid.dtype != torch.int32:
+            gid = gid.to(self.device, torch.int32).contiguous()
+        if early:       # as train_step: the backward's packing (+ the clearing of the accumulators) beside the forward's, on the side stream
+            with self.branch(1, after=self._ev_wn) as self.flight.early_pack:
+                BW.pack_bwd_weights(self)
+        factor = None if ce_count is None else self.grad_scale / float(ce_count)
+        self.flight.accum = win
+        try:
+            if g.scalar_input:
+                fwd = self.forward if g.has_encoder else self.decoder_forward
+                out = fwd(x, c, gid, targets=None, lengths=None, want_logits=True, train=True)
+                loss, dyt = self.scalar_loss_and_grad(out["logits"], x, lengths, quantize_channels, log_scale_min, scale=ce_weight,
+                                                      factor=factor)
+                out["loss"] = loss
+                self.backward(x, gid, None, lengths, ext_dy=dyt, vq_scale=vq_weight)
+            else:
+                fwd = self.forward if g.has_encoder else self.decoder_forward
+                out = fwd(x, c, gid, targets=x, lengths=lengths, want_logits=False, train=True)
+                self.backward(x, gid, x, lengths, loss_scale=ce_weight, vq_scale=vq_weight, dy_factor=factor)
+        except BaseException:
+            # a refused input ended the micro-batch half-way: what it added cannot be told from the rest, so the window goes with it
+            self.join(self.flight.abandon())
+            self.discard_step()
+            raise
+        finally:
+            self.flight.accum = None
+        hist = self._vq_hist if g.has_encoder else None
+        L.check(self.lib.wae_accum_stats(L.ptr(win.sums), L.ptr(win.counts), g.K if g.has_encoder else 0, L.ptr(out["loss"]),
+                                         float(ce_weight), L.ptr(out["vq_loss"]) if g.has_encoder else None, float(vq_weight),
+                                         L.ptr(hist), None, self.stream()), "accum_stats")
+        win.n += 1
+        res = dict(ce=out["loss"])
+        if g.has_encoder:
+            res.update(vq_loss=out["vq_loss"], perp=out["perp"])
+        return res
+
+    def apply_step(self, lr: float = 4e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                   clip_thresh: float = 100.0, ema_decay: float = 0.9999, grad_hook=None, grad_sync=None):
+        """Closes the accumulation window: the finish of the gradients (backward.finish_window: what a plain step's _finish_layers and
+        finish_grads do, once for the window), [data parallel: grad_sync.finish() -- the finished arena goes out here, once per
+        window and never inside a micro-batch (DDP's no_sync); or grad_hook(grads)], clip_grad_norm_ + Adam + EMA.  opt_step advances
+        by one.  Returns dict(loss, ce, grad_norm, micro_batches) and, with an encoder, vq_loss and perp -- 0-d device tensors but
+        micro_batches: ce = sum ce_weight_i ce_i, vq_loss = sum vq_weight_i vq_loss_i, loss = ce + vq_loss, perp = the perplexity of
+        the micro-batches' code counts added per code (score_list's convention: the concatenated batch's perplexity)."""
+        from . import backward as BW
+        win = self.window
+        if win is None or win.n == 0:
+            raise RuntimeError("apply_step without an open accumulation window: accumulate() at least one micro-batch first "
+                               "(or use train_step for a step of one batch)")
+        grads = BW.finish_window(self, win, grad_sync)
+        if grad_sync is not None:
+            grad_sync.finish()
+        if grad_hook is not None:
+            grad_hook(grads)
+        out = torch.empty(5, dtype=torch.float32, device=self.device)
+        L.check(self.lib.wae_accum_stats(L.ptr(win.sums), L.ptr(win.counts), self.g.K if win.counts is not None else 0, None, 0.0, None,
+                                         0.0, None, L.ptr(out), self.stream()), "accum_stats (close)")
+        self.opt_step += 1
+        if self.flight.norm_summed and grad_sync is None and grad_hook is None:
+            L.check(self.lib.wae_clip_adam_ema_summed(L.ptr(self.params), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
+                                                      L.ptr(self.shadow), self.lay.total, L.ptr(self.gn_acc), L.ptr(self.grad_norm),
+                                                      self.opt_step, lr, betas[0], betas[1], eps, weight_decay, clip_thresh,
+                                                      ema_decay, self.stream()), "clip_adam_ema_summed")
+        else:
+            L.check(self.lib.wae_clip_adam_ema(L.ptr(self.params), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
+                                               L.ptr(self.shadow), self.lay.total, L.ptr(self.opt_scratch), L.ptr(self.grad_norm),
+                                               self.opt_step, lr, betas[0], betas[1], eps, weight_decay, clip_thresh, ema_decay,
+                                               self.stream()), "clip_adam_ema")
+        self.flight.norm_summed = False
+        self.window = None
+        self.weights_dirty = True
+        self.hold("window", win.sums, win.counts)
+        res = dict(ce=out[0], grad_norm=self.grad_norm[0], micro_batches=win.n)
+        if self.g.has_encoder:
+            res.update(vq_loss=out[1], perp=out[3], loss=out[2])
+        else:
+            res["loss"] = out[0]
+        return res
+
+    def discard_step(self):
+        """Drops an open accumulation window: the accumulators are cleared, the dropout counter goes back to where the window opened,
+        nothing of its micro-batches reaches the gradients or the optimizer.  Without an open window: nothing."""
+        win, self.window = self.window, None
+        if win is None:
+            return
+        for t in (self.d_eff, self.cbuf, self.gn_acc):
+            t.zero_()
+        self.drop_calls = win.drop_calls
+        self.saved = None
+        self.flight.reset()
+
+    def train_step_accum(self, batches, lr: float = 4e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                         clip_thresh: float = 100.0, ema_decay: float = 0.9999, grad_hook=None, quantize_channels: int = 65536,
+                         log_scale_min: float = -7.0, grad_sync=None, ce_scale: float = 1.0):
+        """One optimisation step on a sequence of micro-batches (x, c, gid, lengths): the weights of distributed.accum_weights, an
+        accumulate() per entry, apply_step().  Under them the step is the one train_step takes on the concatenated batch where the
+        micro-batches share T; where they do not (each padded to its own longest clip) it is the step on the global masked mean over
+        all loss positions and the mean over all latent elements.  grad_sync: the ranks meet once for the window's count and once in
+        apply_step.  ce_scale: one more factor on the CE term.  Returns apply_step's dict."""
+        from . import distributed as DS
+        batches = list(batches)
+        if not batches:
+            raise ValueError("train_step_accum: no micro-batches")
+        self._refuse_in_window("train_step_accum")
+        metas = []
+        for x, c, gid, lengths in batches:
+            frames = c.shape[-1] if (c is not None and self.g.has_encoder) else 0
+            metas.append((x.shape[0], x.shape[1], lengths, self.latent_elements(x.shape[0], frames)))
+        world = grad_sync.world if grad_sync is not None else 1
+        weights, n_tot = DS.accum_weights(metas, world=world, group=getattr(grad_sync, "group", None))
+        # the count that divides this rank's summed CE gradient: N / world (the rank mean follows), over ce_scale
+        ce_count = n_tot / (world * float(ce_scale)) if (n_tot > 0 and ce_scale) else None
+        for (x, c, gid, lengths), (wc, wv) in zip(batches, weights):
+            self.accumulate(x, c, gid, lengths, ce_weight=wc * float(ce_scale), vq_weight=wv, quantize_channels=quantize_channels,
+                            log_scale_min=log_scale_min, ce_count=ce_count)
+        return self.apply_step(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip_thresh=clip_thresh, ema_decay=ema_decay,
+                               grad_hook=grad_hook, grad_sync=grad_sync)

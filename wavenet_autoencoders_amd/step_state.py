@@ -30,11 +30,25 @@ class Saved:
     beta: float = 0.25
 
 
+@dataclasses.dataclass
+class Window:
+    """An open accumulation window (WaeEngine.accumulate .. apply_step): micro-batches whose weight gradients add up in the engine's
+    accumulators (backward.py: deferred finishing) until ONE finish and ONE optimizer step close it."""
+    sums: torch.Tensor                          # (3,) fp64 on the device: sum w ce, sum w vq_loss, micro-batches (wae_accum_stats)
+    counts: Optional[torch.Tensor]              # (K,) int32: the code histograms added per code; None without an encoder
+    drop_calls: int                             # the engine's dropout counter when the window opened (discard_step puts it back)
+    n: int = 0                                  # micro-batches accumulated
+    static: Optional[bool] = None               # which weight-gradient launch fills the tiles (backward.static_tn_shape): one per window
+    shape: Optional[tuple] = None               # (B, T) of the last micro-batch: its workspace's tables serve the finish
+
+
 class InFlight:
     """What the phases of one step hand to each other.  pack_done / early_pack: the completion events (WaeEngine.branch boxes) of the
     forward's / the backward's weight packing on a side stream, each taken once by the phase that waits for it; ev_dc: recorded where
     the conditioning gradient is complete; grads_done: the arena slice decoder_backward finished itself; finish_used: the FinishPlan
-    that did; norm_summed: the gather passes summed the squared norm."""
+    that did; norm_summed: the gather passes summed the squared norm.
+    accum: the Window this backward adds a micro-batch to -- the accumulate-mode switch of decoder_backward (deferred finishing:
+    no clearing from the second micro-batch on, nothing scattered, nothing written to the gradient arena); None: a plain step."""
 
     def __init__(self):
         self.reset()
@@ -43,6 +57,7 @@ class InFlight:
         self.pack_done = self.early_pack = self.ev_dc = None
         self.grads_done = self.finish_used = None
         self.norm_summed = False
+        self.accum = None
 
     def abandon(self):
         """A refused input ended the step half-way: nothing of it may be taken for the next call's.  -> the event of the forward's
