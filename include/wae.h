@@ -975,7 +975,14 @@ int wae_gemm_tm_ce(const wae_tm_desc* d, const void* const* src_host, const int6
  * (onehot[b*T+t] == m0 + m) (first-conv gradient).  ones_col >= 0: a virtual all-ones Q column at that tile-local
  * index; clip b accumulates sum_t P[b,t][m] into C[m][ones_col + b] (bias / per-clip conditioning-bias gradients).
  * Each tile is contracted over the time range of one clip split `splits` ways; results are added with fp32 atomics
- * (not bitwise reproducible run to run). */
+ * (not bitwise reproducible run to run).
+ * Preconditions: P and Q are read in 16-byte pieces -- pointers 16-byte aligned, p_stride / q_stride multiples of 16 bytes, and
+ * the piece that holds the last valid column is read whole (any 0 <= m_valid, n_valid <= 128 is permitted, odd ones included,
+ * while the row is readable up to the next multiple of 16 bytes; what lies there never reaches C).  ones_col + B <= 128 and
+ * shift == 0 with ones_col >= 0: under a shift the three launches disagree on which rows the sums cover.  ones_col < n_valid is
+ * permitted here (not in the team launches): the stored Q column of that index is ignored, and C columns ones_col + 1 ..
+ * ones_col + B - 1 then receive both their own contraction and a clip's sums.  splits may exceed ceil(T / 32) (it is then
+ * ceil(T / 32)).  C rows from m_valid on and C columns outside [0, n_valid) and [ones_col, ones_col + B) are never written. */
 typedef struct wae_tn_tile {
   const void* P;
   const void* Q;
@@ -1032,7 +1039,12 @@ int wae_glu_bwd_fused_dc(const wae_glu_bwd_desc* d, const void* dz, int64_t dz_s
  * (backward.py: StreamTable).  team_size consecutive workgroups form a team that walks one segment list, member m on
  * job (segment job + m) -- the jobs of one layer share operands; team_seg has nteams + 1 prefix offsets into segs;
  * slabs are numbered b * ceil(T/32) + t / 32; a job with m_valid == 0 is skipped; nwg >= nteams * team_size.
- * m_valid <= 384, n_valid <= 256; n_valid % 8 == 0 when ones_col >= 0 (n_valid <= ones_col < 256). */
+ * m_valid <= 384, n_valid <= 256; n_valid % 8 == 0 when ones_col >= 0 (n_valid <= ones_col < 256).
+ * Preconditions: operands move in 16-byte units -- P / Q pointers 16-byte aligned, p_stride / q_stride multiples of 8 elements,
+ * m_valid and n_valid multiples of 8; ones_col + B <= 256 and shift == 0 with ones_col >= 0 (rows whose Q partner lies outside
+ * the clip are dropped from the sums as well); B <= 64; every segment has job + team_size <= the number of job records and
+ * 0 <= slab_begin <= slab_end <= B * ceil(T / 32) (an empty segment and a team without segments are permitted); each (job, slab)
+ * pair is contracted once per segment that covers it. */
 typedef struct wae_ts_job {
   const void* P;
   const void* Q;
@@ -1069,7 +1081,12 @@ int wae_gemm_tn_stream(int32_t dtype /* WAE_BF16 or WAE_F16 */, const wae_ts_job
  * WITHOUT a Q operand (Q0 = NULL, n0_valid = 0: only the per-clip column sums of P, at ones_col), first_conv (wavenet.py:119-122,
  * 203) as a TAPS job whose P is the one-hot operand of wae_onehot_rows, and -- the last layer's conv1x1_out gradient being dead
  * (wavenet.py:205-207) -- dS as Q0 of that layer's OUTSKIP job, whose Cb then is the skip bias gradient.  A record with
- * m_valid <= 0 is a null job (its team member skips the segment). */
+ * m_valid <= 0 is a null job (its team member skips the segment).
+ * Preconditions: shift <= 0 on every job; m_valid, n0_valid, n1_valid multiples of 8, operand pointers 16-byte aligned and
+ * strides multiples of 8 elements (16-byte requests; a partly valid unit would be zero-filled whole); COND's sums and OUTSKIP's Cb
+ * are defined for shift == 0 only (the slabs a shift skips, and the rows t >= T it brings into range, would otherwise enter or
+ * leave them); COND writes C0 columns [0, n0_valid) and [ones_col, ones_col + B), which must lie inside ldc0; n1_valid == 0 goes
+ * with Q1 = C1 = NULL; segments as for wae_gemm_tn_stream. */
 enum { WAE_TQ_TAPS = 0, WAE_TQ_COND = 1, WAE_TQ_OUTSKIP = 2 };
 typedef struct wae_tq_job {
   const void* P;
