@@ -376,6 +376,49 @@ int wae_gproj_bwd_consume(const float* eff, float* d_eff, int64_t wg_off, int64_
 int wae_accum_stats(double* sums, int32_t* counts, int32_t K, const float* ce, double ce_weight, const float* vq_loss,
                     double vq_weight, const int32_t* hist, float* out, void* stream);
 
+/* ---- the fixed-order forms of the small float sums of a train step (EngineOptions.deterministic) ----------------
+ * Each entry below takes its default twin's arguments (plus a partials buffer where it needs one) and computes the same quantity
+ * with every sum that more than one workgroup feeds formed in a FIXED ORDER: one owner per output, or partials finished by a second
+ * small launch in index order.  No floating-point atomics, no workgroup waits for another; partials are stored before they are read,
+ * by plain stores, so no buffer needs clearing.  The same operands give the same bits on the same device model and build; the bits
+ * are not the default twin's (another order of fp32 additions).  A partials buffer too small: WAE_EINVAL before any launch.
+ *
+ * wae_gproj_bwd_det: wae_gproj_bwd (consume = 0) or wae_gproj_bwd_consume (consume = 1).  Conv bias and conv1x1g rows have one owner
+ *   in both forms.  The embedding rows: launch 1 stores, per (layer l, block k of 32 gate rows, clip b, feature c), the block's sum
+ *   to parts[l][k][b][c] (wae_gproj_bwd_det_floats(B, L, Hp, Cg) = L * ceil(2Hp / 32) * B * Cg floats); launch 2, one thread per
+ *   (speaker, feature): the clips of that speaker in index order, per clip the layers 0 .. L-1, per layer the blocks in order, all added
+ *   one after another from zero, then d_eff[row] = d_eff[row] + sum.
+ * wae_upsample_stage_bwd_det: wae_upsample_stage_bwd; din as there; the FIR's weight gradient: block i of the nbw = min(B * C, 256)
+ *   weight blocks stores its 2s+1 tap sums to parts[i][tap] (wae_upsample_stage_bwd_det_floats() floats); one workgroup adds, per tap,
+ *   the blocks 0 .. nbw-1 in order (from block 0's sum) and then dw[tap] = dw[tap] + sum.
+ * wae_vq_slice_bwd_det / wae_vq_bwd_det: wae_vq_slice_bwd / wae_vq_bwd with K, the number of codes; dlat as there; the codebook
+ *   gradient by one workgroup per code: the frames in row order b * Tq + t whose idx is the code add -c_emb * (lat - quant) in turn
+ *   (from zero), then demb[code] = demb[code] + sum; a code that no frame uses is not written.  D <= 1024.
+ * wae_vq_loss_det: stats[0] of wae_vq_slice (modes 0, 2) / wae_vq_nearest again from lat and quant: c_loss * (sum / ((float)(B * Tq) *
+ *   (float)D)), the sum of (quant - lat)^2 over the slice in fp64 by ONE workgroup -- thread j of 256 takes the elements j, j + 256, ...
+ *   in (b, channel, t) order, a xor butterfly over the 64 lanes, the four waves in wave order -- rounded to fp32 once.
+ * wae_clip_adam_ema_det: wae_clip_adam_ema; the squared norm: workgroup i of grid = min(1024, ceil(n / 1024)) sums its elements as
+ *   there (thread by thread, xor butterfly, four waves in order) and stores the fp64 sum to parts[1 + i]; one thread adds parts[1 ..
+ *   grid] in index order into parts[0], which the clip + Adam + EMA launch reads.  parts: at least 1025 doubles. */
+int64_t wae_gproj_bwd_det_floats(int32_t B, int32_t L, int32_t Hp, int32_t Cg);
+int wae_gproj_bwd_det(const float* eff, float* d_eff, int64_t wg_off, int64_t bias_off, int64_t layer_stride,
+                      const int32_t* gid, int64_t emb_off, const float* gvec, float* c1, int64_t c_layer_stride, int64_t ld,
+                      int32_t ones_col, int32_t B, int32_t L, int32_t G, int32_t Hp, int32_t Cg, int32_t n_speakers,
+                      int32_t consume, float* parts, int64_t parts_floats, void* stream);
+int64_t wae_upsample_stage_bwd_det_floats(void);
+int wae_upsample_stage_bwd_det(const float* dout, const float* in, const float* w, float* din, float* dw, float* parts,
+                               int64_t parts_floats, int32_t B, int32_t C, int32_t Tin, int32_t s, void* stream);
+int wae_vq_slice_bwd_det(const float* lat, const float* quant, const int64_t* idx, const float* dquant, float* dlat,
+                         float* demb, int32_t B, int32_t Dtot, int32_t d0, int32_t D, int32_t Tq, int32_t K, float c_lat,
+                         float c_emb, void* stream);
+int wae_vq_bwd_det(const float* lat, const float* quant, const int64_t* idx, const float* dquant, float* dlat, float* demb,
+                   int32_t B, int32_t D, int32_t Tq, int32_t K, float beta, float loss_scale, void* stream);
+int wae_vq_loss_det(const float* lat, const float* quant, float* stats, int32_t B, int32_t Dtot, int32_t d0, int32_t D,
+                    int32_t Tq, float c_loss, void* stream);
+int wae_clip_adam_ema_det(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* shadow, int64_t n,
+                          double* parts, int64_t parts_doubles, float* grad_norm_out, int32_t step, double lr, double beta1,
+                          double beta2, double eps, double weight_decay, double clip_thresh, double ema_decay, void* stream);
+
 /* ---- a5 first_conv on one-hot input = column gather + bias (wavenet.py:119-122,203) --------------------
  * idx (B*T) int32 class ids; table (O,Rp) fp32 = W^T ; x0 (B,T,Rp) dtype.  scalar mode: xs (B*T) fp32,
  * table (1,Rp). */
@@ -997,6 +1040,27 @@ typedef struct wae_tn_tile {
 } wae_tn_tile;
 int wae_gemm_tn_tiles(int32_t dtype, const wae_tn_tile* tiles_dev, int32_t ntiles, int32_t B, int32_t T, int32_t splits,
                       void* stream);
+/* The same contraction with its sums formed in a FIXED ORDER (the deterministic train step): two launches, no workgroup waits for
+ * another, no floating-point atomics.  Tile records, preconditions and what is never written are wae_gemm_tn_tiles'.
+ *   Launch 1: the workgroup of the logical (tile i, kr = clip b * nsp + split s) -- nsp = the splits the launch really makes, as in
+ *     wae_gemm_tn_tiles -- stores alpha * (its MFMA sum over its time range) into slot (i, kr) of `partials`, a [ntiles][B * nsp][128][128]
+ *     fp32 array.  Every element launch 2 reads is stored exactly once per launch (zeros for an empty time range), so the buffer
+ *     needs no clearing and may be reused by the next call on the same stream.
+ *   Launch 2: one thread per element (row, c) of a tile's window, row < m_valid.  THE ORDER BELOW IS THE DEFINITION OF THE RESULT:
+ *       data = ((slot[0] + slot[1]) + slot[2]) + ... + slot[B * nsp - 1]   at [row][c]: clip-major, split-minor; taken when
+ *              c < n_valid and c != ones_col;
+ *       ones = (slot[b * nsp] + slot[b * nsp + 1]) + ... + slot[b * nsp + nsp - 1]   at [row][ones_col]: clip b's splits only; taken
+ *              when c == ones_col + b for a clip 0 <= b < B;
+ *       C[row][c] = C[row][c] + data, + ones, or + (data + ones) -- ONE plain read-modify-write of fp32 adds, started from the first
+ *       partial (not from zero).  Ones columns at or beyond tile-local 128 are added the same way, each alone.
+ * partials_floats < wae_gemm_tn_tiles_det_floats(ntiles, B, T, splits): WAE_EINVAL, nothing launched.
+ * ordered = 0: one reduce launch over all tiles; the caller guarantees that no two tiles of the table touch the same element of C
+ *   (windows and ones columns; backward.py: TileTable.finalize checks it on the host).
+ * ordered = 1: one reduce launch per tile, in table order: tiles that share C are added one after another in that order.
+ * Within one device model and build the result is a function of the operands, C's previous contents, B, T, splits and the table. */
+int64_t wae_gemm_tn_tiles_det_floats(int32_t ntiles, int32_t B, int32_t T, int32_t splits);
+int wae_gemm_tn_tiles_det(int32_t dtype, const wae_tn_tile* tiles_dev, int32_t ntiles, int32_t B, int32_t T, int32_t splits,
+                          float* partials, int64_t partials_floats, int32_t ordered, void* stream);
 
 /* ---- backward data path across one layer boundary, fused (csrc/glu_bwd.hip; autograd of modules.py:115-163) ----------
  *   dx_l-hat = alpha * (dx_{l+1}-hat + sum_tap W1_l,tap^T dz_l[t + (k-1-tap) d])   -> g_out (B,T,Rp), also kept in registers

@@ -191,10 +191,22 @@ def parse_args(argv=None):
                     help="M loader batches per optimizer step (WaeEngine.train_step_accum): each is a micro-batch padded to its own "
                          "longest clip (max_time_steps null), weighted so that the step is the one on all M as one batch; the learning-"
                          "rate schedule, the checkpoint / eval intervals and global_step count optimizer steps.  1: one batch per step")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="the reproducible train step (WAE_DETERMINISTIC=1, wavenet_autoencoders_amd/options.py): the same weights, batch "
+                         "and dropout seed give the same bits, step after step and run after run, on one GPU (not with data parallel)")
     args = ap.parse_args(argv)
     if args.accum_steps < 1:
         ap.error(f"--accum-steps {args.accum_steps}: at least 1 loader batch per optimizer step")
     return args
+
+
+def engine_switches(args):
+    """The command line's launch-path switches into the environment the engine reads them from, once, when it is created
+    (options.py) -> the options that engine will run with"""
+    from wavenet_autoencoders_amd.options import EngineOptions
+    if args.deterministic:
+        os.environ["WAE_DETERMINISTIC"] = "1"
+    return EngineOptions.from_env().pinned()
 
 
 def main(argv=None):
@@ -215,6 +227,8 @@ def main(argv=None):
 
     from wavenet_autoencoders_amd.engine import WaeEngine
     geom = build_geometry(hp)
+    if engine_switches(args).deterministic and world > 1:
+        raise NotImplementedError("--deterministic with data parallel: the all-reduce's order of additions is the collective library's")
     eng = WaeEngine(geom, dtype=args.dtype, device=device, dropout=float(hp.dropout),            # vqwae_train.py:933
                     drop_seed=0x5EED * 4099 + rank)   # replicas draw their own masks
     # reference initialisation, identical on every rank

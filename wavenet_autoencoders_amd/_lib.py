@@ -186,6 +186,18 @@ SIGNATURES = {
     "wae_gemm_tm": (c_i32, [ctypes.POINTER(TmDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "wae_gemm_tm_ce": (c_i32, [ctypes.POINTER(TmDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, ctypes.POINTER(TmCe), c_vp]),
     "wae_gemm_tn_tiles": (c_i32, [c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "wae_gemm_tn_tiles_det_floats": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
+    # dtype, tiles_dev, ntiles, B, T, splits, partials, partials_floats, ordered, stream
+    "wae_gemm_tn_tiles_det": (c_i32, [c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_i32, c_vp]),
+    # the fixed-order forms of the small sums (include/wae.h): their twins' arguments and a partials buffer
+    "wae_gproj_bwd_det_floats": (c_i64, [c_i32] * 4),
+    "wae_gproj_bwd_det": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64] + [c_i32] * 8 + [c_vp, c_i64, c_vp]),
+    "wae_upsample_stage_bwd_det_floats": (c_i64, []),
+    "wae_upsample_stage_bwd_det": (c_i32, [c_vp] * 6 + [c_i64] + [c_i32] * 4 + [c_vp]),
+    "wae_vq_slice_bwd_det": (c_i32, [c_vp] * 6 + [c_i32] * 6 + [c_f32, c_f32, c_vp]),
+    "wae_vq_bwd_det": (c_i32, [c_vp] * 6 + [c_i32] * 4 + [c_f32, c_f32, c_vp]),
+    "wae_vq_loss_det": (c_i32, [c_vp] * 3 + [c_i32] * 5 + [c_f32, c_vp]),
+    "wae_clip_adam_ema_det": (c_i32, [c_vp] * 5 + [c_i64, c_vp, c_i64, c_vp, c_i32] + [ctypes.c_double] * 7 + [c_vp]),
     "wae_glu_bwd_fused_supported": (c_i32, [c_i32, c_i32]),
     "wae_glu_bwd_fused_supported16": (c_i32, [c_i32, c_i32]),
     "wae_glu_bwd_fused": (c_i32, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

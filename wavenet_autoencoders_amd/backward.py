@@ -160,12 +160,37 @@ def _await_packed_weights(eng):
         pack_bwd_weights(eng)      # (also clears eng.d_eff and eng.cbuf)
 
 
+def tn_tiles_overlap(tiles, B):
+    """Do two tiles of a table add into the same fp32 element of C?  -> (i, j), the first such pair in address order, or None.
+    A tile owns, in each of its m_valid rows, the columns [0, n_valid) and [ones_col, ones_col + B) behind its C pointer (include/wae.h);
+    what wae_gemm_tn_tiles_det's single reduce launch (ordered = 0) needs is that no element has two owners."""
+    spans = []                                          # (first byte, one past the last byte, tile)
+    for i, t in enumerate(tiles):
+        cols = [(0, t.n_valid)] if t.n_valid > 0 else []
+        if t.ones_col >= 0:
+            cols.append((t.ones_col, t.ones_col + B))
+        if len(cols) == 2 and cols[1][0] <= cols[0][1]:    # the tile's own two ranges touch: one range (one thread per element adds both)
+            cols = [(0, max(cols[0][1], cols[1][1]))]
+        for c0, c1 in cols:
+            first = (t.C or 0) + 4 * (np.arange(t.m_valid, dtype=np.int64) * t.ldc + c0)
+            spans += [(int(a), int(a) + 4 * (c1 - c0), i) for a in first]
+    spans.sort()
+    end, owner = -1, -1
+    for a, b, i in spans:
+        if a < end and i != owner:
+            return (min(owner, i), max(owner, i))
+        if b > end:
+            end, owner = b, i
+    return None
+
+
 class TileTable:
     """Host builder of a device array of wae_tn_tile (include/wae.h): each add() is one contraction
     C[M][N (+ones)] += alpha * P^T Q, cut into 128x128 output tiles."""
 
     def __init__(self, eng):
         self.eng, self.tiles = eng, []
+        self.det_checked = None        # launch_det: the batch size the table's tiles were last found disjoint in C for
 
     def add(self, M, N, shift, ones_col, alpha, p_ptr, p_stride, q_ptr, q_stride, c_ptr, ldc, onehot_ptr=0):
         es = self.eng.w_glu.element_size()
@@ -190,7 +215,26 @@ class TileTable:
 
     def launch(self, B, T):
         eng = self.eng
+        if eng.opt.deterministic:      # the engine's one partials buffer, reused by every table's launch on the one stream
+            return self.launch_det(B, T, eng.det_buffer("tn", self.det_floats(B, T)))
         L.check(eng.lib.wae_gemm_tn_tiles(eng.dt, L.ptr(self.dev), self.n, B, T, self.splits, eng.stream()), "gemm_tn_tiles")
+
+    def det_floats(self, B, T):
+        """fp32 elements of the partials buffer launch_det needs for this table"""
+        return int(self.eng.lib.wae_gemm_tn_tiles_det_floats(self.n, B, T, self.splits))
+
+    def launch_det(self, B, T, partials):
+        """The same contractions with their sums in a fixed order (wae_gemm_tn_tiles_det, one reduce launch): `partials` is an fp32
+        tensor of at least det_floats(B, T) elements that no other stream uses meanwhile.  Raises if two tiles share an element of C."""
+        eng = self.eng
+        if self.det_checked != B:
+            pair = tn_tiles_overlap(self.tiles, B)
+            if pair is not None:
+                raise ValueError(f"tiles {pair[0]} and {pair[1]} of the table add into the same element of C: the single reduce launch "
+                                 "of wae_gemm_tn_tiles_det (ordered = 0) would add them in no defined order")
+            self.det_checked = B
+        L.check(eng.lib.wae_gemm_tn_tiles_det(eng.dt, L.ptr(self.dev), self.n, B, T, self.splits, L.ptr(partials), partials.numel(), 0,
+                                              eng.stream()), "gemm_tn_tiles_det")
 
 
 def _ncu(eng):
@@ -967,13 +1011,16 @@ def _gproj_bwd(cx, l0, l1, consume=False):
     micro-batch of an accumulation window): the entry that zeroes the per-clip columns it has read (csrc/accum.hip)"""
     eng, g, lay, sm = cx.eng, cx.eng.g, cx.eng.lay, cx.eng.sm
     wg_off = lay.off("wavenet.conv_layers.0.conv1x1g.weight_v") + l0 * lay.layer_stride if g.Cg > 0 else -1
+    args = (L.ptr(eng.eff), L.ptr(eng.d_eff), wg_off, lay.off("wavenet.conv_layers.0.conv.bias") + l0 * lay.layer_stride,
+            lay.layer_stride, L.ptr(cx.gid32) if cx.use_gid else None, lay.offsets.get("wavenet.embed_speakers.weight", 0),
+            L.ptr(cx.gvec), ctypes.c_void_p(eng.cview["c1"].data_ptr() + l0 * cx.Z2 * sm["ld1"] * 4),
+            cx.Z2 * sm["ld1"], sm["ld1"], g.k * g.Rp + g.Ccp, cx.B, l1 - l0, g.G, g.Hp, max(g.Cg, 0), int(g.n_speakers or 0))
+    if eng.opt.deterministic:      # the embedding rows from partials in a fixed order (csrc/accum.hip)
+        parts = eng.det_buffer("gproj", int(eng.lib.wae_gproj_bwd_det_floats(cx.B, l1 - l0, g.Hp, max(g.Cg, 0))))
+        L.check(eng.lib.wae_gproj_bwd_det(*args, int(consume), L.ptr(parts), parts.numel(), eng.stream()), "gproj_bwd_det")
+        return
     entry = eng.lib.wae_gproj_bwd_consume if consume else eng.lib.wae_gproj_bwd
-    L.check(entry(L.ptr(eng.eff), L.ptr(eng.d_eff), wg_off, lay.off("wavenet.conv_layers.0.conv.bias") + l0 * lay.layer_stride,
-                  lay.layer_stride, L.ptr(cx.gid32) if cx.use_gid else None, lay.offsets.get("wavenet.embed_speakers.weight", 0),
-                  L.ptr(cx.gvec), ctypes.c_void_p(eng.cview["c1"].data_ptr() + l0 * cx.Z2 * sm["ld1"] * 4),
-                  cx.Z2 * sm["ld1"], sm["ld1"], g.k * g.Rp + g.Ccp, cx.B, l1 - l0, g.G, g.Hp, max(g.Cg, 0),
-                  int(g.n_speakers or 0), eng.stream()),
-            "gproj_bwd_consume" if consume else "gproj_bwd")
+    L.check(entry(*args, eng.stream()), "gproj_bwd_consume" if consume else "gproj_bwd")
 
 
 def _finish_layers(cx, l0, l1, with_head, zb=True):
@@ -1155,7 +1202,7 @@ def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: O
     cx.gvec = gvec
     sched = _tn_schedule(cx, grad_sync is not None)
     cx.finish = eng.flight.finish_used = _finish_plan(cx)
-    cx.finish_acc = cx.finish is not None and grad_sync is None
+    cx.finish_acc = cx.finish is not None and grad_sync is None and not eng.opt.deterministic      # (its norm: engine._clip_adam_ema)
     eng.flight.norm_summed = False
     if win is not None:
         win.static, win.shape = isinstance(ws["stream"], StaticStreamTable), (B, T)
@@ -1291,7 +1338,7 @@ def finish_window(eng, win, grad_sync=None):
     cx = _step(eng, *win.shape)
     fl = eng.flight
     cx.finish = fl.finish_used = _finish_plan(cx)
-    cx.finish_acc = cx.finish is not None and grad_sync is None
+    cx.finish_acc = cx.finish is not None and grad_sync is None and not eng.opt.deterministic      # (its norm: engine._clip_adam_ema)
     _first_conv_finish(cx)
     done = _finish_layers(cx, 0, eng.g.layers, with_head=True, zb=False)
     eng.join(done[0] if done else None)
@@ -1347,8 +1394,14 @@ def frontend_backward(eng, dc: torch.Tensor, loss_scale: float = 1.0, stop_at_qu
             d = d.contiguous()
             L.check(lib.wae_act_bwd(L.ptr(yout), L.ptr(d), d.numel(), act, float(g.up_act_slope), st), "upsample activation bwd")
         din = torch.empty_like(xin)
-        L.check(lib.wae_upsample_stage_bwd(L.ptr(d), L.ptr(xin), L.ptr(eng.eff[lay.off(name):]), L.ptr(din),
-                                           L.ptr(eng.d_eff[lay.off(name):]), B, g.Cc, xin.shape[-1], s, st), "upsample_stage_bwd")
+        if eng.opt.deterministic:
+            parts = eng.det_buffer("ups", int(lib.wae_upsample_stage_bwd_det_floats()))
+            L.check(lib.wae_upsample_stage_bwd_det(L.ptr(d), L.ptr(xin), L.ptr(eng.eff[lay.off(name):]), L.ptr(din),
+                                                   L.ptr(eng.d_eff[lay.off(name):]), L.ptr(parts), parts.numel(), B, g.Cc, xin.shape[-1], s,
+                                                   st), "upsample_stage_bwd_det")
+        else:
+            L.check(lib.wae_upsample_stage_bwd(L.ptr(d), L.ptr(xin), L.ptr(eng.eff[lay.off(name):]), L.ptr(din),
+                                               L.ptr(eng.d_eff[lay.off(name):]), B, g.Cc, xin.shape[-1], s, st), "upsample_stage_bwd")
         d = din
         keep.append(d)
     if g.conv_in:
@@ -1369,8 +1422,12 @@ def frontend_backward(eng, dc: torch.Tensor, loss_scale: float = 1.0, stop_at_qu
         Tq = lat.shape[-1]
         dlat = torch.empty_like(lat)
         en = "vq.embedding.weight"
-        L.check(lib.wae_vq_bwd(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(eng.d_eff[lay.off(en):]), B, g.Cc,
-                               Tq, sv.beta, loss_scale, st), "vq_bwd")
+        if eng.opt.deterministic:      # the codebook gradient by one workgroup per code
+            L.check(lib.wae_vq_bwd_det(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(eng.d_eff[lay.off(en):]), B,
+                                       g.Cc, Tq, g.K, sv.beta, loss_scale, st), "vq_bwd_det")
+        else:
+            L.check(lib.wae_vq_bwd(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(eng.d_eff[lay.off(en):]), B, g.Cc,
+                                   Tq, sv.beta, loss_scale, st), "vq_bwd")
         ea = sv.enc_acts                     # ea[i] = input of block i, ea[10] = output of block 9
         dx = torch.empty_like(ea[10])
         L.check(lib.wae_enc_conv_bwd(L.ptr(ea[10]), L.ptr(eng.eff[lay.off("encoder.lin.weight"):]), None, L.ptr(dlat), L.ptr(dx),

@@ -15,12 +15,14 @@ __device__ __forceinline__ int acc_checked_id(int v, int n) { return (unsigned)v
 // Block = (layer, 32 gate rows), thread = (row, feature slice): the arithmetic of gproj_bwd_kernel statement for statement -- the same
 // sums in the same order, so d_eff gets the same bits.  The one difference: the thread that stages c1[row][ones_col + B0 + b] stores
 // 0.0f to the address it has just read (a plain vector store; no other thread of the grid touches that element).
-__global__ void __launch_bounds__(256) gproj_bwd_consume_kernel(const float* __restrict__ eff, float* __restrict__ d_eff, int64_t wg_off,
-                                                                int64_t bias_off, int64_t layer_stride,
-                                                                const int32_t* __restrict__ gid, int64_t emb_off,
-                                                                const float* __restrict__ gvec, float* c1, int64_t c_layer_stride,
-                                                                int64_t ld, int ones_col, int B0, int B, int G, int Hp, int Cg,
-                                                                int n_speakers) {
+// DET (wae_gproj_bwd_det): phase 2 stores its (layer, row block, clip, feature) sum to `parts` instead of adding it to the embedding row
+// by an atomic (gproj_emb_finish_kernel adds them in a fixed order); CONSUME = false there leaves c1 as it is (a plain step).
+template <bool CONSUME, bool DET>
+__device__ __forceinline__ void gproj_bwd_consume_body(const float* __restrict__ eff, float* __restrict__ d_eff, int64_t wg_off,
+                                                       int64_t bias_off, int64_t layer_stride, const int32_t* __restrict__ gid,
+                                                       int64_t emb_off, const float* __restrict__ gvec, float* c1,
+                                                       int64_t c_layer_stride, int64_t ld, int ones_col, int B0, int B, int G, int Hp,
+                                                       int Cg, int n_speakers, float* __restrict__ parts) {
   extern __shared__ float ga_lds[];
   float* s_cl = ga_lds;                      // [32][ACC_BMAX]
   float* s_e = ga_lds + 32 * ACC_BMAX;       // [nb][Cg]
@@ -52,7 +54,7 @@ __global__ void __launch_bounds__(256) gproj_bwd_consume_kernel(const float* __r
     if (r < 2 * Hp) {
       float* p = cl + (int64_t)r * ld + B0 + b;
       v = *p;
-      *p = 0.f;                              // consumed
+      if constexpr (CONSUME) *p = 0.f;       // consumed
     }
     s_cl[rr * ACC_BMAX + b] = v;
   }
@@ -105,9 +107,49 @@ __global__ void __launch_bounds__(256) gproj_bwd_consume_kernel(const float* __r
       float a = 0.f;
 #pragma unroll
       for (int rr = 0; rr < 32; ++rr) a = fmaf(s_cl[rr * ACC_BMAX + b], wv[rr], a);
-      atomicAdd(d_eff + emb_off + (int64_t)s_sp[b] * Cg + c, a);
+      if constexpr (DET) parts[((((int64_t)l * gridDim.y + blockIdx.y) * B) + B0 + b) * Cg + c] = a;
+      else atomicAdd(d_eff + emb_off + (int64_t)s_sp[b] * Cg + c, a);
     }
   }
+}
+__global__ void __launch_bounds__(256) gproj_bwd_consume_kernel(const float* __restrict__ eff, float* __restrict__ d_eff, int64_t wg_off,
+                                                                int64_t bias_off, int64_t layer_stride,
+                                                                const int32_t* __restrict__ gid, int64_t emb_off,
+                                                                const float* __restrict__ gvec, float* c1, int64_t c_layer_stride,
+                                                                int64_t ld, int ones_col, int B0, int B, int G, int Hp, int Cg,
+                                                                int n_speakers) {
+  gproj_bwd_consume_body<true, false>(eff, d_eff, wg_off, bias_off, layer_stride, gid, emb_off, gvec, c1, c_layer_stride, ld, ones_col, B0,
+                                      B, G, Hp, Cg, n_speakers, nullptr);
+}
+template <bool CONSUME>
+__global__ void __launch_bounds__(256) gproj_bwd_det_kernel(const float* __restrict__ eff, float* __restrict__ d_eff, int64_t wg_off,
+                                                            int64_t bias_off, int64_t layer_stride, const int32_t* __restrict__ gid,
+                                                            int64_t emb_off, const float* __restrict__ gvec, float* c1,
+                                                            int64_t c_layer_stride, int64_t ld, int ones_col, int B0, int B, int G,
+                                                            int Hp, int Cg, int n_speakers, float* __restrict__ parts) {
+  gproj_bwd_consume_body<CONSUME, true>(eff, d_eff, wg_off, bias_off, layer_stride, gid, emb_off, gvec, c1, c_layer_stride, ld, ones_col,
+                                        B0, B, G, Hp, Cg, n_speakers, parts);
+}
+// The embedding rows from parts[layer][row block][clip][feature], one OWNER per (speaker, feature): the thread of (clip b, feature c)
+// where b is the FIRST clip of its speaker adds, for the clips b' = b, b + 1, ... of that speaker in index order, the layers 0 .. L-1
+// and inside a layer the row blocks 0 .. nblk-1 (started from zero), and adds the sum to the row with one plain read-modify-write.
+__global__ void __launch_bounds__(256) gproj_emb_finish_kernel(const float* __restrict__ parts, const int32_t* __restrict__ gid,
+                                                               float* __restrict__ d_eff, int64_t emb_off, int B, int L, int nblk, int Cg,
+                                                               int n_speakers) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= B * Cg) return;
+  const int b = e / Cg, c = e - b * Cg;
+  const int sp = acc_checked_id(gid[b], n_speakers);
+  for (int i = 0; i < b; ++i)
+    if (acc_checked_id(gid[i], n_speakers) == sp) return;      // an earlier clip of the speaker owns the row
+  float a = 0.f;
+  for (int i = b; i < B; ++i) {
+    if (acc_checked_id(gid[i], n_speakers) != sp) continue;
+    for (int l = 0; l < L; ++l)
+      for (int k = 0; k < nblk; ++k) a += parts[((((int64_t)l * nblk + k) * B) + i) * Cg + c];
+  }
+  float* dst = d_eff + emb_off + (int64_t)sp * Cg + c;
+  *dst = *dst + a;
 }
 
 extern "C" int wae_gproj_bwd_consume(const float* eff, float* d_eff, int64_t wg_off, int64_t bias_off, int64_t layer_stride,
@@ -127,6 +169,40 @@ extern "C" int wae_gproj_bwd_consume(const float* eff, float* d_eff, int64_t wg_
                        bias_off, layer_stride, gid, emb_off, gvec, c1, c_layer_stride, ld, ones_col, b0, B, G, Hp, Cg, n_speakers);
   }
   return wae_check_launch("gproj_bwd_consume");
+}
+
+extern "C" int64_t wae_gproj_bwd_det_floats(int32_t B, int32_t L, int32_t Hp, int32_t Cg) {
+  if (B <= 0 || L <= 0 || Hp <= 0 || Cg <= 0) return 0;
+  return (int64_t)L * ((2 * Hp + 31) / 32) * B * Cg;
+}
+extern "C" int wae_gproj_bwd_det(const float* eff, float* d_eff, int64_t wg_off, int64_t bias_off, int64_t layer_stride,
+                                 const int32_t* gid, int64_t emb_off, const float* gvec, float* c1, int64_t c_layer_stride, int64_t ld,
+                                 int32_t ones_col, int32_t B, int32_t L, int32_t G, int32_t Hp, int32_t Cg, int32_t n_speakers,
+                                 int32_t consume, float* parts, int64_t parts_floats, void* stream) {
+  WAE_REQUIRE(eff && d_eff && c1 && B > 0 && L > 0 && G > 0 && G % 2 == 0, "gproj_bwd_det: bad arguments");
+  WAE_REQUIRE(!gid || n_speakers > 0, "gproj_bwd_det: speaker ids need the size of the embedding table");
+  WAE_REQUIRE(Hp >= G / 2 && ones_col >= 0 && ld >= (int64_t)ones_col + B && c_layer_stride >= (int64_t)2 * Hp * ld,
+              "gproj_bwd_det: the %d per-clip columns at %d do not fit rows of %lld floats (layer stride %lld)", B, ones_col,
+              (long long)ld, (long long)c_layer_stride);
+  const int64_t wg = (gid || gvec) ? wg_off : -1;
+  const bool emb = gid && wg >= 0 && Cg > 0;
+  WAE_REQUIRE(!emb || (parts && parts_floats >= wae_gproj_bwd_det_floats(B, L, Hp, Cg)),
+              "gproj_bwd_det: the partials buffer is smaller than wae_gproj_bwd_det_floats says");
+  const size_t lds = (32 * ACC_BMAX + (size_t)ACC_BMAX * (Cg > 0 ? Cg : 0)) * sizeof(float);
+  WAE_REQUIRE(lds <= 64 * 1024, "gproj_bwd_det: Cg = %d too wide for the staged form", Cg);
+  const int nblk = (2 * Hp + 31) / 32;
+  for (int b0 = 0; b0 < B; b0 += ACC_BMAX) {
+    if (consume)
+      hipLaunchKernelGGL(gproj_bwd_det_kernel<true>, dim3(L, nblk), dim3(256), lds, as_stream(stream), eff, d_eff, wg, bias_off,
+                         layer_stride, gid, emb_off, gvec, c1, c_layer_stride, ld, ones_col, b0, B, G, Hp, Cg, n_speakers, parts);
+    else
+      hipLaunchKernelGGL(gproj_bwd_det_kernel<false>, dim3(L, nblk), dim3(256), lds, as_stream(stream), eff, d_eff, wg, bias_off,
+                         layer_stride, gid, emb_off, gvec, c1, c_layer_stride, ld, ones_col, b0, B, G, Hp, Cg, n_speakers, parts);
+  }
+  if (emb)
+    hipLaunchKernelGGL(gproj_emb_finish_kernel, dim3((B * Cg + 255) / 256), dim3(256), 0, as_stream(stream), (const float*)parts, gid,
+                       d_eff, emb_off, B, L, nblk, Cg, n_speakers);
+  return wae_check_launch("gproj_bwd_det");
 }
 
 // ---- the window's statistics -------------------------------------------------------------------------------------------------

@@ -45,9 +45,12 @@ __device__ __forceinline__ void upsample_stage_bwd_in_body(const float* __restri
 // reproduce the zero padding), dw[j] = sum_rem A[rem][(rem + j) / s].  A thread walks frames q: s contiguous dout loads,
 // three in loads, 3s FMAs (the tap-by-tap form needed s(2s+1) selects + FMAs and took 0.1 ms per step).  A block walks
 // whole (clip, channel) rows; at most 256 blocks leave their 2s+1 sums as atomics.  S = 0: any s <= 16, tap-by-tap.
-template <int S>
+// DET (wae_upsample_stage_bwd_det): the block leaves its 2s+1 sums in parts[bx][tap] with plain stores instead; a second launch adds
+// the blocks' sums in block order (upsample_w_finish_kernel).
+template <int S, bool DET = false>
 __device__ __forceinline__ void upsample_stage_bwd_w_body(const float* __restrict__ dout, const float* __restrict__ in,
-                                                          float* __restrict__ dw, int BC, int Tin, int s_rt, int bx, int nbx) {
+                                                          float* __restrict__ dw, int BC, int Tin, int s_rt, int bx, int nbx,
+                                                          float* __restrict__ parts = nullptr) {
   const int s = S > 0 ? S : s_rt;
   constexpr int NTAP = S > 0 ? 2 * S + 1 : UPW_MAXTAPS;
   const int Tout = Tin * s, ntap = 2 * s + 1;
@@ -105,7 +108,11 @@ __device__ __forceinline__ void upsample_stage_bwd_w_body(const float* __restric
       if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][j] = v;
     }
   __syncthreads();
-  if (threadIdx.x < ntap) atomicAdd(dw + threadIdx.x, part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]);
+  if constexpr (DET) {
+    if (threadIdx.x < ntap) parts[bx * UPW_MAXTAPS + threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+  } else {
+    if (threadIdx.x < ntap) atomicAdd(dw + threadIdx.x, part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]);
+  }
 }
 // the input gradient and the FIR's weight gradient of a stage read the same dout and depend on nothing of each other: ONE launch, the first
 // nxx * C * B workgroups of a flat grid on the input gradient, the rest on the weight gradient (as two launches on one stream they ran one
@@ -130,6 +137,44 @@ extern "C" int wae_upsample_stage_bwd(const float* dout, const float* in, const 
   else if (s == 8) hipLaunchKernelGGL(upsample_stage_bwd_kernel<8>, grid, dim3(256), 0, st, dout, in, w, din, dw, B, C, Tin, s, nxx, nbw);
   else hipLaunchKernelGGL(upsample_stage_bwd_kernel<0>, grid, dim3(256), 0, st, dout, in, w, din, dw, B, C, Tin, s, nxx, nbw);
   return wae_check_launch("upsample_stage_bwd");
+}
+
+// The fixed-order form of the stage's backward: the same two bodies; the weight-gradient blocks store their tap sums to parts[block][tap]
+// (every block of the launch stores every tap once: no clearing), and one small launch adds them per tap in block order 0 .. nbw-1,
+// starting from block 0's sum, and adds the result to dw[tap] with one plain read-modify-write.
+template <int S>
+__global__ void __launch_bounds__(256) upsample_stage_bwd_det_kernel(const float* __restrict__ dout, const float* __restrict__ in,
+                                                                    const float* __restrict__ w, float* __restrict__ din, int B, int C,
+                                                                    int Tin, int s, int nxx, int nbw, float* __restrict__ parts) {
+  const int id = blockIdx.x, nx = nxx * C * B;
+  if (id < nx) upsample_stage_bwd_in_body(dout, w, din, C, Tin, s, id % nxx, (id / nxx) % C, id / (nxx * C));
+  else upsample_stage_bwd_w_body<S, true>(dout, in, nullptr, B * C, Tin, s, id - nx, nbw, parts);
+}
+__global__ void __launch_bounds__(256) upsample_w_finish_kernel(const float* __restrict__ parts, int nbw, int ntap, float* __restrict__ dw) {
+  // through LDS: one thread per tap walking global memory waited out a load per block (61 us per stage at 256 blocks)
+  __shared__ float sp[256 * UPW_MAXTAPS];
+  for (int i = threadIdx.x; i < nbw * UPW_MAXTAPS; i += 256) sp[i] = parts[i];
+  __syncthreads();
+  if ((int)threadIdx.x >= ntap) return;
+  float v = sp[threadIdx.x];
+  for (int i = 1; i < nbw; ++i) v += sp[i * UPW_MAXTAPS + threadIdx.x];
+  dw[threadIdx.x] = dw[threadIdx.x] + v;
+}
+extern "C" int64_t wae_upsample_stage_bwd_det_floats(void) { return 256 * UPW_MAXTAPS; }
+extern "C" int wae_upsample_stage_bwd_det(const float* dout, const float* in, const float* w, float* din, float* dw, float* parts,
+                                          int64_t parts_floats, int32_t B, int32_t C, int32_t Tin, int32_t s, void* stream) {
+  WAE_REQUIRE(dout && in && w && din && dw && parts && B > 0 && C > 0 && Tin > 0 && s > 0, "upsample_stage_bwd_det: bad arguments");
+  WAE_REQUIRE(2 * s + 1 <= UPW_MAXTAPS, "upsample_stage_bwd_det: scale %d > %d is not supported", s, (UPW_MAXTAPS - 1) / 2);
+  WAE_REQUIRE(parts_floats >= 256 * UPW_MAXTAPS, "upsample_stage_bwd_det: the partials buffer is smaller than wae_upsample_stage_bwd_det_floats says");
+  hipStream_t st = as_stream(stream);
+  const int rows = B * C, nbw = rows < 256 ? rows : 256, nxx = (Tin + 255) / 256;
+  const dim3 grid(nxx * C * B + nbw);
+  if (s == 4) hipLaunchKernelGGL(upsample_stage_bwd_det_kernel<4>, grid, dim3(256), 0, st, dout, in, w, din, B, C, Tin, s, nxx, nbw, parts);
+  else if (s == 5) hipLaunchKernelGGL(upsample_stage_bwd_det_kernel<5>, grid, dim3(256), 0, st, dout, in, w, din, B, C, Tin, s, nxx, nbw, parts);
+  else if (s == 8) hipLaunchKernelGGL(upsample_stage_bwd_det_kernel<8>, grid, dim3(256), 0, st, dout, in, w, din, B, C, Tin, s, nxx, nbw, parts);
+  else hipLaunchKernelGGL(upsample_stage_bwd_det_kernel<0>, grid, dim3(256), 0, st, dout, in, w, din, B, C, Tin, s, nxx, nbw, parts);
+  hipLaunchKernelGGL(upsample_w_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)parts, nbw, 2 * s + 1, dw);
+  return wae_check_launch("upsample_stage_bwd_det");
 }
 
 // ---- Conv1d (+ReLU) (+residual) backward ------------------------------------------------------------------------------
@@ -529,4 +574,62 @@ extern "C" int wae_vq_bwd(const float* lat, const float* quant, const int64_t* i
   const float n = (float)((int64_t)B * D * Tq);
   return wae_vq_slice_bwd(lat, quant, idx, dquant, dlat, demb, B, D, 0, D, Tq, loss_scale * 2.f * beta / n, loss_scale * 2.f / n,
                           stream);
+}
+
+// The codebook gradient with one OWNER per code (the fixed-order form; vq_ema_codes_kernel of csrc/misc.hip sums the EMA update the same
+// way): workgroup k, thread = channel; the frames (b, t) in row order b * Tq + t, those with idx == k contribute -c_e * (lat - quant) in
+// turn (started from zero); one plain read-modify-write of demb[k][channel] at the end; a code that no frame uses is not written.
+__global__ void __launch_bounds__(256) vq_bwd_codes_kernel(const float* __restrict__ lat, const float* __restrict__ quant,
+                                                           const int64_t* __restrict__ idx, float* __restrict__ demb, int Dtot, int d0,
+                                                           int D, int Tq, int N, float c_e) {
+  __shared__ int s_hit[256];
+  const int k = blockIdx.x;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};       // channels threadIdx.x + 256 j (D <= 1024)
+  bool any = false;
+  for (int r0 = 0; r0 < N; r0 += 256) {      // N is uniform: every thread meets every barrier
+    const int r = r0 + threadIdx.x;
+    s_hit[threadIdx.x] = (r < N && idx[r] == k) ? 1 : 0;
+    __syncthreads();
+    const int m = min(256, N - r0);
+    for (int i = 0; i < m; ++i)
+      if (s_hit[i]) {
+        any = true;
+        const int row = r0 + i, b = row / Tq, t = row - b * Tq;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int dch = threadIdx.x + 256 * j;
+          if (dch < D) {
+            const int64_t at = ((int64_t)b * Dtot + d0 + dch) * Tq + t;
+            acc[j] += -c_e * (lat[at] - quant[at]);
+          }
+        }
+      }
+    __syncthreads();
+  }
+  if (any)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int dch = threadIdx.x + 256 * j;
+      if (dch < D) demb[(int64_t)k * D + dch] = demb[(int64_t)k * D + dch] + acc[j];
+    }
+}
+extern "C" int wae_vq_slice_bwd_det(const float* lat, const float* quant, const int64_t* idx, const float* dquant, float* dlat,
+                                    float* demb, int32_t B, int32_t Dtot, int32_t d0, int32_t D, int32_t Tq, int32_t K, float c_lat,
+                                    float c_emb, void* stream) {
+  WAE_REQUIRE(lat && quant && idx && dlat && B > 0 && D > 0 && Tq > 0 && d0 >= 0 && d0 + D <= Dtot, "vq_slice_bwd_det: bad arguments");
+  WAE_REQUIRE(!demb || (K > 0 && D <= 1024 && (int64_t)B * Tq < (1ll << 31)), "vq_slice_bwd_det: K > 0, D <= 1024 and B * Tq < 2^31");
+  const int64_t total = (int64_t)B * D * Tq;
+  hipLaunchKernelGGL(vq_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), lat, quant, idx, dquant,
+                     dlat, (float*)nullptr, Dtot, d0, D, Tq, c_lat, c_emb, total);
+  if (demb)
+    hipLaunchKernelGGL(vq_bwd_codes_kernel, dim3(K), dim3(256), 0, as_stream(stream), lat, quant, idx, demb, Dtot, d0, D, Tq, B * Tq,
+                       c_emb);
+  return wae_check_launch("vq_slice_bwd_det");
+}
+extern "C" int wae_vq_bwd_det(const float* lat, const float* quant, const int64_t* idx, const float* dquant, float* dlat, float* demb,
+                              int32_t B, int32_t D, int32_t Tq, int32_t K, float beta, float loss_scale, void* stream) {
+  WAE_REQUIRE(demb, "vq_bwd_det: bad arguments");
+  const float n = (float)((int64_t)B * D * Tq);
+  return wae_vq_slice_bwd_det(lat, quant, idx, dquant, dlat, demb, B, D, 0, D, Tq, K, loss_scale * 2.f * beta / n, loss_scale * 2.f / n,
+                              stream);
 }

@@ -12,6 +12,7 @@
 // (bf16: ds_read_b64_tr_b16, cdna_hip_programming.md T10; fp32: ds_read_b32 columns).  One workgroup = a 128x128 tile
 // of C over one k-range of one clip; 4 waves, each a 64x64 sub-tile (2x2 MFMA tiles); results leave as fp32 atomics
 // (rows of 32 consecutive n per half-wave = full-rate shape, MI355X_MICROARCH.md "Global float atomics").
+#include <type_traits>
 #include "wae_common.hpp"
 
 // One 128x128 output tile of one contraction; a launch processes an array of them (several weight gradients of a
@@ -105,8 +106,13 @@ __device__ __forceinline__ void tn_load_frags(const char* sp, const char* sq, in
   }
 }
 
-template <typename E>
-__global__ void __launch_bounds__(256, sizeof(E) == 2 ? 2 : 1) gemm_tn_kernel(TnArgs p) {
+// DET (wae_gemm_tn_tiles_det): the same loads, slabs, fragment reads and MFMA loop; the epilogue stores alpha * acc with plain
+// stores into the workgroup's own slot of `part` instead of adding it to C (tn_det_reduce_kernel adds the slots in a fixed order).
+struct TnArgsDet : TnArgs {
+  float* part;   // [ntiles][gridDim.y][128][128] fp32
+};
+template <typename E, bool DET>
+__global__ void __launch_bounds__(256, sizeof(E) == 2 ? 2 : 1) gemm_tn_kernel(std::conditional_t<DET, TnArgsDet, TnArgs> p) {
   using frag = typename ET<E>::frag;
   constexpr int ES = sizeof(E);
   constexpr int PITCH = ES == 2 ? TN_PITCH_BF16 : TN_PITCH_F32;
@@ -237,12 +243,73 @@ __global__ void __launch_bounds__(256, sizeof(E) == 2 ? 2 : 1) gemm_tn_kernel(Tn
       int col = wn + 32 * j + nl;
       const bool ones = tl.ones_col >= 0 && col == tl.ones_col;
       if (!(col < tl.n_valid || ones)) continue;
-      if (ones) col += b;
+      if constexpr (DET) {
+        // the slot of the LOGICAL (tile_i, kr): where it lies does not depend on which workgroup ran where.  Every element the
+        // reduce reads (rows < m_valid; columns < n_valid and the ones column, at its tile-local index) is stored exactly once,
+        // zeros for an empty time range included, so the buffer needs no clearing.
+        float* slot = p.part + ((int64_t)tile_i * gridDim.y + kr) * (128 * 128);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (row < tl.m_valid) atomicAdd(tl.C + (int64_t)row * tl.ldc + col, tl.alpha * acc[i][j][r]);
+        for (int r = 0; r < 16; ++r) {
+          const int row = wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
+          if (row < tl.m_valid) slot[row * 128 + col] = tl.alpha * acc[i][j][r];
+        }
+      } else {
+        if (ones) col += b;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
+          if (row < tl.m_valid) atomicAdd(tl.C + (int64_t)row * tl.ldc + col, tl.alpha * acc[i][j][r]);
+        }
       }
+    }
+}
+
+// Launch 2 of wae_gemm_tn_tiles_det: one thread per output element (row, c) of a tile's 128 x 128 window (blockIdx.x = tile,
+// blockIdx.y * 2 + threadIdx.x / 128 = row, threadIdx.x % 128 = c).  The order of include/wae.h, which DEFINES the result:
+//   data = sum of slot[kr][row][c] over kr = 0 .. nkr-1, one after another (kr = clip * nsp + split: clip-major, split-minor),
+//          taken when c < n_valid and c != ones_col;
+//   ones = sum of slot[b * nsp + s][row][ones_col] over s = 0 .. nsp-1, one after another, taken when c = ones_col + b, 0 <= b < B;
+//   C[row][c] = C[row][c] + (data + ones)          (one plain read-modify-write; a part not taken is left out, not added as zero)
+// Ones columns at ones_col + b >= 128 (outside the window) belong to thread c = (ones_col + b) % 128.
+__global__ void __launch_bounds__(256) tn_det_reduce_kernel(const TnTile* tiles, int tile0, const float* part, int nkr, int nsp, int B) {
+  const int tile_i = tile0 + blockIdx.x;
+  const TnTile tl = tiles[tile_i];
+  const int row = blockIdx.y * 2 + (threadIdx.x >> 7), c = threadIdx.x & 127;
+  if (row >= tl.m_valid) return;
+  const float* base = part + (int64_t)tile_i * nkr * (128 * 128) + row * 128;
+  const bool has_data = c < tl.n_valid && c != tl.ones_col;
+  const int b0 = tl.ones_col >= 0 ? c - tl.ones_col : -1;
+  const bool has_ones = b0 >= 0 && b0 < B;
+  float sum = 0.f;
+  if (has_data) {
+    const float* q = base + c;
+    int kr = 0;
+    for (; kr + 4 <= nkr; kr += 4) {      // four loads in flight, added in index order
+      const float v0 = q[(int64_t)kr * 16384], v1 = q[(int64_t)(kr + 1) * 16384], v2 = q[(int64_t)(kr + 2) * 16384],
+                  v3 = q[(int64_t)(kr + 3) * 16384];
+      sum = (((sum + v0) + v1) + v2) + v3;
+    }
+    for (; kr < nkr; ++kr) sum += q[(int64_t)kr * 16384];
+  }
+  auto clip_ones = [&](int b) {
+    const float* q = base + tl.ones_col + (int64_t)b * nsp * 16384;
+    float s = 0.f;
+    for (int i = 0; i < nsp; ++i) s += q[(int64_t)i * 16384];
+    return s;
+  };
+  if (has_ones) {
+    const float o = clip_ones(b0);
+    sum = has_data ? sum + o : o;
+  }
+  if (has_data || has_ones) {
+    float* dst = tl.C + (int64_t)row * tl.ldc + c;
+    *dst = *dst + sum;
+  }
+  if (tl.ones_col >= 0)
+    for (int col = c + 128; col < tl.ones_col + B; col += 128) {
+      if (col < tl.ones_col) continue;
+      float* dst = tl.C + (int64_t)row * tl.ldc + col;
+      *dst = *dst + clip_ones(col - tl.ones_col);
     }
 }
 
@@ -263,12 +330,57 @@ extern "C" int wae_gemm_tn_tiles(int32_t dtype, const wae_tn_tile* tiles_dev, in
   hipStream_t st = as_stream(stream);
   dim3 grid(ntiles, B * nsp);
   if (dtype == WAE_BF16) {
-    hipLaunchKernelGGL(gemm_tn_kernel<__bf16>, grid, dim3(256), lds, st, a);
+    hipLaunchKernelGGL((gemm_tn_kernel<__bf16, false>), grid, dim3(256), lds, st, a);
   } else if (dtype == WAE_F16) {
-    hipLaunchKernelGGL(gemm_tn_kernel<f16>, grid, dim3(256), lds, st, a);
+    hipLaunchKernelGGL((gemm_tn_kernel<f16, false>), grid, dim3(256), lds, st, a);
   } else {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(gemm_tn_kernel<float>, grid, dim3(256), lds, st, a);
+    (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((gemm_tn_kernel<float, false>), grid, dim3(256), lds, st, a);
   }
   return wae_check_launch("gemm_tn_tiles");
+}
+
+// ---- the fixed-order form: partials and an ordered reduce (include/wae.h) ----
+static int tn_det_nsp(int T, int splits, int* tchunk_out) {
+  int tchunk = (T + splits - 1) / splits;
+  tchunk = (tchunk + TN_KT - 1) / TN_KT * TN_KT;
+  if (tchunk_out) *tchunk_out = tchunk;
+  return (T + tchunk - 1) / tchunk;
+}
+extern "C" int64_t wae_gemm_tn_tiles_det_floats(int32_t ntiles, int32_t B, int32_t T, int32_t splits) {
+  if (ntiles <= 0 || B <= 0 || T <= 0 || splits < 1) return 0;
+  return (int64_t)ntiles * B * tn_det_nsp(T, splits, nullptr) * (128 * 128);
+}
+extern "C" int wae_gemm_tn_tiles_det(int32_t dtype, const wae_tn_tile* tiles_dev, int32_t ntiles, int32_t B, int32_t T,
+                                     int32_t splits, float* partials, int64_t partials_floats, int32_t ordered, void* stream) {
+  WAE_REQUIRE(tiles_dev && ntiles > 0 && B > 0 && T > 0 && splits >= 1 && partials, "gemm_tn_tiles_det: bad arguments");
+  WAE_REQUIRE(wae_dtype_ok(dtype), "gemm_tn_tiles_det: bad dtype");
+  WAE_REQUIRE(ordered == 0 || ordered == 1, "gemm_tn_tiles_det: ordered is 0 or 1");
+  WAE_REQUIRE(partials_floats >= wae_gemm_tn_tiles_det_floats(ntiles, B, T, splits),
+              "gemm_tn_tiles_det: the partials buffer is smaller than wae_gemm_tn_tiles_det_floats says");
+  TnArgsDet a;
+  a.tiles = (const TnTile*)tiles_dev;
+  a.B = B; a.T = T; a.dbg = 0;
+  const int nsp = tn_det_nsp(T, splits, &a.tchunk);
+  a.part = partials;
+  const int pitch = wae_is16(dtype) ? TN_PITCH_BF16 : TN_PITCH_F32;
+  const size_t lds = (size_t)4 * TN_KT * pitch;
+  hipStream_t st = as_stream(stream);
+  dim3 grid(ntiles, B * nsp);
+  if (dtype == WAE_BF16) {
+    hipLaunchKernelGGL((gemm_tn_kernel<__bf16, true>), grid, dim3(256), lds, st, a);
+  } else if (dtype == WAE_F16) {
+    hipLaunchKernelGGL((gemm_tn_kernel<f16, true>), grid, dim3(256), lds, st, a);
+  } else {
+    (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((gemm_tn_kernel<float, true>), grid, dim3(256), lds, st, a);
+  }
+  if (int rc = wae_check_launch("gemm_tn_tiles_det")) return rc;
+  if (ordered) {
+    for (int i = 0; i < ntiles; ++i)
+      hipLaunchKernelGGL(tn_det_reduce_kernel, dim3(1, 64), dim3(256), 0, st, a.tiles, i, partials, B * nsp, nsp, B);
+  } else {
+    hipLaunchKernelGGL(tn_det_reduce_kernel, dim3(ntiles, 64), dim3(256), 0, st, a.tiles, 0, partials, B * nsp, nsp, B);
+  }
+  return wae_check_launch("gemm_tn_tiles_det (reduce)");
 }

@@ -333,6 +333,59 @@ extern "C" int wae_clip_adam_ema(float* params, const float* grads, float* exp_a
   return wae_check_launch("clip_adam_ema");
 }
 
+// The same step with the norm summed in a FIXED ORDER (the deterministic train step): grad_sqnorm_kernel's per-thread walk and
+// per-workgroup sum, the workgroup's fp64 sum stored to parts[1 + blockIdx.x] instead of added by an atomic; one thread then adds the
+// workgroups' sums in index order into parts[0], which the clip + Adam + EMA launch reads.  parts: 1 + 1024 doubles, no clearing needed.
+__global__ void __launch_bounds__(256) grad_sqnorm_det_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ parts) {
+  double s = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * 1024;
+  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += stride) {
+    if (i + 3 < n) {
+      const f32x4 v = *(const f32x4*)(g + i);
+      s += (double)v.x * v.x + (double)v.y * v.y + (double)v.z * v.z + (double)v.w * v.w;
+    } else {
+      for (int64_t j = i; j < n; ++j) s += (double)g[j] * g[j];
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  __shared__ double part[4];
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) parts[1 + blockIdx.x] = ((part[0] + part[1]) + part[2]) + part[3];
+}
+__global__ void __launch_bounds__(256) grad_sqnorm_finish_kernel(double* __restrict__ parts, int nparts) {
+  __shared__ double stage[256];
+  double tot = 0.0;
+  for (int i0 = 0; i0 < nparts; i0 += 256) {     // nparts is uniform: every thread meets every barrier
+    const int m = min(256, nparts - i0);
+    if ((int)threadIdx.x < m) stage[threadIdx.x] = parts[1 + i0 + threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 0)
+      for (int i = 0; i < m; ++i) tot += stage[i];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) parts[0] = tot;
+}
+extern "C" int wae_clip_adam_ema_det(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, float* shadow, int64_t n,
+                                     double* parts, int64_t parts_doubles, float* grad_norm_out, int32_t step, double lr, double beta1,
+                                     double beta2, double eps, double weight_decay, double clip_thresh, double ema_decay,
+                                     void* stream) {
+  WAE_REQUIRE(params && grads && exp_avg && exp_avg_sq && parts && n > 0 && step >= 1, "clip_adam_ema_det: bad arguments");
+  WAE_REQUIRE(parts_doubles >= 1025, "clip_adam_ema_det: the partials need 1 + 1024 doubles");
+  hipStream_t st = as_stream(stream);
+  const int grid = (int)((n + 1023) / 1024 > 1024 ? 1024 : (n + 1023) / 1024);
+  hipLaunchKernelGGL(grad_sqnorm_det_kernel, dim3(grid), dim3(256), 0, st, grads, n, parts);
+  hipLaunchKernelGGL(grad_sqnorm_finish_kernel, dim3(1), dim3(256), 0, st, parts, grid);
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  hipLaunchKernelGGL(clip_adam_ema_kernel, dim3(2048), dim3(256), 0, st, params, grads, exp_avg, exp_avg_sq, shadow, n,
+                     (const double*)parts, grad_norm_out, (float)(lr / bc1), (float)beta1, (float)(1.0 - beta1), (float)beta2,
+                     (float)(1.0 - beta2), (float)eps, (float)weight_decay, (float)sqrt(bc2), (float)clip_thresh,
+                     (float)(1.0 - ema_decay));
+  return wae_check_launch("clip_adam_ema_det");
+}
+
 // The same step where `scratch` already holds the sum of the squares of ALL of grads: every wae_grad_finish launch of the backward
 // added the squares of the rows it wrote (csrc/grad_finish.hip), and the accumulator was cleared by the caller -- a fill job of the
 // launch that packs the backward weights.  No memset, no pass over grads for the norm.

@@ -752,6 +752,42 @@ extern "C" int wae_vq_slice(const float* lat, const float* emb, int64_t* idx, fl
   return wae_check_launch("vq_slice");
 }
 
+// The slice's commitment loss again, in a fixed order (the deterministic train step): vq_nearest_kernel adds every wave's squared error to
+// one float by atomics in arrival order, so stats[0] moves in its last bits from run to run.  One workgroup: thread j of 256 takes the
+// elements j, j + 256, ... of the slice in (b, channel, t) order, each difference and the sum in fp64, a xor butterfly over the 64 lanes,
+// the four waves in wave order (the sum of csrc/vq_list.hip); rounded to fp32 once; stats[0] = c_loss * (sum / ((float)N * (float)D)).
+__global__ void __launch_bounds__(256) vq_loss_det_kernel(const float* __restrict__ lat, const float* __restrict__ quant,
+                                                          float* __restrict__ stats, int Dtot, int d0, int D, int Tq, int64_t total,
+                                                          float c_loss) {
+  __shared__ double part[4];
+  double s = 0.0;
+  for (int64_t e = threadIdx.x; e < total; e += 256) {
+    const int t = (int)(e % Tq);
+    const int dch = (int)((e / Tq) % D);
+    const int64_t b = e / ((int64_t)Tq * D);
+    const int64_t at = (b * Dtot + d0 + dch) * Tq + t;
+    const double df = (double)quant[at] - (double)lat[at];
+    s += df * df;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+    for (int i = 0; i < 4; ++i) tot += part[i];
+    const float N = (float)(total / D);
+    stats[0] = c_loss * ((float)tot / (N * (float)D));
+  }
+}
+extern "C" int wae_vq_loss_det(const float* lat, const float* quant, float* stats, int32_t B, int32_t Dtot, int32_t d0, int32_t D,
+                               int32_t Tq, float c_loss, void* stream) {
+  WAE_REQUIRE(lat && quant && stats && B > 0 && D > 0 && Tq > 0 && d0 >= 0 && d0 + D <= Dtot, "vq_loss_det: bad arguments");
+  hipLaunchKernelGGL(vq_loss_det_kernel, dim3(1), dim3(256), 0, as_stream(stream), lat, quant, stats, Dtot, d0, D, Tq,
+                     (int64_t)B * D * Tq, c_loss);
+  return wae_check_launch("vq_loss_det");
+}
+
 extern "C" int wae_vq_nearest(const float* lat, const float* emb, int64_t* idx, float* quant, float* stats, int32_t* hist,
                               int32_t B, int32_t D, int32_t Tq, int32_t K, float beta, void* stream) {
   // vector_quantization.py:41-43: the forward values of the two loss terms are equal, so vq_loss = (beta + 1) * mse

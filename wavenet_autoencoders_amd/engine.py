@@ -53,7 +53,7 @@ class WaeEngine:
             raise L.WaeError("WaeEngine needs a ROCm GPU: the hot path has no CPU implementation")
         self.lib = L.lib()
         from .options import EngineOptions
-        self.opt = EngineOptions.from_env()       # every launch-path switch, read once (options.py)
+        self.opt = EngineOptions.from_env().pinned()       # every launch-path switch, read once (options.py)
         # GLU_PAIR (barrier on every second weight chunk of the fused layer kernel; bit-identical): measured -2.3 % per launch without
         # the z save, nothing with it -- so inference launches take it by default
         self.glu_flags = L.GLU_PAIR if self.opt.glu_pair == "1" else 0
@@ -133,9 +133,28 @@ class WaeEngine:
         # optimizer state (init_optimizer)
         self.exp_avg = self.exp_avg_sq = self.shadow = self.opt_scratch = self.grad_norm = None
         self.opt_step = 0
+        # EngineOptions.deterministic: the partials of the fixed-order sums, each grown to its largest use and reused on the one stream
+        # the mode runs on (det_buffer) -- "tn": wae_gemm_tn_tiles_det, "gproj": wae_gproj_bwd_det, "ups": wae_upsample_stage_bwd_det
+        # (fp32), "norm": wae_clip_adam_ema_det (fp64)
+        self._det_bufs: Dict[str, torch.Tensor] = {}
 
     def hold(self, slot: str, *tensors):
         self._keep[slot] = tensors
+
+    def det_buffer(self, name: str, n: int, dtype=torch.float32) -> torch.Tensor:
+        """The partials buffer `name` of the deterministic mode with at least n elements (never cleared: every user stores before it
+        reads).  A larger request replaces it; the old one stays alive in hold() until the launches that use it have run."""
+        buf = self._det_bufs.get(name)
+        if buf is None or buf.numel() < n:
+            if buf is not None:
+                self.hold("det_" + name, buf)
+            buf = self._det_bufs[name] = torch.empty(max(int(n), 1), dtype=dtype, device=self.device)
+        return buf
+
+    def _refuse_grad_sync(self, grad_sync):
+        if grad_sync is not None and self.opt.deterministic:
+            raise NotImplementedError("EngineOptions.deterministic with grad_sync: the order in which the all-reduce adds the ranks' "
+                                      "gradients is the collective library's; the mode covers one GPU")
 
     # Parameter generations.  Everything derived from the parameters -- the weight-normed arena and the fragment-packed buffers
     # (prepare_weights), the matrix-vector layout of the autoregressive kernels (pack_ar_weights) -- remembers the generation it was
@@ -398,6 +417,9 @@ class WaeEngine:
         L.check(self.lib.wae_vq_nearest(L.ptr(lat), L.ptr(self.eff[self.lay.off("vq.embedding.weight"):]), L.ptr(idx),
                                         L.ptr(quant), L.ptr(stats), L.ptr(hist), B, D, Tq, g.K, beta, self.stream()),
                 "vq_nearest")
+        if self.opt.deterministic:      # stats[0] again, from a fixed-order sum (the search adds its squared errors by float atomics)
+            L.check(self.lib.wae_vq_loss_det(L.ptr(lat), L.ptr(quant), L.ptr(stats), B, D, 0, D, Tq, beta + 1.0, self.stream()),
+                    "vq_loss_det")
         return quant, idx, stats
 
     def encode_list(self, feats, want_latents: bool = False, want_idx: bool = True, max_frames: Optional[int] = None):
@@ -1413,6 +1435,7 @@ class WaeEngine:
         vq_loss term; grad_sync, dy_factor: see backward.decoder_backward.  Inside accumulate() (flight.accum) the gradients stay in the
         accumulators and None is returned."""
         from . import backward as BW
+        self._refuse_grad_sync(grad_sync)
         if self.flight.accum is None:
             self._refuse_in_window("backward outside accumulate()")
         self.flight.ev_dc = None
@@ -1500,6 +1523,7 @@ class WaeEngine:
         Class-id input: masked cross-entropy; scalar input (hparams input_type "raw" / "mulaw"): discretized mixture of logistics,
         or mixture of Gaussians with geometry output_distribution "Normal"."""
         self._refuse_in_window("train_step")
+        self._refuse_grad_sync(grad_sync)
         if self.exp_avg is None:
             self.init_optimizer()
         self.prepare_weights(side=True)
@@ -1545,19 +1569,8 @@ class WaeEngine:
         if grad_hook is not None:
             grad_hook(grads)
         self.opt_step += 1
-        if self.flight.norm_summed and grad_sync is None and grad_hook is None:
-            # the gather passes of the backward (csrc/grad_finish.hip) summed the squares of every gradient while they wrote it, into
-            # an accumulator that the packing launch had cleared: no fill and no pass over the arena for the norm
-            L.check(self.lib.wae_clip_adam_ema_summed(L.ptr(self.params), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                                                      L.ptr(self.shadow), self.lay.total, L.ptr(self.gn_acc), L.ptr(self.grad_norm),
-                                                      self.opt_step, lr, betas[0], betas[1], eps, weight_decay, clip_thresh,
-                                                      ema_decay, self.stream()), "clip_adam_ema_summed")
-        else:
-            L.check(self.lib.wae_clip_adam_ema(L.ptr(self.params), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                                               L.ptr(self.shadow), self.lay.total, L.ptr(self.opt_scratch), L.ptr(self.grad_norm),
-                                               self.opt_step, lr, betas[0], betas[1], eps, weight_decay, clip_thresh, ema_decay,
-                                               self.stream()), "clip_adam_ema")
-        self.flight.norm_summed = False
+        self._clip_adam_ema(grads, self.flight.norm_summed and grad_sync is None and grad_hook is None, lr, betas, eps, weight_decay,
+                            clip_thresh, ema_decay)
         self.weights_dirty = True
         res = dict(ce=out["loss"], grad_norm=self.grad_norm[0])
         if self.g.has_encoder:
@@ -1565,6 +1578,22 @@ class WaeEngine:
         else:
             res["loss"] = out["loss"]
         return res
+
+    def _clip_adam_ema(self, grads, summed, lr, betas, eps, weight_decay, clip_thresh, ema_decay):
+        """clip_grad_norm_ + Adam + EMA on the finished gradients (csrc/loss.hip).  summed: the gather passes of the backward
+        (csrc/grad_finish.hip) summed the squares of every gradient while they wrote it, into an accumulator that the packing launch
+        had cleared -- no fill and no pass over the arena for the norm.  Deterministic mode: the pass over the arena with per-workgroup
+        partials added in index order."""
+        tail = (self.opt_step, lr, betas[0], betas[1], eps, weight_decay, clip_thresh, ema_decay, self.stream())
+        head = (L.ptr(self.params), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), L.ptr(self.shadow), self.lay.total)
+        if self.opt.deterministic:
+            parts = self.det_buffer("norm", 1025, torch.float64)
+            L.check(self.lib.wae_clip_adam_ema_det(*head, L.ptr(parts), parts.numel(), L.ptr(self.grad_norm), *tail), "clip_adam_ema_det")
+        elif summed:
+            L.check(self.lib.wae_clip_adam_ema_summed(*head, L.ptr(self.gn_acc), L.ptr(self.grad_norm), *tail), "clip_adam_ema_summed")
+        else:
+            L.check(self.lib.wae_clip_adam_ema(*head, L.ptr(self.opt_scratch), L.ptr(self.grad_norm), *tail), "clip_adam_ema")
+        self.flight.norm_summed = False
 
     # ------------------------------------------------------------------ gradient accumulation: micro-batches into one optimizer step
     def latent_elements(self, B: int, frames: int) -> int:
@@ -1662,6 +1691,7 @@ class WaeEngine:
         micro_batches: ce = sum ce_weight_i ce_i, vq_loss = sum vq_weight_i vq_loss_i, loss = ce + vq_loss, perp = the perplexity of
         the micro-batches' code counts added per code (score_list's convention: the concatenated batch's perplexity)."""
         from . import backward as BW
+        self._refuse_grad_sync(grad_sync)
         win = self.window
         if win is None or win.n == 0:
             raise RuntimeError("apply_step without an open accumulation window: accumulate() at least one micro-batch first "
@@ -1675,17 +1705,8 @@ class WaeEngine:
         L.check(self.lib.wae_accum_stats(L.ptr(win.sums), L.ptr(win.counts), self.g.K if win.counts is not None else 0, None, 0.0, None,
                                          0.0, None, L.ptr(out), self.stream()), "accum_stats (close)")
         self.opt_step += 1
-        if self.flight.norm_summed and grad_sync is None and grad_hook is None:
-            L.check(self.lib.wae_clip_adam_ema_summed(L.ptr(self.params), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                                                      L.ptr(self.shadow), self.lay.total, L.ptr(self.gn_acc), L.ptr(self.grad_norm),
-                                                      self.opt_step, lr, betas[0], betas[1], eps, weight_decay, clip_thresh,
-                                                      ema_decay, self.stream()), "clip_adam_ema_summed")
-        else:
-            L.check(self.lib.wae_clip_adam_ema(L.ptr(self.params), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq),
-                                               L.ptr(self.shadow), self.lay.total, L.ptr(self.opt_scratch), L.ptr(self.grad_norm),
-                                               self.opt_step, lr, betas[0], betas[1], eps, weight_decay, clip_thresh, ema_decay,
-                                               self.stream()), "clip_adam_ema")
-        self.flight.norm_summed = False
+        self._clip_adam_ema(grads, self.flight.norm_summed and grad_sync is None and grad_hook is None, lr, betas, eps, weight_decay,
+                            clip_thresh, ema_decay)
         self.window = None
         self.weights_dirty = True
         self.hold("window", win.sums, win.counts)
@@ -1721,6 +1742,7 @@ class WaeEngine:
         if not batches:
             raise ValueError("train_step_accum: no micro-batches")
         self._refuse_in_window("train_step_accum")
+        self._refuse_grad_sync(grad_sync)
         metas = []
         for x, c, gid, lengths in batches:
             frames = c.shape[-1] if (c is not None and self.g.has_encoder) else 0

@@ -34,7 +34,23 @@ The newest switch (its flip is checked in tests/test_grad_finish_host.py; bench.
   WAE_GRAD_FINISH          1         0: the step's gradients finished by the split launches (scatter into d_eff, weight-norm backward, a
                                      pass over the arena for the norm) instead of the gather pass behind the weight-gradient launch
                                      (csrc/grad_finish.hip; backward.py: _finish_plan says where the gather pass applies)
+
+The reproducible train step (opt-in; flips and repeats are checked in tests/test_deterministic_cpu.py and
+tests/test_gpu_deterministic.py):
+  WAE_DETERMINISTIC        0         1: every float sum of a train step that more than one workgroup feeds is formed in a fixed order:
+                                     the same weights, optimizer state, inputs, lengths, speaker ids and dropout seed give the same
+                                     bits (losses, every gradient, the norm, the updated state) on the same device model and build.
+                                     Not the default mode's bits.  grad_sync (data parallel) with it raises NotImplementedError.
+                                     It PINS, whatever else is set (EngineOptions.pinned):
+                                       tn_stream = False   the mode's weight gradients are the 128 x 128 tile launch with partials and an
+                                                           ordered reduce (wae_gemm_tn_tiles_det); the team launches have no such form
+                                       side = False        the front end's backward, the gather pass's small launches and the zb chain
+                                                           all add into d_eff; on one stream they do so in program order
+                                       chains = "1"        follows from the tile launches (they read both chains' rows)
+                                     and it takes the norm from a pass over the finished gradients (per-workgroup fp64 partials added
+                                     in index order), not from the gather pass's accumulator.
 """
+import dataclasses
 import os
 from dataclasses import dataclass
 
@@ -57,6 +73,13 @@ class EngineOptions:
     grad_finish: bool = True
     chains: str = "auto"
     side: bool = True
+    deterministic: bool = False
+
+    def pinned(self) -> "EngineOptions":
+        """The options an engine runs with: deterministic pins the switches whose default has no fixed-order form (module docstring)."""
+        if not self.deterministic:
+            return self
+        return dataclasses.replace(self, tn_stream=False, side=False, chains="1")
 
     @staticmethod
     def from_env() -> "EngineOptions":
@@ -77,7 +100,8 @@ class EngineOptions:
                              tn_static_head=e("WAE_TN_STATIC_HEAD", "1") != "0", tn_swap=e("WAE_TN_SWAP", "1") != "0", head_split=e("WAE_HEAD_SPLIT", "1") != "0",
                              head_wide=e("WAE_HEAD_WIDE", "0") == "1", glu_pair=pair, dp_split=e("WAE_DP_SPLIT", "1") != "0",
                              ar_coop=e("WAE_AR_COOP", "1") != "0", ar_coop_c=int(e("WAE_AR_COOP_C", "32")),
-                             bwd_fused=fused, bwd_fold_dc=e("WAE_BWD_FOLD_DC", "1") != "0", grad_finish=e("WAE_GRAD_FINISH", "1") != "0")
+                             bwd_fused=fused, bwd_fold_dc=e("WAE_BWD_FOLD_DC", "1") != "0", grad_finish=e("WAE_GRAD_FINISH", "1") != "0",
+                             deterministic=e("WAE_DETERMINISTIC", "0") == "1")
 
 
 def two_chains(mode: str, is16: bool, B: int, T: int, backward: bool) -> bool:

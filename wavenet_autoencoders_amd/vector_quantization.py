@@ -8,6 +8,13 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from .options import EngineOptions
+
+
+def _deterministic() -> bool:
+    """These modules run without an engine: the one switch they follow (the fixed-order commitment loss and codebook gradient of
+    the reproducible train step) is read when a forward runs."""
+    return EngineOptions.from_env().deterministic
 
 
 class _VQFn(torch.autograd.Function):
@@ -25,6 +32,9 @@ class _VQFn(torch.autograd.Function):
         st = ctypes.c_void_p(torch.cuda.current_stream(lat.device).cuda_stream)
         L.check(lib.wae_vq_nearest(L.ptr(lat), L.ptr(embc), L.ptr(idx), L.ptr(quant), L.ptr(stats), L.ptr(hist), B, D, Tq, K,
                                    float(beta), st), "vq_nearest")
+        ctx.det = _deterministic()
+        if ctx.det:
+            L.check(lib.wae_vq_loss_det(L.ptr(lat), L.ptr(quant), L.ptr(stats), B, D, 0, D, Tq, float(beta) + 1.0, st), "vq_loss_det")
         ctx.save_for_backward(lat, quant, idx)
         ctx.beta, ctx.K = float(beta), K
         ctx.mark_non_differentiable(idx)
@@ -40,8 +50,12 @@ class _VQFn(torch.autograd.Function):
         dq = dquant.contiguous().float() if dquant is not None else None
         scale = float(dloss) if dloss is not None else 0.0
         st = ctypes.c_void_p(torch.cuda.current_stream(lat.device).cuda_stream)
-        L.check(lib.wae_vq_bwd(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(demb), B, D, Tq, ctx.beta, scale,
-                               st), "vq_bwd")
+        if ctx.det:
+            L.check(lib.wae_vq_bwd_det(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(demb), B, D, Tq, ctx.K,
+                                       ctx.beta, scale, st), "vq_bwd_det")
+        else:
+            L.check(lib.wae_vq_bwd(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(demb), B, D, Tq, ctx.beta, scale,
+                                   st), "vq_bwd")
         return dlat, demb, None
 
 
@@ -76,6 +90,7 @@ class _SlicedFn(torch.autograd.Function):
         quant = torch.empty_like(lat)
         stats = torch.empty(len(embs), 2, dtype=torch.float32, device=dev)
         idxs, d0 = [], 0
+        det = ctx.det = _deterministic()
         for i, emb in enumerate(embs):
             K, D = emb.shape
             assert emb.is_contiguous() and emb.dtype == torch.float32
@@ -91,6 +106,8 @@ class _SlicedFn(torch.autograd.Function):
                 L.check(lib.wae_vq_slice(*args, 2, st), "vq_slice")
             else:
                 L.check(lib.wae_vq_slice(*args, 0, st), "vq_slice")
+            if det:      # the slice's loss again, from a fixed-order sum
+                L.check(lib.wae_vq_loss_det(L.ptr(lat), L.ptr(quant), L.ptr(stats[i]), B, Dtot, d0, D, Tq, c_loss, st), "vq_loss_det")
             idxs.append(idx)
             d0 += D
         assert d0 == Dtot, "codebook widths do not add up to the latent width"
@@ -112,8 +129,12 @@ class _SlicedFn(torch.autograd.Function):
         dembs, d0 = [], 0
         for idx, (K, D) in zip(idxs, ctx.shapes):
             demb = torch.zeros(K, D, dtype=torch.float32, device=lat.device) if spec["c_emb"] is not None else None
-            L.check(lib.wae_vq_slice_bwd(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(demb), B, Dtot, d0, D,
-                                         Tq, scale * spec["c_lat"], scale * (spec["c_emb"] or 0.0), st), "vq_slice_bwd")
+            if ctx.det:
+                L.check(lib.wae_vq_slice_bwd_det(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(demb), B, Dtot, d0, D,
+                                                 Tq, K, scale * spec["c_lat"], scale * (spec["c_emb"] or 0.0), st), "vq_slice_bwd_det")
+            else:
+                L.check(lib.wae_vq_slice_bwd(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(demb), B, Dtot, d0, D,
+                                             Tq, scale * spec["c_lat"], scale * (spec["c_emb"] or 0.0), st), "vq_slice_bwd")
             dembs.append(demb)
             d0 += D
         return (dlat, None, *dembs)
