@@ -215,6 +215,29 @@ int wae_vq_slice_bwd(const float* lat, const float* quant, const int64_t* idx, c
                      float* demb, int32_t B, int32_t Dtot, int32_t d0, int32_t D, int32_t Tq, float c_lat, float c_emb,
                      void* stream);
 
+/* ---- every slice of a sliced quantiser in ONE search launch (csrc/misc.hip) -----------------------------------------
+ * wae_vq_search_slices: wae_vq_slice for nslices slices of one (B,Dtot,Tq) tensor at once.  recs_host: a HOST array of nslices
+ * records {emb (K,D) device pointer, d0, D, K, c_loss}; they travel as a kernel argument by value -- no table upload, no
+ * allocation, no synchronisation.  Per slice s the semantics are exactly wae_vq_slice's: mode 0 search + gather, 1 search only,
+ * 2 gather from the idx given; first minimum wins; stats[s] = {c_loss_s * mean((q-x)^2) over the slice, slice perplexity}.
+ * idx: (nslices, B*Tq) int64, row s the slice's indices; quant: (B,Dtot,Tq), channels no slice covers are not written (may be NULL in
+ * mode 1); stats: (nslices, 2).  scratch: wae_vq_search_slices_scratch(recs, nslices) = sum K_s + nslices int32 entries -- the slices'
+ * counts back to back (slice s at offset sum of K_r, r < s: the `hist` wae_vq_ema_update reads), then nslices float cells of squared
+ * error.  A call is ONE memset (mode 2: the float cells only, the counts stay), ONE search launch on a (B*Tq, nslices) grid and ONE
+ * statistics launch, whatever nslices is.
+ * idx, quant, the counts and stats[s][1] are bit for bit what wae_vq_slice gives for slice s alone (the two kernels share the
+ * per-vector function); stats[s][0] is the same sum of float atomics in arrival order, so not bitwise: wae_vq_loss_det per slice
+ * makes it reproducible.
+ * WAE_EINVAL before any launch: a null lat / recs / idx / stats / scratch / emb, quant null outside mode 1, nslices outside
+ * 1..WAE_VQ_MAX_SLICES, a slice with D < 1, K < 1 or not inside [0, Dtot), two slices that overlap, a mode outside 0..2, B, Dtot
+ * or Tq < 1.  WAE_EUNSUPPORTED: a slice wider than 15872 channels (LDS).  The scratch query returns WAE_EINVAL for the same record
+ * errors (it does not know Dtot or the pointers). */
+#define WAE_VQ_MAX_SLICES 8
+typedef struct wae_vq_slice_rec { const float* emb; int32_t d0, D, K; float c_loss; } wae_vq_slice_rec;
+int64_t wae_vq_search_slices_scratch(const wae_vq_slice_rec* recs_host, int32_t nslices);
+int wae_vq_search_slices(const float* lat, const wae_vq_slice_rec* recs_host, int32_t nslices, int64_t* idx, float* quant,
+                         float* stats, int32_t* scratch, int32_t B, int32_t Dtot, int32_t Tq, int32_t mode, void* stream);
+
 /* ---- the quantiser's statistics of a packed list, per utterance and for the list as one batch (vector_quantization.py:41-47 for
  * every item as a batch of one; csrc/vq_list.hip).  wae_vq_nearest on the packed latents of a list (B = 1, Tq = pitch) gives idx and
  * quant per frame; its stats are the aggregate of whatever was packed, and its squared error a chain of float atomics in arrival order.

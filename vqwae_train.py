@@ -67,7 +67,8 @@ def build_geometry(hp) -> Geometry:
                     upsample_scales=list(hp.upsample_params["upsample_scales"]) if hp.upsample_conditional_features else None,
                     cin_pad=hp.cin_pad, scalar_input=is_scalar_input(hp.input_type), use_speaker_embedding=True,
                     c_in=hp.dim_in, encoder_hid=hp.encoder_hid, K=256, conv_in=hp.upsample_net != "UpsampleNetwork",
-                    up_act=up_act, up_act_slope=up_slope, output_distribution=hp.output_distribution)
+                    up_act=up_act, up_act_slope=up_slope, output_distribution=hp.output_distribution, vq=hp.quantizer,
+                    vq_slices=hp.num_slices, vq_decay=hp.vq_decay)
 
 
 def evaluate(eng, loader, device, hp, packed=False, packed_total=False):
@@ -227,6 +228,9 @@ def main(argv=None):
 
     from wavenet_autoencoders_amd.engine import WaeEngine
     geom = build_geometry(hp)
+    if args.accum_steps > 1 and geom.vq != "plain":
+        raise NotImplementedError(f"--accum-steps {args.accum_steps} with hparams quantizer={geom.vq!r}: accumulation windows cover the "
+                                  "plain quantiser (WaeEngine.accumulate)")
     if engine_switches(args).deterministic and world > 1:
         raise NotImplementedError("--deterministic with data parallel: the all-reduce's order of additions is the collective library's")
     eng = WaeEngine(geom, dtype=args.dtype, device=device, dropout=float(hp.dropout),            # vqwae_train.py:933
@@ -239,7 +243,7 @@ def main(argv=None):
         pass
     tmp = _Init()
     tmp._init_arena(geom, "")
-    eng.load_state_dict({k: v.detach() for k, v in tmp.state_dict().items()})
+    eng.load_state_dict({k: v.detach() for k, v in tmp.state_dict().items()}, strict=False)      # (an EMA quantiser's statistics start at zero)
     step, epoch, test_step = 0, 0, 0
     use_ema = bool(hp.exponential_moving_average)
     if args.restore_parts:

@@ -56,6 +56,13 @@ class VqSeg(ctypes.Structure):           # include/wae.h: wae_vq_seg (device arr
     _fields_ = [(n, c_i32) for n in ("q_off", "Tq")]
 
 
+VQ_MAX_SLICES = 8
+
+
+class VqSliceRec(ctypes.Structure):      # include/wae.h: wae_vq_slice_rec (HOST array element of wae_vq_search_slices)
+    _fields_ = [("emb", c_vp), ("d0", c_i32), ("D", c_i32), ("K", c_i32), ("c_loss", c_f32)]
+
+
 class TmDesc(ctypes.Structure):
     _fields_ = [(n, c_i32) for n in ("dtype", "B", "T", "M", "nsrc", "mode")] + [("alpha", c_f32), ("flags", c_i32)]
 
@@ -163,6 +170,9 @@ SIGNATURES = {
     "wae_vq_slice": (c_i32, [c_vp] * 6 + [c_i32] * 6 + [c_f32, c_i32, c_vp]),
     "wae_vq_ema_update": (c_i32, [c_vp] * 6 + [c_i32] * 6 + [c_f32, c_vp]),
     "wae_vq_slice_bwd": (c_i32, [c_vp] * 6 + [c_i32] * 5 + [c_f32, c_f32, c_vp]),
+    "wae_vq_search_slices_scratch": (c_i64, [ctypes.POINTER(VqSliceRec), c_i32]),
+    # lat, recs_host, nslices, idx, quant, stats, scratch, B, Dtot, Tq, mode, stream
+    "wae_vq_search_slices": (c_i32, [c_vp, ctypes.POINTER(VqSliceRec), c_i32, c_vp, c_vp, c_vp, c_vp] + [c_i32] * 4 + [c_vp]),
     "wae_first_conv_fwd": (c_i32, [c_vp] * 5 + [c_i64, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "wae_onehot_rows": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_vp]),
     "wae_softmax_bct_fwd": (c_i32, [c_vp, c_vp, c_i32, c_i32, c_i32, c_vp]),

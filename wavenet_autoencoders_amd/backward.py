@@ -1422,7 +1422,19 @@ def frontend_backward(eng, dc: torch.Tensor, loss_scale: float = 1.0, stop_at_qu
         Tq = lat.shape[-1]
         dlat = torch.empty_like(lat)
         en = "vq.embedding.weight"
-        if eng.opt.deterministic:      # the codebook gradient by one workgroup per code
+        if g.vq != "plain":
+            # the sliced / EMA kinds: every slice's rows of dlat, and its codebook's gradient where it has one (EMA codebooks: none --
+            # their arena slice keeps the zero gradient under which the optimizer leaves them alone)
+            _, c_lat, c_emb = P.vq_coeffs(g, sv.beta)
+            scale = float(loss_scale) * 2.0 / (B * g.Cc * Tq)
+            for s, (name, d0, Ds, K) in enumerate(P.vq_slice_specs(g)):
+                demb = eng.d_eff[lay.off(name + ".weight"):] if c_emb is not None else None
+                head = (L.ptr(lat), L.ptr(quant), L.ptr(idx[s] if g.vq_n > 1 else idx), L.ptr(dq), L.ptr(dlat), L.ptr(demb), B, g.Cc, d0, Ds, Tq)
+                if eng.opt.deterministic:
+                    L.check(lib.wae_vq_slice_bwd_det(*head, K, scale * c_lat, scale * (c_emb or 0.0), st), "vq_slice_bwd_det")
+                else:
+                    L.check(lib.wae_vq_slice_bwd(*head, scale * c_lat, scale * (c_emb or 0.0), st), "vq_slice_bwd")
+        elif eng.opt.deterministic:      # the codebook gradient by one workgroup per code
             L.check(lib.wae_vq_bwd_det(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(eng.d_eff[lay.off(en):]), B,
                                        g.Cc, Tq, g.K, sv.beta, loss_scale, st), "vq_bwd_det")
         else:

@@ -97,6 +97,7 @@ def save_checkpoint(eng, step: int, epoch: int, checkpoint_dir: str, hp, rank: i
         for k in eng.lay.offsets:
             off, n = eng.lay.off(k), eng.lay.numel(k)
             ema_sd[k] = eng.shadow[off:off + n].view(eng.lay.shapes[k]).cpu()
+        ema_sd.update({k: v.cpu() for k, v in eng.vq_buffers.items()})      # the EMA quantisers' statistics: buffers, no shadow of their own
         epath = os.path.join(checkpoint_dir, "checkpoint_step{:09d}_ema.pth".format(step))
         torch.save({"state_dict": ema_sd, "optimizer": opt, "global_step": step, "global_epoch": epoch,
                     "global_test_step": test_step}, epath)

@@ -656,15 +656,14 @@ extern "C" int wae_enc_conv_fwd(const float* x, const float* w, const float* bia
 // The kernel works on channels [d0, d0+D) of a (B, Dtot, Tq) tensor.  mode 0: search + gather, 1: search only,
 // 2: gather with the indices given (after an EMA update moved the codebook).
 // ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) vq_nearest_kernel(const float* __restrict__ lat, const float* __restrict__ emb,
-                                                         int64_t* __restrict__ idx, float* __restrict__ quant,
-                                                         float* __restrict__ sqerr, int32_t* __restrict__ hist, int Dtot,
-                                                         int d0, int D, int Tq, int K, int mode) {
-  extern __shared__ float sh[];
+// The per-vector body, shared by the one-slice kernel and the all-slices kernel below (one function: a slice's idx, quant and counts
+// are the same bits whichever kernel searched it).  sh: (D + 512) floats of LDS; every thread of the 256 calls it.
+__device__ __forceinline__ void vq_row(const float* __restrict__ lat, const float* __restrict__ emb, int64_t* __restrict__ idx,
+                                       float* __restrict__ quant, float* __restrict__ sqerr, int32_t* __restrict__ hist,
+                                       float* sh, int row, int Dtot, int d0, int D, int Tq, int K, int mode) {
   float* xs = sh;                      // D
   float* best_d = sh + D;              // 256
   int* best_i = (int*)(best_d + 256);  // 256
-  const int row = blockIdx.x;          // b*Tq + t
   const int b = row / Tq, t = row % Tq;
   const int64_t base = ((int64_t)b * Dtot + d0) * Tq + t;
   for (int i = threadIdx.x; i < D; i += 256) xs[i] = lat[base + (int64_t)i * Tq];
@@ -717,6 +716,14 @@ __global__ void __launch_bounds__(256) vq_nearest_kernel(const float* __restrict
   }
   se = wave_sum(se);
   if ((threadIdx.x & 63) == 0 && se != 0.f) atomicAdd(sqerr, se);
+}
+
+__global__ void __launch_bounds__(256) vq_nearest_kernel(const float* __restrict__ lat, const float* __restrict__ emb,
+                                                         int64_t* __restrict__ idx, float* __restrict__ quant,
+                                                         float* __restrict__ sqerr, int32_t* __restrict__ hist, int Dtot,
+                                                         int d0, int D, int Tq, int K, int mode) {
+  extern __shared__ float sh[];
+  vq_row(lat, emb, idx, quant, sqerr, hist, sh, blockIdx.x /* b*Tq + t */, Dtot, d0, D, Tq, K, mode);
 }
 
 // stats[0] = c_loss * mean((q-x)^2) over the slice (mode != 1); stats[1] = perplexity of the slice (mode != 2)
@@ -792,6 +799,107 @@ extern "C" int wae_vq_nearest(const float* lat, const float* emb, int64_t* idx, 
                               int32_t B, int32_t D, int32_t Tq, int32_t K, float beta, void* stream) {
   // vector_quantization.py:41-43: the forward values of the two loss terms are equal, so vq_loss = (beta + 1) * mse
   return wae_vq_slice(lat, emb, idx, quant, stats, hist, B, D, 0, D, Tq, K, beta + 1.0f, 0, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// wae_vq_search_slices: every slice of a sliced quantiser in one search launch (include/wae.h).  Workgroup (row, s) runs vq_row on
+// slice s of latent vector row, exactly what wae_vq_slice's workgroup `row` does for that slice alone; one workgroup per slice then
+// makes the slice's two statistics as vq_stats_kernel does.  The slices' records are a kernel argument (by value): nothing is uploaded.
+// scratch: the slices' counts back to back (slice s at hoff[s] = sum of K_r, r < s), then one float of squared error per slice.
+// ---------------------------------------------------------------------------------------------------
+struct vq_slices_arg {
+  const float* emb[WAE_VQ_MAX_SLICES];
+  int32_t d0[WAE_VQ_MAX_SLICES], D[WAE_VQ_MAX_SLICES], K[WAE_VQ_MAX_SLICES], hoff[WAE_VQ_MAX_SLICES];
+  float c_loss[WAE_VQ_MAX_SLICES];
+  int32_t sumK;
+};
+
+__global__ void __launch_bounds__(256) vq_search_slices_kernel(const float* __restrict__ lat, const vq_slices_arg a,
+                                                               int64_t* __restrict__ idx, float* __restrict__ quant,
+                                                               int32_t* __restrict__ scratch, int Dtot, int Tq, int N, int mode) {
+  extern __shared__ float sh[];
+  const int s = blockIdx.y;
+  vq_row(lat, a.emb[s], idx + (int64_t)s * N, quant, (float*)(scratch + a.sumK) + s, scratch + a.hoff[s], sh, blockIdx.x, Dtot,
+         a.d0[s], a.D[s], Tq, a.K[s], mode);
+}
+
+__global__ void __launch_bounds__(256) vq_slices_stats_kernel(const int32_t* __restrict__ scratch, const vq_slices_arg a,
+                                                              float* __restrict__ stats, int N, int mode) {
+  __shared__ float part[4];
+  const int s = blockIdx.x;
+  const float perp = vq_perplexity(scratch + a.hoff[s], a.K[s], (float)N, part, mode != 2);      // csrc/vq_stats.hpp
+  if (threadIdx.x == 0) {
+    const float mse = ((const float*)(scratch + a.sumK))[s] / ((float)N * (float)a.D[s]);
+    if (mode != 1) stats[2 * s] = a.c_loss[s] * mse;
+    if (mode != 2) stats[2 * s + 1] = perp;
+  }
+}
+
+// the records' checks, shared by the two entries: 0 and a message, or the sum of the K_s
+static int64_t vq_slices_check(const wae_vq_slice_rec* recs, int32_t nslices, int32_t Dtot, bool need_emb) {
+  if (!recs || nslices < 1 || nslices > WAE_VQ_MAX_SLICES) {
+    wae_set_error("vq_search_slices: recs is null or nslices = %d outside 1..%d", nslices, WAE_VQ_MAX_SLICES);
+    return 0;
+  }
+  int64_t sumK = 0;
+  for (int s = 0; s < nslices; ++s) {
+    const wae_vq_slice_rec& r = recs[s];
+    if (r.K < 1 || r.D < 1 || r.d0 < 0 || (need_emb && (!r.emb || (int64_t)r.d0 + r.D > Dtot))) {
+      wae_set_error("vq_search_slices: slice %d (d0 %d, D %d, K %d) is empty, has no codebook or lies outside [0, %d)", s, r.d0, r.D, r.K,
+                    Dtot);
+      return 0;
+    }
+    for (int q = 0; q < s; ++q)
+      if (r.d0 < recs[q].d0 + recs[q].D && recs[q].d0 < r.d0 + r.D) {
+        wae_set_error("vq_search_slices: slices %d and %d overlap", q, s);
+        return 0;
+      }
+    sumK += r.K;
+  }
+  if (sumK + nslices >= (int64_t)1 << 31) {
+    wae_set_error("vq_search_slices: %lld codes in all", (long long)sumK);
+    return 0;
+  }
+  return sumK;
+}
+
+extern "C" int64_t wae_vq_search_slices_scratch(const wae_vq_slice_rec* recs_host, int32_t nslices) {
+  const int64_t sumK = vq_slices_check(recs_host, nslices, 0, false);
+  return sumK > 0 ? sumK + nslices : WAE_EINVAL;
+}
+
+extern "C" int wae_vq_search_slices(const float* lat, const wae_vq_slice_rec* recs_host, int32_t nslices, int64_t* idx, float* quant,
+                                    float* stats, int32_t* scratch, int32_t B, int32_t Dtot, int32_t Tq, int32_t mode, void* stream) {
+  WAE_REQUIRE(lat && idx && stats && scratch && mode >= 0 && mode <= 2 && (quant || mode == 1), "vq_search_slices: null pointer or bad mode");
+  WAE_REQUIRE(B > 0 && Dtot > 0 && Tq > 0 && (int64_t)B * Tq < ((int64_t)1 << 31), "vq_search_slices: bad sizes");
+  const int64_t sumK = vq_slices_check(recs_host, nslices, Dtot, true);
+  if (sumK <= 0) return WAE_EINVAL;
+  vq_slices_arg a = {};
+  int maxD = 0;
+  for (int s = 0, off = 0; s < nslices; ++s) {
+    const wae_vq_slice_rec& r = recs_host[s];
+    a.emb[s] = r.emb, a.d0[s] = r.d0, a.D[s] = r.D, a.K[s] = r.K, a.hoff[s] = off, a.c_loss[s] = r.c_loss;
+    off += r.K;
+    maxD = r.D > maxD ? r.D : maxD;
+  }
+  a.sumK = (int32_t)sumK;
+  hipStream_t st = as_stream(stream);
+  // mode 2 keeps the counts: only the squared-error cells behind them are cleared
+  const hipError_t e = mode == 2 ? hipMemsetAsync(scratch + sumK, 0, (size_t)nslices * sizeof(float), st)
+                                 : hipMemsetAsync(scratch, 0, (size_t)(sumK + nslices) * sizeof(int32_t), st);
+  if (e != hipSuccess) {
+    wae_set_error("vq_search_slices: memset failed");
+    return WAE_EHIP;
+  }
+  const size_t lds = (size_t)(maxD + 512) * sizeof(float);
+  if (lds > 65536) {
+    wae_set_error("vq_search_slices: a slice of %d channels; a latent vector and the search's 2 KiB stay in 64 KiB of LDS", maxD);
+    return WAE_EUNSUPPORTED;
+  }
+  const int N = B * Tq;
+  hipLaunchKernelGGL(vq_search_slices_kernel, dim3(N, nslices), dim3(256), lds, st, lat, a, idx, quant, scratch, Dtot, Tq, N, mode);
+  hipLaunchKernelGGL(vq_slices_stats_kernel, dim3(nslices), dim3(256), 0, st, (const int32_t*)scratch, a, stats, N, mode);
+  return wae_check_launch("vq_search_slices");
 }
 
 // ---------------------------------------------------------------------------------------------------

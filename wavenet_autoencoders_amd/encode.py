@@ -264,7 +264,8 @@ class EncodeSession:
             quant, idx, _ = eng.vq_forward(lat.view(1, g.Cc, plan.total_new))
             quant = quant[0]
         else:
-            quant, idx = torch.empty_like(lat), torch.empty(0, dtype=torch.int64, device=dev)
+            quant = torch.empty_like(lat)
+            idx = torch.empty((g.vq_n, 0) if g.vq_n > 1 else 0, dtype=torch.int64, device=dev)      # sliced kinds: a row per slice
         eng.hold("encode_session_feed", table, x)
         out = {}
         for (h, c), ready, o, n in zip(todo, plan.ready, plan.q_off, plan.q_cnt):
@@ -272,7 +273,7 @@ class EncodeSession:
             c.frames += new.get(h, 0)
             c.final = int(ready)
             done = h in ended
-            out[h] = dict(quant=quant[:, s], idx=idx[s], latents=lat[:, s] if self.want_latents else None, final=c.final, done=done)
+            out[h] = dict(quant=quant[:, s], idx=idx[..., s], latents=lat[:, s] if self.want_latents else None, final=c.final, done=done)
             if done:        # its last chunk is handed out: the room goes back
                 del self.clips[h]
                 self._release(c)

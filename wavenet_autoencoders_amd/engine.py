@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
+import functools
 import math
 
 from typing import Dict, Optional
@@ -114,6 +115,11 @@ class WaeEngine:
         self.flight = InFlight()
         self.window: Optional[Window] = None    # an open accumulation window (accumulate .. apply_step / discard_step)
         self._vq_hist = None                    # the code counts of the last vq_forward (K + 1 int32; accumulate adds them to the window's)
+        # the EMA quantisers' statistics (packing.vq_buffer_specs: vq.ema_cluster_size[s], vq.ema_w[s]): fp32 tensors of their own,
+        # outside the parameter arena -- clipping, Adam and the EMA shadow never see them; empty for the other kinds
+        self.vq_buffers: Dict[str, torch.Tensor] = {name: torch.zeros(shape, dtype=torch.float32, device=dev)
+                                                    for name, shape in P.vq_buffer_specs(geom)}
+        self._vq_recs: Dict[float, tuple] = {}  # vq_forward of the sliced / EMA kinds: the slices' records per beta (host array, c_loss_s)
         self._keep = {}                         # hold(): buffers passed by raw pointer, alive until their slot's next use
         # encode_list_stats: the list's quantiser totals over all its groups, (4,) fp32 on the device --
         # [vq_loss, perplexity, sum Tq, sum sqerr] (include/wae.h: wae_vq_stats_segments `out`); None before the first such call
@@ -151,7 +157,15 @@ class WaeEngine:
             buf = self._det_bufs[name] = torch.empty(max(int(n), 1), dtype=dtype, device=self.device)
         return buf
 
+    def _refuse_accum_vq(self):
+        if self.g.has_encoder and self.g.vq != "plain":
+            raise NotImplementedError(f"gradient accumulation with the {self.g.vq!r} quantiser: a window keeps one code histogram "
+                                      "(wae_accum_stats); accumulation windows cover the plain quantiser")
+
     def _refuse_grad_sync(self, grad_sync):
+        if grad_sync is not None and self.g.has_encoder and self.g.vq_ema:
+            raise NotImplementedError(f"grad_sync with the {self.g.vq!r} quantiser: the codebooks move by each rank's EMA statistics, "
+                                      "which would need an all-reduce of their own; data-parallel steps cover the plain and sliced kinds")
         if grad_sync is not None and self.opt.deterministic:
             raise NotImplementedError("EngineOptions.deterministic with grad_sync: the order in which the all-reduce adds the ranks' "
                                       "gradients is the collective library's; the mode covers one GPU")
@@ -295,10 +309,15 @@ class WaeEngine:
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], strict: bool = True):
         self._refuse_in_window("load_state_dict")
-        missing = [k for k in self.lay.offsets if k not in sd]
-        extra = [k for k in sd if k not in self.lay.offsets]
+        keys = list(self.lay.offsets) + list(self.vq_buffers)
+        missing = [k for k in keys if k not in sd]
+        extra = [k for k in sd if k not in self.lay.offsets and k not in self.vq_buffers]
         if strict and (missing or extra):
             raise KeyError(f"state_dict mismatch: missing {missing[:5]}, unexpected {extra[:5]}")
+        for k, buf in self.vq_buffers.items():
+            if k in sd:
+                if tuple(sd[k].shape) != tuple(buf.shape):
+                    raise ValueError(f"{k}: expected {tuple(buf.shape)}, got {tuple(sd[k].shape)}")
         host = torch.zeros(self.lay.total, dtype=torch.float32)
         for k in self.lay.offsets:
             if k in sd:
@@ -307,10 +326,15 @@ class WaeEngine:
                     raise ValueError(f"{k}: expected {self.lay.shapes[k]}, got {tuple(sd[k].shape)}")
                 host[self.lay.off(k):self.lay.off(k) + t.numel()] = t
         self.params.copy_(host.to(self.device))
+        for k, buf in self.vq_buffers.items():
+            if k in sd:
+                buf.copy_(sd[k].detach().to(torch.float32))
         self.weights_dirty = True
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
-        return {k: self.view(k).detach().clone() for k in self.lay.offsets}
+        sd = {k: self.view(k).detach().clone() for k in self.lay.offsets}
+        sd.update({k: v.detach().clone() for k, v in self.vq_buffers.items()})
+        return sd
 
     def prepare_weights(self, side: bool = False):
         """K14 weight norm + fragment packing; call after every parameter update.  side (train_step): the packing runs on a side stream
@@ -406,9 +430,13 @@ class WaeEngine:
             save.enc_acts = acts       # inputs of every block (+ the last block's output): backward needs them
         return lat
 
-    def vq_forward(self, lat: torch.Tensor, beta: float = 0.25):
-        """a2: -> (quant (B,Cc,Tq), idx int64 (B*Tq), stats[2] = (vq_loss, perplexity))."""
+    def vq_forward(self, lat: torch.Tensor, beta: float = 0.25, update: bool = False):
+        """a2: -> (quant (B,Cc,Tq), idx int64 (B*Tq), stats[2] = (vq_loss, perplexity)).  The sliced kinds (Geometry.vq): idx
+        (n, B*Tq), a row per slice; vq_loss and perplexity the sums over the slices (vector_quantization.py:113-127).
+        update (EMA kinds): the training branch -- the codebooks move between the search and the gather."""
         g = self.g
+        if g.vq != "plain":
+            return self._vq_forward_slices(lat, float(beta), bool(update))
         B, D, Tq = lat.shape
         idx = torch.empty(B * Tq, dtype=torch.int64, device=self.device)
         quant = torch.empty_like(lat)
@@ -421,6 +449,61 @@ class WaeEngine:
             L.check(self.lib.wae_vq_loss_det(L.ptr(lat), L.ptr(quant), L.ptr(stats), B, D, 0, D, Tq, beta + 1.0, self.stream()),
                     "vq_loss_det")
         return quant, idx, stats
+
+    def vq_slice_records(self, beta: float):
+        """The slices of the geometry's quantiser for wae_vq_search_slices: (host array of wae_vq_slice_rec -- codebook pointers into
+        the effective arena, c_loss_s = c_loss * D_s / Dtot --, [(codebook name, d0, D, K, c_loss_s)], scratch entries).  Made once per
+        beta: the arena never moves."""
+        hit = self._vq_recs.get(beta)
+        if hit is None:
+            g = self.g
+            c_loss = P.vq_coeffs(g, beta)[0]
+            specs = [(name + ".weight", d0, D, K, c_loss * D / g.Cc) for name, d0, D, K in P.vq_slice_specs(g)]
+            recs = (L.VqSliceRec * len(specs))(*[L.VqSliceRec(self.eff.data_ptr() + 4 * self.lay.off(name), d0, D, K, cl)
+                                                 for name, d0, D, K, cl in specs])
+            words = int(self.lib.wae_vq_search_slices_scratch(recs, len(specs)))
+            if words < 1:
+                raise L.WaeError(f"vq_search_slices_scratch: {self.lib.wae_last_error().decode()}")
+            hit = self._vq_recs[beta] = (recs, specs, words)
+        return hit
+
+    def _vq_forward_slices(self, lat: torch.Tensor, beta: float, update: bool):
+        """vq_forward of the sliced / EMA kinds: ONE wae_vq_search_slices call for all slices (two around the codebook update)."""
+        g, lib, st, dev = self.g, self.lib, self.stream(), self.device
+        B, D, Tq = lat.shape
+        recs, specs, words = self.vq_slice_records(beta)
+        n = len(specs)
+        idx = torch.empty(n, B * Tq, dtype=torch.int64, device=dev)
+        quant = torch.empty_like(lat)
+        stats = torch.empty(n, 2, dtype=torch.float32, device=dev)
+        scratch = self._vq_hist = torch.empty(words, dtype=torch.int32, device=dev)
+        call = lambda mode: L.check(lib.wae_vq_search_slices(L.ptr(lat), recs, n, L.ptr(idx), L.ptr(quant), L.ptr(stats), L.ptr(scratch),  # noqa: E731
+                                                             B, D, Tq, mode, st), "vq_search_slices")
+        if update and g.vq_ema:
+            call(1)
+            hoff = 0
+            for s, (name, d0, Ds, K, _) in enumerate(specs):
+                sfx = name[len("vq.embedding"):-len(".weight")]
+                off = self.lay.off(name)
+                L.check(lib.wae_vq_ema_update(L.ptr(lat), L.ptr(idx[s]), L.ptr(scratch[hoff:]), L.ptr(self.vq_buffers["vq.ema_cluster_size" + sfx]),
+                                              L.ptr(self.vq_buffers["vq.ema_w" + sfx]), L.ptr(self.eff[off:]), B, D, d0, Ds, Tq, K,
+                                              float(g.vq_decay), st), "vq_ema_update")
+                # the codebook moved where the search reads it (the effective arena); the parameters are what state_dict, the next
+                # weight norm pass and the optimizer read
+                self.params[off:off + K * Ds].copy_(self.eff[off:off + K * Ds])
+                hoff += K
+            call(2)
+        else:
+            call(0)
+        if self.opt.deterministic:      # every slice's stats[0] again, from a fixed-order sum
+            for s, (_, d0, Ds, _, cl) in enumerate(specs):
+                L.check(lib.wae_vq_loss_det(L.ptr(lat), L.ptr(quant), L.ptr(stats[s]), B, D, d0, Ds, Tq, cl, st), "vq_loss_det")
+        if g.vq_n == 1:
+            return quant, idx[0], stats[0]
+        tot = stats[0]
+        for s in range(1, n):      # in slice order (element-wise adds: the same bits wherever the same slices' numbers are added)
+            tot = tot + stats[s]
+        return quant, idx, tot
 
     def encode_list(self, feats, want_latents: bool = False, want_idx: bool = True, max_frames: Optional[int] = None):
         """Encoder + quantiser for a LIST of utterances of unequal lengths (include/wae.h: wae_enc_conv_fwd_list): one launch per
@@ -451,7 +534,10 @@ class WaeEngine:
         int32 view: how often the utterance used every code.  The list's totals over all groups go to self.last_list_stats, a (4,)
         device tensor [vq_loss, perplexity, sum Tq, sum sqerr] of the list as ONE batch: vq_loss = (beta + 1) sum sqerr / (Cc sum Tq),
         the perplexity that of the counts added per code -- what vq_forward reports on the packed latents.  All of it is the same
-        for every grouping, and per item for every order.  ValueError as encode_list."""
+        for every grouping, and per item for every order.  ValueError as encode_list.
+        Sliced / EMA quantisers (Geometry.vq): idx is (n, Tq_i), a row per slice; vq_loss = c_loss sum_s sqerr_s / (Tq_i Cc) with the
+        kind's c_loss (packing.vq_coeffs), perp = sum_s perp_s, sqerr = sum_s sqerr_s, hist (n, max K_s) int32, zero beyond K_s; the
+        totals follow the same rule (packing.vq_list_totals per slice, added over the slices)."""
         return self._encode_list(feats, want_latents, want_idx, max_frames, float(beta))
 
     def _encode_list(self, feats, want_latents, want_idx, max_frames, beta):
@@ -475,7 +561,9 @@ class WaeEngine:
         if self.weights_dirty:
             self.prepare_weights()
         out, stats = [], None
-        if want_stats:
+        if want_stats and g.vq != "plain":
+            stats = self._vq_list_stats_open(len(feats), float(beta))
+        elif want_stats:
             n, dev = len(feats), self.device
             stats = dict(c_loss=float(beta) + 1.0, keep=[], sqerr=torch.zeros(n, dtype=torch.float32, device=dev),
                          hist=torch.zeros(n, g.K, dtype=torch.int32, device=dev), item=torch.zeros(n, 2, dtype=torch.float32, device=dev),
@@ -483,6 +571,8 @@ class WaeEngine:
         for lo, hi in P.encode_list_groups([f.shape[1] for f in feats], cap):
             out += self._encode_group(feats[lo:hi], want_latents, want_idx, stats, lo)
         if want_stats:
+            if g.vq != "plain":
+                self._vq_list_stats_close(stats)
             self.last_list_stats = stats["out"]
             self.hold("encode_list_stats", *stats["keep"])       # the tables passed by raw pointer, until the next list
             # the items' views by four unbind calls for the whole list: indexing per item cost more than the kernels (about 10 us an item)
@@ -526,13 +616,48 @@ class WaeEngine:
         quant, idx, _ = self.vq_forward(lat.view(1, g.Cc, plan.total_Tq))
         quant = quant[0]
         sl = [slice(int(o), int(o + t)) for o, t in zip(plan.q_offsets, plan.Tq)]
-        res = [dict(quant=quant[:, s], idx=idx[s] if want_idx else None, latents=lat[:, s] if want_latents else None) for s in sl]
-        if stats is not None:
+        res = [dict(quant=quant[:, s], idx=idx[..., s] if want_idx else None, latents=lat[:, s] if want_latents else None) for s in sl]
+        if stats is not None and g.vq != "plain":
+            self._vq_list_stats_group(stats, lat, quant, idx, table[vq_off:], len(feats), plan.total_Tq, first)
+            stats["keep"].append(table)
+        elif stats is not None:
             L.check(lib.wae_vq_stats_segments(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(table[vq_off:]), len(feats), g.Cc, plan.total_Tq,
                                               g.K, stats["c_loss"], first, L.ptr(stats["sqerr"]), L.ptr(stats["hist"]), L.ptr(stats["item"]),
                                               L.ptr(stats["out"]), st), "vq_stats_segments")
             stats["keep"].append(table)
         return res
+
+    # the list statistics of the sliced / EMA kinds: wae_vq_stats_segments once per SLICE and group, on the slice's rows of the packed
+    # arrays (pointer offset d0 * pitch, D = D_s, the slice's idx row and K_s) with c_loss_s = c_loss * D_s / Dtot, so an item's
+    # vq_loss_s is c_loss sqerr_s / (Tq_i Dtot).  Per item and for the list: vq_loss, perp and sqerr are the slices' numbers added in
+    # slice order, hist (n, max K_s) the slices' counts side by side, zero beyond K_s.
+    def _vq_list_stats_open(self, n_items: int, beta: float) -> dict:
+        dev = self.device
+        _, specs, _ = self.vq_slice_records(beta)
+        z = lambda *shape, dt=torch.float32: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
+        return dict(keep=[], specs=specs, slices=[dict(sqerr=z(n_items), hist=z(n_items, K, dt=torch.int32), item=z(n_items, 2), out=z(4))
+                                                  for _, _, _, K, _ in specs])
+
+    def _vq_list_stats_group(self, stats, lat, quant, idx, segs, nsegs, pitch, first):
+        for s, ((_, d0, Ds, K, cl), a) in enumerate(zip(stats["specs"], stats["slices"])):
+            L.check(self.lib.wae_vq_stats_segments(L.ptr(lat[d0:]), L.ptr(quant[d0:]), L.ptr(idx[s] if idx.dim() == 2 else idx), L.ptr(segs),
+                                                   nsegs, Ds, pitch, K, cl, first, L.ptr(a["sqerr"]), L.ptr(a["hist"]), L.ptr(a["item"]),
+                                                   L.ptr(a["out"]), self.stream()), "vq_stats_segments")
+
+    def _vq_list_stats_close(self, stats):
+        sl = stats["slices"]
+        add = lambda key: functools.reduce(lambda x, y: x + y, [a[key] for a in sl])      # noqa: E731  (in slice order)
+        stats["sqerr"], stats["item"] = add("sqerr"), add("item")
+        out = add("out")
+        out[2] = sl[0]["out"][2]       # sum Tq: every slice counted the same frames
+        stats["out"] = out
+        if self.g.vq_n == 1:
+            stats["hist"] = sl[0]["hist"]
+        else:
+            hist = torch.zeros(sl[0]["hist"].shape[0], len(sl), max(a["hist"].shape[1] for a in sl), dtype=torch.int32, device=self.device)
+            for s, a in enumerate(sl):
+                hist[:, s, :a["hist"].shape[1]] = a["hist"]
+            stats["hist"] = hist
 
     def encode_session(self, want_latents: bool = False, window: Optional[int] = None) -> EncodeSession:
         """An encode session: encode_list for utterances whose feature frames still arrive (include/wae.h: wae_enc_conv_fwd_ranges).
@@ -1403,15 +1528,21 @@ class WaeEngine:
 
     # ------------------------------------------------------------------ full autoencoder
     def forward(self, x: torch.Tensor, c: torch.Tensor, gid: Optional[torch.Tensor], targets=None, lengths=None,
-                want_logits=True, train=False, beta: float = 0.25, dropout_on: bool = True, layer_events: Optional[list] = None):
-        """VQVAE.forward (vqvae_model.py:66-72) -> dict(logits, vq_loss, perp, latents, idx, quant, loss)."""
+                want_logits=True, train=False, beta: float = 0.25, dropout_on: bool = True, layer_events: Optional[list] = None,
+                vq_update: Optional[bool] = None):
+        """VQVAE.forward (vqvae_model.py:66-72) -> dict(logits, vq_loss, perp, latents, idx, quant, loss).
+        vq_update (EMA quantisers): whether this forward moves the codebooks -- the reference's `self.training`, which is not its
+        grad mode; default: train."""
         if train and self.flight.accum is None:
             self._refuse_in_window("a train-mode forward outside accumulate()")
         if self.weights_dirty:
             self.prepare_weights()
         sv = Saved(*x.shape) if train else None
         lat = self.encoder_forward(c, sv)
-        quant, idx, stats = self.vq_forward(lat, beta)
+        if self.g.vq == "plain":
+            quant, idx, stats = self.vq_forward(lat, beta)
+        else:
+            quant, idx, stats = self.vq_forward(lat, beta, update=train if vq_update is None else bool(vq_update))
         if train:
             sv.lat, sv.quant, sv.idx, sv.beta = lat, quant, idx, beta
         out = self.decoder_forward(x, quant, gid, targets, lengths, want_logits, train, dropout_on=dropout_on, layer_events=layer_events,
@@ -1524,6 +1655,11 @@ class WaeEngine:
         or mixture of Gaussians with geometry output_distribution "Normal"."""
         self._refuse_in_window("train_step")
         self._refuse_grad_sync(grad_sync)
+        if weight_decay != 0 and self.g.has_encoder and self.g.vq_ema:
+            # the reference's EMA codebooks have no gradient and the optimizer skips them (grad is None); here they get a zero
+            # gradient, which the fused Adam leaves alone only without weight decay
+            raise NotImplementedError(f"weight_decay = {weight_decay} with the {self.g.vq!r} quantiser: the fused optimizer would "
+                                      "decay the EMA codebooks")
         if self.exp_avg is None:
             self.init_optimizer()
         self.prepare_weights(side=True)
@@ -1623,6 +1759,7 @@ class WaeEngine:
         ones skip both; every one runs the sweep, the weight-gradient launches, the consuming zb chain and the front end's backward;
         nothing is scattered, finished or applied before apply_step."""
         from . import backward as BW
+        self._refuse_accum_vq()
         if self.flight.accum is not None:
             raise RuntimeError("accumulate() inside accumulate()")
         g = self.g
@@ -1742,6 +1879,7 @@ class WaeEngine:
         if not batches:
             raise ValueError("train_step_accum: no micro-batches")
         self._refuse_in_window("train_step_accum")
+        self._refuse_accum_vq()
         self._refuse_grad_sync(grad_sync)
         metas = []
         for x, c, gid, lengths in batches:

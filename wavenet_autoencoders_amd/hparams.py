@@ -31,6 +31,13 @@ _DEFAULTS = dict(
     dim_in=39, encoder_hid=384, language="english", K=256, ema=False,
 )
 
+# Keys this project adds to the reference's registry.  They read as their defaults, `parse` / `parse_json` / assignment set them like
+# any other key, and `values()` -- the registry as the reference would print and save it -- lists one only once it was set, so the
+# hparams.json of a run that uses none of them still loads against the reference's strict parser.
+#   quantizer: the quantiser between encoder and decoder (packing.Geometry.vq): "plain", "sliced", "ema" or "sliced_ema";
+#   num_slices: slices of the sliced kinds; vq_decay: the EMA kinds' decay.  (The reference's own key `ema` stays unused, as there.)
+_EXTENSIONS = dict(quantizer="plain", num_slices=2, vq_decay=0.99)
+
 
 class HParams(object):
     def __init__(self, **kwargs):
@@ -49,16 +56,25 @@ class HParams(object):
         try:
             return object.__getattribute__(self, "_values")[name]
         except KeyError:
+            if name in _EXTENSIONS:
+                return _EXTENSIONS[name]
             raise AttributeError(name)
 
     def __setattr__(self, name, value):
         self.set_hparam(name, value)
 
     def __contains__(self, name):
+        return name in self._values or name in _EXTENSIONS
+
+    def _known(self, name):
+        """an extension key joins the registry, with its default, when it is first set"""
+        if name not in self._values and name in _EXTENSIONS:
+            self.add_hparam(name, _EXTENSIONS[name])
         return name in self._values
 
     def set_hparam(self, name, value):
         """typed override; unknown name -> KeyError like the reference (hparam.py:500)."""
+        self._known(name)
         tp = self._types[name]
         if tp is None or value is None or isinstance(value, (dict, list)):
             self._values[name] = value
@@ -76,7 +92,7 @@ class HParams(object):
     def parse_json(self, text, strict=False):
         text = re.sub(r",(\s*[}\]])", r"\1", text)            # tolerate trailing commas (hps/wv_vqvae_hp.json:74-75)
         for k, v in json.loads(text).items():
-            if k not in self._values:
+            if k not in self._values and (strict or k not in _EXTENSIONS):
                 if strict:
                     raise KeyError(k)
                 self.add_hparam(k, v)
@@ -91,7 +107,7 @@ class HParams(object):
                 raise ValueError("Could not parse hparam %r" % item)
             k, v = item.split("=", 1)
             k = k.strip()
-            if k not in self._values:
+            if not self._known(k):
                 raise KeyError(k)
             tp = self._types[k]
             v = v.strip()

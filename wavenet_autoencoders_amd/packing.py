@@ -37,6 +37,9 @@ def _ru(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
+VQ_KINDS = ("plain", "sliced", "ema", "sliced_ema")
+
+
 @dataclass
 class Geometry:
     """Decoder/encoder sizes (reference ctor args: wavenet.py:98-111, vqvae_model.py:54) + padded sizes."""
@@ -77,8 +80,28 @@ class Geometry:
     # (discretized mixture of logistics) or "Normal" (mixture of Gaussians, mixture.py:161-270).  Ignored for class-id decoders
     # (mulaw-quantize), as in the reference.
     output_distribution: str = "Logistic"
+    # the quantiser between encoder and decoder (vector_quantization.py): "plain" VectorQuantize (:10-49), "sliced"
+    # SlicedVectorQuantize (:51-128: vq_slices equal slices of the channel axis, a codebook each; K1: the second codebook's size, as
+    # the constructor's K1, default K), "ema" VectorQuantizeEMA (:239-306) and "sliced_ema" SlicedVectorQuantizeEMA (:132-235), whose
+    # codebooks move by exponential moving averages (vq_decay) instead of gradients
+    vq: str = "plain"
+    vq_slices: int = 2
+    K1: Optional[int] = None
+    vq_decay: float = 0.99
 
     def __post_init__(self):
+        if self.vq not in VQ_KINDS:
+            raise ValueError(f"quantiser kind {self.vq!r}: one of {VQ_KINDS}")
+        if self.vq in ("sliced", "sliced_ema"):
+            if not 2 <= int(self.vq_slices) <= 8:
+                raise ValueError(f"vq_slices = {self.vq_slices}: a sliced quantiser has 2..8 slices")
+            if self.Cc % int(self.vq_slices) != 0:
+                raise ValueError(f"vq_slices = {self.vq_slices} does not divide the latent width Cc = {self.Cc}")
+        if self.K1 is not None:
+            if self.vq != "sliced":
+                raise ValueError(f"K1 belongs to the 'sliced' quantiser (SlicedVectorQuantize(K1=)), not to {self.vq!r}")
+            if self.vq_slices != 2:
+                raise ValueError(f"K1 is the second of two codebooks: vq_slices = {self.vq_slices}")
         assert self.layers % self.stacks == 0                       # wavenet.py:117
         assert self.G % 2 == 0
         self.H = self.G // 2
@@ -101,6 +124,8 @@ class Geometry:
             self.dilations = [int(d) for d in self.dilations_override]
         self.receptive_field = (self.k - 1) * sum(self.dilations) + 1   # wavenet.py:42-60
         self.has_encoder = self.c_in is not None
+        self.vq_ema = self.vq in ("ema", "sliced_ema")                  # codebooks moved by EMA statistics, no gradient
+        self.vq_n = int(self.vq_slices) if self.vq in ("sliced", "sliced_ema") else 1
         if self.scalar_input:
             if self.output_distribution not in ("Logistic", "Normal"):
                 # vqwae_train.py:810-812
@@ -121,7 +146,8 @@ class Geometry:
                         scalar_input=bool(cfg.get("scalar_input")), c_in=cfg.get("c_in"),
                         encoder_hid=cfg.get("encoder_hid"), K=cfg.get("K", 256), conv_in=bool(cfg.get("conv_in", True)),
                         up_act=cfg.get("up_act", "none"), up_act_slope=float(cfg.get("up_act_slope", 0.01)),
-                        output_distribution=cfg.get("output_distribution", "Logistic"))
+                        output_distribution=cfg.get("output_distribution", "Logistic"), vq=cfg.get("vq", "plain"),
+                        vq_slices=int(cfg.get("vq_slices", 2)), K1=cfg.get("K1"), vq_decay=float(cfg.get("vq_decay", 0.99)))
 
 
 ENCODER_BLOCKS = [(3, 1), (3, 1), (5, 2), (5, 2), (3, 1), (3, 1), (1, 1), (1, 1), (1, 1), (1, 1)]  # vqvae_model.py:32-40
@@ -1006,7 +1032,40 @@ def param_specs(g: Geometry) -> List[Tuple[str, Tuple[int, ...], bool]]:
             out.append((f"encoder.net.{i}.conv.bias", (co,), False))
         out.append(("encoder.lin.weight", (g.Cc, g.encoder_hid), False))
         out.append(("encoder.lin.bias", (g.Cc,), False))
-        out.append(("vq.embedding.weight", (g.K, g.Cc), False))
+        out += [(name + ".weight", (K, D), False) for name, _, D, K in vq_slice_specs(g)]
+    return out
+
+
+def vq_slice_specs(g: Geometry) -> List[Tuple[str, int, int, int]]:
+    """(codebook module name, d0, D, K) per slice of the geometry's quantiser: the whole width under `vq.embedding` for "plain" and
+    "ema"; vq_slices equal slices under `vq.embedding{1..n}` (the reference's names for n = 2, vector_quantization.py:62-65, :143-146)
+    for the sliced kinds, the second of two with K1 codes where given."""
+    if g.vq_n == 1:
+        return [("vq.embedding", 0, g.Cc, g.K)]
+    D = g.Cc // g.vq_n
+    return [(f"vq.embedding{s + 1}", s * D, D, g.K1 if (s == 1 and g.K1 is not None) else g.K) for s in range(g.vq_n)]
+
+
+def vq_coeffs(g: Geometry, beta: float) -> Tuple[float, float, Optional[float]]:
+    """(c_loss, c_lat, c_emb) of the geometry's quantiser: vq_loss = c_loss * mse forward; d vq_loss / d latents carries c_lat and
+    d / d codebook c_emb (None: no codebook gradient).  plain: (:41-43) the two terms' forward values are equal; sliced: weight 1 on
+    the encoder-side term, beta on the codebook's (:113-118); EMA kinds: beta * mse(sg[q], x) alone (:220, :294)."""
+    if g.vq_ema:
+        return float(beta), float(beta), None
+    if g.vq == "sliced":
+        return 1.0 + float(beta), 1.0, float(beta)
+    return float(beta) + 1.0, float(beta), 1.0
+
+
+def vq_buffer_specs(g: Geometry) -> List[Tuple[str, Tuple[int, ...]]]:
+    """(name, shape) of the EMA kinds' statistics in the reference's registration order (vector_quantization.py:148-153, :251-253):
+    vq.ema_cluster_size[s] (K,) and vq.ema_w[s] (K, D_s), the suffix absent for "ema", 1..n for "sliced_ema"."""
+    if not (g.vq_ema and g.has_encoder):
+        return []
+    out = []
+    for name, _, D, K in vq_slice_specs(g):
+        sfx = name[len("vq.embedding"):]
+        out += [("vq.ema_cluster_size" + sfx, (K,)), ("vq.ema_w" + sfx, (K, D))]
     return out
 
 

@@ -46,7 +46,7 @@ def register_params(root: nn.Module, geom: P.Geometry, strip: str = "", skip=Non
                 nn.init.kaiming_normal_(t, nonlinearity="relu")
         elif rel.endswith("embed_speakers.weight"):
             t.normal_(0, 0.1)
-        elif rel.endswith("embedding.weight"):
+        elif rel.endswith("embedding.weight") or name.startswith("vq.embedding"):      # vq.embedding{1..n}: the sliced kinds' codebooks
             t.uniform_(-1.0 / shape[0], 1.0 / shape[0])
         elif rel.endswith(".weight"):
             fan_in = int(torch.tensor(shape[1:]).prod())
@@ -124,9 +124,14 @@ class ArenaModel(nn.Module):
                 view = eng.params[off:off + n].view(eng.lay.shapes[full])
                 view.copy_(params[rel].data)
                 params[rel].data = view                      # the Parameter now aliases the arena
+            # buffers the engine owns (the EMA quantisers' statistics): the module's take the engine's storage, as the parameters do
+            for name, buf in eng.vq_buffers.items():
+                m, leaf = _leaf(self, name[len(self._strip):])
+                buf.copy_(m._buffers[leaf])
+                m._buffers[leaf] = buf
             eng.weights_dirty = True
             self._engine = eng
-        self._engine.weights_dirty = True                    # optimizers write through the aliases
+        self._engine.weights_dirty = True                   # optimizers write through the aliases
         return self._engine
 
     def _apply(self, fn, recurse=True):
