@@ -1217,6 +1217,50 @@ int wae_enc_conv_bwd(const float* x, const float* w, const float* y, const float
 int wae_vq_bwd(const float* lat, const float* quant, const int64_t* idx, const float* dquant, float* dlat, float* demb,
                int32_t B, int32_t D, int32_t Tq, float beta, float loss_scale, void* stream);
 
+/* ---- backward of the front end over a LIST of utterances of unequal lengths (csrc/frontend_bwd_list.hip): the second half of a
+ * ragged train step (WaeEngine.train_step_list).  The decoder needs no list form: in a right-padded batch a valid row reads nothing
+ * to its right, and under a masked loss a pad row sends no gradient to its left.  What zero-padding changes is the front end, so its
+ * forward runs on the packed list (wae_enc_conv_fwd_list, wae_upsample_stage_fwd_list) and these three entries are its backward.
+ * Each takes the packed layout and the tables of its forward twin (packing.encode_list_plan / upsample_list_plan records serve
+ * both ways), enqueues on `stream`, never allocates or synchronises, and returns WAE_EINVAL / WAE_EUNSUPPORTED before any launch.
+ * No entry trusts a table with memory: a record that does not fit its pitches or contradicts the length formula is skipped whole,
+ * nothing read or written for it.  Every item is zero-padded at its own two ends: a tap outside the item contributes nothing and
+ * never reads the neighbour's column.  Per item the gradients are those of the dense entries above for that item as a batch of one;
+ * weight gradients are the sums over the items, ADDED into what dw / dbias hold.  Not reproducible to the bit from run to run where
+ * float atomics add (the stage's dw); there is no deterministic form.
+ * The QUANTISER needs no list entry in either direction: wae_vq_nearest / wae_vq_search_slices, wae_vq_ema_update and wae_vq_bwd /
+ * wae_vq_slice_bwd run on the packed latents (Cc, sum Tq_i) with B = 1, Tq = pitch; their mean over Cc * sum Tq_i is the
+ * list-as-one-batch convention of wae_vq_stats_segments' `out`.  The latent buffer must then have NO GAP COLUMNS: pitch == sum Tq_i
+ * (a gap column would be searched, counted and averaged like a frame).
+ *
+ * wae_from_btc_list, the inverse of wae_to_btc_list: rows [out_off_i, out_off_i + Tin_i) of the time-major `in` (rows, Cp) in
+ *   `dtype` -> columns [in_off_i, in_off_i + Tin_i) of the channel-major `out` (C, pitch) fp32, every element times `scale` (the
+ *   conditioning gradient dc -> the packed gradient, with 1 / grad_scale).  Records wae_ups_seg + the closing one, tiles of 64 rows
+ *   (wae_to_btc_list's table); a record with out_off_i + Tin_i > rows or in_off_i + Tin_i > pitch is skipped.  Columns that no item
+ *   owns are not written.  WAE_EINVAL: a null pointer, C, nsegs, ntiles, pitch or rows < 1, Cp < C, a bad dtype.
+ * wae_upsample_stage_bwd_list, wae_upsample_stage_bwd for every item in one launch: dout (C, out_pitch), item i at the columns
+ *   [out_off_i, out_off_i + Tin_i s); in (C, in_pitch) the stage's packed input; din (C, in_pitch) receives the item's columns;
+ *   dw[2s+1] += the sum over all items (float atomics).  Records wae_ups_seg + the closing one with tiles of WAE_UPS_LIST_TILE_CT
+ *   output columns: the channel-major table of wae_upsample_stage_fwd_list.  WAE_EINVAL: a null pointer, C, s, nsegs, ntiles or a
+ *   pitch < 1, s > 16 (as the dense entry).
+ * wae_enc_conv_bwd_list, wae_enc_conv_bwd over wae_seg records and the (segment, to0) tile table of wae_enc_conv_fwd_list: x
+ *   (Cin, in_pitch), y (or NULL without relu) and dy (Cout, out_pitch); dx (Cin, in_pitch) or NULL (the first block); dw += and
+ *   dbias += (or NULL).  dpre = dy * [relu ? (y - (residual ? x : 0)) > 0 : 1], as the dense kernel forms it; a tap outside
+ *   [0, Tin_i) reads 0.  The tile (i, to0) also stands for the item's input steps [to0 stride, (to0 + et) stride) -- the item's last
+ *   tile for everything up to Tin_i -- so the table must hold the tiles enc_list_tables builds: multiples of et below Tout_i, each
+ *   once.  Every (32 output x 32 input channel) block of dw has ONE owner, which walks the tiles in table order and adds its sum with
+ *   a plain read-modify-write: for a given table the result is reproducible, and in exact arithmetic it does not depend on the
+ *   table's order.  Serves the ten encoder blocks, lin and conv_in.  WAE_EINVAL as wae_enc_conv_fwd_list, and for relu without y;
+ *   WAE_EUNSUPPORTED for a (k, stride) other than (1,1), (3,1), (5,2), (5,1). */
+int wae_from_btc_list(const void* in, float* out, const wae_ups_seg* segs, int32_t nsegs, int32_t ntiles, int32_t pitch, int32_t rows,
+                      int32_t C, int32_t Cp, int32_t dtype, float scale, void* stream);
+int wae_upsample_stage_bwd_list(const float* dout, const float* in, const float* w, float* din, float* dw, const wae_ups_seg* segs,
+                                int32_t nsegs, int32_t ntiles, int32_t in_pitch, int32_t out_pitch, int32_t C, int32_t s, void* stream);
+int wae_enc_conv_bwd_list(const float* x, const float* w, const float* y, const float* dy, float* dx, float* dw, float* dbias,
+                          const wae_seg* segs, int32_t nsegs, const int32_t* tiles, int32_t ntiles, int32_t et, int32_t in_pitch,
+                          int32_t out_pitch, int32_t Cin, int32_t Cout, int32_t k, int32_t stride, int32_t pad, int32_t relu,
+                          int32_t residual, void* stream);
+
 /* layout helpers: (B,C,T) fp32 <-> (B,T,Cp) dtype */
 int wae_to_btc(const float* in, void* out, int32_t B, int32_t C, int32_t T, int32_t Cp, int32_t dtype, void* stream);
 /* the same with the shifted loss mask and weight of vqwae_train.py:374-379,764-766 applied on the way: row t is multiplied by

@@ -19,6 +19,7 @@ options:
     --synthetic                  Train on synthetic batches (no dataset needed).
     --max-steps=<N>              Stop after N steps (overrides max_train_steps).
     --accum-steps=<M>            Loader batches per optimizer step (gradient accumulation) [default: 1].
+    --train-packed               max_time_steps null: train on every batch's utterances unpadded (WaeEngine.train_step_list).
 
 One process per GPU: launch with ``python -m torch.distributed.run --nproc-per-node N vqwae_train.py ...`` for data
 parallel training (gradients are all-reduced over RCCL; every rank reads its own shard).
@@ -168,6 +169,19 @@ def eval_model(eng, x, c, g, lengths, global_step, eval_dir, hp, use_ema, hop):
     return y_hat, y_target
 
 
+def packed_items(x, c, g, lengths, hop, stride=4):
+    """A loader batch (whole utterances zero-padded to the longest) -> the items of WaeEngine.train_step_list: every utterance at its
+    own length, trimmed to a multiple of `stride` feature frames (the encoder's: its latents then upsample to exactly the samples);
+    an utterance shorter than that is left out."""
+    items, ln, gs = [], lengths.tolist(), (g.tolist() if g is not None else None)       # (one read-back each, not one per utterance)
+    for b in range(x.shape[0]):
+        F = min(int(ln[b]) // hop, c.shape[-1])
+        F -= F % stride
+        if F >= stride:
+            items.append(dict(x=x[b, :F * hop], c=c[b, :, :F], gid=gs[b] if gs is not None else None))
+    return items
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--dump-root")
@@ -192,6 +206,13 @@ def parse_args(argv=None):
                     help="M loader batches per optimizer step (WaeEngine.train_step_accum): each is a micro-batch padded to its own "
                          "longest clip (max_time_steps null), weighted so that the step is the one on all M as one batch; the learning-"
                          "rate schedule, the checkpoint / eval intervals and global_step count optimizer steps.  1: one batch per step")
+    ap.add_argument("--train-packed", action="store_true",
+                    help="presets with max_time_steps null: the train phase hands each loader batch's utterances, unpadded, to "
+                         "WaeEngine.train_step_list (the list front end in front of the dense decoder) instead of train_step on the "
+                         "zero-padded batch, whose pad frames enter the commitment loss and the conditioning of every utterance's end; "
+                         "it logs what the padded phase logs.  Every utterance is trimmed to a multiple of 4 feature frames (the "
+                         "encoder's stride) where the dump's are not; one shorter than 4 frames is left out.  One GPU, --accum-steps 1, "
+                         "not with --deterministic.  Length-sorted batches keep the decoder's pad rows low")
     ap.add_argument("--deterministic", action="store_true",
                     help="the reproducible train step (WAE_DETERMINISTIC=1, wavenet_autoencoders_amd/options.py): the same weights, batch "
                          "and dropout seed give the same bits, step after step and run after run, on one GPU (not with data parallel)")
@@ -231,6 +252,13 @@ def main(argv=None):
     if args.accum_steps > 1 and geom.vq != "plain":
         raise NotImplementedError(f"--accum-steps {args.accum_steps} with hparams quantizer={geom.vq!r}: accumulation windows cover the "
                                   "plain quantiser (WaeEngine.accumulate)")
+    if args.train_packed:
+        if hp.max_time_steps is not None:
+            raise ValueError(f"--train-packed with max_time_steps = {hp.max_time_steps}: cropped batches have one length; the packed "
+                             "train phase is for presets with max_time_steps null")
+        if world > 1 or args.accum_steps > 1 or args.deterministic:
+            raise NotImplementedError("--train-packed runs on one GPU, with --accum-steps 1 and without --deterministic "
+                                      "(WaeEngine.train_step_list)")
     if engine_switches(args).deterministic and world > 1:
         raise NotImplementedError("--deterministic with data parallel: the all-reduce's order of additions is the collective library's")
     eng = WaeEngine(geom, dtype=args.dtype, device=device, dropout=float(hp.dropout),            # vqwae_train.py:933
@@ -295,7 +323,12 @@ def main(argv=None):
                 T = x.shape[1]
                 ln = None if bool((lengths == T).all()) else lengths
                 batches_seen += 1
-                if accum > 1:
+                if args.train_packed:
+                    res = eng.train_step_list(packed_items(x, c, g, lengths, hop), lr=lr, betas=adam["betas"], eps=adam["eps"],
+                                              weight_decay=adam["weight_decay"], clip_thresh=hp.clip_thresh, ema_decay=hp.ema_decay,
+                                              quantize_channels=hp.quantize_channels, log_scale_min=hp.log_scale_min)
+                    ce_scale = 1.0
+                elif accum > 1:
                     # M loader batches are the micro-batches of one optimizer step; its numbers are the window's (apply_step), already
                     # weighted -- the global masked mean over every rank's window, one mask-sum all-reduce per window
                     pending.append((x, c, g, ln))

@@ -166,6 +166,13 @@ SIGNATURES = {
     "wae_stream_delay": (c_i32, [ctypes.c_double, c_vp]),
     "wae_upsample_stage_bwd": (c_i32, [c_vp] * 5 + [c_i32] * 4 + [c_vp]),
     "wae_enc_conv_bwd": (c_i32, [c_vp] * 7 + [c_i32] * 9 + [c_vp]),
+    # the list forms of the front end's backward (csrc/frontend_bwd_list.hip)
+    # in, out, segs, nsegs, ntiles, pitch, rows, C, Cp, dtype, scale, stream
+    "wae_from_btc_list": (c_i32, [c_vp] * 3 + [c_i32] * 7 + [c_f32, c_vp]),
+    # dout, in, w, din, dw, segs, nsegs, ntiles, in_pitch, out_pitch, C, s, stream
+    "wae_upsample_stage_bwd_list": (c_i32, [c_vp] * 6 + [c_i32] * 6 + [c_vp]),
+    # x, w, y, dy, dx, dw, dbias, segs, nsegs, tiles, ntiles, et, in_pitch, out_pitch, Cin, Cout, k, stride, pad, relu, residual, stream
+    "wae_enc_conv_bwd_list": (c_i32, [c_vp] * 8 + [c_i32, c_vp] + [c_i32] * 11 + [c_vp]),
     "wae_vq_bwd": (c_i32, [c_vp] * 6 + [c_i32] * 3 + [c_f32, c_f32, c_vp]),
     "wae_vq_slice": (c_i32, [c_vp] * 6 + [c_i32] * 6 + [c_f32, c_i32, c_vp]),
     "wae_vq_ema_update": (c_i32, [c_vp] * 6 + [c_i32] * 6 + [c_f32, c_vp]),

@@ -1369,6 +1369,34 @@ def finish_grads(eng):
     return eng.grads
 
 
+def _vq_backward(eng, sv, dq, B, Tq, loss_scale):
+    """The quantiser's backward on the saved (B, Cc, Tq) record: dlat = dq + the commitment term (straight-through), the codebooks'
+    gradients added into eng.d_eff.  A packed list (frontend_backward_list) is B = 1, Tq = sum Tq_i.  -> dlat"""
+    g, lib, lay, st = eng.g, eng.lib, eng.lay, eng.stream()
+    lat, quant, idx = sv.lat, sv.quant, sv.idx
+    dlat = torch.empty_like(lat)
+    en = "vq.embedding.weight"
+    if g.vq != "plain":
+        # the sliced / EMA kinds: every slice's rows of dlat, and its codebook's gradient where it has one (EMA codebooks: none --
+        # their arena slice keeps the zero gradient under which the optimizer leaves them alone)
+        _, c_lat, c_emb = P.vq_coeffs(g, sv.beta)
+        scale = float(loss_scale) * 2.0 / (B * g.Cc * Tq)
+        for s, (name, d0, Ds, K) in enumerate(P.vq_slice_specs(g)):
+            demb = eng.d_eff[lay.off(name + ".weight"):] if c_emb is not None else None
+            head = (L.ptr(lat), L.ptr(quant), L.ptr(idx[s] if g.vq_n > 1 else idx), L.ptr(dq), L.ptr(dlat), L.ptr(demb), B, g.Cc, d0, Ds, Tq)
+            if eng.opt.deterministic:
+                L.check(lib.wae_vq_slice_bwd_det(*head, K, scale * c_lat, scale * (c_emb or 0.0), st), "vq_slice_bwd_det")
+            else:
+                L.check(lib.wae_vq_slice_bwd(*head, scale * c_lat, scale * (c_emb or 0.0), st), "vq_slice_bwd")
+    elif eng.opt.deterministic:      # the codebook gradient by one workgroup per code
+        L.check(lib.wae_vq_bwd_det(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(eng.d_eff[lay.off(en):]), B,
+                                   g.Cc, Tq, g.K, sv.beta, loss_scale, st), "vq_bwd_det")
+    else:
+        L.check(lib.wae_vq_bwd(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(eng.d_eff[lay.off(en):]), B, g.Cc,
+                               Tq, sv.beta, loss_scale, st), "vq_bwd")
+    return dlat
+
+
 def frontend_backward(eng, dc: torch.Tensor, loss_scale: float = 1.0, stop_at_quant: bool = False):
     """dc (B,T,Ccp) -> upsample stages -> conv_in -> [VQ straight-through + vq_loss -> encoder]; adds the weight
     gradients into eng.d_eff.  Uses the activations kept by the last train-mode forward (eng.saved)."""
@@ -1418,28 +1446,9 @@ def frontend_backward(eng, dc: torch.Tensor, loss_scale: float = 1.0, stop_at_qu
     if stop_at_quant:
         return dq
     if sv.lat is not None and g.has_encoder:
-        lat, quant, idx = sv.lat, sv.quant, sv.idx
+        lat = sv.lat
         Tq = lat.shape[-1]
-        dlat = torch.empty_like(lat)
-        en = "vq.embedding.weight"
-        if g.vq != "plain":
-            # the sliced / EMA kinds: every slice's rows of dlat, and its codebook's gradient where it has one (EMA codebooks: none --
-            # their arena slice keeps the zero gradient under which the optimizer leaves them alone)
-            _, c_lat, c_emb = P.vq_coeffs(g, sv.beta)
-            scale = float(loss_scale) * 2.0 / (B * g.Cc * Tq)
-            for s, (name, d0, Ds, K) in enumerate(P.vq_slice_specs(g)):
-                demb = eng.d_eff[lay.off(name + ".weight"):] if c_emb is not None else None
-                head = (L.ptr(lat), L.ptr(quant), L.ptr(idx[s] if g.vq_n > 1 else idx), L.ptr(dq), L.ptr(dlat), L.ptr(demb), B, g.Cc, d0, Ds, Tq)
-                if eng.opt.deterministic:
-                    L.check(lib.wae_vq_slice_bwd_det(*head, K, scale * c_lat, scale * (c_emb or 0.0), st), "vq_slice_bwd_det")
-                else:
-                    L.check(lib.wae_vq_slice_bwd(*head, scale * c_lat, scale * (c_emb or 0.0), st), "vq_slice_bwd")
-        elif eng.opt.deterministic:      # the codebook gradient by one workgroup per code
-            L.check(lib.wae_vq_bwd_det(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(eng.d_eff[lay.off(en):]), B,
-                                       g.Cc, Tq, g.K, sv.beta, loss_scale, st), "vq_bwd_det")
-        else:
-            L.check(lib.wae_vq_bwd(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(dq), L.ptr(dlat), L.ptr(eng.d_eff[lay.off(en):]), B, g.Cc,
-                                   Tq, sv.beta, loss_scale, st), "vq_bwd")
+        dlat = _vq_backward(eng, sv, dq, B, Tq, loss_scale)
         ea = sv.enc_acts                     # ea[i] = input of block i, ea[10] = output of block 9
         dx = torch.empty_like(ea[10])
         L.check(lib.wae_enc_conv_bwd(L.ptr(ea[10]), L.ptr(eng.eff[lay.off("encoder.lin.weight"):]), None, L.ptr(dlat), L.ptr(dx),
@@ -1458,4 +1467,67 @@ def frontend_backward(eng, dc: torch.Tensor, loss_scale: float = 1.0, stop_at_qu
                                          k, s, k // 2, 1, int(s == 1 and ci == co), st), "enc block bwd")
             keep.append(dxi)
             dcur = dxi
+    return dq
+
+
+def frontend_backward_list(eng, dc: torch.Tensor, loss_scale: float = 1.0):
+    """frontend_backward for the LIST front end of a ragged step (WaeEngine.train_step_list; include/wae.h: "backward of the front end
+    over a LIST"): dc (B, Tmax, Ccp) of the dense decoder -> wae_from_btc_list (item b's rows [b Tmax, b Tmax + T_b) to the packed
+    (Cc, sum T_i) gradient, times 1 / grad_scale) -> the stages -> conv_in -> the quantiser on the packed latents as one clip -> lin
+    and the encoder blocks, one list launch each; adds the weight gradients into eng.d_eff as frontend_backward does.  Uses the
+    packed activations and tables the list forward left in eng.saved.list_fe."""
+    g, lib, lay, st, dev = eng.g, eng.lib, eng.lay, eng.stream(), eng.device
+    B, T = dc.shape[0], dc.shape[1]
+    sv = saved_for(eng, B, T)
+    fe = sv.list_fe
+    tp = fe["plan"]
+    t_enc, t_ups, t_bwd = fe["tables"]
+    total = int(tp.Ts.sum())
+    d = torch.empty(g.Cc, total, dtype=torch.float32, device=dev)
+    L.check(lib.wae_from_btc_list(L.ptr(dc), L.ptr(d), L.ptr(t_bwd[tp.fb_off:]), B, tp.fb_ntiles, total, B * T, g.Cc, g.Ccp, eng.dt,
+                                  1.0 / eng.grad_scale, st), "from_btc_list")
+    acts = fe["up_acts"]                     # [conv_in's packed input | None, stage-0 input, stage-1 input, ...]
+    keep = [d]
+    for i in range(len(g.upsample_scales) - 1, -1, -1):
+        s = int(g.upsample_scales[i])
+        name = P.up_stage_name(g, i) + ".weight_v"
+        in_pitch, out_pitch = tp.stage_pitch[i]
+        din = torch.empty(g.Cc, in_pitch, dtype=torch.float32, device=dev)
+        L.check(lib.wae_upsample_stage_bwd_list(L.ptr(d), L.ptr(acts[1 + i]), L.ptr(eng.eff[lay.off(name):]), L.ptr(din),
+                                                L.ptr(eng.d_eff[lay.off(name):]), L.ptr(t_bwd[tp.stage_off[i]:]), B, tp.stage_ntiles[i],
+                                                in_pitch, out_pitch, g.Cc, s, st), "upsample_stage_bwd_list")
+        d = din
+        keep.append(d)
+    if g.conv_in:
+        ln = tp.ups.launches[0]
+        name = "wavenet.upsample_net.conv_in.weight"
+        dq = torch.empty_like(acts[0])
+        L.check(lib.wae_enc_conv_bwd_list(L.ptr(acts[0]), L.ptr(eng.eff[lay.off(name):]), None, L.ptr(d), L.ptr(dq),
+                                          L.ptr(eng.d_eff[lay.off(name):]), None, L.ptr(t_ups[ln.seg_off:]), ln.nsegs,
+                                          L.ptr(t_ups[ln.tile_off:]), ln.ntiles, ln.et, ln.in_pitch, ln.out_pitch, g.Cc, g.Cc, ln.s, 1, 0, 0,
+                                          0, st), "conv_in bwd (list)")
+    else:
+        dq = d
+    keep.append(dq)
+    eng.hold("fe", keep)
+    if sv.lat is None or not g.has_encoder:
+        return dq
+    Tq = sv.lat.shape[-1]                    # the packed latents as ONE clip: (1, Cc, sum Tq_i), no gap columns
+    dlat = _vq_backward(eng, sv, dq, 1, Tq, loss_scale)
+    ea, layers = fe["enc_acts"], tp.enc.layers        # ea[i]: the packed input of layer i (ten blocks, then lin)
+    convs = [(f"encoder.net.{i}.conv", 1) for i in range(len(P.ENCODER_BLOCKS))] + [("encoder.lin", 0)]
+    dcur = dlat
+    keep.append(dlat)
+    for i in range(len(convs) - 1, -1, -1):
+        (name, relu), ly = convs[i], layers[i]
+        co, ci = lay.shapes[name + ".weight"][:2]
+        dxi = torch.empty_like(ea[i]) if i > 0 else None
+        res = int(bool(relu) and ly.stride == 1 and ci == co)
+        L.check(lib.wae_enc_conv_bwd_list(L.ptr(ea[i]), L.ptr(eng.eff[lay.off(name + ".weight"):]), L.ptr(ea[i + 1]) if relu else None,
+                                          L.ptr(dcur), L.ptr(dxi), L.ptr(eng.d_eff[lay.off(name + ".weight"):]),
+                                          L.ptr(eng.d_eff[lay.off(name + ".bias"):]), L.ptr(t_enc[ly.seg_off:]), ly.nsegs,
+                                          L.ptr(t_enc[ly.tile_off:]), ly.ntiles, ly.et, ly.in_pitch, ly.out_pitch, ci, co, ly.k, ly.stride,
+                                          ly.pad, relu, res, st), "enc_conv_bwd_list")
+        keep.append(dxi)
+        dcur = dxi
     return dq

@@ -840,7 +840,7 @@ class WaeEngine:
                         targets: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None,
                         want_logits: bool = True, train: bool = False, c_is_upsampled: bool = False,
                         gvec: Optional[torch.Tensor] = None, layer_events: Optional[list] = None, dropout_on: bool = True,
-                        saved: Optional[Saved] = None):
+                        saved: Optional[Saved] = None, c_ready: bool = False):
         """WaveNet.forward (wavenet.py:164-216) on class ids.
 
         x: (B,T) int32 class ids (mulaw-quantize) or (B,T) fp32 scalars (scalar_input).
@@ -848,6 +848,8 @@ class WaeEngine:
         gid: (B,) int32 speaker ids.  targets: (B,T) int32 -> fused shifted CE.
         train: the activations stay in the (B, T, True) workspace and this forward's record becomes self.saved once it is complete
         (saved: the record forward() began with the encoder's side; default: a new one).
+        c_ready: the (B, T, Ccp) conditioning operand of the (B, T, train) workspace already holds this call's rows (train_step_list:
+        the list front end wrote them, pad rows zero); c is not read.
         Returns dict(logits (B,O,T) | None, nll (B,T) | None, loss | None).
         """
         if train and self.flight.accum is None:
@@ -872,7 +874,7 @@ class WaeEngine:
                                   L.ptr(ws["zb"]), B, g.layers, g.G, g.Hp, max(g.Cg, 0), int(g.n_speakers or 0), L.ptr(self.err), self.stream()),
                 "gproj")
         # local conditioning
-        if g.Ccp:
+        if g.Ccp and not c_ready:
             if c is None:
                 raise ValueError("model has local conditioning but c is None")
             if c_is_upsampled or not g.upsample_scales:
@@ -1570,6 +1572,8 @@ class WaeEngine:
         if self.flight.accum is None:
             self._refuse_in_window("backward outside accumulate()")
         self.flight.ev_dc = None
+        # (a ragged step's forward left the list front end's record: its backward is the list form's)
+        fe_bwd = BW.frontend_backward_list if (self.saved is not None and self.saved.list_fe is not None) else BW.frontend_backward
         dc = BW.decoder_backward(self, x, targets, lengths, gid, gvec, ext_dy=ext_dy, loss_scale=loss_scale, grad_sync=grad_sync,
                                  dy_factor=dy_factor)
         if self.g.Ccp and self.g.upsample_scales:
@@ -1577,10 +1581,10 @@ class WaeEngine:
                 # dc was complete when the sweep ended (the event): the front end's backward runs on a side stream beside the scatter of
                 # the layers' weight gradients that decoder_backward queued behind the sweep (disjoint slices of the gradient arena)
                 with self.branch(0, after=self.flight.ev_dc) as tail:
-                    BW.frontend_backward(self, dc, loss_scale if vq_scale is None else vq_scale)
+                    fe_bwd(self, dc, loss_scale if vq_scale is None else vq_scale)
                 self.join(tail[0])
             else:
-                BW.frontend_backward(self, dc, loss_scale if vq_scale is None else vq_scale)
+                fe_bwd(self, dc, loss_scale if vq_scale is None else vq_scale)
         if self.flight.accum is not None:
             return None
         return BW.finish_grads(self)
@@ -1655,6 +1659,22 @@ class WaeEngine:
         or mixture of Gaussians with geometry output_distribution "Normal"."""
         self._refuse_in_window("train_step")
         self._refuse_grad_sync(grad_sync)
+        x, gid = self._step_open(x, gid, weight_decay)
+
+        def fwd(targets, lengths, want_logits):
+            kw = dict(targets=targets, lengths=lengths, want_logits=want_logits, train=True)
+            if not self.g.scalar_input:
+                kw["layer_events"] = self._layer_events
+            return (self.forward if self.g.has_encoder else self.decoder_forward)(x, c, gid, **kw)
+
+        out, grads = self._step_run(fwd, x, gid, lengths, quantize_channels, log_scale_min, ce_scale, grad_sync)
+        return self._step_close(out, grads, grad_sync, grad_hook, lr, betas, eps, weight_decay, clip_thresh, ema_decay)
+
+    # The three phases train_step and train_step_list share (the statements train_step ran, in its order): what differs between a
+    # dense and a ragged step is the forward handed to _step_run and, behind it, which front-end backward self.backward dispatches to.
+    def _step_open(self, x, gid, weight_decay):
+        """The optimizer's refusal and state, the weights (packing on a side stream), one int32 copy of the ids, the backward's early
+        packing.  -> (x, gid) as the forward and the backward take them."""
         if weight_decay != 0 and self.g.has_encoder and self.g.vq_ema:
             # the reference's EMA codebooks have no gradient and the optimizer skips them (grad is None); here they get a zero
             # gradient, which the fused Adam leaves alone only without weight decay
@@ -1682,24 +1702,28 @@ class WaeEngine:
             # queues, and streams that share one run one after the other -- four chains of layer launches ran at half the speed of two.)
             with self.branch(1, after=self._ev_wn) as self.flight.early_pack:
                 BW.pack_bwd_weights(self)
+        return x, gid
+
+    def _step_run(self, fwd, x, gid, lengths, quantize_channels, log_scale_min, ce_scale, grad_sync):
+        """Forward, criterion and backward of one step.  fwd(targets, lengths, want_logits): the train-mode forward of the step's
+        inputs -- class ids: the fused masked cross-entropy against x; scalar input: the logits, whose mixture loss and gradient are
+        formed here.  -> (the forward's dict with loss, the finished gradient arena)."""
         try:
             if self.g.scalar_input:
-                fwd = self.forward if self.g.has_encoder else self.decoder_forward
-                out = fwd(x, c, gid, targets=None, lengths=None, want_logits=True, train=True)
+                out = fwd(None, None, True)
                 loss, dyt = self.scalar_loss_and_grad(out["logits"], x, lengths, quantize_channels, log_scale_min, scale=ce_scale)
                 out["loss"] = loss
                 grads = self.backward(x, gid, None, lengths, ext_dy=dyt, vq_scale=1.0, grad_sync=grad_sync)
-            elif self.g.has_encoder:
-                out = self.forward(x, c, gid, targets=x, lengths=lengths, want_logits=False, train=True,
-                                   layer_events=self._layer_events)
             else:
-                out = self.decoder_forward(x, c, gid, targets=x, lengths=lengths, want_logits=False, train=True,
-                                           layer_events=self._layer_events)
-            if not self.g.scalar_input:
+                out = fwd(x, lengths, False)
                 grads = self.backward(x, gid, x, lengths, loss_scale=ce_scale, vq_scale=1.0, grad_sync=grad_sync)
         except BaseException:
             self.join(self.flight.abandon())
             raise
+        return out, grads
+
+    def _step_close(self, out, grads, grad_sync, grad_hook, lr, betas, eps, weight_decay, clip_thresh, ema_decay):
+        """[grad_sync / grad_hook], clip_grad_norm_ + Adam + EMA, the step's numbers."""
         if grad_sync is not None:
             grad_sync.finish()
         if grad_hook is not None:
@@ -1714,6 +1738,149 @@ class WaeEngine:
         else:
             res["loss"] = out["loss"]
         return res
+
+    # ------------------------------------------------------------------ a ragged train step: list front end, dense decoder
+    def train_step_list(self, items, lr: float = 4e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                        clip_thresh: float = 100.0, ema_decay: float = 0.9999, beta: float = 0.25, grad_hook=None,
+                        quantize_channels: int = 65536, log_scale_min: float = -7.0, max_rows: Optional[int] = None, grad_sync=None):
+        """One optimisation step on a LIST of utterances of unequal lengths, none of them padded in front of the decoder.
+        items: dicts x (T_i,) class ids (or scalars), c (c_in, F_i) features (or, forward_list's name, feats) -- an engine without an
+        encoder: c (Cc, Tc_i) -- and gid.
+        train_step on the zero-padded batch masks the cross-entropy only: behind the encoder's first block the pad frames are not zero,
+        their latents enter the commitment mean, and the conditioning of every utterance's end reads them (DESIGN.md has the figures).
+        Here the FRONT END runs on the packed list (encode_list's launches keeping every layer's input, ONE quantiser call on the
+        packed latents, the upsampling list chain writing item b's rows of a zero-filled (B, Tmax, Ccp) operand) and the DECODER runs
+        dense on the right-padded batch with `lengths`, forward and backward exactly as in train_step: a valid row reads nothing to
+        its right, and under the masked loss a pad row sends no gradient to its left.  The list forms of the front end's backward
+        (backward.frontend_backward_list) finish the gradients; the optimizer call is train_step's.
+        ce = sum nll / sum (T_i - 1); vq_loss and perp are the packed quantiser call's, the list as one batch -- score_list's totals.
+        EMA codebooks move once, on the list's packed latents.  Dropout as in train_step.
+        Returns dict(loss, ce, vq_loss, perp, grad_norm, rows = B * Tmax, pad_rows = rows - sum T_i): length-sorted lists keep
+        pad_rows low.
+        ValueError before any launch and any RNG draw: an empty list, a malformed item, len(x_i) != prod(upsample_scales) * Tq_i,
+        F_i < 1, B * Tmax > max_rows (default packing.FWD_LIST_MAX_ROWS; the caller splits longer lists).  NotImplementedError before
+        any launch: EngineOptions.deterministic, grad_sync, cin_pad > 0, an upsample_activation, a geometry without an upsampling
+        network or one the upsampling list kernels do not cover.  RuntimeError inside an open accumulation window."""
+        g, dev = self.g, self.device
+        self._refuse_in_window("train_step_list")
+        if self.opt.deterministic:
+            raise NotImplementedError("train_step_list with EngineOptions.deterministic: the list forms of the front end's backward "
+                                      "have no fixed-order form")
+        if grad_sync is not None:
+            raise NotImplementedError("train_step_list with grad_sync: ragged steps cover one GPU")
+        if not g.upsample_scales or g.Cc <= 0:
+            raise NotImplementedError("train_step_list: this geometry has no upsampling network in front of the decoder; zero-padding "
+                                      "changes nothing there: use train_step with lengths")
+        if g.cin_pad > 0:
+            raise NotImplementedError(f"train_step_list with cin_pad = {g.cin_pad}: the ragged step covers cin_pad = 0")
+        if g.up_act != "none":
+            raise NotImplementedError(f"train_step_list with upsample_activation {g.up_act!r}")
+        if not P.upsample_list_supported(g):
+            raise NotImplementedError("train_step_list: the upsampling list kernels do not cover this geometry (packing.upsample_list_supported)")
+        items = list(items)
+        if not items:
+            raise ValueError("train_step_list: an empty list")
+        crow = g.c_in if g.has_encoder else g.Cc
+        Ts, Fs, feats = [], [], []
+        for i, it in enumerate(items):
+            cv = it.get("c") if it.get("c") is not None else it.get("feats")       # (forward_list's name for the features)
+            xs, cs = tuple(getattr(it.get("x"), "shape", ())), tuple(getattr(cv, "shape", ()))
+            if len(xs) != 1 or xs[0] < 2:
+                raise ValueError(f"train_step_list: item {i}: x has shape {xs}; every x is (T,) with T >= 2")
+            if len(cs) != 2 or cs[0] != crow:
+                raise ValueError(f"train_step_list: item {i}: c has shape {cs}; every c is ({crow}, frames)")
+            if g.n_speakers and it.get("gid") is None:
+                raise ValueError(f"train_step_list: item {i} has no gid")
+            Ts.append(int(xs[0]))
+            Fs.append(int(cs[1]))
+            feats.append(cv)
+        tp = P.train_list_plan(g, Ts, Fs, max_rows)
+        B, Tmax = tp.B, tp.Tmax
+        # the dense decoder's inputs: right-padded ids (class 0 / 0.0 in the pad rows, which the masked loss never reads), lengths, speakers
+        xd = torch.zeros(B, Tmax, dtype=torch.float32 if g.scalar_input else torch.int32)
+        host = all(not (torch.is_tensor(it["x"]) and it["x"].is_cuda) for it in items)
+        if not host:
+            xd = xd.to(dev)
+        for b, it in enumerate(items):
+            xd[b, :Ts[b]] = torch.as_tensor(it["x"]).to(xd.device, xd.dtype)
+        x = xd.to(dev)
+        lengths = torch.tensor(Ts, dtype=torch.int32)
+        gid = torch.tensor([int(it["gid"]) for it in items], dtype=torch.int32, device=dev) if g.n_speakers else None
+        cs = feats
+        x, gid = self._step_open(x, gid, weight_decay)
+
+        def fwd(targets, lengths, want_logits):
+            return self._forward_list_train(tp, x, cs, gid, targets, lengths, want_logits, beta)
+
+        out, grads = self._step_run(fwd, x, gid, lengths, quantize_channels, log_scale_min, 1.0, None)
+        res = self._step_close(out, grads, None, grad_hook, lr, betas, eps, weight_decay, clip_thresh, ema_decay)
+        res.update(rows=tp.rows, pad_rows=tp.pad_rows)
+        return res
+
+    def _forward_list_train(self, tp, x, cs, gid, targets, lengths, want_logits, beta):
+        """The train-mode forward of a ragged step: the list front end (every layer's packed input kept for the backward) into the
+        zero-filled conditioning operand of the (B, Tmax, train) workspace, then the dense decoder_forward on it."""
+        g, lib, st, dev = self.g, self.lib, self.stream(), self.device
+        B, T = tp.B, tp.Tmax
+        sv = Saved(B, T)
+        t_enc = torch.from_numpy(tp.enc.table).to(dev) if tp.enc is not None else None
+        t_ups, t_bwd = torch.from_numpy(tp.ups.table).to(dev), torch.from_numpy(tp.bwd_table).to(dev)
+        fe = sv.list_fe = dict(plan=tp, tables=(t_enc, t_ups, t_bwd), enc_acts=None, up_acts=None)
+        stats = None
+        if g.has_encoder:
+            plan = tp.enc
+            if all(not (torch.is_tensor(f) and f.is_cuda) for f in cs):          # all on the host: pack there, one upload
+                xa = torch.cat([torch.as_tensor(f).to(torch.float32) for f in cs], dim=1).to(dev)
+            else:
+                xa = torch.cat([torch.as_tensor(f).to(dev, torch.float32) for f in cs], dim=1)
+            xa = xa.contiguous()
+            acts = [xa]
+            convs = [(f"encoder.net.{i}.conv", 1) for i in range(len(P.ENCODER_BLOCKS))] + [("encoder.lin", 0)]
+            for (name, relu), ly in zip(convs, plan.layers):
+                co, ci = self.lay.shapes[name + ".weight"][:2]
+                y = torch.empty(co, ly.out_pitch, dtype=torch.float32, device=dev)
+                res = int(bool(relu) and ly.stride == 1 and ci == co)
+                L.check(lib.wae_enc_conv_fwd_list(L.ptr(acts[-1]), L.ptr(self.eff[self.lay.off(name + ".weight"):]),
+                                                  L.ptr(self.eff[self.lay.off(name + ".bias"):]), L.ptr(y), L.ptr(t_enc[ly.seg_off:]),
+                                                  ly.nsegs, L.ptr(t_enc[ly.tile_off:]), ly.ntiles, ly.et, ly.in_pitch, ly.out_pitch, ci, co,
+                                                  ly.k, ly.stride, ly.pad, relu, res, st), "enc_conv_fwd_list")
+                acts.append(y)
+            lat = acts.pop().view(1, g.Cc, plan.total_Tq)       # no gap columns: the quantiser's mean is over Cc * sum Tq_i
+            fe["enc_acts"] = acts
+            quant, idx, stats = self.vq_forward(lat, beta, update=True)
+            sv.lat, sv.quant, sv.idx, sv.beta = lat, quant, idx, beta
+            xc = quant[0]
+        else:
+            xc = self._pack_cond_list(cs)
+        ws = self.workspace(B, T, True)
+        c_up = ws["c_up"]
+        c_up.zero_()                              # the pad rows of every item: what the padded decoder reads there, and zero gradient back
+        ups = [xc if g.conv_in else None]
+        stage = 0
+        for ln in tp.ups.launches:
+            if ln.kind == "conv_in":
+                y = torch.empty(g.Cc, ln.out_pitch, dtype=torch.float32, device=dev)
+                w = self.eff[self.lay.off("wavenet.upsample_net.conv_in.weight"):]
+                L.check(lib.wae_enc_conv_fwd_list(L.ptr(xc), L.ptr(w), None, L.ptr(y), L.ptr(t_ups[ln.seg_off:]), ln.nsegs,
+                                                  L.ptr(t_ups[ln.tile_off:]), ln.ntiles, ln.et, ln.in_pitch, ln.out_pitch, g.Cc, g.Cc,
+                                                  ln.s, 1, 0, 0, 0, st), "conv_in (list)")
+            else:
+                assert ln.kind in ("stage", "last"), ln.kind
+                last = ln.kind == "last"
+                ups.append(xc)
+                w = self.eff[self.lay.off(P.up_stage_name(g, stage) + ".weight_v"):]
+                stage += 1
+                y = c_up if last else torch.empty(g.Cc, ln.out_pitch, dtype=torch.float32, device=dev)
+                L.check(lib.wae_upsample_stage_fwd_list(L.ptr(xc), L.ptr(w), L.ptr(y), L.ptr(t_ups[ln.seg_off:]), ln.nsegs, ln.ntiles,
+                                                        ln.in_pitch, B * T if last else ln.out_pitch, g.Cc, ln.s, int(last), g.Ccp,
+                                                        self.dt, st), "upsample_stage (list)")
+            xc = y
+        fe["up_acts"] = ups
+        kw = dict(layer_events=self._layer_events) if not g.scalar_input else {}
+        out = self.decoder_forward(x, None, gid, targets, lengths, want_logits, True, c_is_upsampled=True, saved=sv, c_ready=True, **kw)
+        if stats is not None:
+            out.update(latents=sv.lat, quant=sv.quant, idx=sv.idx, vq_loss=stats[0], perp=stats[1])
+        return out
 
     def _clip_adam_ema(self, grads, summed, lr, betas, eps, weight_decay, clip_thresh, ema_decay):
         """clip_grad_norm_ + Adam + EMA on the finished gradients (csrc/loss.hip).  summed: the gather passes of the backward

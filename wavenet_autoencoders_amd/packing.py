@@ -697,6 +697,78 @@ def upsample_list_groups(Ts, max_samples: int = UPS_LIST_MAX_SAMPLES) -> List[Tu
     return encode_list_groups(Ts, int(max_samples))
 
 
+# ---- a ragged train step (WaeEngine.train_step_list): the list front end in front of the dense, right-padded decoder
+class TrainListPlan(NamedTuple):
+    """train_list_plan's answer.  enc: the encoder's list plan (None: an engine without an encoder); ups: the conditioning chain's,
+    whose last launch writes item b at the rows [b * Tmax, b * Tmax + T_b) of the dense (B, Tmax, Ccp) operand; Ts: samples per item;
+    B, Tmax: the dense decoder's shape; rows = B * Tmax; pad_rows = rows - sum T_i: the rows the decoder spends on padding.
+    bwd_table: the records of the backward launches that the forward's tables do not hold, in ONE int32 array -- at fb_off the
+    nsegs + 1 wae_ups_seg records of wae_from_btc_list (fb_ntiles tiles of 64 rows: rows b * Tmax + t -> columns of the packed
+    (Cc, sum T_i) gradient), at stage_off[i] those of stage i's wae_upsample_stage_bwd_list (stage_ntiles[i] tiles of 256 output
+    columns; stage_pitch[i] = (in_pitch, out_pitch), both running sums without gaps)."""
+    enc: Optional[EncListPlan]
+    ups: UpsListPlan
+    Ts: np.ndarray
+    B: int
+    Tmax: int
+    rows: int
+    pad_rows: int
+    bwd_table: np.ndarray
+    fb_off: int
+    fb_ntiles: int
+    stage_off: List[int]
+    stage_ntiles: List[int]
+    stage_pitch: List[Tuple[int, int]]
+
+
+def train_list_plan(g: Geometry, Ts, Fs, max_rows: Optional[int] = None) -> TrainListPlan:
+    """Launch plan of WaeEngine.train_step_list for items of Ts samples and Fs feature frames (an engine without an encoder: Fs
+    conditioning frames).  Pure numpy: a function of the lengths alone.  ValueError, with the item's index: an empty list, lists of
+    unequal sizes, an item without a frame, an item whose samples are not prod(scales) * Tq_i (Tq_i: its latent frames; without an
+    encoder its conditioning frames), B * Tmax above max_rows (default FWD_LIST_MAX_ROWS: the caller splits longer lists)."""
+    Ts = np.asarray(Ts, dtype=np.int64).reshape(-1)
+    Fs = np.asarray(Fs, dtype=np.int64).reshape(-1)
+    if Ts.size < 1:
+        raise ValueError("train_list_plan: an empty list")
+    if Fs.size != Ts.size:
+        raise ValueError(f"train_list_plan: {Ts.size} sample counts for {Fs.size} frame counts")
+    if int(Fs.min()) < 1:
+        raise ValueError(f"train_list_plan: item {int(np.argmax(Fs < 1))} has no frame (F >= 1)")
+    if not g.upsample_scales or g.Cc <= 0:
+        raise ValueError("train_list_plan: this geometry has no upsampling network in front of the decoder")
+    enc = encode_list_plan(Fs) if g.has_encoder else None
+    Tq = enc.Tq if enc is not None else Fs
+    scales = [int(s) for s in g.upsample_scales]
+    prod = int(np.prod(scales))
+    wrong = Ts != prod * Tq
+    if wrong.any():
+        i = int(np.argmax(wrong))
+        raise ValueError(f"train_list_plan: item {i} has {int(Ts[i])} samples for {int(Tq[i])} conditioning frames: "
+                         f"len(x) == prod(upsample_scales) * Tq = {prod * int(Tq[i])}")
+    B, Tmax = int(Ts.size), int(Ts.max())
+    cap = FWD_LIST_MAX_ROWS if max_rows is None else int(max_rows)
+    if B * Tmax > cap:
+        raise ValueError(f"train_list_plan: {B} items padded to {Tmax} samples are {B * Tmax} rows > max_rows {cap}: split the list")
+    ups = upsample_list_plan(Tq, g, offsets=np.arange(B, dtype=np.int64) * Tmax)
+    parts, at = [], 0
+    rec, fb_ntiles = ups_list_records(_running(Ts), Ts, np.arange(B, dtype=np.int64) * Tmax, Ts, UPS_LIST_TILE_BTC)
+    fb_off = at
+    parts.append(rec.reshape(-1))
+    at += rec.size
+    stage_off, stage_ntiles, stage_pitch, Tin = [], [], [], Tq
+    for s in scales:
+        To = Tin * s
+        rec, nt = ups_list_records(_running(Tin), Tin, _running(To), To, UPS_LIST_TILE_CT)
+        stage_off.append(at)
+        stage_ntiles.append(nt)
+        stage_pitch.append((int(Tin.sum()), int(To.sum())))
+        parts.append(rec.reshape(-1))
+        at += rec.size
+        Tin = To
+    return TrainListPlan(enc, ups, Ts, B, Tmax, B * Tmax, B * Tmax - int(Ts.sum()), np.concatenate(parts).astype(np.int32), fb_off,
+                         fb_ntiles, stage_off, stage_ntiles, stage_pitch)
+
+
 # ---- the teacher-forced gated stack over a list (include/wae.h: wae_glu_layer_fwd_list, wae_nll_segments)
 GLU_LIST_TILES = {0: 128, 1: 256, 2: 256}      # dtype (WAE_F32, WAE_BF16, WAE_F16) -> time columns of a tile: wae_glu_list_tile()
 # Default cap on the rows (sum T_i) of one group of WaeEngine.decoder_forward_list.  The largest array of a group is u, all layers'

@@ -28,6 +28,11 @@ class Saved:
     quant: Optional[torch.Tensor] = None
     idx: Optional[torch.Tensor] = None
     beta: float = 0.25
+    # the LIST front end of a ragged step (WaeEngine.train_step_list), in place of up_acts / enc_acts: dict(plan: packing.TrainListPlan,
+    # tables: the device tables (enc, ups, bwd), enc_acts: the packed input of every encoder layer then the latents' producer's input,
+    # up_acts: [conv_in's packed input | None, every stage's packed input]); lat / quant / idx are then the packed (1, Cc, sum Tq_i)
+    # arrays.  None: a dense forward.
+    list_fe: Optional[dict] = None
 
 
 @dataclasses.dataclass
