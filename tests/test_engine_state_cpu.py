@@ -7,7 +7,7 @@ import os
 import pytest
 
 PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "wavenet_autoencoders_amd")
-FILES = ["engine.py", "decode.py", "backward.py", "vqvae_model.py", "checkpoint.py", "wavenet_vocoder/wavenet.py", "wavenet_vocoder/modules.py"]
+FILES = ["engine.py", "frontend.py", "train.py", "decode.py", "backward.py", "vqvae_model.py", "checkpoint.py", "wavenet_vocoder/wavenet.py", "wavenet_vocoder/modules.py"]
 ENGINE_NAMES = {"self", "eng", "engine"}
 
 

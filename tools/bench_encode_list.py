@@ -66,7 +66,7 @@ def stats_cost(eng, dev, Fs, repeats):
     same = all(torch.equal(a["quant"], b["quant"]) and torch.equal(a["idx"], b["idx"]) for a, b in zip(plain, full))
     same = same and all(torch.equal(b["hist"].long(), torch.bincount(b["idx"], minlength=g.K)) for b in full[:16])
     whole = pair("whole", lambda: eng.encode_list(dev), lambda: eng.encode_list_stats(dev), repeats)
-    # the two calls alone, on the groups' packed latents as _encode_group holds them
+    # the two calls alone, on the groups' packed latents as frontend._encode_group holds them
     groups = []
     for lo, hi in P.encode_list_groups([int(F) for F in Fs], P.ENC_LIST_MAX_FRAMES):
         lat = torch.cat([r["latents"] for r in plain[lo:hi]], dim=1).contiguous()

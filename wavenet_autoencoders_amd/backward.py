@@ -23,6 +23,7 @@ import torch
 
 from . import _lib as L
 from . import packing as P
+from .frontend import encoder_convs
 from .step_state import saved_for
 
 RS = math.sqrt(0.5)
@@ -1202,7 +1203,7 @@ def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: O
     cx.gvec = gvec
     sched = _tn_schedule(cx, grad_sync is not None)
     cx.finish = eng.flight.finish_used = _finish_plan(cx)
-    cx.finish_acc = cx.finish is not None and grad_sync is None and not eng.opt.deterministic      # (its norm: engine._clip_adam_ema)
+    cx.finish_acc = cx.finish is not None and grad_sync is None and not eng.opt.deterministic      # (its norm: train.clip_adam_ema)
     eng.flight.norm_summed = False
     if win is not None:
         win.static, win.shape = isinstance(ws["stream"], StaticStreamTable), (B, T)
@@ -1338,7 +1339,7 @@ def finish_window(eng, win, grad_sync=None):
     cx = _step(eng, *win.shape)
     fl = eng.flight
     cx.finish = fl.finish_used = _finish_plan(cx)
-    cx.finish_acc = cx.finish is not None and grad_sync is None and not eng.opt.deterministic      # (its norm: engine._clip_adam_ema)
+    cx.finish_acc = cx.finish is not None and grad_sync is None and not eng.opt.deterministic      # (its norm: train.clip_adam_ema)
     _first_conv_finish(cx)
     done = _finish_layers(cx, 0, eng.g.layers, with_head=True, zb=False)
     eng.join(done[0] if done else None)
@@ -1480,13 +1481,13 @@ def frontend_backward_list(eng, dc: torch.Tensor, loss_scale: float = 1.0):
     B, T = dc.shape[0], dc.shape[1]
     sv = saved_for(eng, B, T)
     fe = sv.list_fe
-    tp = fe["plan"]
-    t_enc, t_ups, t_bwd = fe["tables"]
+    tp = fe.plan
+    t_enc, t_ups, t_bwd = fe.tables
     total = int(tp.Ts.sum())
     d = torch.empty(g.Cc, total, dtype=torch.float32, device=dev)
     L.check(lib.wae_from_btc_list(L.ptr(dc), L.ptr(d), L.ptr(t_bwd[tp.fb_off:]), B, tp.fb_ntiles, total, B * T, g.Cc, g.Ccp, eng.dt,
                                   1.0 / eng.grad_scale, st), "from_btc_list")
-    acts = fe["up_acts"]                     # [conv_in's packed input | None, stage-0 input, stage-1 input, ...]
+    acts = fe.up_acts                     # [conv_in's packed input | None, stage-0 input, stage-1 input, ...]
     keep = [d]
     for i in range(len(g.upsample_scales) - 1, -1, -1):
         s = int(g.upsample_scales[i])
@@ -1514,8 +1515,8 @@ def frontend_backward_list(eng, dc: torch.Tensor, loss_scale: float = 1.0):
         return dq
     Tq = sv.lat.shape[-1]                    # the packed latents as ONE clip: (1, Cc, sum Tq_i), no gap columns
     dlat = _vq_backward(eng, sv, dq, 1, Tq, loss_scale)
-    ea, layers = fe["enc_acts"], tp.enc.layers        # ea[i]: the packed input of layer i (ten blocks, then lin)
-    convs = [(f"encoder.net.{i}.conv", 1) for i in range(len(P.ENCODER_BLOCKS))] + [("encoder.lin", 0)]
+    ea, layers = fe.enc_acts, tp.enc.layers        # ea[i]: the packed input of layer i (ten blocks, then lin)
+    convs = encoder_convs(eng)
     dcur = dlat
     keep.append(dlat)
     for i in range(len(convs) - 1, -1, -1):

@@ -14,6 +14,7 @@ from __future__ import annotations
 import ctypes
 import dataclasses
 import math
+import types
 
 from typing import Dict, Optional
 
@@ -21,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import frontend as F
 from . import packing as P
 
 # include/wae.h: wae_ar_item and wae_ar_span, as the host packs them
@@ -982,22 +984,21 @@ class DecodeSession:
                 dst, ns = [p[0] for p in pieces], [p[1] for p in pieces]
             segs, tiles, et, _ = P.enc_list_tables(ns, 1, 1, 0)
             segs[:, 2] = dst
-            conv = (plan.table.size, plan.table.size + segs.size, len(segs), len(tiles), et, int(sum(ns)))
+            conv = types.SimpleNamespace(seg_off=plan.table.size, tile_off=plan.table.size + segs.size, nsegs=len(segs), ntiles=len(tiles),
+                                         et=et, in_pitch=int(sum(ns)))      # (the record frontend.conv_list takes)
             parts += [segs.reshape(-1), tiles.reshape(-1)]
             if not g.conv_in:       # the plain network: the frames are stage 0's input as they are
                 parts.append(np.concatenate([np.arange(o, o + n) for o, n in zip(segs[:, 2], ns)]).astype(np.int32))
         table = torch.from_numpy(np.concatenate(parts)).to(dev)        # ONE upload
         x = None
         if fed:
-            x = eng._pack_cond_list([feeds[h] for h, _ in fed])
-            seg_off, tile_off, nsegs, ntiles, et, pitch = conv
+            x = F.pack_time(eng, [feeds[h] for h, _ in fed], g.Cc)
             if g.conv_in:
-                w = eng.eff[eng.lay.off("wavenet.upsample_net.conv_in.weight"):]
-                L.check(eng.lib.wae_enc_conv_fwd_list(L.ptr(x), L.ptr(w), None, L.ptr(self._fa[0]), L.ptr(table[seg_off:]), nsegs,
-                                                      L.ptr(table[tile_off:]), ntiles, et, pitch, self._fa[0].shape[1], g.Cc, g.Cc, 1, 1,
-                                                      0, 0, 0, eng.stream()), "conv_in (feed)")
+                conv.out_pitch = self._fa[0].shape[1]
+                F.conv_list(eng, x, self._fa[0], table, conv, "wavenet.upsample_net.conv_in.weight", None, g.Cc, g.Cc, (1, 1, 0, 0, 0),
+                            "conv_in (feed)")
             else:
-                self._fa[0].index_copy_(1, table[tile_off + 2 * ntiles:].long(), x)
+                self._fa[0].index_copy_(1, table[conv.tile_off + 2 * conv.ntiles:].long(), x)
         for ln in plan.launches:
             w = eng.eff[eng.lay.off(P.up_stage_name(g, ln.stage) + ".weight_v"):]
             out = self._fa_cup if ln.last else self._fa[ln.stage + 1]

@@ -264,7 +264,7 @@ def step_ce_scale(lengths: Optional[torch.Tensor], T: int, batch: int, variable_
 def accum_weights(metas, world: int = 1, group=None, total=None):
     """The loss weights of an accumulation window (WaeEngine.accumulate): metas holds one (B_i, T_i, lengths_i | None,
     latent_elements_i) per micro-batch -> ([(ce_weight_i, vq_weight_i), ...], N).
-    n_i = sum_b max(min(len_b, T_i) - 1, 0) loss positions (B_i (T_i - 1) without lengths: WaeEngine._masked_step_loss), N = sum n_i;
+    n_i = sum_b max(min(len_b, T_i) - 1, 0) loss positions (B_i (T_i - 1) without lengths: train.mixture_loss_and_grad), N = sum n_i;
     e_i = latent_elements_i, E = sum e_i; ce_weight_i = n_i / N, vq_weight_i = e_i / E (0 where the sum is 0).  Each micro-batch's
     loss is a mean over its own n_i positions / e_i elements, so under these weights the window's loss is the masked mean over ALL
     loss positions plus the mean over ALL latent elements: where the micro-batches share T, the loss of one step on the

@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import frontend as F
 from . import packing as P
 
 
@@ -55,7 +56,7 @@ class EncodeSession:
         self.clips: Dict[int, _EncClip] = {}
         self._next_handle, self._closed = 0, False
         self._ar, self._cap, self._top = None, 0, 0
-        self._names = [f"encoder.net.{i}.conv" for i in range(len(P.ENCODER_BLOCKS))] + ["encoder.lin"]
+        self._names = [name for name, _ in F.encoder_convs(eng)]
         self.window = None if window is None else int(window)
         self.max_feed, self._periods, self._nslots, self._free = None, None, 0, []
         if self.window is not None:
@@ -245,7 +246,7 @@ class EncodeSession:
         table = torch.from_numpy(np.concatenate(parts)).to(dev) if sum(p.size for p in parts) else None
         x = None
         if fed:
-            x = self._pack([feeds[h] for h, _ in fed])
+            x = F.pack_time(eng, [feeds[h] for h, _ in fed], g.c_in)
             self._ar[0].index_copy_(1, table[plan.table.size:].long(), x)
         lat = torch.empty(g.Cc, plan.total_new, dtype=torch.float32, device=dev)
         for ln in plan.launches:
@@ -260,7 +261,7 @@ class EncodeSession:
                           ln.stride, ln.pad, int(not last), res, eng.stream()), "enc_conv_fwd_rings" if ring else "enc_conv_fwd_ranges")
         if plan.total_new:
             # the quantiser on this call's new latents as ONE clip: rows are per frame, so idx and quant are what vq_forward gives
-            # the whole utterance (WaeEngine._encode_group does the same with a list)
+            # the whole utterance (frontend._encode_group does the same with a list)
             quant, idx, _ = eng.vq_forward(lat.view(1, g.Cc, plan.total_new))
             quant = quant[0]
         else:
@@ -278,13 +279,6 @@ class EncodeSession:
                 del self.clips[h]
                 self._release(c)
         return out
-
-    def _pack(self, feats):
-        """(c_in, sum f_i) fp32 on the device, side by side in order: host items in one upload"""
-        dev = self.eng.device
-        if all(not (torch.is_tensor(f) and f.is_cuda) for f in feats):
-            return torch.cat([torch.as_tensor(f).to(torch.float32) for f in feats], dim=1).to(dev).contiguous()
-        return torch.cat([torch.as_tensor(f).to(dev, torch.float32) for f in feats], dim=1).contiguous()
 
     def close(self):
         """Ends the session: every open utterance is dropped and the arenas are freed.  Closing twice is harmless; every other call

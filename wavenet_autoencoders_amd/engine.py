@@ -10,7 +10,6 @@ from __future__ import annotations
 
 import contextlib
 import ctypes
-import functools
 import math
 
 from typing import Dict, Optional
@@ -20,7 +19,9 @@ import torch
 
 from . import _lib as L
 from . import decode as D
+from . import frontend as F
 from . import packing as P
+from . import train as TR
 from .decode import DecodeSession  # noqa: F401  (re-exported)
 from .encode import EncodeSession
 from .options import two_chains
@@ -405,105 +406,19 @@ class WaeEngine:
     def encoder_forward(self, c: torch.Tensor, save: Optional[Saved] = None) -> torch.Tensor:
         """a1: c (B, c_in, F) fp32 -> latents (B, Cc, F')  (vqvae_model.py:48-51).  save: the train-mode forward's record, which
         takes the blocks' inputs; without it nothing outlives the call."""
-        g, lib, st = self.g, self.lib, self.stream()
-        x = c.contiguous().float()
-        B = x.shape[0]
-        acts = [x]
-        for i, (k, s) in enumerate(P.ENCODER_BLOCKS):
-            wname = f"encoder.net.{i}.conv.weight"
-            co, ci, _ = self.lay.shapes[wname]
-            Tin = x.shape[-1]
-            Tout = (Tin + 2 * (k // 2) - k) // s + 1
-            y = torch.empty(B, co, Tout, dtype=torch.float32, device=self.device)
-            w = self.eff[self.lay.off(wname):]
-            bb = self.eff[self.lay.off(f"encoder.net.{i}.conv.bias"):]
-            L.check(lib.wae_enc_conv_fwd(L.ptr(x), L.ptr(w), L.ptr(bb), L.ptr(y), B, ci, Tin, co, k, s, k // 2, 1,
-                                         int(s == 1 and ci == co), st), "enc_conv")
-            x = y
-            acts.append(x)
-        Tq = x.shape[-1]
-        lat = torch.empty(B, g.Cc, Tq, dtype=torch.float32, device=self.device)
-        L.check(lib.wae_enc_conv_fwd(L.ptr(x), L.ptr(self.eff[self.lay.off("encoder.lin.weight"):]),
-                                     L.ptr(self.eff[self.lay.off("encoder.lin.bias"):]), L.ptr(lat), B, g.encoder_hid, Tq,
-                                     g.Cc, 1, 1, 0, 0, 0, st), "enc_lin")
-        if save is not None:
-            save.enc_acts = acts       # inputs of every block (+ the last block's output): backward needs them
-        return lat
+        return F.encoder_forward(self, c, save)
 
     def vq_forward(self, lat: torch.Tensor, beta: float = 0.25, update: bool = False):
         """a2: -> (quant (B,Cc,Tq), idx int64 (B*Tq), stats[2] = (vq_loss, perplexity)).  The sliced kinds (Geometry.vq): idx
         (n, B*Tq), a row per slice; vq_loss and perplexity the sums over the slices (vector_quantization.py:113-127).
         update (EMA kinds): the training branch -- the codebooks move between the search and the gather."""
-        g = self.g
-        if g.vq != "plain":
-            return self._vq_forward_slices(lat, float(beta), bool(update))
-        B, D, Tq = lat.shape
-        idx = torch.empty(B * Tq, dtype=torch.int64, device=self.device)
-        quant = torch.empty_like(lat)
-        stats = torch.empty(2, dtype=torch.float32, device=self.device)
-        hist = self._vq_hist = torch.empty(g.K + 1, dtype=torch.int32, device=self.device)
-        L.check(self.lib.wae_vq_nearest(L.ptr(lat), L.ptr(self.eff[self.lay.off("vq.embedding.weight"):]), L.ptr(idx),
-                                        L.ptr(quant), L.ptr(stats), L.ptr(hist), B, D, Tq, g.K, beta, self.stream()),
-                "vq_nearest")
-        if self.opt.deterministic:      # stats[0] again, from a fixed-order sum (the search adds its squared errors by float atomics)
-            L.check(self.lib.wae_vq_loss_det(L.ptr(lat), L.ptr(quant), L.ptr(stats), B, D, 0, D, Tq, beta + 1.0, self.stream()),
-                    "vq_loss_det")
-        return quant, idx, stats
+        return F.vq_forward(self, lat, beta, update)
 
     def vq_slice_records(self, beta: float):
         """The slices of the geometry's quantiser for wae_vq_search_slices: (host array of wae_vq_slice_rec -- codebook pointers into
         the effective arena, c_loss_s = c_loss * D_s / Dtot --, [(codebook name, d0, D, K, c_loss_s)], scratch entries).  Made once per
         beta: the arena never moves."""
-        hit = self._vq_recs.get(beta)
-        if hit is None:
-            g = self.g
-            c_loss = P.vq_coeffs(g, beta)[0]
-            specs = [(name + ".weight", d0, D, K, c_loss * D / g.Cc) for name, d0, D, K in P.vq_slice_specs(g)]
-            recs = (L.VqSliceRec * len(specs))(*[L.VqSliceRec(self.eff.data_ptr() + 4 * self.lay.off(name), d0, D, K, cl)
-                                                 for name, d0, D, K, cl in specs])
-            words = int(self.lib.wae_vq_search_slices_scratch(recs, len(specs)))
-            if words < 1:
-                raise L.WaeError(f"vq_search_slices_scratch: {self.lib.wae_last_error().decode()}")
-            hit = self._vq_recs[beta] = (recs, specs, words)
-        return hit
-
-    def _vq_forward_slices(self, lat: torch.Tensor, beta: float, update: bool):
-        """vq_forward of the sliced / EMA kinds: ONE wae_vq_search_slices call for all slices (two around the codebook update)."""
-        g, lib, st, dev = self.g, self.lib, self.stream(), self.device
-        B, D, Tq = lat.shape
-        recs, specs, words = self.vq_slice_records(beta)
-        n = len(specs)
-        idx = torch.empty(n, B * Tq, dtype=torch.int64, device=dev)
-        quant = torch.empty_like(lat)
-        stats = torch.empty(n, 2, dtype=torch.float32, device=dev)
-        scratch = self._vq_hist = torch.empty(words, dtype=torch.int32, device=dev)
-        call = lambda mode: L.check(lib.wae_vq_search_slices(L.ptr(lat), recs, n, L.ptr(idx), L.ptr(quant), L.ptr(stats), L.ptr(scratch),  # noqa: E731
-                                                             B, D, Tq, mode, st), "vq_search_slices")
-        if update and g.vq_ema:
-            call(1)
-            hoff = 0
-            for s, (name, d0, Ds, K, _) in enumerate(specs):
-                sfx = name[len("vq.embedding"):-len(".weight")]
-                off = self.lay.off(name)
-                L.check(lib.wae_vq_ema_update(L.ptr(lat), L.ptr(idx[s]), L.ptr(scratch[hoff:]), L.ptr(self.vq_buffers["vq.ema_cluster_size" + sfx]),
-                                              L.ptr(self.vq_buffers["vq.ema_w" + sfx]), L.ptr(self.eff[off:]), B, D, d0, Ds, Tq, K,
-                                              float(g.vq_decay), st), "vq_ema_update")
-                # the codebook moved where the search reads it (the effective arena); the parameters are what state_dict, the next
-                # weight norm pass and the optimizer read
-                self.params[off:off + K * Ds].copy_(self.eff[off:off + K * Ds])
-                hoff += K
-            call(2)
-        else:
-            call(0)
-        if self.opt.deterministic:      # every slice's stats[0] again, from a fixed-order sum
-            for s, (_, d0, Ds, _, cl) in enumerate(specs):
-                L.check(lib.wae_vq_loss_det(L.ptr(lat), L.ptr(quant), L.ptr(stats[s]), B, D, d0, Ds, Tq, cl, st), "vq_loss_det")
-        if g.vq_n == 1:
-            return quant, idx[0], stats[0]
-        tot = stats[0]
-        for s in range(1, n):      # in slice order (element-wise adds: the same bits wherever the same slices' numbers are added)
-            tot = tot + stats[s]
-        return quant, idx, tot
+        return F.vq_slice_records(self, beta)
 
     def encode_list(self, feats, want_latents: bool = False, want_idx: bool = True, max_frames: Optional[int] = None):
         """Encoder + quantiser for a LIST of utterances of unequal lengths (include/wae.h: wae_enc_conv_fwd_list): one launch per
@@ -523,7 +438,7 @@ class WaeEngine:
         utterance alone.  The tensors of an item are views of its group's packed (Cc, sum Tq_i) arrays (not contiguous).
         The quantiser's statistics are not computed here: encode_list_stats is this call with them.
         ValueError, before any launch: an empty list, an item that is not (c_in, F_i) with F_i >= 1, an engine without an encoder."""
-        return self._encode_list(feats, want_latents, want_idx, max_frames, None)
+        return F.encode_list(self, feats, want_latents, want_idx, max_frames, None)
 
     def encode_list_stats(self, feats, beta: float = 0.25, want_latents: bool = False, want_idx: bool = True,
                           max_frames: Optional[int] = None):
@@ -538,126 +453,7 @@ class WaeEngine:
         Sliced / EMA quantisers (Geometry.vq): idx is (n, Tq_i), a row per slice; vq_loss = c_loss sum_s sqerr_s / (Tq_i Cc) with the
         kind's c_loss (packing.vq_coeffs), perp = sum_s perp_s, sqerr = sum_s sqerr_s, hist (n, max K_s) int32, zero beyond K_s; the
         totals follow the same rule (packing.vq_list_totals per slice, added over the slices)."""
-        return self._encode_list(feats, want_latents, want_idx, max_frames, float(beta))
-
-    def _encode_list(self, feats, want_latents, want_idx, max_frames, beta):
-        """encode_list (beta None) / encode_list_stats: the checks, the groups, the per-list arrays of the statistics"""
-        want_stats = beta is not None
-        g = self.g
-        if not g.has_encoder:
-            raise ValueError("encode_list: this engine has no encoder (a decoder-only geometry: c_in is None)")
-        feats = list(feats)
-        if not feats:
-            raise ValueError("encode_list: an empty list")
-        for i, f in enumerate(feats):
-            shape = tuple(getattr(f, "shape", ()))
-            if len(shape) != 2 or shape[0] != g.c_in:
-                raise ValueError(f"encode_list: item {i} has shape {shape}; every item is (c_in, F) = ({g.c_in}, F)")
-            if shape[1] < 1:
-                raise ValueError(f"encode_list: item {i} has no frames (F >= 1)")
-        cap = P.ENC_LIST_MAX_FRAMES if max_frames is None else int(max_frames)
-        if cap < 1:
-            raise ValueError(f"encode_list: max_frames {cap} < 1")
-        if self.weights_dirty:
-            self.prepare_weights()
-        out, stats = [], None
-        if want_stats and g.vq != "plain":
-            stats = self._vq_list_stats_open(len(feats), float(beta))
-        elif want_stats:
-            n, dev = len(feats), self.device
-            stats = dict(c_loss=float(beta) + 1.0, keep=[], sqerr=torch.zeros(n, dtype=torch.float32, device=dev),
-                         hist=torch.zeros(n, g.K, dtype=torch.int32, device=dev), item=torch.zeros(n, 2, dtype=torch.float32, device=dev),
-                         out=torch.zeros(4, dtype=torch.float32, device=dev))
-        for lo, hi in P.encode_list_groups([f.shape[1] for f in feats], cap):
-            out += self._encode_group(feats[lo:hi], want_latents, want_idx, stats, lo)
-        if want_stats:
-            if g.vq != "plain":
-                self._vq_list_stats_close(stats)
-            self.last_list_stats = stats["out"]
-            self.hold("encode_list_stats", *stats["keep"])       # the tables passed by raw pointer, until the next list
-            # the items' views by four unbind calls for the whole list: indexing per item cost more than the kernels (about 10 us an item)
-            cols = (stats["sqerr"].unbind(0), stats["item"][:, 0].unbind(0), stats["item"][:, 1].unbind(0), stats["hist"].unbind(0))
-            for r, sq, vq, pp, h in zip(out, *cols):
-                r.update(sqerr=sq, vq_loss=vq, perp=pp, hist=h)
-        return out
-
-    def _encode_group(self, feats, want_latents, want_idx, stats=None, first=0):
-        """one group of encode_list: pack, eleven list launches, one quantiser call; stats: encode_list's per-list arrays, whose
-        entries first .. first + n - 1 this group fills with one more call"""
-        g, lib, st, dev = self.g, self.lib, self.stream(), self.device
-        plan = P.encode_list_plan([f.shape[1] for f in feats])
-        if all(not (torch.is_tensor(f) and f.is_cuda) for f in feats):          # all on the host: pack there, one upload
-            x = torch.cat([torch.as_tensor(f).to(torch.float32) for f in feats], dim=1).to(dev)
-        else:
-            x = torch.cat([torch.as_tensor(f).to(dev, torch.float32) for f in feats], dim=1)
-        x = x.contiguous()
-        tab, vq_off = plan.table, plan.table.size
-        if stats is not None:
-            # the statistics' records ride behind the layers' in the one upload: a copy of their own behind the quantiser's call would
-            # make the host wait for the group's launches and the groups stop overlapping (0.4 ms a group)
-            tab = np.concatenate([tab, P.vq_seg_table(plan.q_offsets, plan.Tq).reshape(-1)])
-        table = torch.from_numpy(tab).to(dev)
-        width = max(self.lay.shapes[f"encoder.net.{i}.conv.weight"][0] for i in range(len(P.ENCODER_BLOCKS)))
-        pong = [torch.empty(width * plan.total_F, dtype=torch.float32, device=dev) for _ in range(2)]
-        lat = torch.empty(g.Cc, plan.total_Tq, dtype=torch.float32, device=dev)
-        convs = [(f"encoder.net.{i}.conv", 1) for i in range(len(P.ENCODER_BLOCKS))] + [("encoder.lin", 0)]
-        for i, ((name, relu), ly) in enumerate(zip(convs, plan.layers)):
-            co, ci = self.lay.shapes[name + ".weight"][:2]
-            y = lat if not relu else pong[i & 1]
-            res = int(bool(relu) and ly.stride == 1 and ci == co)
-            rc = lib.wae_enc_conv_fwd_list(L.ptr(x), L.ptr(self.eff[self.lay.off(name + ".weight"):]),
-                                           L.ptr(self.eff[self.lay.off(name + ".bias"):]), L.ptr(y), L.ptr(table[ly.seg_off:]), ly.nsegs,
-                                           L.ptr(table[ly.tile_off:]), ly.ntiles, ly.et, ly.in_pitch, ly.out_pitch, ci, co, ly.k,
-                                           ly.stride, ly.pad, relu, res, st)
-            L.check(rc, "enc_conv_fwd_list")
-            x = y
-        # the quantiser on the packed latents as ONE clip of sum Tq_i frames: rows are per frame, so idx and quant are per utterance
-        # what vq_forward gives it alone; stats would be the list's aggregate and are not returned
-        quant, idx, _ = self.vq_forward(lat.view(1, g.Cc, plan.total_Tq))
-        quant = quant[0]
-        sl = [slice(int(o), int(o + t)) for o, t in zip(plan.q_offsets, plan.Tq)]
-        res = [dict(quant=quant[:, s], idx=idx[..., s] if want_idx else None, latents=lat[:, s] if want_latents else None) for s in sl]
-        if stats is not None and g.vq != "plain":
-            self._vq_list_stats_group(stats, lat, quant, idx, table[vq_off:], len(feats), plan.total_Tq, first)
-            stats["keep"].append(table)
-        elif stats is not None:
-            L.check(lib.wae_vq_stats_segments(L.ptr(lat), L.ptr(quant), L.ptr(idx), L.ptr(table[vq_off:]), len(feats), g.Cc, plan.total_Tq,
-                                              g.K, stats["c_loss"], first, L.ptr(stats["sqerr"]), L.ptr(stats["hist"]), L.ptr(stats["item"]),
-                                              L.ptr(stats["out"]), st), "vq_stats_segments")
-            stats["keep"].append(table)
-        return res
-
-    # the list statistics of the sliced / EMA kinds: wae_vq_stats_segments once per SLICE and group, on the slice's rows of the packed
-    # arrays (pointer offset d0 * pitch, D = D_s, the slice's idx row and K_s) with c_loss_s = c_loss * D_s / Dtot, so an item's
-    # vq_loss_s is c_loss sqerr_s / (Tq_i Dtot).  Per item and for the list: vq_loss, perp and sqerr are the slices' numbers added in
-    # slice order, hist (n, max K_s) the slices' counts side by side, zero beyond K_s.
-    def _vq_list_stats_open(self, n_items: int, beta: float) -> dict:
-        dev = self.device
-        _, specs, _ = self.vq_slice_records(beta)
-        z = lambda *shape, dt=torch.float32: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
-        return dict(keep=[], specs=specs, slices=[dict(sqerr=z(n_items), hist=z(n_items, K, dt=torch.int32), item=z(n_items, 2), out=z(4))
-                                                  for _, _, _, K, _ in specs])
-
-    def _vq_list_stats_group(self, stats, lat, quant, idx, segs, nsegs, pitch, first):
-        for s, ((_, d0, Ds, K, cl), a) in enumerate(zip(stats["specs"], stats["slices"])):
-            L.check(self.lib.wae_vq_stats_segments(L.ptr(lat[d0:]), L.ptr(quant[d0:]), L.ptr(idx[s] if idx.dim() == 2 else idx), L.ptr(segs),
-                                                   nsegs, Ds, pitch, K, cl, first, L.ptr(a["sqerr"]), L.ptr(a["hist"]), L.ptr(a["item"]),
-                                                   L.ptr(a["out"]), self.stream()), "vq_stats_segments")
-
-    def _vq_list_stats_close(self, stats):
-        sl = stats["slices"]
-        add = lambda key: functools.reduce(lambda x, y: x + y, [a[key] for a in sl])      # noqa: E731  (in slice order)
-        stats["sqerr"], stats["item"] = add("sqerr"), add("item")
-        out = add("out")
-        out[2] = sl[0]["out"][2]       # sum Tq: every slice counted the same frames
-        stats["out"] = out
-        if self.g.vq_n == 1:
-            stats["hist"] = sl[0]["hist"]
-        else:
-            hist = torch.zeros(sl[0]["hist"].shape[0], len(sl), max(a["hist"].shape[1] for a in sl), dtype=torch.int32, device=self.device)
-            for s, a in enumerate(sl):
-                hist[:, s, :a["hist"].shape[1]] = a["hist"]
-            stats["hist"] = hist
+        return F.encode_list(self, feats, want_latents, want_idx, max_frames, float(beta))
 
     def encode_session(self, want_latents: bool = False, window: Optional[int] = None) -> EncodeSession:
         """An encode session: encode_list for utterances whose feature frames still arrive (include/wae.h: wae_enc_conv_fwd_ranges).
@@ -678,46 +474,7 @@ class WaeEngine:
         (upsample.py:69-85): conv_in eats cin_pad frames at either end, then the stages; plain UpsampleNetwork (Geometry.conv_in False,
         upsample.py:29-66): the stages on all Tc frames, then cin_pad * prod(scales) samples trimmed at either end.
         save: the train-mode forward's record, which takes the stages' inputs; without it (eval, a decode) nothing outlives the call."""
-        g, lib, st = self.g, self.lib, self.stream()
-        B, Cc, Tc = c.shape
-        c = c.contiguous()
-        n = len(g.upsample_scales)
-        trim = 0
-        act = P.UP_ACT_KINDS.get(g.up_act, 0)          # upsample_activation behind every stage (upsample.py:44-46), 0 = none
-        if g.conv_in:
-            kin = 2 * g.cin_pad + 1
-            Tin = Tc - 2 * g.cin_pad
-            x = torch.empty(B, Cc, Tin, dtype=torch.float32, device=self.device)
-            L.check(lib.wae_enc_conv_fwd(L.ptr(c), L.ptr(self.eff[self.lay.off("wavenet.upsample_net.conv_in.weight"):]),
-                                         None, L.ptr(x), B, Cc, Tc, Cc, kin, 1, 0, 0, 0, st), "conv_in")
-            acts = [c, x]          # conv_in input, then every stage's input
-        else:
-            x, Tin = c, Tc
-            trim = g.cin_pad * int(np.prod(g.upsample_scales))
-            acts = [None, x]
-        for i, s in enumerate(g.upsample_scales):
-            w = self.eff[self.lay.off(P.up_stage_name(g, i) + ".weight_v"):]
-            last = i == n - 1 and trim == 0 and not act    # the last stage writes the time-major operand itself, unless something follows
-            if last:
-                assert out.shape[1] == Tin * s, (out.shape, Tin * s)
-                y = out
-            else:
-                y = torch.empty(B, Cc, Tin * s, dtype=torch.float32, device=self.device)
-            L.check(lib.wae_upsample_stage_fwd(L.ptr(x), L.ptr(w), L.ptr(y), B, Cc, Tin, s, int(last), g.Ccp, self.dt, st),
-                    "upsample_stage")
-            x, Tin = y, Tin * s
-            if act:
-                L.check(lib.wae_act_fwd(L.ptr(x), x.numel(), act, float(g.up_act_slope), st), "upsample activation")
-            if i < n - 1:
-                acts.append(x)
-        xt = None
-        if trim or act:       # upsample.py:64-65: c[:, :, indent:-indent]
-            assert out.shape[1] == Tin - 2 * trim, (out.shape, Tin, trim)
-            xt = x[:, :, trim:Tin - trim].contiguous() if trim else x
-            L.check(lib.wae_to_btc(L.ptr(xt), L.ptr(out), B, Cc, Tin - 2 * trim, g.Ccp, self.dt, st), "to_btc (c_up)")
-        if save is not None:
-            save.up_acts, save.up_last, save.up_keep = acts, (x if act else None), xt
-        return out
+        return F.upsample_forward(self, c, out, save)
 
     def upsample_list(self, cs, out: Optional[torch.Tensor] = None, offsets=None, c_is_upsampled: bool = False,
                       max_samples: Optional[int] = None):
@@ -739,94 +496,11 @@ class WaeEngine:
         not cover (conv_in with cin_pad > 2, a time-major last stage with Ccp not dividing 256 or 3 s > 256) run that loop into the same
         rows.  ValueError, before any launch and with the item's index: an empty list, an item that is not (Cc, Tc), an item with no
         output frame, rows outside `out`."""
-        g, dev = self.g, self.device
-        cs = list(cs)
-        if not cs:
-            raise ValueError("upsample_list: an empty list")
-        if g.Cc <= 0:
-            raise ValueError("upsample_list: this engine has no local conditioning (Cc <= 0)")
-        Tcs = []
-        for i, c in enumerate(cs):
-            shape = tuple(getattr(c, "shape", ()))
-            if len(shape) == 3 and shape[0] == 1:
-                shape = shape[1:]
-            if len(shape) != 2 or shape[0] != g.Cc:
-                raise ValueError(f"upsample_list: item {i} has shape {tuple(getattr(c, 'shape', ()))}; every item is (Cc, Tc) or "
-                                 f"(1, Cc, Tc) with Cc = {g.Cc}")
-            Tcs.append(int(shape[1]))
-        cap = P.UPS_LIST_MAX_SAMPLES if max_samples is None else int(max_samples)
-        if cap < 1:
-            raise ValueError(f"upsample_list: max_samples {cap} < 1")
-        whole = P.upsample_list_plan(Tcs, g, offsets, c_is_upsampled)       # the lengths, the rows and their refusals; not launched
-        Ts, offs = [int(t) for t in whole.Ts], [int(o) for o in whole.offsets]
-        if out is None:
-            out = torch.empty(whole.rows, g.Ccp, dtype=self.tdtype, device=dev)
-        elif (out.dim() != 2 or out.shape[1] != g.Ccp or out.dtype != self.tdtype or not out.is_contiguous() or not out.is_cuda
-              or out.shape[0] < whole.rows):
-            raise ValueError(f"upsample_list: out is {tuple(out.shape)} {out.dtype}; the items need a contiguous ({whole.rows}+, {g.Ccp}) "
-                             f"{self.tdtype} operand on {dev}")
-        if self.weights_dirty:
-            self.prepare_weights()
-        if not P.upsample_list_supported(g, c_is_upsampled):
-            for i, c in enumerate(cs):
-                ci = torch.as_tensor(c).to(dev, torch.float32).reshape(1, g.Cc, Tcs[i]).contiguous()
-                self._ar_cond_rows(ci, out[offs[i]:offs[i] + Ts[i]].view(1, Ts[i], g.Ccp), c_is_upsampled, f"item {i}: ")
-            return out, whole.offsets
-        keep, groups = [], P.upsample_list_groups(Ts, cap)
-        for lo, hi in groups:
-            plan = whole if len(groups) == 1 else P.upsample_list_plan(Tcs[lo:hi], g, offs[lo:hi], c_is_upsampled)
-            keep += self._upsample_group(cs[lo:hi], plan, out, c_is_upsampled)
-        self.hold("upsample_list", *keep)       # the tables and intermediates, passed by raw pointer, until the next list
-        return out, whole.offsets
+        return F.upsample_list(self, cs, out, offsets, c_is_upsampled, max_samples)
 
     def _pack_cond_list(self, cs):
         """(Cc, sum Tc_i) fp32 on the device, the items side by side in order: the host items in one upload, the rest by one cat"""
-        g, dev = self.g, self.device
-        host = [i for i, c in enumerate(cs) if not (torch.is_tensor(c) and c.is_cuda)]
-        parts = [c.to(dev, torch.float32).reshape(g.Cc, -1) if torch.is_tensor(c) and c.is_cuda else None for c in cs]
-        if host:
-            up = torch.cat([torch.as_tensor(cs[i]).to(torch.float32).reshape(g.Cc, -1) for i in host], dim=1).to(dev)
-            if len(host) == len(cs):
-                return up.contiguous()
-            at = 0
-            for i in host:
-                n = int(cs[i].shape[-1])
-                parts[i] = up[:, at:at + n]
-                at += n
-        return torch.cat(parts, dim=1).contiguous()
-
-    def _upsample_group(self, cs, plan, out, c_is_upsampled):
-        """one group of upsample_list: pack, one table, the chain's launches; -> the tensors the launches read by raw pointer"""
-        g, lib, st, dev = self.g, self.lib, self.stream(), self.device
-        x = self._pack_cond_list(cs)
-        table = torch.from_numpy(plan.table).to(dev)
-        act = 0 if c_is_upsampled else P.UP_ACT_KINDS.get(g.up_act, 0)
-        keep, stage = [table, x], 0
-        for ln in plan.launches:
-            if ln.kind == "conv_in":
-                y = torch.empty(g.Cc, ln.out_pitch, dtype=torch.float32, device=dev)
-                w = self.eff[self.lay.off("wavenet.upsample_net.conv_in.weight"):]
-                L.check(lib.wae_enc_conv_fwd_list(L.ptr(x), L.ptr(w), None, L.ptr(y), L.ptr(table[ln.seg_off:]), ln.nsegs,
-                                                  L.ptr(table[ln.tile_off:]), ln.ntiles, ln.et, ln.in_pitch, ln.out_pitch, g.Cc, g.Cc,
-                                                  ln.s, 1, 0, 0, 0, st), "conv_in (list)")
-            elif ln.kind == "to_btc":
-                y = out
-                L.check(lib.wae_to_btc_list(L.ptr(x), L.ptr(out), L.ptr(table[ln.seg_off:]), ln.nsegs, ln.ntiles, ln.in_pitch, g.Cc,
-                                            g.Ccp, self.dt, st), "to_btc_list (c_up)")
-            else:
-                last = ln.kind == "last"
-                w = self.eff[self.lay.off(P.up_stage_name(g, stage) + ".weight_v"):]
-                stage += 1
-                y = out if last else torch.empty(g.Cc, ln.out_pitch, dtype=torch.float32, device=dev)
-                L.check(lib.wae_upsample_stage_fwd_list(L.ptr(x), L.ptr(w), L.ptr(y), L.ptr(table[ln.seg_off:]), ln.nsegs, ln.ntiles,
-                                                        ln.in_pitch, out.shape[0] if last else ln.out_pitch, g.Cc, ln.s, int(last),
-                                                        g.Ccp, self.dt, st), "upsample_stage (list)")
-                if act:
-                    L.check(lib.wae_act_fwd(L.ptr(y), y.numel(), act, float(g.up_act_slope), st), "upsample activation")
-            if y is not out:
-                keep.append(y)
-            x = y
-        return keep
+        return F.pack_time(self, cs, self.g.Cc)
 
     def layer_drop_seed(self, call: int, layer: int) -> int:
         """64-bit seed of layer `layer`'s dropout mask in the call-th train-mode forward (csrc/misc.hip: dropout_keep)"""
@@ -863,16 +537,9 @@ class WaeEngine:
         if train:       # the launches below overwrite what the previous train-mode forward of this (B, T) saved
             self.saved, sv = None, (saved if saved is not None else Saved(B, T))
         # global conditioning folded with the conv bias (first: in a train step the launches below run beside the weight packing)
-        wg_off = self.lay.off("wavenet.conv_layers.0.conv1x1g.weight_v") if g.Cg > 0 else -1
-        emb_off = self.lay.offsets.get("wavenet.embed_speakers.weight", 0)
-        use_gid = gid is not None and "wavenet.embed_speakers.weight" in self.lay.offsets
         if gid is not None:
             gid = gid.to(torch.int32).contiguous()
-        L.check(lib.wae_gproj_fwd(L.ptr(self.eff), wg_off if (gid is not None or gvec is not None) else -1,
-                                  self.lay.off("wavenet.conv_layers.0.conv.bias"), self.lay.layer_stride,
-                                  L.ptr(gid) if use_gid else None, emb_off, L.ptr(gvec) if gvec is not None else None,
-                                  L.ptr(ws["zb"]), B, g.layers, g.G, g.Hp, max(g.Cg, 0), int(g.n_speakers or 0), L.ptr(self.err), self.stream()),
-                "gproj")
+        self._ar_speaker_rows(B, gid, gvec, ws["zb"])
         # local conditioning
         if g.Ccp and not c_ready:
             if c is None:
@@ -947,7 +614,6 @@ class WaeEngine:
             e1.record(torch.cuda.current_stream(self.device))
             layer_events.append((e0, e1))
         # head (+ fused CE)
-        hd = L.HeadDesc(self.dt, B, T, g.Ku, g.Sp, g.Op, g.O, math.sqrt(1.0 / g.layers))
         logits = torch.empty(B, g.O, T, dtype=torch.float32, device=self.device) if want_logits else None
         tg = targets.to(torch.int32).contiguous() if targets is not None else None
         if tg is not None and tg.data_ptr() != (xi.data_ptr() if not g.scalar_input else 0):   # targets = inputs: already checked
@@ -956,7 +622,7 @@ class WaeEngine:
         out = dict(logits=logits, nll=None, loss=None)
         if tg is not None:
             ln = lengths.to(self.device, torch.int32).contiguous() if lengths is not None else None
-            L.check(lib.wae_masked_mean(L.ptr(ws["nll"]), L.ptr(ln), L.ptr(ws["loss"]), B, T, st), "masked_mean")
+            TR.masked_mean(self, ws["nll"], ln, ws["loss"])
             out["nll"] = ws["nll"]
             out["loss"] = ws["loss"][0]
         if train:
@@ -1038,21 +704,8 @@ class WaeEngine:
         T_i."""
         g, who = self.g, "decoder_forward_list"
         items = list(items)
-        if not items:
-            raise ValueError(f"{who}: an empty list")
-        Ts = []
-        for i, it in enumerate(items):
-            shape = tuple(getattr(it["x"], "shape", ()))
-            if len(shape) != 1 or shape[0] < 1:
-                raise ValueError(f"{who}: item {i}: x has shape {shape}; every item is (T,) with T >= 1")
-            Ts.append(int(shape[0]))
-        has_gid = [it.get("gid") is not None for it in items]
-        if any(has_gid) and not all(has_gid):
-            raise ValueError(f"{who}: gid on all items or on none")
+        Ts, Tcs, _, _ = TR.list_items(who, items, g, "c")
         if g.Ccp:
-            if any(it.get("c") is None for it in items):
-                raise ValueError(f"{who}: model has local conditioning but an item has no c")
-            Tcs = [int(it["c"].shape[-1]) for it in items]
             Tup = P.upsample_list_plan(Tcs, g, None, c_is_upsampled).Ts       # refuses what upsample_list refuses; not launched
             for i, (a, b) in enumerate(zip(Tup, Ts)):
                 if int(a) != b:
@@ -1091,12 +744,7 @@ class WaeEngine:
             c_up, _ = self.upsample_list([it["c"] for it in items], c_is_upsampled=c_is_upsampled)
         self.join(self.flight.take_pack_done())
         # the inputs side by side in order: the host items in one upload
-        xdt = torch.float32 if g.scalar_input else torch.int32
-        if all(not (torch.is_tensor(it["x"]) and it["x"].is_cuda) for it in items):
-            xi = torch.cat([torch.as_tensor(it["x"]).to(xdt) for it in items]).to(dev)
-        else:
-            xi = torch.cat([torch.as_tensor(it["x"]).to(dev, xdt) for it in items])
-        xi = xi.contiguous()
+        xi = F.pack_time(self, [it["x"] for it in items], 1, torch.float32 if g.scalar_input else torch.int32).view(-1)
         xs = [torch.empty(rows, g.Rp, dtype=td, device=dev) for _ in range(2)]
         u = torch.empty(rows, g.Ku, dtype=td, device=dev)       # all layers' gated activations
         if g.Ku > g.layers * g.Hp:
@@ -1133,11 +781,7 @@ class WaeEngine:
         self._head_fwd(ws, 1, rows, logits, xi if (want_nll and not mixture) else None, False)
         if mixture:
             # per column as the head's cross-entropy: row t against x[t + 1] of the packed rows, 0 at the last row of all
-            if g.output_distribution == "Normal":
-                L.check(lib.wae_mog_loss_fwd(L.ptr(logits), L.ptr(xi), L.ptr(nll), None, 1, g.O, rows, mix[1], 1, st), "mog_loss (list)")
-            else:
-                L.check(lib.wae_dmol_loss_fwd(L.ptr(logits), L.ptr(xi), L.ptr(nll), None, 1, g.O // 3, rows, mix[0], mix[1], 1, st),
-                        "dmol_loss (list)")
+            TR.mixture_nll(self, g.output_distribution == "Normal", logits, xi, nll, None, mix, " (list)")
         if want_nll:
             L.check(lib.wae_nll_segments(L.ptr(nll), L.ptr(table), n, rows, first, L.ptr(sums), L.ptr(counts), L.ptr(loss), st),
                     "nll_segments")
@@ -1373,9 +1017,12 @@ class WaeEngine:
             assert (c.shape[-1] - 2 * g.cin_pad) * int(np.prod(g.upsample_scales)) == T, f"{who}c does not upsample to T"
             self.upsample_forward(c, out)
 
-    def _ar_speaker_rows(self, n, gid32, gvec=None):
-        """zb (n, layers, 2Hp) fp32: every layer's gate bias plus the projection of the speaker vector (gid32's embedding row or gvec)."""
-        g, zb = self.g, torch.empty(n, self.g.layers, 2 * self.g.Hp, dtype=torch.float32, device=self.device)
+    def _ar_speaker_rows(self, n, gid32, gvec=None, zb=None):
+        """zb (n, layers, 2Hp) fp32 (default: a new one): every layer's gate bias plus the projection of the speaker vector (gid32's
+        embedding row or gvec)."""
+        g = self.g
+        if zb is None:
+            zb = torch.empty(n, g.layers, 2 * g.Hp, dtype=torch.float32, device=self.device)
         wg_off = self.lay.off("wavenet.conv_layers.0.conv1x1g.weight_v") if g.Cg > 0 else -1
         use_gid = gid32 is not None and "wavenet.embed_speakers.weight" in self.lay.offsets
         L.check(self.lib.wae_gproj_fwd(L.ptr(self.eff), wg_off if (gid32 is not None or gvec is not None) else -1,
@@ -1554,12 +1201,7 @@ class WaeEngine:
 
     # ------------------------------------------------------------------ training step (vqwae_train.py:709-798)
     def init_optimizer(self, ema: bool = True):
-        self.exp_avg = torch.zeros_like(self.params)
-        self.exp_avg_sq = torch.zeros_like(self.params)
-        self.shadow = self.params.clone() if ema else None        # ExponentialMovingAverage.register (:343-344)
-        self.opt_scratch = torch.zeros(1, dtype=torch.float64, device=self.device)
-        self.grad_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.opt_step = 0
+        TR.init_optimizer(self, ema)
 
     def backward(self, x, gid, targets, lengths, gvec=None, loss_scale: float = 1.0, ext_dy=None, vq_scale: float = None,
                  grad_sync=None, dy_factor: Optional[float] = None):
@@ -1595,57 +1237,20 @@ class WaeEngine:
         -> (masked mean loss, scale * d loss / d y_hat as (B,T,Op) in the compute dtype for decoder_backward's ext_dy).
         Per-step loss and its gradient: wae_dmol_loss_fwd; masked mean: wae_masked_mean; mask, 1/count and the transposition
         of the gradient: wae_to_btc_masked."""
-        g, lib, st = self.g, self.lib, self.stream()
-        B, _, T = y_hat.shape
-        yf = y.contiguous().float()
-        nll = torch.empty(B, T, dtype=torch.float32, device=self.device)
-        dy = torch.empty_like(y_hat)
-        L.check(lib.wae_dmol_loss_fwd(L.ptr(y_hat), L.ptr(yf), L.ptr(nll), L.ptr(dy), B, g.O // 3, T, int(num_classes),
-                                      float(log_scale_min), 1, st), "dmol_loss")
-        loss, dyt, ln = self._masked_step_loss(nll, dy, lengths, scale, factor)
-        self.hold("dmol", yf, nll, dy, ln)
-        return loss, dyt
-
-    def _masked_step_loss(self, nll, dy, lengths, scale, factor=None):
-        """Per-step losses nll (B,T) and their gradient dy (B,O,T) -> (masked mean over the shifted steps, scale * gradient of
-        that mean as (B,T,Op) in the compute dtype, device lengths): wae_masked_mean, wae_to_btc_masked.  factor: the factor on the
-        masked gradient in place of scale * grad_scale / count (accumulate: grad_scale over the window's count)."""
-        g, lib, st = self.g, self.lib, self.stream()
-        B, T = nll.shape
-        if lengths is None:
-            count, ln = B * (T - 1), None
-        else:
-            count = int(torch.clamp(lengths.detach().to("cpu", torch.int64).clamp(max=T) - 1, min=0).sum())
-            ln = lengths.to(self.device, torch.int32).contiguous()
-        loss = torch.empty(2, dtype=torch.float32, device=self.device)
-        L.check(lib.wae_masked_mean(L.ptr(nll), L.ptr(ln), L.ptr(loss), B, T, st), "masked_mean")
-        dyt = torch.zeros(B, T, g.Op, dtype=self.tdtype, device=self.device)
-        L.check(lib.wae_to_btc_masked(L.ptr(dy), L.ptr(dyt), B, g.O, T, g.Op, self.dt, L.ptr(ln),
-                                      float(scale) * self.grad_scale / max(count, 1) if factor is None else float(factor), st),
-                "to_btc dy")
-        return loss[0], dyt, ln
+        return TR.mixture_loss_and_grad(self, False, y_hat, y, lengths, (num_classes, log_scale_min), scale, factor)
 
     def mog_loss_and_grad(self, y_hat: torch.Tensor, y: torch.Tensor, lengths, log_scale_min: float = -7.0, scale: float = 1.0,
                           factor: Optional[float] = None):
         """MixtureGaussianLoss (vqwae_train.py:404-422 with the shift of :766): y_hat (B,C,T) fp32 (C = 2 or 3M), y (B,T) fp32
         -> (masked mean loss, scale * d loss / d y_hat as (B,T,Op) in the compute dtype for decoder_backward's ext_dy).
         Per-step loss and its gradient: wae_mog_loss_fwd; masked mean and transposition as in dmol_loss_and_grad."""
-        lib, st = self.lib, self.stream()
-        B, C, T = y_hat.shape
-        yf = y.contiguous().float()
-        nll = torch.empty(B, T, dtype=torch.float32, device=self.device)
-        dy = torch.empty_like(y_hat)
-        L.check(lib.wae_mog_loss_fwd(L.ptr(y_hat), L.ptr(yf), L.ptr(nll), L.ptr(dy), B, C, T, float(log_scale_min), 1, st), "mog_loss")
-        loss, dyt, ln = self._masked_step_loss(nll, dy, lengths, scale, factor)
-        self.hold("mog", yf, nll, dy, ln)
-        return loss, dyt
+        return TR.mixture_loss_and_grad(self, True, y_hat, y, lengths, (0, log_scale_min), scale, factor)
 
     def scalar_loss_and_grad(self, y_hat, y, lengths, quantize_channels: int = 65536, log_scale_min: float = -7.0,
                              scale: float = 1.0, factor: Optional[float] = None):
         """The criterion of a scalar-input decoder after its output_distribution (vqwae_train.py:802-812)."""
-        if self.g.output_distribution == "Normal":
-            return self.mog_loss_and_grad(y_hat, y, lengths, log_scale_min, scale=scale, factor=factor)
-        return self.dmol_loss_and_grad(y_hat, y, lengths, quantize_channels, log_scale_min, scale=scale, factor=factor)
+        return TR.mixture_loss_and_grad(self, self.g.output_distribution == "Normal", y_hat, y, lengths, (quantize_channels, log_scale_min),
+                                        scale, factor)
 
     def train_step(self, x, c, gid, lengths=None, lr: float = 4e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                    weight_decay: float = 0.0, clip_thresh: float = 100.0, ema_decay: float = 0.9999, grad_hook=None,
@@ -1657,87 +1262,8 @@ class WaeEngine:
         the gradient of the global masked mean of vqwae_train.py:374-379); vq_loss keeps weight 1 (rank mean, :759).
         Class-id input: masked cross-entropy; scalar input (hparams input_type "raw" / "mulaw"): discretized mixture of logistics,
         or mixture of Gaussians with geometry output_distribution "Normal"."""
-        self._refuse_in_window("train_step")
-        self._refuse_grad_sync(grad_sync)
-        x, gid = self._step_open(x, gid, weight_decay)
-
-        def fwd(targets, lengths, want_logits):
-            kw = dict(targets=targets, lengths=lengths, want_logits=want_logits, train=True)
-            if not self.g.scalar_input:
-                kw["layer_events"] = self._layer_events
-            return (self.forward if self.g.has_encoder else self.decoder_forward)(x, c, gid, **kw)
-
-        out, grads = self._step_run(fwd, x, gid, lengths, quantize_channels, log_scale_min, ce_scale, grad_sync)
-        return self._step_close(out, grads, grad_sync, grad_hook, lr, betas, eps, weight_decay, clip_thresh, ema_decay)
-
-    # The three phases train_step and train_step_list share (the statements train_step ran, in its order): what differs between a
-    # dense and a ragged step is the forward handed to _step_run and, behind it, which front-end backward self.backward dispatches to.
-    def _step_open(self, x, gid, weight_decay):
-        """The optimizer's refusal and state, the weights (packing on a side stream), one int32 copy of the ids, the backward's early
-        packing.  -> (x, gid) as the forward and the backward take them."""
-        if weight_decay != 0 and self.g.has_encoder and self.g.vq_ema:
-            # the reference's EMA codebooks have no gradient and the optimizer skips them (grad is None); here they get a zero
-            # gradient, which the fused Adam leaves alone only without weight decay
-            raise NotImplementedError(f"weight_decay = {weight_decay} with the {self.g.vq!r} quantiser: the fused optimizer would "
-                                      "decay the EMA codebooks")
-        if self.exp_avg is None:
-            self.init_optimizer()
-        self.prepare_weights(side=True)
-        # one int32 copy of the ids for forward, targets and backward (each of them converts what it is handed: four 5-us launches)
-        if not self.g.scalar_input and x.dtype != torch.int32:
-            x = x.to(self.device, torch.int32).contiguous()
-        if gid is not None and gid.dtype != torch.int32:
-            # (the same speaker-id tensor step after step -- a benchmark's fixture -- is converted once.  The cache holds the source
-            #  tensor itself and compares by identity: an address comes back from the allocator with the next batch's ids in it)
-            if self._gid_src is not gid or self._gid_version != gid._version:
-                self._gid_src, self._gid_version = gid, gid._version
-                self._gid32 = gid.to(self.device, torch.int32).contiguous()
-            gid = self._gid32
-        from . import backward as BW
-        if self._ev_wn is not None:
-            # the backward's weight packing (+ the clearing of the step's gradient accumulators) needs the effective weights only:
-            # behind the forward's packing on the same side stream, instead of between the head's forward and backward;
-            # decoder_backward waits for it.  (Queued when the first conv is enqueued instead -- beside the first layer -- it made that
-            # layer's launch 45 us longer: 20 us per step worse.  Two side streams carry everything: a process has few hardware
-            # queues, and streams that share one run one after the other -- four chains of layer launches ran at half the speed of two.)
-            with self.branch(1, after=self._ev_wn) as self.flight.early_pack:
-                BW.pack_bwd_weights(self)
-        return x, gid
-
-    def _step_run(self, fwd, x, gid, lengths, quantize_channels, log_scale_min, ce_scale, grad_sync):
-        """Forward, criterion and backward of one step.  fwd(targets, lengths, want_logits): the train-mode forward of the step's
-        inputs -- class ids: the fused masked cross-entropy against x; scalar input: the logits, whose mixture loss and gradient are
-        formed here.  -> (the forward's dict with loss, the finished gradient arena)."""
-        try:
-            if self.g.scalar_input:
-                out = fwd(None, None, True)
-                loss, dyt = self.scalar_loss_and_grad(out["logits"], x, lengths, quantize_channels, log_scale_min, scale=ce_scale)
-                out["loss"] = loss
-                grads = self.backward(x, gid, None, lengths, ext_dy=dyt, vq_scale=1.0, grad_sync=grad_sync)
-            else:
-                out = fwd(x, lengths, False)
-                grads = self.backward(x, gid, x, lengths, loss_scale=ce_scale, vq_scale=1.0, grad_sync=grad_sync)
-        except BaseException:
-            self.join(self.flight.abandon())
-            raise
-        return out, grads
-
-    def _step_close(self, out, grads, grad_sync, grad_hook, lr, betas, eps, weight_decay, clip_thresh, ema_decay):
-        """[grad_sync / grad_hook], clip_grad_norm_ + Adam + EMA, the step's numbers."""
-        if grad_sync is not None:
-            grad_sync.finish()
-        if grad_hook is not None:
-            grad_hook(grads)
-        self.opt_step += 1
-        self._clip_adam_ema(grads, self.flight.norm_summed and grad_sync is None and grad_hook is None, lr, betas, eps, weight_decay,
-                            clip_thresh, ema_decay)
-        self.weights_dirty = True
-        res = dict(ce=out["loss"], grad_norm=self.grad_norm[0])
-        if self.g.has_encoder:
-            res.update(vq_loss=out["vq_loss"], perp=out["perp"], loss=out["loss"] + out["vq_loss"])
-        else:
-            res["loss"] = out["loss"]
-        return res
+        return TR.train_step(self, x, c, gid, lengths, (lr, betas, eps, weight_decay, clip_thresh, ema_decay), grad_hook,
+                             (quantize_channels, log_scale_min), grad_sync, ce_scale)
 
     # ------------------------------------------------------------------ a ragged train step: list front end, dense decoder
     def train_step_list(self, items, lr: float = 4e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
@@ -1761,153 +1287,14 @@ class WaeEngine:
         F_i < 1, B * Tmax > max_rows (default packing.FWD_LIST_MAX_ROWS; the caller splits longer lists).  NotImplementedError before
         any launch: EngineOptions.deterministic, grad_sync, cin_pad > 0, an upsample_activation, a geometry without an upsampling
         network or one the upsampling list kernels do not cover.  RuntimeError inside an open accumulation window."""
-        g, dev = self.g, self.device
-        self._refuse_in_window("train_step_list")
-        if self.opt.deterministic:
-            raise NotImplementedError("train_step_list with EngineOptions.deterministic: the list forms of the front end's backward "
-                                      "have no fixed-order form")
-        if grad_sync is not None:
-            raise NotImplementedError("train_step_list with grad_sync: ragged steps cover one GPU")
-        if not g.upsample_scales or g.Cc <= 0:
-            raise NotImplementedError("train_step_list: this geometry has no upsampling network in front of the decoder; zero-padding "
-                                      "changes nothing there: use train_step with lengths")
-        if g.cin_pad > 0:
-            raise NotImplementedError(f"train_step_list with cin_pad = {g.cin_pad}: the ragged step covers cin_pad = 0")
-        if g.up_act != "none":
-            raise NotImplementedError(f"train_step_list with upsample_activation {g.up_act!r}")
-        if not P.upsample_list_supported(g):
-            raise NotImplementedError("train_step_list: the upsampling list kernels do not cover this geometry (packing.upsample_list_supported)")
-        items = list(items)
-        if not items:
-            raise ValueError("train_step_list: an empty list")
-        crow = g.c_in if g.has_encoder else g.Cc
-        Ts, Fs, feats = [], [], []
-        for i, it in enumerate(items):
-            cv = it.get("c") if it.get("c") is not None else it.get("feats")       # (forward_list's name for the features)
-            xs, cs = tuple(getattr(it.get("x"), "shape", ())), tuple(getattr(cv, "shape", ()))
-            if len(xs) != 1 or xs[0] < 2:
-                raise ValueError(f"train_step_list: item {i}: x has shape {xs}; every x is (T,) with T >= 2")
-            if len(cs) != 2 or cs[0] != crow:
-                raise ValueError(f"train_step_list: item {i}: c has shape {cs}; every c is ({crow}, frames)")
-            if g.n_speakers and it.get("gid") is None:
-                raise ValueError(f"train_step_list: item {i} has no gid")
-            Ts.append(int(xs[0]))
-            Fs.append(int(cs[1]))
-            feats.append(cv)
-        tp = P.train_list_plan(g, Ts, Fs, max_rows)
-        B, Tmax = tp.B, tp.Tmax
-        # the dense decoder's inputs: right-padded ids (class 0 / 0.0 in the pad rows, which the masked loss never reads), lengths, speakers
-        xd = torch.zeros(B, Tmax, dtype=torch.float32 if g.scalar_input else torch.int32)
-        host = all(not (torch.is_tensor(it["x"]) and it["x"].is_cuda) for it in items)
-        if not host:
-            xd = xd.to(dev)
-        for b, it in enumerate(items):
-            xd[b, :Ts[b]] = torch.as_tensor(it["x"]).to(xd.device, xd.dtype)
-        x = xd.to(dev)
-        lengths = torch.tensor(Ts, dtype=torch.int32)
-        gid = torch.tensor([int(it["gid"]) for it in items], dtype=torch.int32, device=dev) if g.n_speakers else None
-        cs = feats
-        x, gid = self._step_open(x, gid, weight_decay)
-
-        def fwd(targets, lengths, want_logits):
-            return self._forward_list_train(tp, x, cs, gid, targets, lengths, want_logits, beta)
-
-        out, grads = self._step_run(fwd, x, gid, lengths, quantize_channels, log_scale_min, 1.0, None)
-        res = self._step_close(out, grads, None, grad_hook, lr, betas, eps, weight_decay, clip_thresh, ema_decay)
-        res.update(rows=tp.rows, pad_rows=tp.pad_rows)
-        return res
-
-    def _forward_list_train(self, tp, x, cs, gid, targets, lengths, want_logits, beta):
-        """The train-mode forward of a ragged step: the list front end (every layer's packed input kept for the backward) into the
-        zero-filled conditioning operand of the (B, Tmax, train) workspace, then the dense decoder_forward on it."""
-        g, lib, st, dev = self.g, self.lib, self.stream(), self.device
-        B, T = tp.B, tp.Tmax
-        sv = Saved(B, T)
-        t_enc = torch.from_numpy(tp.enc.table).to(dev) if tp.enc is not None else None
-        t_ups, t_bwd = torch.from_numpy(tp.ups.table).to(dev), torch.from_numpy(tp.bwd_table).to(dev)
-        fe = sv.list_fe = dict(plan=tp, tables=(t_enc, t_ups, t_bwd), enc_acts=None, up_acts=None)
-        stats = None
-        if g.has_encoder:
-            plan = tp.enc
-            if all(not (torch.is_tensor(f) and f.is_cuda) for f in cs):          # all on the host: pack there, one upload
-                xa = torch.cat([torch.as_tensor(f).to(torch.float32) for f in cs], dim=1).to(dev)
-            else:
-                xa = torch.cat([torch.as_tensor(f).to(dev, torch.float32) for f in cs], dim=1)
-            xa = xa.contiguous()
-            acts = [xa]
-            convs = [(f"encoder.net.{i}.conv", 1) for i in range(len(P.ENCODER_BLOCKS))] + [("encoder.lin", 0)]
-            for (name, relu), ly in zip(convs, plan.layers):
-                co, ci = self.lay.shapes[name + ".weight"][:2]
-                y = torch.empty(co, ly.out_pitch, dtype=torch.float32, device=dev)
-                res = int(bool(relu) and ly.stride == 1 and ci == co)
-                L.check(lib.wae_enc_conv_fwd_list(L.ptr(acts[-1]), L.ptr(self.eff[self.lay.off(name + ".weight"):]),
-                                                  L.ptr(self.eff[self.lay.off(name + ".bias"):]), L.ptr(y), L.ptr(t_enc[ly.seg_off:]),
-                                                  ly.nsegs, L.ptr(t_enc[ly.tile_off:]), ly.ntiles, ly.et, ly.in_pitch, ly.out_pitch, ci, co,
-                                                  ly.k, ly.stride, ly.pad, relu, res, st), "enc_conv_fwd_list")
-                acts.append(y)
-            lat = acts.pop().view(1, g.Cc, plan.total_Tq)       # no gap columns: the quantiser's mean is over Cc * sum Tq_i
-            fe["enc_acts"] = acts
-            quant, idx, stats = self.vq_forward(lat, beta, update=True)
-            sv.lat, sv.quant, sv.idx, sv.beta = lat, quant, idx, beta
-            xc = quant[0]
-        else:
-            xc = self._pack_cond_list(cs)
-        ws = self.workspace(B, T, True)
-        c_up = ws["c_up"]
-        c_up.zero_()                              # the pad rows of every item: what the padded decoder reads there, and zero gradient back
-        ups = [xc if g.conv_in else None]
-        stage = 0
-        for ln in tp.ups.launches:
-            if ln.kind == "conv_in":
-                y = torch.empty(g.Cc, ln.out_pitch, dtype=torch.float32, device=dev)
-                w = self.eff[self.lay.off("wavenet.upsample_net.conv_in.weight"):]
-                L.check(lib.wae_enc_conv_fwd_list(L.ptr(xc), L.ptr(w), None, L.ptr(y), L.ptr(t_ups[ln.seg_off:]), ln.nsegs,
-                                                  L.ptr(t_ups[ln.tile_off:]), ln.ntiles, ln.et, ln.in_pitch, ln.out_pitch, g.Cc, g.Cc,
-                                                  ln.s, 1, 0, 0, 0, st), "conv_in (list)")
-            else:
-                assert ln.kind in ("stage", "last"), ln.kind
-                last = ln.kind == "last"
-                ups.append(xc)
-                w = self.eff[self.lay.off(P.up_stage_name(g, stage) + ".weight_v"):]
-                stage += 1
-                y = c_up if last else torch.empty(g.Cc, ln.out_pitch, dtype=torch.float32, device=dev)
-                L.check(lib.wae_upsample_stage_fwd_list(L.ptr(xc), L.ptr(w), L.ptr(y), L.ptr(t_ups[ln.seg_off:]), ln.nsegs, ln.ntiles,
-                                                        ln.in_pitch, B * T if last else ln.out_pitch, g.Cc, ln.s, int(last), g.Ccp,
-                                                        self.dt, st), "upsample_stage (list)")
-            xc = y
-        fe["up_acts"] = ups
-        kw = dict(layer_events=self._layer_events) if not g.scalar_input else {}
-        out = self.decoder_forward(x, None, gid, targets, lengths, want_logits, True, c_is_upsampled=True, saved=sv, c_ready=True, **kw)
-        if stats is not None:
-            out.update(latents=sv.lat, quant=sv.quant, idx=sv.idx, vq_loss=stats[0], perp=stats[1])
-        return out
-
-    def _clip_adam_ema(self, grads, summed, lr, betas, eps, weight_decay, clip_thresh, ema_decay):
-        """clip_grad_norm_ + Adam + EMA on the finished gradients (csrc/loss.hip).  summed: the gather passes of the backward
-        (csrc/grad_finish.hip) summed the squares of every gradient while they wrote it, into an accumulator that the packing launch
-        had cleared -- no fill and no pass over the arena for the norm.  Deterministic mode: the pass over the arena with per-workgroup
-        partials added in index order."""
-        tail = (self.opt_step, lr, betas[0], betas[1], eps, weight_decay, clip_thresh, ema_decay, self.stream())
-        head = (L.ptr(self.params), L.ptr(grads), L.ptr(self.exp_avg), L.ptr(self.exp_avg_sq), L.ptr(self.shadow), self.lay.total)
-        if self.opt.deterministic:
-            parts = self.det_buffer("norm", 1025, torch.float64)
-            L.check(self.lib.wae_clip_adam_ema_det(*head, L.ptr(parts), parts.numel(), L.ptr(self.grad_norm), *tail), "clip_adam_ema_det")
-        elif summed:
-            L.check(self.lib.wae_clip_adam_ema_summed(*head, L.ptr(self.gn_acc), L.ptr(self.grad_norm), *tail), "clip_adam_ema_summed")
-        else:
-            L.check(self.lib.wae_clip_adam_ema(*head, L.ptr(self.opt_scratch), L.ptr(self.grad_norm), *tail), "clip_adam_ema")
-        self.flight.norm_summed = False
+        return TR.train_step_list(self, items, (lr, betas, eps, weight_decay, clip_thresh, ema_decay), beta, grad_hook,
+                                  (quantize_channels, log_scale_min), max_rows, grad_sync)
 
     # ------------------------------------------------------------------ gradient accumulation: micro-batches into one optimizer step
     def latent_elements(self, B: int, frames: int) -> int:
         """Elements of the latents the encoder makes of (B, c_in, frames) features -- what one micro-batch's vq_loss is a mean over
         (distributed.accum_weights); 0 without an encoder."""
-        if not self.g.has_encoder:
-            return 0
-        Tq = int(frames)
-        for k, s in P.ENCODER_BLOCKS:
-            Tq = (Tq + 2 * (k // 2) - k) // s + 1
-        return int(B) * self.g.Cc * Tq
+        return int(B) * self.g.Cc * P.enc_ready(frames, True) if self.g.has_encoder else 0
 
     def accumulate(self, x, c, gid, lengths=None, *, ce_weight: float = 1.0, vq_weight: float = 1.0, quantize_channels: int = 65536,
                    log_scale_min: float = -7.0, ce_count: Optional[float] = None):
@@ -1925,66 +1312,7 @@ class WaeEngine:
         Deferred finishing (backward.decoder_backward): the first micro-batch packs the weights and clears the accumulators; later
         ones skip both; every one runs the sweep, the weight-gradient launches, the consuming zb chain and the front end's backward;
         nothing is scattered, finished or applied before apply_step."""
-        from . import backward as BW
-        self._refuse_accum_vq()
-        if self.flight.accum is not None:
-            raise RuntimeError("accumulate() inside accumulate()")
-        g = self.g
-        B, T = x.shape
-        kind = BW.window_kind(self, B, T)
-        win = self.window
-        if win is not None and win.n and win.static != kind:
-            raise ValueError(f"accumulate: a ({B}, {T}) micro-batch takes {'the static' if kind else 'another'} weight-gradient launch "
-                             "than the window's earlier ones, whose tiles the one finish reads: keep B <= 32 (and clips of one size "
-                             "class) within a window, or close it with apply_step() first")
-        if self.exp_avg is None:
-            self.init_optimizer()
-        early = False
-        if win is None:
-            if self.weights_dirty:
-                self.prepare_weights(side=True)
-                early = self._ev_wn is not None
-            dev = self.device
-            win = self.window = Window(sums=torch.zeros(3, dtype=torch.float64, device=dev),
-                                       counts=torch.zeros(g.K, dtype=torch.int32, device=dev) if g.has_encoder else None,
-                                       drop_calls=self.drop_calls)
-        if not g.scalar_input and x.dtype != torch.int32:
-            x = x.to(self.device, torch.int32).contiguous()
-        if gid is not None and gid.dtype != torch.int32:
-            gid = gid.to(self.device, torch.int32).contiguous()
-        if early:       # as train_step: the backward's packing (+ the clearing of the accumulators) beside the forward's, on the side stream
-            with self.branch(1, after=self._ev_wn) as self.flight.early_pack:
-                BW.pack_bwd_weights(self)
-        factor = None if ce_count is None else self.grad_scale / float(ce_count)
-        self.flight.accum = win
-        try:
-            if g.scalar_input:
-                fwd = self.forward if g.has_encoder else self.decoder_forward
-                out = fwd(x, c, gid, targets=None, lengths=None, want_logits=True, train=True)
-                loss, dyt = self.scalar_loss_and_grad(out["logits"], x, lengths, quantize_channels, log_scale_min, scale=ce_weight,
-                                                      factor=factor)
-                out["loss"] = loss
-                self.backward(x, gid, None, lengths, ext_dy=dyt, vq_scale=vq_weight)
-            else:
-                fwd = self.forward if g.has_encoder else self.decoder_forward
-                out = fwd(x, c, gid, targets=x, lengths=lengths, want_logits=False, train=True)
-                self.backward(x, gid, x, lengths, loss_scale=ce_weight, vq_scale=vq_weight, dy_factor=factor)
-        except BaseException:
-            # a refused input ended the micro-batch half-way: what it added cannot be told from the rest, so the window goes with it
-            self.join(self.flight.abandon())
-            self.discard_step()
-            raise
-        finally:
-            self.flight.accum = None
-        hist = self._vq_hist if g.has_encoder else None
-        L.check(self.lib.wae_accum_stats(L.ptr(win.sums), L.ptr(win.counts), g.K if g.has_encoder else 0, L.ptr(out["loss"]),
-                                         float(ce_weight), L.ptr(out["vq_loss"]) if g.has_encoder else None, float(vq_weight),
-                                         L.ptr(hist), None, self.stream()), "accum_stats")
-        win.n += 1
-        res = dict(ce=out["loss"])
-        if g.has_encoder:
-            res.update(vq_loss=out["vq_loss"], perp=out["perp"])
-        return res
+        return TR.accumulate(self, x, c, gid, lengths, ce_weight, vq_weight, (quantize_channels, log_scale_min), ce_count)
 
     def apply_step(self, lr: float = 4e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                    clip_thresh: float = 100.0, ema_decay: float = 0.9999, grad_hook=None, grad_sync=None):
@@ -1994,44 +1322,12 @@ class WaeEngine:
         by one.  Returns dict(loss, ce, grad_norm, micro_batches) and, with an encoder, vq_loss and perp -- 0-d device tensors but
         micro_batches: ce = sum ce_weight_i ce_i, vq_loss = sum vq_weight_i vq_loss_i, loss = ce + vq_loss, perp = the perplexity of
         the micro-batches' code counts added per code (score_list's convention: the concatenated batch's perplexity)."""
-        from . import backward as BW
-        self._refuse_grad_sync(grad_sync)
-        win = self.window
-        if win is None or win.n == 0:
-            raise RuntimeError("apply_step without an open accumulation window: accumulate() at least one micro-batch first "
-                               "(or use train_step for a step of one batch)")
-        grads = BW.finish_window(self, win, grad_sync)
-        if grad_sync is not None:
-            grad_sync.finish()
-        if grad_hook is not None:
-            grad_hook(grads)
-        out = torch.empty(5, dtype=torch.float32, device=self.device)
-        L.check(self.lib.wae_accum_stats(L.ptr(win.sums), L.ptr(win.counts), self.g.K if win.counts is not None else 0, None, 0.0, None,
-                                         0.0, None, L.ptr(out), self.stream()), "accum_stats (close)")
-        self.opt_step += 1
-        self._clip_adam_ema(grads, self.flight.norm_summed and grad_sync is None and grad_hook is None, lr, betas, eps, weight_decay,
-                            clip_thresh, ema_decay)
-        self.window = None
-        self.weights_dirty = True
-        self.hold("window", win.sums, win.counts)
-        res = dict(ce=out[0], grad_norm=self.grad_norm[0], micro_batches=win.n)
-        if self.g.has_encoder:
-            res.update(vq_loss=out[1], perp=out[3], loss=out[2])
-        else:
-            res["loss"] = out[0]
-        return res
+        return TR.apply_step(self, (lr, betas, eps, weight_decay, clip_thresh, ema_decay), grad_hook, grad_sync)
 
     def discard_step(self):
         """Drops an open accumulation window: the accumulators are cleared, the dropout counter goes back to where the window opened,
         nothing of its micro-batches reaches the gradients or the optimizer.  Without an open window: nothing."""
-        win, self.window = self.window, None
-        if win is None:
-            return
-        for t in (self.d_eff, self.cbuf, self.gn_acc):
-            t.zero_()
-        self.drop_calls = win.drop_calls
-        self.saved = None
-        self.flight.reset()
+        TR.discard_step(self)
 
     def train_step_accum(self, batches, lr: float = 4e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                          clip_thresh: float = 100.0, ema_decay: float = 0.9999, grad_hook=None, quantize_channels: int = 65536,
@@ -2041,23 +1337,5 @@ class WaeEngine:
         micro-batches share T; where they do not (each padded to its own longest clip) it is the step on the global masked mean over
         all loss positions and the mean over all latent elements.  grad_sync: the ranks meet once for the window's count and once in
         apply_step.  ce_scale: one more factor on the CE term.  Returns apply_step's dict."""
-        from . import distributed as DS
-        batches = list(batches)
-        if not batches:
-            raise ValueError("train_step_accum: no micro-batches")
-        self._refuse_in_window("train_step_accum")
-        self._refuse_accum_vq()
-        self._refuse_grad_sync(grad_sync)
-        metas = []
-        for x, c, gid, lengths in batches:
-            frames = c.shape[-1] if (c is not None and self.g.has_encoder) else 0
-            metas.append((x.shape[0], x.shape[1], lengths, self.latent_elements(x.shape[0], frames)))
-        world = grad_sync.world if grad_sync is not None else 1
-        weights, n_tot = DS.accum_weights(metas, world=world, group=getattr(grad_sync, "group", None))
-        # the count that divides this rank's summed CE gradient: N / world (the rank mean follows), over ce_scale
-        ce_count = n_tot / (world * float(ce_scale)) if (n_tot > 0 and ce_scale) else None
-        for (x, c, gid, lengths), (wc, wv) in zip(batches, weights):
-            self.accumulate(x, c, gid, lengths, ce_weight=wc * float(ce_scale), vq_weight=wv, quantize_channels=quantize_channels,
-                            log_scale_min=log_scale_min, ce_count=ce_count)
-        return self.apply_step(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip_thresh=clip_thresh, ema_decay=ema_decay,
-                               grad_hook=grad_hook, grad_sync=grad_sync)
+        return TR.train_step_accum(self, batches, (lr, betas, eps, weight_decay, clip_thresh, ema_decay), grad_hook,
+                                   (quantize_channels, log_scale_min), grad_sync, ce_scale)

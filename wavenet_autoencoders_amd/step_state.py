@@ -11,6 +11,16 @@ import torch
 
 
 @dataclasses.dataclass
+class ListFrontEnd:
+    """What the LIST front end of a ragged step's forward (frontend.train_list_front) leaves for backward.frontend_backward_list, in
+    place of Saved.up_acts / enc_acts; Saved.lat / quant / idx are then the packed (1, Cc, sum Tq_i) arrays."""
+    plan: object                                # packing.TrainListPlan
+    tables: tuple                               # the device tables (enc | None, ups, bwd)
+    enc_acts: Optional[list] = None             # the packed input of every encoder layer (the blocks, then lin)
+    up_acts: Optional[list] = None              # [conv_in's packed input | None, every stage's packed input]
+
+
+@dataclasses.dataclass
 class Saved:
     """What ONE train-mode forward leaves for its backward beside the activations in the engine's (B, T, True) workspace.  Only a
     train-mode decoder_forward / forward -- and the stand-alone layer's train-mode run -- replaces WaeEngine.saved, each with a new
@@ -28,11 +38,7 @@ class Saved:
     quant: Optional[torch.Tensor] = None
     idx: Optional[torch.Tensor] = None
     beta: float = 0.25
-    # the LIST front end of a ragged step (WaeEngine.train_step_list), in place of up_acts / enc_acts: dict(plan: packing.TrainListPlan,
-    # tables: the device tables (enc, ups, bwd), enc_acts: the packed input of every encoder layer then the latents' producer's input,
-    # up_acts: [conv_in's packed input | None, every stage's packed input]); lat / quant / idx are then the packed (1, Cc, sum Tq_i)
-    # arrays.  None: a dense forward.
-    list_fe: Optional[dict] = None
+    list_fe: Optional[ListFrontEnd] = None      # the LIST front end of a ragged step (WaeEngine.train_step_list); None: a dense forward
 
 
 @dataclasses.dataclass
