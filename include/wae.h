@@ -583,6 +583,20 @@ int wae_head_bwd(const wae_head_desc* d, const void* h0, const void* h1, const v
                  const float* lse, const int32_t* target, const int32_t* lengths, float inv_count, const void* ext_dy,
                  void* dy_out, void* dh1_out, void* dskip_out, void* stream);
 int64_t wae_head_bwd_packed_bytes(const wae_head_desc* d);
+/* The training head in one launch (csrc/head_train.hip): wae_head_fwd_from_h0 with h1_save, the masked mean of its nll and wae_head_bwd
+ * in CE mode, for 16-bit storage with Sp == Op in {128, 256} (wae_head_train_supported; anything else: WAE_EINVAL).  The logits stay in
+ * registers between the forward's GEMM 2 and the softmax gradient, and the relu masks are kept as bits: one GEMM and two reloads less
+ * than the two launches.  w_tail as for wae_head_fwd_from_h0; w_bwd_packed as for wae_head_bwd (its first-order W3 chunks are skipped).
+ * dy_factor is wae_head_bwd's inv_count.  nll and lse (lse may be NULL) are bit for bit wae_head_fwd_from_h0's; dy / dh1 / dskip add the
+ * same products as wae_head_bwd with the dy operand taken from the accumulators.  loss[0] = sum_{b, t < len[b]-1} nll / count and
+ * loss[1] = count as wae_masked_mean writes them: per-workgroup partials in double, summed in index order by the workgroup that finishes
+ * last, so the value does not depend on the order of arrival.  red_ws: wae_head_train_ws_bytes(d) bytes of device memory whose first
+ * 16 are ZERO before the first launch (the launch leaves them zero); one launch at a time per red_ws. */
+int wae_head_train_supported(int32_t dtype, int32_t Sp, int32_t Op);
+int64_t wae_head_train_ws_bytes(const wae_head_desc* d);
+int wae_head_train_from_h0(const wae_head_desc* d, const void* h0, const void* w_tail, const void* w_bwd_packed, const float* bias,
+                           const int32_t* target, const int32_t* lengths, float dy_factor, float* nll, float* lse, void* h1_save,
+                           void* dy_out, void* dh1_out, void* dskip_out, void* red_ws, float* loss, void* stream);
 int64_t wae_head_packed_bytes(const wae_head_desc* d);
 
 /* out[i] = sum_{l<L} src[off + l*stride + i] for i < n, 0 for n <= i < n_pad  (sum of the skip biases) */

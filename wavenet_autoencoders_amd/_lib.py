@@ -200,6 +200,10 @@ SIGNATURES = {
     "wae_head_fwd_from_h0": (c_i32, [ctypes.POINTER(HeadDesc)] + [c_vp] * 9),
     "wae_head_bwd": (c_i32, [ctypes.POINTER(HeadDesc)] + [c_vp] * 7 + [c_f32] + [c_vp] * 5),
     "wae_head_bwd_packed_bytes": (c_i64, [ctypes.POINTER(HeadDesc)]),
+    "wae_head_train_supported": (c_i32, [c_i32, c_i32, c_i32]),
+    "wae_head_train_ws_bytes": (c_i64, [ctypes.POINTER(HeadDesc)]),
+    # d, h0, w_tail, w_bwd_packed, bias, target, lengths, dy_factor, nll, lse, h1_save, dy, dh1, dskip, red_ws, loss, stream
+    "wae_head_train_from_h0": (c_i32, [ctypes.POINTER(HeadDesc)] + [c_vp] * 6 + [c_f32] + [c_vp] * 9),
     "wae_gemm_tm": (c_i32, [ctypes.POINTER(TmDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp]),
     "wae_gemm_tm_ce": (c_i32, [ctypes.POINTER(TmDesc), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, ctypes.POINTER(TmCe), c_vp]),
     "wae_gemm_tn_tiles": (c_i32, [c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),

@@ -1101,8 +1101,42 @@ def _tn_behind_sweep(cx, sched, grad_sync):
         _hand_over(cx, grad_sync, *seg)
 
 
-def _head_backward(cx, xi, tg, ln, inv_count, ext_dy):
-    """dy, dh1, dskip; the head's tile launch and the first conv's one-hot operand where the static launch does not carry them"""
+def head_dy_factor(eng, B, T, lengths, loss_scale=1.0, dy_factor=None):
+    """The factor on d loss / d logits of a (B, T) batch's masked cross-entropy: dy_factor where given (a window's micro-batch), else
+    loss_scale * grad_scale / count over the shifted steps inside `lengths` (None: all).  ONE expression for train.step_run, which
+    announces it to the forward's fused head, and decoder_backward, which skips wae_head_bwd where the two agree."""
+    if dy_factor is not None:
+        return dy_factor
+    if lengths is None:
+        count = B * (T - 1)
+    else:
+        count = int(torch.clamp(lengths.detach().to("cpu", torch.int64).clamp(max=T) - 1, min=0).sum())
+    return loss_scale * eng.grad_scale / max(count, 1)
+
+
+def head_fused_ok(eng) -> bool:
+    """Does this engine have the one-launch training head (csrc/head_train.hip)?  16-bit split heads with Sp == Op."""
+    g = eng.g
+    return bool(eng.opt.head_fused and eng.split_head and not eng.wide_head and not g.scalar_input
+                and eng.lib.wae_head_train_supported(eng.dt, g.Sp, g.Op))
+
+
+def early_onehot(eng, x):
+    """The first conv's one-hot operand depends on the ids alone: train.step_open writes it behind the backward's weight packing on
+    that launch's side stream (decoder_backward waits for both at once) where the fused head has taken the launches around it off the
+    main stream.  ws: the (B, T) backward workspace, made by the caller on the main stream."""
+    B, T = x.shape
+    ws = eng._ws.get(("bwd", B, T))
+    if ws is None or ws["onehot"] is None:
+        return
+    L.check(eng.lib.wae_onehot_rows(L.ptr(x), L.ptr(ws["onehot"]), B * T, ws["onehot"].shape[-1], eng.dt, eng.stream()), "onehot_rows")
+    eng.flight.onehot_early = (x.data_ptr(), B, T)
+    eng.hold("onehot_early", x)
+
+
+def _head_backward(cx, xi, tg, ln, inv_count, ext_dy, done=False):
+    """dy, dh1, dskip (done: the forward's fused head launch wrote them); the head's tile launch and the first conv's one-hot operand
+    where the static launch does not carry them"""
     eng, g, lib, ws, fw, B, T, st = cx.eng, cx.eng.g, cx.eng.lib, cx.ws, cx.fw, cx.B, cx.T, cx.eng.stream()
     b3 = ctypes.c_void_p(eng.b_head.data_ptr() + 2 * g.Sp * 4)
     if eng.wide_head:
@@ -1117,7 +1151,7 @@ def _head_backward(cx, xi, tg, ln, inv_count, ext_dy):
             g.Sp, fw["h1"].data_ptr(), g.Sp)
         _tm(eng, B, T, g.Sp, 4, math.sqrt(1.0 / g.layers), [(ws["dh1"].data_ptr(), g.Sp, g.Sp, 0)], eng.w_hwide["w1t"].data_ptr(),
             ws["dskip"].data_ptr(), g.Sp, fw["h0"].data_ptr(), g.Sp)
-    else:
+    elif not done:
         hd = L.HeadDesc(eng.dt, B, T, g.Ku, g.Sp, g.Op, g.O, math.sqrt(1.0 / g.layers))
         L.check(lib.wae_head_bwd(ctypes.byref(hd), L.ptr(fw["h0"]), L.ptr(fw["h1"]), L.ptr(eng.w_hb), b3, L.ptr(fw["lse"]), L.ptr(tg),
                                  L.ptr(ln), inv_count, L.ptr(ext_dy), L.ptr(ws["dy"]), L.ptr(ws["dh1"]), L.ptr(ws["dskip"]), st),
@@ -1126,7 +1160,8 @@ def _head_backward(cx, xi, tg, ln, inv_count, ext_dy):
             ws["dy"].copy_(ext_dy)                # the tile table points at ws["dy"]
     if ws["tt_head"] is not None:
         ws["tt_head"].launch(B, T)
-    if ws["onehot"] is not None:        # operand of the first conv's weight gradient (a job of the stream launch)
+    early, eng.flight.onehot_early = eng.flight.onehot_early, None
+    if ws["onehot"] is not None and early != (xi.data_ptr(), B, T):        # operand of the first conv's weight gradient (a job of the stream launch)
         L.check(lib.wae_onehot_rows(L.ptr(xi), L.ptr(ws["onehot"]), B * T, ws["onehot"].shape[-1], eng.dt, st), "onehot_rows")
 
 
@@ -1190,14 +1225,13 @@ def decoder_backward(eng, x_ids: torch.Tensor, targets: torch.Tensor, lengths: O
         _await_packed_weights(eng)
     cx = _step(eng, B, T, sv.drop_seeds)
     ws = cx.ws
-    if lengths is None:
-        count = B * (T - 1)
-    else:
-        count = int(torch.clamp(lengths.detach().to("cpu", torch.int64).clamp(max=T) - 1, min=0).sum())
+    factor = head_dy_factor(eng, B, T, lengths, loss_scale, dy_factor)
     xi = x_ids.to(torch.int32).contiguous() if not g.scalar_input else None
     tg = targets.to(torch.int32).contiguous() if targets is not None else None
     ln = lengths.to(torch.int32).to(eng.device).contiguous() if lengths is not None else None
-    _head_backward(cx, xi, tg, ln, loss_scale * eng.grad_scale / max(count, 1) if dy_factor is None else dy_factor, ext_dy)
+    # (the forward's fused head ran the head's backward with the factor train.step_run announced: nothing to launch where it is this one)
+    done = ext_dy is None and sv.head_done is not None and sv.head_done.serves(factor, targets, lengths)
+    _head_backward(cx, xi, tg, ln, factor, ext_dy, done)
     cx.use_gid = gid is not None and "wavenet.embed_speakers.weight" in eng.lay.offsets
     cx.gid32 = gid.to(torch.int32).contiguous() if gid is not None else None
     cx.gvec = gvec

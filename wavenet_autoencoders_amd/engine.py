@@ -25,7 +25,7 @@ from . import train as TR
 from .decode import DecodeSession  # noqa: F401  (re-exported)
 from .encode import EncodeSession
 from .options import two_chains
-from .step_state import InFlight, Saved, Window
+from .step_state import HeadDone, InFlight, Saved, Window
 
 
 def _dt(dtype) -> int:
@@ -618,20 +618,28 @@ class WaeEngine:
         tg = targets.to(torch.int32).contiguous() if targets is not None else None
         if tg is not None and tg.data_ptr() != (xi.data_ptr() if not g.scalar_input else 0):   # targets = inputs: already checked
             L.check(lib.wae_check_ids(L.ptr(tg), B * T, 0, g.O, L.ptr(self.err), L.ERR_TARGET_ID, st), "check targets")
-        self._head_fwd(ws, B, T, logits, tg, train)
+        ln = lengths.to(self.device, torch.int32).contiguous() if (tg is not None and lengths is not None) else None
+        # (a train step announced the factor of its backward: the head's launch may run the head's backward and the loss mean with it)
+        factor = self.flight.take_head_factor()
+        fused = self._head_fwd(ws, B, T, logits, tg, train, ln, factor if train else None)
+        if fused:
+            sv.head_done = HeadDone(factor, targets, lengths)
         out = dict(logits=logits, nll=None, loss=None)
         if tg is not None:
-            ln = lengths.to(self.device, torch.int32).contiguous() if lengths is not None else None
-            TR.masked_mean(self, ws["nll"], ln, ws["loss"])
+            if not fused:
+                TR.masked_mean(self, ws["nll"], ln, ws["loss"])
             out["nll"] = ws["nll"]
             out["loss"] = ws["loss"][0]
         if train:
             self.saved = sv
         return out
 
-    def _head_fwd(self, ws, B, T, logits, tg, train):
+    def _head_fwd(self, ws, B, T, logits, tg, train, ln=None, factor=None) -> bool:
         """wavenet.py:204-214 (+ the shifted CE against tg) on the (B, T) rows of ws["u"]: the head this engine runs -- wide, split or
-        the one kernel; ws holds u and, where that head passes them through memory, h0 / h1, nll and lse."""
+        the one kernel; ws holds u and, where that head passes them through memory, h0 / h1, nll and lse.
+        factor (with ln, the int32 device lengths): the factor on d loss / d logits that the caller's backward will use.  A split 16-bit
+        head with Sp == Op in train mode then runs ONE launch from h0 (csrc/head_train.hip; EngineOptions.head_fused) that also writes
+        ws["loss"] -- the masked mean -- and dy, dh1, dskip of the (B, T) backward workspace: -> True, and the caller records it."""
         g, lib, st = self.g, self.lib, self.stream()
         hd = L.HeadDesc(self.dt, B, T, g.Ku, g.Sp, g.Op, g.O, math.sqrt(1.0 / g.layers))
         if self.wide_head:
@@ -645,6 +653,16 @@ class WaeEngine:
                    ws["h0"].data_ptr(), g.Sp, self.b_head.data_ptr(), 0)
             ck = 64 if es == 2 else 32
             tail = self.w_head.data_ptr() + (g.Ku // ck) * (g.Sp // 32) * 4096
+            if factor is not None and train and tg is not None and logits is None and BW.head_fused_ok(self) and self._bwd_weights_coming():
+                bws = BW.bwd_workspace(self, B, T)
+                red = ws.get("head_red")
+                if red is None:
+                    red = ws["head_red"] = torch.zeros(int(lib.wae_head_train_ws_bytes(ctypes.byref(hd))), dtype=torch.uint8, device=self.device)
+                L.check(lib.wae_head_train_from_h0(ctypes.byref(hd), L.ptr(ws["h0"]), ctypes.c_void_p(tail), L.ptr(self.w_hb), L.ptr(self.b_head),
+                                                   L.ptr(tg), L.ptr(ln), float(factor), L.ptr(ws["nll"]), L.ptr(ws["lse"]), L.ptr(ws["h1"]),
+                                                   L.ptr(bws["dy"]), L.ptr(bws["dh1"]), L.ptr(bws["dskip"]), L.ptr(red), L.ptr(ws["loss"]), st),
+                        "head (train, from h0)")
+                return True
             L.check(lib.wae_head_fwd_from_h0(ctypes.byref(hd), L.ptr(ws["h0"]), ctypes.c_void_p(tail), L.ptr(self.b_head), L.ptr(logits),
                                              L.ptr(tg), L.ptr(ws["nll"]) if tg is not None else None,
                                              L.ptr(ws["lse"]) if (train and tg is not None) else None,
@@ -654,6 +672,18 @@ class WaeEngine:
                                      L.ptr(tg), L.ptr(ws["nll"]) if tg is not None else None,
                                      L.ptr(ws["lse"]) if (train and tg is not None) else None,
                                      L.ptr(ws["h0"]) if train else None, L.ptr(ws["h1"]) if train else None, st), "head")
+        return False
+
+    def _bwd_weights_coming(self) -> bool:
+        """The fused training head reads the backward's packed head weights during the forward.  True where they are this step's: the
+        step's early packing (train.step_open) is in flight -- the current stream then waits for it here; decoder_backward still takes
+        the event -- or an accumulation window's earlier micro-batch packed them for these same weights."""
+        box = self.flight.early_pack
+        if box is not None and box[0] is not None:
+            self.join(box[0])
+            return True
+        win = self.flight.accum
+        return win is not None and win.n > 0
 
     def _head_fwd_wide(self, ws, B, T, logits, tg, train):
         """wavenet.py:204-214 (+ the shifted CE of vqwae_train.py:363-379,:764) for skip widths above 256: three launches of

@@ -35,6 +35,10 @@ The newest switch (its flip is checked in tests/test_grad_finish_host.py; bench.
                                      pass over the arena for the norm) instead of the gather pass behind the weight-gradient launch
                                      (csrc/grad_finish.hip; backward.py: _finish_plan says where the gather pass applies)
 
+  WAE_HEAD_FUSED           1         0: the training head as its launches -- head forward from h0, masked mean, head backward -- instead of
+                                     the one launch that goes from h0 to the loss, dy, dh1 and dskip (csrc/head_train.hip; 16-bit split
+                                     heads with Sp == Op inside a train step: engine._head_fwd says where it applies)
+
 The reproducible train step (opt-in; flips and repeats are checked in tests/test_deterministic_cpu.py and
 tests/test_gpu_deterministic.py):
   WAE_DETERMINISTIC        0         1: every float sum of a train step that more than one workgroup feeds is formed in a fixed order:
@@ -71,6 +75,7 @@ class EngineOptions:
     bwd_fused: str = "auto"
     bwd_fold_dc: bool = True
     grad_finish: bool = True
+    head_fused: bool = True
     chains: str = "auto"
     side: bool = True
     deterministic: bool = False
@@ -101,6 +106,7 @@ class EngineOptions:
                              head_wide=e("WAE_HEAD_WIDE", "0") == "1", glu_pair=pair, dp_split=e("WAE_DP_SPLIT", "1") != "0",
                              ar_coop=e("WAE_AR_COOP", "1") != "0", ar_coop_c=int(e("WAE_AR_COOP_C", "32")),
                              bwd_fused=fused, bwd_fold_dc=e("WAE_BWD_FOLD_DC", "1") != "0", grad_finish=e("WAE_GRAD_FINISH", "1") != "0",
+                             head_fused=e("WAE_HEAD_FUSED", "1") != "0",
                              deterministic=e("WAE_DETERMINISTIC", "0") == "1")
 
 

@@ -21,6 +21,18 @@ class ListFrontEnd:
 
 
 @dataclasses.dataclass
+class HeadDone:
+    """The head's backward as the fused forward launch ran it: the factor on d loss / d logits, and the targets and lengths it masked
+    with.  backward.decoder_backward skips wae_head_bwd only for the same three."""
+    factor: float
+    targets: object                             # the caller's targets and lengths objects themselves (lengths None: every step counts)
+    lengths: object
+
+    def serves(self, factor, targets, lengths) -> bool:
+        return self.factor == factor and self.targets is targets and self.lengths is lengths
+
+
+@dataclasses.dataclass
 class Saved:
     """What ONE train-mode forward leaves for its backward beside the activations in the engine's (B, T, True) workspace.  Only a
     train-mode decoder_forward / forward -- and the stand-alone layer's train-mode run -- replaces WaeEngine.saved, each with a new
@@ -39,6 +51,7 @@ class Saved:
     idx: Optional[torch.Tensor] = None
     beta: float = 0.25
     list_fe: Optional[ListFrontEnd] = None      # the LIST front end of a ragged step (WaeEngine.train_step_list); None: a dense forward
+    head_done: Optional["HeadDone"] = None      # the forward's head launch already wrote dy, dh1 and dskip (csrc/head_train.hip)
 
 
 @dataclasses.dataclass
@@ -58,6 +71,9 @@ class InFlight:
     forward's / the backward's weight packing on a side stream, each taken once by the phase that waits for it; ev_dc: recorded where
     the conditioning gradient is complete; grads_done: the arena slice decoder_backward finished itself; finish_used: the FinishPlan
     that did; norm_summed: the gather passes summed the squared norm.
+    head_factor: the factor on d loss / d logits that the step's backward will use, announced by train.step_run before the forward and
+    taken by the forward's head (engine._head_fwd: the fused training head); onehot_early: (ids address, B, T) of the one-hot rows that
+    step_open already wrote on the packing's side stream.
     accum: the Window this backward adds a micro-batch to -- the accumulate-mode switch of decoder_backward (deferred finishing:
     no clearing from the second micro-batch on, nothing scattered, nothing written to the gradient arena); None: a plain step."""
 
@@ -69,6 +85,7 @@ class InFlight:
         self.grads_done = self.finish_used = None
         self.norm_summed = False
         self.accum = None
+        self.head_factor = self.onehot_early = None
 
     def abandon(self):
         """A refused input ended the step half-way: nothing of it may be taken for the next call's.  -> the event of the forward's
@@ -80,6 +97,10 @@ class InFlight:
     def take_pack_done(self):
         box, self.pack_done = self.pack_done, None
         return box[0] if box else None
+
+    def take_head_factor(self):
+        f, self.head_factor = self.head_factor, None
+        return f
 
     def take_early_pack(self):
         box, self.early_pack = self.early_pack, None
