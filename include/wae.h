@@ -414,6 +414,13 @@ int wae_accum_stats(double* sums, int32_t* counts, int32_t K, const float* ce, d
  * wae_upsample_stage_bwd_det: wae_upsample_stage_bwd; din as there; the FIR's weight gradient: block i of the nbw = min(B * C, 256)
  *   weight blocks stores its 2s+1 tap sums to parts[i][tap] (wae_upsample_stage_bwd_det_floats() floats); one workgroup adds, per tap,
  *   the blocks 0 .. nbw-1 in order (from block 0's sum) and then dw[tap] = dw[tap] + sum.
+ * wae_upsample_stage_bwd_list_det: wae_upsample_stage_bwd_list (the arguments, the table and the refusals of that entry; further down
+ *   in this file); din as there; the FIR's weight gradient: workgroup i of the grid = min(ntiles, 512) workgroups walks the tiles
+ *   i, i + grid, ... in that order, forms its 2s+1 tap sums as the default twin does (per thread over its tiles and channels, a xor
+ *   butterfly over the 64 lanes, the four waves added in wave order) and stores them to parts[i][tap], rows of 33 floats
+ *   (wae_upsample_stage_bwd_list_det_floats() = 512 * 33 floats); one workgroup, thread = tap, adds parts[0 .. grid-1][tap] in index
+ *   order from zero and then dw[tap] = dw[tap] + sum.  A workgroup whose records were all refused stores zeros.  The result depends
+ *   on the table's order (which tiles a workgroup walks); din does not.  parts NULL or short: WAE_EINVAL before any launch.
  * wae_vq_slice_bwd_det / wae_vq_bwd_det: wae_vq_slice_bwd / wae_vq_bwd with K, the number of codes; dlat as there; the codebook
  *   gradient by one workgroup per code: the frames in row order b * Tq + t whose idx is the code add -c_emb * (lat - quant) in turn
  *   (from zero), then demb[code] = demb[code] + sum; a code that no frame uses is not written.  D <= 1024.
@@ -431,6 +438,10 @@ int wae_gproj_bwd_det(const float* eff, float* d_eff, int64_t wg_off, int64_t bi
 int64_t wae_upsample_stage_bwd_det_floats(void);
 int wae_upsample_stage_bwd_det(const float* dout, const float* in, const float* w, float* din, float* dw, float* parts,
                                int64_t parts_floats, int32_t B, int32_t C, int32_t Tin, int32_t s, void* stream);
+int64_t wae_upsample_stage_bwd_list_det_floats(void);
+int wae_upsample_stage_bwd_list_det(const float* dout, const float* in, const float* w, float* din, float* dw,
+                                    const wae_ups_seg* segs, int32_t nsegs, int32_t ntiles, int32_t in_pitch, int32_t out_pitch,
+                                    int32_t C, int32_t s, float* parts, int64_t parts_floats, void* stream);
 int wae_vq_slice_bwd_det(const float* lat, const float* quant, const int64_t* idx, const float* dquant, float* dlat,
                          float* demb, int32_t B, int32_t Dtot, int32_t d0, int32_t D, int32_t Tq, int32_t K, float c_lat,
                          float c_emb, void* stream);
@@ -1254,7 +1265,7 @@ int wae_vq_bwd(const float* lat, const float* quant, const int64_t* idx, const f
  *   owns are not written.  WAE_EINVAL: a null pointer, C, nsegs, ntiles, pitch or rows < 1, Cp < C, a bad dtype.
  * wae_upsample_stage_bwd_list, wae_upsample_stage_bwd for every item in one launch: dout (C, out_pitch), item i at the columns
  *   [out_off_i, out_off_i + Tin_i s); in (C, in_pitch) the stage's packed input; din (C, in_pitch) receives the item's columns;
- *   dw[2s+1] += the sum over all items (float atomics).  Records wae_ups_seg + the closing one with tiles of WAE_UPS_LIST_TILE_CT
+ *   dw[2s+1] += the sum over all items (float atomics; wae_upsample_stage_bwd_list_det: in a fixed order).  Records wae_ups_seg + the closing one with tiles of WAE_UPS_LIST_TILE_CT
  *   output columns: the channel-major table of wae_upsample_stage_fwd_list.  WAE_EINVAL: a null pointer, C, s, nsegs, ntiles or a
  *   pitch < 1, s > 16 (as the dense entry).
  * wae_enc_conv_bwd_list, wae_enc_conv_bwd over wae_seg records and the (segment, to0) tile table of wae_enc_conv_fwd_list: x

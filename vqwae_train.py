@@ -19,7 +19,8 @@ options:
     --synthetic                  Train on synthetic batches (no dataset needed).
     --max-steps=<N>              Stop after N steps (overrides max_train_steps).
     --accum-steps=<M>            Loader batches per optimizer step (gradient accumulation) [default: 1].
-    --train-packed               max_time_steps null: train on every batch's utterances unpadded (WaeEngine.train_step_list).
+    --train-packed               max_time_steps null: train on every batch's utterances unpadded (WaeEngine.train_step_list;
+                                 with --accum-steps M or --deterministic: train_step_list_accum).
 
 One process per GPU: launch with ``python -m torch.distributed.run --nproc-per-node N vqwae_train.py ...`` for data
 parallel training (gradients are all-reduced over RCCL; every rank reads its own shard).
@@ -211,8 +212,10 @@ def parse_args(argv=None):
                          "WaeEngine.train_step_list (the list front end in front of the dense decoder) instead of train_step on the "
                          "zero-padded batch, whose pad frames enter the commitment loss and the conditioning of every utterance's end; "
                          "it logs what the padded phase logs.  Every utterance is trimmed to a multiple of 4 feature frames (the "
-                         "encoder's stride) where the dump's are not; one shorter than 4 frames is left out.  One GPU, --accum-steps 1, "
-                         "not with --deterministic.  Length-sorted batches keep the decoder's pad rows low")
+                         "encoder's stride) where the dump's are not; one shorter than 4 frames is left out.  With --accum-steps M the M "
+                         "batches' lists are the groups of one WaeEngine.train_step_list_accum: the step on all their utterances as one "
+                         "list; --deterministic takes the same call (a window of one group at M = 1).  One GPU.  Length-sorted batches "
+                         "keep the decoder's pad rows low")
     ap.add_argument("--deterministic", action="store_true",
                     help="the reproducible train step (WAE_DETERMINISTIC=1, wavenet_autoencoders_amd/options.py): the same weights, batch "
                          "and dropout seed give the same bits, step after step and run after run, on one GPU (not with data parallel)")
@@ -229,6 +232,25 @@ def engine_switches(args):
     if args.deterministic:
         os.environ["WAE_DETERMINISTIC"] = "1"
     return EngineOptions.from_env().pinned()
+
+
+def refuse_combinations(args, hp, geom, world, opt):
+    """The combinations of switches, preset and world size that no train phase covers: raised before an engine exists.  opt: the
+    options that engine will run with (engine_switches)"""
+    if args.accum_steps > 1 and geom.vq != "plain":
+        raise NotImplementedError(f"--accum-steps {args.accum_steps} with hparams quantizer={geom.vq!r}: accumulation windows cover the "
+                                  "plain quantiser (WaeEngine.accumulate)")
+    if args.train_packed:
+        if hp.max_time_steps is not None:
+            raise ValueError(f"--train-packed with max_time_steps = {hp.max_time_steps}: cropped batches have one length; the packed "
+                             "train phase is for presets with max_time_steps null")
+        if world > 1:
+            raise NotImplementedError("--train-packed runs on one GPU (WaeEngine.train_step_list, train_step_list_accum)")
+        if opt.deterministic and geom.vq != "plain":
+            raise NotImplementedError(f"--train-packed --deterministic with hparams quantizer={geom.vq!r}: the reproducible ragged step "
+                                      "is an accumulation window, which covers the plain quantiser (WaeEngine.train_step_list_accum)")
+    if opt.deterministic and world > 1:
+        raise NotImplementedError("--deterministic with data parallel: the all-reduce's order of additions is the collective library's")
 
 
 def main(argv=None):
@@ -249,18 +271,7 @@ def main(argv=None):
 
     from wavenet_autoencoders_amd.engine import WaeEngine
     geom = build_geometry(hp)
-    if args.accum_steps > 1 and geom.vq != "plain":
-        raise NotImplementedError(f"--accum-steps {args.accum_steps} with hparams quantizer={geom.vq!r}: accumulation windows cover the "
-                                  "plain quantiser (WaeEngine.accumulate)")
-    if args.train_packed:
-        if hp.max_time_steps is not None:
-            raise ValueError(f"--train-packed with max_time_steps = {hp.max_time_steps}: cropped batches have one length; the packed "
-                             "train phase is for presets with max_time_steps null")
-        if world > 1 or args.accum_steps > 1 or args.deterministic:
-            raise NotImplementedError("--train-packed runs on one GPU, with --accum-steps 1 and without --deterministic "
-                                      "(WaeEngine.train_step_list)")
-    if engine_switches(args).deterministic and world > 1:
-        raise NotImplementedError("--deterministic with data parallel: the all-reduce's order of additions is the collective library's")
+    refuse_combinations(args, hp, geom, world, engine_switches(args))
     eng = WaeEngine(geom, dtype=args.dtype, device=device, dropout=float(hp.dropout),            # vqwae_train.py:933
                     drop_seed=0x5EED * 4099 + rank)   # replicas draw their own masks
     # reference initialisation, identical on every rank
@@ -324,10 +335,18 @@ def main(argv=None):
                 ln = None if bool((lengths == T).all()) else lengths
                 batches_seen += 1
                 if args.train_packed:
-                    res = eng.train_step_list(packed_items(x, c, g, lengths, hop), lr=lr, betas=adam["betas"], eps=adam["eps"],
-                                              weight_decay=adam["weight_decay"], clip_thresh=hp.clip_thresh, ema_decay=hp.ema_decay,
-                                              quantize_channels=hp.quantize_channels, log_scale_min=hp.log_scale_min)
-                    ce_scale = 1.0
+                    # M loader batches' utterances are the groups of one ragged optimizer step: the step on all of them as one list.
+                    # The deterministic mode's ragged step is the window, of one group at M = 1
+                    kw = dict(lr=lr, betas=adam["betas"], eps=adam["eps"], weight_decay=adam["weight_decay"], clip_thresh=hp.clip_thresh,
+                              ema_decay=hp.ema_decay, quantize_channels=hp.quantize_channels, log_scale_min=hp.log_scale_min)
+                    pending.append(packed_items(x, c, g, lengths, hop))
+                    if len(pending) < accum:
+                        continue
+                    if accum > 1 or eng.opt.deterministic:
+                        res = eng.train_step_list_accum(pending, **kw)
+                    else:
+                        res = eng.train_step_list(pending[0], **kw)
+                    pending, ce_scale = [], 1.0
                 elif accum > 1:
                     # M loader batches are the micro-batches of one optimizer step; its numbers are the window's (apply_step), already
                     # weighted -- the global masked mean over every rank's window, one mask-sum all-reduce per window

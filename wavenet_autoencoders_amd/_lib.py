@@ -215,6 +215,8 @@ SIGNATURES = {
     "wae_gproj_bwd_det": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64] + [c_i32] * 8 + [c_vp, c_i64, c_vp]),
     "wae_upsample_stage_bwd_det_floats": (c_i64, []),
     "wae_upsample_stage_bwd_det": (c_i32, [c_vp] * 6 + [c_i64] + [c_i32] * 4 + [c_vp]),
+    "wae_upsample_stage_bwd_list_det_floats": (c_i64, []),
+    "wae_upsample_stage_bwd_list_det": (c_i32, [c_vp] * 6 + [c_i32] * 6 + [c_vp, c_i64, c_vp]),
     "wae_vq_slice_bwd_det": (c_i32, [c_vp] * 6 + [c_i32] * 6 + [c_f32, c_f32, c_vp]),
     "wae_vq_bwd_det": (c_i32, [c_vp] * 6 + [c_i32] * 4 + [c_f32, c_f32, c_vp]),
     "wae_vq_loss_det": (c_i32, [c_vp] * 3 + [c_i32] * 5 + [c_f32, c_vp]),

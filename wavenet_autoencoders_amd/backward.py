@@ -1528,9 +1528,13 @@ def frontend_backward_list(eng, dc: torch.Tensor, loss_scale: float = 1.0):
         name = P.up_stage_name(g, i) + ".weight_v"
         in_pitch, out_pitch = tp.stage_pitch[i]
         din = torch.empty(g.Cc, in_pitch, dtype=torch.float32, device=dev)
-        L.check(lib.wae_upsample_stage_bwd_list(L.ptr(d), L.ptr(acts[1 + i]), L.ptr(eng.eff[lay.off(name):]), L.ptr(din),
-                                                L.ptr(eng.d_eff[lay.off(name):]), L.ptr(t_bwd[tp.stage_off[i]:]), B, tp.stage_ntiles[i],
-                                                in_pitch, out_pitch, g.Cc, s, st), "upsample_stage_bwd_list")
+        args = (L.ptr(d), L.ptr(acts[1 + i]), L.ptr(eng.eff[lay.off(name):]), L.ptr(din), L.ptr(eng.d_eff[lay.off(name):]),
+                L.ptr(t_bwd[tp.stage_off[i]:]), B, tp.stage_ntiles[i], in_pitch, out_pitch, g.Cc, s)
+        if eng.opt.deterministic:
+            parts = eng.det_buffer("ups_list", int(lib.wae_upsample_stage_bwd_list_det_floats()))
+            L.check(lib.wae_upsample_stage_bwd_list_det(*args, L.ptr(parts), parts.numel(), st), "upsample_stage_bwd_list_det")
+        else:
+            L.check(lib.wae_upsample_stage_bwd_list(*args, st), "upsample_stage_bwd_list")
         d = din
         keep.append(d)
     if g.conv_in:

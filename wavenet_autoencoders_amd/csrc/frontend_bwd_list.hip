@@ -86,10 +86,14 @@ extern "C" int wae_from_btc_list(const void* in, float* out, const wae_ups_seg* 
 // lane + 256 / F, ...  A workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ... (at most UPLB_MAXWG workgroups) and keeps its
 // correlations across them: the tap sums leave as ONE float atomic per tap and workgroup, however many tiles the list has (the dense
 // kernel's bound on the atomics that meet on the 2s+1 addresses; at 32 utterances of hps/vqwae.json it changed no step time).
+// DET (wae_upsample_stage_bwd_list_det): the workgroup leaves its 2s+1 sums in parts[blockIdx.x][tap] with plain stores instead (every
+// workgroup of the launch stores every tap once, a workgroup whose tiles were all refused its zeros: no clearing); a second launch adds
+// the workgroups' sums in index order (ups_list_w_finish_kernel).  The DET launch hands `parts` in as the kernel's dw argument: one
+// argument list for both instantiations.
 #define UPLB_MAXWG 512
 #define UPLB_MAXTAPS 33
 #define UPLB_MAXS 16
-template <int S>
+template <int S, bool DET = false>
 __global__ void __launch_bounds__(256) ups_stage_bwd_list_kernel(const float* __restrict__ dout, const float* __restrict__ in,
                                                                  const float* __restrict__ w, float* __restrict__ din,
                                                                  float* __restrict__ dw, const wae_ups_seg* __restrict__ segs, int nsegs,
@@ -159,8 +163,13 @@ __global__ void __launch_bounds__(256) ups_stage_bwd_list_kernel(const float* __
     }
   }
   __syncthreads();
-  if ((int)threadIdx.x < ntap)
-    atomicAdd(dw + threadIdx.x, part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]);
+  if constexpr (DET) {
+    if ((int)threadIdx.x < ntap)
+      dw[blockIdx.x * UPLB_MAXTAPS + threadIdx.x] = part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+  } else {
+    if ((int)threadIdx.x < ntap)
+      atomicAdd(dw + threadIdx.x, part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]);
+  }
 }
 
 extern "C" int wae_upsample_stage_bwd_list(const float* dout, const float* in, const float* w, float* din, float* dw,
@@ -181,6 +190,49 @@ extern "C" int wae_upsample_stage_bwd_list(const float* dout, const float* in, c
   else WAE_UPLB(0);
 #undef WAE_UPLB
   return wae_check_launch("upsample_stage_bwd_list");
+}
+
+// The fixed-order form of the stage's backward: the same kernel with its tap sums stored to parts[workgroup][tap], and one small launch
+// of one workgroup, thread = tap, that adds parts[0 .. nwg-1][tap] in index order from zero and then dw[tap] = dw[tap] + sum with one
+// plain read-modify-write.  nwg <= UPLB_MAXWG rows of UPLB_MAXTAPS floats (66 KB) do not fit LDS whole: they pass through it in
+// rounds of UPLBF_ROWS rows, coalesced (one thread per tap walking global memory would wait out a load per workgroup).
+#define UPLBF_ROWS 128
+__global__ void __launch_bounds__(256) ups_list_w_finish_kernel(const float* __restrict__ parts, int nwg, int ntap, float* __restrict__ dw) {
+  __shared__ float sp[UPLBF_ROWS * UPLB_MAXTAPS];
+  float v = 0.f;
+  for (int r0 = 0; r0 < nwg; r0 += UPLBF_ROWS) {
+    const int nr = min(UPLBF_ROWS, nwg - r0);
+    __syncthreads();
+    for (int i = threadIdx.x; i < nr * UPLB_MAXTAPS; i += 256) sp[i] = parts[(int64_t)r0 * UPLB_MAXTAPS + i];
+    __syncthreads();
+    if ((int)threadIdx.x < ntap)
+      for (int i = 0; i < nr; ++i) v += sp[i * UPLB_MAXTAPS + threadIdx.x];
+  }
+  if ((int)threadIdx.x < ntap) dw[threadIdx.x] = dw[threadIdx.x] + v;
+}
+extern "C" int64_t wae_upsample_stage_bwd_list_det_floats(void) { return (int64_t)UPLB_MAXWG * UPLB_MAXTAPS; }
+extern "C" int wae_upsample_stage_bwd_list_det(const float* dout, const float* in, const float* w, float* din, float* dw,
+                                               const wae_ups_seg* segs, int32_t nsegs, int32_t ntiles, int32_t in_pitch,
+                                               int32_t out_pitch, int32_t C, int32_t s, float* parts, int64_t parts_floats, void* stream) {
+  WAE_REQUIRE(dout && in && w && din && dw && C > 0 && s > 0, "upsample_stage_bwd_list_det: bad arguments");
+  WAE_REQUIRE(segs && nsegs > 0, "upsample_stage_bwd_list_det: a table of nsegs > 0 records and a closing one (got %d)", nsegs);
+  WAE_REQUIRE(ntiles > 0, "upsample_stage_bwd_list_det: ntiles must be > 0 (got %d)", ntiles);
+  WAE_REQUIRE(in_pitch > 0 && out_pitch > 0, "upsample_stage_bwd_list_det: pitches must be > 0 (got %d, %d)", in_pitch, out_pitch);
+  WAE_REQUIRE(s <= UPLB_MAXS, "upsample_stage_bwd_list_det: scale %d > %d is not supported", s, UPLB_MAXS);
+  WAE_REQUIRE(parts && parts_floats >= (int64_t)UPLB_MAXWG * UPLB_MAXTAPS,
+              "upsample_stage_bwd_list_det: the partials buffer is smaller than wae_upsample_stage_bwd_list_det_floats says");
+  hipStream_t st = as_stream(stream);
+  const int nwg = ntiles < UPLB_MAXWG ? ntiles : UPLB_MAXWG;
+  const dim3 grid(nwg);
+#define WAE_UPLB(S_) hipLaunchKernelGGL((ups_stage_bwd_list_kernel<S_, true>), grid, dim3(256), 0, st, dout, in, w, din, parts, segs, nsegs, ntiles, in_pitch, out_pitch, C, s)
+  if (s == 4) WAE_UPLB(4);
+  else if (s == 5) WAE_UPLB(5);
+  else if (s == 8) WAE_UPLB(8);
+  else if (s == 16) WAE_UPLB(16);
+  else WAE_UPLB(0);
+#undef WAE_UPLB
+  hipLaunchKernelGGL(ups_list_w_finish_kernel, dim3(1), dim3(256), 0, st, (const float*)parts, nwg, 2 * s + 1, dw);
+  return wae_check_launch("upsample_stage_bwd_list_det");
 }
 
 // ---- Conv1d (+ReLU) (+residual) ------------------------------------------------------------------------------------------------

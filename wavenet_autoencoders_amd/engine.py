@@ -141,8 +141,8 @@ class WaeEngine:
         self.exp_avg = self.exp_avg_sq = self.shadow = self.opt_scratch = self.grad_norm = None
         self.opt_step = 0
         # EngineOptions.deterministic: the partials of the fixed-order sums, each grown to its largest use and reused on the one stream
-        # the mode runs on (det_buffer) -- "tn": wae_gemm_tn_tiles_det, "gproj": wae_gproj_bwd_det, "ups": wae_upsample_stage_bwd_det
-        # (fp32), "norm": wae_clip_adam_ema_det (fp64)
+        # the mode runs on (det_buffer) -- "tn": wae_gemm_tn_tiles_det, "gproj": wae_gproj_bwd_det, "ups": wae_upsample_stage_bwd_det,
+        # "ups_list": wae_upsample_stage_bwd_list_det (fp32), "norm": wae_clip_adam_ema_det (fp64)
         self._det_bufs: Dict[str, torch.Tensor] = {}
 
     def hold(self, slot: str, *tensors):
@@ -1315,7 +1315,7 @@ class WaeEngine:
         pad_rows low.
         ValueError before any launch and any RNG draw: an empty list, a malformed item, len(x_i) != prod(upsample_scales) * Tq_i,
         F_i < 1, B * Tmax > max_rows (default packing.FWD_LIST_MAX_ROWS; the caller splits longer lists).  NotImplementedError before
-        any launch: EngineOptions.deterministic, grad_sync, cin_pad > 0, an upsample_activation, a geometry without an upsampling
+        any launch: EngineOptions.deterministic (train_step_list_accum runs under it), grad_sync, cin_pad > 0, an upsample_activation, a geometry without an upsampling
         network or one the upsampling list kernels do not cover.  RuntimeError inside an open accumulation window."""
         return TR.train_step_list(self, items, (lr, betas, eps, weight_decay, clip_thresh, ema_decay), beta, grad_hook,
                                   (quantize_channels, log_scale_min), max_rows, grad_sync)
@@ -1369,3 +1369,35 @@ class WaeEngine:
         apply_step.  ce_scale: one more factor on the CE term.  Returns apply_step's dict."""
         return TR.train_step_accum(self, batches, (lr, betas, eps, weight_decay, clip_thresh, ema_decay), grad_hook,
                                    (quantize_channels, log_scale_min), grad_sync, ce_scale)
+
+    # ------------------------------------------------------------------ ragged micro-batches in accumulation windows
+    def accumulate_list(self, items, *, ce_weight: float = 1.0, vq_weight: float = 1.0, ce_count: Optional[float] = None,
+                        beta: float = 0.25, quantize_channels: int = 65536, log_scale_min: float = -7.0, max_rows: Optional[int] = None):
+        """One RAGGED micro-batch of an accumulation window: train_step_list's items, intake, plan and forward (the list front end in
+        front of the dense right-padded decoder) and its backward INTO the open window, as accumulate() does for a dense batch; the
+        first call opens the window.  Dense accumulate() calls and accumulate_list() calls may share one window; apply_step() closes
+        it, discard_step() drops it.  ce_weight, vq_weight, ce_count: as accumulate's; train.list_meta gives the micro-batch's entry
+        for distributed.accum_weights (n = sum_b (T_b - 1), e = Cc * sum Tq_b).  The list front end's backward adds its weight
+        gradients into the engine's accumulators, which the window's one finish reads.
+        Returns accumulate's dict (ce and, with an encoder, vq_loss and perp: device tensors, no host sync) plus rows and pad_rows.
+        Runs under EngineOptions.deterministic (the FIR tap gradient through wae_upsample_stage_bwd_list_det; every other sum of the
+        list forms has one owner or a fixed order).
+        Before any launch -- ValueError: train_step_list's item and plan refusals; a (B, Tmax) that takes another weight-gradient
+        launch than the window's earlier micro-batches (accumulate's rule).  NotImplementedError: train_step_list's geometry refusals;
+        the sliced and EMA quantisers (windows cover the plain kind).  A micro-batch that fails half-way takes the window with it
+        (discard_step)."""
+        return TR.accumulate_list(self, items, ce_weight, vq_weight, ce_count, beta, (quantize_channels, log_scale_min), max_rows)
+
+    def train_step_list_accum(self, groups, lr: float = 4e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                              clip_thresh: float = 100.0, ema_decay: float = 0.9999, beta: float = 0.25, grad_hook=None,
+                              quantize_channels: int = 65536, log_scale_min: float = -7.0, max_rows: Optional[int] = None, grad_sync=None):
+        """One optimisation step on a sequence of GROUPS, each a list of train_step_list's items: the weights of
+        distributed.accum_weights over train.list_meta of every group, an accumulate_list() per group, apply_step().  The step is
+        train_step_list on the concatenation of all groups, whose decoder would not fit in one batch: ce = sum nll / sum (T - 1),
+        vq_loss and perp those of all latents as one batch (score_list's totals).  max_rows caps each group.  Returns apply_step's
+        dict plus the summed rows and pad_rows.  Runs under EngineOptions.deterministic: the same weights, optimizer state, groups
+        and dropout seed give the same bits.
+        ValueError before any launch: no groups, an empty group, a malformed item in any group.  NotImplementedError: grad_sync
+        (ragged steps cover one GPU) and accumulate_list's refusals.  RuntimeError inside an open window."""
+        return TR.train_step_list_accum(self, groups, (lr, betas, eps, weight_decay, clip_thresh, ema_decay), beta, grad_hook,
+                                        (quantize_channels, log_scale_min), max_rows, grad_sync)

@@ -1,7 +1,7 @@
 """The training step's host path (vqwae_train.py:709-798): ONE pipeline of three phases -- step_open, step_run, step_apply -- behind
-train_step, train_step_list and accumulate / apply_step, with the criteria, the optimizer call and the list calls' item intake.
-Functions that take the engine as `eng` (as backward.py and decode.py; nothing here imports engine.py): WaeEngine keeps the public
-methods and their docstrings.  `opt`: (lr, betas, eps, weight_decay, clip_thresh, ema_decay); `mix`: (quantize_channels, log_scale_min)."""
+train_step, train_step_list and accumulate / accumulate_list / apply_step, with the criteria, the optimizer call and the list calls'
+item intake.  Functions that take the engine as `eng` (as backward.py and decode.py; nothing here imports engine.py): WaeEngine keeps
+the public methods and their docstrings.  `opt`: (lr, betas, eps, weight_decay, clip_thresh, ema_decay); `mix`: (quantize_channels, log_scale_min)."""
 from __future__ import annotations
 
 import torch
@@ -234,37 +234,51 @@ def train_step(eng, x, c, gid, lengths, opt, grad_hook, mix, grad_sync, ce_scale
     return _step_result(eng, out)
 
 
-def train_step_list(eng, items, opt, beta, grad_hook, mix, max_rows, grad_sync):
-    g, dev = eng.g, eng.device
-    eng._refuse_in_window("train_step_list")
-    if eng.opt.deterministic:
-        raise NotImplementedError("train_step_list with EngineOptions.deterministic: the list forms of the front end's backward "
-                                  "have no fixed-order form")
-    if grad_sync is not None:
-        raise NotImplementedError("train_step_list with grad_sync: ragged steps cover one GPU")
+def list_refusals(eng, who):
+    """The geometries the ragged step does not cover: NotImplementedError before any launch (train_step_list, accumulate_list)"""
+    g = eng.g
     if not g.upsample_scales or g.Cc <= 0:
-        raise NotImplementedError("train_step_list: this geometry has no upsampling network in front of the decoder; zero-padding "
+        raise NotImplementedError(f"{who}: this geometry has no upsampling network in front of the decoder; zero-padding "
                                   "changes nothing there: use train_step with lengths")
     if g.cin_pad > 0:
-        raise NotImplementedError(f"train_step_list with cin_pad = {g.cin_pad}: the ragged step covers cin_pad = 0")
+        raise NotImplementedError(f"{who} with cin_pad = {g.cin_pad}: the ragged step covers cin_pad = 0")
     if g.up_act != "none":
-        raise NotImplementedError(f"train_step_list with upsample_activation {g.up_act!r}")
+        raise NotImplementedError(f"{who} with upsample_activation {g.up_act!r}")
     if not P.upsample_list_supported(g):
-        raise NotImplementedError("train_step_list: the upsampling list kernels do not cover this geometry (packing.upsample_list_supported)")
+        raise NotImplementedError(f"{who}: the upsampling list kernels do not cover this geometry (packing.upsample_list_supported)")
+
+
+def list_intake(eng, who, items, max_rows):
+    """Item intake and launch plan of a ragged step, pure host work: every ValueError before any launch and any RNG draw
+    -> (items, packing.TrainListPlan, the c arrays)"""
     items = list(items)
-    Ts, Fs, cs, _ = list_items("train_step_list", items, g, "train", t_min=2)
-    tp = P.train_list_plan(g, Ts, Fs, max_rows)
-    B, Tmax = tp.B, tp.Tmax
-    # the dense decoder's inputs: right-padded ids (class 0 / 0.0 in the pad rows, which the masked loss never reads), lengths, speakers
-    xd = torch.zeros(B, Tmax, dtype=torch.float32 if g.scalar_input else torch.int32)
+    Ts, Fs, cs, _ = list_items(who, items, eng.g, "train", t_min=2)
+    return items, P.train_list_plan(eng.g, Ts, Fs, max_rows), cs
+
+
+def list_meta(g, tp):
+    """A ragged micro-batch's entry for distributed.accum_weights, from its plan: (B, Tmax, the items' samples as lengths, Cc * sum
+    Tq_i) -- n = sum_b (T_b - 1), e = the elements of the packed latents (engine.latent_elements assumes one frame count per batch);
+    e = 0 without an encoder."""
+    return tp.B, tp.Tmax, torch.as_tensor(tp.Ts, dtype=torch.int64), int(g.Cc) * int(tp.enc.Tq.sum()) if g.has_encoder else 0
+
+
+def list_dense_inputs(eng, items, tp):
+    """The dense decoder's inputs: right-padded ids (class 0 / 0.0 in the pad rows, which the masked loss never reads), lengths, speakers"""
+    g, dev, Ts = eng.g, eng.device, [int(t) for t in tp.Ts]
+    xd = torch.zeros(tp.B, tp.Tmax, dtype=torch.float32 if g.scalar_input else torch.int32)
     if any(torch.is_tensor(it["x"]) and it["x"].is_cuda for it in items):
         xd = xd.to(dev)
     for b, it in enumerate(items):
         xd[b, :Ts[b]] = torch.as_tensor(it["x"]).to(xd.device, xd.dtype)
-    x = xd.to(dev)
     lengths = torch.tensor(Ts, dtype=torch.int32)
     gid = torch.tensor([int(it["gid"]) for it in items], dtype=torch.int32, device=dev) if g.n_speakers else None
-    x, gid = step_open(eng, x, gid, opt[3])
+    return xd.to(dev), lengths, gid
+
+
+def list_forward(eng, tp, cs, x, gid, beta):
+    """-> fwd(targets, lengths, want_logits) for step_run: the train-mode forward of a ragged batch"""
+    g = eng.g
 
     def fwd(targets, lengths, want_logits):
         # the list front end wrote the conditioning operand of the (B, Tmax, train) workspace: the dense decoder_forward on it
@@ -274,27 +288,68 @@ def train_step_list(eng, items, opt, beta, grad_hook, mix, max_rows, grad_sync):
         if stats is not None:
             out.update(latents=sv.lat, quant=sv.quant, idx=sv.idx, vq_loss=stats[0], perp=stats[1])
         return out
+    return fwd
 
+
+def train_step_list(eng, items, opt, beta, grad_hook, mix, max_rows, grad_sync):
+    eng._refuse_in_window("train_step_list")
+    if eng.opt.deterministic:
+        raise NotImplementedError("train_step_list with EngineOptions.deterministic: the plain ragged step is not part of the mode; "
+                                  "train_step_list_accum (a window of one group or more) runs under it")
+    if grad_sync is not None:
+        raise NotImplementedError("train_step_list with grad_sync: ragged steps cover one GPU")
+    list_refusals(eng, "train_step_list")
+    items, tp, cs = list_intake(eng, "train_step_list", items, max_rows)
+    x, lengths, gid = list_dense_inputs(eng, items, tp)
+    x, gid = step_open(eng, x, gid, opt[3])
+    fwd = list_forward(eng, tp, cs, x, gid, beta)
     out, grads = step_run(eng, fwd, x, gid, lengths, mix, 1.0, 1.0, None, None, announce=False)      # (the list step keeps its head launches)
     step_apply(eng, grads, None, grad_hook, opt)
     return dict(_step_result(eng, out), rows=tp.rows, pad_rows=tp.pad_rows)
+
+
+def _refuse_other_kind(eng, who, B, T):
+    """A window holds micro-batches of one weight-gradient launch (backward.window_kind): ValueError before any launch"""
+    win, kind = eng.window, BW.window_kind(eng, B, T)
+    if win is not None and win.n and win.static != kind:
+        raise ValueError(f"{who}: a ({B}, {T}) micro-batch takes {'the static' if kind else 'another'} weight-gradient launch "
+                         "than the window's earlier ones, whose tiles the one finish reads: keep B <= 32 (and clips of one size "
+                         "class) within a window, or close it with apply_step() first")
 
 
 def accumulate(eng, x, c, gid, lengths, ce_weight, vq_weight, mix, ce_count):
     eng._refuse_accum_vq()
     if eng.flight.accum is not None:
         raise RuntimeError("accumulate() inside accumulate()")
-    g, (B, T), win = eng.g, x.shape, eng.window
-    kind = BW.window_kind(eng, B, T)
-    if win is not None and win.n and win.static != kind:
-        raise ValueError(f"accumulate: a ({B}, {T}) micro-batch takes {'the static' if kind else 'another'} weight-gradient launch "
-                         "than the window's earlier ones, whose tiles the one finish reads: keep B <= 32 (and clips of one size "
-                         "class) within a window, or close it with apply_step() first")
+    _refuse_other_kind(eng, "accumulate", *x.shape)
     x, gid = step_open(eng, x, gid, 0.0, window=True)
+    return _window_run(eng, dense_forward(eng, x, c, gid), x, gid, lengths, mix, ce_weight, vq_weight, ce_count)
+
+
+def accumulate_list(eng, items, ce_weight, vq_weight, ce_count, beta, mix, max_rows, intake=None):
+    """intake: list_intake's answer for these items where the caller has it (train_step_list_accum plans every group up front:
+    0.9 ms of host time per group at hps/vqwae.json, which a ragged step does not hide)"""
+    eng._refuse_accum_vq()
+    if eng.flight.accum is not None:
+        raise RuntimeError("accumulate_list() inside accumulate()")
+    list_refusals(eng, "accumulate_list")
+    items, tp, cs = intake if intake is not None else list_intake(eng, "accumulate_list", items, max_rows)
+    _refuse_other_kind(eng, "accumulate_list", tp.B, tp.Tmax)
+    x, lengths, gid = list_dense_inputs(eng, items, tp)
+    x, gid = step_open(eng, x, gid, 0.0, window=True)
+    fwd = list_forward(eng, tp, cs, x, gid, beta)
+    res = _window_run(eng, fwd, x, gid, lengths, mix, ce_weight, vq_weight, ce_count, announce=False)      # (its own head launches)
+    return dict(res, rows=tp.rows, pad_rows=tp.pad_rows)
+
+
+def _window_run(eng, fwd, x, gid, lengths, mix, ce_weight, vq_weight, ce_count, announce=True):
+    """Forward and backward of one micro-batch into the open window (step_open(..., window=True) ran), its numbers into the window's
+    sums -> dict(ce[, vq_loss, perp]) as device tensors"""
+    g = eng.g
     factor = None if ce_count is None else eng.grad_scale / float(ce_count)
     win = eng.flight.accum = eng.window
     try:
-        out, _ = step_run(eng, dense_forward(eng, x, c, gid), x, gid, lengths, mix, ce_weight, vq_weight, factor, None)
+        out, _ = step_run(eng, fwd, x, gid, lengths, mix, ce_weight, vq_weight, factor, None, announce=announce)
     except BaseException:
         # a refused input ended the micro-batch half-way: what it added cannot be told from the rest, so the window goes with it
         discard_step(eng)
@@ -363,3 +418,28 @@ def train_step_accum(eng, batches, opt, grad_hook, mix, grad_sync, ce_scale):
         eng.accumulate(x, c, gid, lengths, ce_weight=wc * float(ce_scale), vq_weight=wv, quantize_channels=mix[0],
                        log_scale_min=mix[1], ce_count=ce_count)
     return eng.apply_step(*opt, grad_hook=grad_hook, grad_sync=grad_sync)
+
+
+def train_step_list_accum(eng, groups, opt, beta, grad_hook, mix, max_rows, grad_sync):
+    from . import distributed as DS
+    groups = [list(items) for items in groups]
+    if not groups:
+        raise ValueError("train_step_list_accum: no groups")
+    if grad_sync is not None:
+        raise NotImplementedError("train_step_list_accum with grad_sync: ragged steps cover one GPU")
+    eng._refuse_in_window("train_step_list_accum")
+    eng._refuse_accum_vq()
+    list_refusals(eng, "train_step_list_accum")
+    # every group's intake in front of the first launch: a malformed item in a later group refuses the step, not half a window
+    intakes = []
+    for i, items in enumerate(groups):
+        try:
+            intakes.append(list_intake(eng, "train_step_list_accum", items, max_rows))
+        except ValueError as e:
+            raise ValueError(f"train_step_list_accum: group {i}: {e}") from None
+    weights, n_tot = DS.accum_weights([list_meta(eng.g, tp) for _, tp, _ in intakes])
+    rows = pad_rows = 0
+    for intake, (wc, wv) in zip(intakes, weights):
+        r = accumulate_list(eng, intake[0], wc, wv, n_tot, beta, mix, max_rows, intake=intake)
+        rows, pad_rows = rows + r["rows"], pad_rows + r["pad_rows"]
+    return dict(eng.apply_step(*opt, grad_hook=grad_hook), rows=rows, pad_rows=pad_rows)
